@@ -25,6 +25,8 @@ Workloads (--workload; "auto" picks by N):
 before anything touches a GPU); under torchrun (RANK / WORLD_SIZE set) it is one rank.
 
 Prints ONE JSON line (rank 0) with the driver's contract plus `roofline`, `cpu_baseline`, `parity_checked`.
+--dump-outputs DIR also writes what the last timed step computed to DIR/*.npy; the inputs depend only on the arguments, so
+two builds run with the same arguments can be compared output for output.
 Exit code != 0 if the GPU results of the last step differ from the oracle's on the same stream.
 """
 import argparse
@@ -43,6 +45,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 PKG = "distributed-multi-agent-slam-swarm-robotics-system_amd"
 
+DUMP_SEED = 0x5EED          # --dump-outputs: the same sample of cells / rows in every run
+DUMP_CELLS = 1 << 21        # grid cells dumped per grid-sized array (all of them when the grid has no more)
+DUMP_ROWS = 1 << 17         # rows dumped per list (closures, landmarks)
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_COPY_GBS = 6290.0       # achievable float4-copy rate, same guide
 N_CU = 256
@@ -85,7 +90,13 @@ def parse(argv=None):
     ap.add_argument("--spawn-selftest", action="store_true",
                     help="no GPU: the ranks only rendezvous (backend as given), all-reduce one number and rank 0 prints "
                          "{n_gpus: world}; used by the CPU test of the launcher")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's mapper, as a caller reads it back) "
+                         "to DIR/<name>.npy, float32/float64, under 64 MB in all: see dump_outputs()")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -437,6 +448,57 @@ def replayed_traffic(profile_dir, kernels):
     return (total, rnd) if found else None
 
 
+def _sample(n, k):
+    """Ascending indices of a fixed, seeded sample of k out of range(n); None when n <= k (keep everything)."""
+    return None if n <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, m, ekf, fused_counts=None):
+    """--dump-outputs: what the last timed step left in the mapper, read back as a caller would, one out_dir/<name>.npy each.
+    Grid-sized arrays (the int8 map view, the hit and miss counters): the cells of a fixed seeded sample (every cell of a grid
+    of at most DUMP_CELLS), plus exact row and column sums over the whole grid.  Lists longer than DUMP_ROWS: a fixed seeded
+    sample of their rows.  fused_counts: N > 1, the int32 [size, size, 2] (misses, hits) tensor the last fuse returned.
+    Returns the bytes written (< 64 MB by construction)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    grids = {"grid": m.grid_i8()}
+    if fused_counts is not None:
+        fz = fused_counts.cpu().numpy()
+        grids["hits"], grids["misses"] = fz[..., 1], fz[..., 0]
+    elif m.cfg.enable_counts:
+        grids["hits"], grids["misses"] = m.counts()
+    cells = _sample(m.size * m.size, DUMP_CELLS)
+    for name, a in grids.items():
+        flat = a.reshape(-1)
+        out[f"{name}_cells"] = (flat if cells is None else flat[cells]).astype(np.float32 if name == "grid" else np.float64)
+        out[f"{name}_row_sums"] = a.sum(axis=1, dtype=np.float64)
+        out[f"{name}_col_sums"] = a.sum(axis=0, dtype=np.float64)
+    sizes, clo, lms = [], [], []
+    for g in range(m.n_graphs):
+        sizes.append(m.slam_sizes(g))
+        ij, corr = m.closures(g)
+        clo.append(np.column_stack([np.full(len(ij), g), ij, corr]))
+        xy, ti = m.landmarks(g)
+        lms.append(np.column_stack([np.full(len(xy), g), xy, ti]))
+    out["slam_sizes"] = np.array(sizes, dtype=np.float64)                    # per pose graph: nodes, landmarks, closures
+    for name, parts in (("closures", clo), ("landmarks", lms)):             # graph, node i, node j, dx, dy / graph, x, y, type, node
+        rows = np.concatenate(parts).astype(np.float64)
+        keep = _sample(len(rows), DUMP_ROWS)
+        out[name] = rows if keep is None else rows[keep]
+    bots = range(1, m.max_agent + 1)
+    out["drift"] = np.array([m.drift(b) for b in bots], dtype=np.float64)
+    out["zones"] = np.array([(1.0, *z) if z else (0.0,) * 5 for z in (m.zone(b) for b in bots)], dtype=np.float64)   # valid, box
+    if ekf:
+        st = [m.ekf_state(b) for b in bots]
+        out["ekf_x"] = np.array([x for x, _ in st], dtype=np.float64)
+        out["ekf_P"] = np.array([P.reshape(-1) for _, P in st], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total < 64e6, f"--dump-outputs: {total} bytes"
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 # ------------------------------------------------------------------------------------------------------
 def selftest_rank(args):
     import torch
@@ -536,6 +598,9 @@ def run_rank(args):
     stages = m.stage_times(reset=True)
     cnt = m.counters()                       # counters of the last step (reset every step)
     st_ms = {k: (v[0] / max(v[1], 1)) for k, v in stages.items() if v[1]}
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before anything below writes the grid (the K3 fuse timings do)
+        dumped = dump_outputs(args.dump_outputs, m, bool(args.ekf), sm.last_fused if world > 1 and counts else None)
 
     # ---- parity of what was just timed (last step) against the oracle on the same stream -----------------------------
     parity, parity_note = None, None
@@ -716,6 +781,8 @@ def run_rank(args):
                 parity = False
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "bytes": dumped}
         print(json.dumps(out))
     if parity is False:
         rc = 1

@@ -218,6 +218,51 @@ def test_bench_refuses_a_gpus_flag_that_contradicts_the_launcher():
     assert out.returncode == 2 and "WORLD_SIZE=3" in out.stderr and out.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs on a stand-in for the mapper: float32 / float64 .npy files only, under 64 MB for the
+    largest lists the bench produces (grid-sized arrays and long lists sampled), the same sample in every call, and
+    a small grid kept whole, cell for cell."""
+    import types
+    import bench
+
+    class Stand:
+        def __init__(self, size, n_lm, n_graphs, bots):
+            self.size, self.n_graphs, self.max_agent, self.n_lm = size, n_graphs, bots, n_lm
+            self.cfg = types.SimpleNamespace(enable_counts=1)
+            cells = np.arange(size * size, dtype=np.int64).reshape(size, size)
+            self.g = ((cells % 3) - 1).astype(np.int8) * 100
+            self.h, self.m = (cells % 1013).astype(np.int32), (cells % 997).astype(np.int32)
+
+        def grid_i8(self): return self.g
+        def counts(self): return self.h, self.m
+        def slam_sizes(self, g): return (3 * self.n_lm, self.n_lm, self.n_lm // 4)
+        def closures(self, g): return (np.arange(self.n_lm // 2).reshape(-1, 2), np.full((self.n_lm // 4, 2), 0.5))
+        def landmarks(self, g): return (np.full((self.n_lm, 2), float(g)), np.arange(2 * self.n_lm).reshape(-1, 2))
+        def drift(self, b): return np.array([0.1 * b, -0.1 * b])
+        def zone(self, b): return None if b % 2 else (1.0, 2.0, 3.0, 4.0)
+        def ekf_state(self, b): return np.full(6, float(b)), np.eye(6) * b
+
+    big = Stand(4096, 1 << 19, 4, 64)                  # 2^21 landmarks: past DUMP_ROWS
+    n1 = bench.dump_outputs(str(tmp_path / "a"), big, ekf=True)
+    n2 = bench.dump_outputs(str(tmp_path / "b"), big, ekf=True)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and n1 == n2
+    assert n1 < 64e6 and sum(os.path.getsize(tmp_path / "a" / f) for f in names) < 64e6
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, b), f"{f}: a different sample in the second call"
+    assert np.load(tmp_path / "a" / "grid_cells.npy").shape == (bench.DUMP_CELLS,)
+    assert np.load(tmp_path / "a" / "landmarks.npy").shape == (bench.DUMP_ROWS, 5)
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_row_sums.npy"), big.h.sum(axis=1, dtype=np.float64))
+
+    small = Stand(64, 12, 1, 2)
+    bench.dump_outputs(str(tmp_path / "s"), small, ekf=False)
+    assert np.array_equal(np.load(tmp_path / "s" / "grid_cells.npy"), small.g.reshape(-1).astype(np.float32))
+    assert np.load(tmp_path / "s" / "landmarks.npy").shape == (12, 5)
+    assert not os.path.exists(tmp_path / "s" / "ekf_x.npy")
+
+
 # ---- round 3: the sparse (dirty-block) fuse -- the protocol of dist.sparse_fuse with a numpy adapter in the kernels' place ----
 BW, BH = 16, 4        # QS_DIRTY_BLOCK_W / QS_DIRTY_BLOCK_H (checked against the header in test_abi_cpu.py)
 

@@ -1335,3 +1335,30 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(extra):
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["parity_checked"] is True
     assert rec["counters_per_step"]["closures"] > 100
+
+
+def test_bench_dump_outputs_same_in_every_run(tmp_path):
+    """bench.py --dump-outputs: the last timed step's results, read back after the steps --steps asked for; every step starts
+    from a fresh session, so a run of 3 steps (parity checked) and a run of 1 step dump the same arrays, and the dumped
+    closure and landmark lists agree with the step's counters."""
+    import json
+    import subprocess
+    import sys
+    recs = []
+    for name, extra in (("a", ["--steps", "3", "--warmup", "1"]), ("b", ["--steps", "1", "--warmup", "0", "--no-cpu-baseline"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "65536", "--no-micro",
+               "--dump-outputs", str(tmp_path / name)] + extra
+        out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    assert recs[0]["steps"] == 3 and recs[1]["steps"] == 1 and recs[0]["parity_checked"] is True
+    assert all(r["ms_per_step"] > 0 and r["outputs_dumped"]["bytes"] < 64e6 for r in recs)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "grid_cells.npy" in names and "ekf_x.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    cnt = recs[0]["counters_per_step"]
+    sizes = np.load(tmp_path / "a" / "slam_sizes.npy")
+    assert sizes[:, 2].sum() == cnt["closures"] > 0 and sizes[:, 1].sum() == cnt["landmarks"]
+    assert len(np.load(tmp_path / "a" / "closures.npy")) == cnt["closures"]

@@ -168,6 +168,7 @@ static int reset_state(qs_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->d_stamps, 0, c->cells * sizeof(unsigned int), c->stream));
     if (c->d_counts) HIPCHK(c, hipMemsetAsync(c->d_counts, 0, c->cells * sizeof(unsigned long long), c->stream));
     if (c->d_counts_fused) HIPCHK(c, hipMemsetAsync(c->d_counts_fused, 0, c->cells * sizeof(unsigned long long), c->stream));
+    c->counts_view_fused = false;             // the views read the local counters until the session's first fuse
     c->dirty_since_fuse = false;
     if (c->d_dirty) HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, c->dirty_words * sizeof(unsigned int), c->stream));
     if (c->d_counts_sent) HIPCHK(c, hipMemsetAsync(c->d_counts_sent, 0, c->cells * sizeof(unsigned long long), c->stream));
@@ -1158,6 +1159,7 @@ extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
     if (!enable) {
         hipFree(c->d_dirty); c->d_dirty = nullptr; c->geom.dirty = nullptr; c->geom.dirty_pitch = 0;
         c->sf_state = 0;
+        c->counts_view_fused = false;         // the fused counters stop following the ranks: the views read the own ones
         return QS_OK;
     }
     if (c->d_dirty) return QS_OK;
@@ -1207,6 +1209,10 @@ extern "C" int qs_sparse_fuse_begin(qs_ctx *c, int32_t world, int32_t rank, void
     if (!c->d_dirty) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_begin: dirty tracking is off (qs_dirty_tracking)");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
+    // a fuse begun here that never reached apply: its blocks did not travel, so they go into this one (before a change of
+    // world reallocates the bitmaps).  Nothing else was committed: the counter deltas are taken from `sent`, which only
+    // apply advances.
+    if (c->sf_state != 0) HIPCHK(c, qs_launch_sf_restore(c));
     if (world != c->sf_world) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, dev_realloc(&c->d_sf_bitmaps, (size_t)world * c->dirty_words));

@@ -277,6 +277,7 @@ hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long
 size_t qs_sf_block_bytes(const qs_ctx *c);
 hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells);
 hipError_t qs_launch_sf_lists(qs_ctx *c);
+hipError_t qs_launch_sf_restore(qs_ctx *c);
 hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst);
 hipError_t qs_launch_sf_apply(qs_ctx *c);
 hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out);

@@ -8,7 +8,10 @@
 //   lists   every rank's bitmap (all-gathered by the caller) -> ascending block ids + count      qs_sf_lists_kernel
 //   pack    this rank's blocks: 64 stamps + 64 counter deltas since its previous fuse, 768 B     qs_sf_pack_kernel
 //   (the caller sends the packed segment to every peer: point-to-point, all xGMI links at once)
-//   apply   every rank's segment folded in: stamps atomicMax, counter deltas atomicAdd            qs_sf_apply_kernel
+//   apply   every rank's segment folded in: stamps atomicMax, counter deltas atomicAdd; the own     qs_sf_apply_kernel
+//           deltas are counted as sent
+// Only apply commits anything.  A fuse abandoned before it (the exchange failed) is carried by the next one: begin ORs
+// the bitmap it saved back into the live one (qs_sf_restore_kernel) and the deltas are still there to be taken.
 // All three are HBM-streaming over the dirty blocks only: a block is 4 grid rows of 64 B (stamps) / 128 B (counters) and
 // one 256 B / 512 B row of the payload per wave-instruction.
 #include "qs_internal.h"
@@ -39,6 +42,22 @@ hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells)
     const int n = (by_hi - by_lo) * c->geom.dirty_pitch;
     hipLaunchKernelGGL(qs_sf_mark_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_dirty, c->geom.dirty_pitch,
                        c->blocks_x, by_lo, by_hi);
+    return hipGetLastError();
+}
+
+// ---- restore: the saved row of a fuse that never reached apply back into the live bitmap -----------------------------
+__global__ void qs_sf_restore_kernel(unsigned int *__restrict__ dirty, const unsigned int *__restrict__ saved, size_t words)
+{
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= words) return;
+    const unsigned int m = saved[w];
+    if (m) dirty[w] |= m;                                    // stream-ordered: nothing else writes the bitmap meanwhile
+}
+hipError_t qs_launch_sf_restore(qs_ctx *c)
+{
+    if (!c->d_dirty || !c->d_sf_bitmaps || c->sf_rank >= c->sf_world) return hipSuccess;
+    hipLaunchKernelGGL(qs_sf_restore_kernel, dim3((unsigned int)((c->dirty_words + 255) / 256)), dim3(256), 0, c->stream, c->d_dirty,
+                       c->d_sf_bitmaps + (size_t)c->sf_rank * c->dirty_words, c->dirty_words);
     return hipGetLastError();
 }
 
@@ -116,7 +135,7 @@ template <bool COUNTS>
 __global__ void __launch_bounds__(256)
 qs_sf_pack_kernel(const unsigned int *__restrict__ list, unsigned int n_blocks, int pitch, int size,
                   const unsigned int *__restrict__ stamps, const unsigned long long *__restrict__ counts,
-                  unsigned long long *__restrict__ sent, unsigned char *__restrict__ dst)
+                  const unsigned long long *__restrict__ sent, unsigned char *__restrict__ dst)
 {
     const int lane = threadIdx.x & (QS_WAVE - 1);
     const unsigned int wave = blockIdx.x * (256 / QS_WAVE) + (threadIdx.x >> 6), n_waves = gridDim.x * (256 / QS_WAVE);
@@ -133,8 +152,7 @@ qs_sf_pack_kernel(const unsigned int *__restrict__ list, unsigned int n_blocks, 
                 // hi32 hits, lo32 misses: the halves are independent counters, so the delta is taken per half
                 d = ((unsigned long long)((unsigned int)(cur >> 32) - (unsigned int)(old >> 32)) << 32) |
                     (unsigned long long)((unsigned int)cur - (unsigned int)old);
-                if (d) sent[cell] = cur;
-            }
+            }                                                  // (`sent` advances in apply, once the segment has travelled)
             ((unsigned long long *)(blk + SF_CELLS * 4))[lane] = d;
         }
     }
@@ -160,7 +178,7 @@ template <bool COUNTS>
 __global__ void __launch_bounds__(256)
 qs_sf_apply_kernel(SfPlan pl, const unsigned int *__restrict__ lists, size_t list_stride, int pitch, int size,
                    const unsigned char *__restrict__ payload, unsigned int *__restrict__ stamps,
-                   unsigned long long *__restrict__ fused)
+                   unsigned long long *__restrict__ fused, unsigned long long *__restrict__ sent)
 {
     const int lane = threadIdx.x & (QS_WAVE - 1);
     const unsigned int wave = blockIdx.x * (256 / QS_WAVE) + (threadIdx.x >> 6), n_waves = gridDim.x * (256 / QS_WAVE);
@@ -179,7 +197,15 @@ qs_sf_apply_kernel(SfPlan pl, const unsigned int *__restrict__ lists, size_t lis
         }
         if (COUNTS) {
             const unsigned long long d = ((const unsigned long long *)(blk + SF_CELLS * 4))[lane];
-            if (in && d) atomicAdd(&fused[cell], d);
+            if (in && d) {
+                atomicAdd(&fused[cell], d);
+                if (s == pl.rank) {                                          // own block: a cell occurs once in the own list
+                    // per half, with wrap-around, as pack took the delta: one 64-bit add would carry misses into hits
+                    const unsigned long long old = sent[cell];
+                    sent[cell] = ((unsigned long long)((unsigned int)(old >> 32) + (unsigned int)(d >> 32)) << 32) |
+                                 (unsigned long long)((unsigned int)old + (unsigned int)d);
+                }
+            }
         }
     }
 }
@@ -194,9 +220,9 @@ hipError_t qs_launch_sf_apply(qs_ctx *c)
     const unsigned int blocks = (run + 3) / 4 < 8192 ? (run + 3) / 4 : 8192;
     if (c->d_counts)
         hipLaunchKernelGGL(qs_sf_apply_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused);
+                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
     else
         hipLaunchKernelGGL(qs_sf_apply_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused);
+                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
     return hipGetLastError();
 }

@@ -83,8 +83,10 @@ const char *qs_last_error(const qs_ctx *ctx);   /* ctx may be NULL: last create 
 /* run on the caller's hipStream_t (e.g. torch's current stream); NULL = own stream */
 int qs_set_stream(qs_ctx *ctx, void *hip_stream);
 int qs_sync(qs_ctx *ctx);
-/* new session: grid -> UNKNOWN, pose graphs, drift, zones, EKF cleared (main() start, :755-785).
- * Enqueued on the context's stream like an ingest; does not wait for the GPU. */
+/* new session: grid -> UNKNOWN, pose graphs, drift, zones, EKF cleared (main() start, :755-785).  The fuse state goes
+ * too: counters, fused counters and dirty bitmaps zeroed, a sparse fuse in flight dropped, and the counts view back on the
+ * local counters until the session's first fuse -- a reset context shows what a new one would.  Dirty tracking and the
+ * chain form (qs_set_chain_form) are kept.  Enqueued on the context's stream like an ingest; does not wait for the GPU. */
 int qs_reset(qs_ctx *ctx);
 /* per-bot x offset; bot 2 defaults to cfg.separation (:851-852) */
 int qs_set_bot_offset(qs_ctx *ctx, int32_t bot, double off_x);
@@ -166,7 +168,8 @@ int qs_fuse_buffers_range(qs_ctx *dst, const void *const *stamps_dev, const void
 /* ---- sharded streams (one context per GPU, the shared grid of dual_bot_mapper.py:785 kept in N pieces) -------------
  * The local counters hold this context's own writes only and are never the target of a collective: qs_fused_counts
  * copies them into a second buffer (on the context's stream) and returns it; the caller sums THAT over the ranks, as
- * often as it likes.  qs_counts_source(ctx, 1) makes qs_grid_counts / qs_grid_logodds read the fused snapshot. */
+ * often as it likes.  qs_counts_source(ctx, 1) makes qs_grid_counts / qs_grid_logodds read the fused snapshot, until
+ * qs_counts_source(ctx, 0), qs_reset or qs_dirty_tracking(ctx, 0). */
 int qs_fused_counts(qs_ctx *ctx, void **fused_dev, size_t *bytes);
 int qs_counts_source(qs_ctx *ctx, int32_t fused);
 /* Stamp epochs: ordinals are 30 bits, so a batch that would pass 2^28 arrival indices first rebases the grid (every
@@ -190,7 +193,13 @@ int qs_mark_fused(qs_ctx *ctx);
  *                          (which qs_grid_counts / qs_grid_logodds then read); qs_mark_fused implied.
  * Result = the dense fuse (MAX all-reduce of the stamps, SUM of the counters) bit for bit, as long as every rank's grid
  * was equal after the previous fuse (true from qs_reset on).  In this mode the fused counters accumulate deltas: do not
- * mix with qs_fused_counts (refused while tracking is on).  world <= QS_SPARSE_MAX_WORLD. */
+ * mix with qs_fused_counts (refused while tracking is on).  world <= QS_SPARSE_MAX_WORLD.
+ * Only apply commits: a fuse that NO rank applied (the exchange failed after begin or plan) is carried in full by the next
+ * qs_sparse_fuse_begin, which puts the blocks it had taken back into the live bitmap; the counter deltas are still there.
+ * A fuse that some ranks applied and others did not cannot be repaired -- sending it again would add the appliers' deltas
+ * twice --: the ranks must qs_reset.  qs_dirty_tracking(ctx, 0) returns the counts view to the local counters;
+ * qs_dirty_tracking(ctx, 1) is refused while the grid has writes no fuse has carried (enable it after qs_create /
+ * qs_reset / a fuse). */
 #define QS_DIRTY_BLOCK_W 16
 #define QS_DIRTY_BLOCK_H 4
 #define QS_SPARSE_MAX_WORLD 64

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Fuzz of the HIP path against the CPU restatement (python tests/fuzz_gpu.py SEED CASES, on the GPU box;
 uses the test-only checker, so it lives under tests/): random grid geometries, separations,
-batch splits and adversarial / session streams; compares grid, counters, closures, drift, zone."""
+batch splits and adversarial / session streams; compares grid, counters, closures, drift, zone.
+Third section: seeded walks over the map's life cycle (ingest, sparse fuse, fuse abandoned after begin / plan, reset,
+read) on 2-3 contexts playing ranks, test_gpu_lifecycle.walk, CASES // 3 of them."""
 import importlib, os, sys
 import numpy as np
+import torch  # before the HIP library (the third section aliases the contexts' buffers with torch)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 PKG = "distributed-multi-agent-slam-swarm-robotics-system_amd"
 pkg = importlib.import_module(PKG)
 replay = importlib.import_module(PKG + ".replay")
@@ -86,4 +90,19 @@ for it in range(n_iter):
         bad2 += 1
         print("MISMATCH(slam)", dict(it=it, nb=nb, bpg=bpg, radius=radius, mb=mb, corr=corr, n=n, cuts=cuts, form=form))
 print("slam fuzz done:", n_iter, "cases,", bad2, "mismatches")
-sys.exit(1 if bad or bad2 else 0)
+
+# ---- life cycle: reset / sparse fuse / abandoned fuse / tracking, checked after every step ---------------------------
+import test_gpu_lifecycle as lc
+dist = importlib.import_module(PKG + ".dist")
+bad3 = 0
+n_walks = max(1, n_iter // 3)
+for it in range(n_walks):
+    world = int(rng.choice([2, 3]))
+    seed = int(rng.integers(1 << 30))
+    try:
+        lc.walk(pkg, dist, replay, world, seed, steps=30)
+    except AssertionError as e:
+        bad3 += 1
+        print("MISMATCH(lifecycle)", dict(it=it, world=world, seed=seed), str(e).splitlines()[0])
+print("lifecycle fuzz done:", n_walks, "walks,", bad3, "mismatches")
+sys.exit(1 if bad or bad2 or bad3 else 0)

@@ -282,6 +282,7 @@ class NumpySparseAdapter:
         self.sent = np.zeros_like(self.counts)
         self.fused = np.zeros_like(self.counts)
         self.dirty = np.zeros((self.by, self.pitch), np.uint32)
+        self.bm = None                                             # the bitmaps of a fuse begun and not yet applied
 
     def write(self, new_stamps, new_counts):
         """The oracle's state after a batch becomes the context's: blocks where a stamp or a counter changed are marked."""
@@ -297,6 +298,8 @@ class NumpySparseAdapter:
         return slice(y0, y0 + BH), slice(x0, min(x0 + BW, self.size)), min(BW, self.size - x0)
 
     def begin(self, world, rank):
+        if self.bm is not None:                                     # a fuse that never reached apply: its blocks go into this one
+            self.dirty |= self.bm[self.rank].numpy().view(np.uint32).reshape(self.dirty.shape)
         self.world, self.rank = world, rank
         self.bm = torch.zeros((world, self.by * self.pitch), dtype=torch.int32)
         self.bm[rank] = torch.from_numpy(self.dirty.reshape(-1).view(np.int32).copy())
@@ -315,7 +318,6 @@ class NumpySparseAdapter:
             ys, xs, w = self._cells(bid)
             st = np.zeros((BH, BW), np.int32); st[:, :w] = self.stamps[ys, xs]
             d = np.zeros((BH, BW, 2), np.int32); d[:, :w] = self.counts[ys, xs] - self.sent[ys, xs]
-            self.sent[ys, xs] = self.counts[ys, xs]
             o = int(off[self.rank]) + k * bb
             seg[o:o + 256] = st.reshape(-1).view(np.uint8)
             seg[o + 256:o + 768] = d.reshape(-1).view(np.uint8)
@@ -332,7 +334,10 @@ class NumpySparseAdapter:
                 d = seg[o + 256:o + 768].view(np.int32).reshape(BH, BW, 2)[:, :w]
                 if s != self.rank:
                     self.stamps[ys, xs] = np.maximum(self.stamps[ys, xs], st)
+                else:
+                    self.sent[ys, xs] += d                          # only apply commits what was sent
                 self.fused[ys, xs] += d
+        self.bm = None
 
 
 def _worker_sparse(rank, world, port, q, size, pitch_m):

@@ -149,16 +149,6 @@ qs_slam_index_kernel(size_t n, QsBatch b, QsSlamBatch sb, const QsGraphDev *__re
     }
 }
 
-#ifdef QS_CHAIN_PROF3
-#define CH_TRACE_WINDOWS 16384
-__device__ unsigned long long g_chain_trace[CH_TRACE_WINDOWS * 16];
-extern "C" int qs_debug_chain_trace(unsigned long long *out, size_t n_windows)
-{
-    if (n_windows > CH_TRACE_WINDOWS) n_windows = CH_TRACE_WINDOWS;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chain_trace), n_windows * 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
-}
-#endif
-
 // ---- the chain: one workgroup (CH_WAVES waves) per pose graph ------------------------------------
 // The graph's landmark events are walked in windows of < MIN_POSES_BETWEEN nodes: a query never sees a
 // landmark of its own window (:300), and an agent closes at most once per window (:304), so the
@@ -513,19 +503,7 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
 #define CH_R1 (ring == 0 ? 2 : ring - 1)       // slot of window V - 1
 #define CH_R2 (ring == 2 ? 0 : ring + 1)       // slot of window V - 2
 // what every role does at the end of a phase
-#ifdef QS_CHAIN_PROF3
-// per-window busy time of every role of graph 0 (first CH_TRACE_WINDOWS phases): [phase][wave] cycles from the barrier to the
-// role's arrival at the next one; tools/chain_trace.py reads it through qs_debug_chain_trace
-#define CH_P3_DECL unsigned long long p3_busy = 0, p3_t = __builtin_amdgcn_s_memtime(); unsigned int p3_w = 0
-#define CH_PHASE_END(active_, k_)  { const unsigned long long p3_d = __builtin_amdgcn_s_memtime() - p3_t; p3_busy += p3_d; \
-    if (g == 0 && lane == 0 && p3_w < CH_TRACE_WINDOWS) g_chain_trace[p3_w * 16 + wave] = p3_d; p3_w++; } \
-    lds_barrier(); p3_t = __builtin_amdgcn_s_memtime(); e += (k_); have_prev = (active_); if (active_) { par ^= 1; ring = ring == 2 ? 0 : ring + 1; }
-#define CH_P3_REPORT(slot_) if (lane == 0) atomicAdd(&counters[slot_], p3_busy)
-#else
-#define CH_P3_DECL
 #define CH_PHASE_END(active_, k_)  lds_barrier(); e += (k_); have_prev = (active_); if (active_) { par ^= 1; ring = ring == 2 ? 0 : ring + 1; }
-#define CH_P3_REPORT(slot_)
-#endif
 
     if (wave == 0) {
         // =================================== wave 0: commit + prepare ===================================
@@ -541,7 +519,6 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
         int a = 0;
         double x = 0, y = 0;
         bool inw = false;
-        CH_P3_DECL;
         for (;;) {
             const bool active = e < e1;
             if (!active && !have_prev) break;
@@ -592,10 +569,7 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
             atomicAdd(&counters[QS_CNT_CLOSURES], (unsigned long long)(n_cls - n_cls0));
             if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAINW_HIT - QS_FLAG_PILE, (unsigned int)(n_cls - n_cls0));
             atomicAdd(&counters[QS_CNT_SLAM_WINDOWS], st_windows);
-#if !defined(QS_CHAIN_PROF) && !defined(QS_CHAIN_PROF2) && !defined(QS_CHAIN_PROF3)
             atomicAdd(&counters[QS_CNT_SLAM_CYC_A], st_a); atomicAdd(&counters[QS_CNT_SLAM_CYC_B], st_b);
-#endif
-            CH_P3_REPORT(QS_CNT_SLAM_CYC_A);
             atomicAdd(&counters[QS_CNT_SLAM_CYCLES], __builtin_amdgcn_s_memtime() - t0_cyc);
             atomicAdd(&counters[QS_CNT_SLAM_REALTIME], __builtin_amdgcn_s_memrealtime() - t0_real);
             Gp->n_nodes = Gp->n_nodes + sb.acc_total[g];
@@ -604,7 +578,6 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
         for (int t = lane; t < nb; t += QS_WAVE) sb.acl_cnt[bot0 + t] = s_acnt[t] - sb.agent_ev[bot0 + t];
     } else if (wave == CH_FETCH) {
         // =================================== wave CH_FETCH: event fetch ===================================
-        CH_P3_DECL;
         for (;;) {
             const bool active = e < e1;
             if (!active && !have_prev) break;
@@ -622,14 +595,12 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
             }
             CH_PHASE_END(active, k);
         }
-        CH_P3_REPORT(QS_CNT_SLAM_CYC_B);
     } else if (wave == CH_INS) {
         // =================================== wave CH_INS: index insert ===================================
         const QsGraphDev G = *Gp;
         long long n_lms = G.n_lms, n_misc = G.n_misc;
         unsigned int pool = G.nodes_used;
         bool pile = false;
-        CH_P3_DECL;
         for (;;) {
             const bool active = e < e1;
             if (!active && !have_prev) break;
@@ -646,7 +617,6 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
             }
             CH_PHASE_END(active, k);
         }
-        CH_P3_REPORT(QS_CNT_SLAM_CYC_C);
         if (lane == 0) {
             atomicAdd(&counters[QS_CNT_LANDMARKS], (unsigned long long)(n_lms - G.n_lms));
             Gp->n_lms = n_lms;
@@ -678,26 +648,9 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
         const int last_lane = min(nbk * QS_NODE_CAP + QS_NODE_CAP - 1, 63);
         const int nb_dx = (nbk % 3) - 1, nb_dy = (nbk / 3) - 1;        // the lane's neighbour of the 3x3
         unsigned long long st_misc = 0;            // side-list scans (rare path; the tests read it)
-#ifdef QS_CHAIN_STATS
-        unsigned long long st_rounds = 0, st_iters = 0;
-#define CH_STAT(x) (x)++
-#else
-#define CH_STAT(x) do { } while (0)
-#endif
-#ifdef QS_CHAIN_PROF
-        unsigned long long pq_a = 0, pq_b = 0, pq_c = 0;
-#endif
-        CH_P3_DECL;
-#ifdef QS_CHAIN_PROF2
-        unsigned long long p2_head = 0, p2_setup = 0, p2_scan = 0, p2_post = 0, p2_pub = 0, p2_bar = 0, p2_t4 = __builtin_amdgcn_s_memtime();
-#endif
         for (;;) {
             const bool active = e < e1;
             if (!active && !have_prev) break;
-#ifdef QS_CHAIN_PROF2
-            const unsigned long long p2_t0 = __builtin_amdgcn_s_memtime();
-            p2_bar += p2_t0 - p2_t4;
-#endif
             int ev_own = 0;
             if (!ONE) {
                 ev_own = (active && lane < 32) ? n_own[par][lane] : 0;
@@ -729,14 +682,7 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
             double nw_dx = st_dx, nw_dy = st_dy;
             long long nw_last = st_last;
             if (!ONE && ownlane) { s_dx[par ^ 1][W.v_a] = st_dx; s_dy[par ^ 1][W.v_a] = st_dy; s_lastc[par ^ 1][W.v_a] = st_last; }
-#ifdef QS_CHAIN_PROF2
-            const unsigned long long p2_t1 = __builtin_amdgcn_s_memtime();
-            p2_head += p2_t1 - p2_t0;
-#endif
             for (unsigned long long qrem = __ballot(may_close); qrem; qrem &= qrem - 1) {
-#if defined(QS_CHAIN_PROF) || defined(QS_CHAIN_PROF2)
-                const unsigned long long tq0 = __builtin_amdgcn_s_memtime();
-#endif
                 const int src = __ffsll((long long)qrem) - 1;
                 const int qa = __builtin_amdgcn_readlane(W.v_a, src);
                 const long long qidx = rl64(W.v_idx, src);
@@ -752,12 +698,8 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
                 if (indexed && lane < 9 * QS_NODE_CAP) node = 1u + (unsigned int)bucket_key(qtype, qcx + nb_dx, qcy + nb_dy, bg);   // the entry's own first node
                 long long best = LL_MAX, gbest = LL_MAX;
                 double bx = 0, by = 0;
-                CH_STAT(st_rounds);
                 long long l_idx = LL_MAX;
                 double l_x = 0, l_y = 0;
-#if defined(QS_CHAIN_PROF) || defined(QS_CHAIN_PROF2)
-                const unsigned long long tq1 = __builtin_amdgcn_s_memtime();
-#endif
                 int rounds = 0;
                 bool dense = false;
                 for (bool first_scan = true;; first_scan = false) {
@@ -781,7 +723,6 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
                     }
                     if (!anyn) break;
                     if (DENSE && rounds++ == dense_after) { dense = true; break; }
-                    CH_STAT(st_iters);
                     const bool inlim = node != 0 && id <= limit;      // empty slots read as a huge index
                     bool newhit = false;
                     if (inlim && best == LL_MAX) {
@@ -802,9 +743,6 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
                     const bool b_full = ((limm >> last_lane) & 1ull) != 0;
                     if (node) node = (b_hit || !b_full || nxt == 0 || lastid >= gbest) ? 0u : nxt;
                 }
-#if defined(QS_CHAIN_PROF) || defined(QS_CHAIN_PROF2)
-                const unsigned long long tq2 = __builtin_amdgcn_s_memtime();
-#endif
                 double wx = 0, wy = 0;
                 if (DENSE && dense) {
                     // self.landmarks in insertion order (:294): the first entry of the query's type within the radius among
@@ -877,16 +815,7 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
                         if (ownlane && W.v_a == qa) { nw_dx = ndx; nw_dy = ndy; nw_last = qidx; }
                     }
                 } else st_nomatch++;
-#ifdef QS_CHAIN_PROF
-                { const unsigned long long tq3 = __builtin_amdgcn_s_memtime(); pq_a += tq1 - tq0; pq_b += tq2 - tq1; pq_c += tq3 - tq2; }
-#endif
-#ifdef QS_CHAIN_PROF2
-                { const unsigned long long tq3 = __builtin_amdgcn_s_memtime(); p2_setup += tq1 - tq0; p2_scan += tq2 - tq1; p2_post += tq3 - tq2; }
-#endif
             }
-#ifdef QS_CHAIN_PROF2
-            const unsigned long long p2_t2 = __builtin_amdgcn_s_memtime();
-#endif
             if (ONE && active && lane == 0) { s_dx[par ^ 1][wave - 1] = c_dx; s_dy[par ^ 1][wave - 1] = c_dy; s_lastc[par ^ 1][wave - 1] = c_last; }
             // the window's landmarks get their final pose from their agent's owner: the drift at window start,
             // or -- later events of an agent that closed in this window -- the drift after the closure (:855-857)
@@ -900,22 +829,8 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
                 i_x[ring][lane] = raw_pose ? W.px : W.px + ddx;
                 i_y[ring][lane] = raw_pose ? W.py : W.py + ddy;
             }
-#ifdef QS_CHAIN_PROF2
-            p2_t4 = __builtin_amdgcn_s_memtime();
-            p2_pub += p2_t4 - p2_t2;
-#endif
             CH_PHASE_END(active, W.k);
         }
-#ifdef QS_CHAIN_PROF2
-        if (lane == 0 && wave == 1) {
-            atomicAdd(&counters[QS_CNT_SLAM_CYC_A], p2_head); atomicAdd(&counters[QS_CNT_SLAM_CYC_B], p2_setup);
-            atomicAdd(&counters[QS_CNT_SLAM_CYC_C], p2_scan); atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], p2_post);
-            atomicAdd(&counters[QS_CNT_EKF_WRAP_CLAMP], p2_pub); atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], p2_bar);
-        }
-#endif
-#ifdef QS_CHAIN_PROF3
-        if (lane == 0) atomicAdd(&counters[wave == 1 ? QS_CNT_SLAM_MISC_ITERS : QS_CNT_EKF_WRAP_CLAMP], p3_busy);
-#endif
         if (ONE) {
             if (lane == 0) { drift[2 * (bot0 + wave - 1)] = c_dx; drift[2 * (bot0 + wave - 1) + 1] = c_dy; last_closure[bot0 + wave - 1] = c_last; }
         } else if (own < nb) {                                // the states after the last window are in the buffer `par` names now
@@ -925,16 +840,7 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
         }
         if (lane == 0) {
             if (st_nomatch && pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAINW_MISS - QS_FLAG_PILE, st_nomatch);
-#if defined(QS_CHAIN_STATS) && !defined(QS_CHAIN_PROF2)
-            atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], st_rounds);
-            atomicAdd(&counters[QS_CNT_SLAM_NODE_ITERS], st_iters);
-#endif
-#if !defined(QS_CHAIN_PROF2) && !defined(QS_CHAIN_PROF3)
             if (st_misc) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], st_misc);
-#endif
-#ifdef QS_CHAIN_PROF
-            atomicAdd(&counters[QS_CNT_SLAM_CYC_A], pq_a); atomicAdd(&counters[QS_CNT_SLAM_CYC_B], pq_b); atomicAdd(&counters[QS_CNT_SLAM_CYC_C], pq_c);
-#endif
         }
     }
 #undef CH_PHASE_END
@@ -1006,14 +912,8 @@ __device__ inline long long free_query(const QsGraphDev *Gp, QsNodeG g_nodes, Qs
     const int dense_after = (int)((nl >> 9) > 8 ? ((nl >> 9) < 100000 ? (nl >> 9) : 100000) : 8);
     int rounds = 0;
     bool dense = false;
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 5
-    const unsigned long long tl_ = __builtin_amdgcn_s_memtime();
-#endif
     while (__ballot(node != 0)) {
         if (DENSE && rounds++ == dense_after) { dense = true; break; }
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 2
-        st_misc++;                                                       // (profile build: node rounds)
-#endif
         FqRows r;
         if (use_pre) { r = pre; use_pre = false; }                        // (by value and a flag: a pointer would put the rows in scratch)
         else fq_load(g_nodes, g_next, node, lane, r);
@@ -1037,9 +937,6 @@ __device__ inline long long free_query(const QsGraphDev *Gp, QsNodeG g_nodes, Qs
         const bool b_full = ((limm >> last_lane) & 1ull) != 0;
         if (node) node = (b_hit || !b_full || nxt == 0 || lastid >= gbest) ? 0u : nxt;
     }
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 5
-    st_misc += __builtin_amdgcn_s_memtime() - tl_;                       // (profile build 5: the node rounds)
-#endif
     wx = 0; wy = 0;
     if (DENSE && dense) {
         // self.landmarks in insertion order (:294), a wave wide; the scan ends at the first entry that is too new
@@ -1097,6 +994,12 @@ __device__ inline long long free_query(const QsGraphDev *Gp, QsNodeG g_nodes, Qs
     return gbest;
 }
 
+// LDS hand-overs between the waves of a workgroup.  Relaxed (LDS_RLX, LDS_ST_RLX): the LDS unit takes a wave's operations in the
+// order they were issued, so all a hand-over of LDS data needs is that the compiler keeps that order (LDS_CBAR).  Acquire / release
+// (lds_ld64 ...): where what is handed over includes stores to memory.
+#define LDS_RLX(p) __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define LDS_ST_RLX(p, v) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define LDS_CBAR() __asm__ volatile("" ::: "memory")
 __device__ inline long long lds_ld64(const long long *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ inline void lds_st64(long long *p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ inline unsigned int lds_ld32(const unsigned int *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -1168,14 +1071,11 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         const QsNodeG g_nodes = (QsNodeG)Gp->nodes;
         const QsU32G g_next = (QsU32G)Gp->nd_next;
         unsigned long long st_misc = 0, st_wait = 0;
-#ifdef QS_FREE_PROF
-        unsigned long long pf_wait = 0, pf_query = 0, pf_post = 0, pf_total0 = __builtin_amdgcn_s_memtime();
-#endif
         auto publish_prog = [&](long long nxt) {
             // what is handed over is the decision ring (LDS), written by this wave just before: the LDS unit takes a wave's
             // operations in the order they were issued, so all that is needed is that the compiler keeps that order
-            __asm__ volatile("" ::: "memory");
-            if (lane == 0) __hip_atomic_store(&s_prog[a], nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            LDS_CBAR();
+            if (lane == 0) LDS_ST_RLX(&s_prog[a], nxt);
         };
         // the next chunk's events are requested while this chunk's are dealt with
         auto load_chunk = [&](unsigned int q0, int &ag, long long &idx, int &type, double &px, double &py, long long &next_first) {
@@ -1190,9 +1090,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         int ag_n = -1, type_n = 0; long long idx_n = LL_MAX, nf_n = LL_MAX; double px_n = 0, py_n = 0;
         if (e0 < e1) load_chunk(e0, ag_n, idx_n, type_n, px_n, py_n, nf_n);
         for (unsigned int q0 = e0; q0 < e1; q0 += QS_WAVE) {
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 4
-            const unsigned long long tc_ = __builtin_amdgcn_s_memtime();
-#endif
             const int ag = ag_n, type = type_n;
             const long long idx = idx_n, next_first = nf_n;
             const double px = px_n, py = py_n;
@@ -1208,20 +1105,17 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                     const unsigned int ps = (q0 - e0 + (unsigned int)lane) % FR_PEND;
                     p_x[ps] = raw_pose ? px : px + c_dx; p_y[ps] = raw_pose ? py : py + c_dy;   // rx += cdx  :856-857
                 }
-                __asm__ volatile("" ::: "memory");
-                if ((m >> lane) & 1) __hip_atomic_store(&p_node[(q0 - e0 + (unsigned int)lane) % FR_PEND], idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                LDS_CBAR();
+                if ((m >> lane) & 1) LDS_ST_RLX(&p_node[(q0 - e0 + (unsigned int)lane) % FR_PEND], idx);
                 posted |= m;
             };
             // (a slot's last holder is long committed)
-            if (POST && own) FR_SPIN(q0 - e0 + QS_WAVE > __hip_atomic_load(&s_comm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + (unsigned int)(FR_PEND - QS_WAVE));
+            if (POST && own) FR_SPIN(q0 - e0 + QS_WAVE > LDS_RLX(&s_comm) + (unsigned int)(FR_PEND - QS_WAVE));
             // the events that may close a loop (:304: their agent is past its cool-down); the ones before the first need no decision
             auto eligible = [&]() -> unsigned long long {
                 return own & ~done & __ballot(idx - c_last >= min_between);
             };
             unsigned long long elig = eligible();
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 4
-            pf_wait += __builtin_amdgcn_s_memtime() - tc_;                         // (profile build 4: top of a chunk)
-#endif
             // A decision: (event f of the chunk, its pose with the agent's drift as it is NOW, the first nodes of its nine buckets,
             // their rows on the way).  The rows of the NEXT decision are asked for as soon as this one's closure is known -- before
             // the hand-over to the committer, whose LDS traffic then runs in the shadow of the loads.
@@ -1232,7 +1126,7 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             FqRows rows = {LL_MAX, LL_MAX, 0, 0, 0u};
             auto start_decision = [&](unsigned long long e_) {
                 // (the frontier first: the rows are asked for after it is read -- an older value is only more cautious)
-                fr_rows = __hip_atomic_load(&s_frontier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                fr_rows = LDS_RLX(&s_frontier);
                 f = __ffsll((long long)e_) - 1;
                 post_upto(f);
                 qidx = rl64(idx, f);
@@ -1254,9 +1148,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                 // the newest landmark a query can see is still the one before it
                 const long long limit = qidx_c - (min_between > 1 ? min_between : 1);
                 long long gbest; double wx, wy;
-#ifdef QS_FREE_PROF
-                const unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
                 {
                     bool pre = true;
                     for (long long fr = fr_rows;;) {
@@ -1286,10 +1177,9 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                             const bool inr = hv && nd > fr && nd <= limit;
                             const unsigned int ps = hv ? (unsigned int)jr % FR_PEND : 0u;
                             // posted -- or, if the committer overtook it meanwhile (its slot may have a new holder), in the index by now
-                            FR_SPIN(__ballot(inr && __hip_atomic_load(&p_node[ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != nd &&
-                                             __hip_atomic_load(&s_frontier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < nd) != 0);
-                            __asm__ volatile("" ::: "memory");
-                            if (__ballot(inr && __hip_atomic_load(&p_node[ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != nd)) { stale = true; break; }
+                            FR_SPIN(__ballot(inr && LDS_RLX(&p_node[ps]) != nd && LDS_RLX(&s_frontier) < nd) != 0);
+                            LDS_CBAR();
+                            if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }
                             bool hit = false;
                             double lx = 0, ly = 0;
                             if (inr && ty == qtype_c) {
@@ -1297,8 +1187,8 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                                 const double dx = qx_c - lx, dy = qy_c - ly;
                                 hit = dx * dx + dy * dy < r2thr;                    // :308-309
                             }
-                            __asm__ volatile("" ::: "memory");
-                            if (__ballot(inr && __hip_atomic_load(&p_node[ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != nd)) { stale = true; break; }
+                            LDS_CBAR();
+                            if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }
                             const unsigned long long hm = __ballot(hit);
                             if (hm) { const int w = 63 - __builtin_clzll(hm); gbest = rl64(nd, w); wx = rlf64(lx, w); wy = rlf64(ly, w); }
                             if (!__ballot(hv && lane == QS_WAVE - 1 && nd > fr)) break;  // the round's oldest event is in the index already
@@ -1309,9 +1199,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");        // the index as of that frontier, not older
                     }
                 }
-#ifdef QS_FREE_PROF
-                pf_query += __builtin_amdgcn_s_memtime() - tq_;
-#endif
                 done |= (2ull << f_c) - 1;                                          // (lanes up to f: decided)
                 double cdx = 0, cdy = 0;
                 if (gbest != LL_MAX) {
@@ -1329,14 +1216,8 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                     if (pq - cq >= (unsigned int)RD) {                              // looks full
                         cq = lds_ld32(&s_cons[qa]);
                         if (pq - cq >= (unsigned int)RD) {
-#ifdef QS_FREE_PROF
-                            const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-#endif
                             publish_prog(qidx_c);
                             FR_SPIN(pq - (cq = lds_ld32(&s_cons[qa])) >= (unsigned int)RD);
-#ifdef QS_FREE_PROF
-                            pf_wait += __builtin_amdgcn_s_memtime() - t_;
-#endif
                         }
                     }
                     if (lane == 0) {
@@ -1344,15 +1225,12 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                         q_idx[qa][sl] = qidx_c; q_midx[qa][sl] = gbest; q_cdx[qa][sl] = cdx; q_cdy[qa][sl] = cdy;
                     }
                     pushed = pq + 1; cons_c = cq;
-                    __asm__ volatile("" ::: "memory");
-                    if (lane == 0) __hip_atomic_store(&s_push[qa], pq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    LDS_CBAR();
+                    if (lane == 0) LDS_ST_RLX(&s_push[qa], pq + 1);
                 }
                 // decided: everything of this owner below its next event that may close (or, failing one in this chunk, below the
                 // next chunk's first event)
                 publish_prog(elig ? qidx : next_first);
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 3
-                pf_post += __builtin_amdgcn_s_memtime() - tq_;                      // (query + everything after it)
-#endif
             }
             post_upto(QS_WAVE - 1);                                                 // (the agent's events after its last decision of the chunk)
             publish_prog(next_first);
@@ -1364,11 +1242,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         if (lane == 0) {
             if (st_misc) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], st_misc);
             if (st_wait) { atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], st_wait); if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAIN_MISS - QS_FLAG_PILE, (unsigned int)st_wait); }
-#ifdef QS_FREE_PROF
-            if (a == 0) { atomicAdd(&counters[QS_CNT_SLAM_CYC_A], pf_wait); atomicAdd(&counters[QS_CNT_SLAM_CYC_B], pf_query);
-                          if (QS_FREE_PROF >= 3) atomicAdd(&counters[QS_CNT_SLAM_CYC_C], pf_post);
-                          atomicAdd(&counters[QS_CNT_SLAM_NODE_ITERS], __builtin_amdgcn_s_memtime() - pf_total0); }
-#endif
         }
     } else if (wave == INS) {
         // =================================== the committer ===================================
@@ -1379,9 +1252,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         unsigned long long st_batches = 0;
         const unsigned long long t0_cyc = __builtin_amdgcn_s_memtime(), t0_real = __builtin_amdgcn_s_memrealtime();
         unsigned int e = e0, idle = 0;
-#ifdef QS_FREE_PROF
-        unsigned long long pf_idle = 0, pf_agents = 0, pf_insert = 0;
-#endif
         // the events at the head of the list, a lane each: asked for again as soon as it is known how many of them go into the batch,
         // so that the next 64 arrive while this batch is dealt with
         long long node = LL_MAX, node_n = LL_MAX;
@@ -1401,24 +1271,18 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             // an event is ready when its agent has decided past it; the batch is the ready PREFIX (node order)
             // (relaxed, here and below: what the owners hand over is in LDS, which takes a wave's operations in the order they were
             // issued -- an acquire would make this wave wait for its own stores to HBM as well)
-            const bool ready = have && __hip_atomic_load(&s_prog[ag], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > node;
-            __asm__ volatile("" ::: "memory");
+            const bool ready = have && LDS_RLX(&s_prog[ag]) > node;
+            LDS_CBAR();
             const unsigned long long rm = __ballot(ready);
             const int k = rm == ~0ull ? 64 : (int)__builtin_ctzll(~rm);
             if (k == 0) {
                 if (++idle > FR_SPIN_MAX) { if (lane == 0) atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], 1ull << 40); break; }   // (never: see FR_SPIN)
                 if ((idle & 63u) == 0 && (__hip_atomic_load(&counters[QS_CNT_SLAM_ROUNDS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 40)) break;
-#ifdef QS_FREE_PROF
-                pf_idle++;
-#endif
                 __builtin_amdgcn_s_sleep(1);
                 continue;
             }
             idle = 0;
             if (e + k < e1) load_events(e + k, node_n, ag_n, type_n, px_n, py_n);
-#ifdef QS_FREE_PROF
-            const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-#endif
             const bool inw = lane < k;
             const int type = inw ? type_l : 0;
             const double px = inw ? px_l : 0, py = inw ? py_l : 0;
@@ -1432,8 +1296,8 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                 rem &= ~La;
                 double cur_dx = c_ddx[aa], cur_dy = c_ddy[aa];
                 unsigned int dc = s_cons[aa];
-                const unsigned int dp = __hip_atomic_load(&s_push[aa], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __asm__ volatile("" ::: "memory");
+                const unsigned int dp = LDS_RLX(&s_push[aa]);
+                LDS_CBAR();
                 unsigned int apos = c_apos[aa];
                 unsigned long long left = La;                                        // lanes of aa not yet given their drift
                 while (dc != dp) {
@@ -1453,13 +1317,9 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                     dc++;
                 }
                 if ((left >> lane) & 1) { dx = cur_dx; dy = cur_dy; }
-                __asm__ volatile("" ::: "memory");
-                if (lane == ld) { c_ddx[aa] = cur_dx; c_ddy[aa] = cur_dy; c_apos[aa] = apos; __hip_atomic_store(&s_cons[aa], dc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+                LDS_CBAR();
+                if (lane == ld) { c_ddx[aa] = cur_dx; c_ddy[aa] = cur_dy; c_apos[aa] = apos; LDS_ST_RLX(&s_cons[aa], dc); }
             }
-#ifdef QS_FREE_PROF
-            const unsigned long long tp1 = __builtin_amdgcn_s_memtime();
-            pf_agents += tp1 - tp0;
-#endif
             const double x = raw_pose ? px : px + dx, y = raw_pose ? py : py + dy;   // rx += cdx, ry += cdy  :856-857
             // ---- closure records, in node order  (:317) ----
             const bool closes = inw && midx != LL_MAX;
@@ -1483,24 +1343,17 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             if (lane == 0) {
                 s_nmisc = n_misc; s_nlms = n_lms;
                 lds_st64(&s_frontier, next_node == LL_MAX ? LL_MAX : next_node - 1);
-                __hip_atomic_store(&s_comm, e + k - e0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                LDS_ST_RLX(&s_comm, e + k - e0);
             }
             e += k;
             node = node_n; ag = ag_n; type_l = type_n; px_l = px_n; py_l = py_n;
             st_batches++;
-#ifdef QS_FREE_PROF
-            pf_insert += __builtin_amdgcn_s_memtime() - tp1;
-#endif
         }
         if (lane == 0) {
             atomicAdd(&counters[QS_CNT_CLOSURES], (unsigned long long)(n_cls - G.n_cls));
             if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAIN_HIT - QS_FLAG_PILE, (unsigned int)(n_cls - G.n_cls));
             atomicAdd(&counters[QS_CNT_LANDMARKS], (unsigned long long)(n_lms - G.n_lms));
             atomicAdd(&counters[QS_CNT_SLAM_WINDOWS], st_batches);
-#ifdef QS_FREE_PROF
-            if (QS_FREE_PROF < 3) atomicAdd(&counters[QS_CNT_SLAM_CYC_C], pf_idle);
-            atomicAdd(&counters[QS_CNT_EKF_WRAP_CLAMP], pf_agents); if (QS_FREE_PROF == 1) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], pf_insert);
-#endif
             atomicAdd(&counters[QS_CNT_SLAM_CYCLES], __builtin_amdgcn_s_memtime() - t0_cyc);
             atomicAdd(&counters[QS_CNT_SLAM_REALTIME], __builtin_amdgcn_s_memrealtime() - t0_real);
             Gp->n_nodes = G.n_nodes + sb.acc_total[g];
@@ -1569,16 +1422,13 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
     if (tid < CH_WAVES) s_prog[tid] = (tid >= 1 && tid <= DY_OWNERS && e0 < e1) ? sb.ev_node[e0] : LL_MAX;
     if (tid == 0) { s_frontier = e0 < e1 ? sb.ev_node[e0] - 1 : LL_MAX; s_nmisc = Gp->n_misc; s_nlms = Gp->n_lms; s_head = 0; s_disp = 0; s_comm = 0; }
     __syncthreads();
-#define LD_RLX(p) __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define ST_RLX(p, v) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define CBAR() __asm__ volatile("" ::: "memory")      // LDS takes a wave's operations in the order they were issued: keeping the compiler to it is all a hand-over needs
 
     if (wave == 0) {
         // =================================== the dispatcher ===================================
         for (unsigned int d = e0; d < e1; d += QS_WAVE) {
             const unsigned int r = d - e0;
             // a ring slot is free once the event that had it is committed
-            FR_SPIN(r + QS_WAVE > DY_RING && LD_RLX(&s_comm) + DY_RING < r + QS_WAVE);
+            FR_SPIN(r + QS_WAVE > DY_RING && LDS_RLX(&s_comm) + DY_RING < r + QS_WAVE);
             const unsigned int q = d + lane;
             const bool have = q < e1;
             const int ag = have ? (int)sb.ev_agent[q] : 0;
@@ -1587,13 +1437,13 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             bool todo = have;
             while (__ballot(todo)) {          // an agent's events of this chunk one per round, in node order
                 if (todo) atomicMin(&d_tag[ag], (unsigned int)lane);
-                CBAR();
-                if (todo && LD_RLX(&d_tag[ag]) == (unsigned int)lane) { prev = d_last[ag]; d_last[ag] = node; d_tag[ag] = 0xffffffffu; todo = false; }
-                CBAR();
+                LDS_CBAR();
+                if (todo && LDS_RLX(&d_tag[ag]) == (unsigned int)lane) { prev = d_last[ag]; d_last[ag] = node; d_tag[ag] = 0xffffffffu; todo = false; }
+                LDS_CBAR();
             }
             if (have) d_ring[(r + lane) % DY_RING] = prev;
-            CBAR();
-            if (lane == 0) ST_RLX(&s_disp, min(r + QS_WAVE, e1 - e0));
+            LDS_CBAR();
+            if (lane == 0) LDS_ST_RLX(&s_disp, min(r + QS_WAVE, e1 - e0));
         }
     } else if (wave <= DY_OWNERS) {
         // =================================== an owner ===================================
@@ -1614,13 +1464,7 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             type = have ? (int)sb.ev_type[q] : 0;
             px = have ? sb.ev_px[q] : 0; py = have ? sb.ev_py[q] : 0;
         };
-#ifdef QS_FREE_PROF
-        unsigned long long pf_wait = 0, pf_query = 0, pf_prev = 0, pf_grab = 0, pf_total0 = __builtin_amdgcn_s_memtime();
-#endif
         for (;;) {
-#ifdef QS_FREE_PROF
-            const unsigned long long tg_ = __builtin_amdgcn_s_memtime();
-#endif
             unsigned int t = 0;
             if (lane == 0) t = atomicAdd(&s_head, 1u);
             const unsigned int r = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
@@ -1636,20 +1480,13 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             const int l = (int)(i - cb);
             const int qa = __builtin_amdgcn_readlane(ag_c, l);
             const long long qidx = rl64(idx_c, l);
-            if (lane == 0) ST_RLX(&s_prog[wave], qidx);
+            if (lane == 0) LDS_ST_RLX(&s_prog[wave], qidx);
             // the agent's previous event has to be decided
-#ifdef QS_FREE_PROF
-            const unsigned long long tv_ = __builtin_amdgcn_s_memtime();
-            pf_grab += tv_ - tg_;
-#endif
-            FR_SPIN(LD_RLX(&s_disp) <= r);
-            CBAR();
+            FR_SPIN(LDS_RLX(&s_disp) <= r);
+            LDS_CBAR();
             const long long prev = d_ring[r % DY_RING];
-            FR_SPIN(LD_RLX(&a_node[qa]) < prev);
-            CBAR();
-#ifdef QS_FREE_PROF
-            pf_prev += __builtin_amdgcn_s_memtime() - tv_;
-#endif
+            FR_SPIN(LDS_RLX(&a_node[qa]) < prev);
+            LDS_CBAR();
             const long long last = a_last[qa];
             const double odx = a_dx[qa], ody = a_dy[qa];
             const double spx = rlf64(px_c, l), spy = rlf64(py_c, l);
@@ -1657,20 +1494,17 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             // the pose this event's landmark is appended at (:288) is known from here on: posted for the queries of younger events,
             // which then need not wait for the committer to put it into the index
             {
-                FR_SPIN(r >= LD_RLX(&s_comm) + (unsigned int)(DY_PEND - QS_WAVE));  // (the slot's last holder is long committed)
+                FR_SPIN(r >= LDS_RLX(&s_comm) + (unsigned int)(DY_PEND - QS_WAVE));  // (the slot's last holder is long committed)
                 const unsigned int ps = r % DY_PEND;
                 if (lane == 0) { p_x[ps] = qx; p_y[ps] = qy; }
-                CBAR();
-                if (lane == 0) ST_RLX(&p_node[ps], qidx);
+                LDS_CBAR();
+                if (lane == 0) LDS_ST_RLX(&p_node[ps], qidx);
             }
             if (qidx - last >= min_between) {                                       // :304
-                const long long fr0 = LD_RLX(&s_frontier);
+                const long long fr0 = LDS_RLX(&s_frontier);
                 const int qtype = __builtin_amdgcn_readlane(type_c, l);
                 const long long limit = qidx - (min_between > 1 ? min_between : 1);  // :300; a node never sees its own landmark (:288)
                 long long gbest; double wx, wy;
-#ifdef QS_FREE_PROF
-                const unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
                 for (long long fr = fr0;; fr = lds_ld64(&s_frontier)) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");            // the index as of that frontier, not older
                     const long long nm = s_nmisc, nl = DENSE ? s_nlms : 0;
@@ -1682,9 +1516,6 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
                     // their poses are in the pending ring as soon as their owners have started on them -- which waits for older events
                     // only.  64 events a round, youngest first; the OLDEST match is the reference's first match.
                     st_wait++;
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 6
-                    const unsigned long long tw_ = __builtin_amdgcn_s_memtime();
-#endif
                     bool stale = false;
                     for (unsigned int back = 0; back < r; back += QS_WAVE) {
                         const long long jr = (long long)r - 1 - (long long)back - lane;
@@ -1694,9 +1525,9 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
                         const bool inr = hv && nd > fr && nd <= limit;
                         const unsigned int ps = hv ? (unsigned int)jr % DY_PEND : 0u;
                         // posted -- or, if the committer overtook it meanwhile (its slot may have a new holder), in the index by now
-                        FR_SPIN(__ballot(inr && LD_RLX(&p_node[ps]) != nd && LD_RLX(&s_frontier) < nd) != 0);
-                        CBAR();
-                        if (__ballot(inr && LD_RLX(&p_node[ps]) != nd)) { stale = true; break; }
+                        FR_SPIN(__ballot(inr && LDS_RLX(&p_node[ps]) != nd && LDS_RLX(&s_frontier) < nd) != 0);
+                        LDS_CBAR();
+                        if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }
                         bool hit = false;
                         double lx = 0, ly = 0;
                         if (inr && ty == qtype) {
@@ -1704,57 +1535,40 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
                             const double dx = qx - lx, dy = qy - ly;
                             hit = dx * dx + dy * dy < r2thr;                        // :308-309
                         }
-                        CBAR();
-                        if (__ballot(inr && LD_RLX(&p_node[ps]) != nd)) { stale = true; break; }   // (the pose read belongs to that event)
+                        LDS_CBAR();
+                        if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }   // (the pose read belongs to that event)
                         const unsigned long long hm = __ballot(hit);
                         if (hm) { const int w = 63 - __builtin_clzll(hm); gbest = rl64(nd, w); wx = rlf64(lx, w); wy = rlf64(ly, w); }
                         if (!__ballot(hv && lane == QS_WAVE - 1 && nd > fr)) break;  // the round's oldest event is in the index already
                     }
-#if defined(QS_FREE_PROF) && QS_FREE_PROF == 6
-                    pf_wait += __builtin_amdgcn_s_memtime() - tw_;                   // (profile build 6: the pending scan)
-#endif
                     if (!stale) break;                                              // match or none: final (index up to fr, events up to limit)
                     gbest = LL_MAX;                                                 // the index has grown under the scan: once more, from it
                 }
-#ifdef QS_FREE_PROF
-                pf_query += __builtin_amdgcn_s_memtime() - tq_;
-#endif
                 if (gbest != LL_MAX) {
                     const double ex = wx - qx, ey = wy - qy;                        // :311-312
                     const double cdx = ex * corr, cdy = ey * corr;                  // :314-315
                     const unsigned int pq = s_push[qa];
-                    unsigned int cq = LD_RLX(&s_cons[qa]);
+                    unsigned int cq = LDS_RLX(&s_cons[qa]);
                     if (pq - cq >= DY_RD) {
-#ifdef QS_FREE_PROF
-                        const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-#endif
-                        FR_SPIN(pq - (cq = LD_RLX(&s_cons[qa])) >= DY_RD);
-#ifdef QS_FREE_PROF
-                        pf_wait += __builtin_amdgcn_s_memtime() - t_;
-#endif
+                        FR_SPIN(pq - (cq = LDS_RLX(&s_cons[qa])) >= DY_RD);
                     }
-                    CBAR();
+                    LDS_CBAR();
                     if (lane == 0) {
                         const unsigned int sl = (unsigned int)qa * DY_RD + (pq & (DY_RD - 1));
                         q_idx[sl] = qidx; q_midx[sl] = gbest; q_cdx[sl] = cdx; q_cdy[sl] = cdy;
                         a_dx[qa] = odx + cdx; a_dy[qa] = ody + cdy; a_last[qa] = qidx;      // :911-914, :318
                     }
-                    CBAR();
-                    if (lane == 0) ST_RLX(&s_push[qa], pq + 1);
+                    LDS_CBAR();
+                    if (lane == 0) LDS_ST_RLX(&s_push[qa], pq + 1);
                 }
             }
-            CBAR();
-            if (lane == 0) ST_RLX(&a_node[qa], qidx);
+            LDS_CBAR();
+            if (lane == 0) LDS_ST_RLX(&a_node[qa], qidx);
         }
-        if (lane == 0) ST_RLX(&s_prog[wave], LL_MAX);
+        if (lane == 0) LDS_ST_RLX(&s_prog[wave], LL_MAX);
         if (lane == 0) {
             if (st_misc) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], st_misc);
             if (st_wait) { atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], st_wait); if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAIN_MISS - QS_FLAG_PILE, (unsigned int)st_wait); }
-#ifdef QS_FREE_PROF
-            if (wave == 1) { atomicAdd(&counters[QS_CNT_SLAM_CYC_A], QS_FREE_PROF == 2 ? pf_prev : pf_wait);
-                             atomicAdd(&counters[QS_CNT_SLAM_CYC_B], QS_FREE_PROF == 2 ? pf_grab : pf_query);
-                             atomicAdd(&counters[QS_CNT_SLAM_NODE_ITERS], __builtin_amdgcn_s_memtime() - pf_total0); }
-#endif
         }
     } else if (wave == CH_WAVES - 1) {
         // =================================== the committer ===================================
@@ -1765,9 +1579,6 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
         unsigned long long st_batches = 0;
         const unsigned long long t0_cyc = __builtin_amdgcn_s_memtime(), t0_real = __builtin_amdgcn_s_memrealtime();
         unsigned int e = e0, idle = 0;
-#ifdef QS_FREE_PROF
-        unsigned long long pf_idle = 0, pf_agents = 0, pf_insert = 0;
-#endif
         long long node = LL_MAX, node_n = LL_MAX;
         int ag = 0, type_l = 0, ag_n = 0, type_n = 0;
         double px_l = 0, py_l = 0, px_n = 0, py_n = 0;
@@ -1783,24 +1594,18 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
         while (e < e1) {
             const bool have = e + lane < e1;
             // the batch: the events older than everything an owner is still working on (a PREFIX of the list)
-            const long long mp = wave_min_nonneg_i64((lane >= 1 && lane <= DY_OWNERS) ? LD_RLX(&s_prog[lane]) : LL_MAX);
-            CBAR();
+            const long long mp = wave_min_nonneg_i64((lane >= 1 && lane <= DY_OWNERS) ? LDS_RLX(&s_prog[lane]) : LL_MAX);
+            LDS_CBAR();
             const unsigned long long rm = __ballot(have && node < mp);
             const int k = rm == ~0ull ? 64 : (int)__builtin_ctzll(~rm);
             if (k == 0) {
                 if (++idle > FR_SPIN_MAX) { if (lane == 0) atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], 1ull << 40); break; }   // (never: see FR_SPIN)
                 if ((idle & 63u) == 0 && (__hip_atomic_load(&counters[QS_CNT_SLAM_ROUNDS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 40)) break;
-#ifdef QS_FREE_PROF
-                pf_idle++;
-#endif
                 __builtin_amdgcn_s_sleep(1);
                 continue;
             }
             idle = 0;
             if (e + k < e1) load_events(e + k, node_n, ag_n, type_n, px_n, py_n);
-#ifdef QS_FREE_PROF
-            const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-#endif
             const bool inw = lane < k;
             const int type = inw ? type_l : 0;
             const double px = inw ? px_l : 0, py = inw ? py_l : 0;
@@ -1811,12 +1616,12 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             bool todo = inw;
             while (__ballot(todo)) {
                 if (todo) atomicMin(&c_tag[ag], (unsigned int)lane);
-                CBAR();
-                if (todo && LD_RLX(&c_tag[ag]) == (unsigned int)lane) {
+                LDS_CBAR();
+                if (todo && LDS_RLX(&c_tag[ag]) == (unsigned int)lane) {
                     const unsigned int dc = s_cons[ag];
-                    const unsigned int dp = LD_RLX(&s_push[ag]);
+                    const unsigned int dp = LDS_RLX(&s_push[ag]);
                     dx = c_ddx[ag]; dy = c_ddy[ag];                                  // matched / stored at the pose BEFORE the closure (:288, :308)
-                    CBAR();
+                    LDS_CBAR();
                     const unsigned int sl = (unsigned int)ag * DY_RD + (dc & (DY_RD - 1));
                     if (dc != dp && q_idx[sl] == node) {                             // (else the agent's next decision is about a later event)
                         midx = q_midx[sl]; cdx = q_cdx[sl]; cdy = q_cdy[sl];
@@ -1824,18 +1629,14 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
                         const unsigned int apos = c_apos[ag];
                         sb.acl_node[apos] = node; sb.acl_dx[apos] = ndx; sb.acl_dy[apos] = ndy;
                         c_ddx[ag] = ndx; c_ddy[ag] = ndy; c_apos[ag] = apos + 1;
-                        CBAR();
-                        ST_RLX(&s_cons[ag], dc + 1);
+                        LDS_CBAR();
+                        LDS_ST_RLX(&s_cons[ag], dc + 1);
                     }
                     c_tag[ag] = 0xffffffffu;
                     todo = false;
                 }
-                CBAR();
+                LDS_CBAR();
             }
-#ifdef QS_FREE_PROF
-            const unsigned long long tp1 = __builtin_amdgcn_s_memtime();
-            pf_agents += tp1 - tp0;
-#endif
             const double x = raw_pose ? px : px + dx, y = raw_pose ? py : py + dy;   // rx += cdx, ry += cdy  :856-857
             // ---- closure records, in node order  (:317) ----
             const bool closes = inw && midx != LL_MAX;
@@ -1859,23 +1660,16 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
             if (lane == 0) {
                 s_nmisc = n_misc; s_nlms = n_lms;
                 lds_st64(&s_frontier, next_node == LL_MAX ? LL_MAX : next_node - 1);
-                ST_RLX(&s_comm, e - e0);
+                LDS_ST_RLX(&s_comm, e - e0);
             }
             node = node_n; ag = ag_n; type_l = type_n; px_l = px_n; py_l = py_n;
             st_batches++;
-#ifdef QS_FREE_PROF
-            pf_insert += __builtin_amdgcn_s_memtime() - tp1;
-#endif
         }
         if (lane == 0) {
             atomicAdd(&counters[QS_CNT_CLOSURES], (unsigned long long)(n_cls - G.n_cls));
             if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAIN_HIT - QS_FLAG_PILE, (unsigned int)(n_cls - G.n_cls));
             atomicAdd(&counters[QS_CNT_LANDMARKS], (unsigned long long)(n_lms - G.n_lms));
             atomicAdd(&counters[QS_CNT_SLAM_WINDOWS], st_batches);
-#ifdef QS_FREE_PROF
-            atomicAdd(&counters[QS_CNT_SLAM_CYC_C], pf_idle);
-            atomicAdd(&counters[QS_CNT_EKF_WRAP_CLAMP], pf_agents); if (QS_FREE_PROF == 1) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], pf_insert);
-#endif
             atomicAdd(&counters[QS_CNT_SLAM_CYCLES], __builtin_amdgcn_s_memtime() - t0_cyc);
             atomicAdd(&counters[QS_CNT_SLAM_REALTIME], __builtin_amdgcn_s_memrealtime() - t0_real);
             Gp->n_nodes = G.n_nodes + sb.acc_total[g];
@@ -1889,9 +1683,6 @@ qs_slam_chain_dyn_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuck
     for (int t = tid; t < nb; t += CH_THREADS) {
         drift[2 * (bot0 + t)] = a_dx[t]; drift[2 * (bot0 + t) + 1] = a_dy[t]; last_closure[bot0 + t] = a_last[t];
     }
-#undef LD_RLX
-#undef ST_RLX
-#undef CBAR
 }
 
 // ---- pose: rx, ry of every accepted record (dual_bot_mapper.py:855-857) ---------------------------

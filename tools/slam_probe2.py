@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""SLAM chain, owner wave 1 of graph 0, cycles per window by segment (QS_CHAIN_PROF2 build: tools/build_variant.sh chprof2
-"-DQS_CHAIN_PROF2" slam.hip; QUASAR_SLAM_LIB=ab_libs/chprof2.so).  With the plain library: stage times only."""
+"""SLAM chain: stage time of the chain per run, windows, cycles per window and closures for one workload
+(QUASAR_SLAM_LIB selects the library, e.g. one built by tools/build_variant.sh)."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,13 +28,6 @@ for r in range(reps):
     c = m.counters(); st = m.stage_times()
     w = c["slam_windows"]
     out.append(round(st["slam_chain"][0], 3))
-prof = "chprof2" in os.environ.get("QUASAR_SLAM_LIB", "")
 res = {"workload": wl, "lib": os.path.basename(os.environ.get("QUASAR_SLAM_LIB", "default")), "chain_ms": out, "windows": w, "cyc_per_window": round(c["slam_cycles"] / w, 1),
        "closures": c["closures"]}
-if prof:
-    res.update({"head": c["slam_cyc_prepare"] / w, "q_setup": c["slam_cyc_query"] / w, "q_scan": c["slam_cyc_commit"] / w,
-                "q_post": c["slam_misc_iters"] / w, "publish": c["ekf_wrap_clamp"] / w, "barrier": c["slam_rounds"] / w})
-if "chprof3" in os.environ.get("QUASAR_SLAM_LIB", ""):
-    res.update({"busy_wave0": c["slam_cyc_prepare"] / w, "busy_fetch": c["slam_cyc_query"] / w, "busy_insert": c["slam_cyc_commit"] / w,
-                "busy_owner1": c["slam_misc_iters"] / w, "busy_other_owners_sum": c["ekf_wrap_clamp"] / w})
 print(json.dumps(res))

@@ -15,6 +15,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "quasar_slam.h")
 QS_CNT_NAMES = ("datagrams", "accepted", "rays", "cells", "hits", "closures", "landmarks", "rebases",
                 "slam_windows", "slam_rounds", "slam_node_iters", "slam_misc_iters", "slam_cycles",
                 "slam_realtime_100mhz", "slam_cyc_prepare", "slam_cyc_query", "slam_cyc_commit", "ekf_wrap_clamp", "edge_rays", "edge_overflow")
+QS_FT_MAX_BOTS = 1024       # bots per qs_frontier_targets call (include/quasar_slam.h)
 QS_STAGE_NAMES = ("decode", "slam", "raycast", "ekf", "slam_chain", "rc_rays", "rc_sort", "rc_raster")
 UINT64_MAX = (1 << 64) - 1
 
@@ -123,6 +124,7 @@ SIGNATURES = {
     "qs_frontier_cells": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_members": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_clusters": (_i32, [_vp, _i32, _vp, _sz, C.POINTER(_sz)]),
+    "qs_frontier_targets": (_i32, [_vp, _i32, _f64, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "qs_ekf_init": (_i32, [_vp, _i32, _f64, _vp]),
     "qs_ekf_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32]),
     "qs_ekf_state": (_i32, [_vp, _i32, _vp, _vp]),

@@ -17,7 +17,7 @@
 #include "qs_internal.h"
 
 #define FR_BLOCK 256
-#define FR_CHUNK 1024
+#define FR_CHUNK QS_FR_CHUNK
 #define FR_NONE 0xffffffffu
 
 __device__ inline bool fr_is_free(unsigned int s) { return s != 0 && !(s & 1u); }
@@ -227,6 +227,25 @@ hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, 
         else if (mode == 2) hipLaunchKernelGGL(qs_frontier_write_kernel<2>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
         else hipLaunchKernelGGL(qs_frontier_write_kernel<1>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
     }
+    return hipGetLastError();
+}
+
+void qs_frontier_ws_parts(const qs_ctx *c, void *ws, unsigned int **cnt, unsigned long long **sumx, unsigned long long **sumy,
+                          unsigned int **chunk, unsigned long long **total)
+{
+    const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
+    *cnt = (unsigned int *)ws + cells;
+    *sumx = (unsigned long long *)(*cnt + cells); *sumy = *sumx + cells;
+    *chunk = (unsigned int *)(*sumy + cells);
+    *total = (unsigned long long *)((char *)*chunk + ((n_chunks * 4 + 15) & ~(size_t)15));
+}
+
+// exclusive scan of the chunk counts a count kernel left in the workspace; the sum -> total
+hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws)
+{
+    unsigned int *cnt, *chunk; unsigned long long *sumx, *sumy, *total;
+    qs_frontier_ws_parts(c, ws, &cnt, &sumx, &sumy, &chunk, &total);
+    hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, chunk, (c->cells + FR_CHUNK - 1) / FR_CHUNK, total);
     return hipGetLastError();
 }
 

@@ -288,7 +288,7 @@ extern "C" int qs_destroy(qs_ctx *c)
     hipFree(c->d_stamps); hipFree(c->d_counts); hipFree(c->d_counts_fused); hipFree(c->d_io_ws); hipFree(c->d_offset); hipFree(c->d_drift);
     hipFree(c->d_last_closure); hipFree(c->d_zone); hipFree(c->d_counters); hipFree(c->d_graph_batch);
     hipFree(c->d_ekf); hipFree(c->d_ekf_prev); hipFree(c->d_ekf_ws); hipFree(c->d_graphs); hipFree(c->d_flags); if (c->h_chain_stat) hipHostFree(c->h_chain_stat); if (c->ev_chain_stat) hipEventDestroy(c->ev_chain_stat); hipFree(c->d_pkts); hipFree(c->d_lens);
-    hipFree(c->d_time); hipFree(c->d_bin_ws); hipFree(c->d_frontier_ws);
+    hipFree(c->d_time); hipFree(c->d_bin_ws); hipFree(c->d_frontier_ws); hipFree(c->d_ft_ws);
     hipFree(c->d_edge);
     hipFree(c->d_dirty); hipFree(c->d_counts_sent); hipFree(c->d_sf_bitmaps); hipFree(c->d_sf_lists); hipFree(c->d_sf_counts); hipFree(c->d_sf_payload);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1658,6 +1658,68 @@ extern "C" int qs_frontier_members(qs_ctx *c, int32_t *xy_root, size_t cap, size
 
 extern "C" int qs_frontier_clusters(qs_ctx *c, int32_t min_cluster, int64_t *stats5, size_t cap, size_t *n_out)
 { return frontier_run(c, 1, min_cluster, nullptr, stats5, cap, n_out); }
+
+// frontier target assignment (frontier_targets.hip): centroids on the device, top-K lists, the greedy pass; the pass
+// stops at a bot whose full list is ineligible, a whole-GPU scan decides that bot, and the pass resumes from it
+extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separation, const double *bot_xy, size_t n_bots,
+                                   int64_t *target_idx, double *target_xy, double *centroids_xy, size_t cap,
+                                   size_t *n_centroids, uint64_t stats[4])
+{
+    ARGCHK(c, c != nullptr);
+    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets: n_bots above QS_FT_MAX_BOTS");
+    ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy));
+    ARGCHK(c, cap == 0 || centroids_xy);
+    HIPCHK(c, hipSetDevice(c->device));
+    FLUSHCHK(c);
+    if (!c->d_frontier_ws) HIPCHK(c, hipMalloc(&c->d_frontier_ws, qs_frontier_workspace_bytes(c)));
+    void *fws = c->d_frontier_ws;
+    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_total_ptr(c, fws), sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n_cent = (size_t)total;
+    const size_t need = qs_ft_workspace_bytes(n_cent, n_bots);
+    if (need > c->ft_ws_bytes) {
+        HIPCHK(c, dev_realloc((char **)&c->d_ft_ws, need));
+        c->ft_ws_bytes = need;
+    }
+    QsFtState *d_st; double2 *d_cent, *d_bots, *d_txy; long long *d_tidx;
+    qs_ft_parts(c->d_ft_ws, n_cent, n_bots, &d_st, &d_cent, &d_bots, &d_tidx, &d_txy);
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, d_cent));
+    uint64_t fallbacks = 0;
+    std::vector<long long> tidx(n_bots, -1);
+    std::vector<double> txy(2 * n_bots);
+    if (n_bots && n_cent) {
+        const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation (0: nothing is too close)
+        HIPCHK(c, hipMemcpyAsync(d_bots, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        int start = 0, m = 0, pending = 0;
+        for (;;) {
+            HIPCHK(c, qs_launch_ft_assign(c, c->d_ft_ws, n_cent, n_bots, r2_sep, start, m, pending));
+            QsFtState st;
+            HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (!st.stop) break;
+            if (st.next_bot < start || st.next_bot >= (int)n_bots || (pending && st.next_bot == start))
+                return qs_fail(c, QS_E_HIP, "qs_frontier_targets: greedy pass made no progress");
+            fallbacks++;
+            start = st.next_bot; m = st.m; pending = 1;
+            HIPCHK(c, qs_launch_ft_fallback(c, c->d_ft_ws, n_cent, n_bots, r2_sep, start, m));
+        }
+        HIPCHK(c, hipMemcpyAsync(tidx.data(), d_tidx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(txy.data(), d_txy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    }
+    const size_t nc = n_cent < cap ? n_cent : cap;
+    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, d_cent, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < n_bots; b++) {
+        target_idx[b] = tidx[b];
+        if (tidx[b] >= 0) { target_xy[2 * b] = txy[2 * b]; target_xy[2 * b + 1] = txy[2 * b + 1]; }
+    }
+    if (n_centroids) *n_centroids = n_cent;
+    if (stats) { stats[0] = n_cent; stats[1] = QS_FT_K; stats[2] = fallbacks; stats[3] = 0; }
+    return QS_OK;
+}
 
 // ---- EKF --------------------------------------------------------------------------------------------
 extern "C" int qs_ekf_init(qs_ctx *c, int32_t bot, double t, const double x0[6])

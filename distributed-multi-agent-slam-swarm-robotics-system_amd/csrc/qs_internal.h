@@ -190,6 +190,7 @@ struct qs_ctx {
     // tile-binned raycast workspace
     void *d_bin_ws = nullptr; size_t bin_ws_bytes = 0;
     void *d_frontier_ws = nullptr;               // frontier labelling workspace (allocated on first use)
+    void *d_ft_ws = nullptr; size_t ft_ws_bytes = 0;     // frontier target assignment (frontier_targets.hip), grown on demand
     void *d_io_ws = nullptr; size_t io_ws_bytes = 0;     // staging of the object-API calls (qs_update_rays, views), grown on demand
     void *d_ekf_ws = nullptr; size_t ekf_ws_bytes = 0;   // parallel-in-time EKF workspace (ekf_scan.hip)
 
@@ -284,10 +285,25 @@ hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out);
 // diag.hip
 hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out);
 // frontier.hip
+#define QS_FR_CHUNK 1024          // cells per chunk of the frontier compactions (count -> scan -> ranked write)
 size_t qs_frontier_workspace_bytes(const qs_ctx *c);
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
 hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap);
 unsigned long long *qs_frontier_total_ptr(const qs_ctx *c, void *ws);
+void qs_frontier_ws_parts(const qs_ctx *c, void *ws, unsigned int **cnt, unsigned long long **sumx, unsigned long long **sumy,
+                          unsigned int **chunk, unsigned long long **total);
+hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
+// frontier_targets.hip
+#define QS_FT_K 32                // candidates per bot (the top-K list of the greedy pass)
+struct QsFtState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
+size_t qs_ft_workspace_bytes(size_t n_cent, size_t n_bots);
+hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
+// the lists, then the greedy pass from start_bot (fb_pending: a fallback scan has decided start_bot); it ends in QsFtState
+hipError_t qs_launch_ft_assign(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep,
+                               int start_bot, int start_m, int fb_pending);
+hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep, int bot, int m);
+void qs_ft_parts(void *ft_ws, size_t n_cent, size_t n_bots, QsFtState **st, double2 **cent, double2 **bots, long long **tgt_idx,
+                 double2 **tgt_xy);
 // icp.hip
 hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
                             double max_d2, int *corr, double *d2);

@@ -480,6 +480,40 @@ class QuasarMapper:
             out.append((self.ox + (ax + 0.5) * self.res, self.oy + (ay + 0.5) * self.res))
         return out
 
+    def frontier_targets(self, bot_xy, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
+                         return_centroids=False):
+        """The greedy frontier assignment of dual_bot_mapper.py:958-992 on the device.  bot_xy: [n, 2] positions in
+        greedy order.  Returns (idx int64 [n]: index into frontier_centroids(min_cluster), -1 = no target;
+        xy float64 [n, 2]: that centroid, NaN where idx is -1), plus (centroids float64 [k, 2], stats dict) on request."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(b)
+        if n > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"frontier_targets: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        idx = np.full(n, -1, dtype=np.int64)
+        xy = np.full((n, 2), np.nan, dtype=np.float64)
+        st = np.zeros(4, dtype=np.uint64)
+        k = C.c_size_t()
+        cents, cap = None, 0
+        if return_centroids:       # the count first: a second call would observe the same map
+            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
+            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
+        self._chk(self._L.qs_frontier_targets(self._h, min_cluster, float(separation), _ptr(b), n, _ptr(idx), _ptr(xy),
+                                              _ptr(cents) if cap else None, cap, C.byref(k), _ptr(st)),
+                  "qs_frontier_targets")
+        if not return_centroids:
+            return idx, xy
+        stats = dict(zip(("n_centroids", "k", "fallbacks", "reserved"), (int(v) for v in st)))
+        return idx, xy, cents[:k.value], stats
+
+    def assign_frontier_targets(self, bot_states, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER):
+        """The reference's target_assignments (:958-992): {bot: (x, y)} of the online bots -> {bot: (tx, ty)} for
+        the bots that got a target, bots taken in ascending id."""
+        bots = sorted(bot_states)
+        if not bots:
+            return {}
+        idx, xy = self.frontier_targets([bot_states[b] for b in bots], separation, min_cluster)
+        return {b: (float(xy[i, 0]), float(xy[i, 1])) for i, b in enumerate(bots) if idx[i] >= 0}
+
     # -- EKF --------------------------------------------------------------------------------------
     def ekf_init(self, bot, t, x0):
         x0 = np.ascontiguousarray(x0, dtype=np.float64)

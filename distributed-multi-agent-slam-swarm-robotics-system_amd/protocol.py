@@ -87,6 +87,11 @@ def zone_packet(box) -> bytes:
     return struct.pack(ZONE_FMT, b"ZONE", box[0], box[1], box[2], box[3])
 
 
+def pack_target(x, y) -> bytes:
+    """send_target_to_bot's payload (dual_bot_mapper.py:691-699): 12 bytes, read by AgentFirmware_Bot1.ino:81-137."""
+    return struct.pack(TARGET_FMT, b"TARG", x, y)
+
+
 def compute_bounding_box(points_x, points_y):
     """dual_bot_mapper.py:702-706."""
     if len(points_x) == 0:

@@ -8,6 +8,10 @@ Mirrors server_nodes/dual_bot_mapper.py:
   heartbeat         :805-812   5 s of silence -> offline; any accepted packet -> online (:860-864)
   zone timer        :922-945   every > 2 s: each bot gets the OTHER bot's bounding box, or the lift
                                box (999, 999, -999, -999) when the other is offline
+  target timer      :947-996   every > 3 s: the online bots, ascending id, are given the nearest frontier
+                               centroid not taken and not within FRONTIER_SEPARATION of an earlier target, sent
+                               as TARG (:691-699).  Commented out in the reference as shipped, so opt-in here
+                               (frontier_targets=True); the mapper then also needs assign_frontier_targets.
 Differences: the reference throttles itself to 20 packets per 30 fps frame (:816, :474); here a
 poll drains the socket (up to max_batch datagrams).  Host-side Python only; the mapper can be any
 object with ingest_array / last_batch / zone_packet (tests use a stub, production the HIP mapper).
@@ -23,8 +27,10 @@ SLOT = 48      # bytes per datagram slot handed to qs_ingest (42-byte packets, r
 
 
 class MissionControl:
-    def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2):
+    def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
+                 frontier_targets=False):
         self.mapper = mapper
+        self.frontier_targets = frontier_targets
         self.max_agent = max_agent
         self.max_batch = max_batch
         if sock is None:
@@ -42,6 +48,8 @@ class MissionControl:
         self.seen = {b: False for b in bots}
         self.zone_boxes = {b: None for b in bots}                                     # :773
         self.last_zone_send = time.time()                                             # :788
+        self.bot_pose = {b: None for b in bots}      # bot_states[b]['x'], ['y']: last accepted pose (:850-866)
+        self.last_target_send = time.time()
         self._buf = np.zeros((max_batch, SLOT), dtype=np.uint8)
         self._lens = np.zeros(max_batch, dtype=np.uint16)
         self._times = np.zeros(max_batch, dtype=np.float64)
@@ -69,7 +77,8 @@ class MissionControl:
             return 0
         self.datagrams += n
         self.mapper.ingest_array(self._buf[:n], self._lens[:n], self._times[:n])
-        accepted, _ = self.mapper.last_batch()
+        accepted, pose = self.mapper.last_batch()
+        keep_pose = self.frontier_targets and pose is not None
         agents = self._buf[:n, 4]
         for i in np.nonzero(accepted)[0]:
             a = int(agents[i])
@@ -78,6 +87,8 @@ class MissionControl:
             self.pkt_counts[a] += 1                                                   # :848
             self.online[a] = True                                                     # :860-864
             self.seen[a] = True
+            if keep_pose:
+                self.bot_pose[a] = (float(pose[i, 0]), float(pose[i, 1]))
         return n
 
     # ---- :805-812 --------------------------------------------------------------------------------
@@ -118,12 +129,36 @@ class MissionControl:
             sent[bot_id] = pkt
         return sent
 
+    # ---- :947-996 (the assignment and send the reference ships commented out) --------------------------------------
+    def target_tick(self, now=None, force=False):
+        """Every > TARGET_INTERVAL s: assign frontier targets to the online bots and send each assigned bot TARG
+        (to its address if known).  Returns {bot: datagram} of the assigned bots."""
+        now = time.time() if now is None else now
+        if not force and not (now - self.last_target_send > P.TARGET_INTERVAL):
+            return {}
+        self.last_target_send = now
+        states = {b: self.bot_pose[b] for b in sorted(self.online) if self.online[b] and self.bot_pose[b] is not None}
+        if not states:
+            return {}
+        sent = {}
+        for bot_id, (tx, ty) in sorted(self.mapper.assign_frontier_targets(states).items()):
+            pkt = P.pack_target(tx, ty)
+            if self.bot_addrs[bot_id] is not None:                                    # send_target_to_bot :693-694
+                try:
+                    self.sock.sendto(pkt, self.bot_addrs[bot_id])
+                except OSError:
+                    pass
+            sent[bot_id] = pkt
+        return sent
+
     def step(self, now=None):
         """One iteration of the reference's while-loop body (without events and rendering)."""
         now = time.time() if now is None else now
         self.heartbeat(now)
         n = self.poll(now)
         self.zone_tick(now)
+        if self.frontier_targets:
+            self.target_tick(now)
         return n
 
     def run(self, duration, idle_sleep=0.001):

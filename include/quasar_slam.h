@@ -291,6 +291,20 @@ int qs_frontier_clusters(qs_ctx *ctx, int32_t min_cluster, int64_t *stats5, size
  * its 4-connected cluster; 3 values per cell: gx, gy, root.  xy_root == NULL queries the count. */
 int qs_frontier_members(qs_ctx *ctx, int32_t *xy_root, size_t cap, size_t *n_out);
 
+/* frontier target assignment: dual_bot_mapper.py:947-996 (commented out in the reference),
+ * consumed by AgentFirmware_Bot1.ino:81-137.  bot_xy: n_bots positions in greedy order.
+ * target_idx[b] = index into the min_cluster-filtered cluster list (qs_frontier_clusters order) or -1;
+ * target_xy[b] = its centroid (untouched when -1).  centroids_xy (optional, cap entries) and
+ * *n_centroids report the centroid list.  stats (optional): n_centroids, K, fallback scans, reserved.
+ * Each bot in turn takes the centroid nearest to it (sqrt of dx*dx + dy*dy, fp64; ties to the lower index) among
+ * those no earlier bot took and none of whose distances to an earlier target is below `separation`; a bot whose
+ * position is NaN or infinite gets -1.  n_bots <= QS_FT_MAX_BOTS; n_bots == 0 and a map without clusters are valid.
+ * Observes the map (flushes waiting exact-trig rays first).  Bad arguments: QS_E_INVAL. */
+#define QS_FT_MAX_BOTS 1024
+int qs_frontier_targets(qs_ctx *ctx, int32_t min_cluster, double separation,
+                        const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
+                        double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[4]);
+
 /* ---- EKF  AgentFirmware_Bot1/ekf.cpp:5-92 ---------------------------------------------- */
 /* On ingest (qs_config.enable_ekf) the filter of every bot runs over the batch: batches of >= 4096
  * packets in a parallel-in-time form that agrees with the step-by-step filter to rounding (~1e-12

@@ -835,19 +835,12 @@ size_t qs_ekf_scan_workspace_bytes(const qs_ctx *c, size_t n)
 hipError_t qs_launch_ekf_scan(qs_ctx *c, size_t n, const double *d_time, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const size_t need = qs_ekf_scan_workspace_bytes(c, c->cap_batch);
-    if (need > c->ekf_ws_bytes) {
-        hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return e;
-        if (c->d_ekf_ws) { hipFree(c->d_ekf_ws); c->d_ekf_ws = nullptr; c->ekf_ws_bytes = 0; }
-        e = hipMalloc(&c->d_ekf_ws, need);
-        if (e != hipSuccess) return e;
-        c->ekf_ws_bytes = need;
-    }
+    hipError_t e = c->ekf_ws.reserve(qs_ekf_scan_workspace_bytes(c, c->cap_batch), st);
+    if (e != hipSuccess) return e;
     const size_t cap = c->cap_batch, ch = es_max_chunks(c, cap);
     EsWs ws;
     ws.chunk = es_chunk_for(c, n);
-    char *p = (char *)c->d_ekf_ws;
+    char *p = c->ekf_ws.p;
     ws.count = (unsigned int *)p; p += es_align(256 * 4);
     ws.cmax = (unsigned long long *)p; p += es_align(ch * 8);           // adjacent to count: one memset clears both
     ws.base = (unsigned int *)p; p += es_align(257 * 4);
@@ -860,7 +853,7 @@ hipError_t qs_launch_ekf_scan(qs_ctx *c, size_t n, const double *d_time, hipStre
     ws.start = (EsStart *)p; p += es_align(ch * sizeof(EsStart));
     ws.agg2 = (EsAgg2 *)p; p += es_align(ch * sizeof(EsAgg2));
     ws.fin = (double *)p;
-    hipError_t e = hipMemsetAsync(ws.count, 0, es_align(256 * 4) + es_align(ch * 8), st);
+    e = hipMemsetAsync(ws.count, 0, es_align(256 * 4) + es_align(ch * 8), st);
     if (e != hipSuccess) return e;
     const int ma = c->cfg.max_agent;
     const double t0 = (double)c->next_seq;

@@ -10,9 +10,6 @@
 #include "qs_internal.h"
 
 static thread_local std::string g_create_err;
-static hipStream_t g_masked[64] = {};       // per device: the CU-masked stream its contexts' filters run on (ingest_device)
-static int g_masked_users[64] = {};
-static std::mutex g_masked_mutex;           // (contexts are independent: two threads may create / destroy theirs at the same time)
 static void chain_stats_poll(qs_ctx *c, bool synced, const unsigned int *fresh);
 static int flush_edge_rays(qs_ctx *c);      // exact-trig mode: rays waiting for libm end points (defined with the ingest path)
 #define FLUSHCHK(c) do { int rcf__ = flush_edge_rays(c); if (rcf__ != QS_OK) return rcf__; } while (0)
@@ -27,6 +24,16 @@ static int qs_fail(qs_ctx *c, int code, const char *what, hipError_t e = hipSucc
 }
 #define HIPCHK(c, x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return qs_fail((c), QS_E_HIP, #x, e__); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return qs_fail((c), QS_E_INVAL, "invalid argument: " #cond); } while (0)
+#define HIPRET(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)     // (helpers that return hipError_t)
+
+struct ScopedEvent {                        // an event of one call, destroyed with its scope (as DevBuf frees a buffer)
+    hipEvent_t e = nullptr;
+    ScopedEvent() = default;
+    ScopedEvent(const ScopedEvent &) = delete;
+    ScopedEvent &operator=(const ScopedEvent &) = delete;
+    ~ScopedEvent() { if (e) hipEventDestroy(e); }
+};
+static const size_t QS_IO_WS_FLOOR = (size_t)1 << 16;      // qs_ctx::io_ws doubles from 64 KiB
 
 template <typename T>
 static hipError_t dev_realloc(T **p, size_t count)
@@ -75,20 +82,17 @@ static void graph_free(QsGraphDev &g)
     memset(&g, 0, sizeof g);
 }
 
+// a graph array grown to new_cap, its first old_n entries kept; on failure the old array stays as it was
 template <typename T>
 static hipError_t grow_array(T **p, long long old_n, long long new_cap, hipStream_t st)
 {
-    T *q = nullptr;
-    hipError_t e = hipMalloc((void **)&q, (size_t)new_cap * sizeof(T));
-    if (e != hipSuccess) return e;
+    DevBuf<T> q;
+    HIPRET(q.alloc((size_t)new_cap));
     if (*p && old_n > 0) {
-        e = hipMemcpyAsync(q, *p, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return e;
+        HIPRET(hipMemcpyAsync(q.p, *p, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        HIPRET(hipStreamSynchronize(st));
     }
-    if (*p) hipFree(*p);
-    *p = q;
+    std::swap(*p, q.p);                      // (q takes the old array with it)
     return hipSuccess;
 }
 
@@ -97,24 +101,20 @@ static hipError_t grow_array(T **p, long long old_n, long long new_cap, hipStrea
 static hipError_t grow_pool(qs_ctx *c, QsGraphDev &G, long long old_cap, long long new_cap)
 {
     const size_t fixed = 1 + c->dir_entries, n_new = fixed + (size_t)new_cap, n_old = fixed + (size_t)old_cap;
-    QsLmNode *nodes = nullptr; unsigned int *next = nullptr, *misc = nullptr;
-    hipError_t e = hipMalloc((void **)&nodes, n_new * sizeof(QsLmNode));
-    if (e == hipSuccess) e = hipMalloc((void **)&next, n_new * sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMalloc((void **)&misc, (size_t)new_cap * sizeof(unsigned int));
-    if (e == hipSuccess && G.nodes) {
-        e = hipMemsetAsync(nodes + n_old, 0x7f, (n_new - n_old) * sizeof(QsLmNode), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(next + n_old, 0, (n_new - n_old) * sizeof(unsigned int), c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nodes, G.nodes, n_old * sizeof(QsLmNode), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(next, G.nd_next, n_old * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess && old_cap > 0) e = hipMemcpyAsync(misc, G.misc, (size_t)old_cap * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream);
-    } else if (e == hipSuccess) {
-        e = hipMemsetAsync(nodes, 0x7f, n_new * sizeof(QsLmNode), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(next, 0, n_new * sizeof(unsigned int), c->stream);
+    const size_t keep = G.nodes ? n_old : 0;            // nodes and links copied over; the rest start empty
+    DevBuf<QsLmNode> nodes; DevBuf<unsigned int> next, misc;
+    HIPRET(nodes.alloc(n_new));
+    HIPRET(next.alloc(n_new));
+    HIPRET(misc.alloc((size_t)new_cap));
+    HIPRET(hipMemsetAsync(nodes.p + keep, 0x7f, (n_new - keep) * sizeof(QsLmNode), c->stream));
+    HIPRET(hipMemsetAsync(next.p + keep, 0, (n_new - keep) * sizeof(unsigned int), c->stream));
+    if (G.nodes) {
+        HIPRET(hipMemcpyAsync(nodes.p, G.nodes, n_old * sizeof(QsLmNode), hipMemcpyDeviceToDevice, c->stream));
+        HIPRET(hipMemcpyAsync(next.p, G.nd_next, n_old * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+        if (old_cap > 0) HIPRET(hipMemcpyAsync(misc.p, G.misc, (size_t)old_cap * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { hipFree(nodes); hipFree(next); hipFree(misc); return e; }
-    hipFree(G.nodes); hipFree(G.nd_next); hipFree(G.misc);
-    G.nodes = nodes; G.nd_next = next; G.misc = misc;
+    HIPRET(hipStreamSynchronize(c->stream));
+    std::swap(G.nodes, nodes.p); std::swap(G.nd_next, next.p); std::swap(G.misc, misc.p);   // (the old blocks go with the scope)
     G.node_cap = (long long)n_new;
     return hipSuccess;
 }
@@ -125,7 +125,7 @@ static int graph_reserve(qs_ctx *c, int g, long long need_lms, long long need_cl
     QsGraphDev &G = c->h_graphs[g];
     bool changed = false;
     if (!G.dir) {
-        HIPCHK(c, hipMalloc((void **)&G.dir, c->dir_entries * sizeof(QsDirEntry)));
+        HIPCHK(c, dev_realloc(&G.dir, c->dir_entries));
         HIPCHK(c, hipMemsetAsync(G.dir, 0, c->dir_entries * sizeof(QsDirEntry), c->stream));
         changed = true;
     }
@@ -263,6 +263,67 @@ extern "C" int qs_create(const qs_config *cfg, qs_ctx **out)
     return QS_OK;
 }
 
+// The filter's stream keeps off the lowest 32 CUs.  Its kernels run beside the loop-closure chain, whose workgroups
+// (one per pose graph, each a whole CU's worth of latency-bound waves) lose ~10 % when scan kernels share their
+// SIMDs; with 32 CUs left alone the dispatcher puts the chain there (64 bots / 32 graphs: chain 1.26 -> 1.15 ms,
+// step 1.89 -> 1.80 ms; tools/ekf_cu_mask_probe.sh).  QS_EKF_CU_MASK = hex words (lowest CUs first) overrides,
+// "none" switches the mask off; a device too small for it, or a refusal, falls back to an ordinary stream.
+// ONE masked stream per device, shared by its contexts (the last one destroys it): a second CU-masked queue on the same GPU
+// slows every kernel of the process by 30-50 % (measured: two contexts, each with its own masked stream, 1.81 ->
+// 2.79 ms per 64-bot step; tools/secondary_probe.py).  Contexts of one process then run their filters one after
+// the other, which is how they are driven anyway (a caller serialises the calls on a context).
+static hipStream_t g_masked[64] = {};       // per device: the CU-masked stream its contexts' filters run on
+static int g_masked_users[64] = {};
+static std::mutex g_masked_mutex;           // (contexts are independent: two threads may create / destroy theirs at the same time)
+
+static int ekf_stream_acquire(qs_ctx *c)
+{
+    const char *mk = getenv("QS_EKF_CU_MASK");
+    std::vector<uint32_t> words;
+    if (mk && *mk && strcmp(mk, "none") != 0) {
+        char *end = nullptr;
+        for (const char *q = mk; *q;) { words.push_back((uint32_t)strtoul(q, &end, 16)); if (end == q) break; q = (*end == ',') ? end + 1 : end; }
+    } else if (!mk || !*mk) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount >= 128) {
+            words.assign((size_t)(prop.multiProcessorCount + 31) / 32, 0xffffffffu);
+            words[0] = 0u;
+        }
+    }
+    if (!words.empty() && c->device < 64) {
+        std::lock_guard<std::mutex> lk(g_masked_mutex);
+        if (!g_masked[c->device] && hipExtStreamCreateWithCUMask(&g_masked[c->device], (uint32_t)words.size(), words.data()) != hipSuccess) {
+            (void)hipGetLastError();
+            g_masked[c->device] = nullptr;
+        }
+        c->ekf_stream = g_masked[c->device];
+        c->ekf_stream_shared = c->ekf_stream != nullptr;
+        if (c->ekf_stream_shared) g_masked_users[c->device]++;
+    }
+    if (!c->ekf_stream)
+        HIPCHK(c, hipStreamCreateWithFlags(&c->ekf_stream, hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_decoded, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_ekf_done, hipEventDisableTiming));
+    return QS_OK;
+}
+
+static void ekf_stream_release(qs_ctx *c)
+{
+    if (c->ekf_stream) {
+        hipStreamSynchronize(c->ekf_stream);
+        if (!c->ekf_stream_shared) hipStreamDestroy(c->ekf_stream);
+        else if (c->device < 64) {
+            std::lock_guard<std::mutex> lk(g_masked_mutex);
+            if (--g_masked_users[c->device] == 0) {                          // the last context of the device takes the shared stream with it
+                hipStreamDestroy(g_masked[c->device]);                       // (a profiler's exit handler trips over a CU-masked queue left behind)
+                g_masked[c->device] = nullptr;
+            }
+        }
+    }
+    if (c->ev_decoded) hipEventDestroy(c->ev_decoded);
+    if (c->ev_ekf_done) hipEventDestroy(c->ev_ekf_done);
+}
+
 static void free_batch(qs_ctx *c)
 {
     QsBatch &b = c->b;
@@ -285,29 +346,16 @@ extern "C" int qs_destroy(qs_ctx *c)
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto &g : c->h_graphs) graph_free(g);
     free_batch(c);
-    hipFree(c->d_stamps); hipFree(c->d_counts); hipFree(c->d_counts_fused); hipFree(c->d_io_ws); hipFree(c->d_offset); hipFree(c->d_drift);
+    hipFree(c->d_stamps); hipFree(c->d_counts); hipFree(c->d_counts_fused); hipFree(c->d_offset); hipFree(c->d_drift);
     hipFree(c->d_last_closure); hipFree(c->d_zone); hipFree(c->d_counters); hipFree(c->d_graph_batch);
-    hipFree(c->d_ekf); hipFree(c->d_ekf_prev); hipFree(c->d_ekf_ws); hipFree(c->d_graphs); hipFree(c->d_flags); if (c->h_chain_stat) hipHostFree(c->h_chain_stat); if (c->ev_chain_stat) hipEventDestroy(c->ev_chain_stat); hipFree(c->d_pkts); hipFree(c->d_lens);
-    hipFree(c->d_time); hipFree(c->d_bin_ws); hipFree(c->d_frontier_ws); hipFree(c->d_ft_ws);
-    hipFree(c->d_edge);
-    hipFree(c->d_dirty); hipFree(c->d_counts_sent); hipFree(c->d_sf_bitmaps); hipFree(c->d_sf_lists); hipFree(c->d_sf_counts); hipFree(c->d_sf_payload);
+    hipFree(c->d_ekf); hipFree(c->d_ekf_prev); hipFree(c->d_graphs); hipFree(c->d_flags); if (c->h_chain_stat) hipHostFree(c->h_chain_stat); if (c->ev_chain_stat) hipEventDestroy(c->ev_chain_stat); hipFree(c->d_pkts); hipFree(c->d_lens);
+    hipFree(c->d_time); hipFree(c->d_edge);
+    hipFree(c->d_dirty); hipFree(c->d_counts_sent); hipFree(c->d_sf_bitmaps); hipFree(c->d_sf_lists); hipFree(c->d_sf_counts);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->ev_pool) hipEventDestroy(e);
-    if (c->ekf_stream) {
-        hipStreamSynchronize(c->ekf_stream);
-        if (!c->ekf_stream_shared) hipStreamDestroy(c->ekf_stream);
-        else if (c->device < 64) {
-            std::lock_guard<std::mutex> lk(g_masked_mutex);
-            if (--g_masked_users[c->device] == 0) {                          // the last context of the device takes the shared stream with it
-                hipStreamDestroy(g_masked[c->device]);                       // (a profiler's exit handler trips over a CU-masked queue left behind)
-                g_masked[c->device] = nullptr;
-            }
-        }
-    }
-    if (c->ev_decoded) hipEventDestroy(c->ev_decoded);
-    if (c->ev_ekf_done) hipEventDestroy(c->ev_ekf_done);
+    ekf_stream_release(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                      // (the workspaces free themselves)
     return QS_OK;
 }
 
@@ -399,20 +447,21 @@ static int ensure_batch(qs_ctx *c, size_t n)
     size_t cap = c->cap_batch ? c->cap_batch : 1024;
     while (cap < n) cap *= 2;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cap_batch = 0;                                        // (until every array below exists)
     QsBatch &b = c->b;
+    if (b.map_ok == b.accept) b.map_ok = nullptr;            // an alias of accept, not an array of its own
     HIPCHK(c, dev_realloc(&b.accept, cap)); HIPCHK(c, dev_realloc(&b.agent, cap)); HIPCHK(c, dev_realloc(&b.lm, cap));
     HIPCHK(c, dev_realloc(&b.px, cap)); HIPCHK(c, dev_realloc(&b.py, cap)); HIPCHK(c, dev_realloc(&b.yaw, cap));
     HIPCHK(c, dev_realloc(&b.dist, cap)); HIPCHK(c, dev_realloc(&b.enc, cap));
     HIPCHK(c, dev_realloc(&b.rx, cap)); HIPCHK(c, dev_realloc(&b.ry, cap));
     HIPCHK(c, dev_realloc(&b.hit, 4 * cap)); HIPCHK(c, dev_realloc(&b.hit_valid, 4 * cap));
     if (c->cfg.shard_bots > 0) {
-        if (b.map_ok == b.accept) b.map_ok = nullptr;        // (accept was re-allocated above)
         HIPCHK(c, dev_realloc(&b.map_ok, cap));
         b.own_lo = c->cfg.shard_rank * c->cfg.shard_bots + 1;
         b.own_hi = std::min(c->cfg.max_agent, (c->cfg.shard_rank + 1) * c->cfg.shard_bots);
     } else { b.map_ok = b.accept; b.own_lo = 1; b.own_hi = c->cfg.max_agent; }
     if (c->cfg.exact_trig) {
-        if (!c->d_edge) HIPCHK(c, hipMalloc((void **)&c->d_edge, (size_t)QS_EDGE_CAP * sizeof(QsEdgeRec)));
+        if (!c->d_edge) HIPCHK(c, dev_realloc(&c->d_edge, (size_t)QS_EDGE_CAP));
         b.edge = c->d_edge; b.edge_n = c->d_flags; b.edge_cap = QS_EDGE_CAP;
     }
     QsSlamBatch &sb = c->sb;
@@ -522,7 +571,6 @@ static int reserve_graphs_for_batch(qs_ctx *c, size_t n)
     return QS_OK;
 }
 
-static int io_reserve(qs_ctx *c, size_t bytes);
 // Exact-trig mode (qs_config.exact_trig, default on): rays the device did not decide (raycast_common.h, qs_edge_ray) wait in
 // a list of self-contained records (pose, distance, stamp) and get their end points from libm here -- math.cos / math.sin of
 // the reference are glibc's -- before they are cast with the stamps their ingest gave them (stamps make the order
@@ -585,9 +633,8 @@ static int flush_edge_rays(qs_ctx *c)
     std::vector<QsEdgeRec> recs(n_edge);
     HIPCHK(c, hipMemcpy(recs.data(), c->d_edge, (size_t)n_edge * sizeof(QsEdgeRec), hipMemcpyDeviceToHost));
     const size_t bytes = (size_t)n_edge * 4 * sizeof(double);
-    int rc = io_reserve(c, bytes);
-    if (rc != QS_OK) return rc;
-    double *d = (double *)c->d_io_ws;
+    HIPCHK(c, c->io_ws.reserve(bytes, c->stream, QS_IO_WS_FLOOR));
+    double *d = (double *)c->io_ws.p;
     std::vector<double> h((size_t)n_edge * 4);
     static const double kPi = 3.141592653589793;                                              // math.pi
     static const double off[4] = {0.0, kPi / 2, kPi, -kPi / 2};                               // :61-66
@@ -638,43 +685,7 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
     if (rc != QS_OK) return rc;
     if (c->cfg.enable_ekf) {
         // fork: the filter only needs the decoded fields, never the map (and the map never the filter)
-        if (!c->ekf_stream) {
-            // The filter's stream keeps off the lowest 32 CUs.  Its kernels run beside the loop-closure chain, whose workgroups
-            // (one per pose graph, each a whole CU's worth of latency-bound waves) lose ~10 % when scan kernels share their
-            // SIMDs; with 32 CUs left alone the dispatcher puts the chain there (64 bots / 32 graphs: chain 1.26 -> 1.15 ms,
-            // step 1.89 -> 1.80 ms; tools/ekf_cu_mask_probe.sh).  QS_EKF_CU_MASK = hex words (lowest CUs first) overrides,
-            // "none" switches the mask off; a device too small for it, or a refusal, falls back to an ordinary stream.
-            const char *mk = getenv("QS_EKF_CU_MASK");
-            std::vector<uint32_t> words;
-            if (mk && *mk && strcmp(mk, "none") != 0) {
-                char *end = nullptr;
-                for (const char *q = mk; *q;) { words.push_back((uint32_t)strtoul(q, &end, 16)); if (end == q) break; q = (*end == ',') ? end + 1 : end; }
-            } else if (!mk || !*mk) {
-                hipDeviceProp_t prop;
-                if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount >= 128) {
-                    words.assign((size_t)(prop.multiProcessorCount + 31) / 32, 0xffffffffu);
-                    words[0] = 0u;
-                }
-            }
-            // ONE masked stream per device, shared by its contexts (the last one destroys it): a second CU-masked queue on the same GPU
-            // slows every kernel of the process by 30-50 % (measured: two contexts, each with its own masked stream, 1.81 ->
-            // 2.79 ms per 64-bot step; tools/secondary_probe.py).  Contexts of one process then run their filters one after
-            // the other, which is how they are driven anyway (a caller serialises the calls on a context).
-            if (!words.empty() && c->device < 64) {
-                std::lock_guard<std::mutex> lk(g_masked_mutex);
-                if (!g_masked[c->device] && hipExtStreamCreateWithCUMask(&g_masked[c->device], (uint32_t)words.size(), words.data()) != hipSuccess) {
-                    (void)hipGetLastError();
-                    g_masked[c->device] = nullptr;
-                }
-                c->ekf_stream = g_masked[c->device];
-                c->ekf_stream_shared = c->ekf_stream != nullptr;
-                if (c->ekf_stream_shared) g_masked_users[c->device]++;
-            }
-            if (!c->ekf_stream)
-                HIPCHK(c, hipStreamCreateWithFlags(&c->ekf_stream, hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_decoded, hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_ekf_done, hipEventDisableTiming));
-        }
+        if (!c->ekf_stream) { int rce = ekf_stream_acquire(c); if (rce != QS_OK) return rce; }
         HIPCHK(c, hipEventRecord(c->ev_decoded, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->ekf_stream, c->ev_decoded, 0));
         { StageTimer t(c, QS_STAGE_EKF, c->ekf_stream); HIPCHK(c, n >= QS_EKF_SCAN_MIN_BATCH ? qs_launch_ekf_scan(c, n, d_time, c->ekf_stream)
@@ -722,6 +733,7 @@ extern "C" int qs_ingest(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride
         size_t cap = c->cap_pkts_bytes ? c->cap_pkts_bytes : (1u << 16);
         while (cap < bytes) cap *= 2;
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->cap_pkts_bytes = 0;                               // (until all three exist)
         HIPCHK(c, dev_realloc(&c->d_pkts, cap));
         HIPCHK(c, dev_realloc(&c->d_lens, cap / QS_PACKET_SIZE_V1 + 1));
         HIPCHK(c, dev_realloc(&c->d_time, cap / QS_PACKET_SIZE_V1 + 1));
@@ -781,18 +793,6 @@ extern "C" int qs_last_hits(qs_ctx *c, double *xy, uint8_t *valid, size_t n)
 }
 
 // ---- OccupancyGrid object API ---------------------------------------------------------------
-static int io_reserve(qs_ctx *c, size_t bytes)
-{
-    if (bytes <= c->io_ws_bytes) return QS_OK;
-    size_t cap = c->io_ws_bytes ? c->io_ws_bytes : (1u << 16);
-    while (cap < bytes) cap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_io_ws) { HIPCHK(c, hipFree(c->d_io_ws)); c->d_io_ws = nullptr; c->io_ws_bytes = 0; }
-    HIPCHK(c, hipMalloc(&c->d_io_ws, cap));
-    c->io_ws_bytes = cap;
-    return QS_OK;
-}
-
 extern "C" int qs_update_rays(qs_ctx *c, const double *rx, const double *ry, const double *hx, const double *hy,
                               const uint8_t *valid, size_t n, uint64_t seq0)
 {
@@ -805,17 +805,14 @@ extern "C" int qs_update_rays(qs_ctx *c, const double *rx, const double *ry, con
     int rc = ensure_epoch(c, seq0, n_seq);
     if (rc != QS_OK) return rc;
     // staging lives with the context (grown on demand): the object API's update_ray is one ray per call
-    int rc2 = io_reserve(c, 4 * n * sizeof(double) + n);
-    if (rc2 != QS_OK) return rc2;
-    double *d = (double *)c->d_io_ws; unsigned char *dv = (unsigned char *)(d + 4 * n);
-    hipError_t e = hipSuccess;
+    HIPCHK(c, c->io_ws.reserve(4 * n * sizeof(double) + n, c->stream, QS_IO_WS_FLOOR));
+    double *d = (double *)c->io_ws.p; unsigned char *dv = (unsigned char *)(d + 4 * n);
     const double *src[4] = {rx, ry, hx, hy};
-    for (int q = 0; q < 4 && e == hipSuccess; q++)
-        e = hipMemcpyAsync(d + q * n, src[q], n * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_update_rays(c, d, d + n, d + 2 * n, d + 3 * n, dv, n, seq0);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_update_rays", e);
+    for (int q = 0; q < 4; q++)
+        HIPCHK(c, hipMemcpyAsync(d + q * n, src[q], n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_update_rays(c, d, d + n, d + 2 * n, d + 3 * n, dv, n, seq0));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dirty_since_fuse = true;
     c->next_seq = seq0 + n_seq;
     c->last_has_poses = false;
@@ -828,15 +825,13 @@ extern "C" int qs_world_to_grid(qs_ctx *c, const double *w, size_t n, int32_t ax
     if (n == 0) return QS_OK;
     ARGCHK(c, w && out);
     HIPCHK(c, hipSetDevice(c->device));
-    double *d = nullptr; long long *o = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d, n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void **)&o, n * sizeof(long long)));
-    hipError_t e = hipMemcpyAsync(d, w, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_world_to_grid(c, d, n, axis, o);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, o, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d); hipFree(o);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_world_to_grid", e);
+    DevBuf<double> d; DevBuf<long long> o;
+    HIPCHK(c, d.alloc(n));
+    HIPCHK(c, o.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(d.p, w, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_world_to_grid(c, d.p, n, axis, o.p));
+    HIPCHK(c, hipMemcpyAsync(out, o.p, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 
@@ -854,13 +849,11 @@ extern "C" int qs_grid_i8(qs_ctx *c, int8_t *out_host)
     ARGCHK(c, c != nullptr && out_host != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    signed char *d = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d, c->cells));
-    hipError_t e = qs_launch_view_i8(c, d);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, d, c->cells, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_grid_i8", e);
+    DevBuf<signed char> d;
+    HIPCHK(c, d.alloc(c->cells));
+    HIPCHK(c, qs_launch_view_i8(c, d.p));
+    HIPCHK(c, hipMemcpyAsync(out_host, d.p, c->cells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 
@@ -870,14 +863,12 @@ extern "C" int qs_grid_counts(qs_ctx *c, int32_t *hits_host, int32_t *misses_hos
     if (!c->d_counts) return qs_fail(c, QS_E_INVAL, "qs_grid_counts: context created with enable_counts = 0");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    int *d = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d, 2 * c->cells * sizeof(int)));
-    hipError_t e = qs_launch_split_counts(c, d, d + c->cells);
-    if (e == hipSuccess) e = hipMemcpyAsync(hits_host, d, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(misses_host, d + c->cells, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_grid_counts", e);
+    DevBuf<int> d;
+    HIPCHK(c, d.alloc(2 * c->cells));
+    HIPCHK(c, qs_launch_split_counts(c, d.p, d.p + c->cells));
+    HIPCHK(c, hipMemcpyAsync(hits_host, d.p, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(misses_host, d.p + c->cells, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 
@@ -887,13 +878,11 @@ extern "C" int qs_grid_logodds(qs_ctx *c, float l_occ, float l_free, float lmin,
     if (!c->d_counts) return qs_fail(c, QS_E_INVAL, "qs_grid_logodds: context created with enable_counts = 0");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    float *d = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d, c->cells * sizeof(float)));
-    hipError_t e = qs_launch_logodds(c, l_occ, l_free, lmin, lmax, d);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, d, c->cells * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_grid_logodds", e);
+    DevBuf<float> d;
+    HIPCHK(c, d.alloc(c->cells));
+    HIPCHK(c, qs_launch_logodds(c, l_occ, l_free, lmin, lmax, d.p));
+    HIPCHK(c, hipMemcpyAsync(out_host, d.p, c->cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 
@@ -1127,7 +1116,7 @@ extern "C" int qs_fused_counts(qs_ctx *c, void **fused_dev, size_t *bytes)
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     const size_t nb = c->cells * sizeof(unsigned long long);
-    if (!c->d_counts_fused) HIPCHK(c, hipMalloc((void **)&c->d_counts_fused, nb));
+    if (!c->d_counts_fused) HIPCHK(c, dev_realloc(&c->d_counts_fused, c->cells));
     HIPCHK(c, hipMemcpyAsync(c->d_counts_fused, c->d_counts, nb, hipMemcpyDeviceToDevice, c->stream));
     *fused_dev = c->d_counts_fused;
     if (bytes) *bytes = nb;
@@ -1157,7 +1146,8 @@ extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!enable) {
-        hipFree(c->d_dirty); c->d_dirty = nullptr; c->geom.dirty = nullptr; c->geom.dirty_pitch = 0;
+        c->geom.dirty = nullptr; c->geom.dirty_pitch = 0;
+        (void)dev_realloc(&c->d_dirty, 0);
         c->sf_state = 0;
         c->counts_view_fused = false;         // the fused counters stop following the ranks: the views read the own ones
         return QS_OK;
@@ -1168,18 +1158,19 @@ extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
     c->blocks_y = (c->cfg.size + QS_DIRTY_BLOCK_H - 1) / QS_DIRTY_BLOCK_H;
     const int pitch = (c->blocks_x + 31) / 32;
     c->dirty_words = (size_t)c->blocks_y * pitch;
-    HIPCHK(c, hipMalloc((void **)&c->d_dirty, c->dirty_words * sizeof(unsigned int)));
-    HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, c->dirty_words * sizeof(unsigned int), c->stream));
     if (c->d_counts) {
         const size_t nb = c->cells * sizeof(unsigned long long);
-        if (!c->d_counts_sent) HIPCHK(c, hipMalloc((void **)&c->d_counts_sent, nb));
+        if (!c->d_counts_sent) HIPCHK(c, dev_realloc(&c->d_counts_sent, c->cells));
         // the fused counters accumulate deltas from here on: they start as "nothing sent", the local counters as all delta
         HIPCHK(c, hipMemsetAsync(c->d_counts_sent, 0, nb, c->stream));
-        if (!c->d_counts_fused) HIPCHK(c, hipMalloc((void **)&c->d_counts_fused, nb));
+        if (!c->d_counts_fused) HIPCHK(c, dev_realloc(&c->d_counts_fused, c->cells));
         HIPCHK(c, hipMemsetAsync(c->d_counts_fused, 0, nb, c->stream));
         // counters written before tracking was switched on have no dirty bit: everything is marked once
     }
+    // the bitmap last, published with geom.dirty: tracking is on (d_dirty set) only once everything it writes exists
+    HIPCHK(c, dev_realloc(&c->d_dirty, c->dirty_words));
     c->geom.dirty = c->d_dirty; c->geom.dirty_pitch = pitch;
+    HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, c->dirty_words * sizeof(unsigned int), c->stream));
     if (c->next_seq != 0) HIPCHK(c, qs_launch_sf_mark_range(c, 0, c->cells));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
@@ -1191,11 +1182,10 @@ extern "C" int qs_dirty_blocks(qs_ctx *c, size_t *n_blocks, size_t *block_cells)
     if (!c->d_dirty) return qs_fail(c, QS_E_STATE, "qs_dirty_blocks: dirty tracking is off (qs_dirty_tracking)");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    int rc = io_reserve(c, sizeof(unsigned long long));
-    if (rc != QS_OK) return rc;
+    HIPCHK(c, c->io_ws.reserve(sizeof(unsigned long long), c->stream, QS_IO_WS_FLOOR));
     unsigned long long v = 0;
-    HIPCHK(c, qs_launch_sf_popcount(c, (unsigned long long *)c->d_io_ws));
-    HIPCHK(c, hipMemcpyAsync(&v, c->d_io_ws, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, qs_launch_sf_popcount(c, (unsigned long long *)c->io_ws.p));
+    HIPCHK(c, hipMemcpyAsync(&v, c->io_ws.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_blocks = (size_t)v;
     if (block_cells) *block_cells = (size_t)QS_DIRTY_BLOCK_W * QS_DIRTY_BLOCK_H;
@@ -1215,6 +1205,7 @@ extern "C" int qs_sparse_fuse_begin(qs_ctx *c, int32_t world, int32_t rank, void
     if (c->sf_state != 0) HIPCHK(c, qs_launch_sf_restore(c));
     if (world != c->sf_world) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->sf_world = 0; c->sf_state = 0;                    // (until all three exist; a fuse in flight was restored above)
         HIPCHK(c, dev_realloc(&c->d_sf_bitmaps, (size_t)world * c->dirty_words));
         HIPCHK(c, dev_realloc(&c->d_sf_lists, (size_t)world * c->dirty_words * 32));
         HIPCHK(c, dev_realloc(&c->d_sf_counts, (size_t)world));
@@ -1242,14 +1233,9 @@ extern "C" int qs_sparse_fuse_plan(qs_ctx *c, uint32_t *n_blocks, size_t *offset
     size_t run = 0;
     for (int s = 0; s < c->sf_world; s++) { c->sf_off[s] = run; run += (size_t)c->sf_n[s] * bb; n_blocks[s] = c->sf_n[s]; offsets[s] = c->sf_off[s]; }
     c->sf_off[c->sf_world] = run; offsets[c->sf_world] = run;
-    if (run > c->sf_payload_bytes) {
-        size_t cap = c->sf_payload_bytes ? c->sf_payload_bytes : ((size_t)1 << 20);
-        while (cap < run) cap *= 2;
-        HIPCHK(c, dev_realloc(&c->d_sf_payload, cap));
-        c->sf_payload_bytes = cap;
-    }
-    HIPCHK(c, qs_launch_sf_pack(c, c->sf_n[c->sf_rank], c->d_sf_payload + c->sf_off[c->sf_rank]));
-    *payload_dev = c->d_sf_payload;
+    HIPCHK(c, c->sf_payload.reserve(run, c->stream, (size_t)1 << 20));        // doubling from 1 MiB
+    HIPCHK(c, qs_launch_sf_pack(c, c->sf_n[c->sf_rank], c->sf_payload.p + c->sf_off[c->sf_rank]));
+    *payload_dev = c->sf_payload.p;
     if (block_bytes) *block_bytes = bb;
     c->sf_state = 2;
     return QS_OK;
@@ -1298,25 +1284,22 @@ extern "C" int qs_grid_to_pcd(qs_ctx *c, const int8_t *grid, int32_t h, int32_t 
     ARGCHK(c, c != nullptr && grid != nullptr && n_out != nullptr && h > 0 && w > 0);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)h * w, n_chunks = (cells + 1023) / 1024;
-    signed char *dg = nullptr; unsigned int *dchunk = nullptr; unsigned long long *dcount = nullptr; double *dxy = nullptr;
-    hipError_t e = hipMalloc((void **)&dg, cells);
-    if (e == hipSuccess) e = hipMalloc((void **)&dchunk, n_chunks * sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMalloc((void **)&dcount, sizeof(unsigned long long));
+    DevBuf<signed char> dg; DevBuf<unsigned int> dchunk; DevBuf<unsigned long long> dcount; DevBuf<double> dxy;
+    HIPCHK(c, dg.alloc(cells));
+    HIPCHK(c, dchunk.alloc(n_chunks));
+    HIPCHK(c, dcount.alloc(1));
     unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(dg, grid, cells, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_grid_to_pcd(c, dg, h, w, res, ox, oy, nullptr, 0, dcount, dchunk);
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, dcount, sizeof total, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHK(c, hipMemcpyAsync(dg.p, grid, cells, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_grid_to_pcd(c, dg.p, h, w, res, ox, oy, nullptr, 0, dcount.p, dchunk.p));
+    HIPCHK(c, hipMemcpyAsync(&total, dcount.p, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_out = (size_t)total;
-    if (e == hipSuccess && xy && total > 0) {
-        const size_t m = total < cap ? (size_t)total : cap;
-        e = hipMalloc((void **)&dxy, 2 * (size_t)total * sizeof(double));
-        if (e == hipSuccess) e = qs_launch_grid_to_pcd(c, dg, h, w, res, ox, oy, dxy, (size_t)total, dcount, dchunk);
-        if (e == hipSuccess) e = hipMemcpyAsync(xy, dxy, 2 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    hipFree(dg); hipFree(dchunk); hipFree(dcount); hipFree(dxy);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_grid_to_pcd", e);
+    if (!xy || total == 0) return QS_OK;
+    const size_t m = total < cap ? (size_t)total : cap;
+    HIPCHK(c, dxy.alloc(2 * (size_t)total));
+    HIPCHK(c, qs_launch_grid_to_pcd(c, dg.p, h, w, res, ox, oy, dxy.p, (size_t)total, dcount.p, dchunk.p));
+    HIPCHK(c, hipMemcpyAsync(xy, dxy.p, 2 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 
@@ -1326,46 +1309,36 @@ extern "C" int qs_rasterise(qs_ctx *c, const double *xy, size_t n, double res, i
     if (n == 0) { dims[0] = dims[1] = 0; return QS_OK; }      // publish_global_map returns early  :88-93
     ARGCHK(c, xy != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
-    double *dxy = nullptr; unsigned long long *dbox = nullptr; signed char *dg = nullptr;
+    DevBuf<double> dxy; DevBuf<unsigned long long> dbox; DevBuf<signed char> dg;
     unsigned long long box[4] = {QS_ORD_MIN_IDENT, QS_ORD_MIN_IDENT, QS_ORD_MAX_IDENT, QS_ORD_MAX_IDENT};
-    hipError_t e = hipMalloc((void **)&dxy, 2 * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&dbox, sizeof box);
-    if (e == hipSuccess) e = hipMemcpyAsync(dxy, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbox, box, sizeof box, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_bbox(c, dxy, n, dbox);
-    if (e == hipSuccess) e = hipMemcpyAsync(box, dbox, sizeof box, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    int rc = QS_OK;
-    if (e == hipSuccess) {
-        const double mnx = qs_double_from_ord(box[0]), mny = qs_double_from_ord(box[1]);
-        const double mxx = qs_double_from_ord(box[2]), mxy = qs_double_from_ord(box[3]);
-        const double wd = ceil((mxx - mnx) / res), hd = ceil((mxy - mny) / res);     // :103-104
-        if (!(wd >= 0 && wd < 65536 && hd >= 0 && hd < 65536)) rc = qs_fail(c, QS_E_RANGE, "qs_rasterise: canvas too large");
-        else {
-            const int w = (int)wd + 1, h = (int)hd + 1;
-            dims[0] = h; dims[1] = w; origin[0] = mnx; origin[1] = mny;
-            if (grid) {
-                e = hipMalloc((void **)&dg, (size_t)h * w);
-                if (e == hipSuccess) e = qs_launch_rasterise(c, dxy, n, res, mnx, mny, h, w, dg);
-                if (e == hipSuccess) e = hipMemcpyAsync(grid, dg, (size_t)h * w, hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            }
-        }
-    }
-    hipFree(dxy); hipFree(dbox); hipFree(dg);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_rasterise", e);
-    return rc;
+    HIPCHK(c, dxy.alloc(2 * n));
+    HIPCHK(c, dbox.alloc(4));
+    HIPCHK(c, hipMemcpyAsync(dxy.p, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dbox.p, box, sizeof box, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_bbox(c, dxy.p, n, dbox.p));
+    HIPCHK(c, hipMemcpyAsync(box, dbox.p, sizeof box, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double mnx = qs_double_from_ord(box[0]), mny = qs_double_from_ord(box[1]);
+    const double mxx = qs_double_from_ord(box[2]), mxy = qs_double_from_ord(box[3]);
+    const double wd = ceil((mxx - mnx) / res), hd = ceil((mxy - mny) / res);     // :103-104
+    if (!(wd >= 0 && wd < 65536 && hd >= 0 && hd < 65536)) return qs_fail(c, QS_E_RANGE, "qs_rasterise: canvas too large");
+    const int w = (int)wd + 1, h = (int)hd + 1;
+    dims[0] = h; dims[1] = w; origin[0] = mnx; origin[1] = mny;
+    if (!grid) return QS_OK;
+    HIPCHK(c, dg.alloc((size_t)h * w));
+    HIPCHK(c, qs_launch_rasterise(c, dxy.p, n, res, mnx, mny, h, w, dg.p));
+    HIPCHK(c, hipMemcpyAsync(grid, dg.p, (size_t)h * w, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
 }
 
 // ---- ICP / voxel down-sample (map_merger.py:45-60; Open3D semantics, parity unpinned) ------------------
 // The correspondence search (nearest target of every source point) has two implementations with identical results:
 // the scalar fp64 brute force and the MFMA-screened one (icp.hip).  mode 0 = auto (MFMA from 64 targets up).
-struct NnPlan { double cx, cy, t2max; size_t n_pad; double *planes; bool mfma; int *part_j; double *part_d2, *thr_seed; };
-static void nn_free(NnPlan &pl) { hipFree(pl.planes); hipFree(pl.part_j); hipFree(pl.part_d2); hipFree(pl.thr_seed); pl.planes = nullptr; }
+struct NnPlan { double cx = 0, cy = 0, t2max = 0; size_t n_pad = 0; bool mfma = false; DevBuf<double> planes, part_d2, thr_seed; DevBuf<int> part_j; };
 
 static hipError_t nn_prepare(qs_ctx *c, const double *dst_xy, size_t n_dst, const double2 *d_dst, int mode, NnPlan &pl, size_t n_src)
 {
-    pl = NnPlan{0, 0, 0, 0, nullptr, false, nullptr, nullptr, nullptr};
     pl.mfma = mode == 2 || (mode == 0 && n_dst >= 64);
     if (!pl.mfma) return hipSuccess;
     double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
@@ -1378,22 +1351,21 @@ static hipError_t nn_prepare(qs_ctx *c, const double *dst_xy, size_t n_dst, cons
     const double hx = isfinite(mnx) ? mxx - pl.cx : 0.0, hy = isfinite(mny) ? mxy - pl.cy : 0.0;
     pl.t2max = 1.0001 * (hx * hx + hy * hy) + 1e-300;          // >= every finite target's centred squared norm
     pl.n_pad = (n_dst + 15) / 16 * 16;
-    hipError_t e = hipMalloc((void **)&pl.planes, 3 * pl.n_pad * sizeof(double));
-    if (e == hipSuccess) e = qs_launch_icp_prep(c, d_dst, n_dst, pl.n_pad, pl.cx, pl.cy, pl.planes);
+    HIPRET(pl.planes.alloc(3 * pl.n_pad));
+    HIPRET(qs_launch_icp_prep(c, d_dst, n_dst, pl.n_pad, pl.cx, pl.cy, pl.planes.p));
     // per-part results and the sources' threshold seeds (the targets are cut into parts: icp.hip)
     unsigned int groups, parts, cpp;
     qs_icp_nn_plan(n_src, pl.n_pad, &groups, &parts, &cpp);
-    if (e == hipSuccess) e = hipMalloc((void **)&pl.part_j, (size_t)parts * n_src * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&pl.part_d2, (size_t)parts * n_src * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&pl.thr_seed, n_src * sizeof(double));
-    return e;
+    HIPRET(pl.part_j.alloc((size_t)parts * n_src));
+    HIPRET(pl.part_d2.alloc((size_t)parts * n_src));
+    return pl.thr_seed.alloc(n_src);
 }
 
 static hipError_t nn_run(qs_ctx *c, const NnPlan &pl, const double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst,
                          double max_d2, int *d_corr, double *d_d2)
 {
-    if (pl.mfma) return qs_launch_icp_nn_mfma(c, d_src, n_src, d_dst, n_dst, pl.planes, pl.n_pad, pl.cx, pl.cy, pl.t2max, max_d2, d_corr, d_d2,
-                                              pl.part_j, pl.part_d2, pl.thr_seed);
+    if (pl.mfma) return qs_launch_icp_nn_mfma(c, d_src, n_src, d_dst, n_dst, pl.planes.p, pl.n_pad, pl.cx, pl.cy, pl.t2max, max_d2, d_corr, d_d2,
+                                              pl.part_j.p, pl.part_d2.p, pl.thr_seed.p);
     return qs_launch_icp_nn(c, d_src, n_src, d_dst, n_dst, max_d2, d_corr, d_d2);
 }
 
@@ -1407,30 +1379,27 @@ extern "C" int qs_nn_search(qs_ctx *c, const double *src_xy, size_t n_src, const
     ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && mode >= 0 && mode <= 2);
     ARGCHK(c, n_dst < (size_t)1 << 31);
     HIPCHK(c, hipSetDevice(c->device));
-    double2 *d_src = nullptr, *d_dst = nullptr; int *d_corr = nullptr; double *d_d2 = nullptr;
-    NnPlan pl{};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipMalloc((void **)&d_src, n_src * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_dst, n_dst * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_corr, n_src * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_d2, n_src * sizeof(double));
-    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_src, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_dst, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess) e = nn_prepare(c, dst_xy, n_dst, d_dst, mode, pl, n_src);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-    if (e == hipSuccess) e = nn_run(c, pl, d_src, n_src, d_dst, n_dst, max_dist * max_dist, d_corr, d_d2);      // warm (code load, caches)
-    if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
-    if (e == hipSuccess) e = nn_run(c, pl, d_src, n_src, d_dst, n_dst, max_dist * max_dist, d_corr, d_d2);
-    if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(corr, d_corr, n_src * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d2, d_d2, n_src * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && ms) { hipEventElapsedTime(&ms[0], ev[2], ev[3]); hipEventElapsedTime(&ms[1], ev[0], ev[1]); }
-    for (int k = 0; k < 4; k++) if (ev[k]) hipEventDestroy(ev[k]);
-    hipFree(d_src); hipFree(d_dst); hipFree(d_corr); hipFree(d_d2); nn_free(pl);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_nn_search", e);
+    DevBuf<double2> d_src, d_dst; DevBuf<int> d_corr; DevBuf<double> d_d2;
+    NnPlan pl;
+    ScopedEvent ev[4];
+    HIPCHK(c, d_src.alloc(n_src));
+    HIPCHK(c, d_dst.alloc(n_dst));
+    HIPCHK(c, d_corr.alloc(n_src));
+    HIPCHK(c, d_d2.alloc(n_src));
+    for (auto &v : ev) HIPCHK(c, hipEventCreate(&v.e));
+    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(ev[0].e, c->stream));
+    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, mode, pl, n_src));
+    HIPCHK(c, hipEventRecord(ev[1].e, c->stream));
+    HIPCHK(c, nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));      // warm (code load, caches)
+    HIPCHK(c, hipEventRecord(ev[2].e, c->stream));
+    HIPCHK(c, nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
+    HIPCHK(c, hipEventRecord(ev[3].e, c->stream));
+    HIPCHK(c, hipMemcpyAsync(corr, d_corr.p, n_src * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d2, d_d2.p, n_src * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ms) { hipEventElapsedTime(&ms[0], ev[2].e, ev[3].e); hipEventElapsedTime(&ms[1], ev[0].e, ev[1].e); }
     return QS_OK;
 }
 
@@ -1442,42 +1411,41 @@ extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const doubl
     ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && max_iter >= 0);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nb = (n_src + 255) / 256;
-    double2 *d_src = nullptr, *d_dst = nullptr; int *d_corr = nullptr; double *d_d2 = nullptr, *d_part = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_src, n_src * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_dst, n_dst * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_corr, n_src * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_d2, n_src * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_part, nb * 6 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 6 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_src, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_dst, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream);
-    NnPlan pl{};
-    if (e == hipSuccess) e = nn_prepare(c, dst_xy, n_dst, d_dst, 0, pl, n_src);     // the targets do not move: operands once per registration
+    DevBuf<double2> d_src, d_dst; DevBuf<int> d_corr; DevBuf<double> d_d2, d_part, d_out;
+    HIPCHK(c, d_src.alloc(n_src));
+    HIPCHK(c, d_dst.alloc(n_dst));
+    HIPCHK(c, d_corr.alloc(n_src));
+    HIPCHK(c, d_d2.alloc(n_src));
+    HIPCHK(c, d_part.alloc(nb * 6));
+    HIPCHK(c, d_out.alloc(6));
+    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    NnPlan pl;
+    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, 0, pl, n_src));     // the targets do not move: operands once per registration
     double tc = 1.0, ts = 0.0, tx = 0.0, ty = 0.0;          // accumulated transform
     double out[6] = {0};
     const double zero4[4] = {0, 0, 0, 0};
     auto evaluate = [&](double &fit, double &rm) -> hipError_t {
-        hipError_t ee = nn_run(c, pl, d_src, n_src, d_dst, n_dst, max_dist * max_dist, d_corr, d_d2);
-        if (ee == hipSuccess) ee = qs_launch_icp_sums(c, d_src, n_src, d_dst, d_corr, d_d2, 0, zero4, d_part, d_out);
-        if (ee == hipSuccess) ee = hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, c->stream);
-        if (ee == hipSuccess) ee = hipStreamSynchronize(c->stream);
+        HIPRET(nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
+        HIPRET(qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 0, zero4, d_part.p, d_out.p));
+        HIPRET(hipMemcpyAsync(out, d_out.p, sizeof out, hipMemcpyDeviceToHost, c->stream));
+        HIPRET(hipStreamSynchronize(c->stream));
         fit = out[0] / (double)n_src;
         rm = out[0] > 0 ? sqrt(out[1] / out[0]) : 0.0;
-        return ee;
+        return hipSuccess;
     };
     double fit = 0, rm = 0;
     int it = 0;
-    if (e == hipSuccess) e = evaluate(fit, rm);
-    for (; e == hipSuccess && it < max_iter; it++) {
+    HIPCHK(c, evaluate(fit, rm));
+    for (; it < max_iter; it++) {
         double uc = 1.0, us = 0.0, ux = 0.0, uy = 0.0;       // ComputeTransformation: identity without correspondences
         if (out[0] > 0) {
             const double nn = out[0];
             const double means[4] = {out[2] / nn, out[3] / nn, out[4] / nn, out[5] / nn};
             double o2[6];
-            e = qs_launch_icp_sums(c, d_src, n_src, d_dst, d_corr, d_d2, 1, means, d_part, d_out);
-            if (e == hipSuccess) e = hipMemcpyAsync(o2, d_out, sizeof o2, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) break;
+            HIPCHK(c, qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 1, means, d_part.p, d_out.p));
+            HIPCHK(c, hipMemcpyAsync(o2, d_out.p, sizeof o2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
             const double theta = atan2(o2[1], o2[0]);
             uc = cos(theta); us = sin(theta);
             ux = means[2] - (uc * means[0] - us * means[1]);
@@ -1487,13 +1455,11 @@ extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const doubl
         const double nc = uc * tc - us * ts, ns = us * tc + uc * ts;
         const double nx = uc * tx - us * ty + ux, ny = us * tx + uc * ty + uy;
         tc = nc; ts = ns; tx = nx; ty = ny;
-        e = qs_launch_icp_transform(c, d_src, n_src, uc, us, ux, uy);
+        HIPCHK(c, qs_launch_icp_transform(c, d_src.p, n_src, uc, us, ux, uy));
         const double bfit = fit, brm = rm;
-        if (e == hipSuccess) e = evaluate(fit, rm);
-        if (e == hipSuccess && fabs(bfit - fit) < rel_fitness && fabs(brm - rm) < rel_rmse) { it++; break; }
+        HIPCHK(c, evaluate(fit, rm));
+        if (fabs(bfit - fit) < rel_fitness && fabs(brm - rm) < rel_rmse) { it++; break; }
     }
-    hipFree(d_src); hipFree(d_dst); hipFree(d_corr); hipFree(d_d2); hipFree(d_part); hipFree(d_out); nn_free(pl);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_icp", e);
     T[0] = tc; T[1] = -ts; T[2] = tx; T[3] = ts; T[4] = tc; T[5] = ty; T[6] = 0; T[7] = 0; T[8] = 1;
     *fitness = fit; *rmse = rm;
     if (iters) *iters = it;
@@ -1505,23 +1471,19 @@ extern "C" int qs_diag_mfma_f64_rate(qs_ctx *c, double *tflops)
 {
     ARGCHK(c, c != nullptr && tflops != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
-    double *sink = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
+    DevBuf<double> sink;
+    ScopedEvent a, b;
     const int blocks = 256 * 2, iters = 20000;             // 2 workgroups of 4 waves per CU
-    hipError_t e = hipMalloc((void **)&sink, 8);
-    if (e == hipSuccess) e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = qs_launch_mfma_f64_rate(c, blocks, 1000, sink);
-    if (e == hipSuccess) e = hipEventRecord(a, c->stream);
-    if (e == hipSuccess) e = qs_launch_mfma_f64_rate(c, blocks, iters, sink);
-    if (e == hipSuccess) e = hipEventRecord(b, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHK(c, sink.alloc(1));
+    HIPCHK(c, hipEventCreate(&a.e));
+    HIPCHK(c, hipEventCreate(&b.e));
+    HIPCHK(c, qs_launch_mfma_f64_rate(c, blocks, 1000, sink.p));
+    HIPCHK(c, hipEventRecord(a.e, c->stream));
+    HIPCHK(c, qs_launch_mfma_f64_rate(c, blocks, iters, sink.p));
+    HIPCHK(c, hipEventRecord(b.e, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-    if (a) hipEventDestroy(a);
-    if (b) hipEventDestroy(b);
-    hipFree(sink);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_diag_mfma_f64_rate", e);
+    HIPCHK(c, hipEventElapsedTime(&ms, a.e, b.e));
     const double flops = (double)blocks * 4 /* waves */ * iters * 4 /* MFMAs */ * (2.0 * 16 * 16 * 4);
     *tflops = flops / (ms * 1e-3) / 1e12;
     return QS_OK;
@@ -1536,20 +1498,18 @@ extern "C" int qs_diag_latencies(qs_ctx *c, double out[QS_DIAG_LAT_N])
     std::vector<unsigned int> h2(n2), h1(n1);
     for (unsigned int k = 0; k < n2; k++) h2[k] = (k * 1664525u + 1013904223u) & (n2 - 1);     // full-period LCG: one cycle through all entries
     for (unsigned int k = 0; k < n1; k++) h1[k] = (k * 1664525u + 1013904223u) & (n1 - 1);
-    unsigned int *d2 = nullptr, *d1 = nullptr; double *d_out = nullptr;
+    DevBuf<unsigned int> d2, d1; DevBuf<double> d_out;
     double h_out[16] = {0};
-    hipError_t e = hipMalloc((void **)&d2, n2 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d1, n1 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof h_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(d2, h2.data(), n2 * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d1, h1.data(), n1 * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof h_out, c->stream);
-    if (e == hipSuccess) e = qs_launch_diag_latencies(c, d2, d1, d_out);          // (warm: code load)
-    if (e == hipSuccess) e = qs_launch_diag_latencies(c, d2, d1, d_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d2); hipFree(d1); hipFree(d_out);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_diag_latencies", e);
+    HIPCHK(c, d2.alloc(n2));
+    HIPCHK(c, d1.alloc(n1));
+    HIPCHK(c, d_out.alloc(16));
+    HIPCHK(c, hipMemcpyAsync(d2.p, h2.data(), n2 * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d1.p, h1.data(), n1 * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_out.p, 0, sizeof h_out, c->stream));
+    HIPCHK(c, qs_launch_diag_latencies(c, d2.p, d1.p, d_out.p));          // (warm: code load)
+    HIPCHK(c, qs_launch_diag_latencies(c, d2.p, d1.p, d_out.p));
+    HIPCHK(c, hipMemcpyAsync(h_out, d_out.p, sizeof h_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < QS_DIAG_LAT_N; i++) out[i] = h_out[i];
     return QS_OK;
 }
@@ -1564,16 +1524,16 @@ extern "C" int qs_voxel_downsample(qs_ctx *c, const double *xy, size_t n, double
     double mnx = xy[0], mny = xy[1];
     for (size_t i = 1; i < n; i++) { if (xy[2 * i] < mnx) mnx = xy[2 * i]; if (xy[2 * i + 1] < mny) mny = xy[2 * i + 1]; }
     mnx -= voxel * 0.5; mny -= voxel * 0.5;                 // voxel_min_bound = min_bound - voxel_size / 2
-    double2 *d = nullptr; unsigned long long *dk = nullptr;
     std::vector<unsigned long long> keys(n);
-    hipError_t e = hipMalloc((void **)&d, n * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void **)&dk, n * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpyAsync(d, xy, n * sizeof(double2), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_voxel_keys(c, d, n, mnx, mny, voxel, dk);
-    if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), dk, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d); hipFree(dk);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_voxel_downsample", e);
+    {
+        DevBuf<double2> d; DevBuf<unsigned long long> dk;
+        HIPCHK(c, d.alloc(n));
+        HIPCHK(c, dk.alloc(n));
+        HIPCHK(c, hipMemcpyAsync(d.p, xy, n * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, qs_launch_voxel_keys(c, d.p, n, mnx, mny, voxel, dk.p));
+        HIPCHK(c, hipMemcpyAsync(keys.data(), dk.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     // group by voxel (ascending key), average in input order: a handful of points per ROS callback
     std::vector<size_t> order(n);
     for (size_t i = 0; i < n; i++) order[i] = i;
@@ -1595,50 +1555,34 @@ static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, i
     ARGCHK(c, c != nullptr && n_out != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    if (!c->d_frontier_ws) HIPCHK(c, hipMalloc(&c->d_frontier_ws, qs_frontier_workspace_bytes(c)));
-    void *ws = c->d_frontier_ws;
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_workspace_bytes(c), c->stream));
+    void *ws = c->frontier_ws.p;
     HIPCHK(c, qs_launch_frontier_label(c, ws, mode != 0));
     HIPCHK(c, qs_launch_frontier_compact(c, ws, mode == 2 ? 0 : mode, 0, nullptr, nullptr, 0));
     unsigned long long total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_total_ptr(c, ws), sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (mode == 0) {
+    if (mode != 1) {
+        // cells (mode 0: gx, gy), or every frontier cell with the first cell (row-major) of its 4-connected cluster (mode 2:
+        // gx, gy, root linear index)
         *n_out = (size_t)total;
         if (!xy || total == 0) return QS_OK;
-        int *d = nullptr;
-        HIPCHK(c, hipMalloc((void **)&d, 2 * (size_t)total * sizeof(int)));
-        hipError_t e = qs_launch_frontier_compact(c, ws, 0, 1, d, nullptr, (size_t)total);
-        const size_t m = total < cap ? (size_t)total : cap;
-        if (e == hipSuccess) e = hipMemcpyAsync(xy, d, 2 * m * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        hipFree(d);
-        if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_frontier_cells", e);
-        return QS_OK;
-    }
-    if (mode == 2) {
-        // every frontier cell with the first cell (row-major) of its 4-connected cluster: gx, gy, root linear index
-        *n_out = (size_t)total;
-        if (!xy || total == 0) return QS_OK;
-        int *d = nullptr;
-        HIPCHK(c, hipMalloc((void **)&d, 3 * (size_t)total * sizeof(int)));
-        hipError_t e = qs_launch_frontier_compact(c, ws, 2, 1, d, nullptr, (size_t)total);
-        const size_t m = total < cap ? (size_t)total : cap;
-        if (e == hipSuccess) e = hipMemcpyAsync(xy, d, 3 * m * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        hipFree(d);
-        if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_frontier_members", e);
+        const size_t per = mode == 0 ? 2 : 3, m = total < cap ? (size_t)total : cap;
+        DevBuf<int> d;
+        HIPCHK(c, d.alloc(per * (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, mode, 1, d.p, nullptr, (size_t)total));
+        HIPCHK(c, hipMemcpyAsync(xy, d.p, per * m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         return QS_OK;
     }
     // clusters: all components come back in first-cell order; the size filter keeps that order (:228-229)
     std::vector<long long> all(5 * (size_t)total);
     if (total) {
-        long long *d = nullptr;
-        HIPCHK(c, hipMalloc((void **)&d, 5 * (size_t)total * sizeof(long long)));
-        hipError_t e = qs_launch_frontier_compact(c, ws, 1, 1, nullptr, d, (size_t)total);
-        if (e == hipSuccess) e = hipMemcpyAsync(all.data(), d, all.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        hipFree(d);
-        if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_frontier_clusters", e);
+        DevBuf<long long> d;
+        HIPCHK(c, d.alloc(5 * (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, 1, 1, nullptr, d.p, (size_t)total));
+        HIPCHK(c, hipMemcpyAsync(all.data(), d.p, all.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     size_t k = 0;
     for (size_t i = 0; i < (size_t)total; i++) {
@@ -1671,21 +1615,17 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
     ARGCHK(c, cap == 0 || centroids_xy);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    if (!c->d_frontier_ws) HIPCHK(c, hipMalloc(&c->d_frontier_ws, qs_frontier_workspace_bytes(c)));
-    void *fws = c->d_frontier_ws;
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_workspace_bytes(c), c->stream));
+    void *fws = c->frontier_ws.p;
     HIPCHK(c, qs_launch_frontier_label(c, fws, true));
     HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
     unsigned long long total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_total_ptr(c, fws), sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n_cent = (size_t)total;
-    const size_t need = qs_ft_workspace_bytes(n_cent, n_bots);
-    if (need > c->ft_ws_bytes) {
-        HIPCHK(c, dev_realloc((char **)&c->d_ft_ws, need));
-        c->ft_ws_bytes = need;
-    }
+    HIPCHK(c, c->ft_ws.reserve(qs_ft_workspace_bytes(n_cent, n_bots), c->stream));
     QsFtState *d_st; double2 *d_cent, *d_bots, *d_txy; long long *d_tidx;
-    qs_ft_parts(c->d_ft_ws, n_cent, n_bots, &d_st, &d_cent, &d_bots, &d_tidx, &d_txy);
+    qs_ft_parts(c->ft_ws.p, n_cent, n_bots, &d_st, &d_cent, &d_bots, &d_tidx, &d_txy);
     HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, d_cent));
     uint64_t fallbacks = 0;
     std::vector<long long> tidx(n_bots, -1);
@@ -1695,7 +1635,7 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
         HIPCHK(c, hipMemcpyAsync(d_bots, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
         int start = 0, m = 0, pending = 0;
         for (;;) {
-            HIPCHK(c, qs_launch_ft_assign(c, c->d_ft_ws, n_cent, n_bots, r2_sep, start, m, pending));
+            HIPCHK(c, qs_launch_ft_assign(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m, pending));
             QsFtState st;
             HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1704,7 +1644,7 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
                 return qs_fail(c, QS_E_HIP, "qs_frontier_targets: greedy pass made no progress");
             fallbacks++;
             start = st.next_bot; m = st.m; pending = 1;
-            HIPCHK(c, qs_launch_ft_fallback(c, c->d_ft_ws, n_cent, n_bots, r2_sep, start, m));
+            HIPCHK(c, qs_launch_ft_fallback(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m));
         }
         HIPCHK(c, hipMemcpyAsync(tidx.data(), d_tidx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(txy.data(), d_txy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
@@ -1742,18 +1682,18 @@ extern "C" int qs_ekf_step(qs_ctx *c, const int32_t *bot_ids, const double *omeg
     if (n == 0) return QS_OK;
     ARGCHK(c, bot_ids && omega_m && t && (!do_update || (z_v && z_omega)));
     HIPCHK(c, hipSetDevice(c->device));
-    int *db = nullptr; double *dd = nullptr;
-    hipError_t e = hipMalloc((void **)&db, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&dd, 4 * n * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(db, bot_ids, n * sizeof(int), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dd, omega_m, n * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dd + n, t, n * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && do_update) e = hipMemcpyAsync(dd + 2 * n, z_v, n * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && do_update) e = hipMemcpyAsync(dd + 3 * n, z_omega, n * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = qs_launch_ekf_step(c, db, dd, dd + n, dd + 2 * n, dd + 3 * n, n, do_update);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(db); hipFree(dd);
-    if (e != hipSuccess) return qs_fail(c, QS_E_HIP, "qs_ekf_step", e);
+    DevBuf<int> db; DevBuf<double> dd;
+    HIPCHK(c, db.alloc(n));
+    HIPCHK(c, dd.alloc(4 * n));
+    HIPCHK(c, hipMemcpyAsync(db.p, bot_ids, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd.p, omega_m, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd.p + n, t, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (do_update) {
+        HIPCHK(c, hipMemcpyAsync(dd.p + 2 * n, z_v, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dd.p + 3 * n, z_omega, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, qs_launch_ekf_step(c, db.p, dd.p, dd.p + n, dd.p + 2 * n, dd.p + 3 * n, n, do_update));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
 

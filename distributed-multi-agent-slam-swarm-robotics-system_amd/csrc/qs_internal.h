@@ -130,6 +130,39 @@ struct QsBatch {
     unsigned char *hit_valid; // MIN < d <= MAX per ray (:888); the tiled raycast writes it on the ingest path
 };
 
+// ---- owning device buffer of host code: freed when it goes out of scope ---------------------------
+// alloc: the scratch of one call, into an empty buffer.  reserve: the one way a grown workspace changes size -- exactly
+// `need` elements, or (floor > 0) floor doubled until it holds them.  The capacity is 0 from before the old block is freed
+// until the new one exists, so a failed growth leaves an empty buffer, never a capacity over a null pointer.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;      // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t n)
+    {
+        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = n;
+        return hipSuccess;
+    }
+    hipError_t reserve(size_t need, hipStream_t st, size_t floor = 0)
+    {
+        if (need <= cap) return hipSuccess;
+        size_t n = floor ? floor : need;
+        while (n < need) n *= 2;
+        hipError_t e = hipStreamSynchronize(st);          // (the old block may still be in use)
+        if (e != hipSuccess) return e;
+        cap = 0;
+        e = hipFree(p);
+        p = nullptr;
+        return e != hipSuccess ? e : alloc(n);
+    }
+};
+
 struct qs_ctx {
     qs_config cfg;
     int device = 0;
@@ -158,7 +191,7 @@ struct qs_ctx {
     unsigned int *d_sf_bitmaps = nullptr;        // [sf_world][dirty_words]: every rank's bitmap of the fuse in flight
     unsigned int *d_sf_lists = nullptr;          // [sf_world][dirty_words * 32] block ids, ascending
     unsigned int *d_sf_counts = nullptr;         // [sf_world] blocks per rank
-    unsigned char *d_sf_payload = nullptr; size_t sf_payload_bytes = 0;
+    DevBuf<unsigned char> sf_payload;            // every rank's segment of the fuse in flight, grown on demand
     std::vector<unsigned int> sf_n;              // host copy of d_sf_counts
     std::vector<size_t> sf_off;                  // [sf_world + 1] byte offsets of the ranks' segments in the payload
     int sf_state = 0;                            // 0 idle, 1 begun, 2 planned
@@ -187,12 +220,12 @@ struct qs_ctx {
     size_t last_n = 0;
     bool last_has_poses = false;
 
-    // tile-binned raycast workspace
-    void *d_bin_ws = nullptr; size_t bin_ws_bytes = 0;
-    void *d_frontier_ws = nullptr;               // frontier labelling workspace (allocated on first use)
-    void *d_ft_ws = nullptr; size_t ft_ws_bytes = 0;     // frontier target assignment (frontier_targets.hip), grown on demand
-    void *d_io_ws = nullptr; size_t io_ws_bytes = 0;     // staging of the object-API calls (qs_update_rays, views), grown on demand
-    void *d_ekf_ws = nullptr; size_t ekf_ws_bytes = 0;   // parallel-in-time EKF workspace (ekf_scan.hip)
+    // workspaces, grown on demand (DevBuf::reserve)
+    DevBuf<char> bin_ws;                         // tile-binned raycast (raycast_tiled.hip)
+    DevBuf<char> frontier_ws;                    // frontier labelling (allocated on first use)
+    DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
+    DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
+    DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
 
     uint64_t next_seq = 0, epoch_base = 0, n_rebases = 0;
     unsigned int *d_flags = nullptr;             // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)

@@ -505,15 +505,8 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
 {
     if (n == 0) return hipSuccess;
     if (!qs_tiled_supported(c)) return qs_launch_raycast_direct(c, n, seq0);
-    const size_t need = qs_tiled_workspace_bytes(c, c->cap_batch);
-    if (need > c->bin_ws_bytes) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return e;
-        if (c->d_bin_ws) { hipFree(c->d_bin_ws); c->d_bin_ws = nullptr; c->bin_ws_bytes = 0; }
-        e = hipMalloc(&c->d_bin_ws, need);
-        if (e != hipSuccess) return e;
-        c->bin_ws_bytes = need;
-    }
+    hipError_t e = c->bin_ws.reserve(qs_tiled_workspace_bytes(c, c->cap_batch), c->stream);
+    if (e != hipSuccess) return e;
     QtWorkspace ws;
     ws.tiles_x = (c->cfg.size + QT_TILE - 1) / QT_TILE;
     ws.n_tiles = ws.tiles_x * ws.tiles_x;
@@ -523,7 +516,7 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
     ws.pk_per_wg = per;
     ws.nwg = (int)((n + per - 1) / per);
     const size_t tbytes = qt_align(((size_t)ws.n_tiles + 1) * sizeof(unsigned int));
-    char *p = (char *)c->d_bin_ws;
+    char *p = c->bin_ws.p;
     ws.table = (unsigned int *)p; p += qt_align((size_t)QT_MAX_WG * ws.n_tiles * sizeof(unsigned int));
     ws.tile_count = (unsigned int *)p; p += tbytes;
     ws.tile_base = (unsigned int *)p; p += tbytes;

@@ -220,9 +220,9 @@ hipError_t qs_launch_sf_apply(qs_ctx *c)
     const unsigned int blocks = (run + 3) / 4 < 8192 ? (run + 3) / 4 : 8192;
     if (c->d_counts)
         hipLaunchKernelGGL(qs_sf_apply_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
+                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
     else
         hipLaunchKernelGGL(qs_sf_apply_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->d_sf_payload, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
+                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
     return hipGetLastError();
 }

@@ -79,6 +79,10 @@ SIGNATURES = {
     "qs_ingest": (_i32, [_vp, _vp, _sz, _sz, _vp, _vp, _u64]),
     "qs_ingest_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _vp, _u64]),
     "qs_last_batch": (_i32, [_vp, _vp, _vp, _sz]),
+    "qs_ingest_sweeps": (_i32, [_vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_ingest_sweeps_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_last_sweeps": (_i32, [_vp, _vp, _vp, _sz]),
+    "qs_set_sweep_filter": (_i32, [_vp, _f64, _f64]),
     "qs_last_hits": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),

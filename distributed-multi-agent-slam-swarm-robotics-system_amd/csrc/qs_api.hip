@@ -180,6 +180,7 @@ static int reset_state(qs_ctx *c)
     HIPCHK(c, qs_launch_slam_reset_index(c));
     for (int g = 0; g < c->n_graphs; g++) { c->lms_upper[g] = 0; c->cls_upper[g] = 0; }
     c->next_seq = 0; c->epoch_base = 0; c->last_n = 0; c->last_has_poses = false; c->n_rebases = 0; c->edge_rays_total = 0;
+    c->last_sweeps = false; c->last_sweeps_n = 0;
     c->pile_mode = false;
     c->edge_maybe = false; c->edge_overflow_total = 0;      // (rays still waiting belonged to the old session: the flags are cleared above)
     return QS_OK;
@@ -641,10 +642,13 @@ static int flush_edge_rays(qs_ctx *c)
     for (unsigned int e = 0; e < n_edge; e++) {
         const QsEdgeRec &r = recs[e];
         const double dd = (double)r.d;
+        const bool sweep = r.beam >= 0;                                                        // a servo-sweep beam (sweep.hip)
         const int sensor = (int)(((r.key_free >> 1) - 1) & 3);                                 // ordinal = 4 * arrival index + sensor + 1
-        const double a = r.yaw + off[sensor];                                                  // :887
-        const bool valid = (c->cfg.min_dist < dd) && (dd <= c->cfg.max_dist);                  // :888
-        const double range = valid ? dd : ((dd > c->cfg.min_dist) ? ((c->cfg.max_dist < dd) ? c->cfg.max_dist : dd) : c->cfg.max_dist);   // :900
+        const double a = sweep ? r.yaw + (double)(r.beam - 90) * (kPi / 180.0)                 // math.radians(i - 90)
+                               : r.yaw + off[sensor];                                          // :887
+        const double lo = sweep ? c->sweep_min : c->cfg.min_dist, hi = sweep ? c->sweep_max : c->cfg.max_dist;
+        const bool valid = (lo < dd) && (dd <= hi);                                            // :888
+        const double range = valid ? dd : ((dd > lo) ? ((hi < dd) ? hi : dd) : hi);            // :900
         h[4 * e] = r.rx + range * cos(a);                                                      // :890 / :901
         h[4 * e + 1] = r.ry + range * sin(a);                                                  // :891 / :902
         h[4 * e + 2] = valid ? 1.0 : 0.0;
@@ -669,7 +673,7 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
                          const double *d_time, uint64_t seq0)
 {
     if (seq0 == UINT64_MAX) seq0 = c->next_seq;
-    c->last_n = n; c->last_has_poses = true;
+    c->last_n = n; c->last_has_poses = true; c->last_sweeps = false;
     if (n == 0) return QS_OK;
     int rc = ensure_batch(c, n);
     if (rc != QS_OK) return rc;
@@ -721,6 +725,21 @@ extern "C" int qs_ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size
     return ingest_device(c, d_pkts, n, stride, d_lens, d_time, seq0);
 }
 
+// device staging of host-side records: bytes of records, one length and one receive time per (shortest) record
+static int reserve_staging(qs_ctx *c, size_t bytes)
+{
+    if (bytes <= c->cap_pkts_bytes) return QS_OK;
+    size_t cap = c->cap_pkts_bytes ? c->cap_pkts_bytes : (1u << 16);
+    while (cap < bytes) cap *= 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cap_pkts_bytes = 0;                               // (until all three exist)
+    HIPCHK(c, dev_realloc(&c->d_pkts, cap));
+    HIPCHK(c, dev_realloc(&c->d_lens, cap / QS_PACKET_SIZE_V1 + 1));
+    HIPCHK(c, dev_realloc(&c->d_time, cap / QS_PACKET_SIZE_V1 + 1));
+    c->cap_pkts_bytes = cap;
+    return QS_OK;
+}
+
 extern "C" int qs_ingest(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens,
                          const double *recv_time, uint64_t seq0)
 {
@@ -729,16 +748,7 @@ extern "C" int qs_ingest(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) { c->last_n = 0; return QS_OK; }
     const size_t bytes = n * stride;
-    if (bytes > c->cap_pkts_bytes) {
-        size_t cap = c->cap_pkts_bytes ? c->cap_pkts_bytes : (1u << 16);
-        while (cap < bytes) cap *= 2;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->cap_pkts_bytes = 0;                               // (until all three exist)
-        HIPCHK(c, dev_realloc(&c->d_pkts, cap));
-        HIPCHK(c, dev_realloc(&c->d_lens, cap / QS_PACKET_SIZE_V1 + 1));
-        HIPCHK(c, dev_realloc(&c->d_time, cap / QS_PACKET_SIZE_V1 + 1));
-        c->cap_pkts_bytes = cap;
-    }
+    { int rcs = reserve_staging(c, bytes); if (rcs != QS_OK) return rcs; }
     HIPCHK(c, hipMemcpyAsync(c->d_pkts, pkts, bytes, hipMemcpyHostToDevice, c->stream));
     if (lens) HIPCHK(c, hipMemcpyAsync(c->d_lens, lens, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     if (recv_time) HIPCHK(c, hipMemcpyAsync(c->d_time, recv_time, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -792,6 +802,117 @@ extern "C" int qs_last_hits(qs_ctx *c, double *xy, uint8_t *valid, size_t n)
     return QS_OK;
 }
 
+// ---- servo sweeps (sweep.hip; semantics in include/quasar_slam.h) ----------------------------------------------------------
+// Records per chunk: the tiled raycast's ray slots (8 B) and tile records (up to 4 x 8 B) of one chunk, 184 slots per
+// record, stay under 0.5 GiB; the host path stages one chunk's records at a time.
+static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
+
+static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
+{
+    if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
+        return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
+    if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
+        return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: sharded contexts (seq_stride > 1, shard_bots > 0) do not take sweeps");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (seq0 == UINT64_MAX) seq0 = c->next_seq;
+    c->last_n = 0; c->last_has_poses = false;              // qs_last_batch / qs_last_hits: length mismatch from here on
+    c->last_sweeps = false; c->last_sweeps_n = 0;
+    if (n == 0) return QS_OK;
+    int rc = ensure_batch(c, 1);                           // the exact-trig waiting list lives with the batch buffers
+    if (rc != QS_OK) return rc;
+    HIPCHK(c, c->sweep_acc.reserve(n, c->stream, 1024));
+    HIPCHK(c, c->sweep_pose.reserve(3 * n, c->stream, 3 * 1024));
+    HIPCHK(c, c->sweep_hv.reserve(QS_SWEEP_SLOTS * std::min(n, QS_SWEEP_CHUNK), c->stream));
+    return QS_OK;
+}
+
+// records [k0, k0 + m) of the call, at d_pkts (already offset to record k0)
+static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0)
+{
+    const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
+    int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
+    if (rc != QS_OK) return rc;
+    // auto: by ray slots, as the 4-ray path decides by its 4 rays per packet
+    const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
+    StageTimer t(c, QS_STAGE_RAYCAST);
+    HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p));
+    t.stop();
+    c->dirty_since_fuse = true;
+    return QS_OK;
+}
+
+static void sweeps_end(qs_ctx *c, size_t n, uint64_t seq0)
+{
+    if (c->b.edge) c->edge_maybe = true;                   // resolved at the next point the map is observed (flush_edge_rays)
+    c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
+    c->last_sweeps = true; c->last_sweeps_n = n;
+}
+
+extern "C" int qs_ingest_sweeps_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stride, const uint16_t *d_lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || d_pkts != nullptr);
+    int rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0);
+        if (rc != QS_OK) return rc;
+    }
+    sweeps_end(c, n, seq0);
+    return QS_OK;
+}
+
+extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || pkts != nullptr);
+    int rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+        rc = reserve_staging(c, m * stride);               // (stream-ordered: the previous chunk's kernels have read theirs)
+        if (rc != QS_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(c->d_lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        rc = sweeps_chunk(c, c->d_pkts, m, stride, lens ? c->d_lens : nullptr, seq0, k0);
+        if (rc != QS_OK) return rc;
+    }
+    sweeps_end(c, n, seq0);
+    // as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
+    return read_pile_flag(c);
+}
+
+extern "C" int qs_last_sweeps(qs_ctx *c, uint8_t *accepted, double *pose, size_t n)
+{
+    ARGCHK(c, c != nullptr);
+    if (!c->last_sweeps || n != c->last_sweeps_n) return qs_fail(c, QS_E_INVAL, "qs_last_sweeps: n does not match the last sweep ingest");
+    if (n == 0) return QS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint8_t> acc(n);
+    std::vector<double> p(pose ? 3 * n : 0);
+    HIPCHK(c, hipMemcpyAsync(acc.data(), c->sweep_acc.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (pose) HIPCHK(c, hipMemcpyAsync(p.data(), c->sweep_pose.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i++) {
+        if (accepted) accepted[i] = acc[i];
+        if (pose) for (int q = 0; q < 3; q++) pose[3 * i + q] = acc[i] ? p[3 * i + q] : NAN;
+    }
+    return QS_OK;
+}
+
+extern "C" int qs_set_sweep_filter(qs_ctx *c, double smin, double smax)
+{
+    ARGCHK(c, c != nullptr);
+    if (!(isfinite(smin) && isfinite(smax) && smin >= 0 && smin < smax))
+        return qs_fail(c, QS_E_INVAL, "qs_set_sweep_filter: need finite 0 <= smin < smax");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = flush_edge_rays(c);                           // waiting beams are resolved with the filter they were cast with
+    if (rc != QS_OK) return rc;
+    c->sweep_min = smin; c->sweep_max = smax;
+    return QS_OK;
+}
+
 // ---- OccupancyGrid object API ---------------------------------------------------------------
 extern "C" int qs_update_rays(qs_ctx *c, const double *rx, const double *ry, const double *hx, const double *hy,
                               const uint8_t *valid, size_t n, uint64_t seq0)
@@ -815,7 +936,7 @@ extern "C" int qs_update_rays(qs_ctx *c, const double *rx, const double *ry, con
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dirty_since_fuse = true;
     c->next_seq = seq0 + n_seq;
-    c->last_has_poses = false;
+    c->last_has_poses = false; c->last_sweeps = false;
     return QS_OK;
 }
 

@@ -106,7 +106,9 @@ enum { QS_FLAG_EDGE_N = 0,        // exact-trig mode: edge rays waiting for the 
        QS_FLAG_CHAINW_MISS = 6,   // per-window form: eligible queries that found nothing ...
        QS_FLAG_CHAINW_HIT = 7,    // ... and its closures
        QS_N_FLAGS = 8 };
-struct QsEdgeRec { double rx, ry, yaw; float d; unsigned int key_free; };     // key_free: stamp of its free cells ((ordinal << 1) | 0)
+// key_free: stamp of its free cells ((ordinal << 1) | 0); beam: -1 = one of a QuasarPacket's four rays (sensor = ordinal & 3),
+// 0..180 = beam of a servo sweep (angle yaw + (beam - 90) * pi / 180, trust filter qs_set_sweep_filter's)
+struct QsEdgeRec { double rx, ry, yaw; float d; unsigned int key_free; int beam, pad; };
 #define QS_EDGE_CAP (1u << 18)
 
 // ---- decoded batch (SoA, one slot per datagram of the batch) -----------------------------
@@ -226,6 +228,12 @@ struct qs_ctx {
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
+    DevBuf<unsigned char> sweep_hv;              // servo sweeps (sweep.hip): hit flags of one chunk's ray slots
+    DevBuf<unsigned char> sweep_acc;             //   ... accepted flag and pose of every record of the last call
+    DevBuf<double> sweep_pose;
+    double sweep_min = 0.1, sweep_max = 1.2;     //   trust filter smin < d <= smax (qs_set_sweep_filter)
+    size_t last_sweeps_n = 0;
+    bool last_sweeps = false;                    //   the last ingest was qs_ingest_sweeps*: qs_last_sweeps may read it
 
     uint64_t next_seq = 0, epoch_base = 0, n_rebases = 0;
     unsigned int *d_flags = nullptr;             // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)
@@ -291,6 +299,9 @@ hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axi
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
 size_t qs_tiled_workspace_bytes(const qs_ctx *c, size_t n);
 bool qs_tiled_supported(const qs_ctx *c);
+// sweep.hip: n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
+hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
+                            uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid);
 // grid_ops.hip
 hipError_t qs_launch_view_i8(qs_ctx *c, signed char *out_dev);
 hipError_t qs_launch_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_dev);

@@ -112,23 +112,8 @@ qs_update_rays_kernel(size_t n, const double *__restrict__ rx, const double *__r
     QsLine ln;
     unsigned int cells = 0;
     if (isfinite(rx[k]) && isfinite(ry[k]) && isfinite(ray.ex) && isfinite(ray.ey) &&
-        qs_line_setup(ray, rx[k], ry[k], geo, ln)) {
-        int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
-        for (;;) {
-            const bool last = (x == ln.x1 && y == ln.y1);
-            if ((!last || ray.valid) && x >= 0 && x < geo.size && y >= 0 && y < geo.size) {
-                const size_t c = (size_t)y * geo.size + x;
-                atomicMax(&stamps[c], key_free | (last ? 1u : 0u));
-                qs_mark_dirty(geo, x, y);
-                if (COUNTS) atomicAdd(&counts[c], last ? (1ull << 32) : 1ull);
-                cells++;
-            }
-            if (last) break;
-            const int e2 = 2 * err;
-            if (e2 > -ln.dy) { err -= ln.dy; x += ln.sx; }
-            if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
-        }
-    }
+        qs_line_setup(ray, rx[k], ry[k], geo, ln))
+        cells = qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
     atomicAdd(&counters[QS_CNT_RAYS], 1ull);
     if (cells) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)cells);
 }
@@ -162,23 +147,7 @@ __global__ void qs_edge_cast_kernel(unsigned int n_edge, const QsEdgeRec *__rest
     const unsigned int key_free = rec.key_free;
     QsLine ln;
     unsigned int cells = 0;
-    if (qs_line_setup(ray, rec.rx, rec.ry, geo, ln)) {
-        int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
-        for (;;) {
-            const bool last = (x == ln.x1 && y == ln.y1);
-            if ((!last || ray.valid) && x >= 0 && x < geo.size && y >= 0 && y < geo.size) {
-                const size_t c = (size_t)y * geo.size + x;
-                atomicMax(&stamps[c], key_free | (last ? 1u : 0u));
-                qs_mark_dirty(geo, x, y);
-                if (COUNTS) atomicAdd(&counts[c], last ? (1ull << 32) : 1ull);
-                cells++;
-            }
-            if (last) break;
-            const int e2 = 2 * err;
-            if (e2 > -ln.dy) { err -= ln.dy; x += ln.sx; }
-            if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
-        }
-    }
+    if (qs_line_setup(ray, rec.rx, rec.ry, geo, ln)) cells = qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
     if (cells) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)cells);
 }
 hipError_t qs_launch_edge_cast(qs_ctx *c, unsigned int n_edge, const double *d_in)

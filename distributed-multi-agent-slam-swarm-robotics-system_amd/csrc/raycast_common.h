@@ -89,11 +89,13 @@ __device__ inline bool qs_edge_ray(const QsRay &ray, const QsGeom &geo)
 }
 
 // leave the ray to the host; false: the list is full (the caller casts the ray with the device's end point after all)
-__device__ inline bool qs_edge_defer(const QsBatch &b, double rx, double ry, double yaw, float d, unsigned int key_free)
+// beam: index of a servo-sweep beam (sweep.hip), -1 for the four rays of a QuasarPacket
+__device__ inline bool qs_edge_defer(const QsBatch &b, double rx, double ry, double yaw, float d, unsigned int key_free,
+                                     int beam = -1)
 {
     const unsigned int slot = atomicAdd(b.edge_n, 1u);
     if (slot >= b.edge_cap) { atomicAdd(b.edge_n + 2, 1u); return false; }
-    QsEdgeRec rec; rec.rx = rx; rec.ry = ry; rec.yaw = yaw; rec.d = d; rec.key_free = key_free;
+    QsEdgeRec rec; rec.rx = rx; rec.ry = ry; rec.yaw = yaw; rec.d = d; rec.key_free = key_free; rec.beam = beam; rec.pad = 0;
     b.edge[slot] = rec;
     return true;
 }
@@ -120,6 +122,31 @@ __device__ inline bool qs_line_setup(const QsRay &ray, double rx, double ry, con
     ln.dx = (int)dx; ln.dy = (int)dy;                                                                // :161-162
     ln.sx = x0 < x1 ? 1 : -1; ln.sy = y0 < y1 ? 1 : -1;                                             // :163-164
     return true;
+}
+
+// The walk of :158-178 straight into the grid, one global atomic per cell (the direct form); returns the cells written.
+// The last cell is written only for an observed hit (:148-150); cells outside the grid are skipped (:149, :155).
+template <bool COUNTS>
+__device__ inline unsigned int qs_cast_line(const QsLine &ln, bool valid, unsigned int key_free, const QsGeom &geo,
+                                            unsigned int *__restrict__ stamps, unsigned long long *__restrict__ counts)
+{
+    unsigned int cells = 0;
+    int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
+    for (;;) {
+        const bool last = (x == ln.x1 && y == ln.y1);
+        if ((!last || valid) && x >= 0 && x < geo.size && y >= 0 && y < geo.size) {
+            const size_t c = (size_t)y * geo.size + x;
+            atomicMax(&stamps[c], key_free | (last ? 1u : 0u));
+            qs_mark_dirty(geo, x, y);
+            if (COUNTS) atomicAdd(&counts[c], last ? (1ull << 32) : 1ull);
+            cells++;
+        }
+        if (last) break;
+        const int e2 = 2 * err;
+        if (e2 > -ln.dy) { err -= ln.dy; x += ln.sx; }
+        if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
+    }
+    return cells;
 }
 
 // Bounding box of a bot's hit points and path (compute_bounding_box, dual_bot_mapper.py:702-706),

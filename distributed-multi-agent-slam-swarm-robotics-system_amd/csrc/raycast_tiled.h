@@ -1,0 +1,61 @@
+// raycast_tiled.h -- the tile-binned raycast's shared pieces: its constants, its workspace and the host helpers that run
+// passes B1 / C / D over any array of ray slots.  Pass A has two producers: qs_rays_kernel (4 rays per packet,
+// raycast_tiled.hip) and qs_sweep_rays_kernel (184 ray slots per servo sweep, sweep.hip).
+#pragma once
+#include "qs_internal.h"
+
+#define QT_TILE 64                       // tile edge in cells: 64 x 64 x u32 = 16 KiB of LDS
+#define QT_TILE_SHIFT 6
+#define QT_CELLS (QT_TILE * QT_TILE)
+#define QT_CHUNK 2048                    // records per raster work item
+#ifndef QT_BLOCK
+#define QT_BLOCK 512                     // raster workgroup: 8 waves share one 32 KiB LDS tile (A/B: 256 -> 512 threads = -5..-18 % stage time)
+#endif
+#ifndef QT_BIN_BLOCK
+#define QT_BIN_BLOCK 1024                // pass A / C workgroup
+#endif
+#ifndef QT_MAX_WG
+#define QT_MAX_WG 512                    // persistent workgroups of pass A / C (2 per CU)
+#endif
+#define QT_MAX_TILES 16384               // LDS histogram limit: 64 KiB (8192^2 cells)
+#define QT_NO_RAY (-32768)              // x0 of "no ray": grids are <= 16384 cells wide, rays < 64 cells past an edge
+#ifndef QT_RASTER_WGS
+#define QT_RASTER_WGS 1024               // persistent raster workgroups (4 per CU)
+#endif
+#ifndef QT_PITCH
+#define QT_PITCH 67                      // LDS row pitch in cells: bank = (x + 3 y) mod 32, see qs_raster_kernel
+#endif
+#define QT_LDS_CELLS (QT_TILE * QT_PITCH)
+
+struct QtWorkspace {
+    unsigned int *table;         // [nwg][n_tiles] per-workgroup record counts -> exclusive offsets
+    unsigned int *tile_count;    // [n_tiles]   records per tile
+    unsigned int *tile_base;     // [n_tiles+1] exclusive scan of tile_count
+    unsigned int *chunk_base;    // [n_tiles+1] exclusive scan of ceil(count / QT_CHUNK)
+    uint2 *rays;                 // [n_rays]    absolute grid end points, i16 x 4: (x0 | y0 << 16, x1 | y1 << 16);
+                                 //             x0 = QT_NO_RAY: none
+    uint2 *recs;                 // [4 n_rays]  tile records: tile-relative end points, i8 x 4; stamp | observed-hit bit
+    int tiles_x, n_tiles, nwg;
+    size_t pk_per_wg;            // pass A of the 4-ray path: packets per workgroup (multiple of 64)
+    size_t rays_per_wg;          // pass C: ray slots per workgroup -- workgroup w owns slots [w * rays_per_wg, (w + 1) * rays_per_wg)
+    unsigned int *dirty;         // sparse fuse: bitmap of written 4 x 16-cell blocks (QsGeom::dirty), or nullptr
+    int dirty_pitch;
+};
+
+__device__ inline void qt_tile_range(int x0, int y0, int x1, int y1, int size, int &tx_lo, int &tx_hi,
+                                     int &ty_lo, int &ty_hi)
+{
+    const int xlo = max(min(x0, x1), 0), xhi = min(max(x0, x1), size - 1);
+    const int ylo = max(min(y0, y1), 0), yhi = min(max(y0, y1), size - 1);
+    tx_lo = xlo >> QT_TILE_SHIFT; tx_hi = xhi >> QT_TILE_SHIFT;
+    ty_lo = ylo >> QT_TILE_SHIFT; ty_hi = yhi >> QT_TILE_SHIFT;
+}
+
+// host side (raycast_tiled.hip).  qt_workspace: grows the context's workspace for up to cap_rays ray slots and carves it;
+// the caller fills nwg, pk_per_wg / rays_per_wg.  qt_dyn_lds: bytes of pass A / C's LDS histogram (large grids raise the
+// kernels' limit: `kernels` lists the pass-A kernels beside qs_scatter_kernel).  qt_launch_sort_raster: passes B1, C, D
+// over ray slots [0, n_rays) whose hit flags are hit_valid[r] and whose stamps are (ord_base + ord_stride * (r >> 2) + (r & 3) + 1) << 1.
+hipError_t qt_workspace(qs_ctx *c, size_t cap_rays, QtWorkspace &ws);
+hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *const *kernels, int n_kernels, size_t &lds);
+hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays, const unsigned char *hit_valid,
+                                 unsigned long long ord_base, unsigned long long ord_stride, size_t lds);

@@ -25,55 +25,9 @@
 // HBM traffic per packet (4 rays, ~1.4 tile records per ray): 45 B decoded fields + 64 B ray
 // end points written and read + ~90 B records written and read, independent of how many cells
 // each ray covers; the per-cell work happens in LDS.
-#include "qs_internal.h"
+#include "raycast_tiled.h"
 #include "raycast_common.h"
 #include <cstdlib>
-
-#define QT_TILE 64                       // tile edge in cells: 64 x 64 x u32 = 16 KiB of LDS
-#define QT_TILE_SHIFT 6
-#define QT_CELLS (QT_TILE * QT_TILE)
-#define QT_CHUNK 2048                    // records per raster work item
-#ifndef QT_BLOCK
-#define QT_BLOCK 512                     // raster workgroup: 8 waves share one 32 KiB LDS tile (A/B: 256 -> 512 threads = -5..-18 % stage time)
-#endif
-#ifndef QT_BIN_BLOCK
-#define QT_BIN_BLOCK 1024                // pass A / C workgroup
-#endif
-#ifndef QT_MAX_WG
-#define QT_MAX_WG 512                    // persistent workgroups of pass A / C (2 per CU)
-#endif
-#define QT_MAX_TILES 16384               // LDS histogram limit: 64 KiB (8192^2 cells)
-#define QT_NO_RAY (-32768)              // x0 of "no ray": grids are <= 16384 cells wide, rays < 64 cells past an edge
-#ifndef QT_RASTER_WGS
-#define QT_RASTER_WGS 1024               // persistent raster workgroups (4 per CU)
-#endif
-#ifndef QT_PITCH
-#define QT_PITCH 67                      // LDS row pitch in cells: bank = (x + 3 y) mod 32, see qs_raster_kernel
-#endif
-#define QT_LDS_CELLS (QT_TILE * QT_PITCH)
-
-struct QtWorkspace {
-    unsigned int *table;         // [nwg][n_tiles] per-workgroup record counts -> exclusive offsets
-    unsigned int *tile_count;    // [n_tiles]   records per tile
-    unsigned int *tile_base;     // [n_tiles+1] exclusive scan of tile_count
-    unsigned int *chunk_base;    // [n_tiles+1] exclusive scan of ceil(count / QT_CHUNK)
-    uint2 *rays;                 // [4n]        absolute grid end points, i16 x 4: (x0 | y0 << 16, x1 | y1 << 16);
-                                 //             x0 = QT_NO_RAY: none
-    uint2 *recs;                 // [16n]       tile records: tile-relative end points, i8 x 4; stamp | observed-hit bit
-    int tiles_x, n_tiles, nwg;
-    size_t pk_per_wg;            // packets per workgroup (multiple of 64)
-    unsigned int *dirty;         // sparse fuse: bitmap of written 4 x 16-cell blocks (QsGeom::dirty), or nullptr
-    int dirty_pitch;
-};
-
-__device__ inline void qt_tile_range(int x0, int y0, int x1, int y1, int size, int &tx_lo, int &tx_hi,
-                                     int &ty_lo, int &ty_hi)
-{
-    const int xlo = max(min(x0, x1), 0), xhi = min(max(x0, x1), size - 1);
-    const int ylo = max(min(y0, y1), 0), yhi = min(max(y0, y1), size - 1);
-    tx_lo = xlo >> QT_TILE_SHIFT; tx_hi = xhi >> QT_TILE_SHIFT;
-    ty_lo = ylo >> QT_TILE_SHIFT; ty_hi = yhi >> QT_TILE_SHIFT;
-}
 
 // ---- pass A -----------------------------------------------------------------------------------
 template <bool COUNTS>
@@ -225,8 +179,8 @@ qs_table_scan_kernel(QtWorkspace ws)
 
 // ---- pass C: scatter tile records ---------------------------------------------------------------
 __global__ void __launch_bounds__(QT_BIN_BLOCK)
-qs_scatter_kernel(size_t n, QsBatch b, QtWorkspace ws, int size, unsigned long long ord_base,
-                  unsigned long long ord_stride)
+qs_scatter_kernel(size_t n_rays, const unsigned char *__restrict__ hit_valid, QtWorkspace ws, int size,
+                  unsigned long long ord_base, unsigned long long ord_stride)
 {
     extern __shared__ unsigned int s_cur[];                        // [n_tiles] next record slot per tile
     __shared__ unsigned int s_wrec[QT_BIN_BLOCK / QS_WAVE], s_wchk[QT_BIN_BLOCK / QS_WAVE];
@@ -260,8 +214,8 @@ qs_scatter_kernel(size_t n, QsBatch b, QtWorkspace ws, int size, unsigned long l
         if (pub && tid == QT_BIN_BLOCK - 1) { ws.tile_base[ws.n_tiles] = ra; ws.chunk_base[ws.n_tiles] = rc; }
     }
     __syncthreads();
-    const size_t r0 = 4 * (size_t)blockIdx.x * ws.pk_per_wg;
-    const size_t r1 = (r0 + 4 * ws.pk_per_wg < 4 * n) ? r0 + 4 * ws.pk_per_wg : 4 * n;
+    const size_t r0 = (size_t)blockIdx.x * ws.rays_per_wg;
+    const size_t r1 = (r0 + ws.rays_per_wg < n_rays) ? r0 + ws.rays_per_wg : n_rays;
     for (size_t r = r0 + tid; r < r1; r += QT_BIN_BLOCK) {
         const uint2 ray = ws.rays[r];
         const int x0 = (short)(ray.x & 0xffffu), y0 = (short)(ray.x >> 16);
@@ -271,7 +225,7 @@ qs_scatter_kernel(size_t n, QsBatch b, QtWorkspace ws, int size, unsigned long l
         qt_tile_range(x0, y0, x1, y1, size, tx_lo, tx_hi, ty_lo, ty_hi);
         // stamp of the ray's free cells; bit 0 (the occupied bit of a cell stamp) carries "the end
         // cell was observed" into the raster pass
-        const unsigned int key = (unsigned int)((ord_base + ord_stride * (r >> 2) + (r & 3) + 1) << 1) | (b.hit_valid[r] ? 1u : 0u);
+        const unsigned int key = (unsigned int)((ord_base + ord_stride * (r >> 2) + (r & 3) + 1) << 1) | (hit_valid[r] ? 1u : 0u);
         // dx, dy < 64: the tile box is 1 x 1, 2 x 1, 1 x 2 or 2 x 2 (same enumeration as pass A)
         #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -501,58 +455,47 @@ size_t qs_tiled_workspace_bytes(const qs_ctx *c, size_t n)
            qt_align(4 * n * sizeof(uint2)) + qt_align(16 * n * sizeof(uint2));
 }
 
-hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
+hipError_t qt_workspace(qs_ctx *c, size_t cap_rays, QtWorkspace &ws)
 {
-    if (n == 0) return hipSuccess;
-    if (!qs_tiled_supported(c)) return qs_launch_raycast_direct(c, n, seq0);
-    hipError_t e = c->bin_ws.reserve(qs_tiled_workspace_bytes(c, c->cap_batch), c->stream);
+    // (the byte count of qs_tiled_workspace_bytes, in ray slots: 4 per packet)
+    hipError_t e = c->bin_ws.reserve(qs_tiled_workspace_bytes(c, (cap_rays + 3) / 4), c->stream);
     if (e != hipSuccess) return e;
-    QtWorkspace ws;
     ws.tiles_x = (c->cfg.size + QT_TILE - 1) / QT_TILE;
     ws.n_tiles = ws.tiles_x * ws.tiles_x;
-    // packets per workgroup: a multiple of 64, at least 256, and at most QT_MAX_WG workgroups
-    size_t per = (n + QT_MAX_WG - 1) / QT_MAX_WG;
-    per = per < 256 ? 256 : ((per + 63) & ~(size_t)63);
-    ws.pk_per_wg = per;
-    ws.nwg = (int)((n + per - 1) / per);
     const size_t tbytes = qt_align(((size_t)ws.n_tiles + 1) * sizeof(unsigned int));
     char *p = c->bin_ws.p;
     ws.table = (unsigned int *)p; p += qt_align((size_t)QT_MAX_WG * ws.n_tiles * sizeof(unsigned int));
     ws.tile_count = (unsigned int *)p; p += tbytes;
     ws.tile_base = (unsigned int *)p; p += tbytes;
     ws.chunk_base = (unsigned int *)p; p += tbytes;
-    ws.rays = (uint2 *)p; p += qt_align(4 * c->cap_batch * sizeof(uint2));
+    ws.rays = (uint2 *)p; p += qt_align(4 * ((cap_rays + 3) / 4) * sizeof(uint2));
     ws.recs = (uint2 *)p;
     ws.dirty = c->geom.dirty; ws.dirty_pitch = c->geom.dirty_pitch;
+    return hipSuccess;
+}
 
-    const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
-    const unsigned long long ord_stride = 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1);
-    const size_t n_rays = 4 * n;
-    const size_t lds = (size_t)ws.n_tiles * sizeof(unsigned int);
+hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *const *kernels, int n_kernels, size_t &lds)
+{
+    lds = (size_t)ws.n_tiles * sizeof(unsigned int);
+    if (lds <= 32 * 1024) return hipSuccess;
+    // large grids (up to 8192^2: 16384 tiles) need more dynamic LDS than the 64 KiB default allows
+    // next to the static arrays; the CU has 160 KiB
+    hipError_t ea = hipFuncSetAttribute((const void *)qs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (int k = 0; k < n_kernels && ea == hipSuccess; k++)
+        ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return ea;
+}
+
+hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays, const unsigned char *hit_valid,
+                                 unsigned long long ord_base, unsigned long long ord_stride, size_t lds)
+{
     // upper bound on raster work items: every record in a full chunk, plus one partial chunk per tile
     size_t max_items = (4 * n_rays) / QT_CHUNK + (size_t)ws.n_tiles + 8;
     if (max_items > 4 * n_rays) max_items = 4 * n_rays;
-    if (lds > 32 * 1024) {
-        // large grids (up to 8192^2: 16384 tiles) need more dynamic LDS than the 64 KiB default allows
-        // next to the static arrays; the CU has 160 KiB
-        hipError_t ea = hipFuncSetAttribute((const void *)qs_rays_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea == hipSuccess) ea = hipFuncSetAttribute((const void *)qs_rays_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea == hipSuccess) ea = hipFuncSetAttribute((const void *)qs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    StageTimer t_rays(c, QS_STAGE_RC_RAYS);
-    if (c->cfg.enable_counts) {
-        hipLaunchKernelGGL(qs_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
-    } else {
-        hipLaunchKernelGGL(qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
-    }
-    t_rays.stop();
     StageTimer t_sort(c, QS_STAGE_RC_SORT);
     hipLaunchKernelGGL(qs_table_scan_kernel, dim3((ws.n_tiles + QT_SCAN_TILES - 1) / QT_SCAN_TILES),
                        dim3(QT_SCAN_TILES * QT_SCAN_SEGS), 0, c->stream, ws);
-    hipLaunchKernelGGL(qs_scatter_kernel, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, ws,
+    hipLaunchKernelGGL(qs_scatter_kernel, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n_rays, hit_valid, ws,
                        c->cfg.size, ord_base, ord_stride);
     t_sort.stop();
     // QS_RASTER_WGS (environment, read once): fewer persistent raster workgroups than the default -- a tuning
@@ -568,4 +511,36 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
                            c->cfg.size, c->d_stamps, c->d_counts, c->d_counters);
     t_raster.stop();
     return hipGetLastError();
+}
+
+hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
+{
+    if (n == 0) return hipSuccess;
+    if (!qs_tiled_supported(c)) return qs_launch_raycast_direct(c, n, seq0);
+    QtWorkspace ws;
+    hipError_t e = qt_workspace(c, 4 * c->cap_batch, ws);
+    if (e != hipSuccess) return e;
+    // packets per workgroup: a multiple of 64, at least 256, and at most QT_MAX_WG workgroups
+    size_t per = (n + QT_MAX_WG - 1) / QT_MAX_WG;
+    per = per < 256 ? 256 : ((per + 63) & ~(size_t)63);
+    ws.pk_per_wg = per;
+    ws.rays_per_wg = 4 * per;
+    ws.nwg = (int)((n + per - 1) / per);
+
+    const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
+    const unsigned long long ord_stride = 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1);
+    const void *pass_a[2] = {(const void *)qs_rays_kernel<true>, (const void *)qs_rays_kernel<false>};
+    size_t lds = 0;
+    e = qt_dyn_lds(ws, pass_a, 2, lds);
+    if (e != hipSuccess) return e;
+    StageTimer t_rays(c, QS_STAGE_RC_RAYS);
+    if (c->cfg.enable_counts) {
+        hipLaunchKernelGGL(qs_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
+                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
+    } else {
+        hipLaunchKernelGGL(qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
+                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
+    }
+    t_rays.stop();
+    return qt_launch_sort_raster(c, ws, 4 * n, c->b.hit_valid, ord_base, ord_stride, lds);
 }

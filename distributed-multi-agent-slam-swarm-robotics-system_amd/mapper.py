@@ -145,6 +145,64 @@ class QuasarMapper:
         self._chk(self._L.qs_last_hits(self._h, _ptr(xy), _ptr(valid), n), "qs_last_hits")
         return xy, valid
 
+    # -- servo sweeps (v0 '<4sBfffH181f' / v0 + odometry '<4sBfffiIH181f'; include/quasar_slam.h) --------------------------
+    def ingest_sweeps(self, datagrams, lengths=None, seq0=None):
+        """Map servo-sweep packets: a list of bytes objects (one format: 743 or 751 bytes; other lengths are dropped) or a
+        uint8 [n, 743 | 751] array with optional uint16 lengths.  Sweep k uses sequence numbers seq0 + 46 k ... + 45."""
+        if isinstance(datagrams, np.ndarray):
+            buf = np.ascontiguousarray(datagrams, dtype=np.uint8)
+            if buf.ndim != 2:
+                raise ValueError("sweeps must be [n, stride]")
+        else:
+            if len(datagrams) == 0:
+                self._sweeps_call(np.zeros((0, P.PACKET_SIZE_V0_ODO), np.uint8), None, seq0)
+                return 0
+            sizes = {len(d) for d in datagrams} & {P.PACKET_SIZE_V0, P.PACKET_SIZE_V0_ODO}
+            if len(sizes) > 1:
+                raise ValueError("one sweep format per call: 743- and 751-byte records mixed")
+            stride = sizes.pop() if sizes else P.PACKET_SIZE_V0_ODO
+            buf = np.zeros((len(datagrams), stride), dtype=np.uint8)
+            lengths = np.zeros(len(datagrams), dtype=np.uint16)
+            for i, d in enumerate(datagrams):
+                m = min(len(d), stride)
+                buf[i, :m] = np.frombuffer(d[:m], dtype=np.uint8)
+                lengths[i] = min(len(d), 65535)
+        return self._sweeps_call(buf, lengths, seq0)
+
+    def _sweeps_call(self, buf, lengths, seq0):
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        self._chk(self._L.qs_ingest_sweeps(self._h, _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                           UINT64_MAX if seq0 is None else int(seq0)), "qs_ingest_sweeps")
+        self._map_version += 1
+        self._last_n = 0
+        self._last_sweeps_n = n
+        return n
+
+    def ingest_sweeps_device(self, d_pkts, n, stride, d_lens=0, seq0=None):
+        """Device-resident sweeps (raw device addresses as ints); asynchronous."""
+        self._chk(self._L.qs_ingest_sweeps_device(self._h, C.c_void_p(d_pkts), n, stride,
+                                                  C.c_void_p(d_lens) if d_lens else None,
+                                                  UINT64_MAX if seq0 is None else int(seq0)), "qs_ingest_sweeps_device")
+        self._map_version += 1
+        self._last_n = 0
+        self._last_sweeps_n = n
+
+    def last_sweeps(self):
+        """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after
+        offset and drift, yaw); NaN for rejected records."""
+        n = getattr(self, "_last_sweeps_n", 0)
+        acc = np.zeros(n, dtype=np.uint8)
+        pose = np.zeros((n, 3), dtype=np.float64)
+        self._chk(self._L.qs_last_sweeps(self._h, _ptr(acc), _ptr(pose), n), "qs_last_sweeps")
+        return acc, pose
+
+    def set_sweep_filter(self, smin=P.SWEEP_MIN_DIST_M, smax=P.SWEEP_MAX_DIST_M):
+        """Trust filter of sweep beams: a hit when smin < d <= smax (default: the reference's 0.1 < d <= 1.2)."""
+        self._chk(self._L.qs_set_sweep_filter(self._h, float(smin), float(smax)), "qs_set_sweep_filter")
+
     # -- grid ---------------------------------------------------------------------------------
     def grid_i8(self):
         out = np.empty((self.size, self.size), dtype=np.int8)

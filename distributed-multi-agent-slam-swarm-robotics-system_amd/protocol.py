@@ -109,6 +109,52 @@ PACKET_DTYPE_V0 = np.dtype([("magic", "S4"), ("agent", "u1"), ("x", "<f4"), ("y"
 assert PACKET_DTYPE_V0.itemsize == PACKET_SIZE_V0
 
 
+# the same sweep with odometry: i32 encoder, u32 v2v before scan_count (server_nodes/udp_receiver_standalone.py:15,
+# room_mapper.py:21); the standalone receiver logs it as CSV (:78-82)
+PACKET_FMT_V0_ODO = "<4sBfffiIH181f"
+PACKET_SIZE_V0_ODO = struct.calcsize(PACKET_FMT_V0_ODO)      # 751
+PACKET_DTYPE_V0_ODO = np.dtype([("magic", "S4"), ("agent", "u1"), ("x", "<f4"), ("y", "<f4"), ("yaw", "<f4"),
+                                ("enc", "<i4"), ("v2v", "<u4"), ("scan_count", "<u2"), ("ranges", "<f4", (181,))])
+assert PACKET_DTYPE_V0_ODO.itemsize == PACKET_SIZE_V0_ODO
+SWEEP_BEAMS = 181
+SWEEP_SEQS = 46              # sequence numbers one sweep uses in the mapper's stamp order (include/quasar_slam.h)
+SWEEP_MIN_DIST_M = 0.1       # trust filter of the reference's sweep map, generate_topdown_map.py:51
+SWEEP_MAX_DIST_M = 1.2
+
+
+def pack_v0(agent, x, y, yaw, ranges, scan_count=SWEEP_BEAMS, magic=b"QSRL") -> bytes:
+    return struct.pack(PACKET_FMT_V0, magic, agent, x, y, yaw, scan_count, *ranges)
+
+
+def pack_v0_odo(agent, x, y, yaw, enc, v2v, ranges, scan_count=SWEEP_BEAMS, magic=b"QSRL") -> bytes:
+    return struct.pack(PACKET_FMT_V0_ODO, magic, agent, x, y, yaw, enc, v2v, scan_count, *ranges)
+
+
+def pack_sweeps(agent, x, y, yaw, ranges, enc=None, v2v=None, odometry=True, scan_count=SWEEP_BEAMS) -> np.ndarray:
+    """Vectorised packer: arrays (ranges [n, 181]) -> uint8 [n, 751] (odometry) or [n, 743]."""
+    n = len(agent)
+    rec = np.zeros(n, dtype=PACKET_DTYPE_V0_ODO if odometry else PACKET_DTYPE_V0)
+    rec["magic"] = b"QSRL"
+    rec["agent"], rec["x"], rec["y"], rec["yaw"] = agent, x, y, yaw
+    if odometry:
+        rec["enc"] = 0 if enc is None else enc
+        rec["v2v"] = 0 if v2v is None else v2v
+    rec["scan_count"] = scan_count
+    rec["ranges"] = np.asarray(ranges, dtype=np.float32).reshape(n, SWEEP_BEAMS)
+    return rec.view(np.uint8).reshape(n, rec.dtype.itemsize)
+
+
+def unpack_v0_odo(data: bytes):
+    """None unless the size and magic match; else (agent, x, y, yaw, encoder, v2v, ranges[181])."""
+    if len(data) != PACKET_SIZE_V0_ODO:
+        return None
+    rec = np.frombuffer(data, dtype=PACKET_DTYPE_V0_ODO)[0]
+    if rec["magic"] != b"QSRL":
+        return None
+    return (int(rec["agent"]), float(rec["x"]), float(rec["y"]), float(rec["yaw"]), int(rec["enc"]), int(rec["v2v"]),
+            rec["ranges"].copy())
+
+
 def unpack_v0(data: bytes):
     """udp_bridge.py:53-75: None unless the size and magic match; else (agent, x, y, yaw, ranges[181])."""
     if len(data) != PACKET_SIZE_V0:

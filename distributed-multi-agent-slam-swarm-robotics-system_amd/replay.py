@@ -9,6 +9,7 @@ Host-side numpy only.
 """
 import csv
 import os
+import re
 
 import numpy as np
 
@@ -35,6 +36,24 @@ def telemetry_csv_to_packets(path=SESSION_CSV):
                   col("back_cm", float) / 100.0, col("right_cm", float) / 100.0], axis=1),
         col("landmark", int))
     return pk, col("time", float)
+
+
+def sweep_csv_to_packets(path, agent=None):
+    """A servo-sweep log of the standalone receiver (server_nodes/udp_receiver_standalone.py:78-82; columns timestamp, idx,
+    x, y, yaw, encoder, v2v_link, r_0..r_180, one file per agent: logs/agent_<id>_log.csv) -> (uint8 [n, 751] v0 + odometry
+    records, timestamp float64 [n]), rows in file order.  agent: the records' agent id; None takes it from an
+    agent_<id>_log.csv file name, else 1.  The log keeps no scan_count: the records carry 181."""
+    if agent is None:
+        m = re.search(r"agent_(\d+)_log\.csv$", os.path.basename(path))
+        agent = int(m.group(1)) if m else 1
+    with open(path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    col = lambda k, t: np.array([t(r[k]) for r in rows])
+    n = len(rows)
+    ranges = np.array([[float(r[f"r_{i}"]) for i in range(P.SWEEP_BEAMS)] for r in rows], dtype=np.float32).reshape(n, P.SWEEP_BEAMS)
+    pk = P.pack_sweeps(np.full(n, agent), col("x", float), col("y", float), col("yaw", float), ranges,
+                       enc=col("encoder", int), v2v=col("v2v_link", int), odometry=True)
+    return pk, col("timestamp", float)
 
 
 def cycle_stream(pkts, n):

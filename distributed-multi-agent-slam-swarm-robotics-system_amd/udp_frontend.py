@@ -12,6 +12,11 @@ Mirrors server_nodes/dual_bot_mapper.py:
                                centroid not taken and not within FRONTIER_SEPARATION of an earlier target, sent
                                as TARG (:691-699).  Commented out in the reference as shipped, so opt-in here
                                (frontier_targets=True); the mapper then also needs assign_frontier_targets.
+Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry packets of the ESP32 firmware
+(esp32_firmware/src/main.cpp:190-215) are mapped too.  Datagrams then get slots of SWEEP_SLOT bytes; the datagrams of a
+poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
+each run one ingest call.  No call names its sequence numbers: the mapper continues its own counter across both kinds
+(1 per packet, 46 per sweep), so stamps follow arrival, after whatever the mapper held before (a replayed log, say).  An accepted sweep marks its bot online and sets its pose, as a packet does.
 Differences: the reference throttles itself to 20 packets per 30 fps frame (:816, :474); here a
 poll drains the socket (up to max_batch datagrams).  Host-side Python only; the mapper can be any
 object with ingest_array / last_batch / zone_packet (tests use a stub, production the HIP mapper).
@@ -24,12 +29,15 @@ import numpy as np
 from . import protocol as P
 
 SLOT = 48      # bytes per datagram slot handed to qs_ingest (42-byte packets, room for oversize marks)
+SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize mark
 
 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
-                 frontier_targets=False):
+                 frontier_targets=False, sweeps=False):
         self.mapper = mapper
+        self.sweeps = sweeps
+        self.slot = SWEEP_SLOT if sweeps else SLOT
         self.frontier_targets = frontier_targets
         self.max_agent = max_agent
         self.max_batch = max_batch
@@ -50,7 +58,7 @@ class MissionControl:
         self.last_zone_send = time.time()                                             # :788
         self.bot_pose = {b: None for b in bots}      # bot_states[b]['x'], ['y']: last accepted pose (:850-866)
         self.last_target_send = time.time()
-        self._buf = np.zeros((max_batch, SLOT), dtype=np.uint8)
+        self._buf = np.zeros((max_batch, self.slot), dtype=np.uint8)
         self._lens = np.zeros(max_batch, dtype=np.uint16)
         self._times = np.zeros(max_batch, dtype=np.float64)
         self._addrs = [None] * max_batch
@@ -61,35 +69,60 @@ class MissionControl:
         """Drain the socket into one batch and ingest it.  Returns the number of datagrams."""
         now = time.time() if now is None else now
         n = 0
+        SL = self.slot
         view = memoryview(self._buf).cast("B")
         while n < self.max_batch:
             try:
-                nbytes, addr = self.sock.recvfrom_into(view[n * SLOT:(n + 1) * SLOT], SLOT)   # :818
+                nbytes, addr = self.sock.recvfrom_into(view[n * SL:(n + 1) * SL], SL)   # :818
             except BlockingIOError:
                 break
             except OSError:
                 break
-            self._lens[n] = nbytes if nbytes < SLOT else 65535     # a datagram that fills the slot may be longer: drop it
+            self._lens[n] = nbytes if nbytes < SL else 65535       # a datagram that fills the slot may be longer: drop it
             self._times[n] = now
             self._addrs[n] = addr
             n += 1
         if n == 0:
             return 0
         self.datagrams += n
-        self.mapper.ingest_array(self._buf[:n], self._lens[:n], self._times[:n])
-        accepted, pose = self.mapper.last_batch()
-        keep_pose = self.frontier_targets and pose is not None
-        agents = self._buf[:n, 4]
-        for i in np.nonzero(accepted)[0]:
-            a = int(agents[i])
+        if not self.sweeps:
+            self.mapper.ingest_array(self._buf[:n], self._lens[:n], self._times[:n])
+            accepted, pose = self.mapper.last_batch()
+            self._mark(0, accepted, pose, now, self.frontier_targets and pose is not None)
+            return n
+        for i0, i1, kind in self._runs(n):
+            lens = self._lens[i0:i1]
+            if kind == 0:
+                self.mapper.ingest_array(self._buf[i0:i1, :SLOT], lens, self._times[i0:i1])
+                accepted, pose = self.mapper.last_batch()
+                self._mark(i0, accepted, pose, now, self.frontier_targets and pose is not None)
+            else:
+                self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens)
+                accepted, pose = self.mapper.last_sweeps()
+                self._mark(i0, accepted, pose, now, pose is not None)
+        return n
+
+    def _runs(self, n):
+        """Maximal runs of one kind in arrival order: (first, end, 0 for packets | the sweep stride)."""
+        lens = self._lens[:n]
+        kind = np.where((lens == P.PACKET_SIZE_V0) | (lens == P.PACKET_SIZE_V0_ODO), lens, 0).astype(np.int64)
+        cuts = np.flatnonzero(np.diff(kind)) + 1
+        starts = np.concatenate(([0], cuts))
+        ends = np.concatenate((cuts, [n]))
+        return [(int(a), int(b), int(kind[a])) for a, b in zip(starts, ends)]
+
+    def _mark(self, i0, accepted, pose, now, keep_pose):
+        """Bookkeeping of the accepted records of one ingest whose first datagram is slot i0 (:846-848, :860-864)."""
+        for j in np.nonzero(accepted)[0]:
+            i = i0 + int(j)
+            a = int(self._buf[i, 4])
             self.bot_addrs[a] = (self._addrs[i][0], self.bot_ports[a])                # :846
             self.last_packet_time[a] = now                                            # :847
             self.pkt_counts[a] += 1                                                   # :848
             self.online[a] = True                                                     # :860-864
             self.seen[a] = True
             if keep_pose:
-                self.bot_pose[a] = (float(pose[i, 0]), float(pose[i, 1]))
-        return n
+                self.bot_pose[a] = (float(pose[j, 0]), float(pose[j, 1]))
 
     # ---- :805-812 --------------------------------------------------------------------------------
     def heartbeat(self, now=None):

@@ -110,6 +110,44 @@ int qs_last_batch(qs_ctx *ctx, uint8_t *accepted, double *pose_xyyaw /* n x 3 */
  * only needs the rays' grid cells. */
 int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 4 */, size_t n);
 
+/* ---- servo sweeps ("Quasar-Lite" packets) ----------------------------------------------------------------------------
+ * A sweep carries a pose and 181 ranges swept from -90 to +90 degrees about the heading:
+ *   v0              '<4sBfffH181f'   743 bytes  (esp32_firmware/src/main.cpp:33-41; udp_bridge.py:25-38)
+ *   v0 + odometry   '<4sBfffiIH181f' 751 bytes  (i32 encoder, u32 v2v before scan_count; udp_receiver_standalone.py:15)
+ * The reference maps sweeps only in its top-down plot (generate_topdown_map.py:39-57); here they go into the occupancy grid
+ * with the reference's own update_ray (:136-179), so that every cell can be checked against it:
+ *   accept   length == stride (743 or 751: one format per call), magic 'QSRL', agent in 1..max_agent; scan_count is
+ *            ignored (udp_bridge.py:71).  A rejected record writes nothing but still uses its sequence numbers.
+ *   pose     rx = f64(x) + offset[bot] + drift_x[bot], ry = f64(y) + drift_y[bot] (offset first, then drift, as :851-857):
+ *            qs_set_bot_offset / separation, and the bot's closure correction as all earlier calls on the context's stream
+ *            left it (read on the device).  A sweep adds NO pose-graph node, landmark, EKF step or zone point.
+ *   beams    beam i has angle a = f64(yaw) + (i - 90) * (pi / 180) (CPython's math.radians; one multiply, one add, no FMA).
+ *            d = the f32 range widened: smin < d <= smax is a hit, update_ray(rx, ry, rx + d cos a, ry + d sin a, True);
+ *            any other beam (NaN, 0, negative included) a free ray of length min(d, smax) if d > smin else smax.
+ *            Defaults smin = 0.1, smax = 1.2 (generate_topdown_map.py:51); qs_set_sweep_filter changes them for the
+ *            context (kept over qs_reset).
+ *   order    sweep k of a call owns the QS_SWEEP_SEQS sequence numbers seq0 + 46 k .. seq0 + 46 k + 45; beam i has stamp
+ *            ordinal 4 (seq0 + 46 k) + i + 1, so a later beam of a sweep wins a cell over an earlier one, and a later
+ *            packet of either kind over an earlier one.  Afterwards the context's next sequence number is seq0 + 46 n.
+ *   writes   grid stamps, hit / miss counters (enable_counts), dirty blocks (qs_dirty_tracking): nothing else.  Counters
+ *            QS_CNT_DATAGRAMS / ACCEPTED / RAYS / CELLS / HITS count sweeps and beams as they count packets and rays.
+ *   trig     exact_trig: beams whose end point lies in the 1e-9 edge band are resolved on the host with libm, as rays are.
+ * Any n: the call is split into chunks internally.  QS_E_INVAL for another stride, seq_stride > 1 or shard_bots > 0
+ * (sharded sweeps are not supported).  After a sweep call qs_last_batch / qs_last_hits refuse (length mismatch);
+ * qs_last_sweeps returns per record the accepted flag and the pose used (NaN for rejected records). */
+#define QS_SWEEP_SIZE_V0 743
+#define QS_SWEEP_SIZE_V0_ODO 751
+#define QS_SWEEP_BEAMS 181
+#define QS_SWEEP_SEQS 46      /* sequence numbers per sweep: 184 stamp ordinals, beams in the first 181 */
+#define QS_SWEEP_SLOTS (4 * QS_SWEEP_SEQS)
+int qs_ingest_sweeps(qs_ctx *ctx, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0);
+/* same with device-resident inputs; asynchronous on the context's stream */
+int qs_ingest_sweeps_device(qs_ctx *ctx, const uint8_t *d_pkts, size_t n, size_t stride, const uint16_t *d_lens,
+                            uint64_t seq0);
+int qs_last_sweeps(qs_ctx *ctx, uint8_t *accepted, double *pose_xyyaw /* n x 3 */, size_t n);
+/* trust filter of the sweep beams: a hit when smin < d <= smax (finite, 0 <= smin < smax) */
+int qs_set_sweep_filter(qs_ctx *ctx, double smin, double smax);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

@@ -24,10 +24,15 @@ Workloads (--workload; "auto" picks by N):
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself (child processes, started
 before anything touches a GPU); under torchrun (RANK / WORLD_SIZE set) it is one rank.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline`, `cpu_baseline`, `parity_checked`.
---dump-outputs DIR also writes what the last timed step computed to DIR/*.npy; the inputs depend only on the arguments, so
-two builds run with the same arguments can be compared output for output.
-Exit code != 0 if the GPU results of the last step differ from the oracle's on the same stream.
+A plain run sets up, warms up, times the steps and prints ONE JSON line (rank 0): the driver's contract plus what the timed
+steps themselves yield (configuration, stage times, counters, `roofline` from those).  --dump-outputs DIR also writes what the
+last timed step computed to DIR/*.npy; the inputs depend only on the arguments, so two builds run with the same arguments can
+be compared output for output.
+--full also runs, after the same timed steps, everything the headline figure does not need: `cpu_baseline` (before the GPU is
+touched), `parity_checked` (the last step against the oracle on the same stream; exit code != 0 if they differ), the chain
+kernel's measured `latency_floor`, `roofline_streaming` (K2 / K3 micro-benches and the device copy rate), the 64-bot lines of
+the N = 1 default workload, and the replayed `same_workload_n1` of an N > 1 line.  --no-cpu-baseline / --no-micro leave the
+CPU legs (and with them parity and the 64-bot lines) / the micro-benches (and the 64-bot lines) out of a full run.
 """
 import argparse
 import hashlib
@@ -77,8 +82,11 @@ def parse(argv=None):
                          "all-gather + point-to-point exchange of the packed blocks + fold); allreduce = RCCL's dense all-reduce of "
                          "the whole map (the reference point); direct = dense point-to-point reduce-scatter + K3 fold + all-gather")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-micro", action="store_true", help="skip the K2 view / K3 fuse timings (N = 1 only anyway)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, parity against the oracle, the latency "
+                         "floor, the K2 / K3 micro-benches, the 64-bot lines (N = 1, c1), the replayed N = 1 line (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs (baselines and parity)")
+    ap.add_argument("--no-micro", action="store_true", help="with --full: skip the K2 view / K3 fuse timings (N = 1 only anyway)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="packets of the same stream timed on the CPU (0: one whole step; the reference's closure\n"
                          "search is O(landmarks) per landmark packet, so the rate depends on the length)")
@@ -536,10 +544,12 @@ def run_rank(args):
         return 2
     stream = make_stream(pkg, replay, wl, bots, B, G, rank, world, replicated)
     max_agent = bots * world if replicated else bots
+    cpu_legs = args.full and not args.no_cpu_baseline          # CPU baselines and the parity check
+    micro_legs = args.full and not args.no_micro
 
     # ---- CPU legs first: nothing below this block has touched a GPU yet, so worker processes may be forked ----------
     cpu, o_state = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_legs:
         cpu, o_state = cpu_baselines(stream, G, args.cpu_sample, bool(args.ekf), bots, bpg, wl)
 
     import torch
@@ -604,7 +614,7 @@ def run_rank(args):
 
     # ---- parity of what was just timed (last step) against the oracle on the same stream -----------------------------
     parity, parity_note = None, None
-    if not args.no_cpu_baseline:
+    if cpu_legs:
         from oracle import oracle as orc
         if world == 1:
             o = o_state
@@ -683,28 +693,29 @@ def run_rank(args):
             "committer_batches_per_launch" if free_running else "windows_per_launch": cnt["slam_windows"],
             "note": "achieved / peak / frac keep the HBM form the contract asks for (the step's D4 bytes over this kernel's time against "
                     "8 TB/s); the kernel is a recurrence bound by the dependent chain between two decisions, priced in latency_floor"}
-        try:
-            lat = m.diag_latencies()
-            # The shortest dependent chain one window's decision can be made of, each link at its latency MEASURED on this GPU by
-            # one workgroup (csrc/diag.hip).  Counts: pose + nine bucket addresses = 5 fp64 + 6 integer dependent
-            # VALU steps; distance test + select = 4 fp64 + 1 lane-to-scalar step; wave-wide minimum = 6 DPP steps + 1 readlane;
-            # winner's fields = 2 lane-to-scalar steps; closure arithmetic = 3 fp64 steps.
-            valu = 5 * lat["fma_f64"] + 6 * lat["dpp_step"] + 4 * lat["fma_f64"] + lat["readlane_step"] + 6 * lat["dpp_step"] + \
-                lat["readlane_step"] + 2 * lat["readlane_step"] + 3 * lat["fma_f64"]
-            floor = lat["barrier_5_waves"] + lat["lds_read"] + lat["l2_load"] + lat["lds_read"] + valu
-            roofline["latency_floor"] = {
-                "cycles_per_decision": floor, "achieved_cycles_per_decision": cyc_unit,
-                "achieved_over_floor": cyc_unit / floor, "frac_of_floor": floor / cyc_unit,
-                "floor_ms_per_launch": floor * (decisions if free_running else win / max(m.n_graphs, 1)) / (lat["clock_mhz"] * 1e3),
-                "chain": "1 workgroup barrier (5 waves; the windowed form's: the free-running form has none, its hand-over is an LDS "
-                         "word) + 1 LDS read (the events / the frontier) + 22 dependent VALU / cross-lane steps (pose -> nine bucket "
-                         "addresses; distance test; wave-wide minimum; winner; closure) + 1 L2 round trip (node rows) + 1 LDS write "
-                         "the next decision's consumer can see",
-                "measured_cycles": lat,
-                "source": "qs_diag_latencies (csrc/diag.hip), measured in this run; one decision per window is the minimum the "
-                          "recurrence allows (dual_bot_mapper.py:292-326: a closure moves every later pose of its agent)"}
-        except Exception as ex:                      # a diagnostic must never take the bench down
-            roofline["latency_floor"] = {"error": repr(ex)}
+        if args.full:                                    # the latency diagnostic is a run of its own
+            try:
+                lat = m.diag_latencies()
+                # The shortest dependent chain one window's decision can be made of, each link at its latency MEASURED on this GPU by
+                # one workgroup (csrc/diag.hip).  Counts: pose + nine bucket addresses = 5 fp64 + 6 integer dependent
+                # VALU steps; distance test + select = 4 fp64 + 1 lane-to-scalar step; wave-wide minimum = 6 DPP steps + 1 readlane;
+                # winner's fields = 2 lane-to-scalar steps; closure arithmetic = 3 fp64 steps.
+                valu = 5 * lat["fma_f64"] + 6 * lat["dpp_step"] + 4 * lat["fma_f64"] + lat["readlane_step"] + 6 * lat["dpp_step"] + \
+                    lat["readlane_step"] + 2 * lat["readlane_step"] + 3 * lat["fma_f64"]
+                floor = lat["barrier_5_waves"] + lat["lds_read"] + lat["l2_load"] + lat["lds_read"] + valu
+                roofline["latency_floor"] = {
+                    "cycles_per_decision": floor, "achieved_cycles_per_decision": cyc_unit,
+                    "achieved_over_floor": cyc_unit / floor, "frac_of_floor": floor / cyc_unit,
+                    "floor_ms_per_launch": floor * (decisions if free_running else win / max(m.n_graphs, 1)) / (lat["clock_mhz"] * 1e3),
+                    "chain": "1 workgroup barrier (5 waves; the windowed form's: the free-running form has none, its hand-over is an LDS "
+                             "word) + 1 LDS read (the events / the frontier) + 22 dependent VALU / cross-lane steps (pose -> nine bucket "
+                             "addresses; distance test; wave-wide minimum; winner; closure) + 1 L2 round trip (node rows) + 1 LDS write "
+                             "the next decision's consumer can see",
+                    "measured_cycles": lat,
+                    "source": "qs_diag_latencies (csrc/diag.hip), measured in this run; one decision per window is the minimum the "
+                              "recurrence allows (dual_bot_mapper.py:292-326: a closure moves every later pose of its agent)"}
+            except Exception as ex:                      # a diagnostic must never take the bench down
+                roofline["latency_floor"] = {"error": repr(ex)}
     else:
         roofline = {"bound": "hbm", "kernel": raycast_entry["kernel"], "achieved": ray_alg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": ray_alg_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": ray_ms,
@@ -714,7 +725,7 @@ def run_rank(args):
 
     micro = None
     copy_gbs = 0.0
-    if rank == 0 and world == 1 and not args.no_micro:
+    if rank == 0 and world == 1 and micro_legs:
         copy_gbs = measured_copy_gbs(torch, dev)
         micro = micro_benches(pkg, torch, dev, m, G)
     rc = 0
@@ -759,7 +770,7 @@ def run_rank(args):
             "roofline_raycast": raycast_entry,
             "parity_checked": parity, "parity_scope": parity_note,
         }
-        if world > 1:
+        if world > 1 and args.full:
             # The N = 1 default is configs[1] (2 bots); this line is configs[3] (64 bots per GPU).  For a scaling figure on ONE
             # workload, the same 64-bot workload at N = 1 -- replayed from the committed run, not measured now.
             ref = os.path.join(ROOT, "profiles", PROFILE_ROUND, f"bench_{wl}{'' if G == 4096 else '_' + str(G)}.json")
@@ -774,7 +785,7 @@ def run_rank(args):
         if micro is not None:
             out["roofline_streaming"] = micro
             out["copy_peak_measured_gbs"] = copy_gbs
-        if world == 1 and wl == "c1" and micro is not None and not args.no_cpu_baseline:
+        if world == 1 and wl == "c1" and micro is not None and cpu_legs:
             out["configs2_64_bots"] = secondary_64_bots(pkg, replay, torch, dev, side, args, G, counts, bpg=2, steps=20, warm=3)
             out["configs2_64_bots_one_graph"] = secondary_64_bots(pkg, replay, torch, dev, side, args, G, counts, bpg=0, steps=5, warm=1)
             if out["configs2_64_bots"]["parity_checked"] is False or out["configs2_64_bots_one_graph"]["parity_checked"] is False:

@@ -1329,7 +1329,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(extra):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rehearse-on-one-gpu",
-           "--batch", "65536", "--steps", "1", "--warmup", "1", "--no-micro"] + extra
+           "--batch", "65536", "--steps", "1", "--warmup", "1", "--full", "--no-micro"] + extra
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1339,19 +1339,20 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(extra):
 
 def test_bench_dump_outputs_same_in_every_run(tmp_path):
     """bench.py --dump-outputs: the last timed step's results, read back after the steps --steps asked for; every step starts
-    from a fresh session, so a run of 3 steps (parity checked) and a run of 1 step dump the same arrays, and the dumped
+    from a fresh session, so a --full run of 3 steps (parity checked) and a plain run of 1 step dump the same arrays, and the dumped
     closure and landmark lists agree with the step's counters."""
     import json
     import subprocess
     import sys
     recs = []
-    for name, extra in (("a", ["--steps", "3", "--warmup", "1"]), ("b", ["--steps", "1", "--warmup", "0", "--no-cpu-baseline"])):
+    for name, extra in (("a", ["--steps", "3", "--warmup", "1", "--full"]), ("b", ["--steps", "1", "--warmup", "0"])):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "65536", "--no-micro",
                "--dump-outputs", str(tmp_path / name)] + extra
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-3000:]
         recs.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
     assert recs[0]["steps"] == 3 and recs[1]["steps"] == 1 and recs[0]["parity_checked"] is True
+    assert recs[1]["parity_checked"] is None and "cpu_baseline" not in recs[1]     # the plain run left the oracle out
     assert all(r["ms_per_step"] > 0 and r["outputs_dumped"]["bytes"] < 64e6 for r in recs)
     names = sorted(os.listdir(tmp_path / "a"))
     assert names == sorted(os.listdir(tmp_path / "b")) and "grid_cells.npy" in names and "ekf_x.npy" in names

@@ -279,7 +279,7 @@ def test_bench_ranks_rehearsed_on_one_gpu_sparse(extra):
     oracle grids) must hold and the line must say what the fuse moved."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "gloo", "--rehearse-on-one-gpu",
-           "--batch", "32768", "--steps", "2", "--warmup", "1", "--no-micro"] + extra
+           "--batch", "32768", "--steps", "2", "--warmup", "1", "--full", "--no-micro"] + extra
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

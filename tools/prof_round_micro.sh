@@ -22,7 +22,7 @@ with open(f"{out}/{dst}", "w", newline="") as o:
 PY
 }
 O=gpurun_out/${QS_PROF_ROUND:-r03}/c1_micro; rm -rf $O; mkdir -p $O
-A="--steps 3 --warmup 1 --no-cpu-baseline"
+A="--steps 3 --warmup 1 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py $A > $O/bench_under_trace.json 2> $O/trace.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -- python3 bench.py $A > /dev/null 2> $O/f.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -- python3 bench.py $A > /dev/null 2> $O/w.err

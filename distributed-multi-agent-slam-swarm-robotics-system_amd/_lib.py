@@ -133,6 +133,8 @@ SIGNATURES = {
     "qs_ekf_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32]),
     "qs_ekf_state": (_i32, [_vp, _i32, _vp, _vp]),
     "qs_counters": (_i32, [_vp, _vp]),
+    "qs_checkpoint": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "qs_restore": (_i32, [_vp, _vp, _sz]),
     "qs_timing_enable": (_i32, [_vp, _i32]),
     "qs_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
 }

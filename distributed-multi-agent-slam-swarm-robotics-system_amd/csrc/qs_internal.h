@@ -94,6 +94,15 @@ struct QsGeom {
 // bit of the block that holds cell (x, y): word index and mask
 __host__ __device__ inline size_t qs_dirty_word(int x, int y, int pitch) { return (size_t)(y / QS_DIRTY_BLOCK_H) * pitch + (x / QS_DIRTY_BLOCK_W) / 32; }
 __host__ __device__ inline unsigned int qs_dirty_mask(int x) { return 1u << ((x / QS_DIRTY_BLOCK_W) & 31); }
+// cell of lane `lane` (one lane per cell) of block `bid` = bit index in the bitmap (row by, column bx): false beyond the
+// grid's right edge
+__device__ inline bool qs_block_cell(unsigned int bid, int lane, int pitch, int size, size_t &cell)
+{
+    const int by = (int)(bid / (unsigned int)(pitch * 32)), bx = (int)(bid % (unsigned int)(pitch * 32));
+    const int x = bx * QS_DIRTY_BLOCK_W + (lane & (QS_DIRTY_BLOCK_W - 1)), y = by * QS_DIRTY_BLOCK_H + (lane >> 4);
+    cell = (size_t)y * size + x;
+    return x < size && y < size;
+}
 
 // a ray left to the host (exact-trig mode): everything needed to cast it later, whatever has happened to its batch since
 // device words read by the host at synchronisation points (qs_ctx::d_flags; qs_reset clears the first four)
@@ -228,6 +237,8 @@ struct qs_ctx {
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
+    DevBuf<unsigned int> ck_census;              // checkpoint (checkpoint.hip): block bitmap, block list, count
+    DevBuf<unsigned char> ck_stage;              //   ... and the body of the file as it travels (both ways)
     DevBuf<unsigned char> sweep_hv;              // servo sweeps (sweep.hip): hit flags of one chunk's ray slots
     DevBuf<unsigned char> sweep_acc;             //   ... accepted flag and pose of every record of the last call
     DevBuf<double> sweep_pose;
@@ -285,6 +296,9 @@ hipError_t qs_launch_decode(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
 // slam.hip
 hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose = false);
 hipError_t qs_launch_slam_reset_index(qs_ctx *c);              // empties the bucket index of every graph (what was used of it)
+// a graph's uploaded landmark log (qs_restore) and the counters that go with it
+struct QsIndexLog { const double *x, *y; const long long *idx; const unsigned char *type; long long n, n_nodes, n_cls; };
+hipError_t qs_launch_slam_rebuild_index(qs_ctx *c, const QsIndexLog *d_logs);   // [n_graphs], into graphs just reset
 int qs_slam_blocks(size_t n);
 // raycast.hip
 #define QS_DIRECT_MAX_BATCH 256   // raycast_mode auto: batches up to this size take the direct kernel
@@ -326,6 +340,15 @@ hipError_t qs_launch_sf_restore(qs_ctx *c);
 hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst);
 hipError_t qs_launch_sf_apply(qs_ctx *c);
 hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out);
+hipError_t qs_launch_sf_list_of(qs_ctx *c, const unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
+                                unsigned int *count);
+// checkpoint.hip: blocks of QS_DIRTY_BLOCK_H x QS_DIRTY_BLOCK_W cells; planes 1 = stamps, 2 = + counters, 4 = + sent + fused
+size_t qs_ck_block_bytes(int planes);
+hipError_t qs_launch_ck_census(qs_ctx *c, unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
+                               unsigned int *count);
+hipError_t qs_launch_ck_pack(qs_ctx *c, const unsigned int *list, unsigned int n_blocks, int pitch, int planes, unsigned char *dst);
+hipError_t qs_launch_ck_unpack(qs_ctx *c, const unsigned int *list, unsigned int n_blocks, int pitch, int planes,
+                               const unsigned char *src);
 // diag.hip
 hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out);
 // frontier.hip

@@ -1764,6 +1764,54 @@ hipError_t qs_launch_slam_reset_index(qs_ctx *c)
     return hipGetLastError();
 }
 
+// ---- restore (qs_restore): the bucket index rebuilt from an uploaded landmark log ----------------------------------------
+// One wave per graph walks the log 64 entries at a time through chain_insert_lanes -- the routine the chain kernels append
+// with -- from the counters a reset left.  The same code writes the log and the index again: the chains hold the same
+// entries in the same order, the side list is the same, and the pile test sees the same chain lengths (pool node numbers may
+// differ from the original's; no query answer depends on them).  Latency-bound: L / 64 dependent steps per graph, the next
+// chunk's entries loaded while this one is inserted.
+__global__ void __launch_bounds__(QS_WAVE)
+qs_slam_rebuild_index_kernel(QsGraphDev *__restrict__ graphs, QsBucketGeom bg, const QsIndexLog *__restrict__ logs,
+                             unsigned int *__restrict__ pile_flag)
+{
+    const int lane = threadIdx.x;
+    QsGraphDev *Gp = graphs + blockIdx.x;
+    const QsGraphDev G = *Gp;
+    const QsIndexLog L = logs[blockIdx.x];
+    long long n_lms = G.n_lms, n_misc = G.n_misc;
+    unsigned int pool = G.nodes_used;
+    bool pile = false;
+    auto load = [&](long long e, double &x, double &y, long long &idx, int &type) {
+        const bool in = e + lane < L.n;
+        x = in ? L.x[e + lane] : 0.0; y = in ? L.y[e + lane] : 0.0;
+        idx = in ? L.idx[e + lane] : LL_MAX; type = in ? (int)L.type[e + lane] : 0;
+    };
+    double x, y; long long idx; int type;
+    load(0, x, y, idx, type);
+    for (long long e = 0; e < L.n; e += QS_WAVE) {
+        double xn, yn; long long idxn; int typen;
+        load(e + QS_WAVE, xn, yn, idxn, typen);
+        const int k = (int)(L.n - e < QS_WAVE ? L.n - e : QS_WAVE);
+        const bool inw = lane < k;
+        int cx, cy;
+        const long long kb = (inw && bucket_cell(x, y, type, bg, cx, cy)) ? bucket_key(type, cx, cy, bg) : -1;
+        chain_insert_lanes(G, inw, lane, idx, kb, x, y, type, k, lane, n_lms, n_misc, pool, pile);
+        x = xn; y = yn; idx = idxn; type = typen;
+    }
+    if (lane == 0) {
+        Gp->n_nodes = L.n_nodes; Gp->n_cls = L.n_cls;
+        Gp->n_lms = n_lms; Gp->n_misc = n_misc; Gp->nodes_used = pool;
+        if (pile) *pile_flag = 1u;
+    }
+}
+hipError_t qs_launch_slam_rebuild_index(qs_ctx *c, const QsIndexLog *d_logs)
+{
+    if (c->n_graphs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(qs_slam_rebuild_index_kernel, dim3(c->n_graphs), dim3(QS_WAVE), 0, c->stream, c->d_graphs, c->bg, d_logs,
+                       c->d_flags + QS_FLAG_PILE);
+    return hipGetLastError();
+}
+
 hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
 {
     if (n == 0) return hipSuccess;

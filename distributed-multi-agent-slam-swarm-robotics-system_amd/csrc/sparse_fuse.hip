@@ -98,6 +98,13 @@ hipError_t qs_launch_sf_lists(qs_ctx *c)
                        c->geom.dirty_pitch, c->blocks_x, c->d_sf_lists, c->d_sf_counts);
     return hipGetLastError();
 }
+// one bitmap of the dirty-bitmap layout -> ascending block ids + count (the checkpoint's census, checkpoint.hip)
+hipError_t qs_launch_sf_list_of(qs_ctx *c, const unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
+                                unsigned int *count)
+{
+    hipLaunchKernelGGL(qs_sf_lists_kernel, dim3(1), dim3(SF_LIST_BLOCK), 0, c->stream, bitmap, words, pitch, blocks_x, list, count);
+    return hipGetLastError();
+}
 
 __global__ void __launch_bounds__(256)
 qs_sf_popcount_kernel(const unsigned int *__restrict__ bm, size_t words, int pitch, int blocks_x, unsigned long long *__restrict__ out)
@@ -121,15 +128,6 @@ hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out)
     return hipGetLastError();
 }
 
-// cell of lane `lane` of block `bid` (bit index in the bitmap: row by, column bx): false beyond the grid's right edge
-__device__ inline bool sf_cell(unsigned int bid, int lane, int pitch, int size, size_t &cell)
-{
-    const int by = (int)(bid / (unsigned int)(pitch * 32)), bx = (int)(bid % (unsigned int)(pitch * 32));
-    const int x = bx * SF_BW + (lane & (SF_BW - 1)), y = by * SF_BH + (lane >> 4);
-    cell = (size_t)y * size + x;
-    return x < size && y < size;
-}
-
 // ---- pack: one wave per block, one lane per cell ---------------------------------------------------------------------
 template <bool COUNTS>
 __global__ void __launch_bounds__(256)
@@ -142,7 +140,7 @@ qs_sf_pack_kernel(const unsigned int *__restrict__ list, unsigned int n_blocks, 
     constexpr size_t BB = SF_CELLS * (4 + (COUNTS ? 8 : 0));
     for (unsigned int k = wave; k < n_blocks; k += n_waves) {
         size_t cell;
-        const bool in = sf_cell(list[k], lane, pitch, size, cell);
+        const bool in = qs_block_cell(list[k], lane, pitch, size, cell);
         unsigned char *blk = dst + (size_t)k * BB;
         ((unsigned int *)blk)[lane] = in ? stamps[cell] : 0u;
         if (COUNTS) {
@@ -189,7 +187,7 @@ qs_sf_apply_kernel(SfPlan pl, const unsigned int *__restrict__ lists, size_t lis
         while (pl.first[s + 1] <= t) s++;                                  // (t ascends: the search never goes back)
         const unsigned int k = t - pl.first[s];
         size_t cell;
-        const bool in = sf_cell(lists[(size_t)s * list_stride + k], lane, pitch, size, cell);
+        const bool in = qs_block_cell(lists[(size_t)s * list_stride + k], lane, pitch, size, cell);
         const unsigned char *blk = payload + pl.off[s] + (size_t)k * BB;
         if (s != pl.rank) {                                                  // own stamps are in place
             const unsigned int v = ((const unsigned int *)blk)[lane];

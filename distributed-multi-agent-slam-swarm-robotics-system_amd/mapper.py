@@ -7,6 +7,9 @@ renderer and timers read -- `OccupancyGrid` (:110-237), `PoseGraphSLAM` (:261-33
 marshals buffers (numpy <-> C ABI).
 """
 import ctypes as C
+import os
+import struct
+import zlib
 
 import numpy as np
 
@@ -19,6 +22,54 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+# ---- checkpoint file header (include/quasar_slam.h: "checkpoint / restore") ------------------------------------------------
+CKPT_MAGIC = b"QSCK"
+CKPT_VERSION = 1
+CKPT_HEADER_FIXED = 144
+CKPT_SECTIONS = {1: "scalars", 2: "bots", 3: "counters", 4: "graphs", 5: "block_ids", 6: "blocks", 7: "dirty"}
+_CKPT_HEAD = struct.Struct("<4sIIIQII")                  # magic, version, header_bytes, n_sections, total_bytes, crc32, reserved
+_CKPT_INTS = ("size", "min_poses_between", "max_agent", "bots_per_graph", "enable_counts", "enable_ekf", "seq_stride",
+              "shard_bots", "shard_rank", "exact_trig", "dirty_tracking")
+_CKPT_F64 = ("res", "ox", "oy", "min_dist", "max_dist", "closure_radius", "closure_correction", "ekf_metres_per_tick")
+_CKPT_CFG = struct.Struct("<12i8d")
+_CKPT_SEC = struct.Struct("<IIQQ")
+
+
+def checkpoint_config(data):
+    """The header of a checkpoint (QuasarMapper.checkpoint / save) as a dict: the configuration it was taken with, the format
+    version, the total length, the sections {name: (offset, length)} and the number of grid blocks.  Checks magic, version,
+    lengths and the CRC-32 of the body (ValueError); needs no GPU."""
+    mv = memoryview(data).cast("B")
+    if len(mv) < CKPT_HEADER_FIXED:
+        raise ValueError(f"checkpoint: truncated header ({len(mv)} bytes)")
+    magic, version, hb, n_sec, total, crc, _ = _CKPT_HEAD.unpack_from(mv, 0)
+    if magic != CKPT_MAGIC:
+        raise ValueError("checkpoint: bad magic (not a checkpoint)")
+    if version != CKPT_VERSION:
+        raise ValueError(f"checkpoint: unknown format version {version} (this reader knows {CKPT_VERSION})")
+    if n_sec not in (6, 7) or hb != CKPT_HEADER_FIXED + _CKPT_SEC.size * n_sec or len(mv) < hb:
+        raise ValueError("checkpoint: bad header or section table")
+    if total != len(mv):
+        raise ValueError(f"checkpoint: length {len(mv)} does not match the header's {total} (truncated?)")
+    if zlib.crc32(mv[hb:]) != crc:
+        raise ValueError("checkpoint: CRC mismatch (corrupted checkpoint)")
+    vals = _CKPT_CFG.unpack_from(mv, 32)
+    out = dict(zip(_CKPT_INTS, vals[:11]))
+    out.update(zip(_CKPT_F64, vals[12:]))
+    for k in ("enable_counts", "enable_ekf", "exact_trig", "dirty_tracking"):
+        out[k] = bool(out[k])
+    sections = {}
+    for i in range(n_sec):
+        kind, _, off, length = _CKPT_SEC.unpack_from(mv, CKPT_HEADER_FIXED + _CKPT_SEC.size * i)
+        if kind not in CKPT_SECTIONS or CKPT_SECTIONS[kind] in sections or off < hb or off % 8 or off + length > total:
+            raise ValueError(f"checkpoint: bad section table entry {i}")
+        sections[CKPT_SECTIONS[kind]] = (off, length)
+    if "block_ids" not in sections:
+        raise ValueError("checkpoint: no block list")
+    out.update(version=version, total_bytes=total, sections=sections, n_blocks=sections["block_ids"][1] // 4)
+    return out
+
+
 class QuasarMapper:
     """One mapper instance on one GPU.  Defaults are the reference's constants."""
 
@@ -27,7 +78,7 @@ class QuasarMapper:
                  enable_counts=True, enable_ekf=False, device=0, raycast_mode=0,
                  ekf_metres_per_tick=0.0107, min_poses_between=P.MIN_POSES_BETWEEN,
                  closure_radius=P.CLOSURE_RADIUS, closure_correction=P.CLOSURE_CORRECTION,
-                 seq_stride=1, shard_bots=0, shard_rank=0, exact_trig=True):
+                 seq_stride=1, shard_bots=0, shard_rank=0, exact_trig=True, min_dist=None, max_dist=None):
         self._L = _lib.load()
         cfg = QsConfig()
         check(None, self._L.qs_config_default(C.byref(cfg)), "qs_config_default")
@@ -42,6 +93,10 @@ class QuasarMapper:
         cfg.seq_stride = seq_stride
         cfg.shard_bots, cfg.shard_rank = shard_bots, shard_rank
         cfg.exact_trig = int(bool(exact_trig))
+        if min_dist is not None:
+            cfg.min_dist = min_dist
+        if max_dist is not None:
+            cfg.max_dist = max_dist
         self.cfg = cfg
         self.size, self.res, self.ox, self.oy = size, resolution, origin_x, origin_y
         self.max_agent = max_agent
@@ -84,6 +139,61 @@ class QuasarMapper:
 
     def sync(self):
         self._chk(self._L.qs_sync(self._h), "qs_sync")
+
+    # -- checkpoint / restore (include/quasar_slam.h) ------------------------------------------------------------------------
+    def checkpoint(self) -> bytes:
+        """The session state as bytes (qs_checkpoint): a fresh context restored from them answers every later call as this
+        one would."""
+        n = C.c_size_t()
+        self._chk(self._L.qs_checkpoint(self._h, None, 0, C.byref(n)), "qs_checkpoint")
+        buf = np.empty(n.value, dtype=np.uint8)
+        self._chk(self._L.qs_checkpoint(self._h, _ptr(buf), n.value, C.byref(n)), "qs_checkpoint")
+        return buf[:n.value].tobytes()
+
+    def restore(self, data):
+        """Load a checkpoint into this context (qs_restore; its configuration must match).  A refused restore leaves the
+        context as it was."""
+        a = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
+        self._chk(self._L.qs_restore(self._h, _ptr(a), len(a)), "qs_restore")
+        self._map_version += 1
+        self._last_n = 0
+        self._last_sweeps_n = 0
+
+    def save(self, path):
+        """checkpoint() written atomically: a temporary file beside `path`, fsync, then os.replace."""
+        data = self.checkpoint()
+        path = os.fspath(path)
+        tmp = f"{path}.tmp-{os.getpid()}"
+        try:
+            with open(tmp, "wb") as f:
+                f.write(data)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return len(data)
+
+    @classmethod
+    def load(cls, path, device=0, raycast_mode=0):
+        """A mapper built from the configuration in the checkpoint's header, with the checkpoint restored into it."""
+        with open(path, "rb") as f:
+            data = f.read()
+        k = checkpoint_config(data)
+        m = cls(k["size"], k["res"], k["ox"], k["oy"], max_agent=k["max_agent"], bots_per_graph=k["bots_per_graph"],
+                enable_counts=k["enable_counts"], enable_ekf=k["enable_ekf"], device=device, raycast_mode=raycast_mode,
+                ekf_metres_per_tick=k["ekf_metres_per_tick"], min_poses_between=k["min_poses_between"],
+                closure_radius=k["closure_radius"], closure_correction=k["closure_correction"], seq_stride=k["seq_stride"],
+                shard_bots=k["shard_bots"], shard_rank=k["shard_rank"], exact_trig=k["exact_trig"],
+                min_dist=k["min_dist"], max_dist=k["max_dist"])
+        try:
+            m.restore(data)
+        except BaseException:
+            m.close()
+            raise
+        return m
 
     def set_stream(self, hip_stream_ptr):
         self._chk(self._L.qs_set_stream(self._h, C.c_void_p(hip_stream_ptr)), "qs_set_stream")

@@ -355,6 +355,59 @@ int qs_ekf_step(qs_ctx *ctx, const int32_t *bot_ids, const double *omega_m, cons
                 const double *z_v, const double *z_omega, size_t n, int32_t do_update);
 int qs_ekf_state(qs_ctx *ctx, int32_t bot, double x[6], double P[36]);
 
+/* ---- checkpoint / restore ------------------------------------------------------------------------------------------------
+ * qs_checkpoint writes the session state of a context into a byte buffer; qs_restore loads it into a context whose
+ * configuration matches.  From then on every call on the restored context returns bit for bit what it would have returned on
+ * the original given the same later calls: ingests (packets, sweeps), grid / counter / log-odds views, closures, closure
+ * agents, landmarks, sizes, drift, zones, EKF state, frontiers and targets, qs_counters, both fuses.
+ *   saved      the grid as blocks of QS_DIRTY_BLOCK_H x QS_DIRTY_BLOCK_W cells (the sparse fuse's), each block that holds
+ *              anything: its stamps and counters (enable_counts), with dirty tracking also the sparse fuse's "sent" and fused
+ *              counters, and the live dirty bitmap; the dirty_since_fuse flag, and with tracking the counts view; per bot the
+ *              offset, drift, last closure, zone box words, EKF state (44 words) and previous values (4 words); per pose graph
+ *              the node count, the landmark log and the closure log; the sequence counter, stamp epoch and rebase count; the
+ *              sweep filter; the exact-trig totals; every QS_CNT_* counter.
+ *   not saved  (as after qs_reset) the resident last batch (qs_last_batch / qs_last_hits / qs_last_sweeps refuse), workspaces,
+ *              timing, the chain form and QS_CHAIN_AUTO's running choice (every form gives the same closures), and the dense
+ *              fuse's counter snapshot (the counts view reads the local counters until the next fuse).  The landmark bucket
+ *              index is not in the file: qs_restore rebuilds it on the device from the landmark log.
+ *   checkpoint observes the map (resolves waiting exact-trig rays first) and waits for the GPU.  buf == NULL: *n_out = the
+ *              size, nothing written.  cap < size: QS_E_RANGE (*n_out = the size).  QS_E_STATE while a sparse fuse is in
+ *              flight, or when a loop-closure chain wait has timed out (bit 40 of QS_CNT_SLAM_ROUNDS): such a map may be wrong.
+ *   restore    everything is checked on the host before anything changes: magic, version, lengths, CRC, block ids, and the
+ *              configuration fields size, res, ox, oy, min_dist, max_dist, closure_radius, min_poses_between,
+ *              closure_correction, max_agent, bots_per_graph, enable_counts, enable_ekf, ekf_metres_per_tick, seq_stride,
+ *              shard_bots, shard_rank, exact_trig (device, raycast_mode and separation may differ).  A refused restore leaves
+ *              the context as it was: QS_E_INVAL (qs_last_error names the first field that differs, or the failed check),
+ *              QS_E_STATE while a sparse fuse is in flight.  A HIP failure after that leaves the context reset.  Dirty
+ *              tracking of the context is switched to the checkpoint's.
+ * Format (version 1), little-endian, every section at an 8-byte aligned offset:
+ *   header   0  char magic[4] = "QSCK"     4  u32 version        8  u32 header_bytes (= 144 + 24 n_sections)
+ *           12  u32 n_sections            16  u64 total_bytes   24  u32 crc32 of bytes [header_bytes, total_bytes) (zlib's)
+ *           28  u32 reserved
+ *           32  i32 size, min_poses_between, max_agent, bots_per_graph, enable_counts, enable_ekf, seq_stride, shard_bots,
+ *               shard_rank, exact_trig, dirty_tracking, reserved
+ *           80  f64 res, ox, oy, min_dist, max_dist, closure_radius, closure_correction, ekf_metres_per_tick
+ *          144  section table: n_sections x {u32 kind, u32 reserved, u64 offset, u64 length}
+ *   SCALARS    u64 next_seq, epoch_base, n_rebases, edge_rays, edge_overflow; f64 sweep_min, sweep_max;
+ *              u32 dirty_since_fuse, counts_view_fused, n_graphs, n_bots (= max_agent + 1)                        72 bytes
+ *   BOTS       n_bots x: f64 offset; f64 drift[2]; i64 last_closure; u64 zone[4]; f64 ekf[44]; f64 ekf_prev[4], as six
+ *              arrays in that order (all bots' offsets, then all drifts, ...)
+ *   COUNTERS   u64[QS_CNT_N] as the device holds them (QS_CNT_REBASES / EDGE_* come from SCALARS)
+ *   GRAPHS     n_graphs x {i64 n_nodes, n_landmarks, n_closures}, then per graph: landmark log f64 x[L], f64 y[L],
+ *              i64 node[L], u8 type[L] (padded to 8), closure log i64 landmark[C], i64 node[C], f64 dx[C], f64 dy[C],
+ *              u8 agent[C] (padded to 8)
+ *   BLOCK_IDS  u32[n_blocks], ascending: block (bx, by) is by * 32 * pitch + bx, pitch = ceil(ceil(size / 16) / 32)
+ *   BLOCKS     per block, cells row-major (lane = 16 * row + column): u32 stamps[64]; enable_counts: u64 counters[64];
+ *              enable_counts and dirty_tracking: u64 sent[64], u64 fused[64].  Cells beyond the grid's edge are 0.
+ *   DIRTY      dirty_tracking only: u32[ceil(size / 4) * pitch], the live dirty bitmap
+ * A version the library does not know is refused. */
+#define QS_CKPT_MAGIC "QSCK"
+#define QS_CKPT_VERSION 1
+#define QS_CKPT_HEADER_FIXED 144
+enum { QS_CKPT_SCALARS = 1, QS_CKPT_BOTS, QS_CKPT_COUNTERS, QS_CKPT_GRAPHS, QS_CKPT_BLOCK_IDS, QS_CKPT_BLOCKS, QS_CKPT_DIRTY };
+int qs_checkpoint(qs_ctx *ctx, uint8_t *buf, size_t cap, size_t *n_out);
+int qs_restore(qs_ctx *ctx, const uint8_t *buf, size_t n);
+
 /* ---- counters / timing ------------------------------------------------------------------ */
 enum { QS_CNT_DATAGRAMS = 0, QS_CNT_ACCEPTED, QS_CNT_RAYS, QS_CNT_CELLS, QS_CNT_HITS,
        QS_CNT_CLOSURES, QS_CNT_LANDMARKS, QS_CNT_REBASES, QS_CNT_SLAM_WINDOWS, QS_CNT_SLAM_ROUNDS,

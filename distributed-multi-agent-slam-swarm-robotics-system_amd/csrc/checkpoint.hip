@@ -44,15 +44,15 @@ hipError_t qs_launch_ck_census(qs_ctx *c, unsigned int *bitmap, size_t words, in
 {
     const size_t nb = words * sizeof(unsigned int);
     // tracking on: the live dirty bitmap (same geometry) is where the census starts -- blocks marked but all zero included
-    hipError_t e = c->d_dirty ? hipMemcpyAsync(bitmap, c->d_dirty, nb, hipMemcpyDeviceToDevice, c->stream)
+    hipError_t e = c->d_dirty.p ? hipMemcpyAsync(bitmap, c->d_dirty.p, nb, hipMemcpyDeviceToDevice, c->stream)
                               : hipMemsetAsync(bitmap, 0, nb, c->stream);
     if (e != hipSuccess) return e;
     const size_t quads = c->cells / 4;
-    const bool sparse = c->d_dirty && c->d_counts;
+    const bool sparse = c->d_dirty.p && c->d_counts.p;
     const unsigned int blocks = (unsigned int)std::min<size_t>((quads + 255) / 256, 2048);
-    hipLaunchKernelGGL(qs_ck_census_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)c->d_stamps,
-                       (const ulonglong2 *)c->d_counts, (const ulonglong2 *)(sparse ? c->d_counts_sent : nullptr),
-                       (const ulonglong2 *)(sparse ? c->d_counts_fused : nullptr), c->cfg.size, quads, pitch, bitmap);
+    hipLaunchKernelGGL(qs_ck_census_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)c->d_stamps.p,
+                       (const ulonglong2 *)c->d_counts.p, (const ulonglong2 *)(sparse ? c->d_counts_sent.p : nullptr),
+                       (const ulonglong2 *)(sparse ? c->d_counts_fused.p : nullptr), c->cfg.size, quads, pitch, bitmap);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return qs_launch_sf_list_of(c, bitmap, words, pitch, blocks_x, list, count);
@@ -105,7 +105,7 @@ hipError_t qs_launch_ck_pack(qs_ctx *c, const unsigned int *list, unsigned int n
     if (n_blocks == 0) return hipSuccess;
     const unsigned int blocks = (n_blocks + 3) / 4 < 4096 ? (n_blocks + 3) / 4 : 4096;
     hipLaunchKernelGGL(qs_ck_pack_kernel, dim3(blocks), dim3(256), 0, c->stream, list, n_blocks, pitch, c->cfg.size, planes,
-                       c->d_stamps, c->d_counts, c->d_counts_sent, c->d_counts_fused, dst);
+                       c->d_stamps.p, c->d_counts.p, c->d_counts_sent.p, c->d_counts_fused.p, dst);
     return hipGetLastError();
 }
 hipError_t qs_launch_ck_unpack(qs_ctx *c, const unsigned int *list, unsigned int n_blocks, int pitch, int planes,
@@ -114,6 +114,6 @@ hipError_t qs_launch_ck_unpack(qs_ctx *c, const unsigned int *list, unsigned int
     if (n_blocks == 0) return hipSuccess;
     const unsigned int blocks = (n_blocks + 3) / 4 < 4096 ? (n_blocks + 3) / 4 : 4096;
     hipLaunchKernelGGL(qs_ck_unpack_kernel, dim3(blocks), dim3(256), 0, c->stream, list, n_blocks, pitch, c->cfg.size, planes, src,
-                       c->d_stamps, c->d_counts, c->d_counts_sent, c->d_counts_fused);
+                       c->d_stamps.p, c->d_counts.p, c->d_counts_sent.p, c->d_counts_fused.p);
     return hipGetLastError();
 }

@@ -190,11 +190,11 @@ hipError_t qs_launch_decode(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
     const unsigned int blocks = (unsigned int)((n + DEC_BLOCK - 1) / DEC_BLOCK);
     if (stride <= DEC_MAX_STRIDE)
         hipLaunchKernelGGL(qs_decode_kernel, dim3((blocks + DEC_TILES - 1) / DEC_TILES), dim3(DEC_BLOCK), 0, c->stream, d_pkts, n,
-                           stride, d_lens, c->d_offset, c->cfg.max_agent, c->bots_per_graph,
-                           c->n_graphs, c->b, c->d_graph_batch, c->sb.agent_ev, c->d_counters);
+                           stride, d_lens, c->d_offset.p, c->cfg.max_agent, c->bots_per_graph,
+                           c->n_graphs, c->b, c->d_graph_batch.p, c->sb.agent_ev, c->d_counters.p);
     else
         hipLaunchKernelGGL(qs_decode_wide_kernel, dim3(blocks), dim3(DEC_BLOCK), 0, c->stream, d_pkts,
-                           n, stride, d_lens, c->d_offset, c->cfg.max_agent, c->bots_per_graph, c->b,
-                           c->d_graph_batch, c->sb.agent_ev, c->d_counters);
+                           n, stride, d_lens, c->d_offset.p, c->cfg.max_agent, c->bots_per_graph, c->b,
+                           c->d_graph_batch.p, c->sb.agent_ev, c->d_counters.p);
     return hipGetLastError();
 }

@@ -333,7 +333,7 @@ hipError_t qs_launch_ekf_ingest(qs_ctx *c, size_t n, const double *d_time, hipSt
     if (n == 0) return hipSuccess;
     const int waves = EKF_BLOCK / QS_WAVE;
     hipLaunchKernelGGL(qs_ekf_ingest_kernel, dim3((c->cfg.max_agent + waves - 1) / waves), dim3(EKF_BLOCK), 0,
-                       st, n, c->b, d_time, (double)c->next_seq, c->d_ekf, c->d_ekf_prev, c->cfg.max_agent,
+                       st, n, c->b, d_time, (double)c->next_seq, c->d_ekf.p, c->d_ekf_prev.p, c->cfg.max_agent,
                        c->cfg.ekf_metres_per_tick);
     return hipGetLastError();
 }
@@ -360,6 +360,6 @@ hipError_t qs_launch_ekf_step(qs_ctx *c, const int *d_bots, const double *d_omeg
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(qs_ekf_step_kernel, dim3((unsigned int)((n + 63) / 64)), dim3(64), 0, c->stream, d_bots,
-                       d_omega, d_t, d_zv, d_zo, n, do_update, c->cfg.max_agent, c->d_ekf);
+                       d_omega, d_t, d_zv, d_zo, n, do_update, c->cfg.max_agent, c->d_ekf.p);
     return hipGetLastError();
 }

@@ -809,8 +809,6 @@ es_fold_kernel(EsWs ws, QsBatch b, const double *__restrict__ recv_time, double 
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-static inline size_t es_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static size_t es_tiles(size_t n) { return (n + 16384 - 1) / 16384 + 1; }
 
 static size_t es_max_chunks(const qs_ctx *c, size_t n) { return n / ES_CHUNK_MIN + (size_t)c->cfg.max_agent + 2; }
@@ -824,36 +822,38 @@ static unsigned int es_chunk_for(const qs_ctx *c, size_t n)
     return ch;
 }
 
-size_t qs_ekf_scan_workspace_bytes(const qs_ctx *c, size_t n)
+// the workspace of batches up to cap records, carved from ws (nullptr: only the size); returns its bytes.  count and
+// cmax lead: one memset of the first `lead` bytes clears both.
+static size_t es_layout(const qs_ctx *c, void *ws, size_t cap, EsWs &w, size_t &lead)
 {
-    const size_t ch = es_max_chunks(c, n);
-    return es_align(256 * 4) + 2 * es_align(257 * 4) + es_align(n * 4) + es_align(257 * es_tiles(n) * 4) + es_align(n * sizeof(EsRec)) + es_align(ch * 8) +
-           es_align(ch * 8) + es_align(ch * sizeof(EsAgg1)) + es_align(ch * sizeof(EsStart)) + es_align(ch * sizeof(EsAgg2)) +
-           es_align(256 * 20 * 8);
+    const size_t ch = es_max_chunks(c, cap);
+    Carve k(ws);
+    w.count = k.take<unsigned int>(256);
+    w.cmax = k.take<unsigned long long>(ch);
+    lead = k.bytes;
+    w.base = k.take<unsigned int>(257);
+    w.chunk_base = k.take<unsigned int>(257);
+    w.idx = k.take<unsigned int>(cap);
+    w.tile_off = k.take<unsigned int>(257 * es_tiles(cap));
+    w.rec = k.take<EsRec>(cap);
+    w.last_in = k.take<double>(ch);
+    w.agg1 = k.take<EsAgg1>(ch);
+    w.start = k.take<EsStart>(ch);
+    w.agg2 = k.take<EsAgg2>(ch);
+    w.fin = k.take<double>(256 * 20);
+    return k.bytes;
 }
 
 hipError_t qs_launch_ekf_scan(qs_ctx *c, size_t n, const double *d_time, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    hipError_t e = c->ekf_ws.reserve(qs_ekf_scan_workspace_bytes(c, c->cap_batch), st);
-    if (e != hipSuccess) return e;
-    const size_t cap = c->cap_batch, ch = es_max_chunks(c, cap);
     EsWs ws;
+    size_t lead;
+    hipError_t e = c->ekf_ws.reserve(es_layout(c, nullptr, c->cap_batch, ws, lead), st);
+    if (e != hipSuccess) return e;
+    es_layout(c, c->ekf_ws.p, c->cap_batch, ws, lead);
     ws.chunk = es_chunk_for(c, n);
-    char *p = c->ekf_ws.p;
-    ws.count = (unsigned int *)p; p += es_align(256 * 4);
-    ws.cmax = (unsigned long long *)p; p += es_align(ch * 8);           // adjacent to count: one memset clears both
-    ws.base = (unsigned int *)p; p += es_align(257 * 4);
-    ws.chunk_base = (unsigned int *)p; p += es_align(257 * 4);
-    ws.idx = (unsigned int *)p; p += es_align(cap * 4);
-    ws.tile_off = (unsigned int *)p; p += es_align(257 * es_tiles(cap) * 4);
-    ws.rec = (EsRec *)p; p += es_align(cap * sizeof(EsRec));
-    ws.last_in = (double *)p; p += es_align(ch * 8);
-    ws.agg1 = (EsAgg1 *)p; p += es_align(ch * sizeof(EsAgg1));
-    ws.start = (EsStart *)p; p += es_align(ch * sizeof(EsStart));
-    ws.agg2 = (EsAgg2 *)p; p += es_align(ch * sizeof(EsAgg2));
-    ws.fin = (double *)p;
-    e = hipMemsetAsync(ws.count, 0, es_align(256 * 4) + es_align(ch * 8), st);
+    e = hipMemsetAsync(ws.count, 0, lead, st);
     if (e != hipSuccess) return e;
     const int ma = c->cfg.max_agent;
     const double t0 = (double)c->next_seq;
@@ -864,12 +864,12 @@ hipError_t qs_launch_ekf_scan(qs_ctx *c, size_t n, const double *d_time, hipStre
     hipLaunchKernelGGL(es_tile_scan_kernel, dim3(ma), dim3(QS_WAVE), 0, st, ws, n_tiles);
     hipLaunchKernelGGL(es_compact_kernel, dim3(n_tiles, ma), dim3(ES_CMP_BLOCK), 0, st, n, c->b, ws, n_tiles);
     hipLaunchKernelGGL(es_wire_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, n, c->b, d_time, t0, ws,
-                       c->d_ekf_prev, c->cfg.ekf_metres_per_tick);
-    hipLaunchKernelGGL(es_last_kernel, dim3((ma + 63) / 64), dim3(64), 0, st, ws, c->d_ekf, c->d_ekf_prev, ma);
+                       c->d_ekf_prev.p, c->cfg.ekf_metres_per_tick);
+    hipLaunchKernelGGL(es_last_kernel, dim3((ma + 63) / 64), dim3(64), 0, st, ws, c->d_ekf.p, c->d_ekf_prev.p, ma);
     hipLaunchKernelGGL(es_agg1_kernel, dim3((chunks + QS_WAVE - 1) / QS_WAVE), dim3(QS_WAVE), 0, st, ws);
-    hipLaunchKernelGGL(es_apply_kernel, dim3(ma), dim3(QS_WAVE), 0, st, ws, c->b, c->d_ekf, c->d_ekf_prev, ma);
+    hipLaunchKernelGGL(es_apply_kernel, dim3(ma), dim3(QS_WAVE), 0, st, ws, c->b, c->d_ekf.p, c->d_ekf_prev.p, ma);
     hipLaunchKernelGGL(es_agg2_kernel, dim3((chunks + QS_WAVE - 1) / QS_WAVE), dim3(QS_WAVE), 0, st, ws);
-    hipLaunchKernelGGL(es_fold_kernel, dim3(ma), dim3(QS_WAVE), 0, st, ws, c->b, d_time, t0, c->d_ekf, c->d_ekf_prev, ma,
-                       c->d_counters);
+    hipLaunchKernelGGL(es_fold_kernel, dim3(ma), dim3(QS_WAVE), 0, st, ws, c->b, d_time, t0, c->d_ekf.p, c->d_ekf_prev.p, ma,
+                       c->d_counters.p);
     return hipGetLastError();
 }

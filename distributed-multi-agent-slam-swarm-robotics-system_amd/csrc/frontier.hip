@@ -183,28 +183,33 @@ static inline unsigned int fr_blocks(size_t items)
     return (unsigned int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-// Workspace layout (bytes): label u32[cells] | cnt u32[cells] | sumx u64[cells] | sumy u64[cells] |
-// chunk u32[n_chunks] | total u64
-size_t qs_frontier_workspace_bytes(const qs_ctx *c)
+QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws)
 {
     const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
-    return cells * (4 + 4 + 8 + 8) + ((n_chunks * 4 + 15) & ~(size_t)15) + 16;
+    Carve k(ws);
+    QsFrLayout L;
+    L.label = k.take<unsigned int>(cells);
+    L.cnt = k.take<unsigned int>(cells);        // cnt .. sumy: one memset clears them (qs_launch_frontier_label)
+    L.sumx = k.take<unsigned long long>(cells);
+    L.sumy = k.take<unsigned long long>(cells);
+    L.chunk = k.take<unsigned int>(n_chunks);
+    L.total = k.take<unsigned long long>(1);
+    L.bytes = k.bytes;
+    return L;
 }
 
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters)
 {
     const size_t cells = c->cells;
-    unsigned int *label = (unsigned int *)ws;
-    unsigned int *cnt = label + cells;
-    unsigned long long *sumx = (unsigned long long *)(cnt + cells), *sumy = sumx + cells;
-    hipLaunchKernelGGL(qs_frontier_mask_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->d_stamps,
-                       c->cfg.size, label);
+    const QsFrLayout L = qs_frontier_layout(c, ws);
+    hipLaunchKernelGGL(qs_frontier_mask_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->d_stamps.p,
+                       c->cfg.size, L.label);
     if (with_clusters) {
-        hipError_t e = hipMemsetAsync(cnt, 0, cells * (4 + 8 + 8), c->stream);
+        hipError_t e = hipMemsetAsync(L.cnt, 0, (char *)(L.sumy + cells) - (char *)L.cnt, c->stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(qs_frontier_union_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->cfg.size, label);
-        hipLaunchKernelGGL(qs_frontier_stats_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->cfg.size, label,
-                           cnt, sumx, sumy);
+        hipLaunchKernelGGL(qs_frontier_union_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->cfg.size, L.label);
+        hipLaunchKernelGGL(qs_frontier_stats_kernel, dim3(fr_blocks(cells)), dim3(FR_BLOCK), 0, c->stream, c->cfg.size, L.label,
+                           L.cnt, L.sumx, L.sumy);
     }
     return hipGetLastError();
 }
@@ -213,15 +218,13 @@ hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters)
 hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap)
 {
     const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
-    unsigned int *label = (unsigned int *)ws;
-    unsigned int *cnt = label + cells;
-    unsigned long long *sumx = (unsigned long long *)(cnt + cells), *sumy = sumx + cells;
-    unsigned int *chunk = (unsigned int *)(sumy + cells);
-    unsigned long long *total = (unsigned long long *)((char *)chunk + ((n_chunks * 4 + 15) & ~(size_t)15));
+    const QsFrLayout L = qs_frontier_layout(c, ws);
+    unsigned int *label = L.label, *cnt = L.cnt, *chunk = L.chunk;
+    unsigned long long *sumx = L.sumx, *sumy = L.sumy;
     if (phase == 0) {
         if (mode == 0) hipLaunchKernelGGL(qs_frontier_count_kernel<0>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, cells, chunk);
         else hipLaunchKernelGGL(qs_frontier_count_kernel<1>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, cells, chunk);
-        hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, chunk, n_chunks, total);
+        hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, chunk, n_chunks, L.total);
     } else {
         if (mode == 0) hipLaunchKernelGGL(qs_frontier_write_kernel<0>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
         else if (mode == 2) hipLaunchKernelGGL(qs_frontier_write_kernel<2>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
@@ -230,28 +233,10 @@ hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, 
     return hipGetLastError();
 }
 
-void qs_frontier_ws_parts(const qs_ctx *c, void *ws, unsigned int **cnt, unsigned long long **sumx, unsigned long long **sumy,
-                          unsigned int **chunk, unsigned long long **total)
-{
-    const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
-    *cnt = (unsigned int *)ws + cells;
-    *sumx = (unsigned long long *)(*cnt + cells); *sumy = *sumx + cells;
-    *chunk = (unsigned int *)(*sumy + cells);
-    *total = (unsigned long long *)((char *)*chunk + ((n_chunks * 4 + 15) & ~(size_t)15));
-}
-
 // exclusive scan of the chunk counts a count kernel left in the workspace; the sum -> total
 hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws)
 {
-    unsigned int *cnt, *chunk; unsigned long long *sumx, *sumy, *total;
-    qs_frontier_ws_parts(c, ws, &cnt, &sumx, &sumy, &chunk, &total);
-    hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, chunk, (c->cells + FR_CHUNK - 1) / FR_CHUNK, total);
+    const QsFrLayout L = qs_frontier_layout(c, ws);
+    hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, L.chunk, (c->cells + FR_CHUNK - 1) / FR_CHUNK, L.total);
     return hipGetLastError();
-}
-
-unsigned long long *qs_frontier_total_ptr(const qs_ctx *c, void *ws)
-{
-    const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
-    char *chunk = (char *)ws + cells * 24;
-    return (unsigned long long *)(chunk + ((n_chunks * 4 + 15) & ~(size_t)15));
 }

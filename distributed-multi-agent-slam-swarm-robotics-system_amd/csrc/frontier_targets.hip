@@ -83,65 +83,42 @@ qs_ft_centroid_kernel(const unsigned int *__restrict__ cnt, const unsigned long 
 
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent)
 {
-    unsigned int *cnt, *chunk; unsigned long long *sumx, *sumy, *total;
-    qs_frontier_ws_parts(c, fr_ws, &cnt, &sumx, &sumy, &chunk, &total);
+    const QsFrLayout F = qs_frontier_layout(c, fr_ws);
     const size_t n_chunks = (c->cells + QS_FR_CHUNK - 1) / QS_FR_CHUNK;
     if (phase == 0) {
-        hipLaunchKernelGGL(qs_ft_count_kernel, dim3((unsigned int)n_chunks), dim3(256), 0, c->stream, cnt, c->cells, min_cluster, chunk);
+        hipLaunchKernelGGL(qs_ft_count_kernel, dim3((unsigned int)n_chunks), dim3(256), 0, c->stream, F.cnt, c->cells, min_cluster, F.chunk);
         hipError_t e = hipGetLastError();
         return e != hipSuccess ? e : qs_launch_frontier_scan(c, fr_ws);
     }
-    hipLaunchKernelGGL(qs_ft_centroid_kernel, dim3((unsigned int)n_chunks), dim3(256), 0, c->stream, cnt, sumx, sumy, c->cells,
-                       min_cluster, chunk, c->cfg.res, c->cfg.ox, c->cfg.oy, d_cent);
+    hipLaunchKernelGGL(qs_ft_centroid_kernel, dim3((unsigned int)n_chunks), dim3(256), 0, c->stream, F.cnt, F.sumx, F.sumy, c->cells,
+                       min_cluster, F.chunk, c->cfg.res, c->cfg.ox, c->cfg.oy, d_cent);
     return hipGetLastError();
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------
-struct FtLayout {
-    QsFtState *st;
-    double2 *cent, *bots, *tgt_xy, *asg_xy;
-    long long *tgt_idx;
-    int *asg_idx;
-    double *part_key; int *part_idx;      // [n_bots][n_chunks][K]
-    int *list_idx, *list_len;             // [n_bots][K], [n_bots]
-    double *fb_key; int *fb_idx;          // [n_fb]: per-block minima of a fallback scan
-    size_t bytes;
-};
-
 static inline size_t ft_chunks(size_t n_cent) { return (n_cent + FT_CHUNK - 1) / FT_CHUNK; }
 static inline size_t ft_fb_blocks(size_t n_cent) { return (n_cent + FT_FB_BLOCK - 1) / FT_FB_BLOCK; }
 
-static FtLayout ft_layout(void *ws, size_t n_cent, size_t n_bots)
+QsFtLayout qs_ft_layout(void *ws, size_t n_cent, size_t n_bots)
 {
-    FtLayout L{};
-    char *p = (char *)ws;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = p + off; off += (bytes + 255) & ~(size_t)255; return (void *)q; };
+    QsFtLayout L;
+    Carve k(ws);
     const size_t nk = n_bots * ft_chunks(n_cent) * FT_K, nfb = ft_fb_blocks(n_cent);
-    L.st = (QsFtState *)take(sizeof(QsFtState));
-    L.cent = (double2 *)take(n_cent * sizeof(double2));
-    L.bots = (double2 *)take(n_bots * sizeof(double2));
-    L.tgt_idx = (long long *)take(n_bots * sizeof(long long));
-    L.tgt_xy = (double2 *)take(n_bots * sizeof(double2));
-    L.asg_xy = (double2 *)take(n_bots * sizeof(double2));
-    L.asg_idx = (int *)take(n_bots * sizeof(int));
-    L.part_key = (double *)take(nk * sizeof(double));
-    L.part_idx = (int *)take(nk * sizeof(int));
-    L.list_idx = (int *)take(n_bots * FT_K * sizeof(int));
-    L.list_len = (int *)take(n_bots * sizeof(int));
-    L.fb_key = (double *)take(nfb * sizeof(double));
-    L.fb_idx = (int *)take(nfb * sizeof(int));
-    L.bytes = off;
+    L.st = k.take<QsFtState>(1);
+    L.cent = k.take<double2>(n_cent);
+    L.bots = k.take<double2>(n_bots);
+    L.tgt_idx = k.take<long long>(n_bots);
+    L.tgt_xy = k.take<double2>(n_bots);
+    L.asg_xy = k.take<double2>(n_bots);
+    L.asg_idx = k.take<int>(n_bots);
+    L.part_key = k.take<double>(nk);
+    L.part_idx = k.take<int>(nk);
+    L.list_idx = k.take<int>(n_bots * FT_K);
+    L.list_len = k.take<int>(n_bots);
+    L.fb_key = k.take<double>(nfb);
+    L.fb_idx = k.take<int>(nfb);
+    L.bytes = k.bytes;
     return L;
-}
-
-size_t qs_ft_workspace_bytes(size_t n_cent, size_t n_bots) { return ft_layout(nullptr, n_cent, n_bots).bytes; }
-
-void qs_ft_parts(void *ws, size_t n_cent, size_t n_bots, QsFtState **st, double2 **cent, double2 **bots, long long **tgt_idx,
-                 double2 **tgt_xy)
-{
-    const FtLayout L = ft_layout(ws, n_cent, n_bots);
-    *st = L.st; *cent = L.cent; *bots = L.bots; *tgt_idx = L.tgt_idx; *tgt_xy = L.tgt_xy;
 }
 
 // ---- the key and the wave-resident sorted list --------------------------------------------------------------
@@ -342,7 +319,7 @@ qs_ft_fallback_kernel(const double2 *__restrict__ cent, int n_cent, const double
 hipError_t qs_launch_ft_assign(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
                                int start_bot, int start_m, int fb_pending)
 {
-    const FtLayout L = ft_layout(ws, n_cent, n_bots);
+    const QsFtLayout L = qs_ft_layout(ws, n_cent, n_bots);
     const int nch = (int)ft_chunks(n_cent);
     if (start_bot == 0 && !fb_pending) {
         const unsigned int gy = (unsigned int)((n_bots + FT_BOTS_PER_BLOCK - 1) / FT_BOTS_PER_BLOCK);
@@ -360,7 +337,7 @@ hipError_t qs_launch_ft_assign(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots
 hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
                                  int bot, int m)
 {
-    const FtLayout L = ft_layout(ws, n_cent, n_bots);
+    const QsFtLayout L = qs_ft_layout(ws, n_cent, n_bots);
     hipLaunchKernelGGL(qs_ft_fallback_kernel, dim3((unsigned int)ft_fb_blocks(n_cent)), dim3(FT_FB_BLOCK), 0, c->stream,
                        L.cent, (int)n_cent, L.bots, bot, m, r2_sep, L.asg_xy, L.asg_idx, L.fb_key, L.fb_idx);
     return hipGetLastError();

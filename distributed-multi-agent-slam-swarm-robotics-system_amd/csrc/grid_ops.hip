@@ -44,7 +44,7 @@ hipError_t qs_launch_view_i8(qs_ctx *c, signed char *out_dev)
 {
     const size_t n16 = c->cells / 16;
     hipLaunchKernelGGL(qs_view_i8_kernel, dim3(go_blocks(n16 ? n16 : c->cells)), dim3(GO_BLOCK), 0, c->stream,
-                       (const uint4 *)c->d_stamps, n16, (uint4 *)out_dev, c->d_stamps, c->cells, out_dev);
+                       (const uint4 *)c->d_stamps.p, n16, (uint4 *)out_dev, c->d_stamps.p, c->cells, out_dev);
     return hipGetLastError();
 }
 
@@ -65,7 +65,7 @@ qs_logodds_kernel(const unsigned long long *__restrict__ counts, size_t cells, f
 hipError_t qs_launch_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_dev)
 {
     hipLaunchKernelGGL(qs_logodds_kernel, dim3(go_blocks(c->cells)), dim3(GO_BLOCK), 0, c->stream,
-                       c->counts_view_fused ? c->d_counts_fused : c->d_counts, c->cells, l_occ, l_free, lmin, lmax, out_dev);
+                       c->counts_view_fused ? c->d_counts_fused.p : c->d_counts.p, c->cells, l_occ, l_free, lmin, lmax, out_dev);
     return hipGetLastError();
 }
 
@@ -83,7 +83,7 @@ qs_split_counts_kernel(const unsigned long long *__restrict__ counts, size_t cel
 hipError_t qs_launch_split_counts(qs_ctx *c, int *hits_dev, int *misses_dev)
 {
     hipLaunchKernelGGL(qs_split_counts_kernel, dim3(go_blocks(c->cells)), dim3(GO_BLOCK), 0, c->stream,
-                       c->counts_view_fused ? c->d_counts_fused : c->d_counts, c->cells, hits_dev, misses_dev);
+                       c->counts_view_fused ? c->d_counts_fused.p : c->d_counts.p, c->cells, hits_dev, misses_dev);
     return hipGetLastError();
 }
 
@@ -103,7 +103,7 @@ qs_rebase_kernel(uint4 *__restrict__ stamps4, size_t n4)
 hipError_t qs_launch_rebase(qs_ctx *c)
 {
     hipLaunchKernelGGL(qs_rebase_kernel, dim3(go_blocks(c->cells / 4)), dim3(GO_BLOCK), 0, c->stream,
-                       (uint4 *)c->d_stamps, c->cells / 4);
+                       (uint4 *)c->d_stamps.p, c->cells / 4);
     return hipGetLastError();
 }
 
@@ -183,7 +183,7 @@ hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *src_stamps,
         }
         if (have_stamps)
             hipLaunchKernelGGL((qs_fuse_kernel<uint4, FuseSrcs>), dim3(go_blocks(n_cells / 4)), dim3(GO_BLOCK), 0, c->stream,
-                               (uint4 *)(c->d_stamps + cell_off), fs, m, n_cells / 4);
+                               (uint4 *)(c->d_stamps.p + cell_off), fs, m, n_cells / 4);
         if (have_counts)
             hipLaunchKernelGGL((qs_fuse_kernel<ulonglong2, FuseCnts>), dim3(go_blocks(n_cells / 2)), dim3(GO_BLOCK), 0, c->stream,
                                (ulonglong2 *)(dst_counts + cell_off), fc, m, n_cells / 2);
@@ -224,15 +224,15 @@ hipError_t qs_launch_reset_small(qs_ctx *c)
 {
     const int nb = c->cfg.max_agent + 1;
     const int n_ekf = nb * 44;
-    hipLaunchKernelGGL(qs_reset_small_kernel, dim3((n_ekf + 255) / 256), dim3(256), 0, c->stream, c->d_drift, nb * 2, c->d_zone, nb,
-                       c->d_counters, c->d_graph_batch, c->n_graphs * 2, c->d_ekf, n_ekf, c->d_ekf_prev, nb * 4, c->d_flags);
+    hipLaunchKernelGGL(qs_reset_small_kernel, dim3((n_ekf + 255) / 256), dim3(256), 0, c->stream, c->d_drift.p, nb * 2, c->d_zone.p, nb,
+                       c->d_counters.p, c->d_graph_batch.p, c->n_graphs * 2, c->d_ekf.p, n_ekf, c->d_ekf_prev.p, nb * 4, c->d_flags.p);
     return hipGetLastError();
 }
 
 hipError_t qs_launch_fill_zone_identity(qs_ctx *c)
 {
     const int nb = c->cfg.max_agent + 1;
-    hipLaunchKernelGGL(qs_zone_identity_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, c->d_zone, nb);
+    hipLaunchKernelGGL(qs_zone_identity_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, c->d_zone.p, nb);
     return hipGetLastError();
 }
 

@@ -35,14 +35,6 @@ struct ScopedEvent {                        // an event of one call, destroyed w
 };
 static const size_t QS_IO_WS_FLOOR = (size_t)1 << 16;      // qs_ctx::io_ws doubles from 64 KiB
 
-template <typename T>
-static hipError_t dev_realloc(T **p, size_t count)
-{
-    if (*p) { hipError_t e = hipFree(*p); *p = nullptr; if (e != hipSuccess) return e; }
-    if (count == 0) return hipSuccess;
-    return hipMalloc((void **)p, count * sizeof(T));
-}
-
 extern "C" const char *qs_version(void) { return "quasar-slam-amd 0.1 (gfx950)"; }
 
 extern "C" int qs_config_default(qs_config *cfg)
@@ -74,90 +66,84 @@ static double r2_threshold_for(double radius)
     return t;
 }
 
-static void graph_free(QsGraphDev &g)
-{
-    hipFree(g.lm_x); hipFree(g.lm_y); hipFree(g.lm_idx); hipFree(g.lm_type);
-    hipFree(g.cl_lm_idx); hipFree(g.cl_node_idx); hipFree(g.cl_dx); hipFree(g.cl_dy); hipFree(g.cl_agent);
-    hipFree(g.dir); hipFree(g.nodes); hipFree(g.nd_next); hipFree(g.misc);
-    memset(&g, 0, sizeof g);
-}
-
 // a graph array grown to new_cap, its first old_n entries kept; on failure the old array stays as it was
 template <typename T>
-static hipError_t grow_array(T **p, long long old_n, long long new_cap, hipStream_t st)
+static hipError_t grow_array(DevBuf<T> &a, long long old_n, long long new_cap, hipStream_t st)
 {
     DevBuf<T> q;
     HIPRET(q.alloc((size_t)new_cap));
-    if (*p && old_n > 0) {
-        HIPRET(hipMemcpyAsync(q.p, *p, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if (a.p && old_n > 0) {
+        HIPRET(hipMemcpyAsync(q.p, a.p, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice, st));
         HIPRET(hipStreamSynchronize(st));
     }
-    std::swap(*p, q.p);                      // (q takes the old array with it)
+    a = std::move(q);                        // (frees the old array)
     return hipSuccess;
 }
 
 // nodes (first node of every directory entry + the overflow pool): "empty" (idx bytes 0x7f -> a huge node
 // index) and unlinked (next 0)
-static hipError_t grow_pool(qs_ctx *c, QsGraphDev &G, long long old_cap, long long new_cap)
+static hipError_t grow_pool(qs_ctx *c, QsGraphBufs &G, long long old_cap, long long new_cap)
 {
     const size_t fixed = 1 + c->dir_entries, n_new = fixed + (size_t)new_cap, n_old = fixed + (size_t)old_cap;
-    const size_t keep = G.nodes ? n_old : 0;            // nodes and links copied over; the rest start empty
+    const size_t keep = G.nodes.p ? n_old : 0;          // nodes and links copied over; the rest start empty
     DevBuf<QsLmNode> nodes; DevBuf<unsigned int> next, misc;
     HIPRET(nodes.alloc(n_new));
     HIPRET(next.alloc(n_new));
     HIPRET(misc.alloc((size_t)new_cap));
     HIPRET(hipMemsetAsync(nodes.p + keep, 0x7f, (n_new - keep) * sizeof(QsLmNode), c->stream));
     HIPRET(hipMemsetAsync(next.p + keep, 0, (n_new - keep) * sizeof(unsigned int), c->stream));
-    if (G.nodes) {
-        HIPRET(hipMemcpyAsync(nodes.p, G.nodes, n_old * sizeof(QsLmNode), hipMemcpyDeviceToDevice, c->stream));
-        HIPRET(hipMemcpyAsync(next.p, G.nd_next, n_old * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
-        if (old_cap > 0) HIPRET(hipMemcpyAsync(misc.p, G.misc, (size_t)old_cap * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+    if (G.nodes.p) {
+        HIPRET(hipMemcpyAsync(nodes.p, G.nodes.p, n_old * sizeof(QsLmNode), hipMemcpyDeviceToDevice, c->stream));
+        HIPRET(hipMemcpyAsync(next.p, G.nd_next.p, n_old * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+        if (old_cap > 0) HIPRET(hipMemcpyAsync(misc.p, G.misc.p, (size_t)old_cap * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPRET(hipStreamSynchronize(c->stream));
-    std::swap(G.nodes, nodes.p); std::swap(G.nd_next, next.p); std::swap(G.misc, misc.p);   // (the old blocks go with the scope)
-    G.node_cap = (long long)n_new;
+    G.nodes = std::move(nodes); G.nd_next = std::move(next); G.misc = std::move(misc);
     return hipSuccess;
 }
 
 static int graph_reserve(qs_ctx *c, int g, long long need_lms, long long need_cls, long long have_lms,
                          long long have_cls)
 {
-    QsGraphDev &G = c->h_graphs[g];
+    QsGraphBufs &G = c->graphs[g];
     bool changed = false;
-    if (!G.dir) {
-        HIPCHK(c, dev_realloc(&G.dir, c->dir_entries));
-        HIPCHK(c, hipMemsetAsync(G.dir, 0, c->dir_entries * sizeof(QsDirEntry), c->stream));
+    if (!G.dir.p) {
+        HIPCHK(c, G.dir.alloc(c->dir_entries));
+        HIPCHK(c, hipMemsetAsync(G.dir.p, 0, c->dir_entries * sizeof(QsDirEntry), c->stream));
         changed = true;
     }
     if (need_lms > G.cap_lms) {
         long long cap = G.cap_lms ? G.cap_lms : 1024;
         while (cap < need_lms) cap *= 2;
-        HIPCHK(c, grow_array(&G.lm_x, have_lms, cap, c->stream));
-        HIPCHK(c, grow_array(&G.lm_y, have_lms, cap, c->stream));
-        HIPCHK(c, grow_array(&G.lm_idx, have_lms, cap, c->stream));
-        HIPCHK(c, grow_array(&G.lm_type, have_lms, cap, c->stream));
+        HIPCHK(c, grow_array(G.lm_x, have_lms, cap, c->stream));
+        HIPCHK(c, grow_array(G.lm_y, have_lms, cap, c->stream));
+        HIPCHK(c, grow_array(G.lm_idx, have_lms, cap, c->stream));
+        HIPCHK(c, grow_array(G.lm_type, have_lms, cap, c->stream));
         HIPCHK(c, grow_pool(c, G, G.cap_lms, cap));
         G.cap_lms = cap; changed = true;
     }
     if (need_cls > G.cap_cls) {
         long long cap = G.cap_cls ? G.cap_cls : 256;
         while (cap < need_cls) cap *= 2;
-        HIPCHK(c, grow_array(&G.cl_lm_idx, have_cls, cap, c->stream));
-        HIPCHK(c, grow_array(&G.cl_node_idx, have_cls, cap, c->stream));
-        HIPCHK(c, grow_array(&G.cl_dx, have_cls, cap, c->stream));
-        HIPCHK(c, grow_array(&G.cl_dy, have_cls, cap, c->stream));
-        HIPCHK(c, grow_array(&G.cl_agent, have_cls, cap, c->stream));
+        HIPCHK(c, grow_array(G.cl_lm_idx, have_cls, cap, c->stream));
+        HIPCHK(c, grow_array(G.cl_node_idx, have_cls, cap, c->stream));
+        HIPCHK(c, grow_array(G.cl_dx, have_cls, cap, c->stream));
+        HIPCHK(c, grow_array(G.cl_dy, have_cls, cap, c->stream));
+        HIPCHK(c, grow_array(G.cl_agent, have_cls, cap, c->stream));
         G.cap_cls = cap; changed = true;
     }
     if (changed) {
-        // pointers and capacities change; the counters live on the device and are preserved
-        QsGraphDev cur;
-        HIPCHK(c, hipMemcpyAsync(&cur, c->d_graphs + g, sizeof cur, hipMemcpyDeviceToHost, c->stream));
+        // the view: pointers and capacities from the arrays; the counters live on the device and are preserved
+        QsGraphDev v;
+        HIPCHK(c, hipMemcpyAsync(&v, c->d_graphs.p + g, sizeof v, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        QsGraphDev upd = G;
-        upd.n_nodes = cur.n_nodes; upd.n_lms = cur.n_lms; upd.n_cls = cur.n_cls;
-        upd.n_misc = cur.n_misc; upd.nodes_used = cur.nodes_used ? cur.nodes_used : (unsigned int)(1 + c->dir_entries);
-        HIPCHK(c, hipMemcpyAsync(c->d_graphs + g, &upd, sizeof upd, hipMemcpyHostToDevice, c->stream));
+        v.cap_lms = G.cap_lms; v.cap_cls = G.cap_cls;
+        v.lm_x = G.lm_x.p; v.lm_y = G.lm_y.p; v.lm_idx = G.lm_idx.p; v.lm_type = G.lm_type.p;
+        v.cl_lm_idx = G.cl_lm_idx.p; v.cl_node_idx = G.cl_node_idx.p; v.cl_dx = G.cl_dx.p; v.cl_dy = G.cl_dy.p; v.cl_agent = G.cl_agent.p;
+        v.dir = G.dir.p; v.nodes = G.nodes.p; v.nd_next = G.nd_next.p; v.misc = G.misc.p;
+        v.node_cap = (long long)G.nodes.cap;
+        if (!v.nodes_used) v.nodes_used = (unsigned int)(1 + c->dir_entries);
+        HIPCHK(c, hipMemcpyAsync(c->d_graphs.p + g, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return QS_OK;
@@ -165,13 +151,13 @@ static int graph_reserve(qs_ctx *c, int g, long long need_lms, long long need_cl
 
 static int reset_state(qs_ctx *c)
 {
-    HIPCHK(c, hipMemsetAsync(c->d_stamps, 0, c->cells * sizeof(unsigned int), c->stream));
-    if (c->d_counts) HIPCHK(c, hipMemsetAsync(c->d_counts, 0, c->cells * sizeof(unsigned long long), c->stream));
-    if (c->d_counts_fused) HIPCHK(c, hipMemsetAsync(c->d_counts_fused, 0, c->cells * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_stamps.p, 0, c->cells * sizeof(unsigned int), c->stream));
+    if (c->d_counts.p) HIPCHK(c, hipMemsetAsync(c->d_counts.p, 0, c->cells * sizeof(unsigned long long), c->stream));
+    if (c->d_counts_fused.p) HIPCHK(c, hipMemsetAsync(c->d_counts_fused.p, 0, c->cells * sizeof(unsigned long long), c->stream));
     c->counts_view_fused = false;             // the views read the local counters until the session's first fuse
     c->dirty_since_fuse = false;
-    if (c->d_dirty) HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, c->dirty_words * sizeof(unsigned int), c->stream));
-    if (c->d_counts_sent) HIPCHK(c, hipMemsetAsync(c->d_counts_sent, 0, c->cells * sizeof(unsigned long long), c->stream));
+    if (c->d_dirty.p) HIPCHK(c, hipMemsetAsync(c->d_dirty.p, 0, c->dirty_words * sizeof(unsigned int), c->stream));
+    if (c->d_counts_sent.p) HIPCHK(c, hipMemsetAsync(c->d_counts_sent.p, 0, c->cells * sizeof(unsigned long long), c->stream));
     c->sf_state = 0;
     HIPCHK(c, qs_launch_reset_small(c));      // drift, zone boxes, counters, per-graph batch counts, EKF state, flags: one launch
     // the bucket index of every graph: only what the session used of it (directory entries, first nodes,
@@ -212,6 +198,8 @@ extern "C" int qs_create(const qs_config *cfg, qs_ctx **out)
     c->r2_threshold = r2_threshold_for(cfg->closure_radius);
     c->cells = (size_t)cfg->size * cfg->size;
     c->geom = QsGeom{cfg->size, cfg->res, cfg->ox, cfg->oy, cfg->min_dist, cfg->max_dist, 1.0 / cfg->res};
+    c->b.own_lo = cfg->shard_bots > 0 ? cfg->shard_rank * cfg->shard_bots + 1 : 1;      // the agents whose rays this context casts
+    c->b.own_hi = cfg->shard_bots > 0 ? std::min(cfg->max_agent, (cfg->shard_rank + 1) * cfg->shard_bots) : cfg->max_agent;
     {   // landmark buckets: edge a hair above the closure radius, so that two points closer than the
         // radius are never two buckets apart whatever the rounding of (v - b0) / cell.  The directory is a
         // hash table over the cells, sized for one entry per cell of the configured world (2^20 at most).
@@ -229,30 +217,30 @@ extern "C" int qs_create(const qs_config *cfg, qs_ctx **out)
     CREATE_CHK(hipSetDevice(c->device));
     CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->own_stream = true;
-    CREATE_CHK(hipMalloc((void **)&c->d_stamps, c->cells * sizeof(unsigned int)));
-    if (cfg->enable_counts) CREATE_CHK(hipMalloc((void **)&c->d_counts, c->cells * sizeof(unsigned long long)));
-    CREATE_CHK(hipMalloc((void **)&c->d_offset, nb * sizeof(double)));
-    CREATE_CHK(hipMalloc((void **)&c->d_drift, nb * 2 * sizeof(double)));
-    CREATE_CHK(hipMalloc((void **)&c->d_last_closure, nb * sizeof(long long)));
-    CREATE_CHK(hipMalloc((void **)&c->d_zone, nb * 4 * sizeof(unsigned long long)));
-    CREATE_CHK(hipMalloc((void **)&c->d_counters, QS_CNT_N * sizeof(unsigned long long)));
-    CREATE_CHK(hipMalloc((void **)&c->d_graph_batch, (size_t)c->n_graphs * 2 * sizeof(unsigned long long)));
-    CREATE_CHK(hipMalloc((void **)&c->d_ekf, (size_t)nb * 44 * sizeof(double)));
-    CREATE_CHK(hipMalloc((void **)&c->d_ekf_prev, (size_t)nb * 4 * sizeof(double)));
-    CREATE_CHK(hipMalloc((void **)&c->d_flags, QS_N_FLAGS * sizeof(unsigned int)));
-    CREATE_CHK(hipMemset(c->d_flags, 0, QS_N_FLAGS * sizeof(unsigned int)));
+    CREATE_CHK(c->d_stamps.alloc(c->cells));
+    if (cfg->enable_counts) CREATE_CHK(c->d_counts.alloc(c->cells));
+    CREATE_CHK(c->d_offset.alloc(nb));
+    CREATE_CHK(c->d_drift.alloc((size_t)nb * 2));
+    CREATE_CHK(c->d_last_closure.alloc(nb));
+    CREATE_CHK(c->d_zone.alloc((size_t)nb * 4));
+    CREATE_CHK(c->d_counters.alloc(QS_CNT_N));
+    CREATE_CHK(c->d_graph_batch.alloc((size_t)c->n_graphs * 2));
+    CREATE_CHK(c->d_ekf.alloc((size_t)nb * 44));
+    CREATE_CHK(c->d_ekf_prev.alloc((size_t)nb * 4));
+    CREATE_CHK(c->d_flags.alloc(QS_N_FLAGS));
+    CREATE_CHK(hipMemset(c->d_flags.p, 0, QS_N_FLAGS * sizeof(unsigned int)));
     CREATE_CHK(hipHostMalloc((void **)&c->h_chain_stat, 8 * sizeof(unsigned int), hipHostMallocDefault));
     memset(c->h_chain_stat, 0, 8 * sizeof(unsigned int));
     CREATE_CHK(hipEventCreateWithFlags(&c->ev_chain_stat, hipEventDisableTiming));
     if (const char *e = getenv("QS_CHAIN_MODE")) c->chain_form = strcmp(e, "window") == 0 ? QS_CHAIN_WINDOW : strcmp(e, "free") == 0 ? QS_CHAIN_FREE : strcmp(e, "free_posting") == 0 ? QS_CHAIN_FREE_POSTING : QS_CHAIN_AUTO;
-    CREATE_CHK(hipMalloc((void **)&c->d_graphs, (size_t)c->n_graphs * sizeof(QsGraphDev)));
-    CREATE_CHK(hipMemset(c->d_graphs, 0, (size_t)c->n_graphs * sizeof(QsGraphDev)));
-    c->h_graphs.assign(c->n_graphs, QsGraphDev{});
+    CREATE_CHK(c->d_graphs.alloc((size_t)c->n_graphs));
+    CREATE_CHK(hipMemset(c->d_graphs.p, 0, (size_t)c->n_graphs * sizeof(QsGraphDev)));
+    c->graphs.resize(c->n_graphs);
     c->lms_upper.assign(c->n_graphs, 0);
     c->cls_upper.assign(c->n_graphs, 0);
     std::vector<double> off(nb, 0.0);
     if (cfg->max_agent >= 2) off[2] = cfg->separation;                       // :851-852
-    CREATE_CHK(hipMemcpy(c->d_offset, off.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    CREATE_CHK(hipMemcpy(c->d_offset.p, off.data(), nb * sizeof(double), hipMemcpyHostToDevice));
 #undef CREATE_CHK
     for (int g = 0; g < c->n_graphs; g++) {
         int rc = graph_reserve(c, g, 1024, 256, 0, 0);
@@ -325,38 +313,18 @@ static void ekf_stream_release(qs_ctx *c)
     if (c->ev_ekf_done) hipEventDestroy(c->ev_ekf_done);
 }
 
-static void free_batch(qs_ctx *c)
-{
-    QsBatch &b = c->b;
-    hipFree(b.accept); hipFree(b.agent); hipFree(b.lm); hipFree(b.px); hipFree(b.py); hipFree(b.yaw);
-    hipFree(b.dist); hipFree(b.enc); hipFree(b.rx); hipFree(b.ry); hipFree(b.hit); hipFree(b.hit_valid);
-    if (b.map_ok != b.accept) hipFree(b.map_ok);
-    memset(&b, 0, sizeof b);
-    QsSlamBatch &sb = c->sb;
-    hipFree(sb.node); hipFree(sb.ev_node); hipFree(sb.ev_agent); hipFree(sb.ev_type); hipFree(sb.ev_px); hipFree(sb.ev_py);
-    hipFree(sb.ev_base); hipFree(sb.acc_total); hipFree(sb.blk_acc); hipFree(sb.blk_ev); hipFree(sb.agent_ev);
-    hipFree(sb.acl_node); hipFree(sb.acl_dx); hipFree(sb.acl_dy); hipFree(sb.acl_cnt); hipFree(sb.drift_start);
-    memset(&sb, 0, sizeof sb);
-    c->cap_batch = 0;
-}
-
 extern "C" int qs_destroy(qs_ctx *c)
 {
     if (!c) return QS_OK;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto &g : c->h_graphs) graph_free(g);
-    free_batch(c);
-    hipFree(c->d_stamps); hipFree(c->d_counts); hipFree(c->d_counts_fused); hipFree(c->d_offset); hipFree(c->d_drift);
-    hipFree(c->d_last_closure); hipFree(c->d_zone); hipFree(c->d_counters); hipFree(c->d_graph_batch);
-    hipFree(c->d_ekf); hipFree(c->d_ekf_prev); hipFree(c->d_graphs); hipFree(c->d_flags); if (c->h_chain_stat) hipHostFree(c->h_chain_stat); if (c->ev_chain_stat) hipEventDestroy(c->ev_chain_stat); hipFree(c->d_pkts); hipFree(c->d_lens);
-    hipFree(c->d_time); hipFree(c->d_edge);
-    hipFree(c->d_dirty); hipFree(c->d_counts_sent); hipFree(c->d_sf_bitmaps); hipFree(c->d_sf_lists); hipFree(c->d_sf_counts);
+    if (c->h_chain_stat) hipHostFree(c->h_chain_stat);
+    if (c->ev_chain_stat) hipEventDestroy(c->ev_chain_stat);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->ev_pool) hipEventDestroy(e);
     ekf_stream_release(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-    delete c;                                      // (the workspaces free themselves)
+    delete c;                                      // (every device block is a DevBuf: they free themselves)
     return QS_OK;
 }
 
@@ -412,7 +380,7 @@ extern "C" int qs_set_bot_offset(qs_ctx *c, int32_t bot, double off_x)
     ARGCHK(c, c != nullptr);
     if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_set_bot_offset: bot out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->d_offset + bot, &off_x, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_offset.p + bot, &off_x, sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
@@ -442,39 +410,47 @@ extern "C" int qs_stage_times(qs_ctx *c, double ms[QS_STAGE_N], uint64_t launche
 }
 
 // ---- batch buffers --------------------------------------------------------------------------
+// the arrays of QsBatch and QsSlamBatch for cap records, carved from base (nullptr: only the size); returns the bytes
+static size_t batch_layout(const qs_ctx *c, void *base, size_t cap, QsBatch &b, QsSlamBatch &sb)
+{
+    const size_t nblk = (size_t)qs_slam_blocks(cap), G = (size_t)c->n_graphs, nb = (size_t)c->cfg.max_agent + 2;
+    Carve k(base);
+    b.accept = k.take<unsigned char>(cap);
+    b.map_ok = c->cfg.shard_bots > 0 ? k.take<unsigned char>(cap) : b.accept;     // an array of its own only in a shard
+    b.agent = k.take<unsigned char>(cap); b.lm = k.take<unsigned char>(cap);
+    b.px = k.take<double>(cap); b.py = k.take<double>(cap); b.yaw = k.take<double>(cap);
+    b.dist = k.take<float4>(cap); b.enc = k.take<int>(cap);
+    b.rx = k.take<double>(cap); b.ry = k.take<double>(cap);
+    b.hit = k.take<double2>(4 * cap); b.hit_valid = k.take<unsigned char>(4 * cap);
+    sb.node = k.take<long long>(cap); sb.ev_node = k.take<long long>(cap);
+    sb.ev_agent = k.take<unsigned char>(cap); sb.ev_type = k.take<unsigned char>(cap);
+    sb.ev_px = k.take<double>(cap); sb.ev_py = k.take<double>(cap);
+    sb.ev_base = k.take<unsigned int>(G + 1); sb.acc_total = k.take<unsigned int>(G);
+    sb.blk_acc = k.take<unsigned int>(G * nblk); sb.blk_ev = k.take<unsigned int>(G * nblk);
+    sb.agent_ev = k.take<unsigned int>(nb); sb.acl_cnt = k.take<unsigned int>(nb);
+    sb.acl_node = k.take<long long>(cap); sb.acl_dx = k.take<double>(cap); sb.acl_dy = k.take<double>(cap);
+    sb.drift_start = k.take<double>(2 * nb);
+    return k.bytes;
+}
+
+// room for n records; a growth that fails leaves the old arrays as they were
 static int ensure_batch(qs_ctx *c, size_t n)
 {
     if (n <= c->cap_batch) return QS_OK;
     size_t cap = c->cap_batch ? c->cap_batch : 1024;
     while (cap < n) cap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->cap_batch = 0;                                        // (until every array below exists)
-    QsBatch &b = c->b;
-    if (b.map_ok == b.accept) b.map_ok = nullptr;            // an alias of accept, not an array of its own
-    HIPCHK(c, dev_realloc(&b.accept, cap)); HIPCHK(c, dev_realloc(&b.agent, cap)); HIPCHK(c, dev_realloc(&b.lm, cap));
-    HIPCHK(c, dev_realloc(&b.px, cap)); HIPCHK(c, dev_realloc(&b.py, cap)); HIPCHK(c, dev_realloc(&b.yaw, cap));
-    HIPCHK(c, dev_realloc(&b.dist, cap)); HIPCHK(c, dev_realloc(&b.enc, cap));
-    HIPCHK(c, dev_realloc(&b.rx, cap)); HIPCHK(c, dev_realloc(&b.ry, cap));
-    HIPCHK(c, dev_realloc(&b.hit, 4 * cap)); HIPCHK(c, dev_realloc(&b.hit_valid, 4 * cap));
-    if (c->cfg.shard_bots > 0) {
-        HIPCHK(c, dev_realloc(&b.map_ok, cap));
-        b.own_lo = c->cfg.shard_rank * c->cfg.shard_bots + 1;
-        b.own_hi = std::min(c->cfg.max_agent, (c->cfg.shard_rank + 1) * c->cfg.shard_bots);
-    } else { b.map_ok = b.accept; b.own_lo = 1; b.own_hi = c->cfg.max_agent; }
+    QsBatch b = c->b;
+    QsSlamBatch sb = c->sb;
+    DevBuf<char> slab;
+    HIPCHK(c, slab.alloc(batch_layout(c, nullptr, cap, b, sb)));
+    batch_layout(c, slab.p, cap, b, sb);
     if (c->cfg.exact_trig) {
-        if (!c->d_edge) HIPCHK(c, dev_realloc(&c->d_edge, (size_t)QS_EDGE_CAP));
-        b.edge = c->d_edge; b.edge_n = c->d_flags; b.edge_cap = QS_EDGE_CAP;
+        if (!c->d_edge.p) HIPCHK(c, c->d_edge.alloc(QS_EDGE_CAP));
+        b.edge = c->d_edge.p; b.edge_n = c->d_flags.p; b.edge_cap = QS_EDGE_CAP;
     }
-    QsSlamBatch &sb = c->sb;
-    const size_t nblk = (size_t)qs_slam_blocks(cap), G = (size_t)c->n_graphs, nb = (size_t)c->cfg.max_agent + 2;
-    HIPCHK(c, dev_realloc(&sb.node, cap)); HIPCHK(c, dev_realloc(&sb.ev_node, cap));
-    HIPCHK(c, dev_realloc(&sb.ev_agent, cap)); HIPCHK(c, dev_realloc(&sb.ev_type, cap));
-    HIPCHK(c, dev_realloc(&sb.ev_px, cap)); HIPCHK(c, dev_realloc(&sb.ev_py, cap));
-    HIPCHK(c, dev_realloc(&sb.ev_base, G + 1)); HIPCHK(c, dev_realloc(&sb.acc_total, G));
-    HIPCHK(c, dev_realloc(&sb.blk_acc, G * nblk)); HIPCHK(c, dev_realloc(&sb.blk_ev, G * nblk));
-    HIPCHK(c, dev_realloc(&sb.agent_ev, nb)); HIPCHK(c, dev_realloc(&sb.acl_cnt, nb));
-    HIPCHK(c, dev_realloc(&sb.acl_node, cap)); HIPCHK(c, dev_realloc(&sb.acl_dx, cap)); HIPCHK(c, dev_realloc(&sb.acl_dy, cap));
-    HIPCHK(c, dev_realloc(&sb.drift_start, 2 * nb));
+    HIPCHK(c, hipStreamSynchronize(c->stream));              // (the old arrays may still be in use)
+    c->batch_ws = std::move(slab);
+    c->b = b; c->sb = sb;
     c->cap_batch = cap;
     return QS_OK;
 }
@@ -525,7 +501,7 @@ static int reserve_graphs_for_batch(qs_ctx *c, size_t n)
 {
     bool need_sync = false;
     for (int g = 0; g < c->n_graphs; g++)
-        if (c->lms_upper[g] + (long long)n > c->h_graphs[g].cap_lms || c->cls_upper[g] + (long long)n > c->h_graphs[g].cap_cls)
+        if (c->lms_upper[g] + (long long)n > c->graphs[g].cap_lms || c->cls_upper[g] + (long long)n > c->graphs[g].cap_cls)
             need_sync = true;
     if (!need_sync) {
         for (int g = 0; g < c->n_graphs; g++) { c->lms_upper[g] += (long long)n; c->cls_upper[g] += (long long)n; }
@@ -541,9 +517,9 @@ static int reserve_graphs_for_batch(qs_ctx *c, size_t n)
         double extra = 0;
         for (int g = 0; g < c->n_graphs; g++) {
             const long long nl = c->lms_upper[g] + (long long)n, nc = c->cls_upper[g] + (long long)n;
-            if (nl > c->h_graphs[g].cap_lms) extra += (double)(2 * nl - c->h_graphs[g].cap_lms) * unit;     // (capacities double)
-            if (!c->h_graphs[g].nodes) extra += (double)(1 + c->dir_entries) * (sizeof(QsLmNode) + 4 + sizeof(QsDirEntry));   // first nodes
-            if (nc > c->h_graphs[g].cap_cls) extra += (double)(2 * nc - c->h_graphs[g].cap_cls) * 32.0;
+            if (nl > c->graphs[g].cap_lms) extra += (double)(2 * nl - c->graphs[g].cap_lms) * unit;     // (capacities double)
+            if (!c->graphs[g].nodes.p) extra += (double)(1 + c->dir_entries) * (sizeof(QsLmNode) + 4 + sizeof(QsDirEntry));   // first nodes
+            if (nc > c->graphs[g].cap_cls) extra += (double)(2 * nc - c->graphs[g].cap_cls) * 32.0;
         }
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra <= 0.25 * (double)free_b) {
@@ -559,8 +535,8 @@ static int reserve_graphs_for_batch(qs_ctx *c, size_t n)
     // tighten the bounds with the exact device-side numbers, then grow what is really short
     std::vector<QsGraphDev> cur(c->n_graphs);
     std::vector<unsigned long long> gb((size_t)c->n_graphs * 2);
-    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(gb.data(), c->d_graph_batch, gb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs.p, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(gb.data(), c->d_graph_batch.p, gb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int g = 0; g < c->n_graphs; g++) {
         const long long ev = (long long)gb[2 * g + 1];
@@ -609,7 +585,7 @@ static int chain_stats_request(qs_ctx *c)
     // one ingest in four: the copy is a blit kernel with a barrier either side (~20 us of a 1.4 ms step when the stream is
     // 64 bots), and what it carries only ever changes the choice of an instantiation
     if ((c->chain_stat_tick++ & 3u) != 0) return QS_OK;
-    HIPCHK(c, hipMemcpyAsync(c->h_chain_stat, c->d_flags + QS_FLAG_CHAIN_MISS, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_chain_stat, c->d_flags.p + QS_FLAG_CHAIN_MISS, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_chain_stat, c->stream));
     c->chain_stat_pending = true;
     return QS_OK;
@@ -619,9 +595,9 @@ static int flush_edge_rays(qs_ctx *c)
 {
     if (!c->edge_maybe && !c->flags_maybe) return QS_OK;
     unsigned int fl[QS_N_FLAGS] = {0};
-    HIPCHK(c, hipMemcpyAsync(fl, c->d_flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fl, c->d_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->stream));
     std::vector<QsGraphDev> cur((size_t)c->n_graphs);
-    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs.p, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->edge_maybe = false; c->flags_maybe = false;
     for (int g = 0; g < c->n_graphs; g++) { c->lms_upper[g] = cur[g].n_lms; c->cls_upper[g] = cur[g].n_cls; }
@@ -632,7 +608,7 @@ static int flush_edge_rays(qs_ctx *c)
     if (n_edge == 0) return QS_OK;
     c->edge_rays_total += n_edge;
     std::vector<QsEdgeRec> recs(n_edge);
-    HIPCHK(c, hipMemcpy(recs.data(), c->d_edge, (size_t)n_edge * sizeof(QsEdgeRec), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(recs.data(), c->d_edge.p, (size_t)n_edge * sizeof(QsEdgeRec), hipMemcpyDeviceToHost));
     const size_t bytes = (size_t)n_edge * 4 * sizeof(double);
     HIPCHK(c, c->io_ws.reserve(bytes, c->stream, QS_IO_WS_FLOOR));
     double *d = (double *)c->io_ws.p;
@@ -656,8 +632,8 @@ static int flush_edge_rays(qs_ctx *c)
     }
     HIPCHK(c, hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, qs_launch_edge_cast(c, n_edge, d));
-    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, sizeof(unsigned int), c->stream));                 // the list is empty again
-    HIPCHK(c, hipMemsetAsync(c->d_flags + 2, 0, sizeof(unsigned int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_flags.p, 0, sizeof(unsigned int), c->stream));                 // the list is empty again
+    HIPCHK(c, hipMemsetAsync(c->d_flags.p + 2, 0, sizeof(unsigned int), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                                                // h goes out of scope
     return QS_OK;
 }
@@ -682,7 +658,7 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
     // epoch decisions use the stride-aligned range so that all ranks of a sharded stream agree
     rc = ensure_epoch(c, seq0 - seq0 % sstride, n * sstride);
     if (rc != QS_OK) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_graph_batch, 0, (size_t)c->n_graphs * 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_graph_batch.p, 0, (size_t)c->n_graphs * 2 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->sb.agent_ev, 0, ((size_t)c->cfg.max_agent + 2) * sizeof(unsigned int), c->stream));
     { StageTimer t(c, QS_STAGE_DECODE); HIPCHK(c, qs_launch_decode(c, d_pkts, n, stride, d_lens)); t.stop(); }
     rc = reserve_graphs_for_batch(c, n);
@@ -726,17 +702,24 @@ extern "C" int qs_ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size
 }
 
 // device staging of host-side records: bytes of records, one length and one receive time per (shortest) record
-static int reserve_staging(qs_ctx *c, size_t bytes)
+struct Staging { unsigned char *pkts; unsigned short *lens; double *time; };
+static size_t staging_layout(void *base, size_t cap, Staging &s)
 {
-    if (bytes <= c->cap_pkts_bytes) return QS_OK;
-    size_t cap = c->cap_pkts_bytes ? c->cap_pkts_bytes : (1u << 16);
+    Carve k(base);
+    s.pkts = k.take<unsigned char>(cap);
+    s.lens = k.take<unsigned short>(cap / QS_PACKET_SIZE_V1 + 1);
+    s.time = k.take<double>(cap / QS_PACKET_SIZE_V1 + 1);
+    return k.bytes;
+}
+
+// staging for `bytes` of records, laid out for the smallest power-of-two multiple of 64 KiB that holds them (the block
+// only grows: the layout of a larger multiple needs more bytes)
+static int reserve_staging(qs_ctx *c, size_t bytes, Staging &s)
+{
+    size_t cap = (size_t)1 << 16;
     while (cap < bytes) cap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->cap_pkts_bytes = 0;                               // (until all three exist)
-    HIPCHK(c, dev_realloc(&c->d_pkts, cap));
-    HIPCHK(c, dev_realloc(&c->d_lens, cap / QS_PACKET_SIZE_V1 + 1));
-    HIPCHK(c, dev_realloc(&c->d_time, cap / QS_PACKET_SIZE_V1 + 1));
-    c->cap_pkts_bytes = cap;
+    HIPCHK(c, c->stage_ws.reserve(staging_layout(nullptr, cap, s), c->stream));
+    staging_layout(c->stage_ws.p, cap, s);
     return QS_OK;
 }
 
@@ -748,11 +731,12 @@ extern "C" int qs_ingest(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) { c->last_n = 0; return QS_OK; }
     const size_t bytes = n * stride;
-    { int rcs = reserve_staging(c, bytes); if (rcs != QS_OK) return rcs; }
-    HIPCHK(c, hipMemcpyAsync(c->d_pkts, pkts, bytes, hipMemcpyHostToDevice, c->stream));
-    if (lens) HIPCHK(c, hipMemcpyAsync(c->d_lens, lens, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-    if (recv_time) HIPCHK(c, hipMemcpyAsync(c->d_time, recv_time, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int rc = ingest_device(c, c->d_pkts, n, stride, lens ? c->d_lens : nullptr, recv_time ? c->d_time : nullptr, seq0);
+    Staging s;
+    { int rcs = reserve_staging(c, bytes, s); if (rcs != QS_OK) return rcs; }
+    HIPCHK(c, hipMemcpyAsync(s.pkts, pkts, bytes, hipMemcpyHostToDevice, c->stream));
+    if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    if (recv_time) HIPCHK(c, hipMemcpyAsync(s.time, recv_time, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    int rc = ingest_device(c, s.pkts, n, stride, lens ? s.lens : nullptr, recv_time ? s.time : nullptr, seq0);
     if (rc != QS_OK) return rc;
     // this call waits for the GPU anyway (the caller's buffers are free when it returns): the waiting edge rays are resolved
     // now, and the graphs' real landmark / closure counts and the pile flag come along
@@ -871,11 +855,12 @@ extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t
     if (rc != QS_OK || n == 0) return rc;
     for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
         const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        rc = reserve_staging(c, m * stride);               // (stream-ordered: the previous chunk's kernels have read theirs)
+        Staging s;
+        rc = reserve_staging(c, m * stride, s);            // (stream-ordered: the previous chunk's kernels have read theirs)
         if (rc != QS_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
-        if (lens) HIPCHK(c, hipMemcpyAsync(c->d_lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        rc = sweeps_chunk(c, c->d_pkts, m, stride, lens ? c->d_lens : nullptr, seq0, k0);
+        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0);
         if (rc != QS_OK) return rc;
     }
     sweeps_end(c, n, seq0);
@@ -981,7 +966,7 @@ extern "C" int qs_grid_i8(qs_ctx *c, int8_t *out_host)
 extern "C" int qs_grid_counts(qs_ctx *c, int32_t *hits_host, int32_t *misses_host)
 {
     ARGCHK(c, c != nullptr && hits_host && misses_host);
-    if (!c->d_counts) return qs_fail(c, QS_E_INVAL, "qs_grid_counts: context created with enable_counts = 0");
+    if (!c->d_counts.p) return qs_fail(c, QS_E_INVAL, "qs_grid_counts: context created with enable_counts = 0");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     DevBuf<int> d;
@@ -996,7 +981,7 @@ extern "C" int qs_grid_counts(qs_ctx *c, int32_t *hits_host, int32_t *misses_hos
 extern "C" int qs_grid_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_host)
 {
     ARGCHK(c, c != nullptr && out_host);
-    if (!c->d_counts) return qs_fail(c, QS_E_INVAL, "qs_grid_logodds: context created with enable_counts = 0");
+    if (!c->d_counts.p) return qs_fail(c, QS_E_INVAL, "qs_grid_logodds: context created with enable_counts = 0");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     DevBuf<float> d;
@@ -1012,10 +997,10 @@ extern "C" int qs_device_buffers(qs_ctx *c, void **stamps_dev, size_t *stamps_by
     ARGCHK(c, c != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);                                   // whoever gets the buffers may read them (a collective)
-    if (stamps_dev) *stamps_dev = c->d_stamps;
+    if (stamps_dev) *stamps_dev = c->d_stamps.p;
     if (stamps_bytes) *stamps_bytes = c->cells * sizeof(unsigned int);
-    if (counts_dev) *counts_dev = c->d_counts;
-    if (counts_bytes) *counts_bytes = c->d_counts ? c->cells * sizeof(unsigned long long) : 0;
+    if (counts_dev) *counts_dev = c->d_counts.p;
+    if (counts_bytes) *counts_bytes = c->d_counts.p ? c->cells * sizeof(unsigned long long) : 0;
     return QS_OK;
 }
 
@@ -1024,7 +1009,7 @@ static int read_graph(qs_ctx *c, int32_t graph, QsGraphDev &g)
 {
     if (graph < 0 || graph >= c->n_graphs) return qs_fail(c, QS_E_RANGE, "graph index out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(&g, c->d_graphs + graph, sizeof g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&g, c->d_graphs.p + graph, sizeof g, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->lms_upper[graph] = g.n_lms; c->cls_upper[graph] = g.n_cls;      // exact now: nothing is in flight
     return QS_OK;
@@ -1118,18 +1103,18 @@ extern "C" int qs_slam_add_poses(qs_ctx *c, const double *x, const double *y, co
     HIPCHK(c, hipMemcpyAsync(c->b.lm, landmark, n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->b.px, x, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->b.py, y, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_graph_batch, gb.data(), gb.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_graph_batch.p, gb.data(), gb.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->sb.agent_ev, aev.data(), aev.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));           // host vectors above go out of use
     c->b.n = n;
     rc = reserve_graphs_for_batch(c, n);
     if (rc != QS_OK) return rc;
     std::vector<QsGraphDev> before(G), after(G);
-    HIPCHK(c, hipMemcpyAsync(before.data(), c->d_graphs, (size_t)G * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(before.data(), c->d_graphs.p, (size_t)G * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
     chain_stats_poll(c, false, nullptr);
     HIPCHK(c, qs_launch_slam(c, n, true));
     { int rcs = chain_stats_request(c); if (rcs != QS_OK) return rcs; }
-    HIPCHK(c, hipMemcpyAsync(after.data(), c->d_graphs, (size_t)G * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(after.data(), c->d_graphs.p, (size_t)G * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
     std::vector<long long> node(n);
     HIPCHK(c, hipMemcpyAsync(node.data(), c->sb.node, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1165,7 +1150,7 @@ extern "C" int qs_drift(qs_ctx *c, int32_t bot, double out[2])
     ARGCHK(c, c != nullptr && out);
     if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_drift: bot out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_drift + 2 * bot, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_drift.p + 2 * bot, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
@@ -1177,7 +1162,7 @@ extern "C" int qs_zone(qs_ctx *c, int32_t bot, double out[4], int32_t *valid)
     if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_zone: bot out of range");
     HIPCHK(c, hipSetDevice(c->device));
     unsigned long long z[4];
-    HIPCHK(c, hipMemcpyAsync(z, c->d_zone + 4 * bot, sizeof z, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(z, c->d_zone.p + 4 * bot, sizeof z, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *valid = z[0] != QS_ORD_MIN_IDENT;                      // compute_bounding_box: None if no points  :704
     for (int i = 0; i < 4; i++) out[i] = *valid ? qs_double_from_ord(z[i]) : NAN;
@@ -1207,10 +1192,10 @@ extern "C" int qs_fuse_buffers_range(qs_ctx *c, const void *const *stamps_dev, c
     if (n == 0 || n_cells == 0) return QS_OK;
     ARGCHK(c, stamps_dev != nullptr || counts_dev != nullptr);
     ARGCHK(c, cell_offset % 4 == 0 && n_cells % 4 == 0 && cell_offset + n_cells <= c->cells);
-    if (counts_dev && counts_into_fused && !c->d_counts_fused)
+    if (counts_dev && counts_into_fused && !c->d_counts_fused.p)
         return qs_fail(c, QS_E_INVAL, "qs_fuse_buffers_range: no fused counter snapshot (call qs_fused_counts first)");
     HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long *dc = c->cfg.enable_counts ? (counts_into_fused ? c->d_counts_fused : c->d_counts) : nullptr;
+    unsigned long long *dc = c->cfg.enable_counts ? (counts_into_fused ? c->d_counts_fused.p : c->d_counts.p) : nullptr;
     HIPCHK(c, qs_launch_fuse(c, (const unsigned int *const *)stamps_dev, (const unsigned long long *const *)counts_dev, n,
                              cell_offset, n_cells, dc));
     if (!counts_into_fused) HIPCHK(c, qs_launch_sf_mark_range(c, cell_offset, n_cells));   // a local fold writes the grid too
@@ -1232,14 +1217,14 @@ extern "C" int qs_fuse_buffers(qs_ctx *c, const void *const *stamps_dev, const v
 extern "C" int qs_fused_counts(qs_ctx *c, void **fused_dev, size_t *bytes)
 {
     ARGCHK(c, c != nullptr && fused_dev != nullptr);
-    if (!c->d_counts) return qs_fail(c, QS_E_INVAL, "qs_fused_counts: context created with enable_counts = 0");
-    if (c->d_dirty) return qs_fail(c, QS_E_STATE, "qs_fused_counts: dirty tracking is on -- the fused counters accumulate the sparse fuse's deltas");
+    if (!c->d_counts.p) return qs_fail(c, QS_E_INVAL, "qs_fused_counts: context created with enable_counts = 0");
+    if (c->d_dirty.p) return qs_fail(c, QS_E_STATE, "qs_fused_counts: dirty tracking is on -- the fused counters accumulate the sparse fuse's deltas");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     const size_t nb = c->cells * sizeof(unsigned long long);
-    if (!c->d_counts_fused) HIPCHK(c, dev_realloc(&c->d_counts_fused, c->cells));
-    HIPCHK(c, hipMemcpyAsync(c->d_counts_fused, c->d_counts, nb, hipMemcpyDeviceToDevice, c->stream));
-    *fused_dev = c->d_counts_fused;
+    if (!c->d_counts_fused.p) HIPCHK(c, c->d_counts_fused.alloc(c->cells));
+    HIPCHK(c, hipMemcpyAsync(c->d_counts_fused.p, c->d_counts.p, nb, hipMemcpyDeviceToDevice, c->stream));
+    *fused_dev = c->d_counts_fused.p;
     if (bytes) *bytes = nb;
     return QS_OK;
 }
@@ -1247,15 +1232,15 @@ extern "C" int qs_fused_counts(qs_ctx *c, void **fused_dev, size_t *bytes)
 extern "C" int qs_fused_counts_buffer(qs_ctx *c, void **fused_dev, size_t *bytes)
 {
     ARGCHK(c, c != nullptr && fused_dev != nullptr);
-    *fused_dev = c->d_counts_fused;
-    if (bytes) *bytes = c->d_counts_fused ? c->cells * sizeof(unsigned long long) : 0;
+    *fused_dev = c->d_counts_fused.p;
+    if (bytes) *bytes = c->d_counts_fused.p ? c->cells * sizeof(unsigned long long) : 0;
     return QS_OK;
 }
 
 extern "C" int qs_counts_source(qs_ctx *c, int32_t fused)
 {
     ARGCHK(c, c != nullptr);
-    if (fused && !c->d_counts_fused) return qs_fail(c, QS_E_INVAL, "qs_counts_source: no fused snapshot yet (qs_fused_counts)");
+    if (fused && !c->d_counts_fused.p) return qs_fail(c, QS_E_INVAL, "qs_counts_source: no fused snapshot yet (qs_fused_counts)");
     c->counts_view_fused = fused != 0;
     return QS_OK;
 }
@@ -1268,30 +1253,30 @@ extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!enable) {
         c->geom.dirty = nullptr; c->geom.dirty_pitch = 0;
-        (void)dev_realloc(&c->d_dirty, 0);
+        c->d_dirty = DevBuf<unsigned int>();
         c->sf_state = 0;
         c->counts_view_fused = false;         // the fused counters stop following the ranks: the views read the own ones
         return QS_OK;
     }
-    if (c->d_dirty) return QS_OK;
+    if (c->d_dirty.p) return QS_OK;
     if (c->dirty_since_fuse) return qs_fail(c, QS_E_STATE, "qs_dirty_tracking: the grid has unfused writes (enable it after qs_create / qs_reset / a fuse)");
     c->blocks_x = (c->cfg.size + QS_DIRTY_BLOCK_W - 1) / QS_DIRTY_BLOCK_W;
     c->blocks_y = (c->cfg.size + QS_DIRTY_BLOCK_H - 1) / QS_DIRTY_BLOCK_H;
     const int pitch = (c->blocks_x + 31) / 32;
     c->dirty_words = (size_t)c->blocks_y * pitch;
-    if (c->d_counts) {
+    if (c->d_counts.p) {
         const size_t nb = c->cells * sizeof(unsigned long long);
-        if (!c->d_counts_sent) HIPCHK(c, dev_realloc(&c->d_counts_sent, c->cells));
+        if (!c->d_counts_sent.p) HIPCHK(c, c->d_counts_sent.alloc(c->cells));
         // the fused counters accumulate deltas from here on: they start as "nothing sent", the local counters as all delta
-        HIPCHK(c, hipMemsetAsync(c->d_counts_sent, 0, nb, c->stream));
-        if (!c->d_counts_fused) HIPCHK(c, dev_realloc(&c->d_counts_fused, c->cells));
-        HIPCHK(c, hipMemsetAsync(c->d_counts_fused, 0, nb, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_counts_sent.p, 0, nb, c->stream));
+        if (!c->d_counts_fused.p) HIPCHK(c, c->d_counts_fused.alloc(c->cells));
+        HIPCHK(c, hipMemsetAsync(c->d_counts_fused.p, 0, nb, c->stream));
         // counters written before tracking was switched on have no dirty bit: everything is marked once
     }
     // the bitmap last, published with geom.dirty: tracking is on (d_dirty set) only once everything it writes exists
-    HIPCHK(c, dev_realloc(&c->d_dirty, c->dirty_words));
-    c->geom.dirty = c->d_dirty; c->geom.dirty_pitch = pitch;
-    HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, c->dirty_words * sizeof(unsigned int), c->stream));
+    HIPCHK(c, c->d_dirty.alloc(c->dirty_words));
+    c->geom.dirty = c->d_dirty.p; c->geom.dirty_pitch = pitch;
+    HIPCHK(c, hipMemsetAsync(c->d_dirty.p, 0, c->dirty_words * sizeof(unsigned int), c->stream));
     if (c->next_seq != 0) HIPCHK(c, qs_launch_sf_mark_range(c, 0, c->cells));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
@@ -1300,7 +1285,7 @@ extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
 extern "C" int qs_dirty_blocks(qs_ctx *c, size_t *n_blocks, size_t *block_cells)
 {
     ARGCHK(c, c != nullptr && n_blocks != nullptr);
-    if (!c->d_dirty) return qs_fail(c, QS_E_STATE, "qs_dirty_blocks: dirty tracking is off (qs_dirty_tracking)");
+    if (!c->d_dirty.p) return qs_fail(c, QS_E_STATE, "qs_dirty_blocks: dirty tracking is off (qs_dirty_tracking)");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     HIPCHK(c, c->io_ws.reserve(sizeof(unsigned long long), c->stream, QS_IO_WS_FLOOR));
@@ -1313,30 +1298,41 @@ extern "C" int qs_dirty_blocks(qs_ctx *c, size_t *n_blocks, size_t *block_cells)
     return QS_OK;
 }
 
+// the per-rank arrays of a fuse of `world` ranks, carved from base (nullptr: only the size); returns the bytes
+static size_t sf_layout(const qs_ctx *c, void *base, int world, unsigned int *&bitmaps, unsigned int *&lists, unsigned int *&counts)
+{
+    Carve k(base);
+    bitmaps = k.take<unsigned int>((size_t)world * c->dirty_words);
+    lists = k.take<unsigned int>((size_t)world * c->dirty_words * 32);
+    counts = k.take<unsigned int>((size_t)world);
+    return k.bytes;
+}
+
 extern "C" int qs_sparse_fuse_begin(qs_ctx *c, int32_t world, int32_t rank, void **bitmaps_dev, size_t *bitmap_bytes)
 {
     ARGCHK(c, c != nullptr && bitmaps_dev != nullptr && bitmap_bytes != nullptr);
     ARGCHK(c, world >= 1 && world <= QS_SPARSE_MAX_WORLD && rank >= 0 && rank < world);
-    if (!c->d_dirty) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_begin: dirty tracking is off (qs_dirty_tracking)");
+    if (!c->d_dirty.p) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_begin: dirty tracking is off (qs_dirty_tracking)");
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     // a fuse begun here that never reached apply: its blocks did not travel, so they go into this one (before a change of
     // world reallocates the bitmaps).  Nothing else was committed: the counter deltas are taken from `sent`, which only
     // apply advances.
-    if (c->sf_state != 0) HIPCHK(c, qs_launch_sf_restore(c));
-    if (world != c->sf_world) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->sf_world = 0; c->sf_state = 0;                    // (until all three exist; a fuse in flight was restored above)
-        HIPCHK(c, dev_realloc(&c->d_sf_bitmaps, (size_t)world * c->dirty_words));
-        HIPCHK(c, dev_realloc(&c->d_sf_lists, (size_t)world * c->dirty_words * 32));
-        HIPCHK(c, dev_realloc(&c->d_sf_counts, (size_t)world));
+    if (c->sf_state != 0) { HIPCHK(c, qs_launch_sf_restore(c)); c->sf_state = 0; }
+    if (world != c->sf_world) {                              // (a growth that fails leaves the old arrays as they were)
+        unsigned int *bm, *li, *co;
+        DevBuf<char> meta;
+        HIPCHK(c, meta.alloc(sf_layout(c, nullptr, world, bm, li, co)));
+        HIPCHK(c, hipStreamSynchronize(c->stream));          // (the old arrays may still be in use)
+        c->sf_meta = std::move(meta);
+        sf_layout(c, c->sf_meta.p, world, c->d_sf_bitmaps, c->d_sf_lists, c->d_sf_counts);
         c->sf_world = world;
         c->sf_n.assign(world, 0); c->sf_off.assign((size_t)world + 1, 0);
     }
     c->sf_rank = rank;
     const size_t nb = c->dirty_words * sizeof(unsigned int);
-    HIPCHK(c, hipMemcpyAsync(c->d_sf_bitmaps + (size_t)rank * c->dirty_words, c->d_dirty, nb, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, nb, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_sf_bitmaps + (size_t)rank * c->dirty_words, c->d_dirty.p, nb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_dirty.p, 0, nb, c->stream));
     *bitmaps_dev = c->d_sf_bitmaps; *bitmap_bytes = nb;
     c->sf_state = 1;
     return QS_OK;
@@ -1370,7 +1366,7 @@ extern "C" int qs_sparse_fuse_apply(qs_ctx *c)
     HIPCHK(c, qs_launch_sf_apply(c));
     c->sf_state = 0;
     c->dirty_since_fuse = false;
-    if (c->d_counts) c->counts_view_fused = true;
+    if (c->d_counts.p) c->counts_view_fused = true;
     return QS_OK;
 }
 
@@ -1380,7 +1376,7 @@ extern "C" int qs_fuse(qs_ctx *dst, qs_ctx *const *srcs, size_t n)
     if (n == 0) return QS_OK;
     ARGCHK(dst, srcs != nullptr);
     std::vector<const void *> st(n), ct(n);
-    bool counts = dst->d_counts != nullptr;
+    bool counts = dst->d_counts.p != nullptr;
     for (size_t i = 0; i < n; i++) {
         qs_ctx *s = srcs[i];
         if (!s || s->device != dst->device || s->cfg.size != dst->cfg.size || s->cfg.res != dst->cfg.res ||
@@ -1390,8 +1386,8 @@ extern "C" int qs_fuse(qs_ctx *dst, qs_ctx *const *srcs, size_t n)
             return qs_fail(dst, QS_E_INVAL, "qs_fuse: source and destination are in different stamp epochs");
         { HIPCHK(dst, hipSetDevice(s->device)); int rcs = flush_edge_rays(s); if (rcs != QS_OK) return qs_fail(dst, rcs, s->err.c_str()); }
         HIPCHK(dst, hipStreamSynchronize(s->stream));
-        st[i] = s->d_stamps; ct[i] = s->d_counts;
-        if (!s->d_counts) counts = false;
+        st[i] = s->d_stamps.p; ct[i] = s->d_counts.p;
+        if (!s->d_counts.p) counts = false;
     }
     int rc = qs_fuse_buffers(dst, st.data(), counts ? ct.data() : nullptr, n);
     if (rc != QS_OK) return rc;
@@ -1676,12 +1672,12 @@ static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, i
     ARGCHK(c, c != nullptr && n_out != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_workspace_bytes(c), c->stream));
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
     void *ws = c->frontier_ws.p;
     HIPCHK(c, qs_launch_frontier_label(c, ws, mode != 0));
     HIPCHK(c, qs_launch_frontier_compact(c, ws, mode == 2 ? 0 : mode, 0, nullptr, nullptr, 0));
     unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_total_ptr(c, ws), sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, ws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (mode != 1) {
         // cells (mode 0: gx, gy), or every frontier cell with the first cell (row-major) of its 4-connected cluster (mode 2:
@@ -1736,29 +1732,28 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
     ARGCHK(c, cap == 0 || centroids_xy);
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_workspace_bytes(c), c->stream));
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
     void *fws = c->frontier_ws.p;
     HIPCHK(c, qs_launch_frontier_label(c, fws, true));
     HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
     unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_total_ptr(c, fws), sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n_cent = (size_t)total;
-    HIPCHK(c, c->ft_ws.reserve(qs_ft_workspace_bytes(n_cent, n_bots), c->stream));
-    QsFtState *d_st; double2 *d_cent, *d_bots, *d_txy; long long *d_tidx;
-    qs_ft_parts(c->ft_ws.p, n_cent, n_bots, &d_st, &d_cent, &d_bots, &d_tidx, &d_txy);
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, d_cent));
+    HIPCHK(c, c->ft_ws.reserve(qs_ft_layout(nullptr, n_cent, n_bots).bytes, c->stream));
+    const QsFtLayout F = qs_ft_layout(c->ft_ws.p, n_cent, n_bots);
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, F.cent));
     uint64_t fallbacks = 0;
     std::vector<long long> tidx(n_bots, -1);
     std::vector<double> txy(2 * n_bots);
     if (n_bots && n_cent) {
         const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation (0: nothing is too close)
-        HIPCHK(c, hipMemcpyAsync(d_bots, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.bots, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
         int start = 0, m = 0, pending = 0;
         for (;;) {
             HIPCHK(c, qs_launch_ft_assign(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m, pending));
             QsFtState st;
-            HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&st, F.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (!st.stop) break;
             if (st.next_bot < start || st.next_bot >= (int)n_bots || (pending && st.next_bot == start))
@@ -1767,11 +1762,11 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
             start = st.next_bot; m = st.m; pending = 1;
             HIPCHK(c, qs_launch_ft_fallback(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m));
         }
-        HIPCHK(c, hipMemcpyAsync(tidx.data(), d_tidx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(txy.data(), d_txy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tidx.data(), F.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(txy.data(), F.tgt_xy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     }
     const size_t nc = n_cent < cap ? n_cent : cap;
-    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, d_cent, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, F.cent, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t b = 0; b < n_bots; b++) {
         target_idx[b] = tidx[b];
@@ -1791,7 +1786,7 @@ extern "C" int qs_ekf_init(qs_ctx *c, int32_t bot, double t, const double x0[6])
     double f[44] = {0};
     for (int i = 0; i < 6; i++) { f[i] = x0 ? x0[i] : 0.0; f[6 + 7 * i] = 1.0; }     // x0, P = I  ekf.cpp:5-19
     f[42] = t; f[43] = 1.0;
-    HIPCHK(c, hipMemcpyAsync(c->d_ekf + (size_t)bot * 44, f, sizeof f, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_ekf.p + (size_t)bot * 44, f, sizeof f, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QS_OK;
 }
@@ -1824,7 +1819,7 @@ extern "C" int qs_ekf_state(qs_ctx *c, int32_t bot, double x[6], double P[36])
     if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_ekf_state: bot out of range");
     HIPCHK(c, hipSetDevice(c->device));
     double f[44];
-    HIPCHK(c, hipMemcpyAsync(f, c->d_ekf + (size_t)bot * 44, sizeof f, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(f, c->d_ekf.p + (size_t)bot * 44, sizeof f, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (x) memcpy(x, f, 6 * sizeof(double));
     if (P) memcpy(P, f + 6, 36 * sizeof(double));
@@ -1837,7 +1832,7 @@ extern "C" int qs_counters(qs_ctx *c, uint64_t out[QS_CNT_N])
     HIPCHK(c, hipSetDevice(c->device));
     FLUSHCHK(c);
     unsigned long long v[QS_CNT_N];
-    HIPCHK(c, hipMemcpyAsync(v, c->d_counters, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(v, c->d_counters.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < QS_CNT_N; i++) out[i] = v[i];
     out[QS_CNT_REBASES] = c->n_rebases;
@@ -1953,8 +1948,8 @@ extern "C" int qs_checkpoint(qs_ctx *c, uint8_t *buf, size_t cap, size_t *n_out)
     FLUSHCHK(c);                                             // waiting exact-trig rays go into the saved grid
     unsigned long long cnt[QS_CNT_N];
     std::vector<QsGraphDev> cur((size_t)c->n_graphs);
-    HIPCHK(c, hipMemcpyAsync(cnt, c->d_counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->d_counters.p, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cur.data(), c->d_graphs.p, cur.size() * sizeof(QsGraphDev), hipMemcpyDeviceToHost, c->stream));
     // census: the blocks that hold anything, listed on the device
     const CkGeom gm = ck_geom(c);
     HIPCHK(c, c->ck_census.reserve(gm.words * 33 + 1, c->stream));
@@ -1965,8 +1960,8 @@ extern "C" int qs_checkpoint(qs_ctx *c, uint8_t *buf, size_t cap, size_t *n_out)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (cnt[QS_CNT_SLAM_ROUNDS] >> 40)
         return qs_fail(c, QS_E_STATE, "qs_checkpoint: a loop-closure chain wait timed out (bit 40 of QS_CNT_SLAM_ROUNDS): the map may be wrong");
-    const bool tracking = c->d_dirty != nullptr;
-    const int planes = ck_planes(c->d_counts != nullptr, tracking), nb = c->cfg.max_agent + 1, G = c->n_graphs;
+    const bool tracking = c->d_dirty.p != nullptr;
+    const int planes = ck_planes(c->d_counts.p != nullptr, tracking), nb = c->cfg.max_agent + 1, G = c->n_graphs;
     std::vector<long long> L(G), C(G);
     for (int g = 0; g < G; g++) {
         L[g] = cur[g].n_lms; C[g] = cur[g].n_cls;
@@ -1986,14 +1981,14 @@ extern "C" int qs_checkpoint(qs_ctx *c, uint8_t *buf, size_t cap, size_t *n_out)
     };
     {
         size_t o = y.off[QS_CKPT_BOTS];
-        HIPCHK(c, d2d(o, c->d_offset, nb * 8)); o += nb * 8;
-        HIPCHK(c, d2d(o, c->d_drift, nb * 16)); o += nb * 16;
-        HIPCHK(c, d2d(o, c->d_last_closure, nb * 8)); o += nb * 8;
-        HIPCHK(c, d2d(o, c->d_zone, nb * 32)); o += nb * 32;
-        HIPCHK(c, d2d(o, c->d_ekf, (size_t)nb * 44 * 8)); o += (size_t)nb * 44 * 8;
-        HIPCHK(c, d2d(o, c->d_ekf_prev, nb * 32));
+        HIPCHK(c, d2d(o, c->d_offset.p, nb * 8)); o += nb * 8;
+        HIPCHK(c, d2d(o, c->d_drift.p, nb * 16)); o += nb * 16;
+        HIPCHK(c, d2d(o, c->d_last_closure.p, nb * 8)); o += nb * 8;
+        HIPCHK(c, d2d(o, c->d_zone.p, nb * 32)); o += nb * 32;
+        HIPCHK(c, d2d(o, c->d_ekf.p, (size_t)nb * 44 * 8)); o += (size_t)nb * 44 * 8;
+        HIPCHK(c, d2d(o, c->d_ekf_prev.p, nb * 32));
     }
-    HIPCHK(c, d2d(y.off[QS_CKPT_COUNTERS], c->d_counters, QS_CNT_N * 8));
+    HIPCHK(c, d2d(y.off[QS_CKPT_COUNTERS], c->d_counters.p, QS_CNT_N * 8));
     {
         size_t o = y.off[QS_CKPT_GRAPHS] + (size_t)G * 24;
         for (int g = 0; g < G; g++) {
@@ -2010,7 +2005,7 @@ extern "C" int qs_checkpoint(qs_ctx *c, uint8_t *buf, size_t cap, size_t *n_out)
     }
     HIPCHK(c, d2d(y.off[QS_CKPT_BLOCK_IDS], d_list, 4 * (size_t)n_blk));
     HIPCHK(c, qs_launch_ck_pack(c, d_list, n_blk, gm.pitch, planes, st + y.off[QS_CKPT_BLOCKS] - hb));
-    if (tracking) HIPCHK(c, d2d(y.off[QS_CKPT_DIRTY], c->d_dirty, 4 * gm.words));
+    if (tracking) HIPCHK(c, d2d(y.off[QS_CKPT_DIRTY], c->d_dirty.p, 4 * gm.words));
     memset(buf, 0, hb);
     HIPCHK(c, hipMemcpyAsync(buf + hb, st, body, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2055,7 +2050,7 @@ static int ck_apply(qs_ctx *c, const uint8_t *buf, const CkLayout &y, bool track
 {
     int rc = reset_state(c);
     if (rc != QS_OK) return rc;
-    if (tracking != (c->d_dirty != nullptr)) {
+    if (tracking != (c->d_dirty.p != nullptr)) {
         rc = qs_dirty_tracking(c, tracking ? 1 : 0);          // (after the reset: no unfused writes, sequence counter 0)
         if (rc != QS_OK) return rc;
     }
@@ -2073,31 +2068,31 @@ static int ck_apply(qs_ctx *c, const uint8_t *buf, const CkLayout &y, bool track
     };
     {
         size_t o = y.off[QS_CKPT_BOTS];
-        HIPCHK(c, d2d(c->d_offset, o, nb * 8)); o += nb * 8;
-        HIPCHK(c, d2d(c->d_drift, o, nb * 16)); o += nb * 16;
-        HIPCHK(c, d2d(c->d_last_closure, o, nb * 8)); o += nb * 8;
-        HIPCHK(c, d2d(c->d_zone, o, nb * 32)); o += nb * 32;
-        HIPCHK(c, d2d(c->d_ekf, o, (size_t)nb * 44 * 8)); o += (size_t)nb * 44 * 8;
-        HIPCHK(c, d2d(c->d_ekf_prev, o, nb * 32));
+        HIPCHK(c, d2d(c->d_offset.p, o, nb * 8)); o += nb * 8;
+        HIPCHK(c, d2d(c->d_drift.p, o, nb * 16)); o += nb * 16;
+        HIPCHK(c, d2d(c->d_last_closure.p, o, nb * 8)); o += nb * 8;
+        HIPCHK(c, d2d(c->d_zone.p, o, nb * 32)); o += nb * 32;
+        HIPCHK(c, d2d(c->d_ekf.p, o, (size_t)nb * 44 * 8)); o += (size_t)nb * 44 * 8;
+        HIPCHK(c, d2d(c->d_ekf_prev.p, o, nb * 32));
     }
-    HIPCHK(c, d2d(c->d_counters, y.off[QS_CKPT_COUNTERS], QS_CNT_N * 8));
+    HIPCHK(c, d2d(c->d_counters.p, y.off[QS_CKPT_COUNTERS], QS_CNT_N * 8));
     const unsigned int *d_list = (const unsigned int *)(st + y.off[QS_CKPT_BLOCK_IDS] - hb);
     HIPCHK(c, qs_launch_ck_unpack(c, d_list, (unsigned int)n_blk, gm.pitch, planes, st + y.off[QS_CKPT_BLOCKS] - hb));
-    if (tracking) HIPCHK(c, d2d(c->d_dirty, y.off[QS_CKPT_DIRTY], 4 * gm.words));
+    if (tracking) HIPCHK(c, d2d(c->d_dirty.p, y.off[QS_CKPT_DIRTY], 4 * gm.words));
     // closure logs in place; landmark logs through the index rebuild (slam.hip), which appends them again
     std::vector<QsIndexLog> logs((size_t)G);
     {
         size_t o = y.off[QS_CKPT_GRAPHS] + (size_t)G * 24;
         for (int g = 0; g < G; g++) {
-            const QsGraphDev &q = c->h_graphs[g];
+            const QsGraphBufs &q = c->graphs[g];
             const size_t l = (size_t)L[g], k = (size_t)C[g];
             const unsigned char *s = st + o - hb;
             logs[g] = QsIndexLog{(const double *)s, (const double *)(s + 8 * l), (const long long *)(s + 16 * l), s + 24 * l,
                                  L[g], N[g], C[g]};
             o += 24 * l + ck_pad8(l);
-            HIPCHK(c, d2d(q.cl_lm_idx, o, 8 * k)); HIPCHK(c, d2d(q.cl_node_idx, o + 8 * k, 8 * k));
-            HIPCHK(c, d2d(q.cl_dx, o + 16 * k, 8 * k)); HIPCHK(c, d2d(q.cl_dy, o + 24 * k, 8 * k));
-            HIPCHK(c, d2d(q.cl_agent, o + 32 * k, k));
+            HIPCHK(c, d2d(q.cl_lm_idx.p, o, 8 * k)); HIPCHK(c, d2d(q.cl_node_idx.p, o + 8 * k, 8 * k));
+            HIPCHK(c, d2d(q.cl_dx.p, o + 16 * k, 8 * k)); HIPCHK(c, d2d(q.cl_dy.p, o + 24 * k, 8 * k));
+            HIPCHK(c, d2d(q.cl_agent.p, o + 32 * k, k));
             o += 32 * k + ck_pad8(k);
         }
     }
@@ -2111,7 +2106,7 @@ static int ck_apply(qs_ctx *c, const uint8_t *buf, const CkLayout &y, bool track
     c->edge_rays_total = ck_get<uint64_t>(s, 24); c->edge_overflow_total = ck_get<uint64_t>(s, 32);
     c->sweep_min = ck_get<double>(s, 40); c->sweep_max = ck_get<double>(s, 48);
     c->dirty_since_fuse = ck_get<uint32_t>(s, 56) != 0;
-    c->counts_view_fused = tracking && c->d_counts && ck_get<uint32_t>(s, 60) != 0;   // (the dense snapshot is not saved)
+    c->counts_view_fused = tracking && c->d_counts.p && ck_get<uint32_t>(s, 60) != 0;   // (the dense snapshot is not saved)
     // the graphs' real counts and the pile flag the rebuild left, as at any synchronisation point
     return read_pile_flag(c);
 }
@@ -2167,7 +2162,7 @@ extern "C" int qs_restore(qs_ctx *c, const uint8_t *buf, size_t n)
             CK_BAD("qs_restore: bad sizes of graph %d", g);
     }
     const CkGeom gm = ck_geom(c);
-    const int planes = ck_planes(c->d_counts != nullptr, tracking);
+    const int planes = ck_planes(c->d_counts.p != nullptr, tracking);
     const size_t n_blk = len[QS_CKPT_BLOCK_IDS] / 4;
     const CkLayout y = ck_layout(nb, G, L, C, n_blk, qs_ck_block_bytes(planes), tracking, gm.words);
     if (y.header_bytes != hb || y.total != n || y.n_sections != (int)n_sec) CK_BAD("qs_restore: section lengths do not add up");

@@ -141,17 +141,22 @@ struct QsBatch {
     unsigned char *hit_valid; // MIN < d <= MAX per ray (:888); the tiled raycast writes it on the ingest path
 };
 
-// ---- owning device buffer of host code: freed when it goes out of scope ---------------------------
-// alloc: the scratch of one call, into an empty buffer.  reserve: the one way a grown workspace changes size -- exactly
-// `need` elements, or (floor > 0) floor doubled until it holds them.  The capacity is 0 from before the old block is freed
-// until the new one exists, so a failed growth leaves an empty buffer, never a capacity over a null pointer.
+// ---- owning device buffer of host code: freed when it goes out of scope or is assigned over ---------------------------
+// alloc: into an empty buffer.  reserve: the one way a grown workspace changes size -- exactly `need` elements, or
+// (floor > 0) floor doubled until it holds them.  The capacity is 0 from before the old block is freed until the new one
+// exists, so a failed growth leaves an empty buffer, never a capacity over a null pointer.  Arrays whose contents must
+// survive a growth (or whose views must stay valid if it fails) are grown by allocating a new buffer and moving it in.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;      // elements
     DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { hipFree(p); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
     ~DevBuf() { hipFree(p); }
     hipError_t alloc(size_t n)
     {
@@ -174,6 +179,29 @@ struct DevBuf {
     }
 };
 
+// ---- workspace layout: a bump allocator over one block, every piece on a 256-byte boundary ----------------------------
+// Each workspace has one layout function that carves it: run over the block it hands out the pieces, run over nullptr it
+// hands out nullptrs and only adds up the bytes the block needs (hipMalloc's blocks are at least 256-byte aligned).
+struct Carve {
+    char *base;
+    size_t bytes = 0;
+    explicit Carve(void *b) : base((char *)b) {}
+    template <typename T> T *take(size_t n)
+    {
+        T *q = base ? (T *)(base + bytes) : nullptr;
+        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+        return q;
+    }
+};
+
+// ---- the device arrays of one pose graph; QsGraphDev, the view the kernels read, is filled from them ------------------
+struct QsGraphBufs {
+    DevBuf<double> lm_x, lm_y; DevBuf<long long> lm_idx; DevBuf<unsigned char> lm_type;
+    DevBuf<long long> cl_lm_idx, cl_node_idx; DevBuf<double> cl_dx, cl_dy; DevBuf<unsigned char> cl_agent;
+    DevBuf<QsDirEntry> dir; DevBuf<QsLmNode> nodes; DevBuf<unsigned int> nd_next, misc;
+    long long cap_lms = 0, cap_cls = 0;      // entries of the landmark / closure logs (set once every array of a log has grown)
+};
+
 struct qs_ctx {
     qs_config cfg;
     int device = 0;
@@ -188,17 +216,19 @@ struct qs_ctx {
     double r2_threshold = 0.0;   // s < r2_threshold  <=>  sqrt(s) < closure_radius
     QsGeom geom;
 
-    unsigned int *d_stamps = nullptr;            // [size][size]; 0 = UNKNOWN, else (ordinal<<1)|occ
-    unsigned long long *d_counts = nullptr;      // [size][size]; hi32 = hits, lo32 = misses (this context's own writes)
-    unsigned long long *d_counts_fused = nullptr; // [size][size]; snapshot of d_counts that a collective sums over the ranks
+    // Every device block the context holds is a DevBuf (freed by `delete`); the raw pointers below are views into them.
+    DevBuf<unsigned int> d_stamps;               // [size][size]; 0 = UNKNOWN, else (ordinal<<1)|occ
+    DevBuf<unsigned long long> d_counts;         // [size][size]; hi32 = hits, lo32 = misses (this context's own writes)
+    DevBuf<unsigned long long> d_counts_fused;   // [size][size]; snapshot of d_counts that a collective sums over the ranks
     bool counts_view_fused = false;              // qs_grid_counts / qs_grid_logodds read the fused snapshot
     bool dirty_since_fuse = false;               // cells written since the last qs_mark_fused (sharded streams: rebase guard)
     // sparse fuse (sparse_fuse.hip)
-    unsigned int *d_dirty = nullptr;             // live bitmap [blocks_y][dirty_pitch]
+    DevBuf<unsigned int> d_dirty;                // live bitmap [blocks_y][dirty_pitch]
     size_t dirty_words = 0;
     int blocks_x = 0, blocks_y = 0;
-    unsigned long long *d_counts_sent = nullptr; // [size][size]: this context's counters as of its last sparse fuse (deltas travel)
+    DevBuf<unsigned long long> d_counts_sent;    // [size][size]: this context's counters as of its last sparse fuse (deltas travel)
     int sf_world = 0, sf_rank = 0;
+    DevBuf<char> sf_meta;                        // the three arrays below, carved for sf_world ranks (qs_api.hip: sf_layout)
     unsigned int *d_sf_bitmaps = nullptr;        // [sf_world][dirty_words]: every rank's bitmap of the fuse in flight
     unsigned int *d_sf_lists = nullptr;          // [sf_world][dirty_words * 32] block ids, ascending
     unsigned int *d_sf_counts = nullptr;         // [sf_world] blocks per rank
@@ -206,24 +236,23 @@ struct qs_ctx {
     std::vector<unsigned int> sf_n;              // host copy of d_sf_counts
     std::vector<size_t> sf_off;                  // [sf_world + 1] byte offsets of the ranks' segments in the payload
     int sf_state = 0;                            // 0 idle, 1 begun, 2 planned
-    double *d_offset = nullptr;                  // [max_agent+1]
-    double *d_drift = nullptr;                   // [max_agent+1][2]
-    long long *d_last_closure = nullptr;         // [max_agent+1]
-    unsigned long long *d_zone = nullptr;        // [max_agent+1][4] ordered-u64 minx,miny,maxx,maxy
-    unsigned long long *d_counters = nullptr;    // [QS_CNT_N]
-    unsigned long long *d_graph_batch = nullptr; // [n_graphs][2]: accepted, landmark events of the batch
-    double *d_ekf = nullptr;                     // [max_agent+1][44]
-    double *d_ekf_prev = nullptr;                // [max_agent+1][4]
+    DevBuf<double> d_offset;                     // [max_agent+1]
+    DevBuf<double> d_drift;                      // [max_agent+1][2]
+    DevBuf<long long> d_last_closure;            // [max_agent+1]
+    DevBuf<unsigned long long> d_zone;           // [max_agent+1][4] ordered-u64 minx,miny,maxx,maxy
+    DevBuf<unsigned long long> d_counters;       // [QS_CNT_N]
+    DevBuf<unsigned long long> d_graph_batch;    // [n_graphs][2]: accepted, landmark events of the batch
+    DevBuf<double> d_ekf;                        // [max_agent+1][44]
+    DevBuf<double> d_ekf_prev;                   // [max_agent+1][4]
 
-    QsGraphDev *d_graphs = nullptr;
-    std::vector<QsGraphDev> h_graphs;            // host mirror of pointers/capacities
+    DevBuf<QsGraphDev> d_graphs;                 // [n_graphs] the views the kernels read (and the counters only they write)
+    std::vector<QsGraphBufs> graphs;             // [n_graphs] their arrays
     std::vector<long long> lms_upper, cls_upper; // host upper bounds on n_lms / n_cls
 
-    // batch staging
+    // batch arrays: b and sb are carved from batch_ws for cap_batch records (qs_api.hip: batch_layout)
     size_t cap_batch = 0;
-    unsigned char *d_pkts = nullptr; size_t cap_pkts_bytes = 0;
-    unsigned short *d_lens = nullptr;
-    double *d_time = nullptr;
+    DevBuf<char> batch_ws;
+    DevBuf<char> stage_ws;                       // host records staged on the device (qs_api.hip: staging_layout)
     QsBatch b{};
     QsSlamBatch sb{};
     QsBucketGeom bg{};
@@ -247,8 +276,8 @@ struct qs_ctx {
     bool last_sweeps = false;                    //   the last ingest was qs_ingest_sweeps*: qs_last_sweeps may read it
 
     uint64_t next_seq = 0, epoch_base = 0, n_rebases = 0;
-    unsigned int *d_flags = nullptr;             // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)
-    QsEdgeRec *d_edge = nullptr;                 // [QS_EDGE_CAP] the waiting rays
+    DevBuf<unsigned int> d_flags;                // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)
+    DevBuf<QsEdgeRec> d_edge;                    // [QS_EDGE_CAP] the waiting rays
     bool edge_maybe = false;                     // an exact-trig ingest has run since the last flush: the list may hold rays
     bool pile_mode = false;                      // launch the chain kernel's DENSE variant
     bool flags_maybe = false;                    // a loop-closure chain has run since the flags were read last
@@ -311,7 +340,6 @@ hipError_t qs_launch_update_rays(qs_ctx *c, const double *rx, const double *ry, 
 hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axis, long long *out);
 // raycast_tiled.hip
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
-size_t qs_tiled_workspace_bytes(const qs_ctx *c, size_t n);
 bool qs_tiled_supported(const qs_ctx *c);
 // sweep.hip: n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
 hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
@@ -353,24 +381,33 @@ hipError_t qs_launch_ck_unpack(qs_ctx *c, const unsigned int *list, unsigned int
 hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out);
 // frontier.hip
 #define QS_FR_CHUNK 1024          // cells per chunk of the frontier compactions (count -> scan -> ranked write)
-size_t qs_frontier_workspace_bytes(const qs_ctx *c);
+// the workspace of the labelling and the compactions, carved from ws (nullptr: only the bytes the block needs):
+// [cells] labels, cells and sums of gx, gy per cluster (at its root); [chunks] counts of a compaction -> offsets; their sum
+struct QsFrLayout { unsigned int *label, *cnt; unsigned long long *sumx, *sumy; unsigned int *chunk; unsigned long long *total; size_t bytes; };
+QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws);
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
 hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap);
-unsigned long long *qs_frontier_total_ptr(const qs_ctx *c, void *ws);
-void qs_frontier_ws_parts(const qs_ctx *c, void *ws, unsigned int **cnt, unsigned long long **sumx, unsigned long long **sumy,
-                          unsigned int **chunk, unsigned long long **total);
 hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
 // frontier_targets.hip
 #define QS_FT_K 32                // candidates per bot (the top-K list of the greedy pass)
 struct QsFtState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
-size_t qs_ft_workspace_bytes(size_t n_cent, size_t n_bots);
+// the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
+struct QsFtLayout {
+    QsFtState *st;
+    double2 *cent, *bots, *tgt_xy, *asg_xy;
+    long long *tgt_idx;
+    int *asg_idx;
+    double *part_key; int *part_idx;      // [n_bots][n_chunks][K]
+    int *list_idx, *list_len;             // [n_bots][K], [n_bots]
+    double *fb_key; int *fb_idx;          // [n_fb]: per-block minima of a fallback scan
+    size_t bytes;
+};
+QsFtLayout qs_ft_layout(void *ws, size_t n_cent, size_t n_bots);
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
 // the lists, then the greedy pass from start_bot (fb_pending: a fallback scan has decided start_bot); it ends in QsFtState
 hipError_t qs_launch_ft_assign(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep,
                                int start_bot, int start_m, int fb_pending);
 hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep, int bot, int m);
-void qs_ft_parts(void *ft_ws, size_t n_cent, size_t n_bots, QsFtState **st, double2 **cent, double2 **bots, long long **tgt_idx,
-                 double2 **tgt_xy);
 // icp.hip
 hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
                             double max_d2, int *corr, double *d2);

@@ -86,12 +86,12 @@ hipError_t qs_launch_raycast_direct(qs_ctx *c, size_t n, uint64_t seq0)
     const unsigned long long ord_stride = 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1);
     if (c->cfg.enable_counts)
         hipLaunchKernelGGL(qs_raycast_direct_kernel<true>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n,
-                           c->b, c->geom, c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone,
-                           c->cfg.max_agent, c->d_counters);
+                           c->b, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p,
+                           c->cfg.max_agent, c->d_counters.p);
     else
         hipLaunchKernelGGL(qs_raycast_direct_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n,
-                           c->b, c->geom, c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone,
-                           c->cfg.max_agent, c->d_counters);
+                           c->b, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p,
+                           c->cfg.max_agent, c->d_counters.p);
     return hipGetLastError();
 }
 
@@ -126,10 +126,10 @@ hipError_t qs_launch_update_rays(qs_ctx *c, const double *rx, const double *ry, 
     const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
     if (c->cfg.enable_counts)
         hipLaunchKernelGGL(qs_update_rays_kernel<true>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n, rx, ry,
-                           hx, hy, valid, c->geom, c->d_stamps, c->d_counts, ord_base, c->d_counters);
+                           hx, hy, valid, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, c->d_counters.p);
     else
         hipLaunchKernelGGL(qs_update_rays_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n, rx, ry,
-                           hx, hy, valid, c->geom, c->d_stamps, c->d_counts, ord_base, c->d_counters);
+                           hx, hy, valid, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, c->d_counters.p);
     return hipGetLastError();
 }
 
@@ -153,11 +153,11 @@ __global__ void qs_edge_cast_kernel(unsigned int n_edge, const QsEdgeRec *__rest
 hipError_t qs_launch_edge_cast(qs_ctx *c, unsigned int n_edge, const double *d_in)
 {
     if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_edge_cast_kernel<true>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge, d_in, c->geom,
-                           c->d_stamps, c->d_counts, c->d_counters);
+        hipLaunchKernelGGL(qs_edge_cast_kernel<true>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge.p, d_in, c->geom,
+                           c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     else
-        hipLaunchKernelGGL(qs_edge_cast_kernel<false>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge, d_in, c->geom,
-                           c->d_stamps, c->d_counts, c->d_counters);
+        hipLaunchKernelGGL(qs_edge_cast_kernel<false>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge.p, d_in, c->geom,
+                           c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     return hipGetLastError();
 }
 

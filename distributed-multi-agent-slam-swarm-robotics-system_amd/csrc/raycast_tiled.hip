@@ -438,8 +438,6 @@ qs_raster_kernel(QtWorkspace ws, int size, unsigned int *__restrict__ stamps,
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-static inline size_t qt_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static inline int qt_n_tiles(const qs_ctx *c)
 {
     const int tiles_x = (c->cfg.size + QT_TILE - 1) / QT_TILE;
@@ -448,28 +446,28 @@ static inline int qt_n_tiles(const qs_ctx *c)
 
 bool qs_tiled_supported(const qs_ctx *c) { return qt_n_tiles(c) <= QT_MAX_TILES; }
 
-size_t qs_tiled_workspace_bytes(const qs_ctx *c, size_t n)
+// the workspace of up to cap_rays ray slots (4 per packet) over ws.n_tiles tiles, carved from base (nullptr: only the
+// size); returns its bytes
+static size_t qt_layout(void *base, size_t cap_rays, QtWorkspace &ws)
 {
-    const size_t n_tiles = (size_t)qt_n_tiles(c);
-    return qt_align((size_t)QT_MAX_WG * n_tiles * sizeof(unsigned int)) + 3 * qt_align((n_tiles + 1) * sizeof(unsigned int)) +
-           qt_align(4 * n * sizeof(uint2)) + qt_align(16 * n * sizeof(uint2));
+    const size_t n_pk = (cap_rays + 3) / 4, tiles = (size_t)ws.n_tiles;
+    Carve k(base);
+    ws.table = k.take<unsigned int>((size_t)QT_MAX_WG * tiles);
+    ws.tile_count = k.take<unsigned int>(tiles + 1);
+    ws.tile_base = k.take<unsigned int>(tiles + 1);
+    ws.chunk_base = k.take<unsigned int>(tiles + 1);
+    ws.rays = k.take<uint2>(4 * n_pk);
+    ws.recs = k.take<uint2>(16 * n_pk);
+    return k.bytes;
 }
 
 hipError_t qt_workspace(qs_ctx *c, size_t cap_rays, QtWorkspace &ws)
 {
-    // (the byte count of qs_tiled_workspace_bytes, in ray slots: 4 per packet)
-    hipError_t e = c->bin_ws.reserve(qs_tiled_workspace_bytes(c, (cap_rays + 3) / 4), c->stream);
-    if (e != hipSuccess) return e;
     ws.tiles_x = (c->cfg.size + QT_TILE - 1) / QT_TILE;
     ws.n_tiles = ws.tiles_x * ws.tiles_x;
-    const size_t tbytes = qt_align(((size_t)ws.n_tiles + 1) * sizeof(unsigned int));
-    char *p = c->bin_ws.p;
-    ws.table = (unsigned int *)p; p += qt_align((size_t)QT_MAX_WG * ws.n_tiles * sizeof(unsigned int));
-    ws.tile_count = (unsigned int *)p; p += tbytes;
-    ws.tile_base = (unsigned int *)p; p += tbytes;
-    ws.chunk_base = (unsigned int *)p; p += tbytes;
-    ws.rays = (uint2 *)p; p += qt_align(4 * ((cap_rays + 3) / 4) * sizeof(uint2));
-    ws.recs = (uint2 *)p;
+    hipError_t e = c->bin_ws.reserve(qt_layout(nullptr, cap_rays, ws), c->stream);
+    if (e != hipSuccess) return e;
+    qt_layout(c->bin_ws.p, cap_rays, ws);
     ws.dirty = c->geom.dirty; ws.dirty_pitch = c->geom.dirty_pitch;
     return hipSuccess;
 }
@@ -505,10 +503,10 @@ hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays
     StageTimer t_raster(c, QS_STAGE_RC_RASTER);
     if (c->cfg.enable_counts)
         hipLaunchKernelGGL(qs_raster_kernel<true>, dim3(raster_wgs), dim3(QT_BLOCK), 0, c->stream, ws,
-                           c->cfg.size, c->d_stamps, c->d_counts, c->d_counters);
+                           c->cfg.size, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     else
         hipLaunchKernelGGL(qs_raster_kernel<false>, dim3(raster_wgs), dim3(QT_BLOCK), 0, c->stream, ws,
-                           c->cfg.size, c->d_stamps, c->d_counts, c->d_counters);
+                           c->cfg.size, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     t_raster.stop();
     return hipGetLastError();
 }
@@ -536,10 +534,10 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
     if (c->cfg.enable_counts) {
         hipLaunchKernelGGL(qs_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
+                           c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
     } else {
         hipLaunchKernelGGL(qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps, c->d_counts, ord_base, ord_stride, c->d_zone, c->cfg.max_agent, c->d_counters);
+                           c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
     }
     t_rays.stop();
     return qt_launch_sort_raster(c, ws, 4 * n, c->b.hit_valid, ord_base, ord_stride, lds);

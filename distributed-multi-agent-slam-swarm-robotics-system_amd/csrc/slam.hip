@@ -1752,15 +1752,15 @@ qs_slam_reset_counters_kernel(QsGraphDev *__restrict__ graphs, int n_graphs, uns
 
 hipError_t qs_launch_slam_reset_index(qs_ctx *c)
 {
-    if (!c->d_graphs || c->n_graphs <= 0) return hipSuccess;
+    if (!c->d_graphs.p || c->n_graphs <= 0) return hipSuccess;
     const unsigned int first_pool = (unsigned int)(1 + c->dir_entries);
     const int nb = c->cfg.max_agent + 1, m = nb > c->n_graphs ? nb : c->n_graphs;
     // (one graph can hold the whole session's landmarks -- 2 x 10^5 entries of 32 words after one configs[1] step --: enough
     // workgroups to fill the chip whatever the number of graphs; 64 per graph took 0.28 ms there, 2048 take 0.03)
     const int per_graph = c->n_graphs >= 32 ? 64 : 2048 / c->n_graphs;
-    hipLaunchKernelGGL(qs_slam_reset_index_kernel, dim3(per_graph, c->n_graphs), dim3(256), 0, c->stream, c->d_graphs, c->bg, first_pool);
-    hipLaunchKernelGGL(qs_slam_reset_counters_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->d_graphs, c->n_graphs,
-                       first_pool, c->d_last_closure, nb, -(long long)c->cfg.min_poses_between);
+    hipLaunchKernelGGL(qs_slam_reset_index_kernel, dim3(per_graph, c->n_graphs), dim3(256), 0, c->stream, c->d_graphs.p, c->bg, first_pool);
+    hipLaunchKernelGGL(qs_slam_reset_counters_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->d_graphs.p, c->n_graphs,
+                       first_pool, c->d_last_closure.p, nb, -(long long)c->cfg.min_poses_between);
     return hipGetLastError();
 }
 
@@ -1807,8 +1807,8 @@ qs_slam_rebuild_index_kernel(QsGraphDev *__restrict__ graphs, QsBucketGeom bg, c
 hipError_t qs_launch_slam_rebuild_index(qs_ctx *c, const QsIndexLog *d_logs)
 {
     if (c->n_graphs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(qs_slam_rebuild_index_kernel, dim3(c->n_graphs), dim3(QS_WAVE), 0, c->stream, c->d_graphs, c->bg, d_logs,
-                       c->d_flags + QS_FLAG_PILE);
+    hipLaunchKernelGGL(qs_slam_rebuild_index_kernel, dim3(c->n_graphs), dim3(QS_WAVE), 0, c->stream, c->d_graphs.p, c->bg, d_logs,
+                       c->d_flags.p + QS_FLAG_PILE);
     return hipGetLastError();
 }
 
@@ -1821,13 +1821,13 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     hipLaunchKernelGGL(qs_slam_count_kernel, dim3(sb.n_blocks), dim3(IDX_BLOCK), 0, c->stream, n, c->b, sb,
                        c->bots_per_graph, G);
     hipLaunchKernelGGL(qs_slam_blockscan_kernel, dim3(G), dim3(256), 0, c->stream, sb);
-    hipLaunchKernelGGL(qs_slam_prefix_kernel, dim3(1), dim3(256), 0, c->stream, sb, G, c->cfg.max_agent, c->d_drift);
+    hipLaunchKernelGGL(qs_slam_prefix_kernel, dim3(1), dim3(256), 0, c->stream, sb, G, c->cfg.max_agent, c->d_drift.p);
     hipLaunchKernelGGL(qs_slam_index_kernel, dim3(sb.n_blocks), dim3(IDX_BLOCK), (size_t)IDX_WAVES * G * 2 * sizeof(unsigned int),
-                       c->stream, n, c->b, sb, c->d_graphs, c->bots_per_graph, G);
+                       c->stream, n, c->b, sb, c->d_graphs.p, c->bots_per_graph, G);
     StageTimer t_chain(c, QS_STAGE_SLAM_CHAIN);
-#define CH_LAUNCH(ONE_, DENSE_) hipLaunchKernelGGL((qs_slam_chain_kernel<ONE_, DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs, sb, c->bg, \
+#define CH_LAUNCH(ONE_, DENSE_) hipLaunchKernelGGL((qs_slam_chain_kernel<ONE_, DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->win, c->cfg.min_poses_between, c->r2_threshold,                          \
-                           c->cfg.closure_correction, c->d_drift, c->d_last_closure, c->d_counters, raw_pose ? 1 : 0, c->d_flags + QS_FLAG_PILE)
+                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
     const bool one = c->bots_per_graph <= CH_AGW;
     // which form (qs_set_chain_form; QS_CHAIN_MODE at qs_create).  Left to itself the library runs the free-running form; for
     // graphs of up to CH_AGW agents without the posting of poses until a batch had more than 1 decision in 8 wait for the
@@ -1837,12 +1837,12 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     const bool free_mode = c->chain_form != QS_CHAIN_WINDOW && !(c->chain_form == QS_CHAIN_AUTO && one && c->chain_windowed);
     c->chain_last_posting = false;
     c->chain_last_free = free_mode;
-#define FR_LAUNCH(DENSE_, WAVES_, POST_) hipLaunchKernelGGL((qs_slam_chain_free_kernel<DENSE_, WAVES_, POST_>), dim3(G), dim3(WAVES_ * QS_WAVE), 0, c->stream, c->d_graphs, sb, c->bg, \
+#define FR_LAUNCH(DENSE_, WAVES_, POST_) hipLaunchKernelGGL((qs_slam_chain_free_kernel<DENSE_, WAVES_, POST_>), dim3(G), dim3(WAVES_ * QS_WAVE), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
-                           c->cfg.closure_correction, c->d_drift, c->d_last_closure, c->d_counters, raw_pose ? 1 : 0, c->d_flags + QS_FLAG_PILE)
-#define DY_LAUNCH(DENSE_) hipLaunchKernelGGL((qs_slam_chain_dyn_kernel<DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs, sb, c->bg, \
+                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
+#define DY_LAUNCH(DENSE_) hipLaunchKernelGGL((qs_slam_chain_dyn_kernel<DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
-                           c->cfg.closure_correction, c->d_drift, c->d_last_closure, c->d_counters, raw_pose ? 1 : 0, c->d_flags + QS_FLAG_PILE)
+                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
     if (free_mode) {
         if (one) {
             const bool post = c->chain_form == QS_CHAIN_FREE_POSTING || (c->chain_form == QS_CHAIN_AUTO && c->chain_posting);

@@ -21,7 +21,7 @@
 #define SF_CELLS (SF_BW * SF_BH)             // 64: one lane per cell
 #define SF_LIST_BLOCK 1024
 
-size_t qs_sf_block_bytes(const qs_ctx *c) { return SF_CELLS * (sizeof(unsigned int) + (c->d_counts ? sizeof(unsigned long long) : 0)); }
+size_t qs_sf_block_bytes(const qs_ctx *c) { return SF_CELLS * (sizeof(unsigned int) + (c->d_counts.p ? sizeof(unsigned long long) : 0)); }
 
 // ---- mark a cell range dirty (qs_fuse_buffers*: a local fold writes the grid without going through a raycast) ---------
 __global__ void qs_sf_mark_rows_kernel(unsigned int *__restrict__ dirty, int pitch, int blocks_x, int by_lo, int by_hi)
@@ -36,11 +36,11 @@ __global__ void qs_sf_mark_rows_kernel(unsigned int *__restrict__ dirty, int pit
 }
 hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells)
 {
-    if (!c->d_dirty || n_cells == 0) return hipSuccess;
+    if (!c->d_dirty.p || n_cells == 0) return hipSuccess;
     const int by_lo = (int)(cell_off / c->cfg.size) / SF_BH;
     const int by_hi = (int)((cell_off + n_cells - 1) / c->cfg.size) / SF_BH + 1;
     const int n = (by_hi - by_lo) * c->geom.dirty_pitch;
-    hipLaunchKernelGGL(qs_sf_mark_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_dirty, c->geom.dirty_pitch,
+    hipLaunchKernelGGL(qs_sf_mark_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_dirty.p, c->geom.dirty_pitch,
                        c->blocks_x, by_lo, by_hi);
     return hipGetLastError();
 }
@@ -55,8 +55,8 @@ __global__ void qs_sf_restore_kernel(unsigned int *__restrict__ dirty, const uns
 }
 hipError_t qs_launch_sf_restore(qs_ctx *c)
 {
-    if (!c->d_dirty || !c->d_sf_bitmaps || c->sf_rank >= c->sf_world) return hipSuccess;
-    hipLaunchKernelGGL(qs_sf_restore_kernel, dim3((unsigned int)((c->dirty_words + 255) / 256)), dim3(256), 0, c->stream, c->d_dirty,
+    if (!c->d_dirty.p || !c->d_sf_bitmaps || c->sf_rank >= c->sf_world) return hipSuccess;
+    hipLaunchKernelGGL(qs_sf_restore_kernel, dim3((unsigned int)((c->dirty_words + 255) / 256)), dim3(256), 0, c->stream, c->d_dirty.p,
                        c->d_sf_bitmaps + (size_t)c->sf_rank * c->dirty_words, c->dirty_words);
     return hipGetLastError();
 }
@@ -123,7 +123,7 @@ hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out)
 {
     hipError_t e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long), c->stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(qs_sf_popcount_kernel, dim3(64), dim3(256), 0, c->stream, c->d_dirty, c->dirty_words, c->geom.dirty_pitch,
+    hipLaunchKernelGGL(qs_sf_popcount_kernel, dim3(64), dim3(256), 0, c->stream, c->d_dirty.p, c->dirty_words, c->geom.dirty_pitch,
                        c->blocks_x, d_out);
     return hipGetLastError();
 }
@@ -160,12 +160,12 @@ hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst)
     if (n_own == 0) return hipSuccess;
     const unsigned int *list = c->d_sf_lists + (size_t)c->sf_rank * c->dirty_words * 32;
     const unsigned int blocks = (n_own + 3) / 4 < 4096 ? (n_own + 3) / 4 : 4096;
-    if (c->d_counts)
+    if (c->d_counts.p)
         hipLaunchKernelGGL(qs_sf_pack_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, list, n_own, c->geom.dirty_pitch, c->cfg.size,
-                           c->d_stamps, c->d_counts, c->d_counts_sent, dst);
+                           c->d_stamps.p, c->d_counts.p, c->d_counts_sent.p, dst);
     else
         hipLaunchKernelGGL(qs_sf_pack_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, list, n_own, c->geom.dirty_pitch, c->cfg.size,
-                           c->d_stamps, c->d_counts, c->d_counts_sent, dst);
+                           c->d_stamps.p, c->d_counts.p, c->d_counts_sent.p, dst);
     return hipGetLastError();
 }
 
@@ -216,11 +216,11 @@ hipError_t qs_launch_sf_apply(qs_ctx *c)
     pl.first[c->sf_world] = run;
     if (run == 0) return hipSuccess;
     const unsigned int blocks = (run + 3) / 4 < 8192 ? (run + 3) / 4 : 8192;
-    if (c->d_counts)
+    if (c->d_counts.p)
         hipLaunchKernelGGL(qs_sf_apply_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
+                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps.p, c->d_counts_fused.p, c->d_counts_sent.p);
     else
         hipLaunchKernelGGL(qs_sf_apply_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
-                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps, c->d_counts_fused, c->d_counts_sent);
+                           c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps.p, c->d_counts_fused.p, c->d_counts_sent.p);
     return hipGetLastError();
 }

@@ -249,7 +249,7 @@ hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
     a.pkts = d_pkts; a.n = n; a.stride = stride; a.lens = d_lens;
     a.ranges_off = stride == QS_SWEEP_SIZE_V0 ? 19u : 27u;
     a.max_agent = c->cfg.max_agent;
-    a.offset = c->d_offset; a.drift = c->d_drift;
+    a.offset = c->d_offset.p; a.drift = c->d_drift.p;
     a.smin = c->sweep_min; a.smax = c->sweep_max;
     a.accept = accept; a.pose = pose;
     a.ord_base = 4ull * (seq0 - c->epoch_base);
@@ -257,10 +257,10 @@ hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
         if (c->cfg.enable_counts)
             hipLaunchKernelGGL(qs_sweep_direct_kernel<true>, dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
-                               c->d_stamps, c->d_counts, c->d_counters);
+                               c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         else
             hipLaunchKernelGGL(qs_sweep_direct_kernel<false>, dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
-                               c->d_stamps, c->d_counts, c->d_counters);
+                               c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         return hipGetLastError();
     }
     QtWorkspace ws;
@@ -280,10 +280,10 @@ hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
     if (c->cfg.enable_counts)
         hipLaunchKernelGGL(qs_sweep_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
-                           hit_valid, c->d_stamps, c->d_counts, c->d_counters);
+                           hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     else
         hipLaunchKernelGGL(qs_sweep_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
-                           hit_valid, c->d_stamps, c->d_counts, c->d_counters);
+                           hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     t_rays.stop();
     // slot r = 184 k + i has stamp ordinal ord_base + 4 (r >> 2) + (r & 3) + 1 = ord_base + r + 1: the 4-ray layout's
     return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);

@@ -18,6 +18,12 @@ QS_CNT_NAMES = ("datagrams", "accepted", "rays", "cells", "hits", "closures", "l
 QS_FT_MAX_BOTS = 1024       # bots per qs_frontier_targets call (include/quasar_slam.h)
 QS_STAGE_NAMES = ("decode", "slam", "raycast", "ekf", "slam_chain", "rc_rays", "rc_sort", "rc_raster")
 UINT64_MAX = (1 << 64) - 1
+QS_PLAN_STATUS = ("ok", "no_start", "no_goal", "unreachable")    # QS_PLAN_OK .. QS_PLAN_UNREACHABLE (include/quasar_slam.h)
+
+
+class QsPlanParams(C.Structure):
+    """struct qs_plan_params (include/quasar_slam.h)."""
+    _fields_ = [("clearance", C.c_int32), ("snap_radius", C.c_int32), ("lookahead", C.c_int32), ("reserved", C.c_int32)]
 
 
 class QsConfig(C.Structure):
@@ -129,6 +135,9 @@ SIGNATURES = {
     "qs_frontier_members": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_clusters": (_i32, [_vp, _i32, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_targets": (_i32, [_vp, _i32, _f64, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "qs_traversable": (_i32, [_vp, _i32, _vp]),
+    "qs_plan_field": (_i32, [_vp, _vp, _vp, _vp]),
+    "qs_plan_paths": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_ekf_init": (_i32, [_vp, _i32, _f64, _vp]),
     "qs_ekf_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32]),
     "qs_ekf_state": (_i32, [_vp, _i32, _vp, _vp]),

@@ -264,6 +264,7 @@ struct qs_ctx {
     DevBuf<char> bin_ws;                         // tile-binned raycast (raycast_tiled.hip)
     DevBuf<char> frontier_ws;                    // frontier labelling (allocated on first use)
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
+    DevBuf<char> plan_ws;                        // path planning (plan.hip: qs_plan_layout)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
     DevBuf<unsigned int> ck_census;              // checkpoint (checkpoint.hip): block bitmap, block list, count
@@ -408,6 +409,32 @@ hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, i
 hipError_t qs_launch_ft_assign(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep,
                                int start_bot, int start_m, int fb_pending);
 hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep, int bot, int m);
+// plan.hip: the planner's workspace, carved from ws (nullptr: only the bytes the block needs) for n requests
+#define QS_PLAN_ROUND_BLOCKS 1024   // workgroups of a relaxation round (they stride over its list)
+struct QsPlanLayout {
+    unsigned int *mask;             // [tiles down * 64][mp] traversable bits, rows padded to whole tiles
+    unsigned int *tile_any;         // [tiles down][tiles across] the tile holds a traversable cell
+    unsigned int *bbox;             // [4] first / last tile across and down of those (the census)
+    unsigned int *cnt;              // [3] list counts of a ring of rounds
+    unsigned long long *stats;      // [4] rounds, tile visits, (unused), snapped endpoints
+    double2 *xy;                    // [2n] starts, then goals
+    long long *cell;                // [2n] their cells (gy * size + gx), -1 = none
+    int4 *out4;                     // [n] status, waypoint gx, gy, cost
+    long long *plen;                // [n] path cells
+    int2 *path;                     // [n][path_cap]
+    unsigned int *list0, *list1, *marks;   // [item_cap] worklists of (field, tile) items and their round marks
+    unsigned int *fields;           // [field_words] one group's fields
+    int mp, gtx;                    // mask words per row, tiles across the grid
+    size_t gmax, field_words, item_cap, bytes;
+};
+QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap);
+hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clearance);
+hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, size_t n_end, int radius);
+size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n);    // requests per group
+hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn);
+hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t gn, unsigned int r);
+hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
+                               int lookahead, size_t path_cap);
 // icp.hip
 hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
                             double max_d2, int *corr, double *d2);

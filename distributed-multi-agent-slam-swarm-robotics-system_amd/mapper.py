@@ -682,6 +682,61 @@ class QuasarMapper:
         idx, xy = self.frontier_targets([bot_states[b] for b in bots], separation, min_cluster)
         return {b: (float(xy[i, 0]), float(xy[i, 1])) for i, b in enumerate(bots) if idx[i] >= 0}
 
+    # -- path planning (include/quasar_slam.h, "path planning"; no reference counterpart) ----------------------
+    def traversable(self, clearance=P.PLAN_CLEARANCE):
+        """Rule 1 over the whole grid: uint8 [size, size] indexed [gy, gx], 1 = traversable."""
+        out = np.zeros((self.size, self.size), dtype=np.uint8)
+        self._chk(self._L.qs_traversable(self._h, int(clearance), _ptr(out)), "qs_traversable")
+        return out
+
+    @staticmethod
+    def _plan_params(clearance, snap_radius, lookahead):
+        return _lib.QsPlanParams(int(clearance), int(snap_radius), int(lookahead), 0)
+
+    def distance_field(self, goal_xy, clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS,
+                       lookahead=P.PLAN_LOOKAHEAD):
+        """Rule 3 for one goal (world x, y): uint32 [size, size] indexed [gy, gx], 0xFFFFFFFF = unreached."""
+        g = np.ascontiguousarray(goal_xy, dtype=np.float64).reshape(2)
+        out = np.empty((self.size, self.size), dtype=np.uint32)
+        prm = self._plan_params(clearance, snap_radius, lookahead)
+        self._chk(self._L.qs_plan_field(self._h, C.byref(prm), _ptr(g), _ptr(out)), "qs_plan_field")
+        return out
+
+    def plan_paths(self, starts, goals, clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS,
+                   lookahead=P.PLAN_LOOKAHEAD, return_paths=False, path_cap=None):
+        """Paths from starts[i] to goals[i] (world [n, 2] each) and the waypoint a bot can drive to straight.  Returns a
+        dict of numpy arrays: status int32 [n] (QS_PLAN_*), waypoint_cell int32 [n, 2], waypoint float64 [n, 2], cost
+        uint32 [n], path_len int64 [n]; with return_paths also paths: a list of int32 [k, 2] cell arrays (the first
+        path_cap cells; None = every cell), and stats: rounds, tile_visits, groups, snapped."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
+        if len(s) != len(g):
+            raise ValueError("plan_paths: starts and goals differ in length")
+        n = len(s)
+        prm = self._plan_params(clearance, snap_radius, lookahead)
+        st = np.zeros(n, dtype=np.int32)
+        wc = np.zeros((n, 2), dtype=np.int32)
+        wxy = np.zeros((n, 2), dtype=np.float64)
+        cost = np.zeros(n, dtype=np.uint32)
+        plen = np.zeros(n, dtype=np.int64)
+        stats = np.zeros(4, dtype=np.uint64)
+        cap, path = 0, None
+        if return_paths:
+            if path_cap is None:       # every cell: the lengths first (a second call observes the same map)
+                self._chk(self._L.qs_plan_paths(self._h, C.byref(prm), _ptr(s), _ptr(g), n, _ptr(st), _ptr(wc), _ptr(wxy),
+                                                _ptr(cost), None, 0, _ptr(plen), None), "qs_plan_paths")
+                path_cap = int(plen.max()) if n else 0
+            cap = int(path_cap)
+            path = np.zeros((n, max(cap, 1), 2), dtype=np.int32)
+        self._chk(self._L.qs_plan_paths(self._h, C.byref(prm), _ptr(s), _ptr(g), n, _ptr(st), _ptr(wc), _ptr(wxy),
+                                        _ptr(cost), _ptr(path) if cap else None, cap, _ptr(plen), _ptr(stats)),
+                  "qs_plan_paths")
+        out = dict(status=st, waypoint_cell=wc, waypoint=wxy, cost=cost, path_len=plen,
+                   stats=dict(zip(("rounds", "tile_visits", "groups", "snapped"), (int(v) for v in stats))))
+        if return_paths:
+            out["paths"] = [path[i, :min(int(plen[i]), cap)].copy() for i in range(n)]
+        return out
+
     # -- EKF --------------------------------------------------------------------------------------
     def ekf_init(self, bot, t, x0):
         x0 = np.ascontiguousarray(x0, dtype=np.float64)

@@ -42,6 +42,10 @@ CLOSURE_CORRECTION = 0.5
 FRONTIER_MIN_CLUSTER = 3
 FRONTIER_SEPARATION = 1.0
 TARGET_INTERVAL = 3.0
+# path planning defaults (include/quasar_slam.h): build choices, the reference has no planner
+PLAN_CLEARANCE = 2          # cells: 0.10 m at 0.05 m per cell (the bots follow walls at 0.25 m)
+PLAN_SNAP_RADIUS = 10       # cells
+PLAN_LOOKAHEAD = 200        # path cells tested for a straight drive
 
 # numpy view of the packed 42-byte record (same field order as PACKET_FMT)
 PACKET_DTYPE = np.dtype([("magic", "S4"), ("agent", "u1"), ("x", "<f4"), ("y", "<f4"), ("yaw", "<f4"),

@@ -12,6 +12,9 @@ Mirrors server_nodes/dual_bot_mapper.py:
                                centroid not taken and not within FRONTIER_SEPARATION of an earlier target, sent
                                as TARG (:691-699).  Commented out in the reference as shipped, so opt-in here
                                (frontier_targets=True); the mapper then also needs assign_frontier_targets.
+                               With plan_paths=True (also opt-in) a TARG carries instead the waypoint of a path over
+                               the mapped free space to that centroid (QuasarMapper.plan_paths), or the centroid itself
+                               when there is no path; plan_params go to plan_paths.
 Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry packets of the ESP32 firmware
 (esp32_firmware/src/main.cpp:190-215) are mapped too.  Datagrams then get slots of SWEEP_SLOT bytes; the datagrams of a
 poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
@@ -34,8 +37,13 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
-                 frontier_targets=False, sweeps=False):
+                 frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None):
+        if plan_paths and not frontier_targets:
+            raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
         self.mapper = mapper
+        self.plan_paths = plan_paths
+        self.plan_params = dict(plan_params or {})
+        self.plan_stats = {"waypoint": 0, "centroid": 0}
         self.sweeps = sweeps
         self.slot = SWEEP_SLOT if sweeps else SLOT
         self.frontier_targets = frontier_targets
@@ -174,7 +182,10 @@ class MissionControl:
         if not states:
             return {}
         sent = {}
-        for bot_id, (tx, ty) in sorted(self.mapper.assign_frontier_targets(states).items()):
+        targets = sorted(self.mapper.assign_frontier_targets(states).items())
+        if self.plan_paths and targets:
+            targets = self._waypoints(states, targets)
+        for bot_id, (tx, ty) in targets:
             pkt = P.pack_target(tx, ty)
             if self.bot_addrs[bot_id] is not None:                                    # send_target_to_bot :693-694
                 try:
@@ -183,6 +194,20 @@ class MissionControl:
                     pass
             sent[bot_id] = pkt
         return sent
+
+    def _waypoints(self, states, targets):
+        """One plan_paths call from the bots' poses to their centroids: the waypoint where the status is OK, else the
+        centroid (what the reference would send); both counted in plan_stats."""
+        res = self.mapper.plan_paths([states[b] for b, _ in targets], [xy for _, xy in targets], **self.plan_params)
+        out = []
+        for i, (b, xy) in enumerate(targets):
+            if int(res["status"][i]) == 0:
+                out.append((b, (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1]))))
+                self.plan_stats["waypoint"] += 1
+            else:
+                out.append((b, xy))
+                self.plan_stats["centroid"] += 1
+        return out
 
     def step(self, now=None):
         """One iteration of the reference's while-loop body (without events and rendering)."""

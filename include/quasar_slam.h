@@ -343,6 +343,56 @@ int qs_frontier_targets(qs_ctx *ctx, int32_t min_cluster, double separation,
                         const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
                         double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[4]);
 
+/* ---- path planning over the mapped free space (no reference counterpart: this build's own rules) ----------------------
+ * A path from a bot to its frontier target over the cells the map knows to be free, and the waypoint a bot can drive to
+ * in a straight line (what a TARG packet carries when MissionControl plans).  All rules are integer, so the device and a
+ * CPU restatement agree bit for bit.
+ *  1. Traversable: a FREE cell (stamp nonzero and even; OCCUPIED = odd, UNKNOWN = 0, frontier.hip's reading) with no
+ *     OCCUPIED cell within `clearance` cells: dx*dx + dy*dy <= clearance*clearance.  UNKNOWN is never traversable;
+ *     clearance 0 = FREE cells only.  clearance <= QS_PLAN_MAX_CLEARANCE.
+ *  2. Snapping: a position maps to a cell by world_to_grid (int((w - o) / res), :121-125).  If that cell is not
+ *     traversable, it snaps to the traversable cell minimising (dx*dx + dy*dy, gy*size + gx) within snap_radius cells
+ *     (dx*dx + dy*dy <= snap_radius^2).  None, or a NaN / infinite / off-grid position: QS_PLAN_NO_START / _NO_GOAL.
+ *  3. Field: exact shortest-path cost to the goal cell over traversable cells; 8-connected moves, an orthogonal step
+ *     costs QS_PLAN_ORTHO and a diagonal QS_PLAN_DIAG, a diagonal move needs both orthogonal neighbours traversable
+ *     (no corner cutting).  uint32 costs, 0xFFFFFFFF = unreached.  The fixpoint is unique: any relaxation order gives it.
+ *  4. Path: from the start cell, at each cell c the first legal move (rule 3) to a neighbour n with
+ *     field[n] + step(c, n) == field[c], moves tried in the order E (+x), N (+y), W, S, NE, NW, SW, SE; it ends at the
+ *     goal.  Path cells are numbered from 0 (the start); path_len counts them all, both ends included.  An infinite
+ *     field[start]: QS_PLAN_UNREACHABLE.
+ *  5. Waypoint: among path cells 1 .. min(lookahead, path_len - 1), a cell is visible when every cell of the reference's
+ *     _bresenham(start, cell) (:158-179) is traversable; the waypoint is the cell just before the first that is not,
+ *     else the last of them.  Start == goal: the waypoint is the start and the cost 0.  Its world position is
+ *     grid_to_world (:127-131, the cell centre).
+ * Defaults (build choices, not the reference's): clearance 2 cells (0.10 m at 0.05 m per cell; the bots follow walls at
+ * 0.25 m), snap_radius 10, lookahead 200.  Every call observes the map (flushes waiting exact-trig rays first) and writes
+ * no session state: a checkpoint before equals one after.  Bad arguments: QS_E_INVAL. */
+#define QS_PLAN_OK 0
+#define QS_PLAN_NO_START 1
+#define QS_PLAN_NO_GOAL 2
+#define QS_PLAN_UNREACHABLE 3
+#define QS_PLAN_ORTHO 5
+#define QS_PLAN_DIAG 7
+#define QS_PLAN_MAX_CLEARANCE 16
+#define QS_PLAN_MAX_SNAP 64
+#define QS_PLAN_MAX_LOOKAHEAD 65536
+/* Fields are computed a group of requests at a time; a group's fields (each the tile-aligned bounding box of the
+ * traversable cells, 4 bytes a cell) fit this many bytes (one field over the whole grid when even that is larger). */
+#define QS_PLAN_WS_CAP ((size_t)2 << 30)
+typedef struct qs_plan_params { int32_t clearance, snap_radius, lookahead, reserved; } qs_plan_params;
+/* rule 1 for the whole grid: mask_host[gy*size + gx] = 1 when traversable (tests and tools) */
+int qs_traversable(qs_ctx *ctx, int32_t clearance, uint8_t *mask_host);
+/* rule 3 for one goal (params NULL = defaults): field_host [size][size]; all 0xFFFFFFFF when the goal does not snap */
+int qs_plan_field(qs_ctx *ctx, const qs_plan_params *params, const double goal_xy[2], uint32_t *field_host);
+/* n requests (start_xy, goal_xy: n x 2).  Per request: status (QS_PLAN_*), the waypoint cell (gx, gy) and its world
+ * position, the cost field[start]; path_xy (optional, path_cap cells of (gx, gy) per request) gets the first path_cap
+ * cells and path_len (optional) the full length.  Requests that are not QS_PLAN_OK get (-1, -1), NaN, 0xFFFFFFFF, 0.
+ * stats (optional): relaxation rounds, tile visits, request groups, snapped endpoints.  n == 0 and a map without FREE
+ * cells are valid. */
+int qs_plan_paths(qs_ctx *ctx, const qs_plan_params *params, const double *start_xy, const double *goal_xy, size_t n,
+                  int32_t *status, int32_t *wp_cell_xy, double *wp_xy, uint32_t *cost, int32_t *path_xy, size_t path_cap,
+                  int64_t *path_len, uint64_t stats[4]);
+
 /* ---- EKF  AgentFirmware_Bot1/ekf.cpp:5-92 ---------------------------------------------- */
 /* On ingest (qs_config.enable_ekf) the filter of every bot runs over the batch: batches of >= 4096
  * packets in a parallel-in-time form that agrees with the step-by-step filter to rounding (~1e-12

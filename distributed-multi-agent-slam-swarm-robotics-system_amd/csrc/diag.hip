@@ -98,8 +98,33 @@ qs_diag_lat_kernel(const unsigned int *__restrict__ chase_l2, const unsigned int
     }
 }
 
-hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out)
+static hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out)
 {
     hipLaunchKernelGGL(qs_diag_lat_kernel, dim3(1), dim3(1024), 0, c->stream, d_chase_l2, d_chase_l1, d_out);
     return hipGetLastError();
+}
+
+// ---- C ABI: measured latencies of the primitives of one loop-closure decision, shader-clock cycles
+extern "C" int qs_diag_latencies(qs_ctx *c, double out[QS_DIAG_LAT_N])
+{
+    ARGCHK(c, c != nullptr && out != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    const unsigned int n2 = 1u << 18, n1 = 1u << 11;            // 1 MiB: past the 32 KiB L1, inside the 4 MiB L2; 8 KiB: inside L1
+    std::vector<unsigned int> h2(n2), h1(n1);
+    for (unsigned int k = 0; k < n2; k++) h2[k] = (k * 1664525u + 1013904223u) & (n2 - 1);     // full-period LCG: one cycle through all entries
+    for (unsigned int k = 0; k < n1; k++) h1[k] = (k * 1664525u + 1013904223u) & (n1 - 1);
+    DevBuf<unsigned int> d2, d1; DevBuf<double> d_out;
+    double h_out[16] = {0};
+    HIPCHK(c, d2.alloc(n2));
+    HIPCHK(c, d1.alloc(n1));
+    HIPCHK(c, d_out.alloc(16));
+    HIPCHK(c, hipMemcpyAsync(d2.p, h2.data(), n2 * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d1.p, h1.data(), n1 * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_out.p, 0, sizeof h_out, c->stream));
+    HIPCHK(c, qs_launch_diag_latencies(c, d2.p, d1.p, d_out.p));          // (warm: code load)
+    HIPCHK(c, qs_launch_diag_latencies(c, d2.p, d1.p, d_out.p));
+    HIPCHK(c, hipMemcpyAsync(h_out, d_out.p, sizeof h_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < QS_DIAG_LAT_N; i++) out[i] = h_out[i];
+    return QS_OK;
 }

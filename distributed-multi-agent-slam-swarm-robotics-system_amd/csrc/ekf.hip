@@ -9,6 +9,8 @@
 // The mapper never uses the EKF pose (dual_bot_mapper.py:829-831 takes the packet pose; the
 // firmware itself runs the filter "for internal state estimation", AgentFirmware_Bot1.ino:
 // 697-707), so this stage is telemetry: it must not feed the raycast.
+#include <string.h>
+
 #include "qs_internal.h"
 
 #define EKF_STRIDE 44   // x[6], P[36], last_time, initialized
@@ -355,11 +357,60 @@ __global__ void qs_ekf_step_kernel(const int *__restrict__ bots, const double *_
     ekf_store(ekf + (size_t)bot * EKF_STRIDE, s);
 }
 
-hipError_t qs_launch_ekf_step(qs_ctx *c, const int *d_bots, const double *d_omega, const double *d_t,
-                              const double *d_zv, const double *d_zo, size_t n, int do_update)
+static hipError_t qs_launch_ekf_step(qs_ctx *c, const int *d_bots, const double *d_omega, const double *d_t,
+                                     const double *d_zv, const double *d_zo, size_t n, int do_update)
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(qs_ekf_step_kernel, dim3((unsigned int)((n + 63) / 64)), dim3(64), 0, c->stream, d_bots,
                        d_omega, d_t, d_zv, d_zo, n, do_update, c->cfg.max_agent, c->d_ekf.p);
     return hipGetLastError();
+}
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------
+extern "C" int qs_ekf_init(qs_ctx *c, int32_t bot, double t, const double x0[6])
+{
+    ARGCHK(c, c != nullptr);
+    if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_ekf_init: bot out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    double f[44] = {0};
+    for (int i = 0; i < 6; i++) { f[i] = x0 ? x0[i] : 0.0; f[6 + 7 * i] = 1.0; }     // x0, P = I  ekf.cpp:5-19
+    f[42] = t; f[43] = 1.0;
+    HIPCHK(c, hipMemcpyAsync(c->d_ekf.p + (size_t)bot * 44, f, sizeof f, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_ekf_step(qs_ctx *c, const int32_t *bot_ids, const double *omega_m, const double *t, const double *z_v,
+                           const double *z_omega, size_t n, int32_t do_update)
+{
+    ARGCHK(c, c != nullptr);
+    if (n == 0) return QS_OK;
+    ARGCHK(c, bot_ids && omega_m && t && (!do_update || (z_v && z_omega)));
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<int> db; DevBuf<double> dd;
+    HIPCHK(c, db.alloc(n));
+    HIPCHK(c, dd.alloc(4 * n));
+    HIPCHK(c, hipMemcpyAsync(db.p, bot_ids, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd.p, omega_m, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd.p + n, t, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (do_update) {
+        HIPCHK(c, hipMemcpyAsync(dd.p + 2 * n, z_v, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dd.p + 3 * n, z_omega, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, qs_launch_ekf_step(c, db.p, dd.p, dd.p + n, dd.p + 2 * n, dd.p + 3 * n, n, do_update));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_ekf_state(qs_ctx *c, int32_t bot, double x[6], double P[36])
+{
+    ARGCHK(c, c != nullptr);
+    if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_ekf_state: bot out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    double f[44];
+    HIPCHK(c, hipMemcpyAsync(f, c->d_ekf.p + (size_t)bot * 44, sizeof f, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (x) memcpy(x, f, 6 * sizeof(double));
+    if (P) memcpy(P, f + 6, 36 * sizeof(double));
+    return QS_OK;
 }

@@ -14,6 +14,8 @@
 // The centroid itself (two divisions per cluster) is left to the host: it is exact integer/fp64
 // arithmetic on these sums.  BFS visiting order inside a cluster is not reproduced (it only orders
 // the membership lists, which nothing downstream reads).
+#include <string.h>
+
 #include "qs_internal.h"
 
 #define FR_BLOCK 256
@@ -215,7 +217,7 @@ hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters)
 }
 
 // phase 0: count + scan (total -> *d_total); phase 1: ranked write
-hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap)
+static hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap)
 {
     const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
     const QsFrLayout L = qs_frontier_layout(c, ws);
@@ -240,3 +242,57 @@ hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws)
     hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, L.chunk, (c->cells + FR_CHUNK - 1) / FR_CHUNK, L.total);
     return hipGetLastError();
 }
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------
+static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, int64_t *stats5, size_t cap, size_t *n_out)
+{
+    ARGCHK(c, c != nullptr && n_out != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
+    void *ws = c->frontier_ws.p;
+    HIPCHK(c, qs_launch_frontier_label(c, ws, mode != 0));
+    HIPCHK(c, qs_launch_frontier_compact(c, ws, mode == 2 ? 0 : mode, 0, nullptr, nullptr, 0));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, ws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mode != 1) {
+        // cells (mode 0: gx, gy), or every frontier cell with the first cell (row-major) of its 4-connected cluster (mode 2:
+        // gx, gy, root linear index)
+        *n_out = (size_t)total;
+        if (!xy || total == 0) return QS_OK;
+        const size_t per = mode == 0 ? 2 : 3, m = total < cap ? (size_t)total : cap;
+        DevBuf<int> d;
+        HIPCHK(c, d.alloc(per * (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, mode, 1, d.p, nullptr, (size_t)total));
+        HIPCHK(c, hipMemcpyAsync(xy, d.p, per * m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return QS_OK;
+    }
+    // clusters: all components come back in first-cell order; the size filter keeps that order (:228-229)
+    std::vector<long long> all(5 * (size_t)total);
+    if (total) {
+        DevBuf<long long> d;
+        HIPCHK(c, d.alloc(5 * (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, 1, 1, nullptr, d.p, (size_t)total));
+        HIPCHK(c, hipMemcpyAsync(all.data(), d.p, all.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    size_t k = 0;
+    for (size_t i = 0; i < (size_t)total; i++) {
+        if (all[5 * i] < min_cluster) continue;
+        if (stats5 && k < cap) memcpy(stats5 + 5 * k, &all[5 * i], 5 * sizeof(long long));
+        k++;
+    }
+    *n_out = k;
+    return QS_OK;
+}
+
+extern "C" int qs_frontier_cells(qs_ctx *c, int32_t *xy, size_t cap, size_t *n_out)
+{ return frontier_run(c, 0, 0, xy, nullptr, cap, n_out); }
+
+extern "C" int qs_frontier_members(qs_ctx *c, int32_t *xy_root, size_t cap, size_t *n_out)
+{ return frontier_run(c, 2, 0, xy_root, nullptr, cap, n_out); }
+
+extern "C" int qs_frontier_clusters(qs_ctx *c, int32_t min_cluster, int64_t *stats5, size_t cap, size_t *n_out)
+{ return frontier_run(c, 1, min_cluster, nullptr, stats5, cap, n_out); }

@@ -11,19 +11,32 @@
 //               within `separation` of a target assigned so far.  The list is the true top-K by the same key, so
 //               its first eligible entry is the minimum over every eligible centroid.  When a full list (K entries)
 //               is entirely ineligible the pass stops; a whole-GPU scan over all centroids finds that bot's pick and
-//               the pass resumes (qs_api.hip drives the loop and counts these fallbacks).
+//               the pass resumes (qs_frontier_targets drives the loop and counts these fallbacks).
 // Arithmetic is the reference's: fp64, no contraction (Makefile), d2 = dx*dx + dy*dy, correctly rounded sqrt.  The
 // separation test uses r2_sep = the smallest double with sqrt(r2_sep) >= separation, so s < r2_sep <=> sqrt(s) < sep.
 // A key that is NaN or +inf (a NaN / inf / far-outlier bot) never enters a list: `NaN < inf` and `inf < inf` are false.
 #include "qs_internal.h"
 
-#define FT_K QS_FT_K
+#define FT_K 32                   // candidates per bot (the top-K list of the greedy pass)
 #define FT_CHUNK 1024              // centroids per (bot, chunk) work item of the top-K pass
 #define FT_BOTS_PER_BLOCK 4        // one wave per bot, 4 waves per workgroup (they read the same centroids)
 #define FT_FB_BLOCK 256
 #define FT_NONE 0x7fffffff
 
 static_assert(FT_K <= QS_WAVE, "one list entry per lane");
+
+struct QsFtState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
+// the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
+struct QsFtLayout {
+    QsFtState *st;
+    double2 *cent, *bots, *tgt_xy, *asg_xy;
+    long long *tgt_idx;
+    int *asg_idx;
+    double *part_key; int *part_idx;      // [n_bots][n_chunks][K]
+    int *list_idx, *list_len;             // [n_bots][K], [n_bots]
+    double *fb_key; int *fb_idx;          // [n_fb]: per-block minima of a fallback scan
+    size_t bytes;
+};
 
 // ---- centroids ------------------------------------------------------------------------------------------------
 __device__ inline bool ft_keep(const unsigned int *cnt, size_t i, int min_cluster)
@@ -81,7 +94,7 @@ qs_ft_centroid_kernel(const unsigned int *__restrict__ cnt, const unsigned long 
     }
 }
 
-hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent)
+static hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent)
 {
     const QsFrLayout F = qs_frontier_layout(c, fr_ws);
     const size_t n_chunks = (c->cells + QS_FR_CHUNK - 1) / QS_FR_CHUNK;
@@ -99,7 +112,7 @@ hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, i
 static inline size_t ft_chunks(size_t n_cent) { return (n_cent + FT_CHUNK - 1) / FT_CHUNK; }
 static inline size_t ft_fb_blocks(size_t n_cent) { return (n_cent + FT_FB_BLOCK - 1) / FT_FB_BLOCK; }
 
-QsFtLayout qs_ft_layout(void *ws, size_t n_cent, size_t n_bots)
+static QsFtLayout qs_ft_layout(void *ws, size_t n_cent, size_t n_bots)
 {
     QsFtLayout L;
     Carve k(ws);
@@ -315,9 +328,10 @@ qs_ft_fallback_kernel(const double2 *__restrict__ cent, int n_cent, const double
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------
+// the lists, then the greedy pass from start_bot (fb_pending: a fallback scan has decided start_bot); it ends in QsFtState.
 // start_bot == 0 && !fb_pending: the first launch of a call, which first builds the lists
-hipError_t qs_launch_ft_assign(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
-                               int start_bot, int start_m, int fb_pending)
+static hipError_t qs_launch_ft_assign(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
+                                      int start_bot, int start_m, int fb_pending)
 {
     const QsFtLayout L = qs_ft_layout(ws, n_cent, n_bots);
     const int nch = (int)ft_chunks(n_cent);
@@ -334,11 +348,69 @@ hipError_t qs_launch_ft_assign(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots
     return hipGetLastError();
 }
 
-hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
-                                 int bot, int m)
+static hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ws, size_t n_cent, size_t n_bots, double r2_sep,
+                                        int bot, int m)
 {
     const QsFtLayout L = qs_ft_layout(ws, n_cent, n_bots);
     hipLaunchKernelGGL(qs_ft_fallback_kernel, dim3((unsigned int)ft_fb_blocks(n_cent)), dim3(FT_FB_BLOCK), 0, c->stream,
                        L.cent, (int)n_cent, L.bots, bot, m, r2_sep, L.asg_xy, L.asg_idx, L.fb_key, L.fb_idx);
     return hipGetLastError();
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+// centroids on the device, top-K lists, the greedy pass; the pass stops at a bot whose full list is ineligible, a whole-GPU
+// scan decides that bot, and the pass resumes from it
+extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separation, const double *bot_xy, size_t n_bots,
+                                   int64_t *target_idx, double *target_xy, double *centroids_xy, size_t cap,
+                                   size_t *n_centroids, uint64_t stats[4])
+{
+    ARGCHK(c, c != nullptr);
+    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets: n_bots above QS_FT_MAX_BOTS");
+    ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy));
+    ARGCHK(c, cap == 0 || centroids_xy);
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
+    void *fws = c->frontier_ws.p;
+    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n_cent = (size_t)total;
+    HIPCHK(c, c->ft_ws.reserve(qs_ft_layout(nullptr, n_cent, n_bots).bytes, c->stream));
+    const QsFtLayout F = qs_ft_layout(c->ft_ws.p, n_cent, n_bots);
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, F.cent));
+    uint64_t fallbacks = 0;
+    std::vector<long long> tidx(n_bots, -1);
+    std::vector<double> txy(2 * n_bots);
+    if (n_bots && n_cent) {
+        const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation (0: nothing is too close)
+        HIPCHK(c, hipMemcpyAsync(F.bots, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        int start = 0, m = 0, pending = 0;
+        for (;;) {
+            HIPCHK(c, qs_launch_ft_assign(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m, pending));
+            QsFtState st;
+            HIPCHK(c, hipMemcpyAsync(&st, F.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (!st.stop) break;
+            if (st.next_bot < start || st.next_bot >= (int)n_bots || (pending && st.next_bot == start))
+                return qs_fail(c, QS_E_HIP, "qs_frontier_targets: greedy pass made no progress");
+            fallbacks++;
+            start = st.next_bot; m = st.m; pending = 1;
+            HIPCHK(c, qs_launch_ft_fallback(c, c->ft_ws.p, n_cent, n_bots, r2_sep, start, m));
+        }
+        HIPCHK(c, hipMemcpyAsync(tidx.data(), F.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(txy.data(), F.tgt_xy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    }
+    const size_t nc = n_cent < cap ? n_cent : cap;
+    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, F.cent, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < n_bots; b++) {
+        target_idx[b] = tidx[b];
+        if (tidx[b] >= 0) { target_xy[2 * b] = txy[2 * b]; target_xy[2 * b + 1] = txy[2 * b + 1]; }
+    }
+    if (n_centroids) *n_centroids = n_cent;
+    if (stats) { stats[0] = n_cent; stats[1] = FT_K; stats[2] = fallbacks; stats[3] = 0; }
+    return QS_OK;
 }

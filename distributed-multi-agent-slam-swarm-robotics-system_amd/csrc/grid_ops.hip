@@ -40,7 +40,7 @@ qs_view_i8_kernel(const uint4 *__restrict__ stamps4, size_t n16, uint4 *__restri
         out[c] = (signed char)go_tri(stamps[c]);
 }
 
-hipError_t qs_launch_view_i8(qs_ctx *c, signed char *out_dev)
+static hipError_t qs_launch_view_i8(qs_ctx *c, signed char *out_dev)
 {
     const size_t n16 = c->cells / 16;
     hipLaunchKernelGGL(qs_view_i8_kernel, dim3(go_blocks(n16 ? n16 : c->cells)), dim3(GO_BLOCK), 0, c->stream,
@@ -62,7 +62,7 @@ qs_logodds_kernel(const unsigned long long *__restrict__ counts, size_t cells, f
         out[c] = l;
     }
 }
-hipError_t qs_launch_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_dev)
+static hipError_t qs_launch_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_dev)
 {
     hipLaunchKernelGGL(qs_logodds_kernel, dim3(go_blocks(c->cells)), dim3(GO_BLOCK), 0, c->stream,
                        c->counts_view_fused ? c->d_counts_fused.p : c->d_counts.p, c->cells, l_occ, l_free, lmin, lmax, out_dev);
@@ -80,7 +80,7 @@ qs_split_counts_kernel(const unsigned long long *__restrict__ counts, size_t cel
         misses[c] = (int)(unsigned int)(v & 0xffffffffu);
     }
 }
-hipError_t qs_launch_split_counts(qs_ctx *c, int *hits_dev, int *misses_dev)
+static hipError_t qs_launch_split_counts(qs_ctx *c, int *hits_dev, int *misses_dev)
 {
     hipLaunchKernelGGL(qs_split_counts_kernel, dim3(go_blocks(c->cells)), dim3(GO_BLOCK), 0, c->stream,
                        c->counts_view_fused ? c->d_counts_fused.p : c->d_counts.p, c->cells, hits_dev, misses_dev);
@@ -229,13 +229,6 @@ hipError_t qs_launch_reset_small(qs_ctx *c)
     return hipGetLastError();
 }
 
-hipError_t qs_launch_fill_zone_identity(qs_ctx *c)
-{
-    const int nb = c->cfg.max_agent + 1;
-    hipLaunchKernelGGL(qs_zone_identity_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, c->d_zone.p, nb);
-    return hipGetLastError();
-}
-
 // ---- MapMerger.grid_to_pcd  server_nodes/map_merger.py:64-85 -----------------------------
 // np.argwhere(data > 50) is row-major, so the points are an order-preserving compaction:
 // per-chunk counts, one scan, ranked writes.  Chunk = 1024 cells.
@@ -308,9 +301,9 @@ qs_pcd_write_kernel(const signed char *__restrict__ grid, size_t cells, int w, d
         __syncthreads();
     }
 }
-hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox,
-                                 double oy, double *d_xy, size_t cap, unsigned long long *d_count,
-                                 unsigned int *d_chunk)
+static hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox,
+                                        double oy, double *d_xy, size_t cap, unsigned long long *d_count,
+                                        unsigned int *d_chunk)
 {
     const size_t cells = (size_t)h * w;
     const size_t n_chunks = (cells + PCD_CHUNK - 1) / PCD_CHUNK;
@@ -345,7 +338,7 @@ qs_bbox_kernel(const double *__restrict__ xy, size_t n, unsigned long long *__re
         atomicMin(&box4[0], s[0]); atomicMin(&box4[1], s[1]); atomicMax(&box4[2], s[2]); atomicMax(&box4[3], s[3]);
     }
 }
-hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4)
+static hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4)
 {
     hipLaunchKernelGGL(qs_bbox_kernel, dim3(go_blocks(n)), dim3(GO_BLOCK), 0, c->stream, d_xy, n, d_box4);
     return hipGetLastError();
@@ -363,12 +356,118 @@ qs_rasterise_kernel(const double *__restrict__ xy, size_t n, double res, double 
         grid[(size_t)yi * w + xi] = 100;                               // :115 (idempotent store)
     }
 }
-hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx, double miny,
-                               int h, int w, signed char *d_grid)
+static hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx, double miny,
+                                      int h, int w, signed char *d_grid)
 {
     hipError_t e = hipMemsetAsync(d_grid, 0xff, (size_t)h * w, c->stream);   // np.full(-1)  :107
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(qs_rasterise_kernel, dim3(go_blocks(n)), dim3(GO_BLOCK), 0, c->stream, d_xy, n, res, minx,
                        miny, h, w, d_grid);
     return hipGetLastError();
+}
+
+// ---- C ABI: grid views, grid_to_pcd, rasterise -----------------------------------------------------------------------
+extern "C" int qs_grid_i8_device(qs_ctx *c, int8_t *out_dev)
+{
+    ARGCHK(c, c != nullptr && out_dev != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, qs_launch_view_i8(c, (signed char *)out_dev));
+    return QS_OK;
+}
+
+extern "C" int qs_grid_i8(qs_ctx *c, int8_t *out_host)
+{
+    ARGCHK(c, c != nullptr && out_host != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    DevBuf<signed char> d;
+    HIPCHK(c, d.alloc(c->cells));
+    HIPCHK(c, qs_launch_view_i8(c, d.p));
+    HIPCHK(c, hipMemcpyAsync(out_host, d.p, c->cells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_grid_counts(qs_ctx *c, int32_t *hits_host, int32_t *misses_host)
+{
+    ARGCHK(c, c != nullptr && hits_host && misses_host);
+    if (!c->d_counts.p) return qs_fail(c, QS_E_INVAL, "qs_grid_counts: context created with enable_counts = 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    DevBuf<int> d;
+    HIPCHK(c, d.alloc(2 * c->cells));
+    HIPCHK(c, qs_launch_split_counts(c, d.p, d.p + c->cells));
+    HIPCHK(c, hipMemcpyAsync(hits_host, d.p, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(misses_host, d.p + c->cells, c->cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_grid_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_host)
+{
+    ARGCHK(c, c != nullptr && out_host);
+    if (!c->d_counts.p) return qs_fail(c, QS_E_INVAL, "qs_grid_logodds: context created with enable_counts = 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    DevBuf<float> d;
+    HIPCHK(c, d.alloc(c->cells));
+    HIPCHK(c, qs_launch_logodds(c, l_occ, l_free, lmin, lmax, d.p));
+    HIPCHK(c, hipMemcpyAsync(out_host, d.p, c->cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_grid_to_pcd(qs_ctx *c, const int8_t *grid, int32_t h, int32_t w, double res, double ox, double oy,
+                              double *xy, size_t cap, size_t *n_out)
+{
+    ARGCHK(c, c != nullptr && grid != nullptr && n_out != nullptr && h > 0 && w > 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)h * w, n_chunks = (cells + 1023) / 1024;
+    DevBuf<signed char> dg; DevBuf<unsigned int> dchunk; DevBuf<unsigned long long> dcount; DevBuf<double> dxy;
+    HIPCHK(c, dg.alloc(cells));
+    HIPCHK(c, dchunk.alloc(n_chunks));
+    HIPCHK(c, dcount.alloc(1));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(dg.p, grid, cells, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_grid_to_pcd(c, dg.p, h, w, res, ox, oy, nullptr, 0, dcount.p, dchunk.p));
+    HIPCHK(c, hipMemcpyAsync(&total, dcount.p, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_out = (size_t)total;
+    if (!xy || total == 0) return QS_OK;
+    const size_t m = total < cap ? (size_t)total : cap;
+    HIPCHK(c, dxy.alloc(2 * (size_t)total));
+    HIPCHK(c, qs_launch_grid_to_pcd(c, dg.p, h, w, res, ox, oy, dxy.p, (size_t)total, dcount.p, dchunk.p));
+    HIPCHK(c, hipMemcpyAsync(xy, dxy.p, 2 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_rasterise(qs_ctx *c, const double *xy, size_t n, double res, int32_t dims[2], double origin[2], int8_t *grid)
+{
+    ARGCHK(c, c != nullptr && dims && origin && res > 0);
+    if (n == 0) { dims[0] = dims[1] = 0; return QS_OK; }      // publish_global_map returns early  :88-93
+    ARGCHK(c, xy != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> dxy; DevBuf<unsigned long long> dbox; DevBuf<signed char> dg;
+    unsigned long long box[4] = {QS_ORD_MIN_IDENT, QS_ORD_MIN_IDENT, QS_ORD_MAX_IDENT, QS_ORD_MAX_IDENT};
+    HIPCHK(c, dxy.alloc(2 * n));
+    HIPCHK(c, dbox.alloc(4));
+    HIPCHK(c, hipMemcpyAsync(dxy.p, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dbox.p, box, sizeof box, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_bbox(c, dxy.p, n, dbox.p));
+    HIPCHK(c, hipMemcpyAsync(box, dbox.p, sizeof box, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double mnx = qs_double_from_ord(box[0]), mny = qs_double_from_ord(box[1]);
+    const double mxx = qs_double_from_ord(box[2]), mxy = qs_double_from_ord(box[3]);
+    const double wd = ceil((mxx - mnx) / res), hd = ceil((mxy - mny) / res);     // :103-104
+    if (!(wd >= 0 && wd < 65536 && hd >= 0 && hd < 65536)) return qs_fail(c, QS_E_RANGE, "qs_rasterise: canvas too large");
+    const int w = (int)wd + 1, h = (int)hd + 1;
+    dims[0] = h; dims[1] = w; origin[0] = mnx; origin[1] = mny;
+    if (!grid) return QS_OK;
+    HIPCHK(c, dg.alloc((size_t)h * w));
+    HIPCHK(c, qs_launch_rasterise(c, dxy.p, n, res, mnx, mny, h, w, dg.p));
+    HIPCHK(c, hipMemcpyAsync(grid, dg.p, (size_t)h * w, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
 }

@@ -14,6 +14,9 @@
 //   loop             : at most max_iteration updates; stop when |d fitness| < 1e-6 and |d rmse| < 1e-6.
 // Nearest neighbours are exact brute force in fp64 (targets staged through LDS tiles; ties -> lowest
 // target index); sums are two-level and fixed-order, so results are reproducible run to run.
+#include <math.h>
+#include <algorithm>
+
 #include "qs_internal.h"
 
 #define ICP_BLOCK 256
@@ -337,8 +340,8 @@ qs_voxel_key_kernel(const double2 *__restrict__ pts, size_t n, double minx, doub
     }
 }
 
-hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
-                            double max_d2, int *corr, double *d2)
+static hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
+                                   double max_d2, int *corr, double *d2)
 {
     hipLaunchKernelGGL(qs_icp_nn_kernel, dim3((unsigned int)((n_src + ICP_BLOCK - 1) / ICP_BLOCK)), dim3(ICP_BLOCK), 0,
                        c->stream, src, n_src, dst, n_dst, max_d2, corr, d2);
@@ -363,13 +366,13 @@ qs_mfma_f64_rate_kernel(int iters, double *__restrict__ sink)
     for (int q = 0; q < 4; q++) v += acc[q][0] + acc[q][1] + acc[q][2] + acc[q][3];
     if (v == 123.456) sink[0] = v;          // keeps the chain alive
 }
-hipError_t qs_launch_mfma_f64_rate(qs_ctx *c, int blocks, int iters, double *sink)
+static hipError_t qs_launch_mfma_f64_rate(qs_ctx *c, int blocks, int iters, double *sink)
 {
     hipLaunchKernelGGL(qs_mfma_f64_rate_kernel, dim3(blocks), dim3(256), 0, c->stream, iters, sink);
     return hipGetLastError();
 }
 
-hipError_t qs_launch_icp_prep(qs_ctx *c, const double2 *dst, size_t n_dst, size_t n_pad, double cx, double cy, double *planes)
+static hipError_t qs_launch_icp_prep(qs_ctx *c, const double2 *dst, size_t n_dst, size_t n_pad, double cx, double cy, double *planes)
 {
     hipLaunchKernelGGL(qs_icp_prep_kernel, dim3((unsigned int)((n_pad + ICP_BLOCK - 1) / ICP_BLOCK)), dim3(ICP_BLOCK), 0, c->stream,
                        dst, n_dst, n_pad, cx, cy, planes);
@@ -378,7 +381,7 @@ hipError_t qs_launch_icp_prep(qs_ctx *c, const double2 *dst, size_t n_dst, size_
 
 // How the targets are cut into parts: enough workgroups to keep every slot busy through the tail (>= 6 per slot of the 1 024 a
 // launch holds: 4 workgroups per CU), no part shorter than 8 chunks.
-void qs_icp_nn_plan(size_t n_src, size_t n_pad, unsigned int *n_groups, unsigned int *n_parts, unsigned int *chunks_per_part)
+static void qs_icp_nn_plan(size_t n_src, size_t n_pad, unsigned int *n_groups, unsigned int *n_parts, unsigned int *chunks_per_part)
 {
     const size_t rows_per_wg = (size_t)NNM_WAVES * 16 * NNM_ROWT;
     const unsigned int groups = (unsigned int)((n_src + rows_per_wg - 1) / rows_per_wg);
@@ -391,9 +394,9 @@ void qs_icp_nn_plan(size_t n_src, size_t n_pad, unsigned int *n_groups, unsigned
     *n_groups = groups; *chunks_per_part = cpp; *n_parts = (n_chunks + cpp - 1) / cpp;
 }
 
-hipError_t qs_launch_icp_nn_mfma(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
-                                 const double *planes, size_t n_pad, double cx, double cy, double t2max, double max_d2,
-                                 int *corr, double *d2, int *part_j, double *part_d2, double *thr_seed)
+static hipError_t qs_launch_icp_nn_mfma(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
+                                        const double *planes, size_t n_pad, double cx, double cy, double t2max, double max_d2,
+                                        int *corr, double *d2, int *part_j, double *part_d2, double *thr_seed)
 {
     unsigned int groups, parts, cpp;
     qs_icp_nn_plan(n_src, n_pad, &groups, &parts, &cpp);
@@ -405,8 +408,8 @@ hipError_t qs_launch_icp_nn_mfma(qs_ctx *c, const double2 *src, size_t n_src, co
     return hipGetLastError();
 }
 
-hipError_t qs_launch_icp_sums(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, const int *corr,
-                              const double *d2, int pass, const double means[4], double *partial, double *out6)
+static hipError_t qs_launch_icp_sums(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, const int *corr,
+                                     const double *d2, int pass, const double means[4], double *partial, double *out6)
 {
     const size_t nb = (n_src + ICP_BLOCK - 1) / ICP_BLOCK;
     hipLaunchKernelGGL(qs_icp_sums_kernel, dim3((unsigned int)nb), dim3(ICP_BLOCK), 0, c->stream, src, n_src, dst, corr, d2,
@@ -415,7 +418,7 @@ hipError_t qs_launch_icp_sums(qs_ctx *c, const double2 *src, size_t n_src, const
     return hipGetLastError();
 }
 
-hipError_t qs_launch_icp_transform(qs_ctx *c, double2 *pts, size_t n, double cs, double sn, double tx, double ty)
+static hipError_t qs_launch_icp_transform(qs_ctx *c, double2 *pts, size_t n, double cs, double sn, double tx, double ty)
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(qs_icp_transform_kernel, dim3((unsigned int)((n + ICP_BLOCK - 1) / ICP_BLOCK)), dim3(ICP_BLOCK), 0,
@@ -423,11 +426,203 @@ hipError_t qs_launch_icp_transform(qs_ctx *c, double2 *pts, size_t n, double cs,
     return hipGetLastError();
 }
 
-hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel,
-                                unsigned long long *keys)
+static hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel,
+                                       unsigned long long *keys)
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(qs_voxel_key_kernel, dim3((unsigned int)((n + ICP_BLOCK - 1) / ICP_BLOCK)), dim3(ICP_BLOCK), 0,
                        c->stream, pts, n, minx, miny, voxel, keys);
     return hipGetLastError();
+}
+
+// ---- C ABI: ICP / voxel down-sample (map_merger.py:45-60; Open3D semantics, parity unpinned) -------------------------
+// The correspondence search (nearest target of every source point) has two implementations with identical results:
+// the scalar fp64 brute force and the MFMA-screened one (above).  mode 0 = auto (MFMA from 64 targets up).
+struct NnPlan { double cx = 0, cy = 0, t2max = 0; size_t n_pad = 0; bool mfma = false; DevBuf<double> planes, part_d2, thr_seed; DevBuf<int> part_j; };
+
+static hipError_t nn_prepare(qs_ctx *c, const double *dst_xy, size_t n_dst, const double2 *d_dst, int mode, NnPlan &pl, size_t n_src)
+{
+    pl.mfma = mode == 2 || (mode == 0 && n_dst >= 64);
+    if (!pl.mfma) return hipSuccess;
+    double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
+    for (size_t j = 0; j < n_dst; j++) {
+        const double x = dst_xy[2 * j], y = dst_xy[2 * j + 1];
+        if (isfinite(x)) { mnx = x < mnx ? x : mnx; mxx = x > mxx ? x : mxx; }
+        if (isfinite(y)) { mny = y < mny ? y : mny; mxy = y > mxy ? y : mxy; }
+    }
+    pl.cx = isfinite(mnx) ? 0.5 * (mnx + mxx) : 0.0; pl.cy = isfinite(mny) ? 0.5 * (mny + mxy) : 0.0;
+    const double hx = isfinite(mnx) ? mxx - pl.cx : 0.0, hy = isfinite(mny) ? mxy - pl.cy : 0.0;
+    pl.t2max = 1.0001 * (hx * hx + hy * hy) + 1e-300;          // >= every finite target's centred squared norm
+    pl.n_pad = (n_dst + 15) / 16 * 16;
+    HIPRET(pl.planes.alloc(3 * pl.n_pad));
+    HIPRET(qs_launch_icp_prep(c, d_dst, n_dst, pl.n_pad, pl.cx, pl.cy, pl.planes.p));
+    // per-part results and the sources' threshold seeds (the targets are cut into parts: qs_icp_nn_plan)
+    unsigned int groups, parts, cpp;
+    qs_icp_nn_plan(n_src, pl.n_pad, &groups, &parts, &cpp);
+    HIPRET(pl.part_j.alloc((size_t)parts * n_src));
+    HIPRET(pl.part_d2.alloc((size_t)parts * n_src));
+    return pl.thr_seed.alloc(n_src);
+}
+
+static hipError_t nn_run(qs_ctx *c, const NnPlan &pl, const double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst,
+                         double max_d2, int *d_corr, double *d_d2)
+{
+    if (pl.mfma) return qs_launch_icp_nn_mfma(c, d_src, n_src, d_dst, n_dst, pl.planes.p, pl.n_pad, pl.cx, pl.cy, pl.t2max, max_d2, d_corr, d_d2,
+                                              pl.part_j.p, pl.part_d2.p, pl.thr_seed.p);
+    return qs_launch_icp_nn(c, d_src, n_src, d_dst, n_dst, max_d2, d_corr, d_d2);
+}
+
+// Build extension (the correspondence step of registration_icp on its own; used by the tests and tools/bench_icp_nn.py):
+// corr[i] = index of the target nearest to source i if closer than max_dist, else -1 (ties: lowest index); d2[i] its squared
+// distance (0 without a correspondence).  ms (may be NULL): HIP-event time of {the search kernel, the operand preparation}.
+extern "C" int qs_nn_search(qs_ctx *c, const double *src_xy, size_t n_src, const double *dst_xy, size_t n_dst, double max_dist,
+                            int32_t mode, int32_t *corr, double *d2, float ms[2])
+{
+    ARGCHK(c, c != nullptr && corr != nullptr && d2 != nullptr);
+    ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && mode >= 0 && mode <= 2);
+    ARGCHK(c, n_dst < (size_t)1 << 31);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double2> d_src, d_dst; DevBuf<int> d_corr; DevBuf<double> d_d2;
+    NnPlan pl;
+    ScopedEvent ev[4];
+    HIPCHK(c, d_src.alloc(n_src));
+    HIPCHK(c, d_dst.alloc(n_dst));
+    HIPCHK(c, d_corr.alloc(n_src));
+    HIPCHK(c, d_d2.alloc(n_src));
+    for (auto &v : ev) HIPCHK(c, hipEventCreate(&v.e));
+    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(ev[0].e, c->stream));
+    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, mode, pl, n_src));
+    HIPCHK(c, hipEventRecord(ev[1].e, c->stream));
+    HIPCHK(c, nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));      // warm (code load, caches)
+    HIPCHK(c, hipEventRecord(ev[2].e, c->stream));
+    HIPCHK(c, nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
+    HIPCHK(c, hipEventRecord(ev[3].e, c->stream));
+    HIPCHK(c, hipMemcpyAsync(corr, d_corr.p, n_src * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d2, d_d2.p, n_src * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ms) { hipEventElapsedTime(&ms[0], ev[2].e, ev[3].e); hipEventElapsedTime(&ms[1], ev[0].e, ev[1].e); }
+    return QS_OK;
+}
+
+extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const double *dst_xy, size_t n_dst, double max_dist,
+                      int32_t max_iter, double rel_fitness, double rel_rmse, double T[9], double *fitness, double *rmse,
+                      int32_t *iters)
+{
+    ARGCHK(c, c != nullptr && T != nullptr && fitness != nullptr && rmse != nullptr);
+    ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && max_iter >= 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nb = (n_src + 255) / 256;
+    DevBuf<double2> d_src, d_dst; DevBuf<int> d_corr; DevBuf<double> d_d2, d_part, d_out;
+    HIPCHK(c, d_src.alloc(n_src));
+    HIPCHK(c, d_dst.alloc(n_dst));
+    HIPCHK(c, d_corr.alloc(n_src));
+    HIPCHK(c, d_d2.alloc(n_src));
+    HIPCHK(c, d_part.alloc(nb * 6));
+    HIPCHK(c, d_out.alloc(6));
+    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    NnPlan pl;
+    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, 0, pl, n_src));     // the targets do not move: operands once per registration
+    double tc = 1.0, ts = 0.0, tx = 0.0, ty = 0.0;          // accumulated transform
+    double out[6] = {0};
+    const double zero4[4] = {0, 0, 0, 0};
+    auto evaluate = [&](double &fit, double &rm) -> hipError_t {
+        HIPRET(nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
+        HIPRET(qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 0, zero4, d_part.p, d_out.p));
+        HIPRET(hipMemcpyAsync(out, d_out.p, sizeof out, hipMemcpyDeviceToHost, c->stream));
+        HIPRET(hipStreamSynchronize(c->stream));
+        fit = out[0] / (double)n_src;
+        rm = out[0] > 0 ? sqrt(out[1] / out[0]) : 0.0;
+        return hipSuccess;
+    };
+    double fit = 0, rm = 0;
+    int it = 0;
+    HIPCHK(c, evaluate(fit, rm));
+    for (; it < max_iter; it++) {
+        double uc = 1.0, us = 0.0, ux = 0.0, uy = 0.0;       // ComputeTransformation: identity without correspondences
+        if (out[0] > 0) {
+            const double nn = out[0];
+            const double means[4] = {out[2] / nn, out[3] / nn, out[4] / nn, out[5] / nn};
+            double o2[6];
+            HIPCHK(c, qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 1, means, d_part.p, d_out.p));
+            HIPCHK(c, hipMemcpyAsync(o2, d_out.p, sizeof o2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            const double theta = atan2(o2[1], o2[0]);
+            uc = cos(theta); us = sin(theta);
+            ux = means[2] - (uc * means[0] - us * means[1]);
+            uy = means[3] - (us * means[0] + uc * means[1]);
+        }
+        // transformation = update * transformation
+        const double nc = uc * tc - us * ts, ns = us * tc + uc * ts;
+        const double nx = uc * tx - us * ty + ux, ny = us * tx + uc * ty + uy;
+        tc = nc; ts = ns; tx = nx; ty = ny;
+        HIPCHK(c, qs_launch_icp_transform(c, d_src.p, n_src, uc, us, ux, uy));
+        const double bfit = fit, brm = rm;
+        HIPCHK(c, evaluate(fit, rm));
+        if (fabs(bfit - fit) < rel_fitness && fabs(brm - rm) < rel_rmse) { it++; break; }
+    }
+    T[0] = tc; T[1] = -ts; T[2] = tx; T[3] = ts; T[4] = tc; T[5] = ty; T[6] = 0; T[7] = 0; T[8] = 1;
+    *fitness = fit; *rmse = rm;
+    if (iters) *iters = it;
+    return QS_OK;
+}
+
+// Diagnostic: measured fp64 MFMA rate of this GPU (dense v_mfma_f64_16x16x4_f64, every CU, 2 waves per SIMD), TFLOP/s.
+extern "C" int qs_diag_mfma_f64_rate(qs_ctx *c, double *tflops)
+{
+    ARGCHK(c, c != nullptr && tflops != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> sink;
+    ScopedEvent a, b;
+    const int blocks = 256 * 2, iters = 20000;             // 2 workgroups of 4 waves per CU
+    HIPCHK(c, sink.alloc(1));
+    HIPCHK(c, hipEventCreate(&a.e));
+    HIPCHK(c, hipEventCreate(&b.e));
+    HIPCHK(c, qs_launch_mfma_f64_rate(c, blocks, 1000, sink.p));
+    HIPCHK(c, hipEventRecord(a.e, c->stream));
+    HIPCHK(c, qs_launch_mfma_f64_rate(c, blocks, iters, sink.p));
+    HIPCHK(c, hipEventRecord(b.e, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, a.e, b.e));
+    const double flops = (double)blocks * 4 /* waves */ * iters * 4 /* MFMAs */ * (2.0 * 16 * 16 * 4);
+    *tflops = flops / (ms * 1e-3) / 1e12;
+    return QS_OK;
+}
+
+extern "C" int qs_voxel_downsample(qs_ctx *c, const double *xy, size_t n, double voxel, double *out_xy, size_t cap, size_t *n_out)
+{
+    ARGCHK(c, c != nullptr && n_out != nullptr && voxel > 0);
+    *n_out = 0;
+    if (n == 0) return QS_OK;
+    ARGCHK(c, xy != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    double mnx = xy[0], mny = xy[1];
+    for (size_t i = 1; i < n; i++) { if (xy[2 * i] < mnx) mnx = xy[2 * i]; if (xy[2 * i + 1] < mny) mny = xy[2 * i + 1]; }
+    mnx -= voxel * 0.5; mny -= voxel * 0.5;                 // voxel_min_bound = min_bound - voxel_size / 2
+    std::vector<unsigned long long> keys(n);
+    {
+        DevBuf<double2> d; DevBuf<unsigned long long> dk;
+        HIPCHK(c, d.alloc(n));
+        HIPCHK(c, dk.alloc(n));
+        HIPCHK(c, hipMemcpyAsync(d.p, xy, n * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, qs_launch_voxel_keys(c, d.p, n, mnx, mny, voxel, dk.p));
+        HIPCHK(c, hipMemcpyAsync(keys.data(), dk.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    // group by voxel (ascending key), average in input order: a handful of points per ROS callback
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return keys[a] < keys[b]; });
+    size_t k = 0;
+    for (size_t p = 0; p < n;) {
+        size_t q = p; double sx = 0, sy = 0;
+        while (q < n && keys[order[q]] == keys[order[p]]) { sx += xy[2 * order[q]]; sy += xy[2 * order[q] + 1]; q++; }
+        if (out_xy && k < cap) { out_xy[2 * k] = sx / (double)(q - p); out_xy[2 * k + 1] = sy / (double)(q - p); }
+        k++; p = q;
+    }
+    *n_out = k;
+    return QS_OK;
 }

@@ -18,6 +18,9 @@
 //                    the path cells are written as they come, and 64 of them at a time are tested for visibility
 //                    (each lane walks the reference's Bresenham line from the start to its cell over the mask).
 // There are no device-side waits and no grid-wide barriers: a round that finds its list empty returns at once.
+#include <string.h>
+#include <algorithm>
+
 #include "qs_internal.h"
 #include "raycast_common.h"
 
@@ -388,9 +391,27 @@ qs_plan_walk_kernel(const unsigned int *__restrict__ fields, size_t fcells, PlBo
 }
 
 // ---- workspace and launchers -------------------------------------------------------------------------------------
+#define QS_PLAN_ROUND_BLOCKS 1024   // workgroups of a relaxation round (they stride over its list)
+// the planner's workspace, carved from ws (nullptr: only the bytes the block needs) for n requests
+struct QsPlanLayout {
+    unsigned int *mask;             // [tiles down * 64][mp] traversable bits, rows padded to whole tiles
+    unsigned int *tile_any;         // [tiles down][tiles across] the tile holds a traversable cell
+    unsigned int *bbox;             // [4] first / last tile across and down of those (the census)
+    unsigned int *cnt;              // [3] list counts of a ring of rounds
+    unsigned long long *stats;      // [4] rounds, tile visits, (unused), snapped endpoints
+    double2 *xy;                    // [2n] starts, then goals
+    long long *cell;                // [2n] their cells (gy * size + gx), -1 = none
+    int4 *out4;                     // [n] status, waypoint gx, gy, cost
+    long long *plen;                // [n] path cells
+    int2 *path;                     // [n][path_cap]
+    unsigned int *list0, *list1, *marks;   // [item_cap] worklists of (field, tile) items and their round marks
+    unsigned int *fields;           // [field_words] one group's fields
+    int mp, gtx;                    // mask words per row, tiles across the grid
+    size_t gmax, field_words, item_cap, bytes;
+};
 static inline int pl_tiles(int size) { return (size + PL_T - 1) / PL_T; }
 
-QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap)
+static QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap)
 {
     QsPlanLayout L;
     Carve k(ws);
@@ -422,7 +443,7 @@ QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap)
     return L;
 }
 
-hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clearance)
+static hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clearance)
 {
     const int gt = pl_tiles(c->cfg.size);
     static const unsigned int init[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
@@ -433,7 +454,7 @@ hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clearance)
     return hipGetLastError();
 }
 
-hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, size_t n_end, int radius)
+static hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, size_t n_end, int radius)
 {
     if (!n_end) return hipSuccess;
     const unsigned int blocks = (unsigned int)((n_end + PL_BLOCK / QS_WAVE - 1) / (PL_BLOCK / QS_WAVE));
@@ -451,14 +472,15 @@ static inline PlBox pl_box(const unsigned int bbox[4])
     return B;
 }
 
-size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n)
+// requests per group
+static size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n)
 {
     const PlBox B = pl_box(bbox);
     size_t g = L.field_words / ((size_t)B.fw * B.fh);
     return g < n ? g : n;
 }
 
-hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn)
+static hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn)
 {
     const PlBox B = pl_box(bbox);
     const size_t fc = (size_t)B.fw * B.fh;
@@ -471,7 +493,7 @@ hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned 
     return hipGetLastError();
 }
 
-hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t gn, unsigned int r)
+static hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t gn, unsigned int r)
 {
     const PlBox B = pl_box(bbox);
     size_t items = gn * B.ntx * B.nty;
@@ -482,8 +504,8 @@ hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned
     return hipGetLastError();
 }
 
-hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
-                               int lookahead, size_t path_cap)
+static hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
+                                      int lookahead, size_t path_cap)
 {
     const PlBox B = pl_box(bbox);
     const unsigned int blocks = (unsigned int)((gn + PL_BLOCK / QS_WAVE - 1) / (PL_BLOCK / QS_WAVE));
@@ -491,4 +513,147 @@ hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned 
                        L.mask, L.mp, c->cfg.size, L.cell, L.cell + n, (int)g0, (int)gn, lookahead, L.path, path_cap, L.out4,
                        L.plen);
     return hipGetLastError();
+}
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------
+static int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out)
+{
+    out = p ? *p : qs_plan_params{2, 10, 200, 0};        // the defaults (include/quasar_slam.h)
+    if (out.clearance < 0 || out.clearance > QS_PLAN_MAX_CLEARANCE)
+        return qs_fail(c, QS_E_INVAL, "path planning: clearance must lie in [0, QS_PLAN_MAX_CLEARANCE]");
+    if (out.snap_radius < 0 || out.snap_radius > QS_PLAN_MAX_SNAP)
+        return qs_fail(c, QS_E_INVAL, "path planning: snap_radius must lie in [0, QS_PLAN_MAX_SNAP]");
+    if (out.lookahead < 1 || out.lookahead > QS_PLAN_MAX_LOOKAHEAD)
+        return qs_fail(c, QS_E_INVAL, "path planning: lookahead must lie in [1, QS_PLAN_MAX_LOOKAHEAD]");
+    return QS_OK;
+}
+
+// the mask and the census for n requests (layout of the planner workspace); bbox[0] > bbox[2]: no traversable cell
+static int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPlanLayout &L, unsigned int bbox[4])
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, c->plan_ws.reserve(qs_plan_layout(nullptr, c->cfg.size, n, path_cap).bytes, c->stream));
+    L = qs_plan_layout(c->plan_ws.p, c->cfg.size, n, path_cap);
+    HIPCHK(c, hipMemsetAsync(L.stats, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, qs_launch_plan_trav(c, L, clearance));
+    HIPCHK(c, hipMemcpyAsync(bbox, L.bbox, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+// the fields of requests g0 .. g0 + gn: seed, then rounds in batches of QS_PLAN_ROUND_BATCH without a sync (a round that
+// finds its list empty returns at once), the live count read once per batch; then the walk
+#define QS_PLAN_ROUND_BATCH 8
+static int plan_group(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
+                      int lookahead, size_t path_cap)
+{
+    HIPCHK(c, qs_launch_plan_seed(c, L, bbox, n, g0, gn));
+    for (unsigned int r = 1;; r += QS_PLAN_ROUND_BATCH) {
+        for (unsigned int k = 0; k < QS_PLAN_ROUND_BATCH; k++) HIPCHK(c, qs_launch_plan_round(c, L, bbox, gn, r + k));
+        unsigned int live = 0;
+        HIPCHK(c, hipMemcpyAsync(&live, L.cnt + (r + QS_PLAN_ROUND_BATCH) % 3, sizeof live, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!live) break;
+        if (r > 0x7fffffffu) return qs_fail(c, QS_E_STATE, "path planning: the relaxation did not settle");
+    }
+    if (lookahead > 0) HIPCHK(c, qs_launch_plan_walk(c, L, bbox, n, g0, gn, lookahead, path_cap));
+    return QS_OK;
+}
+
+extern "C" int qs_traversable(qs_ctx *c, int32_t clearance, uint8_t *mask_host)
+{
+    ARGCHK(c, c != nullptr && mask_host != nullptr);
+    if (clearance < 0 || clearance > QS_PLAN_MAX_CLEARANCE)
+        return qs_fail(c, QS_E_INVAL, "qs_traversable: clearance must lie in [0, QS_PLAN_MAX_CLEARANCE]");
+    QsPlanLayout L;
+    unsigned int bbox[4];
+    int rc = plan_begin(c, clearance, 0, 0, L, bbox);
+    if (rc != QS_OK) return rc;
+    const size_t size = (size_t)c->cfg.size, mp = (size_t)L.mp;
+    std::vector<unsigned int> bits(size * mp);
+    HIPCHK(c, hipMemcpy(bits.data(), L.mask, bits.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    for (size_t y = 0; y < size; y++)
+        for (size_t x = 0; x < size; x++) mask_host[y * size + x] = (bits[y * mp + (x >> 5)] >> (x & 31)) & 1u;
+    return QS_OK;
+}
+
+extern "C" int qs_plan_field(qs_ctx *c, const qs_plan_params *params, const double goal_xy[2], uint32_t *field_host)
+{
+    ARGCHK(c, c != nullptr && goal_xy != nullptr && field_host != nullptr);
+    qs_plan_params p;
+    int rc = plan_params(c, params, p);
+    if (rc != QS_OK) return rc;
+    QsPlanLayout L;
+    unsigned int bbox[4];
+    rc = plan_begin(c, p.clearance, 1, 0, L, bbox);
+    if (rc != QS_OK) return rc;
+    const size_t size = (size_t)c->cfg.size;
+    std::fill(field_host, field_host + size * size, 0xffffffffu);
+    if (bbox[0] > bbox[2]) return QS_OK;                  // nothing is traversable
+    const double xy[4] = {goal_xy[0], goal_xy[1], goal_xy[0], goal_xy[1]};   // (start = goal: only the field is wanted)
+    HIPCHK(c, hipMemcpyAsync(L.xy, xy, sizeof xy, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, qs_launch_plan_snap(c, L, 2, p.snap_radius));
+    rc = plan_group(c, L, bbox, 1, 0, 1, 0, 0);
+    if (rc != QS_OK) return rc;
+    // the bounding box's cells that lie on the grid, rows of the field into rows of the host array
+    const size_t x0 = (size_t)bbox[0] * 64, y0 = (size_t)bbox[1] * 64, fw = (size_t)(bbox[2] - bbox[0] + 1) * 64;
+    const size_t fh = (size_t)(bbox[3] - bbox[1] + 1) * 64;
+    const size_t w = std::min(fw, size - x0), h = std::min(fh, size - y0);
+    HIPCHK(c, hipMemcpy2D(field_host + y0 * size + x0, size * sizeof(uint32_t), L.fields, fw * sizeof(uint32_t),
+                          w * sizeof(uint32_t), h, hipMemcpyDeviceToHost));
+    return QS_OK;
+}
+
+extern "C" int qs_plan_paths(qs_ctx *c, const qs_plan_params *params, const double *start_xy, const double *goal_xy, size_t n,
+                             int32_t *status, int32_t *wp_cell_xy, double *wp_xy, uint32_t *cost, int32_t *path_xy,
+                             size_t path_cap, int64_t *path_len, uint64_t stats[4])
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || (start_xy && goal_xy && status && wp_cell_xy && wp_xy && cost));
+    ARGCHK(c, path_cap == 0 || path_xy != nullptr);
+    ARGCHK(c, n <= ((size_t)1 << 24));
+    qs_plan_params p;
+    int rc = plan_params(c, params, p);
+    if (rc != QS_OK) return rc;
+    QsPlanLayout L;
+    unsigned int bbox[4];
+    rc = plan_begin(c, p.clearance, n, path_cap, L, bbox);
+    if (rc != QS_OK) return rc;
+    uint64_t groups = 0;
+    unsigned long long st[4] = {0, 0, 0, 0};
+    std::vector<int4> out(n, make_int4(QS_PLAN_NO_START, -1, -1, -1));
+    std::vector<long long> plen(n, 0);
+    if (n && bbox[0] <= bbox[2]) {
+        std::vector<double> xy(4 * n);
+        memcpy(xy.data(), start_xy, 2 * n * sizeof(double));
+        memcpy(xy.data() + 2 * n, goal_xy, 2 * n * sizeof(double));
+        HIPCHK(c, hipMemcpyAsync(L.xy, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, qs_launch_plan_snap(c, L, 2 * n, p.snap_radius));
+        const size_t g = qs_plan_group(L, bbox, n);
+        if (g == 0) return qs_fail(c, QS_E_STATE, "qs_plan_paths: workspace holds no field");
+        for (size_t g0 = 0; g0 < n; g0 += g, groups++) {
+            rc = plan_group(c, L, bbox, n, g0, std::min(g, n - g0), p.lookahead, path_cap);
+            if (rc != QS_OK) return rc;
+        }
+        HIPCHK(c, hipMemcpyAsync(out.data(), L.out4, n * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(plen.data(), L.plen, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        if (path_cap) HIPCHK(c, hipMemcpyAsync(path_xy, L.path, n * path_cap * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st, L.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }   // (no traversable cell: every start fails to snap, QS_PLAN_NO_START, what the snap kernel would say)
+    for (size_t i = 0; i < n; i++) {
+        const int4 o = out[i];
+        if (o.x < 0) return qs_fail(c, QS_E_STATE, "qs_plan_paths: a path walk found no descending move");
+        status[i] = o.x;
+        const bool ok = o.x == QS_PLAN_OK;
+        wp_cell_xy[2 * i] = ok ? o.y : -1;
+        wp_cell_xy[2 * i + 1] = ok ? o.z : -1;
+        wp_xy[2 * i] = ok ? c->cfg.ox + (o.y + 0.5) * c->cfg.res : NAN;        // grid_to_world :127-131
+        wp_xy[2 * i + 1] = ok ? c->cfg.oy + (o.z + 0.5) * c->cfg.res : NAN;
+        cost[i] = ok ? (uint32_t)o.w : 0xffffffffu;
+        if (path_len) path_len[i] = ok ? plen[i] : 0;
+    }
+    if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = groups; stats[3] = st[3]; }
+    return QS_OK;
 }

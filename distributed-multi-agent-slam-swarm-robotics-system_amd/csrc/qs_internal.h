@@ -129,7 +129,7 @@ struct QsBatch {
     int own_lo, own_hi;      // agents whose rays this context casts (1..max_agent when not sharded)
     QsEdgeRec *edge;         // exact-trig mode: rays whose end point lies within 1e-9 cells of a cell boundary are not cast by the
     unsigned int *edge_n;    //   device but appended here, self-contained (pose, distance, stamp): the host resolves them at the next
-    unsigned int edge_cap;   //   point the map is observed (qs_api.hip: flush_edge_rays); edge_n[0] = records so far, [2] = rays that
+    unsigned int edge_cap;   //   point the map is observed (qs_api.hip: sync_host_state); edge_n[0] = records so far, [2] = rays that
                              //   found the list full and were cast with the device's trig after all
     unsigned char *agent;    // agent_id
     unsigned char *lm;       // landmark_type (0 for v1 packets)
@@ -228,7 +228,7 @@ struct qs_ctx {
     int blocks_x = 0, blocks_y = 0;
     DevBuf<unsigned long long> d_counts_sent;    // [size][size]: this context's counters as of its last sparse fuse (deltas travel)
     int sf_world = 0, sf_rank = 0;
-    DevBuf<char> sf_meta;                        // the three arrays below, carved for sf_world ranks (qs_api.hip: sf_layout)
+    DevBuf<char> sf_meta;                        // the three arrays below, carved for sf_world ranks (sparse_fuse.hip: sf_layout)
     unsigned int *d_sf_bitmaps = nullptr;        // [sf_world][dirty_words]: every rank's bitmap of the fuse in flight
     unsigned int *d_sf_lists = nullptr;          // [sf_world][dirty_words * 32] block ids, ascending
     unsigned int *d_sf_counts = nullptr;         // [sf_world] blocks per rank
@@ -318,7 +318,44 @@ struct StageTimer {
     void stop() { if (c->timing && a) { hipEventRecord(b, st); c->pending.push_back({stage, a, b}); a = nullptr; } }
 };
 
-// ---- kernel launchers (each defined next to its kernel) ----------------------------------
+// ---- host side of the C ABI: what the files that define extern "C" entry points share ----------------------------------
+// qs_fail records the message (per context, or per thread before one exists) and returns the code; the macros return from
+// the calling entry point (HIPRET from a helper that returns hipError_t).
+int qs_fail(qs_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
+#define HIPCHK(c, x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return qs_fail((c), QS_E_HIP, #x, e__); } while (0)
+#define ARGCHK(c, cond) do { if (!(cond)) return qs_fail((c), QS_E_INVAL, "invalid argument: " #cond); } while (0)
+#define HIPRET(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
+
+struct ScopedEvent {                        // an event of one call, destroyed with its scope (as DevBuf frees a buffer)
+    hipEvent_t e = nullptr;
+    ScopedEvent() = default;
+    ScopedEvent(const ScopedEvent &) = delete;
+    ScopedEvent &operator=(const ScopedEvent &) = delete;
+    ~ScopedEvent() { if (e) hipEventDestroy(e); }
+};
+static const size_t QS_IO_WS_FLOOR = (size_t)1 << 16;      // qs_ctx::io_ws doubles from 64 KiB
+
+// smallest double T with sqrt(T) >= radius: (s < T) <=> (sqrt(s) < radius) for correctly rounded sqrt
+double r2_threshold_for(double radius);
+// capacity of graph g's logs for need_* entries, the first have_* kept
+int graph_reserve(qs_ctx *c, int g, long long need_lms, long long need_cls, long long have_lms, long long have_cls);
+int reset_state(qs_ctx *c);                              // qs_reset: an empty map, enqueued (no wait for the GPU)
+int ensure_batch(qs_ctx *c, size_t n);                   // room for n records; a growth that fails leaves the old arrays
+// n_seq sequence numbers from seq0 fit the stamp epoch (a rebase first if they do not)
+int ensure_epoch(qs_ctx *c, uint64_t seq0, size_t n_seq);
+// device staging of host-side records: bytes of records, one length and one receive time per (shortest) record, laid out for
+// the smallest power-of-two multiple of 64 KiB that holds `bytes` (the block only grows)
+struct Staging { unsigned char *pkts; unsigned short *lens; double *time; };
+int reserve_staging(qs_ctx *c, size_t bytes, Staging &s);
+
+// The sync point: every call that observes the map, the counters or the pose graphs goes through it first.  It resolves
+// the exact-trig edge rays waiting on the device, reads the pile flag and the loop-closure chain's statistics, and sets
+// the host's landmark / closure bounds to the graphs' exact counts.  Without host_waits it does nothing when no ingest or
+// chain has run since the last time; host_waits: the caller waits for the stream anyway, so the flags are read regardless.
+int sync_host_state(qs_ctx *c, bool host_waits);
+#define SYNCCHK(c) do { int rcs__ = sync_host_state((c), false); if (rcs__ != QS_OK) return rcs__; } while (0)
+
+// ---- kernel launchers (each defined next to its kernel) that another file calls ----------------
 // decode.hip
 hipError_t qs_launch_decode(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride,
                             const unsigned short *d_lens);
@@ -342,44 +379,16 @@ hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axi
 // raycast_tiled.hip
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
 bool qs_tiled_supported(const qs_ctx *c);
-// sweep.hip: n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
-hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
-                            uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid);
 // grid_ops.hip
-hipError_t qs_launch_view_i8(qs_ctx *c, signed char *out_dev);
-hipError_t qs_launch_logodds(qs_ctx *c, float l_occ, float l_free, float lmin, float lmax, float *out_dev);
-hipError_t qs_launch_split_counts(qs_ctx *c, int *hits_dev, int *misses_dev);
 hipError_t qs_launch_rebase(qs_ctx *c);
 hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,
                           const unsigned long long *const *d_src_counts, size_t n_src, size_t cell_off, size_t n_cells,
                           unsigned long long *dst_counts);
-hipError_t qs_launch_fill_zone_identity(qs_ctx *c);
 hipError_t qs_launch_reset_small(qs_ctx *c);
-hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res,
-                                 double ox, double oy, double *d_xy, size_t cap,
-                                 unsigned long long *d_count, unsigned int *d_rowcount);
-hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx,
-                               double miny, int h, int w, signed char *d_grid);
-hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4);
 // sparse_fuse.hip
-size_t qs_sf_block_bytes(const qs_ctx *c);
 hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells);
-hipError_t qs_launch_sf_lists(qs_ctx *c);
-hipError_t qs_launch_sf_restore(qs_ctx *c);
-hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst);
-hipError_t qs_launch_sf_apply(qs_ctx *c);
-hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out);
 hipError_t qs_launch_sf_list_of(qs_ctx *c, const unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
                                 unsigned int *count);
-// checkpoint.hip: blocks of QS_DIRTY_BLOCK_H x QS_DIRTY_BLOCK_W cells; planes 1 = stamps, 2 = + counters, 4 = + sent + fused
-size_t qs_ck_block_bytes(int planes);
-hipError_t qs_launch_ck_census(qs_ctx *c, unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
-                               unsigned int *count);
-hipError_t qs_launch_ck_pack(qs_ctx *c, const unsigned int *list, unsigned int n_blocks, int pitch, int planes, unsigned char *dst);
-hipError_t qs_launch_ck_unpack(qs_ctx *c, const unsigned int *list, unsigned int n_blocks, int pitch, int planes,
-                               const unsigned char *src);
-// diag.hip
-hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, const unsigned int *d_chase_l1, double *d_out);
 // frontier.hip
 #define QS_FR_CHUNK 1024          // cells per chunk of the frontier compactions (count -> scan -> ranked write)
 // the workspace of the labelling and the compactions, carved from ws (nullptr: only the bytes the block needs):
@@ -387,72 +396,9 @@ hipError_t qs_launch_diag_latencies(qs_ctx *c, const unsigned int *d_chase_l2, c
 struct QsFrLayout { unsigned int *label, *cnt; unsigned long long *sumx, *sumy; unsigned int *chunk; unsigned long long *total; size_t bytes; };
 QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws);
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
-hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap);
 hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
-// frontier_targets.hip
-#define QS_FT_K 32                // candidates per bot (the top-K list of the greedy pass)
-struct QsFtState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
-// the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
-struct QsFtLayout {
-    QsFtState *st;
-    double2 *cent, *bots, *tgt_xy, *asg_xy;
-    long long *tgt_idx;
-    int *asg_idx;
-    double *part_key; int *part_idx;      // [n_bots][n_chunks][K]
-    int *list_idx, *list_len;             // [n_bots][K], [n_bots]
-    double *fb_key; int *fb_idx;          // [n_fb]: per-block minima of a fallback scan
-    size_t bytes;
-};
-QsFtLayout qs_ft_layout(void *ws, size_t n_cent, size_t n_bots);
-hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
-// the lists, then the greedy pass from start_bot (fb_pending: a fallback scan has decided start_bot); it ends in QsFtState
-hipError_t qs_launch_ft_assign(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep,
-                               int start_bot, int start_m, int fb_pending);
-hipError_t qs_launch_ft_fallback(qs_ctx *c, void *ft_ws, size_t n_cent, size_t n_bots, double r2_sep, int bot, int m);
-// plan.hip: the planner's workspace, carved from ws (nullptr: only the bytes the block needs) for n requests
-#define QS_PLAN_ROUND_BLOCKS 1024   // workgroups of a relaxation round (they stride over its list)
-struct QsPlanLayout {
-    unsigned int *mask;             // [tiles down * 64][mp] traversable bits, rows padded to whole tiles
-    unsigned int *tile_any;         // [tiles down][tiles across] the tile holds a traversable cell
-    unsigned int *bbox;             // [4] first / last tile across and down of those (the census)
-    unsigned int *cnt;              // [3] list counts of a ring of rounds
-    unsigned long long *stats;      // [4] rounds, tile visits, (unused), snapped endpoints
-    double2 *xy;                    // [2n] starts, then goals
-    long long *cell;                // [2n] their cells (gy * size + gx), -1 = none
-    int4 *out4;                     // [n] status, waypoint gx, gy, cost
-    long long *plen;                // [n] path cells
-    int2 *path;                     // [n][path_cap]
-    unsigned int *list0, *list1, *marks;   // [item_cap] worklists of (field, tile) items and their round marks
-    unsigned int *fields;           // [field_words] one group's fields
-    int mp, gtx;                    // mask words per row, tiles across the grid
-    size_t gmax, field_words, item_cap, bytes;
-};
-QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap);
-hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clearance);
-hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, size_t n_end, int radius);
-size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n);    // requests per group
-hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn);
-hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t gn, unsigned int r);
-hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
-                               int lookahead, size_t path_cap);
-// icp.hip
-hipError_t qs_launch_icp_nn(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
-                            double max_d2, int *corr, double *d2);
-hipError_t qs_launch_mfma_f64_rate(qs_ctx *c, int blocks, int iters, double *sink);
-hipError_t qs_launch_icp_prep(qs_ctx *c, const double2 *dst, size_t n_dst, size_t n_pad, double cx, double cy, double *planes);
-void qs_icp_nn_plan(size_t n_src, size_t n_pad, unsigned int *n_groups, unsigned int *n_parts, unsigned int *chunks_per_part);
-hipError_t qs_launch_icp_nn_mfma(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, size_t n_dst,
-                                 const double *planes, size_t n_pad, double cx, double cy, double t2max, double max_d2,
-                                 int *corr, double *d2, int *part_j, double *part_d2, double *thr_seed);
-hipError_t qs_launch_icp_sums(qs_ctx *c, const double2 *src, size_t n_src, const double2 *dst, const int *corr,
-                              const double *d2, int pass, const double means[4], double *partial, double *out6);
-hipError_t qs_launch_icp_transform(qs_ctx *c, double2 *pts, size_t n, double cs, double sn, double tx, double ty);
-hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel,
-                                unsigned long long *keys);
 // ekf.hip
 hipError_t qs_launch_ekf_ingest(qs_ctx *c, size_t n, const double *d_time, hipStream_t st);
 // ekf_scan.hip: the same filter over a large batch, parallel in time
 #define QS_EKF_SCAN_MIN_BATCH 4096
 hipError_t qs_launch_ekf_scan(qs_ctx *c, size_t n, const double *d_time, hipStream_t st);
-hipError_t qs_launch_ekf_step(qs_ctx *c, const int *d_bots, const double *d_omega, const double *d_t,
-                              const double *d_zv, const double *d_zo, size_t n, int do_update);

@@ -46,7 +46,7 @@ qs_raycast_direct_kernel(size_t n, QsBatch b, QsGeom geo, unsigned int *__restri
         const unsigned int key_free = (unsigned int)((ord_base + ord_stride * i + s + 1) << 1);
         QsLine ln;
         if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, rx, ry, yaw, df, key_free)) {
-            // the host decides this ray's cells (qs_api.hip: flush_edge_rays)
+            // the host decides this ray's cells (qs_api.hip: sync_host_state)
         } else if (qs_line_setup(ray, rx, ry, geo, ln)) {
             int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
             for (;;) {

@@ -21,7 +21,7 @@
 #define SF_CELLS (SF_BW * SF_BH)             // 64: one lane per cell
 #define SF_LIST_BLOCK 1024
 
-size_t qs_sf_block_bytes(const qs_ctx *c) { return SF_CELLS * (sizeof(unsigned int) + (c->d_counts.p ? sizeof(unsigned long long) : 0)); }
+static size_t qs_sf_block_bytes(const qs_ctx *c) { return SF_CELLS * (sizeof(unsigned int) + (c->d_counts.p ? sizeof(unsigned long long) : 0)); }
 
 // ---- mark a cell range dirty (qs_fuse_buffers*: a local fold writes the grid without going through a raycast) ---------
 __global__ void qs_sf_mark_rows_kernel(unsigned int *__restrict__ dirty, int pitch, int blocks_x, int by_lo, int by_hi)
@@ -53,7 +53,7 @@ __global__ void qs_sf_restore_kernel(unsigned int *__restrict__ dirty, const uns
     const unsigned int m = saved[w];
     if (m) dirty[w] |= m;                                    // stream-ordered: nothing else writes the bitmap meanwhile
 }
-hipError_t qs_launch_sf_restore(qs_ctx *c)
+static hipError_t qs_launch_sf_restore(qs_ctx *c)
 {
     if (!c->d_dirty.p || !c->d_sf_bitmaps || c->sf_rank >= c->sf_world) return hipSuccess;
     hipLaunchKernelGGL(qs_sf_restore_kernel, dim3((unsigned int)((c->dirty_words + 255) / 256)), dim3(256), 0, c->stream, c->d_dirty.p,
@@ -92,7 +92,7 @@ qs_sf_lists_kernel(const unsigned int *__restrict__ bitmaps, size_t words, int p
     }
     if (tid == SF_LIST_BLOCK - 1) counts[blockIdx.x] = run;
 }
-hipError_t qs_launch_sf_lists(qs_ctx *c)
+static hipError_t qs_launch_sf_lists(qs_ctx *c)
 {
     hipLaunchKernelGGL(qs_sf_lists_kernel, dim3(c->sf_world), dim3(SF_LIST_BLOCK), 0, c->stream, c->d_sf_bitmaps, c->dirty_words,
                        c->geom.dirty_pitch, c->blocks_x, c->d_sf_lists, c->d_sf_counts);
@@ -119,7 +119,7 @@ qs_sf_popcount_kernel(const unsigned int *__restrict__ bm, size_t words, int pit
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, (unsigned long long)n);
 }
-hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out)
+static hipError_t qs_launch_sf_popcount(qs_ctx *c, unsigned long long *d_out)
 {
     hipError_t e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long), c->stream);
     if (e != hipSuccess) return e;
@@ -155,7 +155,7 @@ qs_sf_pack_kernel(const unsigned int *__restrict__ list, unsigned int n_blocks, 
         }
     }
 }
-hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst)
+static hipError_t qs_launch_sf_pack(qs_ctx *c, unsigned int n_own, unsigned char *dst)
 {
     if (n_own == 0) return hipSuccess;
     const unsigned int *list = c->d_sf_lists + (size_t)c->sf_rank * c->dirty_words * 32;
@@ -207,7 +207,7 @@ qs_sf_apply_kernel(SfPlan pl, const unsigned int *__restrict__ lists, size_t lis
         }
     }
 }
-hipError_t qs_launch_sf_apply(qs_ctx *c)
+static hipError_t qs_launch_sf_apply(qs_ctx *c)
 {
     SfPlan pl{};
     pl.world = c->sf_world; pl.rank = c->sf_rank;
@@ -223,4 +223,129 @@ hipError_t qs_launch_sf_apply(qs_ctx *c)
         hipLaunchKernelGGL(qs_sf_apply_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, pl, c->d_sf_lists, c->dirty_words * 32,
                            c->geom.dirty_pitch, c->cfg.size, c->sf_payload.p, c->d_stamps.p, c->d_counts_fused.p, c->d_counts_sent.p);
     return hipGetLastError();
+}
+
+// ---- C ABI: sparse fuse (protocol in include/quasar_slam.h) ----------------------------------------------------------
+extern "C" int qs_dirty_tracking(qs_ctx *c, int32_t enable)
+{
+    ARGCHK(c, c != nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!enable) {
+        c->geom.dirty = nullptr; c->geom.dirty_pitch = 0;
+        c->d_dirty = DevBuf<unsigned int>();
+        c->sf_state = 0;
+        c->counts_view_fused = false;         // the fused counters stop following the ranks: the views read the own ones
+        return QS_OK;
+    }
+    if (c->d_dirty.p) return QS_OK;
+    if (c->dirty_since_fuse) return qs_fail(c, QS_E_STATE, "qs_dirty_tracking: the grid has unfused writes (enable it after qs_create / qs_reset / a fuse)");
+    c->blocks_x = (c->cfg.size + QS_DIRTY_BLOCK_W - 1) / QS_DIRTY_BLOCK_W;
+    c->blocks_y = (c->cfg.size + QS_DIRTY_BLOCK_H - 1) / QS_DIRTY_BLOCK_H;
+    const int pitch = (c->blocks_x + 31) / 32;
+    c->dirty_words = (size_t)c->blocks_y * pitch;
+    if (c->d_counts.p) {
+        const size_t nb = c->cells * sizeof(unsigned long long);
+        if (!c->d_counts_sent.p) HIPCHK(c, c->d_counts_sent.alloc(c->cells));
+        // the fused counters accumulate deltas from here on: they start as "nothing sent", the local counters as all delta
+        HIPCHK(c, hipMemsetAsync(c->d_counts_sent.p, 0, nb, c->stream));
+        if (!c->d_counts_fused.p) HIPCHK(c, c->d_counts_fused.alloc(c->cells));
+        HIPCHK(c, hipMemsetAsync(c->d_counts_fused.p, 0, nb, c->stream));
+        // counters written before tracking was switched on have no dirty bit: everything is marked once
+    }
+    // the bitmap last, published with geom.dirty: tracking is on (d_dirty set) only once everything it writes exists
+    HIPCHK(c, c->d_dirty.alloc(c->dirty_words));
+    c->geom.dirty = c->d_dirty.p; c->geom.dirty_pitch = pitch;
+    HIPCHK(c, hipMemsetAsync(c->d_dirty.p, 0, c->dirty_words * sizeof(unsigned int), c->stream));
+    if (c->next_seq != 0) HIPCHK(c, qs_launch_sf_mark_range(c, 0, c->cells));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QS_OK;
+}
+
+extern "C" int qs_dirty_blocks(qs_ctx *c, size_t *n_blocks, size_t *block_cells)
+{
+    ARGCHK(c, c != nullptr && n_blocks != nullptr);
+    if (!c->d_dirty.p) return qs_fail(c, QS_E_STATE, "qs_dirty_blocks: dirty tracking is off (qs_dirty_tracking)");
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, c->io_ws.reserve(sizeof(unsigned long long), c->stream, QS_IO_WS_FLOOR));
+    unsigned long long v = 0;
+    HIPCHK(c, qs_launch_sf_popcount(c, (unsigned long long *)c->io_ws.p));
+    HIPCHK(c, hipMemcpyAsync(&v, c->io_ws.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_blocks = (size_t)v;
+    if (block_cells) *block_cells = (size_t)QS_DIRTY_BLOCK_W * QS_DIRTY_BLOCK_H;
+    return QS_OK;
+}
+
+// the per-rank arrays of a fuse of `world` ranks, carved from base (nullptr: only the size); returns the bytes
+static size_t sf_layout(const qs_ctx *c, void *base, int world, unsigned int *&bitmaps, unsigned int *&lists, unsigned int *&counts)
+{
+    Carve k(base);
+    bitmaps = k.take<unsigned int>((size_t)world * c->dirty_words);
+    lists = k.take<unsigned int>((size_t)world * c->dirty_words * 32);
+    counts = k.take<unsigned int>((size_t)world);
+    return k.bytes;
+}
+
+extern "C" int qs_sparse_fuse_begin(qs_ctx *c, int32_t world, int32_t rank, void **bitmaps_dev, size_t *bitmap_bytes)
+{
+    ARGCHK(c, c != nullptr && bitmaps_dev != nullptr && bitmap_bytes != nullptr);
+    ARGCHK(c, world >= 1 && world <= QS_SPARSE_MAX_WORLD && rank >= 0 && rank < world);
+    if (!c->d_dirty.p) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_begin: dirty tracking is off (qs_dirty_tracking)");
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    // a fuse begun here that never reached apply: its blocks did not travel, so they go into this one (before a change of
+    // world reallocates the bitmaps).  Nothing else was committed: the counter deltas are taken from `sent`, which only
+    // apply advances.
+    if (c->sf_state != 0) { HIPCHK(c, qs_launch_sf_restore(c)); c->sf_state = 0; }
+    if (world != c->sf_world) {                              // (a growth that fails leaves the old arrays as they were)
+        unsigned int *bm, *li, *co;
+        DevBuf<char> meta;
+        HIPCHK(c, meta.alloc(sf_layout(c, nullptr, world, bm, li, co)));
+        HIPCHK(c, hipStreamSynchronize(c->stream));          // (the old arrays may still be in use)
+        c->sf_meta = std::move(meta);
+        sf_layout(c, c->sf_meta.p, world, c->d_sf_bitmaps, c->d_sf_lists, c->d_sf_counts);
+        c->sf_world = world;
+        c->sf_n.assign(world, 0); c->sf_off.assign((size_t)world + 1, 0);
+    }
+    c->sf_rank = rank;
+    const size_t nb = c->dirty_words * sizeof(unsigned int);
+    HIPCHK(c, hipMemcpyAsync(c->d_sf_bitmaps + (size_t)rank * c->dirty_words, c->d_dirty.p, nb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_dirty.p, 0, nb, c->stream));
+    *bitmaps_dev = c->d_sf_bitmaps; *bitmap_bytes = nb;
+    c->sf_state = 1;
+    return QS_OK;
+}
+
+extern "C" int qs_sparse_fuse_plan(qs_ctx *c, uint32_t *n_blocks, size_t *offsets, void **payload_dev, size_t *block_bytes)
+{
+    ARGCHK(c, c != nullptr && n_blocks != nullptr && offsets != nullptr && payload_dev != nullptr);
+    if (c->sf_state != 1) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_plan: call qs_sparse_fuse_begin (and all-gather the bitmaps) first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, qs_launch_sf_lists(c));
+    HIPCHK(c, hipMemcpyAsync(c->sf_n.data(), c->d_sf_counts, (size_t)c->sf_world * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bb = qs_sf_block_bytes(c);
+    size_t run = 0;
+    for (int s = 0; s < c->sf_world; s++) { c->sf_off[s] = run; run += (size_t)c->sf_n[s] * bb; n_blocks[s] = c->sf_n[s]; offsets[s] = c->sf_off[s]; }
+    c->sf_off[c->sf_world] = run; offsets[c->sf_world] = run;
+    HIPCHK(c, c->sf_payload.reserve(run, c->stream, (size_t)1 << 20));        // doubling from 1 MiB
+    HIPCHK(c, qs_launch_sf_pack(c, c->sf_n[c->sf_rank], c->sf_payload.p + c->sf_off[c->sf_rank]));
+    *payload_dev = c->sf_payload.p;
+    if (block_bytes) *block_bytes = bb;
+    c->sf_state = 2;
+    return QS_OK;
+}
+
+extern "C" int qs_sparse_fuse_apply(qs_ctx *c)
+{
+    ARGCHK(c, c != nullptr);
+    if (c->sf_state != 2) return qs_fail(c, QS_E_STATE, "qs_sparse_fuse_apply: call qs_sparse_fuse_plan (and exchange the segments) first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, qs_launch_sf_apply(c));
+    c->sf_state = 0;
+    c->dirty_since_fuse = false;
+    if (c->d_counts.p) c->counts_view_fused = true;
+    return QS_OK;
 }

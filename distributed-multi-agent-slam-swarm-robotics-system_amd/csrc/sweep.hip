@@ -15,6 +15,9 @@
 //                           rays longer than a tile go to the grid directly (as qs_rays_kernel)
 //   qs_sweep_direct_kernel  the whole cast with one global atomic per cell (small calls, raycast_mode 1)
 // A sweep adds no pose-graph node, landmark, EKF step or zone point: those belong to the 42 / 41-byte path.
+#include <math.h>
+#include <algorithm>
+
 #include "raycast_tiled.h"
 #include "raycast_common.h"
 
@@ -149,7 +152,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
                 const unsigned int key_free = (unsigned int)((a.ord_base + r + 1) << 1);
                 QsLine ln;
                 if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, h.rx, h.ry, h.yaw, df, key_free, i)) {
-                    // the host decides this beam's cells (qs_api.hip: flush_edge_rays)
+                    // the host decides this beam's cells (qs_api.hip: sync_host_state)
                 } else if (qs_line_setup(ray, h.rx, h.ry, geo, ln)) {
                     if (ln.dx < QT_TILE && ln.dy < QT_TILE) {
                         int tx_lo, tx_hi, ty_lo, ty_hi;
@@ -219,7 +222,7 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
                 const unsigned int key_free = (unsigned int)((a.ord_base + QS_SWEEP_SLOTS * k + i + 1) << 1);
                 QsLine ln;
                 if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, h.rx, h.ry, h.yaw, df, key_free, i)) {
-                    // the host decides this beam's cells (qs_api.hip: flush_edge_rays)
+                    // the host decides this beam's cells (qs_api.hip: sync_host_state)
                 } else if (qs_line_setup(ray, h.rx, h.ry, geo, ln)) {
                     my_cells += qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
                 }
@@ -241,8 +244,9 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
-                            uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid)
+// n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
+static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
+                                   uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid)
 {
     if (n == 0) return hipSuccess;
     QsSweepArgs a;
@@ -287,4 +291,115 @@ hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, si
     t_rays.stop();
     // slot r = 184 k + i has stamp ordinal ord_base + 4 (r >> 2) + (r & 3) + 1 = ord_base + r + 1: the 4-ray layout's
     return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);
+}
+
+// ---- C ABI: servo sweeps (semantics in include/quasar_slam.h) --------------------------------------------------------
+// Records per chunk: the tiled raycast's ray slots (8 B) and tile records (up to 4 x 8 B) of one chunk, 184 slots per
+// record, stay under 0.5 GiB; the host path stages one chunk's records at a time.
+static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
+
+static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
+{
+    if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
+        return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
+    if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
+        return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: sharded contexts (seq_stride > 1, shard_bots > 0) do not take sweeps");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (seq0 == UINT64_MAX) seq0 = c->next_seq;
+    c->last_n = 0; c->last_has_poses = false;              // qs_last_batch / qs_last_hits: length mismatch from here on
+    c->last_sweeps = false; c->last_sweeps_n = 0;
+    if (n == 0) return QS_OK;
+    int rc = ensure_batch(c, 1);                           // the exact-trig waiting list lives with the batch buffers
+    if (rc != QS_OK) return rc;
+    HIPCHK(c, c->sweep_acc.reserve(n, c->stream, 1024));
+    HIPCHK(c, c->sweep_pose.reserve(3 * n, c->stream, 3 * 1024));
+    HIPCHK(c, c->sweep_hv.reserve(QS_SWEEP_SLOTS * std::min(n, QS_SWEEP_CHUNK), c->stream));
+    return QS_OK;
+}
+
+// records [k0, k0 + m) of the call, at d_pkts (already offset to record k0)
+static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0)
+{
+    const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
+    int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
+    if (rc != QS_OK) return rc;
+    // auto: by ray slots, as the 4-ray path decides by its 4 rays per packet
+    const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
+    StageTimer t(c, QS_STAGE_RAYCAST);
+    HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p));
+    t.stop();
+    c->dirty_since_fuse = true;
+    return QS_OK;
+}
+
+static void sweeps_end(qs_ctx *c, size_t n, uint64_t seq0)
+{
+    if (c->b.edge) c->edge_maybe = true;                   // resolved at the next point the map is observed (sync_host_state)
+    c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
+    c->last_sweeps = true; c->last_sweeps_n = n;
+}
+
+extern "C" int qs_ingest_sweeps_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stride, const uint16_t *d_lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || d_pkts != nullptr);
+    int rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0);
+        if (rc != QS_OK) return rc;
+    }
+    sweeps_end(c, n, seq0);
+    return QS_OK;
+}
+
+extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || pkts != nullptr);
+    int rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+        Staging s;
+        rc = reserve_staging(c, m * stride, s);            // (stream-ordered: the previous chunk's kernels have read theirs)
+        if (rc != QS_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0);
+        if (rc != QS_OK) return rc;
+    }
+    sweeps_end(c, n, seq0);
+    // as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
+    return sync_host_state(c, true);
+}
+
+extern "C" int qs_last_sweeps(qs_ctx *c, uint8_t *accepted, double *pose, size_t n)
+{
+    ARGCHK(c, c != nullptr);
+    if (!c->last_sweeps || n != c->last_sweeps_n) return qs_fail(c, QS_E_INVAL, "qs_last_sweeps: n does not match the last sweep ingest");
+    if (n == 0) return QS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint8_t> acc(n);
+    std::vector<double> p(pose ? 3 * n : 0);
+    HIPCHK(c, hipMemcpyAsync(acc.data(), c->sweep_acc.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (pose) HIPCHK(c, hipMemcpyAsync(p.data(), c->sweep_pose.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i++) {
+        if (accepted) accepted[i] = acc[i];
+        if (pose) for (int q = 0; q < 3; q++) pose[3 * i + q] = acc[i] ? p[3 * i + q] : NAN;
+    }
+    return QS_OK;
+}
+
+extern "C" int qs_set_sweep_filter(qs_ctx *c, double smin, double smax)
+{
+    ARGCHK(c, c != nullptr);
+    if (!(isfinite(smin) && isfinite(smax) && smin >= 0 && smin < smax))
+        return qs_fail(c, QS_E_INVAL, "qs_set_sweep_filter: need finite 0 <= smin < smax");
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);                                            // waiting beams are resolved with the filter they were cast with
+    c->sweep_min = smin; c->sweep_max = smax;
+    return QS_OK;
 }

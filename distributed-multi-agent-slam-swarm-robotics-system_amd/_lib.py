@@ -26,6 +26,19 @@ class QsPlanParams(C.Structure):
     _fields_ = [("clearance", C.c_int32), ("snap_radius", C.c_int32), ("lookahead", C.c_int32), ("reserved", C.c_int32)]
 
 
+class QsMatchParams(C.Structure):
+    """struct qs_match_params (include/quasar_slam.h)."""
+    _fields_ = [("radius", C.c_int32), ("window", C.c_int32), ("angle_steps", C.c_int32), ("min_hits", C.c_int32),
+                ("min_percent", C.c_int32), ("reserved", C.c_int32), ("angle_step", C.c_double)]
+
+
+class QsSweepMatch(C.Structure):
+    """struct qs_sweep_match (include/quasar_slam.h)."""
+    _fields_ = [("ix", C.c_int32), ("iy", C.c_int32), ("it", C.c_int32), ("score", C.c_int32), ("score0", C.c_int32),
+                ("hits", C.c_int32), ("accepted_record", C.c_uint8), ("accepted_match", C.c_uint8), ("pad", C.c_uint8 * 6),
+                ("dx", C.c_double), ("dy", C.c_double), ("dyaw", C.c_double)]
+
+
 class QsConfig(C.Structure):
     """struct qs_config (include/quasar_slam.h)."""
     _fields_ = [
@@ -89,6 +102,12 @@ SIGNATURES = {
     "qs_ingest_sweeps_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_last_sweeps": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_set_sweep_filter": (_i32, [_vp, _f64, _f64]),
+    "qs_match_field": (_i32, [_vp, _i32, _vp]),
+    "qs_match_sweeps": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "qs_match_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "qs_ingest_sweeps_matched": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_ingest_sweeps_matched_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_last_sweep_matches": (_i32, [_vp, _vp, _sz]),
     "qs_last_hits": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),

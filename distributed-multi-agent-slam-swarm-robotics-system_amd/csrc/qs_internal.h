@@ -275,6 +275,10 @@ struct qs_ctx {
     double sweep_min = 0.1, sweep_max = 1.2;     //   trust filter smin < d <= smax (qs_set_sweep_filter)
     size_t last_sweeps_n = 0;
     bool last_sweeps = false;                    //   the last ingest was qs_ingest_sweeps*: qs_last_sweeps may read it
+    DevBuf<double> match_tab;                    // sweep matching (match.hip): cos, sin of the 181 beam angles, from the host's libm
+    DevBuf<qs_sweep_match> match_out;            //   ... the matches of the last matched ingest (qs_last_sweep_matches)
+    size_t last_matches_n = 0;
+    bool last_matches = false;
 
     uint64_t next_seq = 0, epoch_base = 0, n_rebases = 0;
     DevBuf<unsigned int> d_flags;                // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)
@@ -379,6 +383,12 @@ hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axi
 // raycast_tiled.hip
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
 bool qs_tiled_supported(const qs_ctx *c);
+// match.hip: the parameters of one matching call, checked against the context's sweep filter and resolution
+struct QsMatchSetup { int R, W, T, min_hits, min_percent, reach; double step; };
+int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, QsMatchSetup &ms);
+// n device-resident records matched against the map as the stream finds it; rot (optional): [n][2 T + 1][2] the (sin, cos) used
+hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,
+                           const unsigned short *d_lens, qs_sweep_match *out, double *rot);
 // grid_ops.hip
 hipError_t qs_launch_rebase(qs_ctx *c);
 hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,

@@ -15,74 +15,16 @@
 //                           rays longer than a tile go to the grid directly (as qs_rays_kernel)
 //   qs_sweep_direct_kernel  the whole cast with one global atomic per cell (small calls, raycast_mode 1)
 // A sweep adds no pose-graph node, landmark, EKF step or zone point: those belong to the 42 / 41-byte path.
+// The matched ingest (qs_ingest_sweeps_matched*, at the end of this file) runs match.hip's kernel over the whole call and then
+// these kernels' CORR instantiations, which add each record's correction to its pose before anything else.
 #include <math.h>
 #include <algorithm>
 
 #include "raycast_tiled.h"
 #include "raycast_common.h"
+#include "sweep_common.h"
 
-#define SW_DW 192                 // LDS dwords per staged record: >= (3 + 751 + 3) / 4 + 1 (the alignbyte reads one dword ahead)
 #define SW_DIRECT_BLOCK 256       // direct kernel: 4 records per workgroup
-#define SW_MAGIC 0x4c525351u      // 'Q','S','R','L'
-
-struct QsSweepArgs {
-    const unsigned char *pkts;    // record k at pkts + k * stride (this chunk)
-    size_t n, stride;
-    const unsigned short *lens;   // [n] or nullptr (every length == stride)
-    unsigned int ranges_off;      // byte offset of r_0: 19 (v0) or 27 (v0 + odometry)
-    int max_agent;
-    const double *offset, *drift; // [max_agent + 1], [max_agent + 1][2]: read on the device, after every earlier launch
-    double smin, smax;            // trust filter: smin < d <= smax
-    unsigned char *accept;        // [n] out
-    double *pose;                 // [n][3] out: rx, ry, yaw of accepted records
-    unsigned long long ord_base;  // 4 * (seq0 - epoch_base) of record 0
-};
-
-// the record's dwords [addr & ~3, addr + stride) into s[0 .. 191]; dwords that reach outside the caller's buffer (its first and
-// last bytes need not be dword-aligned) are read bytewise
-__device__ inline void sw_stage(const QsSweepArgs &a, size_t k, unsigned int *s, int lane)
-{
-    const unsigned long long base = (unsigned long long)a.pkts, end = base + a.n * a.stride;
-    const unsigned long long addr0 = base + k * a.stride, w0 = addr0 & ~3ull;
-    unsigned int v[3];
-    #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const unsigned long long p = w0 + 4ull * (unsigned long long)(lane + QS_WAVE * q);
-        v[q] = 0;
-        if (k < a.n && p < addr0 + a.stride) {
-            if (p >= base && p + 4 <= end) v[q] = *(const unsigned int *)p;
-            else
-                for (int j = 0; j < 4; j++)
-                    if (p + j >= base && p + j < end) v[q] |= (unsigned int)*(const unsigned char *)(p + j) << (8 * j);
-        }
-    }
-    #pragma unroll
-    for (int q = 0; q < 3; q++) s[lane + QS_WAVE * q] = v[q];
-}
-
-// little-endian u32 at byte o of the staged record (mis = the record's start within its first dword)
-__device__ inline unsigned int sw_u32(const unsigned int *s, unsigned int mis, unsigned int o)
-{
-    const unsigned int b = mis + o;
-    return __builtin_amdgcn_alignbyte(s[(b >> 2) + 1], s[b >> 2], b & 3u);
-}
-
-struct SwHead { bool ok; double rx, ry, yaw; };
-
-__device__ inline SwHead sw_head(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
-{
-    SwHead h{false, 0.0, 0.0, 0.0};
-    const int len = a.lens ? (int)a.lens[k] : (int)a.stride;
-    const int agent = (int)(sw_u32(s, mis, 4) & 0xffu);
-    h.ok = len == (int)a.stride && sw_u32(s, mis, 0) == SW_MAGIC && agent >= 1 && agent <= a.max_agent;
-    if (h.ok) {
-        const float x = __uint_as_float(sw_u32(s, mis, 5)), y = __uint_as_float(sw_u32(s, mis, 9));
-        h.rx = ((double)x + a.offset[agent]) + a.drift[2 * agent];      // offset first, then drift (:851-857)
-        h.ry = (double)y + a.drift[2 * agent + 1];
-        h.yaw = (double)__uint_as_float(sw_u32(s, mis, 13));
-    }
-    return h;
-}
 
 // beam i: angle ryaw + math.radians(i - 90) -- CPython's radians is x * (pi / 180), one multiply and one add (no FMA: the
 // library is built with -ffp-contract=off); hit and free-ray rule as qs_project_ray's (A6): NaN, 0 and negative ranges give
@@ -110,7 +52,8 @@ __device__ inline void sw_out(const QsSweepArgs &a, size_t k, const SwHead &h)
 // ---- pass A of the tiled raycast -----------------------------------------------------------------------------------------
 // Workgroup w owns records [w * pk_per_wg, (w + 1) * pk_per_wg) (pk_per_wg a multiple of 16), its 16 waves one record each per
 // round, and writes ray slots [184 * that range) plus its row of the tile table.
-template <bool COUNTS>
+// CORR: the matched ingest's instantiation (every pose gets its record's correction first); the plain ingest's is CORR = false
+template <bool COUNTS, bool CORR>
 __global__ void __launch_bounds__(QT_BIN_BLOCK)
 qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsigned char *__restrict__ hit_valid,
                      unsigned int *__restrict__ stamps, unsigned long long *__restrict__ counts,
@@ -134,7 +77,8 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
         if (k >= k1) continue;
         const unsigned int *s = s_rec[wave];
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
-        const SwHead h = sw_head(a, k, s, mis);
+        SwHead h = sw_head(a, k, s, mis);
+        if (CORR) sw_correct(a, k, h);
         if (lane == 0) { sw_out(a, k, h); my_acc += h.ok ? 1u : 0u; }
         #pragma unroll
         for (int q = 0; q < 3; q++) {
@@ -191,7 +135,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
 }
 
 // ---- direct form: one wave per record, every cell one global atomic --------------------------------------------------------
-template <bool COUNTS>
+template <bool COUNTS, bool CORR>
 __global__ void __launch_bounds__(SW_DIRECT_BLOCK)
 qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__restrict__ stamps,
                        unsigned long long *__restrict__ counts, unsigned long long *__restrict__ counters)
@@ -208,7 +152,8 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
     if (k < a.n) {
         const unsigned int *s = s_rec[wave];
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
-        const SwHead h = sw_head(a, k, s, mis);
+        SwHead h = sw_head(a, k, s, mis);
+        if (CORR) sw_correct(a, k, h);
         if (lane == 0) { sw_out(a, k, h); if (h.ok) atomicAdd(&s_cnt[3], 1u); }
         if (h.ok) {
             #pragma unroll
@@ -245,25 +190,16 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
-static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
-                                   uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid)
+template <bool CORR>
+static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, bool tiled, unsigned char *hit_valid)
 {
-    if (n == 0) return hipSuccess;
-    QsSweepArgs a;
-    a.pkts = d_pkts; a.n = n; a.stride = stride; a.lens = d_lens;
-    a.ranges_off = stride == QS_SWEEP_SIZE_V0 ? 19u : 27u;
-    a.max_agent = c->cfg.max_agent;
-    a.offset = c->d_offset.p; a.drift = c->d_drift.p;
-    a.smin = c->sweep_min; a.smax = c->sweep_max;
-    a.accept = accept; a.pose = pose;
-    a.ord_base = 4ull * (seq0 - c->epoch_base);
     if (!tiled || !qs_tiled_supported(c)) {
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
         if (c->cfg.enable_counts)
-            hipLaunchKernelGGL(qs_sweep_direct_kernel<true>, dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
+            hipLaunchKernelGGL((qs_sweep_direct_kernel<true, CORR>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
                                c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         else
-            hipLaunchKernelGGL(qs_sweep_direct_kernel<false>, dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
+            hipLaunchKernelGGL((qs_sweep_direct_kernel<false, CORR>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
                                c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         return hipGetLastError();
     }
@@ -277,20 +213,46 @@ static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_
     ws.pk_per_wg = per;
     ws.rays_per_wg = QS_SWEEP_SLOTS * per;
     ws.nwg = (int)((n + per - 1) / per);
-    const void *pass_a[2] = {(const void *)qs_sweep_rays_kernel<true>, (const void *)qs_sweep_rays_kernel<false>};
+    const void *pass_a[2] = {(const void *)qs_sweep_rays_kernel<true, CORR>, (const void *)qs_sweep_rays_kernel<false, CORR>};
     size_t lds = 0;
     e = qt_dyn_lds(ws, pass_a, 2, lds);
     if (e != hipSuccess) return e;
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
     if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_sweep_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
+        hipLaunchKernelGGL((qs_sweep_rays_kernel<true, CORR>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
                            hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     else
-        hipLaunchKernelGGL(qs_sweep_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
+        hipLaunchKernelGGL((qs_sweep_rays_kernel<false, CORR>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
                            hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     t_rays.stop();
     // slot r = 184 k + i has stamp ordinal ord_base + 4 (r >> 2) + (r & 3) + 1 = ord_base + r + 1: the 4-ray layout's
     return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);
+}
+
+// what every sweep kernel reads of the context (match.hip fills its own with it too)
+void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, QsSweepArgs &a)
+{
+    a.pkts = d_pkts; a.n = n; a.stride = stride; a.lens = d_lens;
+    a.ranges_off = stride == QS_SWEEP_SIZE_V0 ? 19u : 27u;
+    a.max_agent = c->cfg.max_agent;
+    a.offset = c->d_offset.p; a.drift = c->d_drift.p;
+    a.smin = c->sweep_min; a.smax = c->sweep_max;
+    a.accept = nullptr; a.pose = nullptr; a.ord_base = 0; a.corr = nullptr;
+}
+
+// n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]; corr: the
+// matched ingest's corrections of these records, nullptr for the plain ingest
+static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
+                                   uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid,
+                                   const qs_sweep_match *corr)
+{
+    if (n == 0) return hipSuccess;
+    QsSweepArgs a;
+    qs_sweep_args(c, d_pkts, n, stride, d_lens, a);
+    a.accept = accept; a.pose = pose;
+    a.ord_base = 4ull * (seq0 - c->epoch_base);
+    a.corr = corr;
+    return corr ? qs_launch_sweeps_t<true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false>(c, a, n, tiled, hit_valid);
 }
 
 // ---- C ABI: servo sweeps (semantics in include/quasar_slam.h) --------------------------------------------------------
@@ -300,6 +262,7 @@ static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
 
 static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 {
+    c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
     if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
     if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
@@ -318,7 +281,8 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 }
 
 // records [k0, k0 + m) of the call, at d_pkts (already offset to record k0)
-static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0)
+static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0,
+                        const qs_sweep_match *corr = nullptr)
 {
     const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
     int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
@@ -326,7 +290,8 @@ static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t strid
     // auto: by ray slots, as the 4-ray path decides by its 4 rays per packet
     const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
     StageTimer t(c, QS_STAGE_RAYCAST);
-    HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p));
+    HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p,
+                               corr));
     t.stop();
     c->dirty_since_fuse = true;
     return QS_OK;
@@ -372,6 +337,72 @@ extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t
     }
     sweeps_end(c, n, seq0);
     // as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
+    return sync_host_state(c, true);
+}
+
+// ---- matched ingest (semantics in include/quasar_slam.h, "sweep matching"): every record of the call is matched against the
+// map as it stands before the call (match.hip), then the records are mapped chunk by chunk from their corrected poses
+static int matched_begin(qs_ctx *c, const qs_match_params *params, size_t n, size_t stride, uint64_t &seq0, QsMatchSetup &ms)
+{
+    int rc = qs_match_setup(c, params, "qs_ingest_sweeps_matched", ms);
+    if (rc != QS_OK) return rc;
+    rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
+    SYNCCHK(c);                                            // the matcher reads the map: waiting edge beams go in first
+    return QS_OK;
+}
+
+static void matched_end(qs_ctx *c, size_t n, uint64_t seq0)
+{
+    sweeps_end(c, n, seq0);
+    c->last_matches = true; c->last_matches_n = n;
+}
+
+extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                               const uint16_t *d_lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || d_pkts != nullptr);
+    QsMatchSetup ms;
+    int rc = matched_begin(c, params, n, stride, seq0, ms);
+    if (rc != QS_OK || n == 0) return rc;
+    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, c->match_out.p, nullptr));
+    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, c->match_out.p + k0);
+        if (rc != QS_OK) return rc;
+    }
+    matched_end(c, n, seq0);
+    return QS_OK;
+}
+
+extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                                        const uint16_t *lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || pkts != nullptr);
+    QsMatchSetup ms;
+    int rc = matched_begin(c, params, n, stride, seq0, ms);
+    if (rc != QS_OK || n == 0) return rc;
+    // the staging block holds one chunk: a call of several chunks stages each of them twice, first to match them all against
+    // the map nobody has written yet, then to map them
+    const bool one = n <= QS_SWEEP_CHUNK;
+    for (int pass = one ? 1 : 0; pass < 2; pass++)
+        for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+            const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+            Staging s;
+            rc = reserve_staging(c, m * stride, s);        // (stream-ordered: the previous chunk's kernels have read theirs)
+            if (rc != QS_OK) return rc;
+            HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
+            if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+            if (pass == 0 || one) HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, c->match_out.p + k0, nullptr));
+            if (pass == 1) {
+                rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, c->match_out.p + k0);
+                if (rc != QS_OK) return rc;
+            }
+        }
+    matched_end(c, n, seq0);
     return sync_host_state(c, true);
 }
 

@@ -1,0 +1,79 @@
+// sweep_common.h -- a servo-sweep record on the device: staging and header parse shared by the sweep mapper (sweep.hip) and
+// the sweep matcher (match.hip).
+#pragma once
+#include "raycast_common.h"
+
+#define SW_DW 192                 // LDS dwords per staged record: >= (3 + 751 + 3) / 4 + 1 (the alignbyte reads one dword ahead)
+#define SW_MAGIC 0x4c525351u      // 'Q','S','R','L'
+
+struct QsSweepArgs {
+    const unsigned char *pkts;    // record k at pkts + k * stride (this chunk)
+    size_t n, stride;
+    const unsigned short *lens;   // [n] or nullptr (every length == stride)
+    unsigned int ranges_off;      // byte offset of r_0: 19 (v0) or 27 (v0 + odometry)
+    int max_agent;
+    const double *offset, *drift; // [max_agent + 1], [max_agent + 1][2]: read on the device, after every earlier launch
+    double smin, smax;            // trust filter: smin < d <= smax
+    unsigned char *accept;        // [n] out
+    double *pose;                 // [n][3] out: rx, ry, yaw of accepted records
+    unsigned long long ord_base;  // 4 * (seq0 - epoch_base) of record 0
+    const qs_sweep_match *corr;   // [n] matched ingest only (the kernels' CORR instantiations): the correction of each record
+};
+
+// sweep.hip: everything of a that comes from the context (filter, offsets, drift); outputs and corr empty
+void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, QsSweepArgs &a);
+
+// the record's dwords [addr & ~3, addr + stride) into s[0 .. 191]; dwords that reach outside the caller's buffer (its first and
+// last bytes need not be dword-aligned) are read bytewise
+__device__ inline void sw_stage(const QsSweepArgs &a, size_t k, unsigned int *s, int lane)
+{
+    const unsigned long long base = (unsigned long long)a.pkts, end = base + a.n * a.stride;
+    const unsigned long long addr0 = base + k * a.stride, w0 = addr0 & ~3ull;
+    unsigned int v[3];
+    #pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const unsigned long long p = w0 + 4ull * (unsigned long long)(lane + QS_WAVE * q);
+        v[q] = 0;
+        if (k < a.n && p < addr0 + a.stride) {
+            if (p >= base && p + 4 <= end) v[q] = *(const unsigned int *)p;
+            else
+                for (int j = 0; j < 4; j++)
+                    if (p + j >= base && p + j < end) v[q] |= (unsigned int)*(const unsigned char *)(p + j) << (8 * j);
+        }
+    }
+    #pragma unroll
+    for (int q = 0; q < 3; q++) s[lane + QS_WAVE * q] = v[q];
+}
+
+// little-endian u32 at byte o of the staged record (mis = the record's start within its first dword)
+__device__ inline unsigned int sw_u32(const unsigned int *s, unsigned int mis, unsigned int o)
+{
+    const unsigned int b = mis + o;
+    return __builtin_amdgcn_alignbyte(s[(b >> 2) + 1], s[b >> 2], b & 3u);
+}
+
+struct SwHead { bool ok; double rx, ry, yaw; };
+
+__device__ inline SwHead sw_head(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
+{
+    SwHead h{false, 0.0, 0.0, 0.0};
+    const int len = a.lens ? (int)a.lens[k] : (int)a.stride;
+    const int agent = (int)(sw_u32(s, mis, 4) & 0xffu);
+    h.ok = len == (int)a.stride && sw_u32(s, mis, 0) == SW_MAGIC && agent >= 1 && agent <= a.max_agent;
+    if (h.ok) {
+        const float x = __uint_as_float(sw_u32(s, mis, 5)), y = __uint_as_float(sw_u32(s, mis, 9));
+        h.rx = ((double)x + a.offset[agent]) + a.drift[2 * agent];      // offset first, then drift (:851-857)
+        h.ry = (double)y + a.drift[2 * agent + 1];
+        h.yaw = (double)__uint_as_float(sw_u32(s, mis, 13));
+    }
+    return h;
+}
+
+// matched ingest: the pose the sweep is cast from, rx' = rx + dx, ry' = ry + dy, yaw' = yaw + dyaw (one add each; a match
+// that was not accepted carries zeros, which leave the pose bit for bit)
+__device__ inline void sw_correct(const QsSweepArgs &a, size_t k, SwHead &h)
+{
+    if (!h.ok) return;
+    const qs_sweep_match &m = a.corr[k];
+    h.rx = h.rx + m.dx; h.ry = h.ry + m.dy; h.yaw = h.yaw + m.dyaw;
+}

@@ -256,36 +256,50 @@ class QuasarMapper:
         return xy, valid
 
     # -- servo sweeps (v0 '<4sBfffH181f' / v0 + odometry '<4sBfffiIH181f'; include/quasar_slam.h) --------------------------
-    def ingest_sweeps(self, datagrams, lengths=None, seq0=None):
+    def ingest_sweeps(self, datagrams, lengths=None, seq0=None, match=None):
         """Map servo-sweep packets: a list of bytes objects (one format: 743 or 751 bytes; other lengths are dropped) or a
-        uint8 [n, 743 | 751] array with optional uint16 lengths.  Sweep k uses sequence numbers seq0 + 46 k ... + 45."""
+        uint8 [n, 743 | 751] array with optional uint16 lengths.  Sweep k uses sequence numbers seq0 + 46 k ... + 45.
+        match: True (default parameters) or what match_params takes -- every sweep of the call is first matched against
+        the map as it stands and mapped from its corrected pose (qs_ingest_sweeps_matched); last_sweep_matches() has the
+        matches.  None or False: the plain ingest."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        return self._sweeps_call(buf, lengths, seq0, match)
+
+    @staticmethod
+    def _sweep_buffer(datagrams, lengths):
         if isinstance(datagrams, np.ndarray):
             buf = np.ascontiguousarray(datagrams, dtype=np.uint8)
             if buf.ndim != 2:
                 raise ValueError("sweeps must be [n, stride]")
-        else:
-            if len(datagrams) == 0:
-                self._sweeps_call(np.zeros((0, P.PACKET_SIZE_V0_ODO), np.uint8), None, seq0)
-                return 0
-            sizes = {len(d) for d in datagrams} & {P.PACKET_SIZE_V0, P.PACKET_SIZE_V0_ODO}
-            if len(sizes) > 1:
-                raise ValueError("one sweep format per call: 743- and 751-byte records mixed")
-            stride = sizes.pop() if sizes else P.PACKET_SIZE_V0_ODO
-            buf = np.zeros((len(datagrams), stride), dtype=np.uint8)
-            lengths = np.zeros(len(datagrams), dtype=np.uint16)
-            for i, d in enumerate(datagrams):
-                m = min(len(d), stride)
-                buf[i, :m] = np.frombuffer(d[:m], dtype=np.uint8)
-                lengths[i] = min(len(d), 65535)
-        return self._sweeps_call(buf, lengths, seq0)
+            return buf, lengths
+        if len(datagrams) == 0:
+            return np.zeros((0, P.PACKET_SIZE_V0_ODO), np.uint8), None
+        sizes = {len(d) for d in datagrams} & {P.PACKET_SIZE_V0, P.PACKET_SIZE_V0_ODO}
+        if len(sizes) > 1:
+            raise ValueError("one sweep format per call: 743- and 751-byte records mixed")
+        stride = sizes.pop() if sizes else P.PACKET_SIZE_V0_ODO
+        buf = np.zeros((len(datagrams), stride), dtype=np.uint8)
+        lengths = np.zeros(len(datagrams), dtype=np.uint16)
+        for i, d in enumerate(datagrams):
+            m = min(len(d), stride)
+            buf[i, :m] = np.frombuffer(d[:m], dtype=np.uint8)
+            lengths[i] = min(len(d), 65535)
+        return buf, lengths
 
-    def _sweeps_call(self, buf, lengths, seq0):
+    def _sweeps_call(self, buf, lengths, seq0, match=None):
         n, stride = buf.shape
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
         if lens is not None and len(lens) != n:
             raise ValueError("lengths must have one entry per record")
-        self._chk(self._L.qs_ingest_sweeps(self._h, _ptr(buf) if n else None, n, stride, _ptr(lens),
-                                           UINT64_MAX if seq0 is None else int(seq0)), "qs_ingest_sweeps")
+        seq = UINT64_MAX if seq0 is None else int(seq0)
+        if match is None or match is False:
+            self._chk(self._L.qs_ingest_sweeps(self._h, _ptr(buf) if n else None, n, stride, _ptr(lens), seq), "qs_ingest_sweeps")
+            self._last_matches_n = None
+        else:
+            prm = self.match_params(match)
+            self._chk(self._L.qs_ingest_sweeps_matched(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens), seq),
+                      "qs_ingest_sweeps_matched")
+            self._last_matches_n = n
         self._map_version += 1
         self._last_n = 0
         self._last_sweeps_n = n
@@ -299,6 +313,73 @@ class QuasarMapper:
         self._map_version += 1
         self._last_n = 0
         self._last_sweeps_n = n
+        self._last_matches_n = None
+
+    # -- sweep matching (include/quasar_slam.h, "sweep matching") -----------------------------------------------------------
+    @staticmethod
+    def match_params(params=None, **kw):
+        """A qs_match_params from None / True (the defaults of protocol.MATCH_*), a dict of its fields, or one already built."""
+        if isinstance(params, _lib.QsMatchParams):
+            return params
+        d = dict(radius=P.MATCH_RADIUS, window=P.MATCH_WINDOW, angle_steps=P.MATCH_ANGLE_STEPS, min_hits=P.MATCH_MIN_HITS,
+                 min_percent=P.MATCH_MIN_PERCENT, angle_step=P.MATCH_ANGLE_STEP)
+        if isinstance(params, dict):
+            d.update(params)
+        elif params not in (None, True):
+            raise TypeError("match parameters: None, True, a dict or a QsMatchParams")
+        d.update(kw)
+        return _lib.QsMatchParams(radius=int(d["radius"]), window=int(d["window"]), angle_steps=int(d["angle_steps"]),
+                                  min_hits=int(d["min_hits"]), min_percent=int(d["min_percent"]), reserved=0,
+                                  angle_step=float(d["angle_step"]))
+
+    def match_field(self, radius=P.MATCH_RADIUS):
+        """The likelihood field of the whole grid, uint8 [size, size]: max(0, radius + 1 - Chebyshev distance to the nearest
+        occupied cell)."""
+        out = np.empty((self.size, self.size), dtype=np.uint8)
+        self._chk(self._L.qs_match_field(self._h, int(radius), _ptr(out)), "qs_match_field")
+        return out
+
+    def match_sweeps(self, datagrams, lengths=None, params=None, rotations=False):
+        """Match sweeps (as ingest_sweeps takes them) against the map without mapping them or changing anything: a structured
+        array of protocol.MATCH_DTYPE, one entry per record; with rotations also the (sin, cos) the device used, float64
+        [n, 2 * angle_steps + 1, 2]."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        prm = self.match_params(params)
+        out = np.zeros(n, dtype=P.MATCH_DTYPE)
+        rot = np.zeros((n, 2 * prm.angle_steps + 1, 2), dtype=np.float64) if rotations else None
+        self._chk(self._L.qs_match_sweeps(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                          _ptr(out) if n else None, _ptr(rot) if rotations and n else None), "qs_match_sweeps")
+        return (out, rot) if rotations else out
+
+    def match_sweeps_device(self, d_pkts, n, stride, d_out, d_lens=0, d_rot=0, params=None):
+        """Device-resident match (raw device addresses as ints; d_out: n records of protocol.MATCH_DTYPE); asynchronous."""
+        prm = self.match_params(params)
+        self._chk(self._L.qs_match_sweeps_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                 C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_out),
+                                                 C.c_void_p(d_rot) if d_rot else None), "qs_match_sweeps_device")
+
+    def ingest_sweeps_matched_device(self, d_pkts, n, stride, d_lens=0, seq0=None, params=None):
+        """Device-resident matched ingest (raw device addresses as ints); asynchronous."""
+        prm = self.match_params(params)
+        self._chk(self._L.qs_ingest_sweeps_matched_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                          C.c_void_p(d_lens) if d_lens else None,
+                                                          UINT64_MAX if seq0 is None else int(seq0)),
+                  "qs_ingest_sweeps_matched_device")
+        self._map_version += 1
+        self._last_n = 0
+        self._last_sweeps_n = n
+        self._last_matches_n = n
+
+    def last_sweep_matches(self):
+        """The matches of the last matched sweep ingest (protocol.MATCH_DTYPE [n]); an error after any other ingest."""
+        n = getattr(self, "_last_matches_n", None)
+        out = np.zeros(n or 0, dtype=P.MATCH_DTYPE)
+        self._chk(self._L.qs_last_sweep_matches(self._h, _ptr(out) if n else None, n or 0), "qs_last_sweep_matches")
+        return out
 
     def last_sweeps(self):
         """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after

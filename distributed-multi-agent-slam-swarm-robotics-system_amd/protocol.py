@@ -124,6 +124,16 @@ SWEEP_BEAMS = 181
 SWEEP_SEQS = 46              # sequence numbers one sweep uses in the mapper's stamp order (include/quasar_slam.h)
 SWEEP_MIN_DIST_M = 0.1       # trust filter of the reference's sweep map, generate_topdown_map.py:51
 SWEEP_MAX_DIST_M = 1.2
+# sweep matching (include/quasar_slam.h, "sweep matching"): build choices, there is no reference counterpart
+MATCH_RADIUS = 2             # cells the likelihood field reaches from an occupied cell
+MATCH_WINDOW = 6             # candidate shifts: +- cells on both axes
+MATCH_ANGLE_STEPS = 10       # candidate rotations: +- steps
+MATCH_ANGLE_STEP = math.pi / 180
+MATCH_MIN_HITS = 20          # a sweep with fewer hit beams is not moved
+MATCH_MIN_PERCENT = 50       # ... nor one whose best score is under this share of hits * (radius + 1)
+MATCH_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("it", "<i4"), ("score", "<i4"), ("score0", "<i4"), ("hits", "<i4"),
+                        ("accepted_record", "u1"), ("accepted_match", "u1"), ("pad", "u1", (6,)),
+                        ("dx", "<f8"), ("dy", "<f8"), ("dyaw", "<f8")])
 
 
 def pack_v0(agent, x, y, yaw, ranges, scan_count=SWEEP_BEAMS, magic=b"QSRL") -> bytes:

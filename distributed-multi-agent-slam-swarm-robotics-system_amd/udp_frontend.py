@@ -20,6 +20,9 @@ Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry p
 poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
 each run one ingest call.  No call names its sequence numbers: the mapper continues its own counter across both kinds
 (1 per packet, 46 per sweep), so stamps follow arrival, after whatever the mapper held before (a replayed log, say).  An accepted sweep marks its bot online and sets its pose, as a packet does.
+With match_sweeps=True (opt-in, needs sweeps=True) a run of sweeps is matched against the map before it is mapped
+(QuasarMapper.ingest_sweeps(match=...), match_params its parameters): the bot's pose is then the corrected one, and
+last_matches holds the matches of the latest run.
 Differences: the reference throttles itself to 20 packets per 30 fps frame (:816, :474); here a
 poll drains the socket (up to max_batch datagrams).  Host-side Python only; the mapper can be any
 object with ingest_array / last_batch / zone_packet (tests use a stub, production the HIP mapper).
@@ -37,9 +40,15 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
-                 frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None):
+                 frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
+                 match_params=None):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
+        if match_sweeps and not sweeps:
+            raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
+        self.match_sweeps = match_sweeps
+        self.match_params = dict(match_params) if match_params else True
+        self.last_matches = None
         self.mapper = mapper
         self.plan_paths = plan_paths
         self.plan_params = dict(plan_params or {})
@@ -105,7 +114,11 @@ class MissionControl:
                 accepted, pose = self.mapper.last_batch()
                 self._mark(i0, accepted, pose, now, self.frontier_targets and pose is not None)
             else:
-                self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens)
+                if self.match_sweeps:
+                    self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens, match=self.match_params)
+                    self.last_matches = self.mapper.last_sweep_matches()
+                else:
+                    self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens)
                 accepted, pose = self.mapper.last_sweeps()
                 self._mark(i0, accepted, pose, now, pose is not None)
         return n

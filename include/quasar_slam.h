@@ -148,6 +148,68 @@ int qs_last_sweeps(qs_ctx *ctx, uint8_t *accepted, double *pose_xyyaw /* n x 3 *
 /* trust filter of the sweep beams: a hit when smin < d <= smax (finite, 0 <= smin < smax) */
 int qs_set_sweep_filter(qs_ctx *ctx, double smin, double smax);
 
+/* ---- sweep matching (no reference counterpart: this build's own rule) ------------------------------------------------------
+ * A sweep is matched against the map before it is mapped: a window of candidate poses around the packet's pose is scored
+ * on a likelihood field of the occupied cells, and the best candidate is the correction.  Integers are exact, floating
+ * point is fp64 without contraction, so the device and a CPU restatement (tests/match_rules.py) agree bit for bit once
+ * they share the (sin, cos) of the rotations.
+ *  1. Field: for a radius R in 0..QS_MATCH_MAX_RADIUS, L[gy][gx] = max(0, R + 1 - c), c the Chebyshev distance from
+ *     (gx, gy) to the nearest OCCUPIED cell of the grid (odd stamp; the 100 of qs_grid_i8).  UNKNOWN and FREE are not
+ *     told apart; L = 0 outside the grid.
+ *  2. Candidates (ix, iy, it): |ix|, |iy| <= window (cells), |it| <= angle_steps (steps of angle_step radians).
+ *  3. Per accepted record (qs_ingest_sweeps' acceptance rule): rx, ry as qs_ingest_sweeps forms them (offset first, then
+ *     the bot's drift, read on the device), yaw = f64(packet yaw).  Hit beams: smin < d_i <= smax (the context's sweep
+ *     filter); only they score, H is their number.  Beam in the robot frame: bx_i = d_i * CB[i], by_i = d_i * SB[i], with
+ *     CB, SB the cos / sin of (i - 90) * (pi / 180) from the HOST's libm (uploaded once per context).
+ *     Rotation it: th = yaw + it * angle_step (one multiply, one add), (s, c) = the device's sincos(th): 2 T + 1 per sweep.
+ *     End point ex = rx + (c * bx_i - s * by_i), ey = ry + (s * bx_i + c * by_i), in this association; its cell
+ *     (cx, cy) = world_to_grid (int((w - o) / res), :121-125).  An end point whose quotient is not finite or is beyond
+ *     2^30 cells in magnitude scores 0 (world_to_grid would raise).
+ *     score(ix, iy, it) = sum over hit beams of L[cy + iy][cx + ix]: the translation shifts the look-up, not the pose.
+ *  4. Best candidate: highest score; ties to the smallest ix*ix + iy*iy, then the smallest |it|, then the smaller it, then
+ *     the smaller iy, then the smaller ix.  One total order: the answer is unique.
+ *  5. Gate: accepted_match when H >= min_hits and score * 100 >= min_percent * H * (R + 1).  Then dx = ix * res,
+ *     dy = iy * res, dyaw = it * angle_step (one multiply each); otherwise all three are 0.  ix, iy, it, score report the
+ *     best candidate either way; score0 is the score of (0, 0, 0).  An empty map never moves a sweep.
+ * A rejected record gets zeros throughout (accepted_record = 0).
+ * Limits: radius <= QS_MATCH_MAX_RADIUS, angle_steps <= QS_MATCH_MAX_ANGLE_STEPS, 0 <= min_percent <= 100, angle_step
+ * finite and >= 0, and ceil(smax / res) + window + radius + 2 <= QS_MATCH_MAX_REACH, so that the patch of the field a sweep
+ * can reach is at most 255 cells on a side.  QS_E_INVAL beyond them; the text says which quantity is too large.
+ * params NULL = radius 2, window 6, angle_steps 10, angle_step pi / 180, min_hits 20, min_percent 50.
+ *
+ * qs_match_sweeps* read the map (waiting exact-trig rays are flushed first) and write nothing to the context: no stamps,
+ * counters, dirty blocks or sequence numbers; a checkpoint before equals one after.  rot_out (optional) receives
+ * n x (2 T + 1) x 2 doubles, the (s, c) the device used for it = -T .. T (zeros for rejected records): with them as input
+ * the restatement is exact, whatever the last bit of the device's sincos.
+ *
+ * qs_ingest_sweeps_matched*: ALL records of the call are matched against the map as it stood before the call, however
+ * the call is chunked; then they are mapped by the rules of qs_ingest_sweeps from the corrected pose rx' = rx + dx,
+ * ry' = ry + dy, yaw' = yaw + dyaw (beam angle yaw' + (i - 90) * (pi / 180)).  Stamps, counters, sequence numbers, refusals
+ * as qs_ingest_sweeps; qs_last_sweeps reports the corrected pose, qs_last_sweep_matches the matches (n = the call's n;
+ * QS_E_INVAL after any other ingest).  With exact_trig a beam in the edge band waits for the host with its corrected
+ * pose.  The bot's drift, the pose graphs, the EKF and the zone points are not touched. */
+#define QS_MATCH_MAX_RADIUS 7
+#define QS_MATCH_MAX_ANGLE_STEPS 45
+#define QS_MATCH_MAX_REACH 127
+typedef struct qs_match_params { int32_t radius, window, angle_steps, min_hits, min_percent, reserved; double angle_step; } qs_match_params;
+typedef struct qs_sweep_match {
+    int32_t ix, iy, it, score, score0, hits;
+    uint8_t accepted_record, accepted_match, pad[6];
+    double dx, dy, dyaw;
+} qs_sweep_match;
+/* rule 1 for the whole grid: field_host[gy*size + gx] (tests and tools) */
+int qs_match_field(qs_ctx *ctx, int32_t radius, uint8_t *field_host);
+int qs_match_sweeps(qs_ctx *ctx, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                    const uint16_t *lens, qs_sweep_match *out, double *rot_out);
+/* same with device-resident pkts / lens / out / rot_out; asynchronous on the context's stream */
+int qs_match_sweeps_device(qs_ctx *ctx, const qs_match_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                           const uint16_t *d_lens, qs_sweep_match *d_out, double *d_rot_out);
+int qs_ingest_sweeps_matched(qs_ctx *ctx, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                             const uint16_t *lens, uint64_t seq0);
+int qs_ingest_sweeps_matched_device(qs_ctx *ctx, const qs_match_params *params, const uint8_t *d_pkts, size_t n,
+                                    size_t stride, const uint16_t *d_lens, uint64_t seq0);
+int qs_last_sweep_matches(qs_ctx *ctx, qs_sweep_match *out, size_t n);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

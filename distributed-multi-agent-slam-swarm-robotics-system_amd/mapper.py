@@ -231,7 +231,11 @@ class QuasarMapper:
         return n
 
     def ingest_device(self, d_pkts, n, stride, d_lens=0, d_time=0, seq0=None):
-        """Device-resident input (raw device addresses as ints); asynchronous."""
+        """Device-resident input (raw device addresses as ints): n records, record k at d_pkts + k * stride, stride >= 41.
+        d_pkts may be any byte address (the decoder reads only the n * stride bytes given); d_lens (uint16 [n], 0 = every
+        length is the stride) and d_time (float64 [n], 0 = none) must be aligned to their element size.  Asynchronous on the
+        context's stream: the buffers must be written before the call (for that stream) and stay alive and unchanged until
+        the work has run (sync(), or any call that waits for the stream)."""
         self._chk(self._L.qs_ingest_device(self._h, C.c_void_p(d_pkts), n, stride,
                                            C.c_void_p(d_lens) if d_lens else None,
                                            C.c_void_p(d_time) if d_time else None,

@@ -157,6 +157,8 @@ SIGNATURES = {
     "qs_traversable": (_i32, [_vp, _i32, _vp]),
     "qs_plan_field": (_i32, [_vp, _vp, _vp, _vp]),
     "qs_plan_paths": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "qs_frontier_targets_by_path": (_i32, [_vp, _i32, _f64, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                           C.POINTER(_sz), _vp]),
     "qs_ekf_init": (_i32, [_vp, _i32, _f64, _vp]),
     "qs_ekf_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32]),
     "qs_ekf_state": (_i32, [_vp, _i32, _vp, _vp]),

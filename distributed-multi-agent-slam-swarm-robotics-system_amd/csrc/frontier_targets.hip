@@ -94,7 +94,7 @@ qs_ft_centroid_kernel(const unsigned int *__restrict__ cnt, const unsigned long 
     }
 }
 
-static hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent)
+hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent)
 {
     const QsFrLayout F = qs_frontier_layout(c, fr_ws);
     const size_t n_chunks = (c->cells + QS_FR_CHUNK - 1) / QS_FR_CHUNK;

@@ -21,15 +21,8 @@
 #include <string.h>
 #include <algorithm>
 
-#include "qs_internal.h"
+#include "plan_common.h"
 #include "raycast_common.h"
-
-#define PL_T 64                       // tile edge (cells)
-#define PL_H (PL_T + 2)               // tile + one-cell halo
-#define PL_BLOCK 256
-#define PL_INF 0xffffffffu
-#define PL_MAXC QS_PLAN_MAX_CLEARANCE
-#define PL_R (PL_T + 2 * PL_MAXC)     // largest dilation region edge
 
 static_assert(PL_T == QS_WAVE, "one lane per cell of a tile row");
 
@@ -136,13 +129,15 @@ qs_plan_snap_kernel(const double2 *__restrict__ xy, int n_end, double res, doubl
 }
 
 // ---- fields ----------------------------------------------------------------------------------------------------
-struct PlBox { int bx0, by0, ntx, nty, fw, fh; };    // bounding box: first tile, tiles across / down, field edge in cells
-
-// seed: field[goal] = 0 and the goal's tile in the first list (round 1: list 1, count 1 of the ring, mark 1)
+// seed: field[goal] = 0 and the goal's tile in the first list (round 1: list 1, count 1 of the ring, mark 1).  A round
+// appends a neighbour tile when a border cell of the tile IMPROVED, and the seed cell itself never does: a goal on a tile's
+// border row or column (or corner) also puts the tiles across that border in the first list, or a goal whose only moves
+// lead across the border would never leave its tile.  They read the seed through their halo.
 __global__ void __launch_bounds__(PL_BLOCK)
 qs_plan_seed_kernel(const long long *__restrict__ start, const long long *__restrict__ goal, int g0, int gn, int size,
-                    PlBox B, size_t fcells, unsigned int *__restrict__ fields, unsigned int *__restrict__ list,
-                    unsigned int *__restrict__ cnt, unsigned int *__restrict__ marks)
+                    PlBox B, size_t fcells, const unsigned int *__restrict__ tile_any, int gtx,
+                    unsigned int *__restrict__ fields, unsigned int *__restrict__ list, unsigned int *__restrict__ cnt,
+                    unsigned int *__restrict__ marks)
 {
     const int f = blockIdx.x * PL_BLOCK + threadIdx.x;
     if (f >= gn) return;
@@ -150,9 +145,16 @@ qs_plan_seed_kernel(const long long *__restrict__ start, const long long *__rest
     if (s < 0 || g < 0) return;
     const int fx = (int)(g % size) - B.bx0 * PL_T, fy = (int)(g / size) - B.by0 * PL_T;
     fields[(size_t)f * fcells + (size_t)fy * B.fw + fx] = 0;
-    const unsigned int item = (unsigned int)f * (B.ntx * B.nty) + (fy / PL_T) * B.ntx + fx / PL_T;
-    marks[item] = 1;
-    list[atomicAdd(&cnt[1], 1u)] = item;
+    const int tx = fx / PL_T, ty = fy / PL_T;
+    const int ex = fx % PL_T == 0 ? -1 : (fx % PL_T == PL_T - 1 ? 1 : 0), ey = fy % PL_T == 0 ? -1 : (fy % PL_T == PL_T - 1 ? 1 : 0);
+    for (int k = 0; k < 4; k++) {                           // the tile, then those across x, across y, across the corner
+        const int nx = tx + ((k & 1) ? ex : 0), ny = ty + ((k & 2) ? ey : 0);
+        if (((k & 1) && !ex) || ((k & 2) && !ey)) continue;
+        if (nx < 0 || ny < 0 || nx >= B.ntx || ny >= B.nty || !tile_any[(size_t)(B.by0 + ny) * gtx + B.bx0 + nx]) continue;
+        const unsigned int item = (unsigned int)f * (B.ntx * B.nty) + ny * B.ntx + nx;
+        marks[item] = 1;
+        list[atomicAdd(&cnt[1], 1u)] = item;
+    }
 }
 
 // min-plus scan with step weight w along the 64 lanes of a line, in lane order: v[x] = min over k <= x of the same
@@ -392,26 +394,9 @@ qs_plan_walk_kernel(const unsigned int *__restrict__ fields, size_t fcells, PlBo
 
 // ---- workspace and launchers -------------------------------------------------------------------------------------
 #define QS_PLAN_ROUND_BLOCKS 1024   // workgroups of a relaxation round (they stride over its list)
-// the planner's workspace, carved from ws (nullptr: only the bytes the block needs) for n requests
-struct QsPlanLayout {
-    unsigned int *mask;             // [tiles down * 64][mp] traversable bits, rows padded to whole tiles
-    unsigned int *tile_any;         // [tiles down][tiles across] the tile holds a traversable cell
-    unsigned int *bbox;             // [4] first / last tile across and down of those (the census)
-    unsigned int *cnt;              // [3] list counts of a ring of rounds
-    unsigned long long *stats;      // [4] rounds, tile visits, (unused), snapped endpoints
-    double2 *xy;                    // [2n] starts, then goals
-    long long *cell;                // [2n] their cells (gy * size + gx), -1 = none
-    int4 *out4;                     // [n] status, waypoint gx, gy, cost
-    long long *plen;                // [n] path cells
-    int2 *path;                     // [n][path_cap]
-    unsigned int *list0, *list1, *marks;   // [item_cap] worklists of (field, tile) items and their round marks
-    unsigned int *fields;           // [field_words] one group's fields
-    int mp, gtx;                    // mask words per row, tiles across the grid
-    size_t gmax, field_words, item_cap, bytes;
-};
 static inline int pl_tiles(int size) { return (size + PL_T - 1) / PL_T; }
 
-static QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap)
+QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap)
 {
     QsPlanLayout L;
     Carve k(ws);
@@ -454,33 +439,26 @@ static hipError_t qs_launch_plan_trav(qs_ctx *c, const QsPlanLayout &L, int clea
     return hipGetLastError();
 }
 
-static hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, size_t n_end, int radius)
+hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, const double2 *xy, long long *cell, size_t n_end, int radius,
+                               unsigned long long *snapped)
 {
     if (!n_end) return hipSuccess;
     const unsigned int blocks = (unsigned int)((n_end + PL_BLOCK / QS_WAVE - 1) / (PL_BLOCK / QS_WAVE));
-    hipLaunchKernelGGL(qs_plan_snap_kernel, dim3(blocks), dim3(PL_BLOCK), 0, c->stream, L.xy, (int)n_end, c->cfg.res,
-                       c->cfg.ox, c->cfg.oy, c->cfg.size, L.mask, L.mp, radius, L.cell, L.stats + 3);
+    hipLaunchKernelGGL(qs_plan_snap_kernel, dim3(blocks), dim3(PL_BLOCK), 0, c->stream, xy, (int)n_end, c->cfg.res,
+                       c->cfg.ox, c->cfg.oy, c->cfg.size, L.mask, L.mp, radius, cell, snapped);
     return hipGetLastError();
 }
 
-static inline PlBox pl_box(const unsigned int bbox[4])
-{
-    PlBox B;
-    B.bx0 = (int)bbox[0]; B.by0 = (int)bbox[1];
-    B.ntx = (int)(bbox[2] - bbox[0] + 1); B.nty = (int)(bbox[3] - bbox[1] + 1);
-    B.fw = B.ntx * PL_T; B.fh = B.nty * PL_T;
-    return B;
-}
-
 // requests per group
-static size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n)
+size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n)
 {
     const PlBox B = pl_box(bbox);
     size_t g = L.field_words / ((size_t)B.fw * B.fh);
     return g < n ? g : n;
 }
 
-static hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn)
+static hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
+                                      const long long *goal, size_t g0, size_t gn)
 {
     const PlBox B = pl_box(bbox);
     const size_t fc = (size_t)B.fw * B.fh;
@@ -489,7 +467,7 @@ static hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const un
     if (e == hipSuccess) e = hipMemsetAsync(L.cnt, 0, 3 * sizeof(unsigned int), c->stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(qs_plan_seed_kernel, dim3((unsigned int)((gn + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, c->stream,
-                       L.cell, L.cell + n, (int)g0, (int)gn, c->cfg.size, B, fc, L.fields, L.list1, L.cnt, L.marks);
+                       start, goal, (int)g0, (int)gn, c->cfg.size, B, fc, L.tile_any, L.gtx, L.fields, L.list1, L.cnt, L.marks);
     return hipGetLastError();
 }
 
@@ -504,19 +482,19 @@ static hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const u
     return hipGetLastError();
 }
 
-static hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
-                                      int lookahead, size_t path_cap)
+hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
+                               const long long *goal, size_t g0, size_t gn, int lookahead, size_t path_cap)
 {
     const PlBox B = pl_box(bbox);
     const unsigned int blocks = (unsigned int)((gn + PL_BLOCK / QS_WAVE - 1) / (PL_BLOCK / QS_WAVE));
     hipLaunchKernelGGL(qs_plan_walk_kernel, dim3(blocks), dim3(PL_BLOCK), 0, c->stream, L.fields, (size_t)B.fw * B.fh, B,
-                       L.mask, L.mp, c->cfg.size, L.cell, L.cell + n, (int)g0, (int)gn, lookahead, L.path, path_cap, L.out4,
+                       L.mask, L.mp, c->cfg.size, start, goal, (int)g0, (int)gn, lookahead, L.path, path_cap, L.out4,
                        L.plen);
     return hipGetLastError();
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
-static int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out)
+int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out)
 {
     out = p ? *p : qs_plan_params{2, 10, 200, 0};        // the defaults (include/quasar_slam.h)
     if (out.clearance < 0 || out.clearance > QS_PLAN_MAX_CLEARANCE)
@@ -529,7 +507,7 @@ static int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out)
 }
 
 // the mask and the census for n requests (layout of the planner workspace); bbox[0] > bbox[2]: no traversable cell
-static int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPlanLayout &L, unsigned int bbox[4])
+int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPlanLayout &L, unsigned int bbox[4])
 {
     HIPCHK(c, hipSetDevice(c->device));
     SYNCCHK(c);
@@ -543,12 +521,12 @@ static int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPla
 }
 
 // the fields of requests g0 .. g0 + gn: seed, then rounds in batches of QS_PLAN_ROUND_BATCH without a sync (a round that
-// finds its list empty returns at once), the live count read once per batch; then the walk
+// finds its list empty returns at once), the live count read once per batch
 #define QS_PLAN_ROUND_BATCH 8
-static int plan_group(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
-                      int lookahead, size_t path_cap)
+int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start, const long long *goal,
+                size_t g0, size_t gn)
 {
-    HIPCHK(c, qs_launch_plan_seed(c, L, bbox, n, g0, gn));
+    HIPCHK(c, qs_launch_plan_seed(c, L, bbox, start, goal, g0, gn));
     for (unsigned int r = 1;; r += QS_PLAN_ROUND_BATCH) {
         for (unsigned int k = 0; k < QS_PLAN_ROUND_BATCH; k++) HIPCHK(c, qs_launch_plan_round(c, L, bbox, gn, r + k));
         unsigned int live = 0;
@@ -557,7 +535,16 @@ static int plan_group(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[
         if (!live) break;
         if (r > 0x7fffffffu) return qs_fail(c, QS_E_STATE, "path planning: the relaxation did not settle");
     }
-    if (lookahead > 0) HIPCHK(c, qs_launch_plan_walk(c, L, bbox, n, g0, gn, lookahead, path_cap));
+    return QS_OK;
+}
+
+// ... then the walk
+static int plan_group(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
+                      int lookahead, size_t path_cap)
+{
+    int rc = plan_fields(c, L, bbox, L.cell, L.cell + n, g0, gn);
+    if (rc != QS_OK) return rc;
+    if (lookahead > 0) HIPCHK(c, qs_launch_plan_walk(c, L, bbox, L.cell, L.cell + n, g0, gn, lookahead, path_cap));
     return QS_OK;
 }
 
@@ -593,7 +580,7 @@ extern "C" int qs_plan_field(qs_ctx *c, const qs_plan_params *params, const doub
     if (bbox[0] > bbox[2]) return QS_OK;                  // nothing is traversable
     const double xy[4] = {goal_xy[0], goal_xy[1], goal_xy[0], goal_xy[1]};   // (start = goal: only the field is wanted)
     HIPCHK(c, hipMemcpyAsync(L.xy, xy, sizeof xy, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, qs_launch_plan_snap(c, L, 2, p.snap_radius));
+    HIPCHK(c, qs_launch_plan_snap(c, L, L.xy, L.cell, 2, p.snap_radius, L.stats + 3));
     rc = plan_group(c, L, bbox, 1, 0, 1, 0, 0);
     if (rc != QS_OK) return rc;
     // the bounding box's cells that lie on the grid, rows of the field into rows of the host array
@@ -629,7 +616,7 @@ extern "C" int qs_plan_paths(qs_ctx *c, const qs_plan_params *params, const doub
         memcpy(xy.data(), start_xy, 2 * n * sizeof(double));
         memcpy(xy.data() + 2 * n, goal_xy, 2 * n * sizeof(double));
         HIPCHK(c, hipMemcpyAsync(L.xy, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, qs_launch_plan_snap(c, L, 2 * n, p.snap_radius));
+        HIPCHK(c, qs_launch_plan_snap(c, L, L.xy, L.cell, 2 * n, p.snap_radius, L.stats + 3));
         const size_t g = qs_plan_group(L, bbox, n);
         if (g == 0) return qs_fail(c, QS_E_STATE, "qs_plan_paths: workspace holds no field");
         for (size_t g0 = 0; g0 < n; g0 += g, groups++) {

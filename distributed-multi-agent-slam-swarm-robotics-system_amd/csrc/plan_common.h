@@ -1,0 +1,58 @@
+// plan_common.h -- what plan.hip (path planning) shares with targets_by_path.hip (§4.12): the tile
+// geometry, the planner's workspace and the launchers of its kernels.  The kernels themselves stay in plan.hip.
+#pragma once
+#include "qs_internal.h"
+
+#define PL_T 64                       // tile edge (cells)
+#define PL_H (PL_T + 2)               // tile + one-cell halo
+#define PL_BLOCK 256
+#define PL_INF 0xffffffffu
+#define PL_MAXC QS_PLAN_MAX_CLEARANCE
+#define PL_R (PL_T + 2 * PL_MAXC)     // largest dilation region edge
+
+struct PlBox { int bx0, by0, ntx, nty, fw, fh; };    // bounding box: first tile, tiles across / down, field edge in cells
+
+// the planner's workspace, carved from ws (nullptr: only the bytes the block needs) for n requests
+struct QsPlanLayout {
+    unsigned int *mask;             // [tiles down * 64][mp] traversable bits, rows padded to whole tiles
+    unsigned int *tile_any;         // [tiles down][tiles across] the tile holds a traversable cell
+    unsigned int *bbox;             // [4] first / last tile across and down of those (the census)
+    unsigned int *cnt;              // [3] list counts of a ring of rounds
+    unsigned long long *stats;      // [4] rounds, tile visits, (unused), snapped endpoints
+    double2 *xy;                    // [2n] starts, then goals
+    long long *cell;                // [2n] their cells (gy * size + gx), -1 = none
+    int4 *out4;                     // [n] status, waypoint gx, gy, cost
+    long long *plen;                // [n] path cells
+    int2 *path;                     // [n][path_cap]
+    unsigned int *list0, *list1, *marks;   // [item_cap] worklists of (field, tile) items and their round marks
+    unsigned int *fields;           // [field_words] one group's fields
+    int mp, gtx;                    // mask words per row, tiles across the grid
+    size_t gmax, field_words, item_cap, bytes;
+};
+
+static inline PlBox pl_box(const unsigned int bbox[4])
+{
+    PlBox B;
+    B.bx0 = (int)bbox[0]; B.by0 = (int)bbox[1];
+    B.ntx = (int)(bbox[2] - bbox[0] + 1); B.nty = (int)(bbox[3] - bbox[1] + 1);
+    B.fw = B.ntx * PL_T; B.fh = B.nty * PL_T;
+    return B;
+}
+
+// ---- host side of plan.hip that targets_by_path.hip calls ---------------------------------------------------------------
+QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap);
+// params (NULL = the defaults) checked into out; QS_E_INVAL with a message otherwise
+int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out);
+// the mask and the census for n requests (layout of the planner workspace); bbox[0] > bbox[2]: no traversable cell
+int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPlanLayout &L, unsigned int bbox[4]);
+// fields of a group that fit the workspace, at most n
+size_t qs_plan_group(const QsPlanLayout &L, const unsigned int bbox[4], size_t n);
+// n_end endpoints xy -> cell (rule 2); *snapped counts those that moved
+hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, const double2 *xy, long long *cell, size_t n_end, int radius,
+                               unsigned long long *snapped);
+// gn fields seeded at goal[g0 .. g0 + gn) (where start and goal both have a cell), then relaxed to the fixpoint
+int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start, const long long *goal,
+                size_t g0, size_t gn);
+// the walks of requests g0 .. g0 + gn over the group's fields: L.out4, L.plen, L.path
+hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
+                               const long long *goal, size_t g0, size_t gn, int lookahead, size_t path_cap);

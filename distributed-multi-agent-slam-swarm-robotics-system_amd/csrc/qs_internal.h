@@ -265,6 +265,7 @@ struct qs_ctx {
     DevBuf<char> frontier_ws;                    // frontier labelling (allocated on first use)
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
     DevBuf<char> plan_ws;                        // path planning (plan.hip: qs_plan_layout)
+    DevBuf<char> tbp_ws;                         // targets by path cost (targets_by_path.hip: qs_tbp_layout)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
     DevBuf<unsigned int> ck_census;              // checkpoint (checkpoint.hip): block bitmap, block list, count
@@ -407,6 +408,9 @@ struct QsFrLayout { unsigned int *label, *cnt; unsigned long long *sumx, *sumy; 
 QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws);
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
 hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
+// frontier_targets.hip: the centroids of the clusters of a labelled frontier workspace with >= min_cluster cells, in first-cell
+// order.  phase 0 counts them (QsFrLayout::total, after the scan); phase 1 writes them to d_cent
+hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
 // ekf.hip
 hipError_t qs_launch_ekf_ingest(qs_ctx *c, size_t n, const double *d_time, hipStream_t st);
 // ekf_scan.hip: the same filter over a large batch, parallel in time

@@ -758,14 +758,67 @@ class QuasarMapper:
         stats = dict(zip(("n_centroids", "k", "fallbacks", "reserved"), (int(v) for v in st)))
         return idx, xy, cents[:k.value], stats
 
-    def assign_frontier_targets(self, bot_states, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER):
+    def assign_frontier_targets(self, bot_states, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
+                                by_path=False, return_waypoints=False, **plan_params):
         """The reference's target_assignments (:958-992): {bot: (x, y)} of the online bots -> {bot: (tx, ty)} for
-        the bots that got a target, bots taken in ascending id."""
+        the bots that got a target, bots taken in ascending id.  by_path=True (opt-in): the targets of
+        frontier_targets_by_path instead (plan_params: clearance, snap_radius, lookahead), and with return_waypoints
+        also {bot: (wx, wy)}, the waypoint of each assigned bot's path, as a second dict."""
+        if not by_path:
+            if return_waypoints or plan_params:
+                raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True")
+            bots = sorted(bot_states)
+            if not bots:
+                return {}
+            idx, xy = self.frontier_targets([bot_states[b] for b in bots], separation, min_cluster)
+            return {b: (float(xy[i, 0]), float(xy[i, 1])) for i, b in enumerate(bots) if idx[i] >= 0}
         bots = sorted(bot_states)
         if not bots:
-            return {}
-        idx, xy = self.frontier_targets([bot_states[b] for b in bots], separation, min_cluster)
-        return {b: (float(xy[i, 0]), float(xy[i, 1])) for i, b in enumerate(bots) if idx[i] >= 0}
+            return ({}, {}) if return_waypoints else {}
+        res = self.frontier_targets_by_path([bot_states[b] for b in bots], separation, min_cluster,
+                                            waypoints=return_waypoints, **plan_params)
+        got = [(i, b) for i, b in enumerate(bots) if res["idx"][i] >= 0]
+        targets = {b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}
+        if not return_waypoints:
+            return targets
+        return targets, {b: (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1])) for i, b in got}
+
+    def frontier_targets_by_path(self, bot_xy, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
+                                 clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS, lookahead=P.PLAN_LOOKAHEAD,
+                                 return_centroids=False, waypoints=True):
+        """Frontier targets ranked by path cost over the mapped free space (include/quasar_slam.h, "frontier targets by
+        path cost"): bots in greedy order, each takes the eligible centroid with the smallest (cost, index).  Returns a
+        dict of numpy arrays: idx int64 [n] (index into frontier_centroids(min_cluster), -1 = none), xy float64 [n, 2]
+        (NaN where none), cost uint32 [n], status int32 [n] (QS_PLAN_OK / _NO_START / _UNREACHABLE), waypoint_cell int32
+        [n, 2] and waypoint float64 [n, 2] (what plan_paths(bot, target) returns; -1 / NaN where none or with
+        waypoints=False, which skips that stage), stats; with return_centroids also centroids float64 [k, 2]."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(b)
+        if n > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"frontier_targets_by_path: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        prm = self._plan_params(clearance, snap_radius, lookahead)
+        idx = np.full(n, -1, dtype=np.int64)
+        xy = np.full((n, 2), np.nan, dtype=np.float64)
+        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        wc = np.full((n, 2), -1, dtype=np.int32)
+        wxy = np.full((n, 2), np.nan, dtype=np.float64)
+        st = np.zeros(8, dtype=np.uint64)
+        k = C.c_size_t()
+        cents, cap = None, 0
+        if return_centroids:       # the count first: a second call would observe the same map
+            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
+            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
+        self._chk(self._L.qs_frontier_targets_by_path(
+            self._h, min_cluster, float(separation), C.byref(prm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost), _ptr(status),
+            _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(cents) if cap else None, cap,
+            C.byref(k), _ptr(st)), "qs_frontier_targets_by_path")
+        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy,
+                   stats=dict(zip(("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits",
+                                   "fallbacks", "reserved"), (int(v) for v in st))))
+        if return_centroids:
+            out["centroids"] = cents[:k.value]
+        return out
 
     # -- path planning (include/quasar_slam.h, "path planning"; no reference counterpart) ----------------------
     def traversable(self, clearance=P.PLAN_CLEARANCE):

@@ -15,6 +15,10 @@ Mirrors server_nodes/dual_bot_mapper.py:
                                With plan_paths=True (also opt-in) a TARG carries instead the waypoint of a path over
                                the mapped free space to that centroid (QuasarMapper.plan_paths), or the centroid itself
                                when there is no path; plan_params go to plan_paths.
+                               With targets_by_path=True (also opt-in) the centroids are ranked by path cost instead
+                               of straight-line distance (QuasarMapper.assign_frontier_targets(by_path=True), ONE
+                               device call per tick, plan_params its planning parameters): every assigned bot has a
+                               path to its target, so with plan_paths=True every TARG carries a waypoint.
 Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry packets of the ESP32 firmware
 (esp32_firmware/src/main.cpp:190-215) are mapped too.  Datagrams then get slots of SWEEP_SLOT bytes; the datagrams of a
 poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
@@ -41,9 +45,11 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
-                 match_params=None):
+                 match_params=None, targets_by_path=False):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
+        if targets_by_path and not frontier_targets:
+            raise ValueError("MissionControl: targets_by_path=True needs frontier_targets=True")
         if match_sweeps and not sweeps:
             raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
         self.match_sweeps = match_sweeps
@@ -51,6 +57,7 @@ class MissionControl:
         self.last_matches = None
         self.mapper = mapper
         self.plan_paths = plan_paths
+        self.targets_by_path = targets_by_path
         self.plan_params = dict(plan_params or {})
         self.plan_stats = {"waypoint": 0, "centroid": 0}
         self.sweeps = sweeps
@@ -195,9 +202,12 @@ class MissionControl:
         if not states:
             return {}
         sent = {}
-        targets = sorted(self.mapper.assign_frontier_targets(states).items())
-        if self.plan_paths and targets:
-            targets = self._waypoints(states, targets)
+        if self.targets_by_path:
+            targets = self._targets_by_path(states)
+        else:
+            targets = sorted(self.mapper.assign_frontier_targets(states).items())
+            if self.plan_paths and targets:
+                targets = self._waypoints(states, targets)
         for bot_id, (tx, ty) in targets:
             pkt = P.pack_target(tx, ty)
             if self.bot_addrs[bot_id] is not None:                                    # send_target_to_bot :693-694
@@ -221,6 +231,15 @@ class MissionControl:
                 out.append((b, xy))
                 self.plan_stats["centroid"] += 1
         return out
+
+    def _targets_by_path(self, states):
+        """One call that ranks the centroids by path cost: the centroids of the assigned bots, or (plan_paths) their
+        waypoints, which always exist; counted in plan_stats as _waypoints counts them."""
+        if not self.plan_paths:
+            return sorted(self.mapper.assign_frontier_targets(states, by_path=True, **self.plan_params).items())
+        _, wps = self.mapper.assign_frontier_targets(states, by_path=True, return_waypoints=True, **self.plan_params)
+        self.plan_stats["waypoint"] += len(wps)
+        return sorted(wps.items())
 
     def step(self, now=None):
         """One iteration of the reference's while-loop body (without events and rendering)."""

@@ -455,6 +455,38 @@ int qs_plan_paths(qs_ctx *ctx, const qs_plan_params *params, const double *start
                   int32_t *status, int32_t *wp_cell_xy, double *wp_xy, uint32_t *cost, int32_t *path_xy, size_t path_cap,
                   int64_t *path_len, uint64_t stats[4]);
 
+/* ---- frontier targets by path cost (no reference counterpart: this build's own rules) ------------------------------------
+ * qs_frontier_targets gives a bot the centroid nearest in a straight line, which the bot may have no path to.  This call
+ * ranks the centroids by the cost of the path over the mapped free space instead and returns target and waypoint together.
+ * All rules are integer once the centroids exist, so the device and a CPU restatement agree bit for bit.
+ *  1. Centroids: the list, order and positions of qs_frontier_targets / qs_frontier_clusters(min_cluster).
+ *  2. Cells: the traversable mask is planning rule 1 with params.clearance; every bot position and every centroid
+ *     position maps to a cell by planning rule 2 (world_to_grid, then the snap within params.snap_radius).  A position that
+ *     does not snap (NaN, infinite, off-grid, nothing traversable in the radius) has no cell.
+ *  3. Cost: cost(b, k) is the planning rule 3 shortest-path cost between bot b's cell and centroid k's cell (moves of 5 and
+ *     7, no corner cutting, uint32); 0xFFFFFFFF when either has no cell or the two are not connected.  The moves are
+ *     symmetric (a move and its reverse are legal together and cost the same), so ONE field seeded at the bot's cell
+ *     gives the bot's cost to every centroid.  A cost of 0 (the bot stands on the centroid's cell) is valid.
+ *  4. Greedy: bots in the order given.  Centroid k is eligible for bot b when cost(b, k) is finite, no earlier bot took k,
+ *     and for every earlier target t `sqrt(dx*dx + dy*dy) < separation` is false (qs_frontier_targets' fp64 test between
+ *     world centroid positions).  The bot takes the eligible k with the smallest (cost, k).  A bot with no cell gets
+ *     status QS_PLAN_NO_START, a bot with a cell but no eligible centroid QS_PLAN_UNREACHABLE; both get index -1, NaN
+ *     positions, cost 0xFFFFFFFF, and add no target.
+ *  5. Waypoint: an assigned bot gets exactly what qs_plan_paths(params, bot_xy[b], target_xy[b]) returns on the same map:
+ *     status QS_PLAN_OK (both ends have cells and the cost is finite), the waypoint cell, its world position, and the
+ *     cost, which equals cost(b, k).  Unassigned bots get (-1, -1) and NaN.
+ *  6. The call observes the map (flushes waiting exact-trig rays first) and writes no session state: a checkpoint before
+ *     equals one after.  n_bots <= QS_FT_MAX_BOTS.  Argument checks are those of qs_frontier_targets and of qs_plan_params
+ *     (QS_E_INVAL).  n_bots == 0, a map without clusters and a map without FREE cells are valid.
+ * wp_cell_xy and wp_xy are an optional pair (both NULL: no waypoints are computed).  centroids_xy (optional, cap entries)
+ * and *n_centroids report the centroid list.  stats (optional): centroids, centroids with a cell, bots with a cell, field
+ * groups (bot fields, fields recomputed for a fallback, waypoint fields), relaxation rounds, tile visits, top-K fallbacks
+ * (bots whose 32 cheapest centroids were all ineligible: decided by a scan of every centroid), reserved. */
+int qs_frontier_targets_by_path(qs_ctx *ctx, int32_t min_cluster, double separation, const qs_plan_params *params,
+                                const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
+                                uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
+                                double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8]);
+
 /* ---- EKF  AgentFirmware_Bot1/ekf.cpp:5-92 ---------------------------------------------- */
 /* On ingest (qs_config.enable_ekf) the filter of every bot runs over the batch: batches of >= 4096
  * packets in a parallel-in-time form that agrees with the step-by-step filter to rounding (~1e-12

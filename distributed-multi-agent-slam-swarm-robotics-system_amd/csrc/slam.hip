@@ -181,8 +181,11 @@ __device__ inline void lds_barrier()
 __device__ inline int bucket_coord(double v, double b0, double inv_cell)
 {
     const double f = floor((v - b0) * inv_cell);
-    // one conversion instruction (f64 -> i64 is a sequence); monotone, saturating at +-1e9 cells
-    return (fabs(f) < 1.0e9) ? (int)f : (f > 0 ? 1000000000 : -1000000000);
+    // one conversion instruction (f64 -> i64 is a sequence); monotone, saturating at +-1e9 cells.  The clamp is a max and a min
+    // in fp64 ahead of the conversion (two instructions; two compares and two selects after it come to the same cell for every
+    // input): both are monotone, and fmax returns its other operand for a NaN, so a NaN pose lands in cell -1e9 -- a cell like
+    // any other, the same one at insert and at query.
+    return (int)fmin(fmax(f, -1.0e9), 1.0e9);
 }
 
 __device__ inline long long rl64(long long v, int src_lane)      // wave-uniform read of one lane

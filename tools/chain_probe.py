@@ -1,0 +1,43 @@
+#!/usr/bin/env python3
+"""chain A/B probe: chain stage ms per run, closures, a digest of (closures, landmarks, drift), which instantiation ran.
+usage: tools/chain_probe.py WORKLOAD [B] [reps] [form]   (QUASAR_SLAM_LIB selects the library)"""
+import hashlib, importlib, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "distributed-multi-agent-slam-swarm-robotics-system_amd"
+import torch
+pkg = importlib.import_module(PKG)
+replay = importlib.import_module(PKG + ".replay")
+wl = sys.argv[1]
+B = int(sys.argv[2]) if len(sys.argv) > 2 else (1 << 20)
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+form = sys.argv[4] if len(sys.argv) > 4 else None
+session, _ = replay.telemetry_csv_to_packets()
+ng = 1
+if wl == "adv":
+    d = torch.from_numpy(replay.adversarial_stream(B)).cuda()
+    m = pkg.QuasarMapper(4096, 0.05, -102.4, -102.4, max_agent=2, exact_trig=False); na = 2
+elif wl == "c1":
+    d = torch.from_numpy(replay.cycle_stream(session, B)).cuda()
+    m = pkg.QuasarMapper(4096, 0.05, -102.4, -102.4, max_agent=2, exact_trig=False); na = 2
+else:
+    d = torch.from_numpy(replay.multi_bot_stream(None, 64, B)).cuda()
+    m = pkg.QuasarMapper(4096, 0.05, -102.4, -102.4, max_agent=64, bots_per_graph=0 if wl == "one64" else 2, exact_trig=False); na = 64
+    ng = 1 if wl == "one64" else 32
+if form: m.set_chain_form(form)
+m.reset(); m.ingest_device(d.data_ptr(), B, 42, 0, 0, seq0=0); m.sync()
+out = []
+for r in range(reps):
+    m.reset(); m.stage_times(reset=True); m.timing_enable(True); m.ingest_device(d.data_ptr(), B, 42, 0, 0, seq0=0); m.sync()
+    c = m.counters(); st = m.stage_times()
+    out.append(round(st["slam_chain"][0], 3))
+h = hashlib.sha1()
+for g in range(ng):
+    idx, corr = m.closures(g); xy, ti = m.landmarks(g)
+    for a in (idx, corr, xy, ti): h.update(a.tobytes())
+for b in range(1, na + 1): h.update(m.drift(b).tobytes())
+res = {"workload": wl, "lib": os.path.basename(ROOT), "form": form, "chain_ms": out,
+       "batches": c["slam_windows"], "closures": c["closures"], "rounds": c["slam_rounds"], "digest": h.hexdigest()[:16],
+       "lean": m.chain_lean() if hasattr(m, "chain_lean") else None,
+       "chain_form": m.chain_form()}
+print(json.dumps(res), flush=True)

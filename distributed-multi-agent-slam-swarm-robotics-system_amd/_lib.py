@@ -39,6 +39,15 @@ class QsSweepMatch(C.Structure):
                 ("dx", C.c_double), ("dy", C.c_double), ("dyaw", C.c_double)]
 
 
+class QsMergeResult(C.Structure):
+    """struct qs_merge_result (include/quasar_slam.h)."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_local", C.c_uint64), ("n_global", C.c_uint64),
+                ("fitness", C.c_double), ("rmse", C.c_double), ("T", C.c_double * 9)]
+
+
+QS_MERGE_STATUS = ("empty", "adopted", "merged", "rejected")     # QS_MERGE_EMPTY .. QS_MERGE_REJECTED (include/quasar_slam.h)
+
+
 class QsConfig(C.Structure):
     """struct qs_config (include/quasar_slam.h)."""
     _fields_ = [
@@ -150,6 +159,14 @@ SIGNATURES = {
     "qs_set_chain_form": (_i32, [_vp, _i32]),
     "qs_chain_form": (_i32, [_vp]),
     "qs_voxel_downsample": (_i32, [_vp, _vp, _sz, _f64, _vp, _sz, C.POINTER(_sz)]),
+    "qs_voxel_downsample_device": (_i32, [_vp, _vp, _sz, _f64, _vp, _sz, C.POINTER(_sz)]),
+    "qs_merge_reset": (_i32, [_vp]),
+    "qs_merge_params": (_i32, [_vp, _f64, _i32, _f64]),
+    "qs_merge_grid": (_i32, [_vp, _vp, _i32, _i32, _f64, _f64, _f64, _vp]),
+    "qs_merge_grid_device": (_i32, [_vp, _vp, _i32, _i32, _f64, _f64, _f64, _vp]),
+    "qs_merge_map": (_i32, [_vp, _vp, _vp]),
+    "qs_merge_cloud": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "qs_merge_global_map": (_i32, [_vp, _vp, _vp, _vp]),
     "qs_frontier_cells": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_members": (_i32, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "qs_frontier_clusters": (_i32, [_vp, _i32, _vp, _sz, C.POINTER(_sz)]),

@@ -232,9 +232,28 @@ hipError_t qs_launch_reset_small(qs_ctx *c)
 // ---- MapMerger.grid_to_pcd  server_nodes/map_merger.py:64-85 -----------------------------
 // np.argwhere(data > 50) is row-major, so the points are an order-preserving compaction:
 // per-chunk counts, one scan, ranked writes.  Chunk = 1024 cells.
+// The three kernels are written once over (what marks an item, what a marked item leaves behind) and instantiated for
+//   the int8 grid of a map message (data > 50 -> a point),
+//   a context's own stamps (an odd stamp = occupied -> the same point; merge.hip: qs_merge_map), and
+//   a sorted key array (a key that differs from its predecessor -> its position; merge.hip: the voxel runs).
 #define PCD_CHUNK 1024
+struct PcdGridI8 { const signed char *g; __device__ bool marked(size_t c) const { return g[c] > 50; } };               // data > 50   :72
+struct PcdStamps { const unsigned int *s; __device__ bool marked(size_t c) const { return (s[c] & 1u) != 0u; } };     // (ordinal << 1) | occ
+struct PcdRunHead { const unsigned long long *k; __device__ bool marked(size_t c) const { return c == 0 || k[c] != k[c - 1]; } };
+struct PcdEmitXY {
+    int w; double res, ox, oy; double *xy;
+    __device__ void put(size_t slot, size_t c) const
+    {
+        const long long row = (long long)(c / w), col = (long long)(c % w);
+        xy[2 * slot] = (double)col * res + ox;                  // x = col*res + origin_x  :77
+        xy[2 * slot + 1] = (double)row * res + oy;              // y = row*res + origin_y  :76
+    }
+};
+struct PcdEmitPos { unsigned int *pos; __device__ void put(size_t slot, size_t c) const { pos[slot] = (unsigned int)c; } };
+
+template <typename Src>
 __global__ void __launch_bounds__(GO_BLOCK)
-qs_pcd_count_kernel(const signed char *__restrict__ grid, size_t cells, unsigned int *__restrict__ chunk_count)
+qs_pcd_count_kernel(const Src src, size_t cells, unsigned int *__restrict__ chunk_count)
 {
     __shared__ unsigned int s;
     if (threadIdx.x == 0) s = 0;
@@ -243,7 +262,7 @@ qs_pcd_count_kernel(const signed char *__restrict__ grid, size_t cells, unsigned
     unsigned int m = 0;
     for (int q = 0; q < PCD_CHUNK / GO_BLOCK; q++) {
         const size_t c = base + q * GO_BLOCK + threadIdx.x;
-        if (c < cells && grid[c] > 50) m++;
+        if (c < cells && src.marked(c)) m++;
     }
     if (m) atomicAdd(&s, m);
     __syncthreads();
@@ -270,9 +289,9 @@ qs_pcd_scan_kernel(unsigned int *__restrict__ chunk_count, size_t n_chunks, unsi
     unsigned long long run = s_part[tid];
     for (size_t k = lo; k < hi; k++) { const unsigned int v = chunk_count[k]; chunk_count[k] = (unsigned int)run; run += v; }
 }
+template <typename Src, typename Emit>
 __global__ void __launch_bounds__(GO_BLOCK)
-qs_pcd_write_kernel(const signed char *__restrict__ grid, size_t cells, int w, double res, double ox, double oy,
-                    const unsigned int *__restrict__ chunk_off, double *__restrict__ xy, size_t cap)
+qs_pcd_write_kernel(const Src src, size_t cells, const unsigned int *__restrict__ chunk_off, const Emit emit, size_t cap)
 {
     __shared__ unsigned int s_wave[GO_BLOCK / QS_WAVE];
     __shared__ unsigned int s_run;
@@ -282,7 +301,7 @@ qs_pcd_write_kernel(const signed char *__restrict__ grid, size_t cells, int w, d
     const size_t base = (size_t)blockIdx.x * PCD_CHUNK;
     for (int q = 0; q < PCD_CHUNK / GO_BLOCK; q++) {
         const size_t c = base + q * GO_BLOCK + tid;
-        const bool occ = c < cells && grid[c] > 50;                      // data > 50   :72
+        const bool occ = c < cells && src.marked(c);
         const unsigned long long m = __ballot(occ);
         if (lane == 0) s_wave[wave] = __popcll(m);
         __syncthreads();
@@ -290,32 +309,44 @@ qs_pcd_write_kernel(const signed char *__restrict__ grid, size_t cells, int w, d
         for (int v = 0; v < wave; v++) off += s_wave[v];
         if (occ) {
             const size_t slot = off + __popcll(m & ((1ull << lane) - 1));
-            if (slot < cap) {
-                const long long row = (long long)(c / w), col = (long long)(c % w);
-                xy[2 * slot] = (double)col * res + ox;                  // x = col*res + origin_x  :77
-                xy[2 * slot + 1] = (double)row * res + oy;              // y = row*res + origin_y  :76
-            }
+            if (slot < cap) emit.put(slot, c);
         }
         __syncthreads();
         if (tid == 0) { unsigned int t = 0; for (int v = 0; v < GO_BLOCK / QS_WAVE; v++) t += s_wave[v]; s_run += t; }
         __syncthreads();
     }
 }
-static hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox,
-                                        double oy, double *d_xy, size_t cap, unsigned long long *d_count,
-                                        unsigned int *d_chunk)
+// phase 0 (emit target nullptr): chunk counts -> exclusive offsets, the total in *d_count; phase 1: the ranked writes
+template <typename Src, typename Emit>
+static hipError_t pcd_compact(qs_ctx *c, const Src src, size_t cells, bool write, const Emit emit, size_t cap,
+                              unsigned long long *d_count, unsigned int *d_chunk)
 {
-    const size_t cells = (size_t)h * w;
     const size_t n_chunks = (cells + PCD_CHUNK - 1) / PCD_CHUNK;
-    if (d_xy == nullptr) {
-        hipLaunchKernelGGL(qs_pcd_count_kernel, dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, d_grid,
-                           cells, d_chunk);
+    if (!write) {
+        hipLaunchKernelGGL(qs_pcd_count_kernel<Src>, dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, src, cells, d_chunk);
         hipLaunchKernelGGL(qs_pcd_scan_kernel, dim3(1), dim3(1024), 0, c->stream, d_chunk, n_chunks, d_count);
     } else {
-        hipLaunchKernelGGL(qs_pcd_write_kernel, dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, d_grid,
-                           cells, w, res, ox, oy, d_chunk, d_xy, cap);
+        hipLaunchKernelGGL((qs_pcd_write_kernel<Src, Emit>), dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, src, cells,
+                           d_chunk, emit, cap);
     }
     return hipGetLastError();
+}
+hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox,
+                                 double oy, double *d_xy, size_t cap, unsigned long long *d_count,
+                                 unsigned int *d_chunk)
+{
+    return pcd_compact(c, PcdGridI8{d_grid}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_count, d_chunk);
+}
+hipError_t qs_launch_stamps_to_pcd(qs_ctx *c, const unsigned int *d_stamps, int h, int w, double res, double ox,
+                                   double oy, double *d_xy, size_t cap, unsigned long long *d_count,
+                                   unsigned int *d_chunk)
+{
+    return pcd_compact(c, PcdStamps{d_stamps}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_count, d_chunk);
+}
+hipError_t qs_launch_run_heads(qs_ctx *c, const unsigned long long *d_keys, size_t n, unsigned int *d_pos, size_t cap,
+                               unsigned long long *d_count, unsigned int *d_chunk)
+{
+    return pcd_compact(c, PcdRunHead{d_keys}, n, d_pos != nullptr, PcdEmitPos{d_pos}, cap, d_count, d_chunk);
 }
 
 // ---- MapMerger.publish_global_map  map_merger.py:87-127 -----------------------------------
@@ -338,7 +369,7 @@ qs_bbox_kernel(const double *__restrict__ xy, size_t n, unsigned long long *__re
         atomicMin(&box4[0], s[0]); atomicMin(&box4[1], s[1]); atomicMax(&box4[2], s[2]); atomicMax(&box4[3], s[3]);
     }
 }
-static hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4)
+hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4)
 {
     hipLaunchKernelGGL(qs_bbox_kernel, dim3(go_blocks(n)), dim3(GO_BLOCK), 0, c->stream, d_xy, n, d_box4);
     return hipGetLastError();
@@ -356,7 +387,7 @@ qs_rasterise_kernel(const double *__restrict__ xy, size_t n, double res, double 
         grid[(size_t)yi * w + xi] = 100;                               // :115 (idempotent store)
     }
 }
-static hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx, double miny,
+hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx, double miny,
                                       int h, int w, signed char *d_grid)
 {
     hipError_t e = hipMemsetAsync(d_grid, 0xff, (size_t)h * w, c->stream);   // np.full(-1)  :107

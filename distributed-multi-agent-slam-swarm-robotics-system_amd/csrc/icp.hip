@@ -426,7 +426,7 @@ static hipError_t qs_launch_icp_transform(qs_ctx *c, double2 *pts, size_t n, dou
     return hipGetLastError();
 }
 
-static hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel,
+hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel,
                                        unsigned long long *keys)
 {
     if (n == 0) return hipSuccess;
@@ -438,18 +438,25 @@ static hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, 
 // ---- C ABI: ICP / voxel down-sample (map_merger.py:45-60; Open3D semantics, parity unpinned) -------------------------
 // The correspondence search (nearest target of every source point) has two implementations with identical results:
 // the scalar fp64 brute force and the MFMA-screened one (above).  mode 0 = auto (MFMA from 64 targets up).
-struct NnPlan { double cx = 0, cy = 0, t2max = 0; size_t n_pad = 0; bool mfma = false; DevBuf<double> planes, part_d2, thr_seed; DevBuf<int> part_j; };
-
-static hipError_t nn_prepare(qs_ctx *c, const double *dst_xy, size_t n_dst, const double2 *d_dst, int mode, NnPlan &pl, size_t n_src)
+// the targets' box from a host copy of them
+static void nn_box_host(const double *dst_xy, size_t n_dst, double box[4])
 {
-    pl.mfma = mode == 2 || (mode == 0 && n_dst >= 64);
-    if (!pl.mfma) return hipSuccess;
     double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
     for (size_t j = 0; j < n_dst; j++) {
         const double x = dst_xy[2 * j], y = dst_xy[2 * j + 1];
         if (isfinite(x)) { mnx = x < mnx ? x : mnx; mxx = x > mxx ? x : mxx; }
         if (isfinite(y)) { mny = y < mny ? y : mny; mxy = y > mxy ? y : mxy; }
     }
+    box[0] = mnx; box[1] = mny; box[2] = mxx; box[3] = mxy;
+}
+struct NnPlan { double cx = 0, cy = 0, t2max = 0; size_t n_pad = 0; bool mfma = false; DevBuf<double> planes, part_d2, thr_seed; DevBuf<int> part_j; };
+
+// box: {min x, min y, max x, max y} of the targets' finite coordinates (+inf / -inf where there is none)
+static hipError_t nn_prepare(qs_ctx *c, const double box[4], size_t n_dst, const double2 *d_dst, int mode, NnPlan &pl, size_t n_src)
+{
+    pl.mfma = mode == 2 || (mode == 0 && n_dst >= 64);
+    if (!pl.mfma) return hipSuccess;
+    const double mnx = box[0], mny = box[1], mxx = box[2], mxy = box[3];
     pl.cx = isfinite(mnx) ? 0.5 * (mnx + mxx) : 0.0; pl.cy = isfinite(mny) ? 0.5 * (mny + mxy) : 0.0;
     const double hx = isfinite(mnx) ? mxx - pl.cx : 0.0, hy = isfinite(mny) ? mxy - pl.cy : 0.0;
     pl.t2max = 1.0001 * (hx * hx + hy * hy) + 1e-300;          // >= every finite target's centred squared norm
@@ -493,7 +500,9 @@ extern "C" int qs_nn_search(qs_ctx *c, const double *src_xy, size_t n_src, const
     HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(ev[0].e, c->stream));
-    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, mode, pl, n_src));
+    double box[4];
+    nn_box_host(dst_xy, n_dst, box);
+    HIPCHK(c, nn_prepare(c, box, n_dst, d_dst.p, mode, pl, n_src));
     HIPCHK(c, hipEventRecord(ev[1].e, c->stream));
     HIPCHK(c, nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));      // warm (code load, caches)
     HIPCHK(c, hipEventRecord(ev[2].e, c->stream));
@@ -506,31 +515,26 @@ extern "C" int qs_nn_search(qs_ctx *c, const double *src_xy, size_t n_src, const
     return QS_OK;
 }
 
-extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const double *dst_xy, size_t n_dst, double max_dist,
-                      int32_t max_iter, double rel_fitness, double rel_rmse, double T[9], double *fitness, double *rmse,
-                      int32_t *iters)
+// registration_icp over device clouds: d_src (n_src points, MOVED in place step by step as the loop runs) against d_dst, whose
+// box is given (nn_box_host, or qs_bbox_kernel's for a cloud that lives on the device: the same numbers for finite clouds; the
+// box only centres the screen of the search, which never decides a result).  The host reads the six sums of every iteration.
+int qs_icp_device(qs_ctx *c, double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst, const double box[4], double max_dist,
+                  int32_t max_iter, double rel_fitness, double rel_rmse, double T[9], double *fitness, double *rmse, int32_t *iters)
 {
-    ARGCHK(c, c != nullptr && T != nullptr && fitness != nullptr && rmse != nullptr);
-    ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && max_iter >= 0);
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t nb = (n_src + 255) / 256;
-    DevBuf<double2> d_src, d_dst; DevBuf<int> d_corr; DevBuf<double> d_d2, d_part, d_out;
-    HIPCHK(c, d_src.alloc(n_src));
-    HIPCHK(c, d_dst.alloc(n_dst));
+    DevBuf<int> d_corr; DevBuf<double> d_d2, d_part, d_out;
     HIPCHK(c, d_corr.alloc(n_src));
     HIPCHK(c, d_d2.alloc(n_src));
     HIPCHK(c, d_part.alloc(nb * 6));
     HIPCHK(c, d_out.alloc(6));
-    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
     NnPlan pl;
-    HIPCHK(c, nn_prepare(c, dst_xy, n_dst, d_dst.p, 0, pl, n_src));     // the targets do not move: operands once per registration
+    HIPCHK(c, nn_prepare(c, box, n_dst, d_dst, 0, pl, n_src));     // the targets do not move: operands once per registration
     double tc = 1.0, ts = 0.0, tx = 0.0, ty = 0.0;          // accumulated transform
     double out[6] = {0};
     const double zero4[4] = {0, 0, 0, 0};
     auto evaluate = [&](double &fit, double &rm) -> hipError_t {
-        HIPRET(nn_run(c, pl, d_src.p, n_src, d_dst.p, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
-        HIPRET(qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 0, zero4, d_part.p, d_out.p));
+        HIPRET(nn_run(c, pl, d_src, n_src, d_dst, n_dst, max_dist * max_dist, d_corr.p, d_d2.p));
+        HIPRET(qs_launch_icp_sums(c, d_src, n_src, d_dst, d_corr.p, d_d2.p, 0, zero4, d_part.p, d_out.p));
         HIPRET(hipMemcpyAsync(out, d_out.p, sizeof out, hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipStreamSynchronize(c->stream));
         fit = out[0] / (double)n_src;
@@ -546,7 +550,7 @@ extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const doubl
             const double nn = out[0];
             const double means[4] = {out[2] / nn, out[3] / nn, out[4] / nn, out[5] / nn};
             double o2[6];
-            HIPCHK(c, qs_launch_icp_sums(c, d_src.p, n_src, d_dst.p, d_corr.p, d_d2.p, 1, means, d_part.p, d_out.p));
+            HIPCHK(c, qs_launch_icp_sums(c, d_src, n_src, d_dst, d_corr.p, d_d2.p, 1, means, d_part.p, d_out.p));
             HIPCHK(c, hipMemcpyAsync(o2, d_out.p, sizeof o2, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             const double theta = atan2(o2[1], o2[0]);
@@ -558,7 +562,7 @@ extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const doubl
         const double nc = uc * tc - us * ts, ns = us * tc + uc * ts;
         const double nx = uc * tx - us * ty + ux, ny = us * tx + uc * ty + uy;
         tc = nc; ts = ns; tx = nx; ty = ny;
-        HIPCHK(c, qs_launch_icp_transform(c, d_src.p, n_src, uc, us, ux, uy));
+        HIPCHK(c, qs_launch_icp_transform(c, d_src, n_src, uc, us, ux, uy));
         const double bfit = fit, brm = rm;
         HIPCHK(c, evaluate(fit, rm));
         if (fabs(bfit - fit) < rel_fitness && fabs(brm - rm) < rel_rmse) { it++; break; }
@@ -567,6 +571,23 @@ extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const doubl
     *fitness = fit; *rmse = rm;
     if (iters) *iters = it;
     return QS_OK;
+}
+
+extern "C" int qs_icp(qs_ctx *c, const double *src_xy, size_t n_src, const double *dst_xy, size_t n_dst, double max_dist,
+                      int32_t max_iter, double rel_fitness, double rel_rmse, double T[9], double *fitness, double *rmse,
+                      int32_t *iters)
+{
+    ARGCHK(c, c != nullptr && T != nullptr && fitness != nullptr && rmse != nullptr);
+    ARGCHK(c, n_src > 0 && n_dst > 0 && src_xy && dst_xy && max_dist > 0 && max_iter >= 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double2> d_src, d_dst;
+    HIPCHK(c, d_src.alloc(n_src));
+    HIPCHK(c, d_dst.alloc(n_dst));
+    HIPCHK(c, hipMemcpyAsync(d_src.p, src_xy, n_src * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dst.p, dst_xy, n_dst * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    double box[4];
+    nn_box_host(dst_xy, n_dst, box);
+    return qs_icp_device(c, d_src.p, n_src, d_dst.p, n_dst, box, max_dist, max_iter, rel_fitness, rel_rmse, T, fitness, rmse, iters);
 }
 
 // Diagnostic: measured fp64 MFMA rate of this GPU (dense v_mfma_f64_16x16x4_f64, every CU, 2 waves per SIMD), TFLOP/s.

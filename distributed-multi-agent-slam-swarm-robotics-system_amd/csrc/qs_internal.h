@@ -281,6 +281,15 @@ struct qs_ctx {
     size_t last_matches_n = 0;
     bool last_matches = false;
 
+    // map merge session (merge.hip): the merger node's state.  qs_reset and checkpoints leave it alone
+    DevBuf<double2> mg_cloud;                    // the global cloud; grown by allocate-new-and-move (a failed growth keeps it)
+    size_t mg_n = 0;                             //   ... its points
+    double mg_res = 0.05, mg_ox = 0.0, mg_oy = 0.0;       // map_resolution, map_origin (map_merger.py:31-33)
+    double mg_icp_threshold = 1.0, mg_min_fitness = 0.6;  // qs_merge_params (map_merger.py:46-54)
+    int mg_icp_iterations = 30;
+    DevBuf<char> mg_grid_ws;                     // a map message on its way to a cloud (merge.hip: qs_merge_grid_layout)
+    DevBuf<char> mg_pts_ws;                      // clouds, sort and run arrays of one callback (merge.hip: qs_merge_pts_layout)
+
     uint64_t next_seq = 0, epoch_base = 0, n_rebases = 0;
     DevBuf<unsigned int> d_flags;                // [QS_N_FLAGS] device words the host reads at synchronisation points (QS_FLAG_*)
     DevBuf<QsEdgeRec> d_edge;                    // [QS_EDGE_CAP] the waiting rays
@@ -396,6 +405,20 @@ hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,
                           const unsigned long long *const *d_src_counts, size_t n_src, size_t cell_off, size_t n_cells,
                           unsigned long long *dst_counts);
 hipError_t qs_launch_reset_small(qs_ctx *c);
+// order-preserving compactions (count -> scan -> ranked write): d_xy / d_pos == nullptr runs count and scan (chunk offsets into
+// d_chunk, [ceil(items / 1024)], the total into *d_count), otherwise the ranked writes of the first `cap` items.
+// cells > 50 of an int8 grid -> points; occupied (odd) stamps of a context's own map -> the same points;
+// positions where a sorted key array starts a new run
+hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox, double oy, double *d_xy,
+                                 size_t cap, unsigned long long *d_count, unsigned int *d_chunk);
+hipError_t qs_launch_stamps_to_pcd(qs_ctx *c, const unsigned int *d_stamps, int h, int w, double res, double ox, double oy, double *d_xy,
+                                   size_t cap, unsigned long long *d_count, unsigned int *d_chunk);
+hipError_t qs_launch_run_heads(qs_ctx *c, const unsigned long long *d_keys, size_t n, unsigned int *d_pos, size_t cap,
+                               unsigned long long *d_count, unsigned int *d_chunk);
+// box4 (ordered u64: min x, min y, max x, max y; the caller stores the identities first) of n points; the canvas of a cloud
+hipError_t qs_launch_bbox(qs_ctx *c, const double *d_xy, size_t n, unsigned long long *d_box4);
+hipError_t qs_launch_rasterise(qs_ctx *c, const double *d_xy, size_t n, double res, double minx, double miny, int h, int w,
+                               signed char *d_grid);
 // sparse_fuse.hip
 hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells);
 hipError_t qs_launch_sf_list_of(qs_ctx *c, const unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
@@ -411,6 +434,10 @@ hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
 // frontier_targets.hip: the centroids of the clusters of a labelled frontier workspace with >= min_cluster cells, in first-cell
 // order.  phase 0 counts them (QsFrLayout::total, after the scan); phase 1 writes them to d_cent
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
+// icp.hip
+hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel, unsigned long long *keys);
+int qs_icp_device(qs_ctx *c, double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst, const double box[4], double max_dist,
+                  int32_t max_iter, double rel_fitness, double rel_rmse, double T[9], double *fitness, double *rmse, int32_t *iters);
 // ekf.hip
 hipError_t qs_launch_ekf_ingest(qs_ctx *c, size_t n, const double *d_time, hipStream_t st);
 // ekf_scan.hip: the same filter over a large batch, parallel in time

@@ -14,12 +14,17 @@ import zlib
 import numpy as np
 
 from . import _lib
-from ._lib import QsConfig, QuasarError, UINT64_MAX, check
+from ._lib import QsConfig, QsMergeResult, QS_MERGE_STATUS, QuasarError, UINT64_MAX, check
 from . import protocol as P
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _dev_addr(a):
+    """A device address: an int, or anything with data_ptr() (a torch tensor)."""
+    return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a or 0)
 
 
 # ---- checkpoint file header (include/quasar_slam.h: "checkpoint / restore") ------------------------------------------------
@@ -692,6 +697,74 @@ class QuasarMapper:
             self._chk(self._L.qs_voxel_downsample(self._h, _ptr(a), len(a), voxel, _ptr(out), n.value, C.byref(n)),
                       "qs_voxel_downsample")
         return out
+
+    def voxel_downsample_device(self, d_xy, n, voxel, d_out=0, cap=0):
+        """voxel_downsample over a cloud on the device (qs_voxel_downsample_device): d_xy, d_out are device addresses of float64
+        x y pairs (n points in, room for cap out; d_out = 0 queries the count) or torch tensors on this GPU.  -> number of
+        voxels.  Same points, same order, same bits as voxel_downsample."""
+        k = C.c_size_t()
+        self._chk(self._L.qs_voxel_downsample_device(self._h, C.c_void_p(_dev_addr(d_xy)), int(n), voxel,
+                                                     C.c_void_p(_dev_addr(d_out)), int(cap), C.byref(k)), "qs_voxel_downsample_device")
+        return k.value
+
+    # -- map merge session: map_merger.py:28-127 with the node's state on the device ----------------
+    def merge_reset(self):
+        """Empty the session's global cloud (the ICP parameters stay); the next map is adopted."""
+        self._chk(self._L.qs_merge_reset(self._h), "qs_merge_reset")
+
+    def merge_params(self, icp_threshold=1.0, icp_iterations=30, min_fitness=0.6):
+        self._chk(self._L.qs_merge_params(self._h, icp_threshold, icp_iterations, min_fitness), "qs_merge_params")
+
+    @staticmethod
+    def _merge_result(r):
+        return {"status": QS_MERGE_STATUS[r.status], "iterations": int(r.iterations), "n_local": int(r.n_local),
+                "n_global": int(r.n_global), "fitness": float(r.fitness), "rmse": float(r.rmse),
+                "T": np.array(r.T, dtype=np.float64).reshape(3, 3)}
+
+    def merge_grid(self, grid, res, ox, oy):
+        """One map_callback (map_merger.py:35-62) of the session: grid is an int8 [h, w] numpy array, or a contiguous torch
+        int8 tensor on this GPU whose contents are complete (nothing is uploaded then).  -> dict: status ("empty", "adopted",
+        "merged", "rejected"), T, fitness, rmse, iterations (those of icp(local, global cloud)), n_local, n_global."""
+        r = QsMergeResult()
+        if hasattr(grid, "data_ptr"):
+            if not (grid.is_cuda and grid.is_contiguous() and grid.dim() == 2 and grid.element_size() == 1):
+                raise ValueError("merge_grid: a device grid is a contiguous 2-D int8 tensor on the GPU")
+            h, w = grid.shape
+            self._chk(self._L.qs_merge_grid_device(self._h, C.c_void_p(grid.data_ptr()), h, w, res, ox, oy, C.byref(r)),
+                      "qs_merge_grid_device")
+        else:
+            grid = np.ascontiguousarray(grid, dtype=np.int8)
+            h, w = grid.shape
+            self._chk(self._L.qs_merge_grid(self._h, _ptr(grid), h, w, res, ox, oy, C.byref(r)), "qs_merge_grid")
+        return self._merge_result(r)
+
+    def merge_map(self, src):
+        """One map_callback with another mapper's own map (or this one's) as the message, read from its stamps on the device:
+        what merge_grid(src.grid_i8(), src.res, src.ox, src.oy) gives, with no int8 view and no transfer."""
+        r = QsMergeResult()
+        self._chk(self._L.qs_merge_map(self._h, src._h, C.byref(r)), "qs_merge_map")
+        return self._merge_result(r)
+
+    def merge_cloud(self):
+        """The session's global cloud -> float64 [n, 2]."""
+        n = C.c_size_t()
+        self._chk(self._L.qs_merge_cloud(self._h, None, 0, C.byref(n)), "qs_merge_cloud")
+        xy = np.zeros((n.value, 2), dtype=np.float64)
+        if n.value:
+            self._chk(self._L.qs_merge_cloud(self._h, _ptr(xy), n.value, C.byref(n)), "qs_merge_cloud")
+        return xy
+
+    def merge_global_map(self):
+        """publish_global_map (map_merger.py:87-127) of the session's cloud -> (int8 grid, (min_x, min_y)), or (None, None)
+        while it is empty."""
+        dims = np.zeros(2, dtype=np.int32)
+        origin = np.zeros(2, dtype=np.float64)
+        self._chk(self._L.qs_merge_global_map(self._h, _ptr(dims), _ptr(origin), None), "qs_merge_global_map")
+        if dims[0] == 0:
+            return None, None
+        grid = np.empty((int(dims[0]), int(dims[1])), dtype=np.int8)
+        self._chk(self._L.qs_merge_global_map(self._h, _ptr(dims), _ptr(origin), _ptr(grid)), "qs_merge_global_map")
+        return grid, origin
 
     # -- frontiers: dual_bot_mapper.py:181-237, :948-956 ----------------------------------------
     def frontier_cells(self):

@@ -377,6 +377,60 @@ int qs_diag_latencies(qs_ctx *ctx, double out[QS_DIAG_LAT_N]);
 int qs_voxel_downsample(qs_ctx *ctx, const double *xy, size_t n, double voxel, double *out_xy,
                         size_t cap, size_t *n_out);
 
+/* The same down-sampling over a cloud that is already on the device, with the grouping there too: d_xy (n points, x y pairs)
+ * and d_out_xy (room for cap points; may be NULL to query the count) are device pointers on the context's GPU and must not
+ * overlap.  Returns exactly what qs_voxel_downsample returns for the same points: one point per voxel in ascending key
+ * order, key (vy << 32) | vx, each mean the fp64 sum of the voxel's points taken one after the other IN INPUT ORDER, divided
+ * by their number.  Keys are grouped by a stable least-significant-digit radix sort of (key, input index), 8 bits per pass,
+ * over the bytes the cloud's bounding box says are in use (a room-sized cloud: 2 to 4 passes).  The input must be finite.
+ * The caller's own work on the two arrays must be complete before the call; the result is complete when it returns.
+ * cap < *n_out writes the first cap points. */
+int qs_voxel_downsample_device(qs_ctx *ctx, const double *d_xy, size_t n, double voxel, double *d_out_xy,
+                               size_t cap, size_t *n_out);
+
+/* ---- map merge session: the MapMerger node, server_nodes/map_merger.py:28-127, with its state on the device ----------------
+ * The context keeps the node's state: the global cloud (global_pcd, :31), map_resolution and map_origin (:32-33) and the ICP
+ * parameters (:46-54; defaults: threshold 1.0, 30 iterations, min fitness 0.6).  One qs_merge_grid / _grid_device / _map call is
+ * one map_callback (:35-62), step for step; every step runs the kernels of the entry point named beside it, so each can be
+ * checked against that entry point bit for bit:
+ *   1. local cloud: the cells with grid > 50 in row-major order, x = col*res + ox, y = row*res + oy [qs_grid_to_pcd].
+ *      qs_merge_map reads src's own map instead, straight from its stamps (occupied = an odd stamp; geometry = src's
+ *      configuration; no int8 view is built): the cloud qs_merge_grid makes of src's qs_grid_i8.  src must be on ctx's GPU
+ *      (QS_E_INVAL otherwise) and may be ctx itself; its waiting edge rays are resolved first, as in every call that observes
+ *      the map.  No point: QS_MERGE_EMPTY, nothing changes.
+ *   2. empty global cloud: the local cloud, res and the origin are adopted: QS_MERGE_ADOPTED.
+ *   3. otherwise the local cloud is registered against the global cloud [the loop of qs_icp, identity start, the session's
+ *      threshold and iterations, rel_fitness = rel_rmse = 1e-6]: T, fitness, rmse, iterations are those of
+ *      qs_icp(local, global).
+ *   4. fitness < min_fitness: QS_MERGE_REJECTED, the global cloud is unchanged.
+ *   5. the accumulated T is applied to the ORIGINAL local points (not the copy the loop moved step by step),
+ *      x' = (T[0]*x + T[1]*y) + T[2], y' = (T[3]*x + T[4]*y) + T[5], products and sums rounded one by one; they are appended
+ *      behind the global cloud and the whole is down-sampled at map_resolution [qs_voxel_downsample_device]: QS_MERGE_MERGED.
+ *   6. qs_merge_global_map is publish_global_map (:87-127) [qs_rasterise over the resident cloud, the same QS_E_RANGE rule];
+ *      dims {0, 0} while the cloud is empty.
+ * No cloud crosses to the host inside a callback: the host reads scalars only (the local count, the global cloud's box, the
+ * six sums of every ICP iteration, the final count).  qs_merge_grid uploads the message's grid, qs_merge_grid_device and
+ * qs_merge_map upload nothing.  d_grid is a device pointer on the context's GPU whose contents are complete before the call.
+ * qs_reset does not touch the session (the merger is a node of its own in the reference): qs_merge_reset empties it
+ * (parameters stay).  Checkpoints do not hold the session.  out (may be NULL) reports the callback.
+ * qs_merge_params: icp_threshold > 0, icp_iterations >= 0, min_fitness not NaN, else QS_E_INVAL.
+ * qs_merge_cloud: *n_out = points of the global cloud; the first cap of them to xy (host, may be NULL). */
+enum { QS_MERGE_EMPTY = 0, QS_MERGE_ADOPTED = 1, QS_MERGE_MERGED = 2, QS_MERGE_REJECTED = 3 };
+typedef struct qs_merge_result {
+    int32_t status, iterations;
+    uint64_t n_local, n_global;      /* points of this map; points of the global cloud after the call */
+    double fitness, rmse, T[9];      /* as qs_icp reports them; identity / 0 when no registration ran */
+} qs_merge_result;
+int qs_merge_reset(qs_ctx *ctx);
+int qs_merge_params(qs_ctx *ctx, double icp_threshold, int32_t icp_iterations, double min_fitness);
+int qs_merge_grid(qs_ctx *ctx, const int8_t *grid, int32_t h, int32_t w, double res, double ox, double oy,
+                  qs_merge_result *out);
+int qs_merge_grid_device(qs_ctx *ctx, const int8_t *d_grid, int32_t h, int32_t w, double res, double ox, double oy,
+                         qs_merge_result *out);
+int qs_merge_map(qs_ctx *ctx, qs_ctx *src, qs_merge_result *out);
+int qs_merge_cloud(qs_ctx *ctx, double *xy, size_t cap, size_t *n_out);
+int qs_merge_global_map(qs_ctx *ctx, int32_t dims[2], double origin[2], int8_t *grid);
+
 /* ---- frontiers  dual_bot_mapper.py:181-237, :948-956 -------------------------------------------
  * OccupancyGrid.get_frontiers: interior FREE cells with a 4-neighbour UNKNOWN, row-major order
  * (gx, gy pairs).  xy == NULL queries the count. */

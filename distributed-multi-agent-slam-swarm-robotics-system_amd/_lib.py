@@ -32,6 +32,11 @@ class QsMatchParams(C.Structure):
                 ("min_percent", C.c_int32), ("reserved", C.c_int32), ("angle_step", C.c_double)]
 
 
+class QsSweepGraphParams(C.Structure):
+    """struct qs_sweep_graph_params (include/quasar_slam.h)."""
+    _fields_ = [("half_width", C.c_int32), ("reserved", C.c_int32), ("close", C.c_double), ("open", C.c_double)]
+
+
 class QsSweepMatch(C.Structure):
     """struct qs_sweep_match (include/quasar_slam.h)."""
     _fields_ = [("ix", C.c_int32), ("iy", C.c_int32), ("it", C.c_int32), ("score", C.c_int32), ("score0", C.c_int32),
@@ -111,6 +116,11 @@ SIGNATURES = {
     "qs_ingest_sweeps_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_last_sweeps": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_set_sweep_filter": (_i32, [_vp, _f64, _f64]),
+    "qs_set_sweep_graph": (_i32, [_vp, _i32, _vp]),
+    "qs_sweep_graph": (_i32, [_vp, C.POINTER(_i32), C.POINTER(QsSweepGraphParams)]),
+    "qs_sweep_signatures": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "qs_sweep_signatures_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "qs_last_sweep_nodes": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_match_field": (_i32, [_vp, _i32, _vp]),
     "qs_match_sweeps": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "qs_match_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),

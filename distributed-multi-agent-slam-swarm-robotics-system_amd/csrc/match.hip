@@ -314,7 +314,7 @@ static int match_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
 }
 
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,
-                           const unsigned short *d_lens, qs_sweep_match *out, double *rot)
+                           const unsigned short *d_lens, qs_sweep_match *out, double *rot, size_t graph_k0)
 {
     if (n == 0) return hipSuccess;
     if (!c->match_tab.p) {                                         // the beam angles' cos / sin: libm's, once per context
@@ -328,7 +328,7 @@ hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned cha
         HIPRET(hipMemcpy(c->match_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
     }
     QsSweepArgs a;
-    qs_sweep_args(c, d_pkts, n, stride, d_lens, a);
+    qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     QsMatchArgs m;
     m.R = ms.R; m.W = ms.W; m.T = ms.T; m.min_hits = ms.min_hits; m.min_percent = ms.min_percent;
     m.half = ms.reach + 1 + ms.W;
@@ -377,7 +377,7 @@ extern "C" int qs_match_sweeps_device(qs_ctx *c, const qs_match_params *params, 
     if (rc != QS_OK || n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SYNCCHK(c);
-    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, d_out, d_rot_out));
+    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, d_out, d_rot_out, QS_SWEEP_NO_GRAPH));
     return QS_OK;
 }
 
@@ -408,7 +408,7 @@ extern "C" int qs_match_sweeps(qs_ctx *c, const qs_match_params *params, const u
         double *d_rot = rot_out ? io.take<double>(m * rot_per) : nullptr;
         HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
         if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, d_out, d_rot));
+        HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, d_out, d_rot, QS_SWEEP_NO_GRAPH));
         HIPCHK(c, hipMemcpyAsync(out + k0, d_out, m * sizeof(qs_sweep_match), hipMemcpyDeviceToHost, c->stream));
         if (rot_out) HIPCHK(c, hipMemcpyAsync(rot_out + k0 * rot_per, d_rot, m * rot_per * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));

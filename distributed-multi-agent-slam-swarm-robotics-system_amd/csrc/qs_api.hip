@@ -623,24 +623,39 @@ int sync_host_state(qs_ctx *c, bool host_waits)
     return QS_OK;
 }
 
+int qs_batch_prepare(qs_ctx *c, size_t n)
+{
+    int rc = ensure_batch(c, n);
+    if (rc != QS_OK) return rc;
+    c->b.n = n;
+    HIPCHK(c, hipMemsetAsync(c->d_graph_batch.p, 0, (size_t)c->n_graphs * 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->sb.agent_ev, 0, ((size_t)c->cfg.max_agent + 2) * sizeof(unsigned int), c->stream));
+    return QS_OK;
+}
+
+int qs_batch_slam(qs_ctx *c, size_t n)
+{
+    int rc = reserve_graphs_for_batch(c, n);
+    if (rc != QS_OK) return rc;
+    chain_stats_poll(c, false, nullptr);
+    { StageTimer t(c, QS_STAGE_SLAM); HIPCHK(c, qs_launch_slam(c, n)); t.stop(); }
+    c->flags_maybe = true;
+    return chain_stats_request(c);
+}
+
 static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stride, const uint16_t *d_lens,
                          const double *d_time, uint64_t seq0)
 {
     if (seq0 == UINT64_MAX) seq0 = c->next_seq;
     c->last_n = n; c->last_has_poses = true; c->last_sweeps = false; c->last_matches = false;
     if (n == 0) return QS_OK;
-    int rc = ensure_batch(c, n);
+    int rc = qs_batch_prepare(c, n);
     if (rc != QS_OK) return rc;
-    c->b.n = n;
     const uint64_t sstride = c->cfg.seq_stride > 0 ? (uint64_t)c->cfg.seq_stride : 1;
     // epoch decisions use the stride-aligned range so that all ranks of a sharded stream agree
     rc = ensure_epoch(c, seq0 - seq0 % sstride, n * sstride);
     if (rc != QS_OK) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_graph_batch.p, 0, (size_t)c->n_graphs * 2 * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->sb.agent_ev, 0, ((size_t)c->cfg.max_agent + 2) * sizeof(unsigned int), c->stream));
     { StageTimer t(c, QS_STAGE_DECODE); HIPCHK(c, qs_launch_decode(c, d_pkts, n, stride, d_lens)); t.stop(); }
-    rc = reserve_graphs_for_batch(c, n);
-    if (rc != QS_OK) return rc;
     if (c->cfg.enable_ekf) {
         // fork: the filter only needs the decoded fields, never the map (and the map never the filter)
         if (!c->ekf_stream) { int rce = ekf_stream_acquire(c); if (rce != QS_OK) return rce; }
@@ -650,9 +665,8 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
                                                    : qs_launch_ekf_ingest(c, n, d_time, c->ekf_stream)); t.stop(); }
         HIPCHK(c, hipEventRecord(c->ev_ekf_done, c->ekf_stream));
     }
-    chain_stats_poll(c, false, nullptr);
-    { StageTimer t(c, QS_STAGE_SLAM); HIPCHK(c, qs_launch_slam(c, n)); t.stop(); }
-    { int rcs = chain_stats_request(c); if (rcs != QS_OK) return rcs; }
+    rc = qs_batch_slam(c, n);
+    if (rc != QS_OK) return rc;
     {
         StageTimer t(c, QS_STAGE_RAYCAST);
         // auto (0): a handful of packets (the live UDP path: <= 20 per frame) is one direct kernel instead
@@ -664,7 +678,6 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
     }
     if (c->cfg.enable_ekf) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ekf_done, 0));   // join
     if (c->b.edge) c->edge_maybe = true;                 // resolved at the next point the map is observed (sync_host_state)
-    c->flags_maybe = true;
     c->next_seq = seq0 + n * sstride;
     c->dirty_since_fuse = true;
     return QS_OK;
@@ -931,7 +944,7 @@ extern "C" int qs_slam_add_poses(qs_ctx *c, const double *x, const double *y, co
     HIPCHK(c, hipStreamSynchronize(c->stream));
     rc = sync_host_state(c, true);
     if (rc != QS_OK) return rc;
-    c->last_has_poses = false;
+    c->last_has_poses = false; c->last_sweep_graph = false;      // (the batch arrays are this call's now)
     if (closed) memset(closed, 0, n);
     if (corr2) for (size_t i = 0; i < 2 * n; i++) corr2[i] = 0.0;
     if (!closed && !corr2) return QS_OK;

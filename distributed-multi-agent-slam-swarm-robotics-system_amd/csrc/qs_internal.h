@@ -276,6 +276,9 @@ struct qs_ctx {
     double sweep_min = 0.1, sweep_max = 1.2;     //   trust filter smin < d <= smax (qs_set_sweep_filter)
     size_t last_sweeps_n = 0;
     bool last_sweeps = false;                    //   the last ingest was qs_ingest_sweeps*: qs_last_sweeps may read it
+    bool sweep_graph = false;                    // graph mode (qs_set_sweep_graph, sweep_graph.hip): a sweep is a pose-graph node
+    qs_sweep_graph_params sg_params{5, 0, 0.40, 0.80};
+    bool last_sweep_graph = false;               //   the last sweep ingest ran in graph mode: qs_last_sweep_nodes may read the batch
     DevBuf<double> match_tab;                    // sweep matching (match.hip): cos, sin of the 181 beam angles, from the host's libm
     DevBuf<qs_sweep_match> match_out;            //   ... the matches of the last matched ingest (qs_last_sweep_matches)
     size_t last_matches_n = 0;
@@ -355,6 +358,12 @@ double r2_threshold_for(double radius);
 int graph_reserve(qs_ctx *c, int g, long long need_lms, long long need_cls, long long have_lms, long long have_cls);
 int reset_state(qs_ctx *c);                              // qs_reset: an empty map, enqueued (no wait for the GPU)
 int ensure_batch(qs_ctx *c, size_t n);                   // room for n records; a growth that fails leaves the old arrays
+// What every ingest that feeds the pose graphs does round its own decoder, before its rays are cast.  qs_batch_prepare: room for
+// n records, the batch's per-graph and per-bot counts cleared.  Then the caller's decoder fills QsBatch, graph_batch and agent_ev
+// for the n records (under QS_STAGE_DECODE).  qs_batch_slam: the graphs' capacity for the batch, then the SLAM stage under
+// QS_STAGE_SLAM with the chain statistics polled before it and asked for behind it.
+int qs_batch_prepare(qs_ctx *c, size_t n);
+int qs_batch_slam(qs_ctx *c, size_t n);
 // n_seq sequence numbers from seq0 fit the stamp epoch (a rebase first if they do not)
 int ensure_epoch(qs_ctx *c, uint64_t seq0, size_t n_seq);
 // device staging of host-side records: bytes of records, one length and one receive time per (shortest) record, laid out for
@@ -393,12 +402,20 @@ hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axi
 // raycast_tiled.hip
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
 bool qs_tiled_supported(const qs_ctx *c);
+// sweep_graph.hip: signature and acceptance of n device-resident sweep records.  lm_out == nullptr: into the batch arrays from
+// record k0 on (QsBatch fields, graph_batch, agent_ev); otherwise only lm_out[k] (255 = rejected), nothing of the context
+hipError_t qs_launch_sweep_signatures(qs_ctx *c, const qs_sweep_graph_params &p, const unsigned char *d_pkts, size_t n, size_t stride,
+                                      const unsigned short *d_lens, size_t k0, unsigned char *lm_out);
+// graph mode's pass over all n records of a sweep call before any chunk is mapped: signatures into the batch, then the SLAM stage.
+// host: pkts / lens are host buffers, staged `chunk` records at a time
+int qs_sweep_graph_pass(qs_ctx *c, const uint8_t *pkts, bool host, size_t n, size_t stride, const uint16_t *lens, size_t chunk);
 // match.hip: the parameters of one matching call, checked against the context's sweep filter and resolution
 struct QsMatchSetup { int R, W, T, min_hits, min_percent, reach; double step; };
 int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, QsMatchSetup &ms);
-// n device-resident records matched against the map as the stream finds it; rot (optional): [n][2 T + 1][2] the (sin, cos) used
+// n device-resident records matched against the map as the stream finds it; rot (optional): [n][2 T + 1][2] the (sin, cos) used;
+// graph_k0 as qs_sweep_args takes it (sweep_common.h): QS_SWEEP_NO_GRAPH, or the record of a graph-mode call the n records start at
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,
-                           const unsigned short *d_lens, qs_sweep_match *out, double *rot);
+                           const unsigned short *d_lens, qs_sweep_match *out, double *rot, size_t graph_k0);
 // grid_ops.hip
 hipError_t qs_launch_rebase(qs_ctx *c);
 hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,

@@ -14,7 +14,10 @@
 //   qs_sweep_rays_kernel    pass A: projection, grid end points, edge test, ray slots + hit flags, per-tile LDS histogram row;
 //                           rays longer than a tile go to the grid directly (as qs_rays_kernel)
 //   qs_sweep_direct_kernel  the whole cast with one global atomic per cell (small calls, raycast_mode 1)
-// A sweep adds no pose-graph node, landmark, EKF step or zone point: those belong to the 42 / 41-byte path.
+// A sweep adds no pose-graph node, landmark, EKF step or zone point: those belong to the 42 / 41-byte path -- unless the context
+// is in graph mode (qs_set_sweep_graph; sweep_graph.hip).  Then, before any chunk is mapped, a signature pass decides every record of
+// the call and derives its landmark byte from the ranges, the unchanged SLAM stage adds the nodes and runs the loop-closure chain,
+// and these kernels' GRAPH instantiations take acceptance and pose from the batch it left (sw_head_t) and add the zone points.
 // The matched ingest (qs_ingest_sweeps_matched*, at the end of this file) runs match.hip's kernel over the whole call and then
 // these kernels' CORR instantiations, which add each record's correction to its pose before anything else.
 #include <math.h>
@@ -49,11 +52,37 @@ __device__ inline void sw_out(const QsSweepArgs &a, size_t k, const SwHead &h)
     if (h.ok) { a.pose[3 * k] = h.rx; a.pose[3 * k + 1] = h.ry; a.pose[3 * k + 2] = h.yaw; }
 }
 
+// graph mode's zone points of one record: every lane keeps the box of its own beams' hit points (lane 0 starts from the pose the
+// sweep is cast from, paths[agent].append :878-879), the wave folds the 64 boxes -- min and max are exact in any order -- and
+// lane 0 puts the result into the workgroup's box of the bot: eight LDS atomics per record (qs_zone_point for the low and for the
+// high corner), not four per hit beam
+struct SwBox { double x0, y0, x1, y1; };
+__device__ inline SwBox sw_box(const SwHead &h)
+{
+    const bool p = h.ok && (threadIdx.x & (QS_WAVE - 1)) == 0;
+    return SwBox{p ? h.rx : __builtin_inf(), p ? h.ry : __builtin_inf(), p ? h.rx : -__builtin_inf(), p ? h.ry : -__builtin_inf()};
+}
+__device__ inline void sw_box_point(SwBox &b, double x, double y)
+{
+    b.x0 = fmin(b.x0, x); b.y0 = fmin(b.y0, y); b.x1 = fmax(b.x1, x); b.y1 = fmax(b.y1, y);
+}
+// (every lane of the wave is here: the record's acceptance is uniform over it)
+__device__ inline void sw_box_commit(SwBox b, double (*s_zone)[4], int agent, int lane)
+{
+    #pragma unroll
+    for (int m = QS_WAVE / 2; m >= 1; m >>= 1) {
+        b.x0 = fmin(b.x0, __shfl_xor(b.x0, m)); b.y0 = fmin(b.y0, __shfl_xor(b.y0, m));
+        b.x1 = fmax(b.x1, __shfl_xor(b.x1, m)); b.y1 = fmax(b.y1, __shfl_xor(b.y1, m));
+    }
+    if (lane == 0) { qs_zone_point(s_zone, agent, b.x0, b.y0); qs_zone_point(s_zone, agent, b.x1, b.y1); }
+}
+
 // ---- pass A of the tiled raycast -----------------------------------------------------------------------------------------
 // Workgroup w owns records [w * pk_per_wg, (w + 1) * pk_per_wg) (pk_per_wg a multiple of 16), its 16 waves one record each per
 // round, and writes ray slots [184 * that range) plus its row of the tile table.
 // CORR: the matched ingest's instantiation (every pose gets its record's correction first); the plain ingest's is CORR = false
-template <bool COUNTS, bool CORR>
+// GRAPH: graph mode's (acceptance and pose from the batch slice; path and cloud points into the bots' zone boxes)
+template <bool COUNTS, bool CORR, bool GRAPH>
 __global__ void __launch_bounds__(QT_BIN_BLOCK)
 qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsigned char *__restrict__ hit_valid,
                      unsigned int *__restrict__ stamps, unsigned long long *__restrict__ counts,
@@ -63,8 +92,10 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
     extern __shared__ unsigned int s_hist[];                       // [n_tiles]
     __shared__ unsigned int s_rec[NW][SW_DW];
     __shared__ unsigned int s_cnt[4];
+    __shared__ double s_zone[GRAPH ? QS_MAX_AGENT + 1 : 1][4];
     const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) s_hist[t] = 0;
+    if (GRAPH) for (int t = tid; t <= a.max_agent; t += QT_BIN_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
     if (tid < 4) s_cnt[tid] = 0;
     const size_t k0 = (size_t)blockIdx.x * ws.pk_per_wg;
     const size_t k1 = (k0 + ws.pk_per_wg < a.n) ? k0 + ws.pk_per_wg : a.n;
@@ -77,9 +108,10 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
         if (k >= k1) continue;
         const unsigned int *s = s_rec[wave];
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
-        SwHead h = sw_head(a, k, s, mis);
+        SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
         if (lane == 0) { sw_out(a, k, h); my_acc += h.ok ? 1u : 0u; }
+        SwBox box = sw_box(h);
         #pragma unroll
         for (int q = 0; q < 3; q++) {
             const int i = lane + QS_WAVE * q;
@@ -91,6 +123,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
                 const float df = __uint_as_float(sw_u32(s, mis, a.ranges_off + 4u * (unsigned int)i));
                 const QsRay ray = sw_beam(h, i, (double)df, a.smin, a.smax);
                 valid = ray.valid;
+                if (GRAPH && valid) sw_box_point(box, ray.ex, ray.ey);         // point_clouds[..].append  :892
                 my_hits += valid ? 1u : 0u;
                 my_rays++;
                 const unsigned int key_free = (unsigned int)((a.ord_base + r + 1) << 1);
@@ -117,6 +150,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
             ws.rays[r] = rec;
             hit_valid[r] = valid ? 1 : 0;
         }
+        if (GRAPH && h.ok) sw_box_commit(box, s_zone, h.agent, lane);
     }
     if (my_rays) atomicAdd(&s_cnt[0], my_rays);
     if (my_cells) atomicAdd(&s_cnt[1], my_cells);
@@ -125,6 +159,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
     __syncthreads();
     unsigned int *row = ws.table + (size_t)blockIdx.x * ws.n_tiles;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) row[t] = s_hist[t];
+    if (GRAPH) for (int t = tid; t <= a.max_agent; t += QT_BIN_BLOCK) qs_zone_commit(s_zone, t, a.zone);
     if (tid == 0) {
         atomicAdd(&counters[QS_CNT_DATAGRAMS], (unsigned long long)(k1 - k0));
         if (s_cnt[3]) atomicAdd(&counters[QS_CNT_ACCEPTED], (unsigned long long)s_cnt[3]);
@@ -135,7 +170,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
 }
 
 // ---- direct form: one wave per record, every cell one global atomic --------------------------------------------------------
-template <bool COUNTS, bool CORR>
+template <bool COUNTS, bool CORR, bool GRAPH>
 __global__ void __launch_bounds__(SW_DIRECT_BLOCK)
 qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__restrict__ stamps,
                        unsigned long long *__restrict__ counts, unsigned long long *__restrict__ counters)
@@ -143,8 +178,10 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
     constexpr int NW = SW_DIRECT_BLOCK / QS_WAVE;
     __shared__ unsigned int s_rec[NW][SW_DW];
     __shared__ unsigned int s_cnt[4];
+    __shared__ double s_zone[GRAPH ? QS_MAX_AGENT + 1 : 1][4];
     const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
     if (tid < 4) s_cnt[tid] = 0;
+    if (GRAPH) for (int t = tid; t <= a.max_agent; t += SW_DIRECT_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
     const size_t k = (size_t)blockIdx.x * NW + wave;
     sw_stage(a, k, s_rec[wave], lane);
     __syncthreads();
@@ -152,16 +189,18 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
     if (k < a.n) {
         const unsigned int *s = s_rec[wave];
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
-        SwHead h = sw_head(a, k, s, mis);
+        SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
         if (lane == 0) { sw_out(a, k, h); if (h.ok) atomicAdd(&s_cnt[3], 1u); }
         if (h.ok) {
+            SwBox box = sw_box(h);
             #pragma unroll
             for (int q = 0; q < 3; q++) {
                 const int i = lane + QS_WAVE * q;
                 if (i >= QS_SWEEP_BEAMS) break;
                 const float df = __uint_as_float(sw_u32(s, mis, a.ranges_off + 4u * (unsigned int)i));
                 const QsRay ray = sw_beam(h, i, (double)df, a.smin, a.smax);
+                if (GRAPH && ray.valid) sw_box_point(box, ray.ex, ray.ey);     // point_clouds[..].append  :892
                 my_hits += ray.valid ? 1u : 0u;
                 my_rays++;
                 const unsigned int key_free = (unsigned int)((a.ord_base + QS_SWEEP_SLOTS * k + i + 1) << 1);
@@ -172,12 +211,14 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
                     my_cells += qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
                 }
             }
+            if (GRAPH) sw_box_commit(box, s_zone, h.agent, lane);
         }
     }
     if (my_rays) atomicAdd(&s_cnt[0], my_rays);
     if (my_cells) atomicAdd(&s_cnt[1], my_cells);
     if (my_hits) atomicAdd(&s_cnt[2], my_hits);
     __syncthreads();
+    if (GRAPH) for (int t = tid; t <= a.max_agent; t += SW_DIRECT_BLOCK) qs_zone_commit(s_zone, t, a.zone);
     if (tid == 0) {
         const size_t k0 = (size_t)blockIdx.x * NW;
         atomicAdd(&counters[QS_CNT_DATAGRAMS], (unsigned long long)(a.n - k0 < (size_t)NW ? a.n - k0 : (size_t)NW));
@@ -190,16 +231,16 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
-template <bool CORR>
+template <bool CORR, bool GRAPH>
 static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, bool tiled, unsigned char *hit_valid)
 {
     if (!tiled || !qs_tiled_supported(c)) {
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
         if (c->cfg.enable_counts)
-            hipLaunchKernelGGL((qs_sweep_direct_kernel<true, CORR>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
+            hipLaunchKernelGGL((qs_sweep_direct_kernel<true, CORR, GRAPH>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
                                c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         else
-            hipLaunchKernelGGL((qs_sweep_direct_kernel<false, CORR>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
+            hipLaunchKernelGGL((qs_sweep_direct_kernel<false, CORR, GRAPH>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
                                c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         return hipGetLastError();
     }
@@ -213,24 +254,26 @@ static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, 
     ws.pk_per_wg = per;
     ws.rays_per_wg = QS_SWEEP_SLOTS * per;
     ws.nwg = (int)((n + per - 1) / per);
-    const void *pass_a[2] = {(const void *)qs_sweep_rays_kernel<true, CORR>, (const void *)qs_sweep_rays_kernel<false, CORR>};
+    const void *pass_a[2] = {(const void *)qs_sweep_rays_kernel<true, CORR, GRAPH>, (const void *)qs_sweep_rays_kernel<false, CORR, GRAPH>};
     size_t lds = 0;
     e = qt_dyn_lds(ws, pass_a, 2, lds);
     if (e != hipSuccess) return e;
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
     if (c->cfg.enable_counts)
-        hipLaunchKernelGGL((qs_sweep_rays_kernel<true, CORR>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
+        hipLaunchKernelGGL((qs_sweep_rays_kernel<true, CORR, GRAPH>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
                            hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     else
-        hipLaunchKernelGGL((qs_sweep_rays_kernel<false, CORR>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
+        hipLaunchKernelGGL((qs_sweep_rays_kernel<false, CORR, GRAPH>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
                            hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     t_rays.stop();
     // slot r = 184 k + i has stamp ordinal ord_base + 4 (r >> 2) + (r & 3) + 1 = ord_base + r + 1: the 4-ray layout's
     return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);
 }
 
-// what every sweep kernel reads of the context (match.hip fills its own with it too)
-void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, QsSweepArgs &a)
+// what every sweep kernel reads of the context (match.hip fills its own with it too).  graph_k0: QS_SWEEP_NO_GRAPH, or the record of
+// a graph-mode call these n records start at -- their slice of the batch that qs_sweep_graph_pass left
+void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, size_t graph_k0,
+                   QsSweepArgs &a)
 {
     a.pkts = d_pkts; a.n = n; a.stride = stride; a.lens = d_lens;
     a.ranges_off = stride == QS_SWEEP_SIZE_V0 ? 19u : 27u;
@@ -238,21 +281,28 @@ void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_
     a.offset = c->d_offset.p; a.drift = c->d_drift.p;
     a.smin = c->sweep_min; a.smax = c->sweep_max;
     a.accept = nullptr; a.pose = nullptr; a.ord_base = 0; a.corr = nullptr;
+    a.g_accept = a.g_agent = nullptr; a.g_rx = a.g_ry = nullptr; a.zone = nullptr;
+    if (graph_k0 != QS_SWEEP_NO_GRAPH) {
+        a.g_accept = c->b.accept + graph_k0; a.g_agent = c->b.agent + graph_k0;
+        a.g_rx = c->b.rx + graph_k0; a.g_ry = c->b.ry + graph_k0;
+        a.zone = c->d_zone.p;
+    }
 }
 
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]; corr: the
-// matched ingest's corrections of these records, nullptr for the plain ingest
+// matched ingest's corrections of these records, nullptr for the plain ingest; graph_k0 as qs_sweep_args takes it
 static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
                                    uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid,
-                                   const qs_sweep_match *corr)
+                                   const qs_sweep_match *corr, size_t graph_k0)
 {
     if (n == 0) return hipSuccess;
     QsSweepArgs a;
-    qs_sweep_args(c, d_pkts, n, stride, d_lens, a);
+    qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     a.accept = accept; a.pose = pose;
     a.ord_base = 4ull * (seq0 - c->epoch_base);
     a.corr = corr;
-    return corr ? qs_launch_sweeps_t<true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false>(c, a, n, tiled, hit_valid);
+    if (a.g_accept) return corr ? qs_launch_sweeps_t<true, true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, true>(c, a, n, tiled, hit_valid);
+    return corr ? qs_launch_sweeps_t<true, false>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, false>(c, a, n, tiled, hit_valid);
 }
 
 // ---- C ABI: servo sweeps (semantics in include/quasar_slam.h) --------------------------------------------------------
@@ -263,6 +313,7 @@ static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
 static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 {
     c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
+    c->last_sweep_graph = false;                           // qs_last_sweep_nodes: only after an ingest in graph mode
     if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
     if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
@@ -280,9 +331,9 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
     return QS_OK;
 }
 
-// records [k0, k0 + m) of the call, at d_pkts (already offset to record k0)
+// records [k0, k0 + m) of the call, at d_pkts (already offset to record k0); graph: the call runs in graph mode
 static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0,
-                        const qs_sweep_match *corr = nullptr)
+                        bool graph, const qs_sweep_match *corr = nullptr)
 {
     const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
     int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
@@ -291,14 +342,24 @@ static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t strid
     const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
     StageTimer t(c, QS_STAGE_RAYCAST);
     HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p,
-                               corr));
+                               corr, graph ? k0 : QS_SWEEP_NO_GRAPH));
     t.stop();
     c->dirty_since_fuse = true;
     return QS_OK;
 }
 
-static void sweeps_end(qs_ctx *c, size_t n, uint64_t seq0)
+// Graph mode (qs_set_sweep_graph): before any chunk is mapped or matched, the pass over the whole call that decides every record,
+// adds the nodes and runs the chain (sweep_graph.hip).  Every later launch of the call is then told which record of the call its
+// records start at (graph_k0), and reads acceptance, agent and pose from that slice of the batch
+static int sweeps_graph_pass(qs_ctx *c, const uint8_t *pkts, bool host, size_t n, size_t stride, const uint16_t *lens, bool &graph)
 {
+    graph = c->sweep_graph;
+    return graph ? qs_sweep_graph_pass(c, pkts, host, n, stride, lens, QS_SWEEP_CHUNK) : QS_OK;
+}
+
+static void sweeps_end(qs_ctx *c, size_t n, uint64_t seq0, bool graph)
+{
+    c->last_sweep_graph = graph;
     if (c->b.edge) c->edge_maybe = true;                   // resolved at the next point the map is observed (sync_host_state)
     c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
     c->last_sweeps = true; c->last_sweeps_n = n;
@@ -310,12 +371,15 @@ extern "C" int qs_ingest_sweeps_device(qs_ctx *c, const uint8_t *d_pkts, size_t 
     ARGCHK(c, n == 0 || d_pkts != nullptr);
     int rc = sweeps_begin(c, n, stride, seq0);
     if (rc != QS_OK || n == 0) return rc;
+    bool graph;
+    rc = sweeps_graph_pass(c, d_pkts, false, n, stride, d_lens, graph);
+    if (rc != QS_OK) return rc;
     for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
         const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0);
+        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, graph);
         if (rc != QS_OK) return rc;
     }
-    sweeps_end(c, n, seq0);
+    sweeps_end(c, n, seq0, graph);
     return QS_OK;
 }
 
@@ -325,6 +389,10 @@ extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t
     ARGCHK(c, n == 0 || pkts != nullptr);
     int rc = sweeps_begin(c, n, stride, seq0);
     if (rc != QS_OK || n == 0) return rc;
+    // graph mode: every chunk is staged twice (the signature pass sees them all first)
+    bool graph;
+    rc = sweeps_graph_pass(c, pkts, true, n, stride, lens, graph);
+    if (rc != QS_OK) return rc;
     for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
         const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
         Staging s;
@@ -332,10 +400,10 @@ extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t
         if (rc != QS_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
         if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0);
+        rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, graph);
         if (rc != QS_OK) return rc;
     }
-    sweeps_end(c, n, seq0);
+    sweeps_end(c, n, seq0, graph);
     // as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
     return sync_host_state(c, true);
 }
@@ -353,9 +421,9 @@ static int matched_begin(qs_ctx *c, const qs_match_params *params, size_t n, siz
     return QS_OK;
 }
 
-static void matched_end(qs_ctx *c, size_t n, uint64_t seq0)
+static void matched_end(qs_ctx *c, size_t n, uint64_t seq0, bool graph)
 {
-    sweeps_end(c, n, seq0);
+    sweeps_end(c, n, seq0, graph);
     c->last_matches = true; c->last_matches_n = n;
 }
 
@@ -367,13 +435,16 @@ extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params 
     QsMatchSetup ms;
     int rc = matched_begin(c, params, n, stride, seq0, ms);
     if (rc != QS_OK || n == 0) return rc;
-    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, c->match_out.p, nullptr));
+    bool graph;                                            // graph mode: signature, chain, then the match from the chain's poses
+    rc = sweeps_graph_pass(c, d_pkts, false, n, stride, d_lens, graph);
+    if (rc != QS_OK) return rc;
+    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, c->match_out.p, nullptr, graph ? 0 : QS_SWEEP_NO_GRAPH));
     for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
         const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, c->match_out.p + k0);
+        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, graph, c->match_out.p + k0);
         if (rc != QS_OK) return rc;
     }
-    matched_end(c, n, seq0);
+    matched_end(c, n, seq0, graph);
     return QS_OK;
 }
 
@@ -385,6 +456,9 @@ extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params
     QsMatchSetup ms;
     int rc = matched_begin(c, params, n, stride, seq0, ms);
     if (rc != QS_OK || n == 0) return rc;
+    bool graph;                                            // graph mode: signature, chain, then the match from the chain's poses
+    rc = sweeps_graph_pass(c, pkts, true, n, stride, lens, graph);
+    if (rc != QS_OK) return rc;
     // the staging block holds one chunk: a call of several chunks stages each of them twice, first to match them all against
     // the map nobody has written yet, then to map them
     const bool one = n <= QS_SWEEP_CHUNK;
@@ -396,13 +470,15 @@ extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params
             if (rc != QS_OK) return rc;
             HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
             if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-            if (pass == 0 || one) HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, c->match_out.p + k0, nullptr));
+            if (pass == 0 || one)
+                HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, c->match_out.p + k0, nullptr,
+                                          graph ? k0 : QS_SWEEP_NO_GRAPH));
             if (pass == 1) {
-                rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, c->match_out.p + k0);
+                rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, graph, c->match_out.p + k0);
                 if (rc != QS_OK) return rc;
             }
         }
-    matched_end(c, n, seq0);
+    matched_end(c, n, seq0, graph);
     return sync_host_state(c, true);
 }
 

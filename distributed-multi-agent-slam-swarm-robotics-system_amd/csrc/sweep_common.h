@@ -18,10 +18,18 @@ struct QsSweepArgs {
     double *pose;                 // [n][3] out: rx, ry, yaw of accepted records
     unsigned long long ord_base;  // 4 * (seq0 - epoch_base) of record 0
     const qs_sweep_match *corr;   // [n] matched ingest only (the kernels' CORR instantiations): the correction of each record
+    // graph mode (sweep_graph.hip): this chunk's slice of the batch the signature pass and the SLAM stage filled -- the ONE
+    // acceptance decision, the agent and the chain's pose.  nullptr: acceptance and pose from the record, as without the mode
+    const unsigned char *g_accept, *g_agent;
+    const double *g_rx, *g_ry;
+    unsigned long long *zone;     // the bots' zone boxes (the kernels' GRAPH instantiations)
 };
 
-// sweep.hip: everything of a that comes from the context (filter, offsets, drift); outputs and corr empty
-void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, QsSweepArgs &a);
+// sweep.hip: everything of a that comes from the context (filter, offsets, drift); outputs and corr empty.  graph_k0: QS_SWEEP_NO_GRAPH,
+// or the record of a graph-mode call these n records start at (their slice of the batch: acceptance, agent, rx, ry)
+#define QS_SWEEP_NO_GRAPH ((size_t)-1)
+void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens, size_t graph_k0,
+                   QsSweepArgs &a);
 
 // the record's dwords [addr & ~3, addr + stride) into s[0 .. 191]; dwords that reach outside the caller's buffer (its first and
 // last bytes need not be dword-aligned) are read bytewise
@@ -52,21 +60,45 @@ __device__ inline unsigned int sw_u32(const unsigned int *s, unsigned int mis, u
     return __builtin_amdgcn_alignbyte(s[(b >> 2) + 1], s[b >> 2], b & 3u);
 }
 
-struct SwHead { bool ok; double rx, ry, yaw; };
+struct SwHead { bool ok; int agent; double rx, ry, yaw; };
 
-__device__ inline SwHead sw_head(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
+// length, magic and agent of qs_ingest_sweeps' acceptance rule; the agent byte either way
+__device__ inline bool sw_accept(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis, int &agent)
 {
-    SwHead h{false, 0.0, 0.0, 0.0};
     const int len = a.lens ? (int)a.lens[k] : (int)a.stride;
-    const int agent = (int)(sw_u32(s, mis, 4) & 0xffu);
-    h.ok = len == (int)a.stride && sw_u32(s, mis, 0) == SW_MAGIC && agent >= 1 && agent <= a.max_agent;
+    agent = (int)(sw_u32(s, mis, 4) & 0xffu);
+    return len == (int)a.stride && sw_u32(s, mis, 0) == SW_MAGIC && agent >= 1 && agent <= a.max_agent;
+}
+
+// GRAPH: acceptance, agent and (rx, ry) from the batch slice (decided and posed before this launch); otherwise from the record
+template <bool GRAPH>
+__device__ inline SwHead sw_head_t(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
+{
+    SwHead h{false, 0, 0.0, 0.0, 0.0};
+    if (GRAPH) {
+        h.ok = a.g_accept[k] != 0;
+        if (h.ok) {
+            h.agent = a.g_agent[k];
+            h.rx = a.g_rx[k]; h.ry = a.g_ry[k];
+            h.yaw = (double)__uint_as_float(sw_u32(s, mis, 13));
+        }
+        return h;
+    }
+    h.ok = sw_accept(a, k, s, mis, h.agent);
     if (h.ok) {
+        const int agent = h.agent;
         const float x = __uint_as_float(sw_u32(s, mis, 5)), y = __uint_as_float(sw_u32(s, mis, 9));
         h.rx = ((double)x + a.offset[agent]) + a.drift[2 * agent];      // offset first, then drift (:851-857)
         h.ry = (double)y + a.drift[2 * agent + 1];
         h.yaw = (double)__uint_as_float(sw_u32(s, mis, 13));
     }
     return h;
+}
+
+// the matcher's form: whichever the arguments say
+__device__ inline SwHead sw_head(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
+{
+    return a.g_accept ? sw_head_t<true>(a, k, s, mis) : sw_head_t<false>(a, k, s, mis);
 }
 
 // matched ingest: the pose the sweep is cast from, rx' = rx + dx, ry' = ry + dy, yaw' = yaw + dyaw (one add each; a match

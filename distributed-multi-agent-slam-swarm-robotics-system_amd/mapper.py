@@ -324,6 +324,66 @@ class QuasarMapper:
         self._last_sweeps_n = n
         self._last_matches_n = None
 
+    # -- sweeps in the pose graph (include/quasar_slam.h, "sweeps in the pose graph") ---------------------------------------------
+    @staticmethod
+    def sweep_graph_params(params=None, **kw):
+        """A qs_sweep_graph_params from None / True (the defaults of protocol.SWEEP_GRAPH_*), a dict of its fields, or one
+        already built."""
+        if isinstance(params, _lib.QsSweepGraphParams):
+            return params
+        d = dict(half_width=P.SWEEP_GRAPH_HALF_WIDTH, close=P.SWEEP_GRAPH_CLOSE_M, open=P.SWEEP_GRAPH_OPEN_M)
+        if isinstance(params, dict):
+            d.update(params)
+        elif params not in (None, True):
+            raise TypeError("sweep graph parameters: None, True, a dict or a QsSweepGraphParams")
+        d.update({k: v for k, v in kw.items() if v is not None})
+        return _lib.QsSweepGraphParams(half_width=int(d["half_width"]), reserved=0, close=float(d["close"]), open=float(d["open"]))
+
+    def set_sweep_graph(self, on=True, half_width=None, close=None, open=None):
+        """Graph mode of the sweep ingests: every accepted sweep becomes a pose-graph node with a landmark signature derived
+        from its ranges (the median of 2 * half_width + 1 beams to the right, front and left against the firmware's close /
+        open thresholds), the loop-closure chain runs, the sweep is cast from the pose the chain gives it and feeds the bot's
+        zone box.  Off by default; kept over reset(), not saved in a checkpoint."""
+        prm = self.sweep_graph_params(None, half_width=half_width, close=close, open=open)
+        self._chk(self._L.qs_set_sweep_graph(self._h, int(bool(on)), C.byref(prm)), "qs_set_sweep_graph")
+
+    def sweep_graph(self):
+        """(enabled, {"half_width", "close", "open"}) as the context holds them."""
+        on, prm = C.c_int32(), _lib.QsSweepGraphParams()
+        self._chk(self._L.qs_sweep_graph(self._h, C.byref(on), C.byref(prm)), "qs_sweep_graph")
+        return bool(on.value), {"half_width": prm.half_width, "close": prm.close, "open": prm.open}
+
+    def sweep_signatures(self, datagrams, lengths=None, params=None):
+        """The landmark signature of every sweep (as ingest_sweeps takes them) by the graph-mode rule, uint8 [n]:
+        protocol.LM_* or SWEEP_LM_REJECTED for a record that is not accepted.  Writes nothing to the mapper.  params: None
+        (the mapper's current parameters) or what sweep_graph_params takes."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        prm = None if params is None else C.byref(self.sweep_graph_params(params))
+        out = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.qs_sweep_signatures(self._h, prm, _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                              _ptr(out) if n else None), "qs_sweep_signatures")
+        return out
+
+    def sweep_signatures_device(self, d_pkts, n, stride, d_out, d_lens=0, params=None):
+        """Device-resident form (raw device addresses as ints; d_out: n bytes); asynchronous."""
+        prm = None if params is None else C.byref(self.sweep_graph_params(params))
+        self._chk(self._L.qs_sweep_signatures_device(self._h, prm, C.c_void_p(d_pkts), n, stride,
+                                                     C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_out)),
+                  "qs_sweep_signatures_device")
+
+    def last_sweep_nodes(self):
+        """(node int64 [n], lm uint8 [n]) of the last sweep ingest in graph mode: the node index of each sweep in its bot's
+        pose graph (-1: rejected) and its signature (SWEEP_LM_REJECTED: rejected); an error after any other ingest."""
+        n = getattr(self, "_last_sweeps_n", 0)
+        node = np.zeros(n, dtype=np.int64)
+        lm = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.qs_last_sweep_nodes(self._h, _ptr(node) if n else None, _ptr(lm) if n else None, n), "qs_last_sweep_nodes")
+        return node, lm
+
     # -- sweep matching (include/quasar_slam.h, "sweep matching") -----------------------------------------------------------
     @staticmethod
     def match_params(params=None, **kw):

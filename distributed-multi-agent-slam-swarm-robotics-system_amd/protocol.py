@@ -124,6 +124,12 @@ SWEEP_BEAMS = 181
 SWEEP_SEQS = 46              # sequence numbers one sweep uses in the mapper's stamp order (include/quasar_slam.h)
 SWEEP_MIN_DIST_M = 0.1       # trust filter of the reference's sweep map, generate_topdown_map.py:51
 SWEEP_MAX_DIST_M = 1.2
+# sweeps in the pose graph (include/quasar_slam.h, "sweeps in the pose graph"): the signature rule's defaults and limits
+SWEEP_GRAPH_HALF_WIDTH = 5   # beams either side of beams 0 (right), 90 (front), 180 (left) whose median is the sector's range
+SWEEP_GRAPH_MAX_HALF_WIDTH = 29
+SWEEP_GRAPH_CLOSE_M = 0.40   # detectLandmark's thresholds, AgentFirmware_Bot1.ino:152-169
+SWEEP_GRAPH_OPEN_M = 0.80
+SWEEP_LM_REJECTED = 255      # sweep_signatures / last_sweep_nodes: the record was not accepted
 # sweep matching (include/quasar_slam.h, "sweep matching"): build choices, there is no reference counterpart
 MATCH_RADIUS = 2             # cells the likelihood field reaches from an occupied cell
 MATCH_WINDOW = 6             # candidate shifts: +- cells on both axes

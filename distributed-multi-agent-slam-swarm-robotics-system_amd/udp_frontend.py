@@ -27,6 +27,9 @@ each run one ingest call.  No call names its sequence numbers: the mapper contin
 With match_sweeps=True (opt-in, needs sweeps=True) a run of sweeps is matched against the map before it is mapped
 (QuasarMapper.ingest_sweeps(match=...), match_params its parameters): the bot's pose is then the corrected one, and
 last_matches holds the matches of the latest run.
+With sweep_graph=True or a dict of half_width / close / open (opt-in, needs sweeps=True) the mapper is put into graph mode at
+construction (QuasarMapper.set_sweep_graph): sweeps become pose-graph nodes, close loops and feed their bot's zone box, so
+zone_tick sends a sweep bot's partner a real box.
 Differences: the reference throttles itself to 20 packets per 30 fps frame (:816, :474); here a
 poll drains the socket (up to max_batch datagrams).  Host-side Python only; the mapper can be any
 object with ingest_array / last_batch / zone_packet (tests use a stub, production the HIP mapper).
@@ -45,13 +48,18 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
-                 match_params=None, targets_by_path=False):
+                 match_params=None, targets_by_path=False, sweep_graph=False):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
         if targets_by_path and not frontier_targets:
             raise ValueError("MissionControl: targets_by_path=True needs frontier_targets=True")
         if match_sweeps and not sweeps:
             raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
+        self.sweep_graph = sweep_graph is not False and sweep_graph is not None      # ({} is on, with the defaults)
+        if self.sweep_graph and not sweeps:
+            raise ValueError("MissionControl: sweep_graph needs sweeps=True")
+        if self.sweep_graph:
+            mapper.set_sweep_graph(True, **(dict(sweep_graph) if isinstance(sweep_graph, dict) else {}))
         self.match_sweeps = match_sweeps
         self.match_params = dict(match_params) if match_params else True
         self.last_matches = None

@@ -120,7 +120,8 @@ int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 
  *            ignored (udp_bridge.py:71).  A rejected record writes nothing but still uses its sequence numbers.
  *   pose     rx = f64(x) + offset[bot] + drift_x[bot], ry = f64(y) + drift_y[bot] (offset first, then drift, as :851-857):
  *            qs_set_bot_offset / separation, and the bot's closure correction as all earlier calls on the context's stream
- *            left it (read on the device).  A sweep adds NO pose-graph node, landmark, EKF step or zone point.
+ *            left it (read on the device).  A sweep adds NO pose-graph node, landmark, EKF step or zone point, unless the
+ *            context is in graph mode (qs_set_sweep_graph, "sweeps in the pose graph" below: off by default).
  *   beams    beam i has angle a = f64(yaw) + (i - 90) * (pi / 180) (CPython's math.radians; one multiply, one add, no FMA).
  *            d = the f32 range widened: smin < d <= smax is a hit, update_ray(rx, ry, rx + d cos a, ry + d sin a, True);
  *            any other beam (NaN, 0, negative included) a free ray of length min(d, smax) if d > smin else smax.
@@ -147,6 +148,57 @@ int qs_ingest_sweeps_device(qs_ctx *ctx, const uint8_t *d_pkts, size_t n, size_t
 int qs_last_sweeps(qs_ctx *ctx, uint8_t *accepted, double *pose_xyyaw /* n x 3 */, size_t n);
 /* trust filter of the sweep beams: a hit when smin < d <= smax (finite, 0 <= smin < smax) */
 int qs_set_sweep_filter(qs_ctx *ctx, double smin, double smax);
+
+/* ---- sweeps in the pose graph (graph mode; no reference counterpart: this build's own rule) ------------------------------------
+ * The firmware that sends sweeps (esp32_firmware/src/main.cpp) computes no landmark byte; the one that does
+ * (AgentFirmware_Bot1.ino:152-169, detectLandmark) reads fixed sonars to the front, left and right.  A sweep holds the same three
+ * directions: beam 0 is right, beam 90 front, beam 180 left.  In graph mode the library derives the signature itself, adds the
+ * sweep as a pose-graph node, runs the loop-closure chain and casts the sweep from the pose the chain gives it -- what the
+ * 42-byte path does for a packet.  All comparisons are on exact values: a NumPy restatement (tests/sweep_graph_rules.py) agrees
+ * bit for bit.
+ *  setting   qs_set_sweep_graph(ctx, enable, params); params NULL = half_width 5, close 0.40, open 0.80 (the firmware's 40 cm
+ *            and 80 cm).  Limits: 0 <= half_width <= 29 (the three sectors never share a beam), finite 0 < close <= open;
+ *            QS_E_INVAL otherwise, the text names the field.  Kept over qs_reset (as the sweep filter and the chain form), NOT
+ *            saved in a checkpoint: qs_restore leaves the context's current setting alone.  Off (the default): every call
+ *            behaves as described above.  A sharded context refuses sweeps either way.
+ *  accept    qs_ingest_sweeps' rule, and x, y, yaw finite (the packet path's test).  ONE decision per record: the signature
+ *            pass makes it, matching and mapping read it.
+ *  sectors   w = half_width.  Right: beams 0 .. 2w; front: 90 - w .. 90 + w; left: 180 - 2w .. 180; 2w + 1 beams each.  A range
+ *            is usable when finite and > 0; any other (NaN, +-inf, 0, negative) counts as +inf (the firmware's timeout reads
+ *            as "far", :239).  The sector value S is the element of rank w (0-based) of the 2w + 1 values ordered by (value,
+ *            beam index): the median, the cheapest rule that ignores one stray echo.  w = 0: the single beams 0, 90, 180.
+ *  decision  detectLandmark on S widened to fp64: X_close = S_X < close, X_open = S_X > open.  DEAD_END (4) if front, left and
+ *            right are close; else CORNER_L (1) if front and left; else CORNER_R (2) if front and right; else CORRIDOR (3) if
+ *            left and right are close and front is open; else OPEN (5) if all three are open; else NONE (0).
+ *            (f32(0.4) widens to 0.4000000059604645, which is not < 0.40.)
+ *  node      every accepted sweep is one PoseGraphSLAM.add_pose(rx, ry, yaw, agent, lm) (:273-326) in record order within the
+ *            call, continuing the node index of its graph (shared with packets, per bots_per_graph): px = f64(x) +
+ *            offset[bot], py = f64(y), rx = px + drift_x, ry = py + drift_y with the bot's drift BEFORE this record's own
+ *            closure -- what the packet path reports as its pose.  A closure at sweep k moves the sweeps of that bot after k in
+ *            the same call.  closure_radius, min_poses_between, closure_correction are the context's.
+ *  mapping   beams are cast by qs_ingest_sweeps' rules from (rx, ry, yaw).  Matched ingest: signature, chain, then the match
+ *            from the chain's (rx, ry) against the map as it stood before the call, then the map from rx + dx, ry + dy,
+ *            yaw + dyaw.  The match correction does not enter the graph: the node is the drift-corrected packet pose.
+ *  zone      per accepted sweep the pose it is cast from is a path point (:878-879) and the end point of every hit beam a cloud
+ *            point (:892) of the bot's zone box (qs_zone), both from the device's trig whether or not the beam waits in the
+ *            exact-trig edge band (as for packets).
+ *  no EKF    the sweep entry points carry no receive time: a sweep is no EKF step in either mode.
+ *  the rest  stamps, sequence numbers (46 per sweep), QS_CNT_*, dirty blocks and chunking as qs_ingest_sweeps.  The four sweep
+ *            ingest entry points keep their signatures; qs_last_sweeps reports the pose each sweep was cast from. */
+#define QS_SWEEP_GRAPH_MAX_HALF_WIDTH 29
+typedef struct qs_sweep_graph_params { int32_t half_width, reserved; double close, open; } qs_sweep_graph_params;
+int qs_set_sweep_graph(qs_ctx *ctx, int32_t enable, const qs_sweep_graph_params *params);
+int qs_sweep_graph(qs_ctx *ctx, int32_t *enabled, qs_sweep_graph_params *out);
+/* rule only, writes nothing to the context (tests and tools): lm_out[k] = signature, 255 for a rejected record.
+ * params NULL = the context's current parameters (the defaults unless set) */
+int qs_sweep_signatures(qs_ctx *ctx, const qs_sweep_graph_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                        const uint16_t *lens, uint8_t *lm_out);
+/* same with device-resident pkts / lens / lm_out; asynchronous on the context's stream */
+int qs_sweep_signatures_device(qs_ctx *ctx, const qs_sweep_graph_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                               const uint16_t *d_lens, uint8_t *d_lm_out);
+/* after a sweep ingest in graph mode: node index in the record's graph (-1: rejected) and signature (255: rejected);
+ * QS_E_INVAL otherwise */
+int qs_last_sweep_nodes(qs_ctx *ctx, int64_t *node, uint8_t *lm, size_t n);
 
 /* ---- sweep matching (no reference counterpart: this build's own rule) ------------------------------------------------------
  * A sweep is matched against the map before it is mapped: a window of candidate poses around the packet's pose is scored
@@ -187,7 +239,7 @@ int qs_set_sweep_filter(qs_ctx *ctx, double smin, double smax);
  * ry' = ry + dy, yaw' = yaw + dyaw (beam angle yaw' + (i - 90) * (pi / 180)).  Stamps, counters, sequence numbers, refusals
  * as qs_ingest_sweeps; qs_last_sweeps reports the corrected pose, qs_last_sweep_matches the matches (n = the call's n;
  * QS_E_INVAL after any other ingest).  With exact_trig a beam in the edge band waits for the host with its corrected
- * pose.  The bot's drift, the pose graphs, the EKF and the zone points are not touched. */
+ * pose.  The bot's drift, the pose graphs, the EKF and the zone points are not touched (graph mode: see above). */
 #define QS_MATCH_MAX_RADIUS 7
 #define QS_MATCH_MAX_ANGLE_STEPS 45
 #define QS_MATCH_MAX_REACH 127

@@ -10,16 +10,15 @@
 //                 first cell the reference's row-major seed loop meets (:210), which is also what
 //                 orders the reference's cluster list;
 //   3. flatten + integer sums per root (count, sum gx, sum gy: what cluster_centroid_world divides);
-//   4. order-preserving compaction of the roots -> clusters in the reference's order.
+//   4. order-preserving compaction (compact.h) of the roots -> clusters in the reference's order.
 // The centroid itself (two divisions per cluster) is left to the host: it is exact integer/fp64
 // arithmetic on these sums.  BFS visiting order inside a cluster is not reproduced (it only orders
 // the membership lists, which nothing downstream reads).
 #include <string.h>
 
-#include "qs_internal.h"
+#include "compact.h"
 
 #define FR_BLOCK 256
-#define FR_CHUNK QS_FR_CHUNK
 #define FR_NONE 0xffffffffu
 
 __device__ inline bool fr_is_free(unsigned int s) { return s != 0 && !(s & 1u); }
@@ -87,97 +86,33 @@ qs_frontier_stats_kernel(int size, unsigned int *__restrict__ label, unsigned in
     }
 }
 
-// order-preserving compaction (chunk counts -> scan -> ranked writes); MODE 0: every frontier
-// cell (get_frontiers), MODE 1: component roots (one per cluster, in first-cell order)
-template <int MODE>
-__device__ inline bool fr_pred(const unsigned int *label, const unsigned int *cnt, size_t i)
-{
-    if (MODE == 0 || MODE == 2) return label[i] != FR_NONE;
-    return cnt[i] != 0;
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(FR_BLOCK)
-qs_frontier_count_kernel(const unsigned int *__restrict__ label, const unsigned int *__restrict__ cnt, size_t cells,
-                         unsigned int *__restrict__ chunk_count)
-{
-    __shared__ unsigned int s;
-    if (threadIdx.x == 0) s = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * FR_CHUNK;
-    unsigned int m = 0;
-    for (int q = 0; q < FR_CHUNK / FR_BLOCK; q++) {
-        const size_t i = base + q * FR_BLOCK + threadIdx.x;
-        if (i < cells && fr_pred<MODE>(label, cnt, i)) m++;
+// the compactions (compact.h): every frontier cell (get_frontiers) -> (gx, gy), or -> (gx, gy, root); the component roots
+// (cnt != 0: one per cluster, in first-cell order) -> the five statistics
+struct FrCell { const unsigned int *label; __device__ bool marked(size_t i) const { return label[i] != FR_NONE; } };
+struct FrRoot { const unsigned int *cnt; __device__ bool marked(size_t i) const { return cnt[i] != 0; } };
+struct FrEmitXY {
+    int size; int *xy;
+    __device__ void put(size_t slot, size_t i) const { xy[2 * slot] = (int)(i % size); xy[2 * slot + 1] = (int)(i / size); }
+};
+struct FrEmitXYRoot {
+    const unsigned int *label; int size; int *xy;
+    __device__ void put(size_t slot, size_t i) const
+    {
+        unsigned int r = (unsigned int)i;                       // the cluster's first cell: walk to the root
+        for (unsigned int p = label[r]; p != r; p = label[r]) r = p;
+        xy[3 * slot] = (int)(i % size); xy[3 * slot + 1] = (int)(i / size); xy[3 * slot + 2] = (int)r;
     }
-    if (m) atomicAdd(&s, m);
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_count[blockIdx.x] = s;
-}
-
-__global__ void __launch_bounds__(1024)
-qs_frontier_scan_kernel(unsigned int *__restrict__ chunk_count, size_t n_chunks, unsigned long long *__restrict__ total)
-{
-    __shared__ unsigned long long s_part[1024];
-    const int tid = threadIdx.x;
-    const size_t per = (n_chunks + 1023) / 1024;
-    const size_t lo = min((size_t)tid * per, n_chunks), hi = min(lo + per, n_chunks);
-    unsigned long long sum = 0;
-    for (size_t k = lo; k < hi; k++) sum += chunk_count[k];
-    s_part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < 1024; t++) { const unsigned long long v = s_part[t]; s_part[t] = run; run += v; }
-        *total = run;
+};
+struct FrEmitStats {
+    const unsigned int *cnt; const unsigned long long *sumx, *sumy; int size; long long *stats;
+    __device__ void put(size_t slot, size_t i) const
+    {
+        const long long n = cnt[i], sx = (long long)sumx[i], sy = (long long)sumy[i];
+        stats[5 * slot] = n;
+        stats[5 * slot + 1] = (long long)(i % size); stats[5 * slot + 2] = (long long)(i / size);
+        stats[5 * slot + 3] = sx; stats[5 * slot + 4] = sy;
     }
-    __syncthreads();
-    unsigned long long run = s_part[tid];
-    for (size_t k = lo; k < hi; k++) { const unsigned int v = chunk_count[k]; chunk_count[k] = (unsigned int)run; run += v; }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(FR_BLOCK)
-qs_frontier_write_kernel(const unsigned int *__restrict__ label, const unsigned int *__restrict__ cnt,
-                         const unsigned long long *__restrict__ sumx, const unsigned long long *__restrict__ sumy,
-                         size_t cells, int size, const unsigned int *__restrict__ chunk_off,
-                         int *__restrict__ out_xy, long long *__restrict__ out_stats, size_t cap)
-{
-    __shared__ unsigned int s_wave[FR_BLOCK / QS_WAVE];
-    __shared__ unsigned int s_run;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_run = chunk_off[blockIdx.x];
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * FR_CHUNK;
-    for (int q = 0; q < FR_CHUNK / FR_BLOCK; q++) {
-        const size_t i = base + q * FR_BLOCK + tid;
-        const bool on = i < cells && fr_pred<MODE>(label, cnt, i);
-        const unsigned long long m = __ballot(on);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        unsigned int off = s_run;
-        for (int v = 0; v < wave; v++) off += s_wave[v];
-        if (on) {
-            const size_t slot = off + __popcll(m & ((1ull << lane) - 1));
-            if (slot < cap) {
-                if (MODE == 0) { out_xy[2 * slot] = (int)(i % size); out_xy[2 * slot + 1] = (int)(i / size); }
-                else if (MODE == 2) {
-                    unsigned int r = (unsigned int)i;                       // the cluster's first cell: walk to the root
-                    for (unsigned int p = label[r]; p != r; p = label[r]) r = p;
-                    out_xy[3 * slot] = (int)(i % size); out_xy[3 * slot + 1] = (int)(i / size); out_xy[3 * slot + 2] = (int)r;
-                }
-                else {
-                    out_stats[5 * slot] = cnt[i];
-                    out_stats[5 * slot + 1] = (long long)(i % size); out_stats[5 * slot + 2] = (long long)(i / size);
-                    out_stats[5 * slot + 3] = (long long)sumx[i]; out_stats[5 * slot + 4] = (long long)sumy[i];
-                }
-            }
-        }
-        __syncthreads();
-        if (tid == 0) { unsigned int t = 0; for (int v = 0; v < FR_BLOCK / QS_WAVE; v++) t += s_wave[v]; s_run += t; }
-        __syncthreads();
-    }
-}
+};
 
 static inline unsigned int fr_blocks(size_t items)
 {
@@ -187,14 +122,14 @@ static inline unsigned int fr_blocks(size_t items)
 
 QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws)
 {
-    const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
+    const size_t cells = c->cells;
     Carve k(ws);
     QsFrLayout L;
     L.label = k.take<unsigned int>(cells);
     L.cnt = k.take<unsigned int>(cells);        // cnt .. sumy: one memset clears them (qs_launch_frontier_label)
     L.sumx = k.take<unsigned long long>(cells);
     L.sumy = k.take<unsigned long long>(cells);
-    L.chunk = k.take<unsigned int>(n_chunks);
+    L.chunk = k.take<unsigned int>(qs_compact_chunks(cells));
     L.total = k.take<unsigned long long>(1);
     L.bytes = k.bytes;
     return L;
@@ -216,31 +151,15 @@ hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters)
     return hipGetLastError();
 }
 
-// phase 0: count + scan (total -> *d_total); phase 1: ranked write
-static hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, int phase, int *d_xy, long long *d_stats, size_t cap)
-{
-    const size_t cells = c->cells, n_chunks = (cells + FR_CHUNK - 1) / FR_CHUNK;
-    const QsFrLayout L = qs_frontier_layout(c, ws);
-    unsigned int *label = L.label, *cnt = L.cnt, *chunk = L.chunk;
-    unsigned long long *sumx = L.sumx, *sumy = L.sumy;
-    if (phase == 0) {
-        if (mode == 0) hipLaunchKernelGGL(qs_frontier_count_kernel<0>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, cells, chunk);
-        else hipLaunchKernelGGL(qs_frontier_count_kernel<1>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, cells, chunk);
-        hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, chunk, n_chunks, L.total);
-    } else {
-        if (mode == 0) hipLaunchKernelGGL(qs_frontier_write_kernel<0>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
-        else if (mode == 2) hipLaunchKernelGGL(qs_frontier_write_kernel<2>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
-        else hipLaunchKernelGGL(qs_frontier_write_kernel<1>, dim3((unsigned int)n_chunks), dim3(FR_BLOCK), 0, c->stream, label, cnt, sumx, sumy, cells, c->cfg.size, chunk, d_xy, d_stats, cap);
-    }
-    return hipGetLastError();
-}
-
-// exclusive scan of the chunk counts a count kernel left in the workspace; the sum -> total
-hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws)
+// mode 0: cells, 1: cluster roots, 2: cells with their roots.  !write: count + scan (the total -> L.total); write: the ranked
+// writes of the first cap items to d_xy (modes 0, 2) / d_stats (mode 1)
+static hipError_t qs_launch_frontier_compact(qs_ctx *c, void *ws, int mode, bool write, int *d_xy, long long *d_stats, size_t cap)
 {
     const QsFrLayout L = qs_frontier_layout(c, ws);
-    hipLaunchKernelGGL(qs_frontier_scan_kernel, dim3(1), dim3(1024), 0, c->stream, L.chunk, (c->cells + FR_CHUNK - 1) / FR_CHUNK, L.total);
-    return hipGetLastError();
+    const int size = c->cfg.size;
+    if (mode == 0) return qs_compact(c->stream, FrCell{L.label}, c->cells, write, FrEmitXY{size, d_xy}, cap, L.chunk, L.total);
+    if (mode == 2) return qs_compact(c->stream, FrCell{L.label}, c->cells, write, FrEmitXYRoot{L.label, size, d_xy}, cap, L.chunk, L.total);
+    return qs_compact(c->stream, FrRoot{L.cnt}, c->cells, write, FrEmitStats{L.cnt, L.sumx, L.sumy, size, d_stats}, cap, L.chunk, L.total);
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -252,7 +171,7 @@ static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, i
     HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
     void *ws = c->frontier_ws.p;
     HIPCHK(c, qs_launch_frontier_label(c, ws, mode != 0));
-    HIPCHK(c, qs_launch_frontier_compact(c, ws, mode == 2 ? 0 : mode, 0, nullptr, nullptr, 0));
+    HIPCHK(c, qs_launch_frontier_compact(c, ws, mode, false, nullptr, nullptr, 0));
     unsigned long long total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, ws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -264,7 +183,7 @@ static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, i
         const size_t per = mode == 0 ? 2 : 3, m = total < cap ? (size_t)total : cap;
         DevBuf<int> d;
         HIPCHK(c, d.alloc(per * (size_t)total));
-        HIPCHK(c, qs_launch_frontier_compact(c, ws, mode, 1, d.p, nullptr, (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, mode, true, d.p, nullptr, (size_t)total));
         HIPCHK(c, hipMemcpyAsync(xy, d.p, per * m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return QS_OK;
@@ -274,7 +193,7 @@ static int frontier_run(qs_ctx *c, int mode, int32_t min_cluster, int32_t *xy, i
     if (total) {
         DevBuf<long long> d;
         HIPCHK(c, d.alloc(5 * (size_t)total));
-        HIPCHK(c, qs_launch_frontier_compact(c, ws, 1, 1, nullptr, d.p, (size_t)total));
+        HIPCHK(c, qs_launch_frontier_compact(c, ws, 1, true, nullptr, d.p, (size_t)total));
         HIPCHK(c, hipMemcpyAsync(all.data(), d.p, all.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }

@@ -2,7 +2,7 @@
 // stamp grid, K3 grid fuse, stamp rebase, and map_merger's grid_to_pcd / rasterise.
 // All of them are HBM-streaming: 16-byte accesses per lane, consecutive lanes on consecutive
 // addresses, grid-stride loops capped at 2048 workgroups.
-#include "qs_internal.h"
+#include "compact.h"
 
 #define GO_BLOCK 256
 #define GO_MAX_BLOCKS 2048
@@ -230,13 +230,10 @@ hipError_t qs_launch_reset_small(qs_ctx *c)
 }
 
 // ---- MapMerger.grid_to_pcd  server_nodes/map_merger.py:64-85 -----------------------------
-// np.argwhere(data > 50) is row-major, so the points are an order-preserving compaction:
-// per-chunk counts, one scan, ranked writes.  Chunk = 1024 cells.
-// The three kernels are written once over (what marks an item, what a marked item leaves behind) and instantiated for
+// np.argwhere(data > 50) is row-major, so the points are an order-preserving compaction (compact.h), instantiated here for
 //   the int8 grid of a map message (data > 50 -> a point),
 //   a context's own stamps (an odd stamp = occupied -> the same point; merge.hip: qs_merge_map), and
 //   a sorted key array (a key that differs from its predecessor -> its position; merge.hip: the voxel runs).
-#define PCD_CHUNK 1024
 struct PcdGridI8 { const signed char *g; __device__ bool marked(size_t c) const { return g[c] > 50; } };               // data > 50   :72
 struct PcdStamps { const unsigned int *s; __device__ bool marked(size_t c) const { return (s[c] & 1u) != 0u; } };     // (ordinal << 1) | occ
 struct PcdRunHead { const unsigned long long *k; __device__ bool marked(size_t c) const { return c == 0 || k[c] != k[c - 1]; } };
@@ -251,31 +248,14 @@ struct PcdEmitXY {
 };
 struct PcdEmitPos { unsigned int *pos; __device__ void put(size_t slot, size_t c) const { pos[slot] = (unsigned int)c; } };
 
-template <typename Src>
-__global__ void __launch_bounds__(GO_BLOCK)
-qs_pcd_count_kernel(const Src src, size_t cells, unsigned int *__restrict__ chunk_count)
-{
-    __shared__ unsigned int s;
-    if (threadIdx.x == 0) s = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * PCD_CHUNK;
-    unsigned int m = 0;
-    for (int q = 0; q < PCD_CHUNK / GO_BLOCK; q++) {
-        const size_t c = base + q * GO_BLOCK + threadIdx.x;
-        if (c < cells && src.marked(c)) m++;
-    }
-    if (m) atomicAdd(&s, m);
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_count[blockIdx.x] = s;
-}
-// single-workgroup exclusive scan of the chunk counts (<= a few 10^5 entries)
+// single-workgroup exclusive scan of the chunk counts (<= a few 10^5 entries): the one scan of every compaction (compact.h)
 __global__ void __launch_bounds__(1024)
-qs_pcd_scan_kernel(unsigned int *__restrict__ chunk_count, size_t n_chunks, unsigned long long *__restrict__ total)
+qs_compact_scan_kernel(unsigned int *__restrict__ chunk_count, size_t n_chunks, unsigned long long *__restrict__ total)
 {
     __shared__ unsigned long long s_part[1024];
     const int tid = threadIdx.x;
     const size_t per = (n_chunks + 1023) / 1024;
-    const size_t lo = (size_t)tid * per, hi = (lo + per < n_chunks) ? lo + per : n_chunks;
+    const size_t lo = min((size_t)tid * per, n_chunks), hi = min(lo + per, n_chunks);
     unsigned long long sum = 0;
     for (size_t k = lo; k < hi; k++) sum += chunk_count[k];
     s_part[tid] = sum;
@@ -289,64 +269,28 @@ qs_pcd_scan_kernel(unsigned int *__restrict__ chunk_count, size_t n_chunks, unsi
     unsigned long long run = s_part[tid];
     for (size_t k = lo; k < hi; k++) { const unsigned int v = chunk_count[k]; chunk_count[k] = (unsigned int)run; run += v; }
 }
-template <typename Src, typename Emit>
-__global__ void __launch_bounds__(GO_BLOCK)
-qs_pcd_write_kernel(const Src src, size_t cells, const unsigned int *__restrict__ chunk_off, const Emit emit, size_t cap)
+hipError_t qs_launch_compact_scan(hipStream_t stream, unsigned int *d_chunk, size_t n_chunks, unsigned long long *d_total)
 {
-    __shared__ unsigned int s_wave[GO_BLOCK / QS_WAVE];
-    __shared__ unsigned int s_run;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_run = chunk_off[blockIdx.x];
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * PCD_CHUNK;
-    for (int q = 0; q < PCD_CHUNK / GO_BLOCK; q++) {
-        const size_t c = base + q * GO_BLOCK + tid;
-        const bool occ = c < cells && src.marked(c);
-        const unsigned long long m = __ballot(occ);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        unsigned int off = s_run;
-        for (int v = 0; v < wave; v++) off += s_wave[v];
-        if (occ) {
-            const size_t slot = off + __popcll(m & ((1ull << lane) - 1));
-            if (slot < cap) emit.put(slot, c);
-        }
-        __syncthreads();
-        if (tid == 0) { unsigned int t = 0; for (int v = 0; v < GO_BLOCK / QS_WAVE; v++) t += s_wave[v]; s_run += t; }
-        __syncthreads();
-    }
-}
-// phase 0 (emit target nullptr): chunk counts -> exclusive offsets, the total in *d_count; phase 1: the ranked writes
-template <typename Src, typename Emit>
-static hipError_t pcd_compact(qs_ctx *c, const Src src, size_t cells, bool write, const Emit emit, size_t cap,
-                              unsigned long long *d_count, unsigned int *d_chunk)
-{
-    const size_t n_chunks = (cells + PCD_CHUNK - 1) / PCD_CHUNK;
-    if (!write) {
-        hipLaunchKernelGGL(qs_pcd_count_kernel<Src>, dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, src, cells, d_chunk);
-        hipLaunchKernelGGL(qs_pcd_scan_kernel, dim3(1), dim3(1024), 0, c->stream, d_chunk, n_chunks, d_count);
-    } else {
-        hipLaunchKernelGGL((qs_pcd_write_kernel<Src, Emit>), dim3((unsigned int)n_chunks), dim3(GO_BLOCK), 0, c->stream, src, cells,
-                           d_chunk, emit, cap);
-    }
+    hipLaunchKernelGGL(qs_compact_scan_kernel, dim3(1), dim3(1024), 0, stream, d_chunk, n_chunks, d_total);
     return hipGetLastError();
 }
+// d_xy / d_pos == nullptr: phase 0 of qs_compact, otherwise phase 1
 hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox,
                                  double oy, double *d_xy, size_t cap, unsigned long long *d_count,
                                  unsigned int *d_chunk)
 {
-    return pcd_compact(c, PcdGridI8{d_grid}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_count, d_chunk);
+    return qs_compact(c->stream, PcdGridI8{d_grid}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_chunk, d_count);
 }
 hipError_t qs_launch_stamps_to_pcd(qs_ctx *c, const unsigned int *d_stamps, int h, int w, double res, double ox,
                                    double oy, double *d_xy, size_t cap, unsigned long long *d_count,
                                    unsigned int *d_chunk)
 {
-    return pcd_compact(c, PcdStamps{d_stamps}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_count, d_chunk);
+    return qs_compact(c->stream, PcdStamps{d_stamps}, (size_t)h * w, d_xy != nullptr, PcdEmitXY{w, res, ox, oy, d_xy}, cap, d_chunk, d_count);
 }
 hipError_t qs_launch_run_heads(qs_ctx *c, const unsigned long long *d_keys, size_t n, unsigned int *d_pos, size_t cap,
                                unsigned long long *d_count, unsigned int *d_chunk)
 {
-    return pcd_compact(c, PcdRunHead{d_keys}, n, d_pos != nullptr, PcdEmitPos{d_pos}, cap, d_count, d_chunk);
+    return qs_compact(c->stream, PcdRunHead{d_keys}, n, d_pos != nullptr, PcdEmitPos{d_pos}, cap, d_chunk, d_count);
 }
 
 // ---- MapMerger.publish_global_map  map_merger.py:87-127 -----------------------------------
@@ -454,7 +398,7 @@ extern "C" int qs_grid_to_pcd(qs_ctx *c, const int8_t *grid, int32_t h, int32_t 
 {
     ARGCHK(c, c != nullptr && grid != nullptr && n_out != nullptr && h > 0 && w > 0);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t cells = (size_t)h * w, n_chunks = (cells + 1023) / 1024;
+    const size_t cells = (size_t)h * w, n_chunks = qs_compact_chunks(cells);
     DevBuf<signed char> dg; DevBuf<unsigned int> dchunk; DevBuf<unsigned long long> dcount; DevBuf<double> dxy;
     HIPCHK(c, dg.alloc(cells));
     HIPCHK(c, dchunk.alloc(n_chunks));

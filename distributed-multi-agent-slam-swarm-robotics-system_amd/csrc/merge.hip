@@ -19,7 +19,7 @@
 #include <math.h>
 #include <utility>
 
-#include "qs_internal.h"
+#include "compact.h"
 
 #define MS_BLOCK 256
 #define MS_WAVES (MS_BLOCK / QS_WAVE)
@@ -169,7 +169,7 @@ static QsMergeGridLayout qs_merge_grid_layout(size_t cells, bool with_grid, void
 {
     Carve cv(ws);
     QsMergeGridLayout L;
-    L.chunk = cv.take<unsigned int>((cells + 1023) / 1024);
+    L.chunk = cv.take<unsigned int>(qs_compact_chunks(cells));
     L.count = cv.take<unsigned long long>(1);
     L.box4 = cv.take<unsigned long long>(4);
     L.grid = cv.take<signed char>(with_grid ? cells : 0);
@@ -192,7 +192,7 @@ static QsMergePtsLayout qs_merge_pts_layout(size_t n_local, size_t n_cat, bool w
     L.cat = cv.take<double2>(with_cat ? n_cat : 0);
     for (int q = 0; q < 2; q++) { L.keys[q] = cv.take<unsigned long long>(n_cat); L.idx[q] = cv.take<unsigned int>(n_cat); }
     L.pos = cv.take<unsigned int>(n_cat);
-    L.chunk = cv.take<unsigned int>((n_cat + 1023) / 1024);
+    L.chunk = cv.take<unsigned int>(qs_compact_chunks(n_cat));
     L.table = cv.take<unsigned int>((size_t)MS_MAX_WG * MS_RADIX);
     L.count = cv.take<unsigned long long>(1);
     L.box4 = cv.take<unsigned long long>(4);

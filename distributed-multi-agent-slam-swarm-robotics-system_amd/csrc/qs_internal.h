@@ -422,8 +422,8 @@ hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,
                           const unsigned long long *const *d_src_counts, size_t n_src, size_t cell_off, size_t n_cells,
                           unsigned long long *dst_counts);
 hipError_t qs_launch_reset_small(qs_ctx *c);
-// order-preserving compactions (count -> scan -> ranked write): d_xy / d_pos == nullptr runs count and scan (chunk offsets into
-// d_chunk, [ceil(items / 1024)], the total into *d_count), otherwise the ranked writes of the first `cap` items.
+// order-preserving compactions (compact.h): d_xy / d_pos == nullptr runs count and scan (chunk offsets into d_chunk,
+// [qs_compact_chunks(items)], the total into *d_count), otherwise the ranked writes of the first `cap` items.
 // cells > 50 of an int8 grid -> points; occupied (odd) stamps of a context's own map -> the same points;
 // positions where a sorted key array starts a new run
 hipError_t qs_launch_grid_to_pcd(qs_ctx *c, const signed char *d_grid, int h, int w, double res, double ox, double oy, double *d_xy,
@@ -441,15 +441,13 @@ hipError_t qs_launch_sf_mark_range(qs_ctx *c, size_t cell_off, size_t n_cells);
 hipError_t qs_launch_sf_list_of(qs_ctx *c, const unsigned int *bitmap, size_t words, int pitch, int blocks_x, unsigned int *list,
                                 unsigned int *count);
 // frontier.hip
-#define QS_FR_CHUNK 1024          // cells per chunk of the frontier compactions (count -> scan -> ranked write)
 // the workspace of the labelling and the compactions, carved from ws (nullptr: only the bytes the block needs):
 // [cells] labels, cells and sums of gx, gy per cluster (at its root); [chunks] counts of a compaction -> offsets; their sum
 struct QsFrLayout { unsigned int *label, *cnt; unsigned long long *sumx, *sumy; unsigned int *chunk; unsigned long long *total; size_t bytes; };
 QsFrLayout qs_frontier_layout(const qs_ctx *c, void *ws);
 hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
-hipError_t qs_launch_frontier_scan(qs_ctx *c, void *ws);
 // frontier_targets.hip: the centroids of the clusters of a labelled frontier workspace with >= min_cluster cells, in first-cell
-// order.  phase 0 counts them (QsFrLayout::total, after the scan); phase 1 writes them to d_cent
+// order.  phase 0 counts them (QsFrLayout::total); phase 1 writes them all to d_cent, which holds that many
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
 // icp.hip
 hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel, unsigned long long *keys);

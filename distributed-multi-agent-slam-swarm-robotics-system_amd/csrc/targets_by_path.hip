@@ -7,9 +7,9 @@
 //              centroids' cells into offsets into a field (the bounding box of the census) and counts who has a cell;
 //   fields   : one field per bot with a cell, seeded at the bot (the moves are symmetric: the field of a bot's cell holds
 //              the cost to every cell), in groups that fit QS_PLAN_WS_CAP, relaxed by the planner's host-driven rounds;
-//   gather   : while a group's fields are resident, one wave per (bot, chunk of TP_CHUNK centroids): lanes read the
-//              centroids' offsets coalesced, gather field[offset], and the wave keeps the TP_K smallest 64-bit keys
-//              (cost << 32) | k in a sorted list across lanes 0..TP_K-1 (ballot insertion, one shfl_up).  Infinite costs
+//   gather   : while a group's fields are resident, one wave per (bot, chunk of AS_CHUNK centroids): lanes read the
+//              centroids' offsets coalesced, gather field[offset], and the wave keeps the AS_K smallest 64-bit keys
+//              (cost << 32) | k in a sorted list across lanes 0..AS_K-1 (ballot insertion, one shfl_up).  Infinite costs
 //              never enter a list.  One wave per bot then merges its chunk lists into the exact top-K;
 //   greedy   : ONE wave walks the bots in order; a bot takes the first entry of its list that is neither taken nor within
 //              `separation` of a target assigned so far (frontier_targets.hip's fp64 test).  The list is the true top-K by
@@ -18,25 +18,21 @@
 //              all centroids finds its pick, and the pass resumes (counted in stats);
 //   waypoints: the body of qs_plan_paths for the assigned pairs: fields seeded at the assigned centroids' cells, the walk.
 // No device-side waits, no grid-wide barriers, no graphs.
+// The sorted list, the blocked test, the greedy walk and the host's stop / resume loop are assign_common.h's, shared with
+// frontier_targets.hip; here are the entry they order by, the gather that produces the chunk lists and the fallback's key.
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
 
+#include "assign_common.h"
 #include "plan_common.h"
 
-#define TP_K 32                   // candidates per bot
-#define TP_CHUNK 1024             // centroids per (bot, chunk) work item of the gather
-#define TP_BOTS_PER_BLOCK 4       // one wave per bot, 4 waves per workgroup (they read the same centroid offsets)
-#define TP_FB_BLOCK 256
 #define TP_NOKEY 0xffffffffffffffffull
 #define TP_NOCELL 0xffffffffu
 
-static_assert(TP_K <= QS_WAVE, "one list entry per lane");
-
-struct QsTbpState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
 // the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
 struct QsTbpLayout {
-    QsTbpState *st;
+    QsAssignState *st;
     unsigned long long *count;            // [2] centroids, bots with a cell
     double2 *xy;                          // [n_cent + n_bots] centroids, then bots
     long long *cell;                      // [n_cent + n_bots] their cells (gy * size + gx), -1 = none
@@ -56,22 +52,19 @@ struct QsTbpLayout {
     size_t bytes;
 };
 
-static inline size_t tp_chunks(size_t n_cent) { return (n_cent + TP_CHUNK - 1) / TP_CHUNK; }
-static inline size_t tp_fb_blocks(size_t n_cent) { return (n_cent + TP_FB_BLOCK - 1) / TP_FB_BLOCK; }
-
 static QsTbpLayout qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
 {
     QsTbpLayout L;
     Carve k(ws);
-    L.st = k.take<QsTbpState>(1);
+    L.st = k.take<QsAssignState>(1);
     L.count = k.take<unsigned long long>(2);
     L.xy = k.take<double2>(n_cent + n_bots);
     L.cell = k.take<long long>(n_cent + n_bots);
     L.coff = k.take<unsigned int>(n_cent);
     L.fcell = k.take<long long>(n_bots);
     L.fbot = k.take<int>(n_bots);
-    L.part = k.take<unsigned long long>(n_bots * tp_chunks(n_cent) * TP_K);
-    L.list = k.take<unsigned long long>(n_bots * TP_K);
+    L.part = k.take<unsigned long long>(n_bots * as_chunks(n_cent) * AS_K);
+    L.list = k.take<unsigned long long>(n_bots * AS_K);
     L.list_len = k.take<int>(n_bots);
     L.asg_xy = k.take<double2>(n_bots);
     L.asg_idx = k.take<int>(n_bots);
@@ -80,7 +73,7 @@ static QsTbpLayout qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
     L.tgt_status = k.take<int>(n_bots);
     L.pair = k.take<long long>(2 * n_bots);
     L.pair_bot = k.take<int>(n_bots);
-    L.fb_key = k.take<unsigned long long>(tp_fb_blocks(n_cent));
+    L.fb_key = k.take<unsigned long long>(as_fb_blocks(n_cent));
     L.bytes = k.bytes;
     return L;
 }
@@ -110,80 +103,91 @@ qs_tbp_offsets_kernel(const long long *__restrict__ cell, int n_cent, int n_bots
     }
 }
 
-// ---- the wave-resident sorted list of 64-bit keys ---------------------------------------------------------------------
-// Lanes 0..K-1 hold the list in ascending order; empty entries are TP_NOKEY and sort last.  Keys are distinct (the low
-// word is the centroid).  Insert the wave-uniform candidate ck unless K entries already come before it.
-__device__ inline void tp_insert(unsigned long long &lk, unsigned long long ck, int lane)
-{
-    const unsigned long long m = __ballot(lane < TP_K && lk < ck);
-    const int p = __popcll(m);                          // entries before the candidate: lanes 0..p-1
-    if (p >= TP_K) return;
-    const unsigned long long uk = __shfl_up(lk, 1);
-    if (lane > p && lane < TP_K) lk = uk;
-    if (lane == p) lk = ck;
-}
+// ---- the entry of the lists: the 64-bit key (cost << 32) | centroid -----------------------------------------------------
+// Keys are distinct (the low word is the centroid); TP_NOKEY is the empty entry.
+struct TpEntry {
+    unsigned long long key;
+    typedef unsigned long long *Part;
+    typedef const unsigned long long *CPart;
+    typedef unsigned long long Item;
+    __device__ static TpEntry none() { return {TP_NOKEY}; }
+    __device__ bool valid() const { return key != TP_NOKEY; }
+    __device__ bool before(TpEntry o) const { return key < o.key; }
+    template <typename F> __device__ TpEntry map(F f) const { return {f(key)}; }
+    __device__ static TpEntry load(const CPart p, size_t o) { return {p[o]}; }
+    __device__ void store(const Part p, size_t o) const { p[o] = key; }
+    __device__ Item item() const { return key; }
+    __device__ static int centroid(Item it) { return (int)(it & 0xffffffffull); }
+};
 
-// candidates (one per lane, TP_NOKEY = none) into the list, in lane order
-__device__ inline void tp_offer(unsigned long long &lk, unsigned long long key, int lane)
+// the key of centroid j in the field fld: its cost there, or none
+__device__ inline TpEntry tp_key(const unsigned int *__restrict__ fld, const unsigned int *__restrict__ coff, int j)
 {
-    const unsigned long long kth = __shfl(lk, TP_K - 1);
-    unsigned long long m = __ballot(key < kth);         // false for TP_NOKEY
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        tp_insert(lk, __shfl(key, src), lane);
+    const unsigned int o = coff[j];
+    if (o != TP_NOCELL) {
+        const unsigned int v = fld[o];
+        if (v != PL_INF) return {((unsigned long long)v << 32) | (unsigned int)j};
     }
+    return TpEntry::none();
 }
 
 // one wave per (field of the group, chunk of centroids): fields[f] is the field of bot fbot[g0 + f]
-__global__ void __launch_bounds__(64 * TP_BOTS_PER_BLOCK)
+__global__ void __launch_bounds__(64 * AS_BOTS_PER_BLOCK)
 qs_tbp_gather_kernel(const unsigned int *__restrict__ fields, size_t fcells, const unsigned int *__restrict__ coff, int n_cent,
                      const int *__restrict__ fbot, int g0, int gn, int n_chunks, unsigned long long *__restrict__ part)
 {
     const int lane = threadIdx.x & 63;
-    const int f = blockIdx.y * TP_BOTS_PER_BLOCK + (threadIdx.x >> 6), chunk = blockIdx.x;
+    const int f = blockIdx.y * AS_BOTS_PER_BLOCK + (threadIdx.x >> 6), chunk = blockIdx.x;
     if (f >= gn) return;                                // whole waves; no workgroup barrier below
     const unsigned int *fld = fields + (size_t)f * fcells;
-    unsigned long long lk = TP_NOKEY;
-    const int lo = chunk * TP_CHUNK, hi = min(lo + TP_CHUNK, n_cent);
+    TpEntry l = TpEntry::none();
+    const int lo = chunk * AS_CHUNK, hi = min(lo + AS_CHUNK, n_cent);
     for (int base = lo; base < hi; base += 64) {
         const int j = base + lane;
-        unsigned long long key = TP_NOKEY;
-        if (j < hi) {
-            const unsigned int o = coff[j];
-            if (o != TP_NOCELL) {
-                const unsigned int v = fld[o];
-                if (v != PL_INF) key = ((unsigned long long)v << 32) | (unsigned int)j;
-            }
-        }
-        tp_offer(lk, key, lane);
+        as_offer(l, j < hi ? tp_key(fld, coff, j) : TpEntry::none(), lane);
     }
-    if (lane < TP_K) part[((size_t)fbot[g0 + f] * n_chunks + chunk) * TP_K + lane] = lk;
+    if (lane < AS_K) l.store(part, ((size_t)fbot[g0 + f] * n_chunks + chunk) * AS_K + lane);
 }
 
 // one wave per bot with a cell: merge its chunk lists into the exact top-K (list, list_len = entries in it)
-__global__ void __launch_bounds__(64 * TP_BOTS_PER_BLOCK)
+__global__ void __launch_bounds__(64 * AS_BOTS_PER_BLOCK)
 qs_tbp_merge_kernel(const int *__restrict__ fbot, int n_live, int n_chunks, const unsigned long long *__restrict__ part,
                     unsigned long long *__restrict__ list, int *__restrict__ list_len)
 {
     const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * TP_BOTS_PER_BLOCK + (threadIdx.x >> 6);
+    const int i = blockIdx.x * AS_BOTS_PER_BLOCK + (threadIdx.x >> 6);
     if (i >= n_live) return;
     const int bot = fbot[i];
-    unsigned long long lk = TP_NOKEY;
-    const size_t n = (size_t)n_chunks * TP_K, base0 = (size_t)bot * n;
-    for (size_t base = 0; base < n; base += 64) {
-        const size_t e = base + lane;
-        tp_offer(lk, e < n ? part[base0 + e] : TP_NOKEY, lane);
-    }
-    if (lane < TP_K) list[(size_t)bot * TP_K + lane] = lk;
-    const int len = __popcll(__ballot(lane < TP_K && lk != TP_NOKEY));
+    const size_t n = (size_t)n_chunks * AS_K;
+    int len;
+    const TpEntry l = as_merge_lists<TpEntry>(part, (size_t)bot * n, n, lane, len);
+    if (lane < AS_K) list[(size_t)bot * AS_K + lane] = l.item();
     if (lane == 0) list_len[bot] = len;
 }
 
-// ---- the greedy pass: one wave, the bots in order -------------------------------------------------------------------
-// Targets assigned so far live in LDS (and in asg_* / pair* for a resumed pass and for the waypoints).  fb_pending: the
-// previous launch stopped at start_bot and a fallback scan has left its per-block minima in fb_key.
+// ---- the greedy pass (assign_common.h): a decision leaves the centroid, the cost, a status and, for the waypoints, the
+// (start, goal) cells of the assigned bots in assignment order.  A bot without a cell has no list to look at.
+struct TpPolicy {
+    const long long *cent_cell, *bot_cell;
+    int n_bots;
+    long long *pair; int *pair_bot;
+    long long *tgt_idx; unsigned int *tgt_cost; int *tgt_status;
+    __device__ void assigned(int b, int m, unsigned long long key, double2) const
+    {
+        const int k = TpEntry::centroid(key);
+        pair[m] = bot_cell[b]; pair[n_bots + m] = cent_cell[k]; pair_bot[m] = b;
+        tgt_idx[b] = k; tgt_cost[b] = (unsigned int)(key >> 32); tgt_status[b] = QS_PLAN_OK;
+    }
+    __device__ void none(int b, int status) const { tgt_idx[b] = -1; tgt_cost[b] = PL_INF; tgt_status[b] = status; }
+    __device__ void unassigned(int b) const { none(b, QS_PLAN_UNREACHABLE); }
+    __device__ bool skip(int b, int lane) const
+    {
+        if (bot_cell[b] >= 0) return false;
+        if (lane == 0) none(b, QS_PLAN_NO_START);
+        return true;
+    }
+};
+
 __global__ void __launch_bounds__(64)
 qs_tbp_greedy_kernel(const double2 *__restrict__ cent, const long long *__restrict__ cent_cell,
                      const long long *__restrict__ bot_cell, int n_bots, double r2_sep,
@@ -191,106 +195,23 @@ qs_tbp_greedy_kernel(const double2 *__restrict__ cent, const long long *__restri
                      int fb_pending, const unsigned long long *__restrict__ fb_key, int n_fb, double2 *__restrict__ asg_xy,
                      int *__restrict__ asg_idx, long long *__restrict__ pair, int *__restrict__ pair_bot,
                      long long *__restrict__ tgt_idx, unsigned int *__restrict__ tgt_cost, int *__restrict__ tgt_status,
-                     QsTbpState *__restrict__ st)
+                     QsAssignState *__restrict__ st)
 {
-    __shared__ double2 s_xy[QS_FT_MAX_BOTS];
-    __shared__ int s_idx[QS_FT_MAX_BOTS];
-    const int lane = threadIdx.x;
-    int m = start_m, b = start_bot;
-    for (int j = lane; j < m; j += 64) { s_xy[j] = asg_xy[j]; s_idx[j] = asg_idx[j]; }
-    __syncthreads();
-    auto assign = [&](unsigned long long key) {
-        const int k = (int)(key & 0xffffffffull);
-        const double2 t = cent[k];
-        if (lane == 0) {
-            s_xy[m] = t; s_idx[m] = k; asg_xy[m] = t; asg_idx[m] = k;
-            pair[m] = bot_cell[b]; pair[n_bots + m] = cent_cell[k]; pair_bot[m] = b;
-            tgt_idx[b] = k; tgt_cost[b] = (unsigned int)(key >> 32); tgt_status[b] = QS_PLAN_OK;
-        }
-        m++;
-        __syncthreads();
-    };
-    auto none = [&](int status) {
-        if (lane == 0) { tgt_idx[b] = -1; tgt_cost[b] = PL_INF; tgt_status[b] = status; }
-    };
-    if (fb_pending) {
-        unsigned long long k = TP_NOKEY;
-        for (int q = lane; q < n_fb; q += 64) k = fb_key[q] < k ? fb_key[q] : k;
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_xor(k, off);
-            k = o < k ? o : k;
-        }
-        if (k != TP_NOKEY) assign(k);
-        else none(QS_PLAN_UNREACHABLE);
-        b++;
-    }
-    for (; b < n_bots; b++) {
-        if (bot_cell[b] < 0) { none(QS_PLAN_NO_START); continue; }
-        const int len = list_len[b];
-        const unsigned long long *lst = list + (size_t)b * TP_K;
-        unsigned long long pick = TP_NOKEY;
-        for (int e = 0; e < len; e++) {
-            const unsigned long long key = lst[e];
-            const int k = (int)(key & 0xffffffffull);
-            const double2 q = cent[k];
-            bool blk = false;
-            for (int j = lane; j < m; j += 64) {
-                const double2 t = s_xy[j];
-                const double dx = q.x - t.x, dy = q.y - t.y;
-                blk |= s_idx[j] == k || dx * dx + dy * dy < r2_sep;      // taken / too close (qs_frontier_targets' test)
-            }
-            if (__ballot(blk) == 0) { pick = key; break; }
-        }
-        if (pick != TP_NOKEY) assign(pick);
-        else if (len == TP_K) {                          // a full list, all of it ineligible: a whole-GPU scan decides
-            if (lane == 0) { st->next_bot = b; st->m = m; st->stop = 1; }
-            return;
-        } else none(QS_PLAN_UNREACHABLE);                // the list holds every centroid with a finite cost
-    }
-    if (lane == 0) { st->next_bot = n_bots; st->m = m; st->stop = 0; }
+    as_greedy_walk<TpEntry>(TpPolicy{cent_cell, bot_cell, n_bots, pair, pair_bot, tgt_idx, tgt_cost, tgt_status}, cent, n_bots, r2_sep,
+                            list, list_len, start_bot, start_m, fb_pending, fb_key, n_fb, asg_xy, asg_idx, st);
 }
 
 // ---- the fallback: every centroid for one bot, whose field is fields[0] -----------------------------------------------
-__global__ void __launch_bounds__(TP_FB_BLOCK)
+__global__ void __launch_bounds__(AS_FB_BLOCK)
 qs_tbp_fallback_kernel(const unsigned int *__restrict__ fld, const unsigned int *__restrict__ coff,
                        const double2 *__restrict__ cent, int n_cent, int m, double r2_sep, const double2 *__restrict__ asg_xy,
                        const int *__restrict__ asg_idx, unsigned long long *__restrict__ fb_key)
 {
-    __shared__ double2 s_xy[TP_FB_BLOCK];
-    __shared__ int s_idx[TP_FB_BLOCK];
-    __shared__ unsigned long long s_k[TP_FB_BLOCK / QS_WAVE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = blockIdx.x * TP_FB_BLOCK + tid;
+    const int j = blockIdx.x * AS_FB_BLOCK + threadIdx.x;
     double2 q = make_double2(0.0, 0.0);
-    unsigned long long k = TP_NOKEY;
-    if (j < n_cent) {
-        q = cent[j];
-        const unsigned int o = coff[j];
-        if (o != TP_NOCELL) {
-            const unsigned int v = fld[o];
-            if (v != PL_INF) k = ((unsigned long long)v << 32) | (unsigned int)j;
-        }
-    }
-    for (int t0 = 0; t0 < m; t0 += TP_FB_BLOCK) {
-        __syncthreads();
-        if (t0 + tid < m) { s_xy[tid] = asg_xy[t0 + tid]; s_idx[tid] = asg_idx[t0 + tid]; }
-        __syncthreads();
-        const int tn = min(TP_FB_BLOCK, m - t0);
-        for (int t = 0; t < tn && k != TP_NOKEY; t++) {
-            const double dx = q.x - s_xy[t].x, dy = q.y - s_xy[t].y;
-            if (s_idx[t] == j || dx * dx + dy * dy < r2_sep) k = TP_NOKEY;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(k, off);
-        k = o < k ? o : k;
-    }
-    if (lane == 0) s_k[wave] = k;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < TP_FB_BLOCK / QS_WAVE; w++) k = s_k[w] < k ? s_k[w] : k;
-        fb_key[blockIdx.x] = k;
-    }
+    TpEntry e = TpEntry::none();
+    if (j < n_cent) { q = cent[j]; e = tp_key(fld, coff, j); }
+    as_fallback_block<TpEntry>(e.valid(), j, q, m, r2_sep, asg_xy, asg_idx, fb_key, [&] { return e; });
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
@@ -353,7 +274,7 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
         for (size_t b = 0; b < n_bots; b++)
             if (bcell[b] >= 0) { fcell.push_back(bcell[b]); fbot.push_back((int)b); }
         const size_t n_live = fcell.size();
-        const int nch = (int)tp_chunks(n_cent);
+        const int nch = (int)as_chunks(n_cent);
         if (n_live && n_cent) {
             HIPCHK(c, hipMemcpyAsync(T.fcell, fcell.data(), n_live * sizeof(long long), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(T.fbot, fbot.data(), n_live * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -363,39 +284,35 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
                 const size_t gn = std::min(g, n_live - g0);
                 rc = plan_fields(c, L, bbox, T.fcell, T.fcell, g0, gn);
                 if (rc != QS_OK) return rc;
-                const unsigned int gy = (unsigned int)((gn + TP_BOTS_PER_BLOCK - 1) / TP_BOTS_PER_BLOCK);
-                hipLaunchKernelGGL(qs_tbp_gather_kernel, dim3((unsigned int)nch, gy), dim3(64 * TP_BOTS_PER_BLOCK), 0, c->stream,
+                const unsigned int gy = (unsigned int)((gn + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK);
+                hipLaunchKernelGGL(qs_tbp_gather_kernel, dim3((unsigned int)nch, gy), dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream,
                                    L.fields, fcells, T.coff, (int)n_cent, T.fbot, (int)g0, (int)gn, nch, T.part);
                 HIPCHK(c, hipGetLastError());
             }
-            hipLaunchKernelGGL(qs_tbp_merge_kernel, dim3((unsigned int)((n_live + TP_BOTS_PER_BLOCK - 1) / TP_BOTS_PER_BLOCK)),
-                               dim3(64 * TP_BOTS_PER_BLOCK), 0, c->stream, T.fbot, (int)n_live, nch, T.part, T.list, T.list_len);
+            hipLaunchKernelGGL(qs_tbp_merge_kernel, dim3((unsigned int)((n_live + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK)),
+                               dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream, T.fbot, (int)n_live, nch, T.part, T.list, T.list_len);
             HIPCHK(c, hipGetLastError());
         }
         // the greedy pass; a bot whose full list is ineligible gets its field again and a scan of every centroid
         const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation
-        int start = 0, pending = 0;
-        for (;;) {
-            hipLaunchKernelGGL(qs_tbp_greedy_kernel, dim3(1), dim3(64), 0, c->stream, T.xy, T.cell, T.cell + n_cent, (int)n_bots,
-                               r2_sep, T.list, T.list_len, start, m, pending, T.fb_key, (int)tp_fb_blocks(n_cent), T.asg_xy,
-                               T.asg_idx, T.pair, T.pair_bot, T.tgt_idx, T.tgt_cost, T.tgt_status, T.st);
-            HIPCHK(c, hipGetLastError());
-            QsTbpState gs;
-            HIPCHK(c, hipMemcpyAsync(&gs, T.st, sizeof gs, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            m = gs.m;
-            if (!gs.stop) break;
-            if (gs.next_bot < start || gs.next_bot >= (int)n_bots || (pending && gs.next_bot == start))
-                return qs_fail(c, QS_E_HIP, "qs_frontier_targets_by_path: greedy pass made no progress");
-            fallbacks++;
-            groups++;
-            start = gs.next_bot; pending = 1;
-            rc = plan_fields(c, L, bbox, T.cell + n_cent, T.cell + n_cent, (size_t)start, 1);
-            if (rc != QS_OK) return rc;
-            hipLaunchKernelGGL(qs_tbp_fallback_kernel, dim3((unsigned int)tp_fb_blocks(n_cent)), dim3(TP_FB_BLOCK), 0, c->stream,
-                               L.fields, T.coff, T.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, T.fb_key);
-            HIPCHK(c, hipGetLastError());
-        }
+        const int nfb = (int)as_fb_blocks(n_cent);
+        rc = as_run_greedy(c, "qs_frontier_targets_by_path: greedy pass made no progress", T.st, n_bots,
+            [&](int start, int m, int pending) {
+                hipLaunchKernelGGL(qs_tbp_greedy_kernel, dim3(1), dim3(64), 0, c->stream, T.xy, T.cell, T.cell + n_cent, (int)n_bots,
+                                   r2_sep, T.list, T.list_len, start, m, pending, T.fb_key, nfb, T.asg_xy, T.asg_idx, T.pair,
+                                   T.pair_bot, T.tgt_idx, T.tgt_cost, T.tgt_status, T.st);
+                return hipGetLastError();
+            },
+            [&](int bot, int m) {                                   // the bot's field again, then every centroid for it
+                groups++;
+                const int rcf = plan_fields(c, L, bbox, T.cell + n_cent, T.cell + n_cent, (size_t)bot, 1);
+                if (rcf != QS_OK) return rcf;
+                hipLaunchKernelGGL(qs_tbp_fallback_kernel, dim3((unsigned int)nfb), dim3(AS_FB_BLOCK), 0, c->stream, L.fields, T.coff,
+                                   T.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, T.fb_key);
+                HIPCHK(c, hipGetLastError());
+                return (int)QS_OK;
+            }, m, fallbacks);
+        if (rc != QS_OK) return rc;
         // waypoints: qs_plan_paths' fields and walks for the m assigned pairs (starts pair[0..m), goals pair[n_bots ..))
         if (wp_xy && m) {
             const size_t g = qs_plan_group(L, bbox, (size_t)m);

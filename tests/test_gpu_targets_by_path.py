@@ -13,7 +13,7 @@ import plan_rules as R
 from conftest import GOLDEN, load_pkg
 
 pytestmark = pytest.mark.gpu
-K = 32          # TP_K
+K = 32          # AS_K
 
 
 @pytest.fixture(scope="module")

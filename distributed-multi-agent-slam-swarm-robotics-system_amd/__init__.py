@@ -8,11 +8,11 @@ or through the alias module `quasar_amd` at the repository root.
 """
 from . import protocol
 from ._lib import QuasarError, QsConfig, build, load, LIB_PATH
-from .mapper import OccupancyGrid, PoseGraphSLAM, QuasarMapper, checkpoint_config
+from .mapper import MapView, OccupancyGrid, PoseGraphSLAM, QuasarMapper, checkpoint_config
 from .protocol import (PACKET_FMT, PACKET_FMT_V1, PACKET_SIZE, PACKET_SIZE_V1, ZONE_FMT, ZONE_SIZE,
                        compute_bounding_box, pack_packet, pack_packets, zone_packet)
 
-__all__ = ["protocol", "QuasarError", "QsConfig", "build", "load", "LIB_PATH", "OccupancyGrid",
+__all__ = ["protocol", "QuasarError", "QsConfig", "build", "load", "LIB_PATH", "MapView", "OccupancyGrid",
            "PoseGraphSLAM", "QuasarMapper", "checkpoint_config", "PACKET_FMT", "PACKET_FMT_V1", "PACKET_SIZE",
            "PACKET_SIZE_V1", "ZONE_FMT", "ZONE_SIZE", "compute_bounding_box", "pack_packet",
            "pack_packets", "zone_packet"]

@@ -50,6 +50,14 @@ class QsMergeResult(C.Structure):
                 ("fitness", C.c_double), ("rmse", C.c_double), ("T", C.c_double * 9)]
 
 
+class QsViewParams(C.Structure):
+    """struct qs_view_params (include/quasar_slam.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("scale", C.c_double), ("offset_x", C.c_double),
+                ("offset_y", C.c_double), ("line_min", C.c_int32), ("line_max", C.c_int32), ("bg", C.c_uint8 * 4),
+                ("line", C.c_uint8 * 4), ("free", C.c_uint8 * 4), ("occ", C.c_uint8 * 4), ("draw_occupied", C.c_int32),
+                ("minify", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 QS_MERGE_STATUS = ("empty", "adopted", "merged", "rejected")     # QS_MERGE_EMPTY .. QS_MERGE_REJECTED (include/quasar_slam.h)
 
 
@@ -186,6 +194,8 @@ SIGNATURES = {
     "qs_plan_paths": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_frontier_targets_by_path": (_i32, [_vp, _i32, _f64, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                            C.POINTER(_sz), _vp]),
+    "qs_render_view": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "qs_render_view_device": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "qs_ekf_init": (_i32, [_vp, _i32, _f64, _vp]),
     "qs_ekf_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32]),
     "qs_ekf_state": (_i32, [_vp, _i32, _vp, _vp]),

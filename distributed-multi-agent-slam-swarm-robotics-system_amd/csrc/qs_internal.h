@@ -267,6 +267,7 @@ struct qs_ctx {
     DevBuf<char> plan_ws;                        // path planning (plan.hip: qs_plan_layout)
     DevBuf<char> tbp_ws;                         // targets by path cost (targets_by_path.hip: qs_tbp_layout)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
+    DevBuf<char> view_ws;                        // map view (view.hip: qs_view_layout): state / owner frames, index tables, uploaded lists
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
     DevBuf<unsigned int> ck_census;              // checkpoint (checkpoint.hip): block bitmap, block list, count
     DevBuf<unsigned char> ck_stage;              //   ... and the body of the file as it travels (both ways)

@@ -14,7 +14,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from ._lib import QsConfig, QsMergeResult, QS_MERGE_STATUS, QuasarError, UINT64_MAX, check
+from ._lib import QsConfig, QsMergeResult, QsViewParams, QS_MERGE_STATUS, QuasarError, UINT64_MAX, check
 from . import protocol as P
 
 
@@ -471,6 +471,37 @@ class QuasarMapper:
 
     def grid_i8_device(self, d_out):
         self._chk(self._L.qs_grid_i8_device(self._h, C.c_void_p(d_out)), "qs_grid_i8_device")
+
+    # -- map view: MapRenderer, dual_bot_mapper.py:380-668, rendered on the device (include/quasar_slam.h) ----------------
+    def render_view(self, width=P.VIEW_WIDTH, height=P.VIEW_HEIGHT, scale=P.VIEW_SCALE, offset_x=None, offset_y=None,
+                    zones=None, prims=None, line_min=P.VIEW_LINE_MIN, line_max=P.VIEW_LINE_MAX, bg=P.BG_COLOR,
+                    line=P.GRID_COLOR, free=P.CELL_COLOR_FREE, occ=P.CELL_COLOR_OCCUPIED, draw_occupied=False, minify=True,
+                    d_out=None):
+        """One frame of the map -> uint8 [height, width, 4] (R, G, B, 255; row 0 at the top).  The defaults are the
+        reference's view (:383-397): offsets default to width / 2 and height / 2.  zones: P.VIEW_ZONE_DTYPE records (or None),
+        prims: P.VIEW_PRIM_DTYPE records (or None), drawn in array order; MapView.lists builds both in the reference's draw
+        order.  minify=False gives the reference's behaviour below 2 pixels per cell: no occupancy at all.  With d_out (a
+        device address or a torch uint8 tensor of height * width * 4 bytes on this GPU) the frame stays on the device and
+        None is returned.  Reads the map, writes nothing."""
+        vp = QsViewParams()
+        vp.width, vp.height, vp.scale = int(width), int(height), float(scale)
+        vp.offset_x = float(width / 2 if offset_x is None else offset_x)
+        vp.offset_y = float(height / 2 if offset_y is None else offset_y)
+        vp.line_min, vp.line_max = int(line_min), int(line_max)
+        for name, c in (("bg", bg), ("line", line), ("free", free), ("occ", occ)):
+            getattr(vp, name)[:3] = [int(v) for v in c[:3]]
+        vp.draw_occupied, vp.minify = int(bool(draw_occupied)), int(bool(minify))
+        z = np.ascontiguousarray(zones if zones is not None else [], dtype=P.VIEW_ZONE_DTYPE).reshape(-1)
+        q = np.ascontiguousarray(prims if prims is not None else [], dtype=P.VIEW_PRIM_DTYPE).reshape(-1)
+        zp, qp = (_ptr(z) if len(z) else None), (_ptr(q) if len(q) else None)
+        if d_out is not None:
+            self._chk(self._L.qs_render_view_device(self._h, C.byref(vp), zp, len(z), qp, len(q), C.c_void_p(_dev_addr(d_out))),
+                      "qs_render_view_device")
+            return None
+        ok = 1 <= vp.width <= 8192 and 1 <= vp.height <= 8192          # (the library refuses the rest; no buffer for it)
+        out = np.empty((vp.height, vp.width, 4) if ok else (1, 1, 4), dtype=np.uint8)
+        self._chk(self._L.qs_render_view(self._h, C.byref(vp), zp, len(z), qp, len(q), _ptr(out)), "qs_render_view")
+        return out
 
     def counts(self):
         hits = np.empty((self.size, self.size), dtype=np.int32)
@@ -1043,6 +1074,111 @@ class QuasarMapper:
         ln = np.zeros(len(_lib.QS_STAGE_NAMES), dtype=np.uint64)
         self._chk(self._L.qs_stage_times(self._h, _ptr(ms), _ptr(ln), int(reset)), "qs_stage_times")
         return {k: (float(m), int(c)) for k, m, c in zip(_lib.QS_STAGE_NAMES, ms, ln)}
+
+
+class MapView:
+    """The view state of the reference's renderer (MapRenderer.__init__, :383-402): width, height, scale (pixels per
+    metre), offset_x / offset_y (screen position of the world origin), with its zoom and pan (:415-430) and the lists of one
+    frame in its draw order (:447-468).  scale_limits are the reference's 20..500 by default; a 200 m map needs about
+    4 px/m, so they are a parameter."""
+
+    def __init__(self, width=P.VIEW_WIDTH, height=P.VIEW_HEIGHT, scale=P.VIEW_SCALE, offset_x=None, offset_y=None,
+                 scale_limits=P.VIEW_SCALE_LIMITS):
+        self.width, self.height = int(width), int(height)
+        self.scale_limits = (float(scale_limits[0]), float(scale_limits[1]))
+        self.scale = float(scale)
+        self.offset_x = width / 2 if offset_x is None else offset_x          # :396-397
+        self.offset_y = height / 2 if offset_y is None else offset_y
+
+    def zoom(self, factor):
+        """The mouse wheel (:417-419): scale *= factor, clamped to scale_limits."""
+        self.scale = max(self.scale_limits[0], min(self.scale_limits[1], self.scale * factor))
+        return self.scale
+
+    def pan(self, dx, dy):
+        """A drag by (dx, dy) pixels (:427-430)."""
+        self.offset_x += dx
+        self.offset_y += dy
+
+    def world_to_screen(self, wx, wy):                                       # :404-408
+        return int(self.offset_x + wx * self.scale), int(self.offset_y - wy * self.scale)
+
+    def _on_screen(self, xy):
+        """The reference's test before a cloud point is drawn (:567-568), vectorised: R0 of the points inside the frame."""
+        with np.errstate(all="ignore"):
+            vx = self.offset_x + xy[:, 0] * self.scale
+            vy = self.offset_y - xy[:, 1] * self.scale
+            ok = (np.abs(vx) <= 2.0 ** 30) & (np.abs(vy) <= 2.0 ** 30)
+            sx, sy = np.trunc(np.where(ok, vx, -9.0)), np.trunc(np.where(ok, vy, -9.0))
+        return ok & (sx >= 0) & (sx < self.width) & (sy >= 0) & (sy < self.height)
+
+    def lists(self, zone_boxes=None, point_clouds=None, paths=None, bot_states=None, targets=None, closures=None):
+        """(zones, prims) of one frame, in the reference's draw order (:447-468):
+          1. zones in bot-id order, colour 'main' (:537-551); a None box is skipped;
+          2. per bot (ascending id) and sensor (the clouds' own order) the last 2000 cloud points whose screen point is inside
+             the frame (:561, :568), 8 x 8 squares for bot 1 left and bot 2 right (:563-565), single pixels otherwise;
+          3. per bot its path ([xs], [ys]) subsampled by max(1, len // 500), as segments in 'path' (:576-589);
+          4. target lines from an online bot's state to its target in 'main' (:619-628), then closure lines
+             (x1, y1, x2, y2) (:632-637).
+        Colours are protocol.bot_colors(bot_id)."""
+        zones = []
+        for b in sorted(zone_boxes or {}):
+            box = zone_boxes[b]
+            if box is not None:
+                zones.append((tuple(float(v) for v in box), tuple(P.bot_colors(b)["main"]) + (0,), 0))
+        chunks = []
+
+        def add(kind, size, color, x0, y0, x1=None, y1=None):
+            a = np.zeros(len(x0), dtype=P.VIEW_PRIM_DTYPE)
+            a["x0"], a["y0"] = x0, y0
+            a["x1"], a["y1"] = (x0 if x1 is None else x1), (y0 if y1 is None else y1)
+            a["kind"], a["size"] = kind, size
+            a["color"][:, :3] = color
+            chunks.append(a)
+
+        for b in sorted(point_clouds or {}):
+            colors = P.bot_colors(b)
+            for sensor, points in point_clouds[b].items():
+                if len(points) == 0:
+                    continue
+                xy = np.asarray(points[-P.VIEW_CLOUD_RECENT:], dtype=np.float64).reshape(-1, 2)
+                xy = xy[self._on_screen(xy)]
+                rect = (b == 1 and sensor == "left") or (b == 2 and sensor == "right")
+                add(P.VIEW_SQUARE if rect else P.VIEW_POINT, P.VIEW_CLOUD_RECT if rect else 1,
+                    colors.get(sensor, (150, 150, 150)), xy[:, 0], xy[:, 1])
+        for b in sorted(paths or {}):
+            xs, ys = paths[b]
+            if len(xs) < 2:
+                continue
+            step = max(1, len(xs) // P.VIEW_PATH_POINTS)
+            x = np.asarray(xs, dtype=np.float64)[::step]
+            y = np.asarray(ys, dtype=np.float64)[::step]
+            if len(x) >= 2:
+                add(P.VIEW_SEGMENT, 1, P.bot_colors(b)["path"], x[:-1], y[:-1], x[1:], y[1:])
+        for b, (tx, ty) in (targets or {}).items():
+            st = (bot_states or {}).get(b)
+            if st and st["online"]:
+                add(P.VIEW_SEGMENT, 1, P.bot_colors(b)["main"], [st["x"]], [st["y"]], [tx], [ty])
+        for x1, y1, x2, y2 in (closures or ()):
+            add(P.VIEW_SEGMENT, 1, P.CLOSURE_LINE_COLOR, [x1], [y1], [x2], [y2])
+        return (np.array(zones, dtype=P.VIEW_ZONE_DTYPE).reshape(-1),
+                np.concatenate(chunks) if chunks else np.zeros(0, dtype=P.VIEW_PRIM_DTYPE))
+
+    def frame(self, mapper, zone_boxes=None, point_clouds=None, paths=None, bot_states=None, targets=None, closures=None,
+              **render_args):
+        """One frame of `mapper`'s map under this view with the lists above -> uint8 [height, width, 4]; render_args go to
+        QuasarMapper.render_view (colours, draw_occupied, minify, d_out)."""
+        zones, prims = self.lists(zone_boxes, point_clouds, paths, bot_states, targets, closures)
+        return mapper.render_view(self.width, self.height, self.scale, self.offset_x, self.offset_y, zones=zones, prims=prims,
+                                  **render_args)
+
+    @staticmethod
+    def save_ppm(path, frame):
+        """A frame as a binary PPM (P6): viewable without any imaging library."""
+        frame = np.asarray(frame)
+        with open(path, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (frame.shape[1], frame.shape[0]))
+            f.write(np.ascontiguousarray(frame[:, :, :3]).tobytes())
 
 
 class OccupancyGrid:

@@ -142,6 +142,45 @@ MATCH_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("it", "<i4"), ("score", "
                         ("dx", "<f8"), ("dy", "<f8"), ("dyaw", "<f8")])
 
 
+# ---- map view (include/quasar_slam.h, "map view"): the renderer's constants, dual_bot_mapper.py:346-377, :383-397 ----------
+BG_COLOR = (22, 33, 62)
+GRID_COLOR = (40, 50, 80)
+CELL_COLOR_FREE = (30, 45, 70)
+CELL_COLOR_OCCUPIED = (200, 200, 200)
+CLOSURE_LINE_COLOR = (0, 255, 100)           # :637
+BOT_COLORS = {
+    1: {"main": (0, 191, 255), "path": (0, 120, 180), "front": (255, 68, 68), "left": (68, 255, 68), "back": (255, 136, 0),
+        "right": (68, 136, 255), "name": "Bot1"},
+    2: {"main": (255, 105, 180), "path": (180, 60, 120), "front": (204, 0, 0), "left": (0, 204, 0), "back": (204, 102, 0),
+        "right": (0, 68, 204), "name": "Bot2"},
+}
+VIEW_WIDTH, VIEW_HEIGHT, VIEW_SCALE = 1000, 800, 100.0       # MapRenderer(width, height), self.scale  :383, :395
+VIEW_SCALE_LIMITS = (20.0, 500.0)            # the zoom clamp  :419
+VIEW_LINE_MIN, VIEW_LINE_MAX = -20, 20       # metre lines  :479
+VIEW_CLOUD_RECENT = 2000                     # cloud points drawn per bot and sensor  :561
+VIEW_CLOUD_RECT = 8                          # bot 1 left / bot 2 right are 8 x 8 squares  :563-565
+VIEW_PATH_POINTS = 500                       # a path is subsampled by max(1, len // 500)  :583
+VIEW_POINT, VIEW_SQUARE, VIEW_SEGMENT = 0, 1, 2
+VIEW_ZONE_DTYPE = np.dtype([("box", "<f8", (4,)), ("color", "u1", (4,)), ("reserved", "<i4")])            # struct qs_view_zone
+VIEW_PRIM_DTYPE = np.dtype([("x0", "<f8"), ("y0", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("kind", "<i4"), ("size", "<i4"),
+                            ("color", "u1", (4,)), ("reserved", "<i4")])                                    # struct qs_view_prim
+assert VIEW_ZONE_DTYPE.itemsize == 40 and VIEW_PRIM_DTYPE.itemsize == 48
+
+
+def bot_colors(bot_id):
+    """BOT_COLORS for every id: bots 1 and 2 are the reference's (:351-370).  Beyond them the reference has no colours; the
+    stated rule: 'main' is the fully saturated hue (bot_id * 47) % 360 degrees (integer HSV sectors), 'path' two thirds of it,
+    and the four sensor colours are bot 1's for odd ids and bot 2's for even ids."""
+    if bot_id in BOT_COLORS:
+        return BOT_COLORS[bot_id]
+    hue = (bot_id * 47) % 360
+    sector, ramp = hue // 60, (hue % 60) * 255 // 60
+    main = ((255, ramp, 0), (255 - ramp, 255, 0), (0, 255, ramp), (0, 255 - ramp, 255), (ramp, 0, 255), (255, 0, 255 - ramp))[sector]
+    out = dict(BOT_COLORS[1 if bot_id % 2 else 2])
+    out.update(main=main, path=tuple(2 * v // 3 for v in main), name=f"Bot{bot_id}")
+    return out
+
+
 def pack_v0(agent, x, y, yaw, ranges, scan_count=SWEEP_BEAMS, magic=b"QSRL") -> bytes:
     return struct.pack(PACKET_FMT_V0, magic, agent, x, y, yaw, scan_count, *ranges)
 

@@ -30,6 +30,9 @@ last_matches holds the matches of the latest run.
 With sweep_graph=True or a dict of half_width / close / open (opt-in, needs sweeps=True) the mapper is put into graph mode at
 construction (QuasarMapper.set_sweep_graph): sweeps become pose-graph nodes, close loops and feed their bot's zone box, so
 zone_tick sends a sweep bot's partner a real box.
+With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
+point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
+poses; mapper.MapView.frame draws them.
 Differences: the reference throttles itself to 20 packets per 30 fps frame (:816, :474); here a
 poll drains the socket (up to max_batch datagrams).  Host-side Python only; the mapper can be any
 object with ingest_array / last_batch / zone_packet (tests use a stub, production the HIP mapper).
@@ -48,7 +51,7 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
-                 match_params=None, targets_by_path=False, sweep_graph=False):
+                 match_params=None, targets_by_path=False, sweep_graph=False, track_view=False):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
         if targets_by_path and not frontier_targets:
@@ -60,6 +63,9 @@ class MissionControl:
             raise ValueError("MissionControl: sweep_graph needs sweeps=True")
         if self.sweep_graph:
             mapper.set_sweep_graph(True, **(dict(sweep_graph) if isinstance(sweep_graph, dict) else {}))
+        self.track_view = track_view
+        self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
+        self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
         self.match_sweeps = match_sweeps
         self.match_params = dict(match_params) if match_params else True
         self.last_matches = None
@@ -121,6 +127,8 @@ class MissionControl:
             self.mapper.ingest_array(self._buf[:n], self._lens[:n], self._times[:n])
             accepted, pose = self.mapper.last_batch()
             self._mark(0, accepted, pose, now, self.frontier_targets and pose is not None)
+            if self.track_view:
+                self._track(0, accepted, pose)
             return n
         for i0, i1, kind in self._runs(n):
             lens = self._lens[i0:i1]
@@ -128,6 +136,8 @@ class MissionControl:
                 self.mapper.ingest_array(self._buf[i0:i1, :SLOT], lens, self._times[i0:i1])
                 accepted, pose = self.mapper.last_batch()
                 self._mark(i0, accepted, pose, now, self.frontier_targets and pose is not None)
+                if self.track_view:
+                    self._track(i0, accepted, pose)
             else:
                 if self.match_sweeps:
                     self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens, match=self.match_params)
@@ -159,6 +169,17 @@ class MissionControl:
             self.seen[a] = True
             if keep_pose:
                 self.bot_pose[a] = (float(pose[j, 0]), float(pose[j, 1]))
+
+    def _track(self, i0, accepted, pose):
+        """track_view: the renderer's inputs of the accepted packets of one ingest (:878-879 the path, :892 the clouds)."""
+        xy, valid = self.mapper.last_hits()
+        for j in np.nonzero(accepted)[0]:
+            a = int(self._buf[i0 + int(j), 4])
+            self.paths[a][0].append(float(pose[j, 0]))
+            self.paths[a][1].append(float(pose[j, 1]))
+            for s, name in enumerate(P.SENSOR_NAMES):
+                if valid[j, s]:
+                    self.point_clouds[a][name].append((float(xy[j, s, 0]), float(xy[j, s, 1])))
 
     # ---- :805-812 --------------------------------------------------------------------------------
     def heartbeat(self, now=None):

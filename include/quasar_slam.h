@@ -593,6 +593,74 @@ int qs_frontier_targets_by_path(qs_ctx *ctx, int32_t min_cluster, double separat
                                 uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
                                 double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8]);
 
+/* ---- map view: the "Mission Control" map, MapRenderer  dual_bot_mapper.py:380-668 -------------------------------------------
+ * One call renders a frame of the map for any pan and zoom on the device and hands back only the frame: [height][width][4]
+ * bytes R, G, B, 255, row 0 at the top.  The layers are the reference's (:433-468) as far as its own Python pins their pixels
+ * (set_at, a filled rect, a 1-pixel axis-parallel line); a NumPy restatement (tests/view_rules.py) agrees byte for byte.
+ * Every expression is fp64, each operation rounded on its own; int() truncates toward zero, as Python's does.
+ *  R0 screen mapping (:404-408): sx = int(offset_x + wx*scale), sy = int(offset_y - wy*scale).  A value that is not finite or
+ *     beyond 2^30 in magnitude is not drawn (a zone or segment with one such corner or end is not drawn at all).  Truncation
+ *     toward zero makes pixel column and row 0 take the values in (-1, 1): the reference's behaviour, kept everywhere.
+ *  R1 the frame is filled with bg.
+ *  R2 metre lines (:476-485): for v in line_min..line_max column sx(v) if inside [0, width) and row sy(v) if inside
+ *     [0, height), in `line`.  The origin crosshair is a 2-pixel-wide pygame line: its pixels are pygame's, it is left out.
+ *  R3 occupancy (:492-527): cell_px = max(1, int(res*scale)); a cell's screen point is R0 of its centre ox + (gx+0.5)*res,
+ *     oy + (gy+0.5)*res; its state is the stamp's (0 UNKNOWN, odd OCCUPIED, else FREE).
+ *       cell_px >= 3  each FREE cell fills the cell_px x cell_px square whose top-left is (sx - cell_px/2, sy - cell_px/2),
+ *                     clipped to the frame;
+ *       cell_px == 2  each FREE cell sets the pixel (sx, sy) (the reference's set_at branch);
+ *       cell_px <  2  minify != 0: a pixel's footprint is the set of cells whose screen point is that pixel; with
+ *                     draw_occupied the pixel is `occ` if any footprint cell is OCCUPIED, otherwise `free` if any is FREE,
+ *                     otherwise it stays as R1 / R2 made it.  minify == 0: nothing is drawn (the reference: "too zoomed
+ *                     out", :495-496).
+ *     draw_occupied (a build extension; the reference skips OCCUPIED cells, :519-520): OCCUPIED cells are drawn by the same
+ *     geometry in `occ`, after all FREE cells.
+ *     The rule looks at EVERY cell.  The reference first culls to a visible cell range (:500-508) with no margin on the side of
+ *     the larger indices; a cell just beyond it whose screen y lies in (-cell_px, 0) can still reach frame row 0 through the
+ *     truncation toward zero, and the culled loop drops it.  Frame row 0 is the only place the two can differ.
+ *  R4 zones (:537-551), in array order: (sx1, sy1) = R0(minx, maxy), (sx2, sy2) = R0(maxx, miny), w = sx2 - sx1,
+ *     h = sy2 - sy1; drawn only if w > 0 and h > 0.  Every pixel of [sx1, sx1+w) x [sy1, sy1+h) becomes
+ *     (c*25 + dst*230 + 127) / 255 per channel, then the 1-pixel border of that rectangle is set to c.  Later zones blend over
+ *     earlier ones, borders included.  Rectangle and border geometry are the reference's; the blend arithmetic is this
+ *     build's (alpha 25 of 255, rounded to nearest): pygame's own blit cannot be run where the fixtures are recorded.
+ *  R5 primitives, opaque, in array order: per pixel the highest index that covers it wins.
+ *       QS_VIEW_POINT    the pixel R0(x0, y0) (:574);
+ *       QS_VIEW_SQUARE   size x size pixels, top-left (sx - size/2, sy - size/2) (:570-572), 1 <= size <= 64, clipped;
+ *       QS_VIEW_SEGMENT  the cells of the reference's _bresenham (:158-179) from R0(x0, y0) to R0(x1, y1), both ends
+ *                        inclusive, clipped to the frame, one pixel wide (the reference draws paths and closures with
+ *                        pygame's width-2 lines, whose pixels are pygame's: one pixel wide is this build's rule).  Cell k has
+ *                        major offset k and minor offset (2*k*m + M - 1) / (2*M), M >= m the two extents; k is clipped to the
+ *                        frame along the major axis first, so a segment costs at most the frame's side, whatever its length.
+ *     Robot triangles, labels and the HUD text stay with the host.
+ * Parameters: 1 <= width, height <= QS_VIEW_MAX_DIM; scale finite and > 0 with res*scale <= QS_VIEW_MAX_CELL_PX; offsets
+ * finite; line_max - line_min < QS_VIEW_MAX_LINES (line_max < line_min: no lines); colours are bytes R, G, B (the fourth is
+ * ignored); n_zones <= QS_VIEW_MAX_ZONES, n_prims <= QS_VIEW_MAX_PRIMS; a primitive's kind is one of the three.  Anything
+ * else: QS_E_INVAL.  zones / prims are host arrays in both entry points; d_rgba is device memory on the context's GPU
+ * (asynchronous on the context's stream), rgba_host is complete when the call returns.
+ * The call observes the map (waiting exact-trig rays are resolved first) and writes nothing to the context: stamps,
+ * counters, dirty blocks and zone boxes stay as they were; a checkpoint before equals one after. */
+#define QS_VIEW_MAX_DIM 8192
+#define QS_VIEW_MAX_ZONES 1024
+#define QS_VIEW_MAX_PRIMS (1 << 24)
+#define QS_VIEW_MAX_SQUARE 64
+#define QS_VIEW_MAX_LINES 65536
+#define QS_VIEW_MAX_CELL_PX (1 << 20)
+enum { QS_VIEW_POINT = 0, QS_VIEW_SQUARE = 1, QS_VIEW_SEGMENT = 2 };
+typedef struct qs_view_params {
+    int32_t width, height;                      /* MapRenderer(width, height)  :383 */
+    double scale, offset_x, offset_y;           /* pixels per metre; screen position of the world origin  :395-397 */
+    int32_t line_min, line_max;                 /* metre lines, the reference: -20..20  :479 */
+    uint8_t bg[4], line[4], free[4], occ[4];    /* BG_COLOR, GRID_COLOR, CELL_COLOR_FREE, CELL_COLOR_OCCUPIED  :346-347, :373-374 */
+    int32_t draw_occupied, minify;
+    int32_t reserved[2];
+} qs_view_params;
+typedef struct qs_view_zone { double minx, miny, maxx, maxy; uint8_t color[4]; int32_t reserved; } qs_view_zone;
+typedef struct qs_view_prim { double x0, y0, x1, y1; int32_t kind, size; uint8_t color[4]; int32_t reserved; } qs_view_prim;
+int qs_render_view(qs_ctx *ctx, const qs_view_params *params, const qs_view_zone *zones, size_t n_zones,
+                   const qs_view_prim *prims, size_t n_prims, uint8_t *rgba_host);
+int qs_render_view_device(qs_ctx *ctx, const qs_view_params *params, const qs_view_zone *zones, size_t n_zones,
+                          const qs_view_prim *prims, size_t n_prims, uint8_t *d_rgba);
+
 /* ---- EKF  AgentFirmware_Bot1/ekf.cpp:5-92 ---------------------------------------------- */
 /* On ingest (qs_config.enable_ekf) the filter of every bot runs over the batch: batches of >= 4096
  * packets in a parallel-in-time form that agrees with the step-by-step filter to rounding (~1e-12

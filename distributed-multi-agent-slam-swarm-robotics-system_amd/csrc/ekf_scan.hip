@@ -24,7 +24,11 @@
 // (3) The heading wrap of ekf.cpp:40-41 (one +-2 pi per predict) never feeds back into the
 //     filter (sin, cos and the covariance do not see it), so theta is carried unwrapped and the
 //     number of wraps is replayed: every chunk evaluates the wrap rule for the three wrap counts its
-//     start can have, E4 picks.
+//     start can have, E4 picks.  "Unwrapped" is kept as a pair (theta_r, turns): E2 takes the whole
+//     turns out of the heading at every chunk start (theta = theta_r + 2 pi turns, |theta_r| <= pi, one
+//     fma: exact), so no chunk computes on a heading larger than its own steps add up to.  A heading
+//     carried as one double loses ulp(|theta|) per operation: 6e-11 rad at 3e5 rad, and the positions
+//     integrate it.
 //
 // The arithmetic is a re-association of the sequential filter's, so results agree with it to
 // rounding (1e-13 relative on the CPU restatement of this file's algebra, tests/test_ekf_scan_math.py;
@@ -36,13 +40,14 @@
 #define ES_CHUNK_MAX 1024         // batch is ~256 chunks (E2 / E4 walk a bot's chunks one after the other)
 #define ES_PI 3.14159265358979323846
 #define ES_TWO_PI 6.28318530717958647692
+#define ES_FIN 21
 
 // per accepted record, bot-major, arrival order
 struct EsRec { double t, om, ve; unsigned int kind, pad; };   // kind 0 init, 1 step, 2 nothing
 
 // per chunk
 struct EsAgg1 { double A[16], b[4], C[16], h[4], J[16]; };
-struct EsStart { double s[4], A[16]; };
+struct EsStart { double s[4], A[16]; int turns, pad; };   // heading at the chunk start = s[0] + 2 pi turns
 struct EsAgg2 { double L[16], N[8], m[4], q[2], W[16], U[8], V[4]; int wrap_c, wrap_out[3]; double last_out; };
 
 struct EsWs {
@@ -58,7 +63,7 @@ struct EsWs {
     EsAgg1 *agg1;                // [chunks]
     EsStart *start;              // [chunks]
     EsAgg2 *agg2;                // [chunks]
-    double *fin;                 // [256][20] (s, A) after the batch
+    double *fin;                 // [256][ES_FIN] (s, A, turns) after the batch: heading = s[0] + 2 pi turns
 };
 
 __device__ inline void es_sincos(double x, double *sn, double *cs)
@@ -445,6 +450,15 @@ __device__ inline void es_prior(const EsWs &ws, const QsBatch &b, const double *
     }
 }
 
+// theta -> theta - 2 pi k with k = rint(theta / 2 pi), returns k.  The product k * 2 pi is not rounded (fma), so the pair
+// (theta, k) stands for exactly the heading that came in, as far as the sequential filter's own "-= 2 * pi" does.
+__device__ inline int es_take_turns(double &theta)
+{
+    const double k = rint(theta * (1.0 / ES_TWO_PI));
+    theta = __builtin_fma(-k, ES_TWO_PI, theta);
+    return (int)k;
+}
+
 typedef unsigned long long __attribute__((may_alias)) es_word;      // a chunk's element / coefficients, moved a word per lane
 
 // One WAVE per bot.  The walk over the bot's chunks is a strict recurrence, a 4 x 4 solve per chunk; what it must not do is
@@ -470,12 +484,14 @@ es_apply_kernel(EsWs ws, QsBatch b, const double *__restrict__ ekf, const double
     }
     const unsigned int c0 = ws.chunk_base[bot], c1 = ws.chunk_base[bot + 1];
     es_word nxt = (c0 < c1 && lane < NW) ? ((const es_word *)(ws.agg1 + c0))[lane] : 0ull;
-    int par = 0;
+    int par = 0, turns = 0;
     for (unsigned int c = c0; c < c1; c++, par ^= 1) {
         if (lane < NW) ((es_word *)&el[par])[lane] = nxt;
         if (c + 1 < c1 && lane < NW) nxt = ((const es_word *)(ws.agg1 + c + 1))[lane];
+        turns += es_take_turns(s[0]);
         if (lane == 0) {
             EsStart st;
+            st.turns = turns; st.pad = 0;
             #pragma unroll
             for (int i = 0; i < 4; i++) st.s[i] = s[i];
             #pragma unroll
@@ -485,11 +501,13 @@ es_apply_kernel(EsWs ws, QsBatch b, const double *__restrict__ ekf, const double
         const EsAgg1 e = el[par];
         es_apply(e, s, A);
     }
+    turns += es_take_turns(s[0]);
     if (lane == 0) {
         #pragma unroll
-        for (int i = 0; i < 4; i++) ws.fin[(size_t)bot * 20 + i] = s[i];
+        for (int i = 0; i < 4; i++) ws.fin[(size_t)bot * ES_FIN + i] = s[i];
         #pragma unroll
-        for (int i = 0; i < 16; i++) ws.fin[(size_t)bot * 20 + 4 + i] = A[i];
+        for (int i = 0; i < 16; i++) ws.fin[(size_t)bot * ES_FIN + 4 + i] = A[i];
+        ws.fin[(size_t)bot * ES_FIN + 20] = (double)turns;
     }
 }
 
@@ -514,12 +532,14 @@ es_agg2_kernel(EsWs ws)
     const unsigned int j0 = ws.base[bot] + (c - ws.chunk_base[bot]) * ws.chunk;
     const unsigned int j1 = min(j0 + ws.chunk, ws.base[bot + 1]);
     double s[4], A[16];
+    int wc;                                                   // whole turns E2 took out of the heading at this chunk's start
     {
         const EsStart st = ws.start[c];
         #pragma unroll
         for (int i = 0; i < 4; i++) s[i] = st.s[i];
         #pragma unroll
         for (int i = 0; i < 16; i++) A[i] = st.A[i];
+        wc = st.turns;
     }
     double L[16], N[8], m[4], q[2], W[16], U[8], V[4];
     #pragma unroll
@@ -529,8 +549,7 @@ es_agg2_kernel(EsWs ws)
     #pragma unroll
     for (int i = 0; i < 4; i++) { m[i] = 0.0; V[i] = 0.0; }
     q[0] = 0.0; q[1] = 0.0;
-    const int wc = (int)rint(s[0] * (1.0 / ES_TWO_PI));
-    int wn0 = wc - 1, wn1 = wc, wn2 = wc + 1;
+    int wn0 = -1, wn1 = 0, wn2 = 1;                           // wrap counts relative to wc, as s[0] is
     double last = ws.last_in[c];
     EsRec r = ws.rec[j0];
     for (unsigned int j = j0; j < j1; j++) {
@@ -572,9 +591,9 @@ es_agg2_kernel(EsWs ws)
                 for (int cc = 0; cc < 2; cc++) GAG[2 * rr + cc] = GA[4 * rr] * G0[cc] + GA[4 * rr + 1] * G1[cc];
             // wrap rule of ekf.cpp:40-41 for the three possible wrap counts at the chunk start
             const double a = sp[0];
-            { const double w = a - ES_TWO_PI * wn0; if (w > ES_PI) wn0++; else if (w < -ES_PI) wn0--; }
-            { const double w = a - ES_TWO_PI * wn1; if (w > ES_PI) wn1++; else if (w < -ES_PI) wn1--; }
-            { const double w = a - ES_TWO_PI * wn2; if (w > ES_PI) wn2++; else if (w < -ES_PI) wn2--; }
+            { const double w = __builtin_fma(-(double)wn0, ES_TWO_PI, a); if (w > ES_PI) wn0++; else if (w < -ES_PI) wn0--; }
+            { const double w = __builtin_fma(-(double)wn1, ES_TWO_PI, a); if (w > ES_PI) wn1++; else if (w < -ES_PI) wn1--; }
+            { const double w = __builtin_fma(-(double)wn2, ES_TWO_PI, a); if (w > ES_PI) wn2++; else if (w < -ES_PI) wn2--; }
         } else {
             G0[0] = G0[1] = G1[0] = G1[1] = q0[0] = q0[1] = 0.0;
             #pragma unroll
@@ -704,7 +723,7 @@ es_agg2_kernel(EsWs ws)
     #pragma unroll
     for (int i = 0; i < 4; i++) { o.m[i] = m[i]; o.V[i] = V[i]; }
     o.q[0] = q[0]; o.q[1] = q[1];
-    o.wrap_c = wc; o.wrap_out[0] = wn0; o.wrap_out[1] = wn1; o.wrap_out[2] = wn2;
+    o.wrap_c = wc; o.wrap_out[0] = wc + wn0; o.wrap_out[1] = wc + wn1; o.wrap_out[2] = wc + wn2;
     o.last_out = last;
     ws.agg2[c] = o;
 }
@@ -789,9 +808,10 @@ es_fold_kernel(EsWs ws, QsBatch b, const double *__restrict__ recv_time, double 
         last = a.last_out;
     }
     if (lane != 0) return;
-    const double *fin = ws.fin + (size_t)bot * 20;
+    const double *fin = ws.fin + (size_t)bot * ES_FIN;
     double *f = ekf + (size_t)bot * 44;
-    f[0] = p[0]; f[1] = p[1]; f[2] = fin[0] - ES_TWO_PI * (double)nw; f[3] = fin[1]; f[4] = fin[2]; f[5] = fin[3];
+    f[0] = p[0]; f[1] = p[1]; f[2] = __builtin_fma((double)((int)fin[20] - nw), ES_TWO_PI, fin[0]);
+    f[3] = fin[1]; f[4] = fin[2]; f[5] = fin[3];
     #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
         f[6 + 6 * rr] = D[2 * rr]; f[6 + 6 * rr + 1] = D[2 * rr + 1];
@@ -840,7 +860,7 @@ static size_t es_layout(const qs_ctx *c, void *ws, size_t cap, EsWs &w, size_t &
     w.agg1 = k.take<EsAgg1>(ch);
     w.start = k.take<EsStart>(ch);
     w.agg2 = k.take<EsAgg2>(ch);
-    w.fin = k.take<double>(256 * 20);
+    w.fin = k.take<double>(256 * ES_FIN);
     return k.bytes;
 }
 

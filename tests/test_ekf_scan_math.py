@@ -59,6 +59,13 @@ def apply(e, m, P):
     return A2 @ X @ (m + P @ h2) + b2, A2 @ X @ P @ A2.T + C2
 
 
+def take_turns(s):
+    """es_take_turns: s[0] -> s[0] - 2 pi k, k = rint(s[0] / 2 pi); the product is not rounded (the kernel's fma)."""
+    k = int(np.rint(s[0] * (1.0 / (2 * PI))))
+    s[0] = float(np.longdouble(s[0]) - np.longdouble(k) * np.longdouble(2 * PI))
+    return k
+
+
 def wiring(t, yaw, enc, mpt):
     """(dt, omega_m, v_enc, predict?) of every step record; the first record initialises the filter."""
     steps, last_t = [], t[0]
@@ -87,20 +94,21 @@ def scan_filter(t, px, py, yaw, enc, mpt, chunk):
         for dt, om, ve, pred in ch:
             e = extend(e, dt, om, np.array([ve, om]), pred)
         aggs.append(e)
-    # E2
-    s, A = np.array([yaw[0], 0, 0, 0.0]), np.eye(4)
+    # E2: the heading is carried as (theta_r, whole turns), the turns taken out at every chunk start
+    s, A, turns = np.array([yaw[0], 0, 0, 0.0]), np.eye(4), 0
     starts = []
     for e in aggs:
-        starts.append((s.copy(), A.copy()))
+        turns += take_turns(s)
+        starts.append((s.copy(), A.copy(), turns))
         s, A = apply(e, s, A)
+    turns += take_turns(s)
     s_fin, A_fin = s, A
     # E3
     agg2 = []
-    for ch, (s, A) in zip(chunks, starts):
+    for ch, (s, A, wc) in zip(chunks, starts):
         L = np.eye(4); N = np.zeros((2, 4)); m = np.zeros(4); q = np.zeros(2)
         Wc = np.zeros((4, 4)); Uc = np.zeros((4, 2)); Vc = np.zeros((2, 2))
-        wc = int(np.rint(s[0] / (2 * PI)))
-        wn = [wc - 1, wc, wc + 1]
+        wn = [-1, 0, 1]                                       # relative to wc, as s[0] is
         for dt, om, ve, pred in ch:
             z = np.array([ve, om]); th, v = s[0], s[1]
             if pred:
@@ -123,7 +131,7 @@ def scan_filter(t, px, py, yaw, enc, mpt, chunk):
             Wc = Wc + L @ W @ L.T
             N = (N + GA) @ M; L = L @ M
             Ks = Ap @ E @ Si; s = sp + Ks @ y; A = Ap - Ks @ E.T @ Ap
-        agg2.append((L, N, m, q, Wc, Uc, Vc, wc, wn))
+        agg2.append((L, N, m, q, Wc, Uc, Vc, wc, [wc + w for w in wn]))
     # E4
     p = np.array([px[0], py[0]]); B = np.zeros((2, 4)); D = np.eye(2); nw = 0
     for L, N, m, q, Wc, Uc, Vc, wc, wn in agg2:
@@ -132,7 +140,7 @@ def scan_filter(t, px, py, yaw, enc, mpt, chunk):
         B = B @ L + N
         assert 0 <= nw - wc + 1 <= 2
         nw = wn[nw - wc + 1]
-    x = np.concatenate([p, [s_fin[0] - 2 * PI * nw], s_fin[1:]])
+    x = np.concatenate([p, [s_fin[0] + 2 * PI * (turns - nw)], s_fin[1:]])
     return x, np.block([[D, B], [B.T, A_fin]]), nw
 
 

@@ -10,7 +10,10 @@
 //                      inlier_rmse = sqrt(sum d^2 / #corr);
 //   update           : Umeyama without scaling on the correspondences; for planar clouds (z = 0,
 //                      as grid_to_pcd produces) that is the closed-form 2-D Kabsch rotation
-//                      theta = atan2(sum(ax*by - ay*bx), sum(ax*bx + ay*by)) on demeaned pairs;
+//                      theta = atan2(sum(ax*by - ay*bx), sum(ax*bx + ay*by)) on demeaned pairs a', b';
+//                      theta = 0 when the covariance is degenerate: sum |a'|^2 <= 2^-80 n |mean a|^2 or
+//                      sum |b'|^2 <= 2^-80 n |mean b|^2 (Umeyama on a zero covariance: U = V = I);
+//                      translation = mean b - R mean a either way;
 //   loop             : at most max_iteration updates; stop when |d fitness| < 1e-6 and |d rmse| < 1e-6.
 // Nearest neighbours are exact brute force in fp64 (targets staged through LDS tiles; ties -> lowest
 // target index); sums are two-level and fixed-order, so results are reproducible run to run.
@@ -274,7 +277,7 @@ qs_icp_fill_inf_kernel(double *__restrict__ v, size_t n)
 
 // ---- fixed-order two-level sums ---------------------------------------------------------------------
 // pass 0: per block {n, sum d2, sum ax, sum ay, sum bx, sum by}; pass 1 (means known):
-// {sum (ax-am)(bx-bm) + (ay..)(by..), sum (ax-am)(by-bm) - (ay-am)(bx-bm)}
+// {sum (ax-am)(bx-bm) + (ay..)(by..), sum (ax-am)(by-bm) - (ay-am)(bx-bm), sum |a - am|^2, sum |b - bm|^2}
 #define ICP_NSUM 6
 __global__ void __launch_bounds__(ICP_BLOCK)
 qs_icp_sums_kernel(const double2 *__restrict__ src, size_t n_src, const double2 *__restrict__ dst,
@@ -291,6 +294,8 @@ qs_icp_sums_kernel(const double2 *__restrict__ src, size_t n_src, const double2 
             const double ax = a.x - amx, ay = a.y - amy, bx = b.x - bmx, by = b.y - bmy;
             v[0] = ax * bx + ay * by;
             v[1] = ax * by - ay * bx;
+            v[2] = ax * ax + ay * ay;                                         // the two spreads: the degenerate rule (qs_icp_device)
+            v[3] = bx * bx + by * by;
         }
     }
     #pragma unroll
@@ -553,7 +558,14 @@ int qs_icp_device(qs_ctx *c, double2 *d_src, size_t n_src, const double2 *d_dst,
             HIPCHK(c, qs_launch_icp_sums(c, d_src, n_src, d_dst, d_corr.p, d_d2.p, 1, means, d_part.p, d_out.p));
             HIPCHK(c, hipMemcpyAsync(o2, d_out.p, sizeof o2, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            const double theta = atan2(o2[1], o2[0]);
+            // Degenerate covariance: every matched source, or every matched target, is one point up to the rounding of the
+            // mean (a global map of one cell; local cells that all snap to one cell).  Both sums are then rounding noise and
+            // their atan2 an arbitrary angle; Umeyama on a zero covariance gives U = V = I: no rotation.  A spread of exactly
+            // 0 always qualifies (one correspondence).
+            const double tiny = 0x1p-80 * nn;
+            const bool degenerate = o2[2] <= tiny * (means[0] * means[0] + means[1] * means[1]) ||
+                                    o2[3] <= tiny * (means[2] * means[2] + means[3] * means[3]);
+            const double theta = degenerate ? 0.0 : atan2(o2[1], o2[0]);
             uc = cos(theta); us = sin(theta);
             ux = means[2] - (uc * means[0] - us * means[1]);
             uy = means[3] - (us * means[0] + uc * means[1]);

@@ -388,7 +388,14 @@ int qs_rasterise(qs_ctx *ctx, const double *xy, size_t n, double res, int32_t di
  * registration_icp(source, target, max_dist, identity, PointToPoint, max_iteration) on planar
  * clouds (Open3D semantics; parity unpinned: Open3D is not available).  T = 3x3 row-major planar
  * rigid transform source -> target; fitness = #correspondences / n_src; rmse over correspondences;
- * stops early when |d fitness| < rel_fitness and |d rmse| < rel_rmse (Open3D defaults: 1e-6). */
+ * stops early when |d fitness| < rel_fitness and |d rmse| < rel_rmse (Open3D defaults: 1e-6).
+ * Every update is the planar Kabsch step on the demeaned correspondences a' (sources), b' (targets):
+ * theta = atan2(sum a' x b', sum a' . b'), translation = mean b - R mean a.  Degenerate rule: when
+ * sum |a'|^2 <= 2^-80 n |mean a|^2 or sum |b'|^2 <= 2^-80 n |mean b|^2 (n correspondences; a sum of exactly 0 always
+ * qualifies) all matched sources, or all matched targets, are one point up to the rounding of their mean, both sums are
+ * rounding noise, and the update's rotation is the identity, theta = 0 (Umeyama on a zero covariance: U = V = I); the
+ * translation stays mean b - mean a.  Genuine clouds sit far above the threshold (a room 1.0e4 m from the origin: 3.5e-8;
+ * 2^-80 = 8.3e-25; degenerate ones: <= 6e-30).  With max_iter = 0: T = identity, fitness and rmse of the inputs. */
 int qs_icp(qs_ctx *ctx, const double *src_xy, size_t n_src, const double *dst_xy, size_t n_dst,
            double max_dist, int32_t max_iter, double rel_fitness, double rel_rmse, double T[9],
            double *fitness, double *rmse, int32_t *iters);

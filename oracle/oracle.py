@@ -359,6 +359,11 @@ def icp_planar(src, dst, max_dist=1.0, max_iter=30, rel_fitness=1e-6, rel_rmse=1
             am, bm = a.mean(0), b.mean(0)
             ac, bc = a - am, b - bm
             theta = np.arctan2((ac[:, 0] * bc[:, 1] - ac[:, 1] * bc[:, 0]).sum(), (ac[:, 0] * bc[:, 0] + ac[:, 1] * bc[:, 1]).sum())
+            # degenerate covariance (all matched sources, or all matched targets, one point up to the rounding of their
+            # mean): both sums above are rounding noise; Umeyama on a zero covariance gives U = V = I (quasar_slam.h, qs_icp)
+            tiny = 2.0 ** -80 * len(a)
+            if (ac * ac).sum() <= tiny * (am * am).sum() or (bc * bc).sum() <= tiny * (bm * bm).sum():
+                theta = 0.0
             c, s = np.cos(theta), np.sin(theta)
             R = np.array([[c, -s], [s, c]])
             U[:2, :2] = R; U[:2, 2] = bm - R @ am

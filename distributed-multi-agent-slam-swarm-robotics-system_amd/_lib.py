@@ -194,6 +194,9 @@ SIGNATURES = {
     "qs_plan_paths": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_frontier_targets_by_path": (_i32, [_vp, _i32, _f64, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                            C.POINTER(_sz), _vp]),
+    "qs_territories": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qs_frontier_targets_by_territory": (_i32, [_vp, _i32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                C.POINTER(_sz), _vp]),
     "qs_render_view": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "qs_render_view_device": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "qs_ekf_init": (_i32, [_vp, _i32, _f64, _vp]),

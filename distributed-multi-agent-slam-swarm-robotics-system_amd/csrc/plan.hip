@@ -157,22 +157,29 @@ qs_plan_seed_kernel(const long long *__restrict__ start, const long long *__rest
     }
 }
 
+// The key a field holds: the uint32 cost (path planning), or the 64-bit (cost << 32) | bot of a multi-seeded field
+// (territory.hip), whose minimum orders by cost first, then by bot.  A step adds w << shift.
+template <typename K> struct PlKey;
+template <> struct PlKey<unsigned int> { static constexpr unsigned int inf = PL_INF; static constexpr int shift = 0; };
+template <> struct PlKey<unsigned long long> { static constexpr unsigned long long inf = ~0ull; static constexpr int shift = 32; };
+
 // min-plus scan with step weight w along the 64 lanes of a line, in lane order: v[x] = min over k <= x of the same
 // segment of v[k] + w (x - k); a segment starts at a lane whose move from the lane before is not allowed (!e)
-__device__ inline unsigned int pl_scan(unsigned int v, bool e, unsigned int w, int lane)
+template <typename K> __device__ inline K pl_scan(K v, bool e, unsigned int w, int lane)
 {
-    const unsigned int off = w * (unsigned int)(QS_WAVE - 1 - lane);
-    unsigned int g = v == PL_INF ? PL_INF : v + off;
+    const K inf = PlKey<K>::inf;
+    const K off = (K)(w * (unsigned int)(QS_WAVE - 1 - lane)) << PlKey<K>::shift;
+    K g = v == inf ? inf : v + off;
     bool start = !e;
     for (int d = 1; d < QS_WAVE; d <<= 1) {
-        const unsigned int gl = __shfl_up(g, d);
+        const K gl = __shfl_up(g, d);
         const bool sl = __shfl_up((int)start, d) != 0;
         if (lane >= d) {
             if (!start) g = gl < g ? gl : g;
             start = start || sl;
         }
     }
-    const unsigned int c = g == PL_INF ? PL_INF : g - off;
+    const K c = g == inf ? inf : g - off;
     return c < v ? c : v;
 }
 
@@ -180,17 +187,18 @@ __device__ inline int pl_li(int x, int y) { return (y + 1) * PL_H + x + 1; }   /
 
 // One round: list `in` of round r (count cnt[r % 3]); appends to the other list (count cnt[(r + 1) % 3], cleared by round
 // r - 1) and clears cnt[(r + 2) % 3] for round r + 1 to append to.  Invariant at the start of round r: cnt[(r + 1) % 3]
-// == 0.  Grid-stride over the items; every block reads the count itself.
-__global__ void __launch_bounds__(PL_BLOCK)
-qs_plan_round_kernel(unsigned int *__restrict__ fields, size_t fcells, PlBox B, const unsigned int *__restrict__ mask, int mp,
+// == 0.  Grid-stride over the items; every block reads the count itself.  K: the key of the fields (PlKey).
+template <typename K> __global__ void __launch_bounds__(PL_BLOCK)
+qs_plan_round_kernel(K *__restrict__ fields, size_t fcells, PlBox B, const unsigned int *__restrict__ mask, int mp,
                      int size, const unsigned int *__restrict__ tile_any, int gtx, const unsigned int *__restrict__ list_in,
                      unsigned int *__restrict__ list_out, unsigned int *__restrict__ cnt, unsigned int *__restrict__ marks,
                      unsigned int r, unsigned long long *__restrict__ stats)
 {
-    __shared__ unsigned int s_f[PL_H * PL_H];
+    __shared__ K s_f[PL_H * PL_H];
     __shared__ unsigned char s_t[PL_H * PL_H];
     __shared__ int s_chg;
     __shared__ unsigned int s_side;
+    const K inf = PlKey<K>::inf;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned int n = cnt[r % 3];
     // cnt[(r + 2) % 3] holds round r - 1's count: cleared by every round, an empty one included, or round r + 2 would
@@ -204,11 +212,11 @@ qs_plan_round_kernel(unsigned int *__restrict__ fields, size_t fcells, PlBox B, 
         const unsigned int item = list_in[it];
         const unsigned int f = item / tiles, t = item % tiles;
         const int tx = (int)(t % B.ntx), ty = (int)(t / B.ntx);
-        unsigned int *fld = fields + (size_t)f * fcells;
+        K *fld = fields + (size_t)f * fcells;
         __syncthreads();                                   // the previous item's LDS is no longer read
         for (int i = tid; i < PL_H * PL_H; i += PL_BLOCK) {
             const int fx = tx * PL_T + i % PL_H - 1, fy = ty * PL_T + i / PL_H - 1;
-            unsigned int v = PL_INF;
+            K v = inf;
             unsigned char tr = 0;
             if (fx >= 0 && fy >= 0 && fx < B.fw && fy < B.fh) {
                 v = fld[(size_t)fy * B.fw + fx];
@@ -220,7 +228,7 @@ qs_plan_round_kernel(unsigned int *__restrict__ fields, size_t fcells, PlBox B, 
         __syncthreads();
         // border cells: the old value (to see what improved), then one relaxation from the halo (constant this visit)
         int bx = 0, by = 0;
-        unsigned int old = PL_INF;
+        K old = inf;
         if (tid < 4 * PL_T - 4) {
             if (tid < PL_T) { bx = tid; by = 0; }
             else if (tid < 2 * PL_T) { bx = tid - PL_T; by = PL_T - 1; }
@@ -229,14 +237,14 @@ qs_plan_round_kernel(unsigned int *__restrict__ fields, size_t fcells, PlBox B, 
             const int c = pl_li(bx, by);
             old = s_f[c];
             if (s_t[c]) {
-                unsigned int v = old;
+                K v = old;
                 for (int dy = -1; dy <= 1; dy++)
                     for (int dx = -1; dx <= 1; dx++) {
                         if (!dx && !dy) continue;
                         const int nb = pl_li(bx + dx, by + dy);
-                        if (!s_t[nb] || s_f[nb] == PL_INF) continue;
+                        if (!s_t[nb] || s_f[nb] == inf) continue;
                         if (dx && dy && !(s_t[pl_li(bx + dx, by)] && s_t[pl_li(bx, by + dy)])) continue;
-                        const unsigned int cand = s_f[nb] + (dx && dy ? QS_PLAN_DIAG : QS_PLAN_ORTHO);
+                        const K cand = s_f[nb] + ((K)(dx && dy ? QS_PLAN_DIAG : QS_PLAN_ORTHO) << PlKey<K>::shift);
                         v = cand < v ? cand : v;
                     }
                 s_f[c] = v;
@@ -258,11 +266,11 @@ qs_plan_round_kernel(unsigned int *__restrict__ fields, size_t fcells, PlBox B, 
                     const int c = pl_li(x, y);
                     bool e = lane > 0 && px >= 0 && py >= 0 && py < PL_T && s_t[c] && s_t[pl_li(px, py)];
                     if (fam >= 2) e = e && s_t[pl_li(px, y)] && s_t[pl_li(x, py)];
-                    const unsigned int v0 = s_f[c];
-                    unsigned int v = pl_scan(v0, e, w, lane);
+                    const K v0 = s_f[c];
+                    K v = pl_scan<K>(v0, e, w, lane);
                     // the other way: lane j takes cell 63 - j; its move from the lane before is the move into cell 64 - j
                     const bool eb = __shfl((int)e, (QS_WAVE - lane) & 63) != 0 && lane > 0;
-                    const unsigned int vb = pl_scan(__shfl(v, QS_WAVE - 1 - lane), eb, w, lane);
+                    const K vb = pl_scan<K>(__shfl(v, QS_WAVE - 1 - lane), eb, w, lane);
                     v = __shfl(vb, QS_WAVE - 1 - lane);
                     if (v != v0) { s_f[c] = v; s_chg = 1; }
                 }
@@ -471,12 +479,14 @@ static hipError_t qs_launch_plan_seed(qs_ctx *c, const QsPlanLayout &L, const un
     return hipGetLastError();
 }
 
-static hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t gn, unsigned int r)
+// fields: the gn fields of a group (L.fields), or the one field of 64-bit keys a caller holds
+template <typename K>
+static hipError_t qs_launch_plan_round(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], K *fields, size_t gn, unsigned int r)
 {
     const PlBox B = pl_box(bbox);
     size_t items = gn * B.ntx * B.nty;
     const unsigned int blocks = (unsigned int)(items < QS_PLAN_ROUND_BLOCKS ? items : QS_PLAN_ROUND_BLOCKS);
-    hipLaunchKernelGGL(qs_plan_round_kernel, dim3(blocks), dim3(PL_BLOCK), 0, c->stream, L.fields, (size_t)B.fw * B.fh, B,
+    hipLaunchKernelGGL(qs_plan_round_kernel<K>, dim3(blocks), dim3(PL_BLOCK), 0, c->stream, fields, (size_t)B.fw * B.fh, B,
                        L.mask, L.mp, c->cfg.size, L.tile_any, L.gtx, (r & 1) ? L.list1 : L.list0, (r & 1) ? L.list0 : L.list1,
                        L.cnt, L.marks, r, L.stats);
     return hipGetLastError();
@@ -520,15 +530,14 @@ int plan_begin(qs_ctx *c, int clearance, size_t n, size_t path_cap, QsPlanLayout
     return QS_OK;
 }
 
-// the fields of requests g0 .. g0 + gn: seed, then rounds in batches of QS_PLAN_ROUND_BATCH without a sync (a round that
-// finds its list empty returns at once), the live count read once per batch
+// the rounds of seeded fields (list 1 holds round 1's items, marks 1): batches of QS_PLAN_ROUND_BATCH without a sync (a
+// round that finds its list empty returns at once), the live count read once per batch
 #define QS_PLAN_ROUND_BATCH 8
-int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start, const long long *goal,
-                size_t g0, size_t gn)
+template <typename K>
+static int plan_rounds_of(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], K *fields, size_t gn)
 {
-    HIPCHK(c, qs_launch_plan_seed(c, L, bbox, start, goal, g0, gn));
     for (unsigned int r = 1;; r += QS_PLAN_ROUND_BATCH) {
-        for (unsigned int k = 0; k < QS_PLAN_ROUND_BATCH; k++) HIPCHK(c, qs_launch_plan_round(c, L, bbox, gn, r + k));
+        for (unsigned int k = 0; k < QS_PLAN_ROUND_BATCH; k++) HIPCHK(c, qs_launch_plan_round(c, L, bbox, fields, gn, r + k));
         unsigned int live = 0;
         HIPCHK(c, hipMemcpyAsync(&live, L.cnt + (r + QS_PLAN_ROUND_BATCH) % 3, sizeof live, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -536,6 +545,19 @@ int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], co
         if (r > 0x7fffffffu) return qs_fail(c, QS_E_STATE, "path planning: the relaxation did not settle");
     }
     return QS_OK;
+}
+
+int plan_rounds_key64(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], unsigned long long *key)
+{
+    return plan_rounds_of(c, L, bbox, key, 1);
+}
+
+// the fields of requests g0 .. g0 + gn: seed, then the rounds
+int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start, const long long *goal,
+                size_t g0, size_t gn)
+{
+    HIPCHK(c, qs_launch_plan_seed(c, L, bbox, start, goal, g0, gn));
+    return plan_rounds_of(c, L, bbox, L.fields, gn);
 }
 
 // ... then the walk

@@ -1,5 +1,6 @@
-// plan_common.h -- what plan.hip (path planning) shares with targets_by_path.hip (§4.12): the tile
-// geometry, the planner's workspace and the launchers of its kernels.  The kernels themselves stay in plan.hip.
+// plan_common.h -- what plan.hip (path planning) shares with targets_by_path.hip (§4.12) and
+// territory.hip (§4.16): the tile geometry, the planner's workspace and the launchers of its kernels.  The kernels
+// themselves stay in plan.hip.
 #pragma once
 #include "qs_internal.h"
 
@@ -53,6 +54,9 @@ hipError_t qs_launch_plan_snap(qs_ctx *c, const QsPlanLayout &L, const double2 *
 // gn fields seeded at goal[g0 .. g0 + gn) (where start and goal both have a cell), then relaxed to the fixpoint
 int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start, const long long *goal,
                 size_t g0, size_t gn);
+// the rounds of ONE field of 64-bit keys (cost << 32) | seed over the census box (territory.hip): the caller has seeded it
+// and entered the seeds' tiles (item = tile index) in L.list1 / L.cnt[1] with L.marks = 1, as qs_plan_seed_kernel does
+int plan_rounds_key64(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], unsigned long long *key);
 // the walks of requests g0 .. g0 + gn over the group's fields: L.out4, L.plen, L.path
 hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
                                const long long *goal, size_t g0, size_t gn, int lookahead, size_t path_cap);

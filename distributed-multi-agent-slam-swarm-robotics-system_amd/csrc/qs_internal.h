@@ -266,6 +266,7 @@ struct qs_ctx {
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
     DevBuf<char> plan_ws;                        // path planning (plan.hip: qs_plan_layout)
     DevBuf<char> tbp_ws;                         // targets by path cost (targets_by_path.hip: qs_tbp_layout)
+    DevBuf<char> terr_ws;                        // territories (territory.hip: qs_terr_layout)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> view_ws;                        // map view (view.hip: qs_view_layout): state / owner frames, index tables, uploaded lists
     DevBuf<char> ekf_ws;                         // parallel-in-time EKF (ekf_scan.hip)
@@ -450,6 +451,10 @@ hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
 // frontier_targets.hip: the centroids of the clusters of a labelled frontier workspace with >= min_cluster cells, in first-cell
 // order.  phase 0 counts them (QsFrLayout::total); phase 1 writes them all to d_cent, which holds that many
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
+// targets_by_path.hip: cell[0 .. n_cent) of the centroids -> their offsets in a field over the census box bbox (0xffffffff =
+// no cell); count[0] += centroids with a cell, count[1] += cells among cell[n_cent .. n_cent + n_bots), the bots'
+hipError_t qs_launch_tbp_offsets(qs_ctx *c, const long long *cell, size_t n_cent, size_t n_bots, const unsigned int bbox[4],
+                                 unsigned int *coff, unsigned long long *count);
 // icp.hip
 hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel, unsigned long long *keys);
 int qs_icp_device(qs_ctx *c, double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst, const double box[4], double max_dist,

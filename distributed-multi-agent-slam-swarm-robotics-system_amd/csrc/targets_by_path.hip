@@ -103,6 +103,16 @@ qs_tbp_offsets_kernel(const long long *__restrict__ cell, int n_cent, int n_bots
     }
 }
 
+hipError_t qs_launch_tbp_offsets(qs_ctx *c, const long long *cell, size_t n_cent, size_t n_bots, const unsigned int bbox[4],
+                                 unsigned int *coff, unsigned long long *count)
+{
+    const size_t n_end = n_cent + n_bots;
+    if (!n_end) return hipSuccess;
+    hipLaunchKernelGGL(qs_tbp_offsets_kernel, dim3((unsigned int)((n_end + 255) / 256)), dim3(256), 0, c->stream, cell,
+                       (int)n_cent, (int)n_bots, c->cfg.size, pl_box(bbox), coff, count);
+    return hipGetLastError();
+}
+
 // ---- the entry of the lists: the 64-bit key (cost << 32) | centroid -----------------------------------------------------
 // Keys are distinct (the low word is the centroid); TP_NOKEY is the empty entry.
 struct TpEntry {
@@ -262,9 +272,7 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
         HIPCHK(c, hipMemsetAsync(T.count, 0, 2 * sizeof(unsigned long long), c->stream));
         HIPCHK(c, hipMemsetAsync(T.list_len, 0, n_bots * sizeof(int), c->stream));
         HIPCHK(c, qs_launch_plan_snap(c, L, T.xy, T.cell, n_end, p.snap_radius, L.stats + 3));
-        hipLaunchKernelGGL(qs_tbp_offsets_kernel, dim3((unsigned int)((n_end + 255) / 256)), dim3(256), 0, c->stream, T.cell,
-                           (int)n_cent, (int)n_bots, c->cfg.size, B, T.coff, T.count);
-        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, qs_launch_tbp_offsets(c, T.cell, n_cent, n_bots, bbox, T.coff, T.count));
         HIPCHK(c, hipMemcpyAsync(bcell.data(), T.cell + n_cent, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -331,9 +339,7 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
     } else if (any_trav && n_cent) {                     // no bots: the centroids' cells are still counted
         HIPCHK(c, hipMemsetAsync(T.count, 0, 2 * sizeof(unsigned long long), c->stream));
         HIPCHK(c, qs_launch_plan_snap(c, L, T.xy, T.cell, n_cent, p.snap_radius, L.stats + 3));
-        hipLaunchKernelGGL(qs_tbp_offsets_kernel, dim3((unsigned int)((n_cent + 255) / 256)), dim3(256), 0, c->stream, T.cell,
-                           (int)n_cent, 0, c->cfg.size, pl_box(bbox), T.coff, T.count);
-        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, qs_launch_tbp_offsets(c, T.cell, n_cent, 0, bbox, T.coff, T.count));
         HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
     }   // (no traversable cell: nothing snaps, every bot is QS_PLAN_NO_START, what the snap kernel would say)
     const size_t nc = n_cent < cap ? n_cent : cap;

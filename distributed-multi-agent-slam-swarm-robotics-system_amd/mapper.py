@@ -923,11 +923,30 @@ class QuasarMapper:
         return idx, xy, cents[:k.value], stats
 
     def assign_frontier_targets(self, bot_states, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
-                                by_path=False, return_waypoints=False, **plan_params):
+                                by_path=False, return_waypoints=False, by_territory=False, return_territory=False,
+                                **plan_params):
         """The reference's target_assignments (:958-992): {bot: (x, y)} of the online bots -> {bot: (tx, ty)} for
         the bots that got a target, bots taken in ascending id.  by_path=True (opt-in): the targets of
         frontier_targets_by_path instead (plan_params: clearance, snap_radius, lookahead), and with return_waypoints
-        also {bot: (wx, wy)}, the waypoint of each assigned bot's path, as a second dict."""
+        also {bot: (wx, wy)}, the waypoint of each assigned bot's path, as a second dict.  by_territory=True (opt-in,
+        excludes by_path): the targets of frontier_targets_by_territory likewise (`separation` plays no part), and with
+        return_territory also {bot: (area, box)} of every bot given, box a tuple of cells or None, as the last value."""
+        if by_path and by_territory:
+            raise ValueError("assign_frontier_targets: by_path and by_territory exclude each other")
+        if return_territory and not by_territory:
+            raise ValueError("assign_frontier_targets: return_territory needs by_territory=True")
+        if by_territory:
+            bots = sorted(bot_states)
+            res = self.frontier_targets_by_territory([bot_states[b] for b in bots], min_cluster, waypoints=return_waypoints,
+                                                     **plan_params) if bots else None
+            got = [(i, b) for i, b in enumerate(bots) if res["idx"][i] >= 0]
+            out = [{b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}]
+            if return_waypoints:
+                out.append({b: (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1])) for i, b in got})
+            if return_territory:
+                out.append({b: (int(res["area"][i]), tuple(int(v) for v in res["box"][i]) if res["area"][i] else None)
+                            for i, b in enumerate(bots)})
+            return out[0] if len(out) == 1 else tuple(out)
         if not by_path:
             if return_waypoints or plan_params:
                 raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True")
@@ -982,6 +1001,78 @@ class QuasarMapper:
                                    "fallbacks", "reserved"), (int(v) for v in st))))
         if return_centroids:
             out["centroids"] = cents[:k.value]
+        return out
+
+    # -- territories (include/quasar_slam.h, "territories"; no reference counterpart) ----------------------------
+    def territories(self, bot_xy, clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS, return_owner=False,
+                    return_cost=False):
+        """The traversable cells partitioned among the bots by path cost: each cell belongs to the bot with the smallest
+        (cost, bot).  Returns a dict of numpy arrays: status int32 [n] (QS_PLAN_OK / _NO_START), area int64 [n] (cells
+        owned), box int32 [n, 4] (min gx, min gy, max gx, max gy; -1 where area is 0), stats; with return_owner also owner
+        int16 [size, size] indexed [gy, gx] (-1 = nobody's), with return_cost also cost uint32 [size, size] (0xFFFFFFFF
+        there)."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(b)
+        if n > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"territories: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        prm = self._plan_params(clearance, snap_radius, P.PLAN_LOOKAHEAD)
+        status = np.zeros(n, dtype=np.int32)
+        area = np.zeros(n, dtype=np.int64)
+        box = np.full((n, 4), -1, dtype=np.int32)
+        st = np.zeros(8, dtype=np.uint64)
+        owner = np.empty((self.size, self.size), dtype=np.int16) if return_owner else None
+        cost = np.empty((self.size, self.size), dtype=np.uint32) if return_cost else None
+        self._chk(self._L.qs_territories(self._h, C.byref(prm), _ptr(b), n, _ptr(owner) if return_owner else None,
+                                         _ptr(cost) if return_cost else None, _ptr(status), _ptr(area), _ptr(box), _ptr(st)),
+                  "qs_territories")
+        out = dict(status=status, area=area, box=box, stats=self._territory_stats(st))
+        if return_owner:
+            out["owner"] = owner
+        if return_cost:
+            out["cost"] = cost
+        return out
+
+    @staticmethod
+    def _territory_stats(st):
+        return dict(zip(("rounds", "tile_visits", "bot_cells", "owned_cells", "n_centroids", "centroid_cells",
+                         "centroids_owned", "reserved"), (int(v) for v in st)))
+
+    def frontier_targets_by_territory(self, bot_xy, min_cluster=P.FRONTIER_MIN_CLUSTER, clearance=P.PLAN_CLEARANCE,
+                                      snap_radius=P.PLAN_SNAP_RADIUS, lookahead=P.PLAN_LOOKAHEAD, return_centroids=False,
+                                      waypoints=True):
+        """Frontier targets by territory (include/quasar_slam.h, "territories", T5): each bot takes the centroid with the
+        smallest (cost, index) among those whose cell it owns; there is no separation rule.  Returns the keys of
+        frontier_targets_by_path (idx, xy, cost, status, waypoint_cell, waypoint, stats) plus area int64 [n] and box int32
+        [n, 4]; with return_centroids also centroids float64 [k, 2] and centroid_owner int32 [k] (-1 = nobody's)."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(b)
+        if n > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"frontier_targets_by_territory: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        prm = self._plan_params(clearance, snap_radius, lookahead)
+        idx = np.full(n, -1, dtype=np.int64)
+        xy = np.full((n, 2), np.nan, dtype=np.float64)
+        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        wc = np.full((n, 2), -1, dtype=np.int32)
+        wxy = np.full((n, 2), np.nan, dtype=np.float64)
+        area = np.zeros(n, dtype=np.int64)
+        box = np.full((n, 4), -1, dtype=np.int32)
+        st = np.zeros(8, dtype=np.uint64)
+        k = C.c_size_t()
+        cents, cown, cap = None, None, 0
+        if return_centroids:       # the count first: a second call would observe the same map
+            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
+            cents, cown, cap = np.zeros((k.value, 2), dtype=np.float64), np.full(k.value, -1, dtype=np.int32), k.value
+        self._chk(self._L.qs_frontier_targets_by_territory(
+            self._h, min_cluster, C.byref(prm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost), _ptr(status),
+            _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(area), _ptr(box),
+            _ptr(cents) if cap else None, _ptr(cown) if cap else None, cap, C.byref(k), _ptr(st)),
+            "qs_frontier_targets_by_territory")
+        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy, area=area, box=box,
+                   stats=self._territory_stats(st))
+        if return_centroids:
+            out["centroids"] = cents[:k.value]
+            out["centroid_owner"] = cown[:k.value]
         return out
 
     # -- path planning (include/quasar_slam.h, "path planning"; no reference counterpart) ----------------------

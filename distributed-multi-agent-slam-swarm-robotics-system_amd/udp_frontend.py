@@ -19,6 +19,11 @@ Mirrors server_nodes/dual_bot_mapper.py:
                                of straight-line distance (QuasarMapper.assign_frontier_targets(by_path=True), ONE
                                device call per tick, plan_params its planning parameters): every assigned bot has a
                                path to its target, so with plan_paths=True every TARG carries a waypoint.
+                               With targets_by_territory=True (also opt-in, excludes targets_by_path) the mapped free
+                               space is partitioned among the online bots by path cost and each bot takes the cheapest
+                               centroid of its own share (QuasarMapper.assign_frontier_targets(by_territory=True), ONE
+                               device call per tick); with plan_paths=True every TARG carries a waypoint.  `territory`
+                               then holds {bot: (cells owned, world box or None)} of the last tick.
 Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry packets of the ESP32 firmware
 (esp32_firmware/src/main.cpp:190-215) are mapped too.  Datagrams then get slots of SWEEP_SLOT bytes; the datagrams of a
 poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
@@ -51,11 +56,16 @@ SWEEP_SLOT = 752   # with sweeps on: room for a 751-byte sweep and the oversize 
 class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
-                 match_params=None, targets_by_path=False, sweep_graph=False, track_view=False):
+                 match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
+                 targets_by_territory=False):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
         if targets_by_path and not frontier_targets:
             raise ValueError("MissionControl: targets_by_path=True needs frontier_targets=True")
+        if targets_by_territory and not frontier_targets:
+            raise ValueError("MissionControl: targets_by_territory=True needs frontier_targets=True")
+        if targets_by_territory and targets_by_path:
+            raise ValueError("MissionControl: targets_by_territory=True excludes targets_by_path=True")
         if match_sweeps and not sweeps:
             raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
         self.sweep_graph = sweep_graph is not False and sweep_graph is not None      # ({} is on, with the defaults)
@@ -72,6 +82,8 @@ class MissionControl:
         self.mapper = mapper
         self.plan_paths = plan_paths
         self.targets_by_path = targets_by_path
+        self.targets_by_territory = targets_by_territory
+        self.territory = {}
         self.plan_params = dict(plan_params or {})
         self.plan_stats = {"waypoint": 0, "centroid": 0}
         self.sweeps = sweeps
@@ -233,6 +245,8 @@ class MissionControl:
         sent = {}
         if self.targets_by_path:
             targets = self._targets_by_path(states)
+        elif self.targets_by_territory:
+            targets = self._targets_by_territory(states)
         else:
             targets = sorted(self.mapper.assign_frontier_targets(states).items())
             if self.plan_paths and targets:
@@ -269,6 +283,22 @@ class MissionControl:
         _, wps = self.mapper.assign_frontier_targets(states, by_path=True, return_waypoints=True, **self.plan_params)
         self.plan_stats["waypoint"] += len(wps)
         return sorted(wps.items())
+
+    def _targets_by_territory(self, states):
+        """One call that partitions the free space among the bots and gives each the cheapest centroid of its share: the
+        centroids of the assigned bots, or (plan_paths) their waypoints, counted in plan_stats as _targets_by_path counts
+        them.  Keeps territory = {bot: (cells owned, world box or None)}."""
+        res = self.mapper.assign_frontier_targets(states, by_territory=True, return_waypoints=self.plan_paths,
+                                                  return_territory=True, **self.plan_params)
+        m = self.mapper
+        self.territory = {
+            b: (area, None if box is None else (m.ox + box[0] * m.res, m.oy + box[1] * m.res,
+                                                m.ox + (box[2] + 1) * m.res, m.oy + (box[3] + 1) * m.res))
+            for b, (area, box) in res[-1].items()}
+        if not self.plan_paths:
+            return sorted(res[0].items())
+        self.plan_stats["waypoint"] += len(res[1])
+        return sorted(res[1].items())
 
     def step(self, now=None):
         """One iteration of the reference's while-loop body (without events and rendering)."""

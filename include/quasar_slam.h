@@ -600,6 +600,46 @@ int qs_frontier_targets_by_path(qs_ctx *ctx, int32_t min_cluster, double separat
                                 uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
                                 double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8]);
 
+/* ---- territories: the mapped free space partitioned among the bots by path cost (this build's own rules) ------------------
+ * qs_frontier_targets_by_path pays one shortest-path field per bot and assigns greedily in bot order.  Here every bot is
+ * a seed of ONE field and each cell keeps the smallest (cost, bot): who is nearest by path to every free cell and every
+ * frontier, how much each bot has left, and the box of its share.  All rules are integer, so the device and a CPU
+ * restatement agree bit for bit.
+ *  T1 Cells: the traversable mask is planning rule 1 with params.clearance; each bot position maps to a cell by planning
+ *     rule 2 (world_to_grid, then the snap within params.snap_radius).  A bot whose position does not snap has no cell,
+ *     gets status QS_PLAN_NO_START and owns nothing.  Several bots may have the same cell.
+ *  T2 Cost: cost(b, c) is the planning rule 3 cost between bot b's cell and cell c (moves of 5 and 7, no corner cutting,
+ *     uint32).
+ *  T3 Owner: for a traversable cell c reached by at least one bot, key(c) is the minimum over those bots of
+ *     (cost(b, c), b), compared as a pair; owner(c) is that b and cost(c) that cost: the lowest bot index wins a tie.
+ *     Every other cell has owner -1 and cost 0xFFFFFFFF.
+ *  T4 Per bot: area[b] is the number of cells owned (int64); box[b] is (min gx, min gy, max gx, max gy) over them, or
+ *     (-1, -1, -1, -1) when there are none.  A bot with a cell owns at least that cell unless a lower-indexed bot shares
+ *     it; such a bot has status QS_PLAN_OK, area 0 and the empty box.
+ *  T5 Frontier targets by territory: the centroids are the list, order and positions of qs_frontier_targets(min_cluster);
+ *     each snaps by rule 2; centroid_owner[k] is owner(cell_k), or -1 without a cell, and its cost likewise.  Bot b's
+ *     target is the centroid it owns with the smallest (cost, k).  A bot with a cell but no owned centroid gets
+ *     QS_PLAN_UNREACHABLE, index -1, NaN positions and cost 0xFFFFFFFF.  There is NO separation rule: territories are
+ *     disjoint, so no two bots share a centroid, but the targets of two neighbouring bots may be close.  The waypoint
+ *     pair is optional, as in qs_frontier_targets_by_path: an assigned bot gets exactly what
+ *     qs_plan_paths(params, bot_xy[b], target_xy[b]) returns on the same map, and its cost equals the target's cost in
+ *     the partition (the moves are symmetric).
+ *  T6 Every call observes the map (flushes waiting exact-trig rays first) and writes no session state: a checkpoint
+ *     before equals one after.  n_bots <= QS_FT_MAX_BOTS.  Argument checks are those of qs_plan_params (QS_E_INVAL).
+ *     n_bots == 0, a map without FREE cells and a map without clusters are valid.
+ * owner_host (int16) and cost_host (uint32) are optional [size][size] arrays indexed [gy][gx]; box is n_bots x 4.
+ * stats (optional): relaxation rounds, tile visits (both include the waypoint stage's), bots with a cell, owned cells in
+ * total, centroids, centroids with a cell, centroids with an owner, reserved (0); qs_territories leaves the centroid
+ * entries 0.  centroids_xy and centroid_owner (both optional, cap entries) and *n_centroids report the centroid list. */
+int qs_territories(qs_ctx *ctx, const qs_plan_params *params, const double *bot_xy, size_t n_bots,
+                   int16_t *owner_host, uint32_t *cost_host, int32_t *status, int64_t *area, int32_t *box,
+                   uint64_t stats[8]);
+int qs_frontier_targets_by_territory(qs_ctx *ctx, int32_t min_cluster, const qs_plan_params *params,
+                                     const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
+                                     uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy, int64_t *area,
+                                     int32_t *box, double *centroids_xy, int32_t *centroid_owner, size_t cap,
+                                     size_t *n_centroids, uint64_t stats[8]);
+
 /* ---- map view: the "Mission Control" map, MapRenderer  dual_bot_mapper.py:380-668 -------------------------------------------
  * One call renders a frame of the map for any pan and zoom on the device and hands back only the frame: [height][width][4]
  * bytes R, G, B, 255, row 0 at the top.  The layers are the reference's (:433-468) as far as its own Python pins their pixels

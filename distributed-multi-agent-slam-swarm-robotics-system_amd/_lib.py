@@ -26,6 +26,14 @@ class QsPlanParams(C.Structure):
     _fields_ = [("clearance", C.c_int32), ("snap_radius", C.c_int32), ("lookahead", C.c_int32), ("reserved", C.c_int32)]
 
 
+class QsGainParams(C.Structure):
+    """struct qs_gain_params (include/quasar_slam.h)."""
+    _fields_ = [("range", C.c_int32), ("bias", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
+QS_GAIN_MAX_RANGE, QS_GAIN_DEFAULT_RANGE, QS_GAIN_DEFAULT_BIAS = 64, 24, 120     # include/quasar_slam.h, "frontier gain"
+
+
 class QsMatchParams(C.Structure):
     """struct qs_match_params (include/quasar_slam.h)."""
     _fields_ = [("radius", C.c_int32), ("window", C.c_int32), ("angle_steps", C.c_int32), ("min_hits", C.c_int32),
@@ -194,6 +202,9 @@ SIGNATURES = {
     "qs_plan_paths": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_frontier_targets_by_path": (_i32, [_vp, _i32, _f64, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                            C.POINTER(_sz), _vp]),
+    "qs_frontier_gain": (_i32, [_vp, _i32, _i32, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "qs_frontier_targets_by_gain": (_i32, [_vp, _i32, _f64, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                           C.POINTER(_sz), _vp, _vp]),
     "qs_territories": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qs_frontier_targets_by_territory": (_i32, [_vp, _i32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                                 C.POINTER(_sz), _vp]),

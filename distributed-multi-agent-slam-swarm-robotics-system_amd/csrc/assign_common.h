@@ -1,5 +1,5 @@
-// assign_common.h -- what the two greedy target assignments share (frontier_targets.hip: DESIGN.md §4.7, by distance;
-// targets_by_path.hip: §4.12, by path cost): the wave-resident top-K list, the blocked test, the greedy walk over the bots
+// assign_common.h -- what the greedy target assignments share (frontier_targets.hip: DESIGN.md §4.7, by distance;
+// targets_by_path.hip: §4.12, by path cost, and §4.17, by gain over cost): the wave-resident top-K list, the blocked test, the greedy walk over the bots
 // and the host loop that resumes it after a fallback scan.
 //
 // Each file supplies an entry type E, the (key, centroid) its lists order by:
@@ -23,6 +23,17 @@ static_assert(AS_K <= QS_WAVE, "one list entry per lane");
 
 static inline size_t as_chunks(size_t n_cent) { return (n_cent + AS_CHUNK - 1) / AS_CHUNK; }
 static inline size_t as_fb_blocks(size_t n_cent) { return (n_cent + AS_FB_BLOCK - 1) / AS_FB_BLOCK; }
+
+// the clusters every target call keeps as centroids: the roots of the frontier workspace with cnt >= min_cluster.  One
+// predicate, so a compaction over it gives every call the same slots (frontier_targets.hip: centroids; gain.hip: viewpoints)
+struct FtKeep {
+    const unsigned int *cnt; int min_cluster;
+    __device__ bool marked(size_t i) const
+    {
+        const unsigned int n = cnt[i];                      // non-zero only at a cluster's root
+        return n != 0 && (long long)n >= (long long)min_cluster;
+    }
+};
 
 struct QsAssignState { int next_bot, m, stop, pad; };   // greedy pass: first bot not yet decided, targets so far, 1 = needs a full scan
 

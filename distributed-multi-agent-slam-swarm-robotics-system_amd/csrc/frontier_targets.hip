@@ -35,14 +35,6 @@ struct QsFtLayout {
 };
 
 // ---- centroids ------------------------------------------------------------------------------------------------
-struct FtKeep {
-    const unsigned int *cnt; int min_cluster;
-    __device__ bool marked(size_t i) const
-    {
-        const unsigned int n = cnt[i];                      // non-zero only at a cluster's root
-        return n != 0 && (long long)n >= (long long)min_cluster;
-    }
-};
 struct FtEmitCentroid {
     const unsigned int *cnt; const unsigned long long *sumx, *sumy; double res, ox, oy; double2 *out;
     __device__ void put(size_t slot, size_t i) const

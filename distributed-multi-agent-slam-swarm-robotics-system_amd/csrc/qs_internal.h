@@ -266,6 +266,7 @@ struct qs_ctx {
     DevBuf<char> ft_ws;                          // frontier target assignment (frontier_targets.hip)
     DevBuf<char> plan_ws;                        // path planning (plan.hip: qs_plan_layout)
     DevBuf<char> tbp_ws;                         // targets by path cost (targets_by_path.hip: qs_tbp_layout)
+    DevBuf<char> gain_ws;                        // frontier gain (gain.hip: qs_gain_layout)
     DevBuf<char> terr_ws;                        // territories (territory.hip: qs_terr_layout)
     DevBuf<char> io_ws;                          // staging of the object-API calls (qs_update_rays, views)
     DevBuf<char> view_ws;                        // map view (view.hip: qs_view_layout): state / owner frames, index tables, uploaded lists
@@ -455,6 +456,13 @@ hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, i
 // no cell); count[0] += centroids with a cell, count[1] += cells among cell[n_cent .. n_cent + n_bots), the bots'
 hipError_t qs_launch_tbp_offsets(qs_ctx *c, const long long *cell, size_t n_cent, size_t n_bots, const unsigned int bbox[4],
                                  unsigned int *coff, unsigned long long *count);
+// gain.hip: the workspace of the viewpoints and gains of n_cent clusters, carved from ws (nullptr: only the bytes the block
+// needs): the kept roots in slot order, the viewpoint keys (d2 << 32) | cell, then what the calls read: (gx, gy) and the gain
+struct QsGainLayout { unsigned int *root; unsigned long long *key; int2 *view; int *gain; size_t bytes; };
+QsGainLayout qs_gain_layout(void *ws, size_t n_cent);
+// into G.view / G.gain, for the n_cent clusters that qs_launch_ft_centroids(.., min_cluster, 0, ..) has just counted in fr_ws
+hipError_t qs_launch_gain(qs_ctx *c, void *fr_ws, int32_t min_cluster, int32_t range, size_t n_cent, const QsGainLayout &G);
+int gain_range(qs_ctx *c, int32_t range, const char *who);      // G5: QS_OK, or QS_E_INVAL with a message
 // icp.hip
 hipError_t qs_launch_voxel_keys(qs_ctx *c, const double2 *pts, size_t n, double minx, double miny, double voxel, unsigned long long *keys);
 int qs_icp_device(qs_ctx *c, double2 *d_src, size_t n_src, const double2 *d_dst, size_t n_dst, const double box[4], double max_dist,

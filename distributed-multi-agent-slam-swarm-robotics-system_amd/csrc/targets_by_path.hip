@@ -20,6 +20,8 @@
 // No device-side waits, no grid-wide barriers, no graphs.
 // The sorted list, the blocked test, the greedy walk and the host's stop / resume loop are assign_common.h's, shared with
 // frontier_targets.hip; here are the entry they order by, the gather that produces the chunk lists and the fallback's key.
+// The stages are written over that entry, so qs_frontier_targets_by_gain (§4.17) is the same call with another order: its
+// entry carries (cost + bias, gain, centroid), and the gains come from gain.hip before the mask is built.
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
@@ -31,6 +33,7 @@
 #define TP_NOCELL 0xffffffffu
 
 // the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
+template <typename E>
 struct QsTbpLayout {
     QsAssignState *st;
     unsigned long long *count;            // [2] centroids, bots with a cell
@@ -39,8 +42,8 @@ struct QsTbpLayout {
     unsigned int *coff;                   // [n_cent] offset of the centroid's cell in a field, TP_NOCELL = none
     long long *fcell;                     // [n_bots] the cells of the bots that have one, in bot order ...
     int *fbot;                            // [n_bots] ... and their bots
-    unsigned long long *part;             // [n_bots][n_chunks][K] chunk lists
-    unsigned long long *list;             // [n_bots][K] the top-K of a bot (by bot)
+    typename E::Item *part;               // [n_bots][n_chunks][K] chunk lists
+    typename E::Item *list;               // [n_bots][K] the top-K of a bot (by bot)
     int *list_len;                        // [n_bots]
     double2 *asg_xy; int *asg_idx;        // [n_bots] the targets so far: centroid position, index
     long long *tgt_idx;                   // [n_bots] per bot: the centroid or -1
@@ -48,13 +51,14 @@ struct QsTbpLayout {
     int *tgt_status;                      // [n_bots]
     long long *pair;                      // [2 n_bots] start cells of the assigned bots (in assignment order), then their goals
     int *pair_bot;                        // [n_bots] the bot of each pair
-    unsigned long long *fb_key;           // [n_fb] per-block minima of a fallback scan
+    typename E::Item *fb_key;             // [n_fb] per-block minima of a fallback scan
     size_t bytes;
 };
 
-static QsTbpLayout qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
+template <typename E>
+static QsTbpLayout<E> qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
 {
-    QsTbpLayout L;
+    QsTbpLayout<E> L;
     Carve k(ws);
     L.st = k.take<QsAssignState>(1);
     L.count = k.take<unsigned long long>(2);
@@ -63,8 +67,8 @@ static QsTbpLayout qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
     L.coff = k.take<unsigned int>(n_cent);
     L.fcell = k.take<long long>(n_bots);
     L.fbot = k.take<int>(n_bots);
-    L.part = k.take<unsigned long long>(n_bots * as_chunks(n_cent) * AS_K);
-    L.list = k.take<unsigned long long>(n_bots * AS_K);
+    L.part = k.take<typename E::Item>(n_bots * as_chunks(n_cent) * AS_K);
+    L.list = k.take<typename E::Item>(n_bots * AS_K);
     L.list_len = k.take<int>(n_bots);
     L.asg_xy = k.take<double2>(n_bots);
     L.asg_idx = k.take<int>(n_bots);
@@ -73,7 +77,7 @@ static QsTbpLayout qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
     L.tgt_status = k.take<int>(n_bots);
     L.pair = k.take<long long>(2 * n_bots);
     L.pair_bot = k.take<int>(n_bots);
-    L.fb_key = k.take<unsigned long long>(as_fb_blocks(n_cent));
+    L.fb_key = k.take<typename E::Item>(as_fb_blocks(n_cent));
     L.bytes = k.bytes;
     return L;
 }
@@ -113,13 +117,21 @@ hipError_t qs_launch_tbp_offsets(qs_ctx *c, const long long *cell, size_t n_cent
     return hipGetLastError();
 }
 
-// ---- the entry of the lists: the 64-bit key (cost << 32) | centroid -----------------------------------------------------
-// Keys are distinct (the low word is the centroid); TP_NOKEY is the empty entry.
+// ---- the entries of the lists -------------------------------------------------------------------------------------------
+// The stages below are written once over the entry E a rule orders by; beyond assign_common.h's interface an entry has
+//   typedef Aux                          what the rule needs beside a field, passed by value to the kernels
+//   static E make(cost, j, Aux)          the entry of centroid j at a finite cost
+//   static unsigned int cost(Item, Aux)  the cost an item of a list stands for
+// and its Part is a plain array of Items.
+//
+// §4.12: the 64-bit key (cost << 32) | centroid.  Keys are distinct (the low word is the centroid); TP_NOKEY is the empty entry.
+struct TpNoAux {};
 struct TpEntry {
     unsigned long long key;
     typedef unsigned long long *Part;
     typedef const unsigned long long *CPart;
     typedef unsigned long long Item;
+    typedef TpNoAux Aux;
     __device__ static TpEntry none() { return {TP_NOKEY}; }
     __device__ bool valid() const { return key != TP_NOKEY; }
     __device__ bool before(TpEntry o) const { return key < o.key; }
@@ -128,41 +140,75 @@ struct TpEntry {
     __device__ void store(const Part p, size_t o) const { p[o] = key; }
     __device__ Item item() const { return key; }
     __device__ static int centroid(Item it) { return (int)(it & 0xffffffffull); }
+    __device__ static TpEntry make(unsigned int cost, int j, Aux) { return {((unsigned long long)cost << 32) | (unsigned int)j}; }
+    __device__ static unsigned int cost(Item it, Aux) { return (unsigned int)(it >> 32); }
 };
 
-// the key of centroid j in the field fld: its cost there, or none
-__device__ inline TpEntry tp_key(const unsigned int *__restrict__ fld, const unsigned int *__restrict__ coff, int j)
+// §4.17 (G6): (cost + bias, gain, centroid); a comes before b when (cost_a + bias) * gain_b < (cost_b + bias) * gain_a, ties
+// to the smaller cost, then the lower centroid: a strict total order.  cost + bias < 2^33 and gain < 2^15 (the cells of a
+// disc of QS_GAIN_MAX_RANGE), so the products are exact in 64 bits.  The empty entry has gain 0 and so comes after every
+// entry with a gain: 0 < cb * gain on one side, cb * gain < 0 never on the other.  Written without short-circuits, as ft_before.
+struct GnItem { unsigned long long cb; unsigned int gain; int k; };
+struct GnAux { const int *gain; unsigned int bias; };
+struct GnEntry {
+    unsigned long long cb; unsigned int gain; int k;
+    typedef GnItem *Part;
+    typedef const GnItem *CPart;
+    typedef GnItem Item;
+    typedef GnAux Aux;
+    __device__ static GnEntry none() { return {1ull << 40, 0u, 0x7fffffff}; }
+    __device__ bool valid() const { return gain != 0; }
+    __device__ bool before(GnEntry o) const
+    {
+        const unsigned long long l = cb * o.gain, r = o.cb * gain;
+        return (l < r) | ((l == r) & ((cb < o.cb) | ((cb == o.cb) & (k < o.k))));
+    }
+    template <typename F> __device__ GnEntry map(F f) const { return {f(cb), f(gain), f(k)}; }
+    __device__ static GnEntry load(const CPart p, size_t o) { const GnItem i = p[o]; return {i.cb, i.gain, i.k}; }
+    __device__ void store(const Part p, size_t o) const { p[o] = item(); }
+    __device__ Item item() const { return {cb, gain, k}; }
+    __device__ static int centroid(Item it) { return it.k; }
+    __device__ static GnEntry make(unsigned int cost, int j, Aux a) { return {(unsigned long long)cost + a.bias, (unsigned int)a.gain[j], j}; }
+    __device__ static unsigned int cost(Item it, Aux a) { return (unsigned int)(it.cb - a.bias); }
+};
+
+// the entry of centroid j in the field fld: made of its cost there, or none
+template <typename E>
+__device__ inline E tp_key(const unsigned int *__restrict__ fld, const unsigned int *__restrict__ coff, int j, typename E::Aux aux)
 {
     const unsigned int o = coff[j];
     if (o != TP_NOCELL) {
         const unsigned int v = fld[o];
-        if (v != PL_INF) return {((unsigned long long)v << 32) | (unsigned int)j};
+        if (v != PL_INF) return E::make(v, j, aux);
     }
-    return TpEntry::none();
+    return E::none();
 }
 
 // one wave per (field of the group, chunk of centroids): fields[f] is the field of bot fbot[g0 + f]
+template <typename E>
 __global__ void __launch_bounds__(64 * AS_BOTS_PER_BLOCK)
 qs_tbp_gather_kernel(const unsigned int *__restrict__ fields, size_t fcells, const unsigned int *__restrict__ coff, int n_cent,
-                     const int *__restrict__ fbot, int g0, int gn, int n_chunks, unsigned long long *__restrict__ part)
+                     const int *__restrict__ fbot, int g0, int gn, int n_chunks, typename E::Aux aux,
+                     typename E::Item *__restrict__ part)
 {
     const int lane = threadIdx.x & 63;
     const int f = blockIdx.y * AS_BOTS_PER_BLOCK + (threadIdx.x >> 6), chunk = blockIdx.x;
     if (f >= gn) return;                                // whole waves; no workgroup barrier below
     const unsigned int *fld = fields + (size_t)f * fcells;
-    TpEntry l = TpEntry::none();
+    E l = E::none();
     const int lo = chunk * AS_CHUNK, hi = min(lo + AS_CHUNK, n_cent);
     for (int base = lo; base < hi; base += 64) {
         const int j = base + lane;
-        as_offer(l, j < hi ? tp_key(fld, coff, j) : TpEntry::none(), lane);
+        as_offer(l, j < hi ? tp_key<E>(fld, coff, j, aux) : E::none(), lane);
     }
     if (lane < AS_K) l.store(part, ((size_t)fbot[g0 + f] * n_chunks + chunk) * AS_K + lane);
 }
 
 // one wave per bot with a cell: merge its chunk lists into the exact top-K (list, list_len = entries in it)
+template <typename E>
 __global__ void __launch_bounds__(64 * AS_BOTS_PER_BLOCK)
-qs_tbp_merge_kernel(const int *__restrict__ fbot, int n_live, int n_chunks, const unsigned long long *__restrict__ part,
-                    unsigned long long *__restrict__ list, int *__restrict__ list_len)
+qs_tbp_merge_kernel(const int *__restrict__ fbot, int n_live, int n_chunks, const typename E::Item *__restrict__ part,
+                    typename E::Item *__restrict__ list, int *__restrict__ list_len)
 {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * AS_BOTS_PER_BLOCK + (threadIdx.x >> 6);
@@ -170,23 +216,25 @@ qs_tbp_merge_kernel(const int *__restrict__ fbot, int n_live, int n_chunks, cons
     const int bot = fbot[i];
     const size_t n = (size_t)n_chunks * AS_K;
     int len;
-    const TpEntry l = as_merge_lists<TpEntry>(part, (size_t)bot * n, n, lane, len);
+    const E l = as_merge_lists<E>(part, (size_t)bot * n, n, lane, len);
     if (lane < AS_K) list[(size_t)bot * AS_K + lane] = l.item();
     if (lane == 0) list_len[bot] = len;
 }
 
 // ---- the greedy pass (assign_common.h): a decision leaves the centroid, the cost, a status and, for the waypoints, the
 // (start, goal) cells of the assigned bots in assignment order.  A bot without a cell has no list to look at.
+template <typename E>
 struct TpPolicy {
     const long long *cent_cell, *bot_cell;
     int n_bots;
+    typename E::Aux aux;
     long long *pair; int *pair_bot;
     long long *tgt_idx; unsigned int *tgt_cost; int *tgt_status;
-    __device__ void assigned(int b, int m, unsigned long long key, double2) const
+    __device__ void assigned(int b, int m, typename E::Item it, double2) const
     {
-        const int k = TpEntry::centroid(key);
+        const int k = E::centroid(it);
         pair[m] = bot_cell[b]; pair[n_bots + m] = cent_cell[k]; pair_bot[m] = b;
-        tgt_idx[b] = k; tgt_cost[b] = (unsigned int)(key >> 32); tgt_status[b] = QS_PLAN_OK;
+        tgt_idx[b] = k; tgt_cost[b] = E::cost(it, aux); tgt_status[b] = QS_PLAN_OK;
     }
     __device__ void none(int b, int status) const { tgt_idx[b] = -1; tgt_cost[b] = PL_INF; tgt_status[b] = status; }
     __device__ void unassigned(int b) const { none(b, QS_PLAN_UNREACHABLE); }
@@ -198,40 +246,45 @@ struct TpPolicy {
     }
 };
 
+template <typename E>
 __global__ void __launch_bounds__(64)
 qs_tbp_greedy_kernel(const double2 *__restrict__ cent, const long long *__restrict__ cent_cell,
-                     const long long *__restrict__ bot_cell, int n_bots, double r2_sep,
-                     const unsigned long long *__restrict__ list, const int *__restrict__ list_len, int start_bot, int start_m,
-                     int fb_pending, const unsigned long long *__restrict__ fb_key, int n_fb, double2 *__restrict__ asg_xy,
+                     const long long *__restrict__ bot_cell, int n_bots, double r2_sep, typename E::Aux aux,
+                     const typename E::Item *__restrict__ list, const int *__restrict__ list_len, int start_bot, int start_m,
+                     int fb_pending, const typename E::Item *__restrict__ fb_key, int n_fb, double2 *__restrict__ asg_xy,
                      int *__restrict__ asg_idx, long long *__restrict__ pair, int *__restrict__ pair_bot,
                      long long *__restrict__ tgt_idx, unsigned int *__restrict__ tgt_cost, int *__restrict__ tgt_status,
                      QsAssignState *__restrict__ st)
 {
-    as_greedy_walk<TpEntry>(TpPolicy{cent_cell, bot_cell, n_bots, pair, pair_bot, tgt_idx, tgt_cost, tgt_status}, cent, n_bots, r2_sep,
-                            list, list_len, start_bot, start_m, fb_pending, fb_key, n_fb, asg_xy, asg_idx, st);
+    as_greedy_walk<E>(TpPolicy<E>{cent_cell, bot_cell, n_bots, aux, pair, pair_bot, tgt_idx, tgt_cost, tgt_status}, cent, n_bots,
+                      r2_sep, list, list_len, start_bot, start_m, fb_pending, fb_key, n_fb, asg_xy, asg_idx, st);
 }
 
 // ---- the fallback: every centroid for one bot, whose field is fields[0] -----------------------------------------------
+template <typename E>
 __global__ void __launch_bounds__(AS_FB_BLOCK)
 qs_tbp_fallback_kernel(const unsigned int *__restrict__ fld, const unsigned int *__restrict__ coff,
                        const double2 *__restrict__ cent, int n_cent, int m, double r2_sep, const double2 *__restrict__ asg_xy,
-                       const int *__restrict__ asg_idx, unsigned long long *__restrict__ fb_key)
+                       const int *__restrict__ asg_idx, typename E::Aux aux, typename E::Item *__restrict__ fb_key)
 {
     const int j = blockIdx.x * AS_FB_BLOCK + threadIdx.x;
     double2 q = make_double2(0.0, 0.0);
-    TpEntry e = TpEntry::none();
-    if (j < n_cent) { q = cent[j]; e = tp_key(fld, coff, j); }
-    as_fallback_block<TpEntry>(e.valid(), j, q, m, r2_sep, asg_xy, asg_idx, fb_key, [&] { return e; });
+    E e = E::none();
+    if (j < n_cent) { q = cent[j]; e = tp_key<E>(fld, coff, j, aux); }
+    as_fallback_block<E>(e.valid(), j, q, m, r2_sep, asg_xy, asg_idx, fb_key, [&] { return e; });
 }
 
-// ---- C ABI -------------------------------------------------------------------------------------------------------------
-extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, double separation, const qs_plan_params *params,
-                                           const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
-                                           uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
-                                           double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8])
+// ---- the call, over the entry E its rule orders by ----------------------------------------------------------------------
+// rank(fws, n_cent, aux), called once the frontier workspace is labelled and the n_cent centroids are counted, enqueues what
+// the rule needs beside the fields and fills aux (QS_OK or the call's failure).  stats[7] is left 0 for the caller.
+template <typename E, typename Rank>
+static int tbp_run(qs_ctx *c, const std::string &who, int32_t min_cluster, double separation, const qs_plan_params *params,
+                   Rank rank, const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy, uint32_t *cost,
+                   int32_t *status, int32_t *wp_cell_xy, double *wp_xy, double *centroids_xy, size_t cap, size_t *n_centroids,
+                   uint64_t stats[8])
 {
     ARGCHK(c, c != nullptr);
-    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets_by_path: n_bots above QS_FT_MAX_BOTS");
+    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, (who + ": n_bots above QS_FT_MAX_BOTS").c_str());
     ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy && cost && status));
     ARGCHK(c, (wp_cell_xy == nullptr) == (wp_xy == nullptr));
     ARGCHK(c, cap == 0 || centroids_xy);
@@ -249,9 +302,12 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
     HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n_cent = (size_t)total, n_end = n_cent + n_bots;
-    HIPCHK(c, c->tbp_ws.reserve(qs_tbp_layout(nullptr, n_cent, n_bots).bytes, c->stream));
-    const QsTbpLayout T = qs_tbp_layout(c->tbp_ws.p, n_cent, n_bots);
+    HIPCHK(c, c->tbp_ws.reserve(qs_tbp_layout<E>(nullptr, n_cent, n_bots).bytes, c->stream));
+    const QsTbpLayout<E> T = qs_tbp_layout<E>(c->tbp_ws.p, n_cent, n_bots);
     HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, T.xy));
+    typename E::Aux aux{};
+    rc = rank(fws, n_cent, aux);
+    if (rc != QS_OK) return rc;
     // the mask and the census; the cells of the centroids and the bots
     QsPlanLayout L;
     unsigned int bbox[4];
@@ -287,27 +343,27 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
             HIPCHK(c, hipMemcpyAsync(T.fcell, fcell.data(), n_live * sizeof(long long), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(T.fbot, fbot.data(), n_live * sizeof(int), hipMemcpyHostToDevice, c->stream));
             const size_t g = qs_plan_group(L, bbox, n_live);
-            if (g == 0) return qs_fail(c, QS_E_STATE, "qs_frontier_targets_by_path: workspace holds no field");
+            if (g == 0) return qs_fail(c, QS_E_STATE, (who + ": workspace holds no field").c_str());
             for (size_t g0 = 0; g0 < n_live; g0 += g, groups++) {
                 const size_t gn = std::min(g, n_live - g0);
                 rc = plan_fields(c, L, bbox, T.fcell, T.fcell, g0, gn);
                 if (rc != QS_OK) return rc;
                 const unsigned int gy = (unsigned int)((gn + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK);
-                hipLaunchKernelGGL(qs_tbp_gather_kernel, dim3((unsigned int)nch, gy), dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream,
-                                   L.fields, fcells, T.coff, (int)n_cent, T.fbot, (int)g0, (int)gn, nch, T.part);
+                hipLaunchKernelGGL(qs_tbp_gather_kernel<E>, dim3((unsigned int)nch, gy), dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream,
+                                   L.fields, fcells, T.coff, (int)n_cent, T.fbot, (int)g0, (int)gn, nch, aux, T.part);
                 HIPCHK(c, hipGetLastError());
             }
-            hipLaunchKernelGGL(qs_tbp_merge_kernel, dim3((unsigned int)((n_live + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK)),
+            hipLaunchKernelGGL(qs_tbp_merge_kernel<E>, dim3((unsigned int)((n_live + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK)),
                                dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream, T.fbot, (int)n_live, nch, T.part, T.list, T.list_len);
             HIPCHK(c, hipGetLastError());
         }
         // the greedy pass; a bot whose full list is ineligible gets its field again and a scan of every centroid
         const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation
         const int nfb = (int)as_fb_blocks(n_cent);
-        rc = as_run_greedy(c, "qs_frontier_targets_by_path: greedy pass made no progress", T.st, n_bots,
+        rc = as_run_greedy(c, (who + ": greedy pass made no progress").c_str(), T.st, n_bots,
             [&](int start, int m, int pending) {
-                hipLaunchKernelGGL(qs_tbp_greedy_kernel, dim3(1), dim3(64), 0, c->stream, T.xy, T.cell, T.cell + n_cent, (int)n_bots,
-                                   r2_sep, T.list, T.list_len, start, m, pending, T.fb_key, nfb, T.asg_xy, T.asg_idx, T.pair,
+                hipLaunchKernelGGL(qs_tbp_greedy_kernel<E>, dim3(1), dim3(64), 0, c->stream, T.xy, T.cell, T.cell + n_cent, (int)n_bots,
+                                   r2_sep, aux, T.list, T.list_len, start, m, pending, T.fb_key, nfb, T.asg_xy, T.asg_idx, T.pair,
                                    T.pair_bot, T.tgt_idx, T.tgt_cost, T.tgt_status, T.st);
                 return hipGetLastError();
             },
@@ -315,8 +371,8 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
                 groups++;
                 const int rcf = plan_fields(c, L, bbox, T.cell + n_cent, T.cell + n_cent, (size_t)bot, 1);
                 if (rcf != QS_OK) return rcf;
-                hipLaunchKernelGGL(qs_tbp_fallback_kernel, dim3((unsigned int)nfb), dim3(AS_FB_BLOCK), 0, c->stream, L.fields, T.coff,
-                                   T.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, T.fb_key);
+                hipLaunchKernelGGL(qs_tbp_fallback_kernel<E>, dim3((unsigned int)nfb), dim3(AS_FB_BLOCK), 0, c->stream, L.fields, T.coff,
+                                   T.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, aux, T.fb_key);
                 HIPCHK(c, hipGetLastError());
                 return (int)QS_OK;
             }, m, fallbacks);
@@ -361,15 +417,15 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
     }
     for (int i = 0; i < m; i++) {
         const int b = abot[i];
-        if (b < 0 || b >= (int)n_bots || tidx[b] < 0) return qs_fail(c, QS_E_STATE, "qs_frontier_targets_by_path: assignment list is inconsistent");
+        if (b < 0 || b >= (int)n_bots || tidx[b] < 0) return qs_fail(c, QS_E_STATE, (who + ": assignment list is inconsistent").c_str());
         target_xy[2 * b] = axy[i].x; target_xy[2 * b + 1] = axy[i].y;
         if (!wp_xy) continue;
         const int4 o = out[i];
         // both ends have cells and the cost is finite: the walk cannot fail, and its cost is the bot field's (symmetric moves)
         if (o.x != QS_PLAN_OK || (unsigned int)o.w != tcost[b]) {
             char msg[160];
-            snprintf(msg, sizeof msg, "qs_frontier_targets_by_path: bot %d: the waypoint's path (status %d, cost %u) disagrees "
-                     "with the assignment's cost %u", b, o.x, (unsigned int)o.w, tcost[b]);
+            snprintf(msg, sizeof msg, "%s: bot %d: the waypoint's path (status %d, cost %u) disagrees "
+                     "with the assignment's cost %u", who.c_str(), b, o.x, (unsigned int)o.w, tcost[b]);
             return qs_fail(c, QS_E_STATE, msg);
         }
         wp_cell_xy[2 * b] = o.y; wp_cell_xy[2 * b + 1] = o.z;
@@ -381,5 +437,48 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
         stats[0] = n_cent; stats[1] = count[0]; stats[2] = count[1]; stats[3] = groups;
         stats[4] = st[0]; stats[5] = st[1]; stats[6] = fallbacks; stats[7] = 0;
     }
+    return QS_OK;
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, double separation, const qs_plan_params *params,
+                                           const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy,
+                                           uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
+                                           double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8])
+{
+    return tbp_run<TpEntry>(c, "qs_frontier_targets_by_path", min_cluster, separation, params,
+                            [](void *, size_t, TpNoAux &) { return (int)QS_OK; }, bot_xy, n_bots, target_idx, target_xy, cost, status,
+                            wp_cell_xy, wp_xy, centroids_xy, cap, n_centroids, stats);
+}
+
+// §4.17: the same stages ordered by G6; the gains (gain.hip) are computed while the frontier workspace is still labelled
+extern "C" int qs_frontier_targets_by_gain(qs_ctx *c, int32_t min_cluster, double separation, const qs_plan_params *params,
+                                           const qs_gain_params *gain_params, const double *bot_xy, size_t n_bots,
+                                           int64_t *target_idx, double *target_xy, uint32_t *cost, int32_t *status,
+                                           int32_t *wp_cell_xy, double *wp_xy, double *centroids_xy, size_t cap,
+                                           size_t *n_centroids, int32_t *target_gain, uint64_t stats[8])
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n_bots == 0 || target_gain);
+    qs_gain_params g = {QS_GAIN_DEFAULT_RANGE, QS_GAIN_DEFAULT_BIAS, {0, 0}};
+    if (gain_params) g = *gain_params;
+    int rc = gain_range(c, g.range, "qs_frontier_targets_by_gain");
+    if (rc != QS_OK) return rc;
+    if (g.bias > QS_GAIN_MAX_BIAS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets_by_gain: bias above QS_GAIN_MAX_BIAS");
+    if (g.reserved[0] || g.reserved[1]) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets_by_gain: reserved must be 0");
+    std::vector<int> hgain;
+    rc = tbp_run<GnEntry>(c, "qs_frontier_targets_by_gain", min_cluster, separation, params,
+        [&](void *fws, size_t n_cent, GnAux &aux) {
+            HIPCHK(c, c->gain_ws.reserve(qs_gain_layout(nullptr, n_cent).bytes, c->stream));
+            const QsGainLayout G = qs_gain_layout(c->gain_ws.p, n_cent);
+            HIPCHK(c, qs_launch_gain(c, fws, min_cluster, g.range, n_cent, G));
+            hgain.resize(n_cent);             // (read after the call's last synchronise)
+            if (n_cent) HIPCHK(c, hipMemcpyAsync(hgain.data(), G.gain, n_cent * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            aux = GnAux{G.gain, g.bias};
+            return (int)QS_OK;
+        }, bot_xy, n_bots, target_idx, target_xy, cost, status, wp_cell_xy, wp_xy, centroids_xy, cap, n_centroids, stats);
+    if (rc != QS_OK) return rc;
+    for (size_t b = 0; b < n_bots; b++) target_gain[b] = target_idx[b] >= 0 ? hgain[(size_t)target_idx[b]] : 0;
+    if (stats) for (int v : hgain) stats[7] += (uint64_t)v;
     return QS_OK;
 }

@@ -924,15 +924,17 @@ class QuasarMapper:
 
     def assign_frontier_targets(self, bot_states, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
                                 by_path=False, return_waypoints=False, by_territory=False, return_territory=False,
-                                **plan_params):
+                                by_gain=False, **plan_params):
         """The reference's target_assignments (:958-992): {bot: (x, y)} of the online bots -> {bot: (tx, ty)} for
         the bots that got a target, bots taken in ascending id.  by_path=True (opt-in): the targets of
         frontier_targets_by_path instead (plan_params: clearance, snap_radius, lookahead), and with return_waypoints
         also {bot: (wx, wy)}, the waypoint of each assigned bot's path, as a second dict.  by_territory=True (opt-in,
         excludes by_path): the targets of frontier_targets_by_territory likewise (`separation` plays no part), and with
-        return_territory also {bot: (area, box)} of every bot given, box a tuple of cells or None, as the last value."""
-        if by_path and by_territory:
-            raise ValueError("assign_frontier_targets: by_path and by_territory exclude each other")
+        return_territory also {bot: (area, box)} of every bot given, box a tuple of cells or None, as the last value.
+        by_gain=True (opt-in, excludes the other two): the targets of frontier_targets_by_gain, with by_path's returns;
+        plan_params may then also hold gain_range and gain_bias."""
+        if by_path + by_territory + by_gain > 1:
+            raise ValueError("assign_frontier_targets: by_path, by_territory and by_gain exclude each other")
         if return_territory and not by_territory:
             raise ValueError("assign_frontier_targets: return_territory needs by_territory=True")
         if by_territory:
@@ -947,9 +949,9 @@ class QuasarMapper:
                 out.append({b: (int(res["area"][i]), tuple(int(v) for v in res["box"][i]) if res["area"][i] else None)
                             for i, b in enumerate(bots)})
             return out[0] if len(out) == 1 else tuple(out)
-        if not by_path:
+        if not by_path and not by_gain:
             if return_waypoints or plan_params:
-                raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True")
+                raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True or by_gain=True")
             bots = sorted(bot_states)
             if not bots:
                 return {}
@@ -958,8 +960,8 @@ class QuasarMapper:
         bots = sorted(bot_states)
         if not bots:
             return ({}, {}) if return_waypoints else {}
-        res = self.frontier_targets_by_path([bot_states[b] for b in bots], separation, min_cluster,
-                                            waypoints=return_waypoints, **plan_params)
+        call = self.frontier_targets_by_gain if by_gain else self.frontier_targets_by_path
+        res = call([bot_states[b] for b in bots], separation, min_cluster, waypoints=return_waypoints, **plan_params)
         got = [(i, b) for i, b in enumerate(bots) if res["idx"][i] >= 0]
         targets = {b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}
         if not return_waypoints:
@@ -999,6 +1001,56 @@ class QuasarMapper:
         out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy,
                    stats=dict(zip(("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits",
                                    "fallbacks", "reserved"), (int(v) for v in st))))
+        if return_centroids:
+            out["centroids"] = cents[:k.value]
+        return out
+
+    # -- frontier gain (include/quasar_slam.h, "frontier gain"; no reference counterpart) --------------------------
+    def frontier_gain(self, min_cluster=P.FRONTIER_MIN_CLUSTER, range=_lib.QS_GAIN_DEFAULT_RANGE):
+        """(viewpoints int32 [k, 2] (gx, gy), gain int32 [k]) of the clusters of frontier_clusters(min_cluster), in their
+        order: the member cell nearest the integer centroid, and the UNKNOWN cells within `range` cells of it that no
+        OCCUPIED cell hides."""
+        n = C.c_size_t()
+        self._chk(self._L.qs_frontier_gain(self._h, min_cluster, int(range), None, None, 0, C.byref(n)), "qs_frontier_gain")
+        view, gain = np.zeros((n.value, 2), dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._chk(self._L.qs_frontier_gain(self._h, min_cluster, int(range), _ptr(view), _ptr(gain), n.value, C.byref(n)),
+                      "qs_frontier_gain")
+        return view, gain
+
+    def frontier_targets_by_gain(self, bot_xy, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
+                                 clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS, lookahead=P.PLAN_LOOKAHEAD,
+                                 gain_range=_lib.QS_GAIN_DEFAULT_RANGE, gain_bias=_lib.QS_GAIN_DEFAULT_BIAS,
+                                 return_centroids=False, waypoints=True):
+        """frontier_targets_by_path with the centroids ordered by gain over cost (include/quasar_slam.h, "frontier gain",
+        G6): a bot takes the eligible centroid k with the smallest (cost + gain_bias) / gain[k].  Returns that call's dict
+        plus gain int32 [n] (the gain of each bot's target, 0 where none); stats["gain_sum"] is the sum of all gains."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(b)
+        if n > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"frontier_targets_by_gain: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        prm = self._plan_params(clearance, snap_radius, lookahead)
+        gprm = _lib.QsGainParams(int(gain_range), int(gain_bias), (0, 0))
+        idx = np.full(n, -1, dtype=np.int64)
+        xy = np.full((n, 2), np.nan, dtype=np.float64)
+        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        wc = np.full((n, 2), -1, dtype=np.int32)
+        wxy = np.full((n, 2), np.nan, dtype=np.float64)
+        gain = np.zeros(n, dtype=np.int32)
+        st = np.zeros(8, dtype=np.uint64)
+        k = C.c_size_t()
+        cents, cap = None, 0
+        if return_centroids:       # the count first: a second call would observe the same map
+            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
+            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
+        self._chk(self._L.qs_frontier_targets_by_gain(
+            self._h, min_cluster, float(separation), C.byref(prm), C.byref(gprm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost),
+            _ptr(status), _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(cents) if cap else None, cap,
+            C.byref(k), _ptr(gain), _ptr(st)), "qs_frontier_targets_by_gain")
+        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy, gain=gain,
+                   stats=dict(zip(("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits",
+                                   "fallbacks", "gain_sum"), (int(v) for v in st))))
         if return_centroids:
             out["centroids"] = cents[:k.value]
         return out

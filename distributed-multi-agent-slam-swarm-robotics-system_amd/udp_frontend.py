@@ -24,6 +24,10 @@ Mirrors server_nodes/dual_bot_mapper.py:
                                centroid of its own share (QuasarMapper.assign_frontier_targets(by_territory=True), ONE
                                device call per tick); with plan_paths=True every TARG carries a waypoint.  `territory`
                                then holds {bot: (cells owned, world box or None)} of the last tick.
+                               With targets_by_gain=True (also opt-in, excludes the other two) the centroids are ranked by
+                               the unknown area a bot would see from them over the path cost
+                               (QuasarMapper.assign_frontier_targets(by_gain=True), ONE device call per tick; gain_params:
+                               gain_range, gain_bias); TARG and plan_stats as with targets_by_path.
 Servo sweeps (opt-in, sweeps=True): the 743-byte v0 and 751-byte v0 + odometry packets of the ESP32 firmware
 (esp32_firmware/src/main.cpp:190-215) are mapped too.  Datagrams then get slots of SWEEP_SLOT bytes; the datagrams of a
 poll are cut, in arrival order, into maximal runs of one kind (41/42-byte packets, 743-byte sweeps, 751-byte sweeps),
@@ -57,7 +61,7 @@ class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
-                 targets_by_territory=False):
+                 targets_by_territory=False, targets_by_gain=False, gain_params=None):
         if plan_paths and not frontier_targets:
             raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
         if targets_by_path and not frontier_targets:
@@ -66,6 +70,10 @@ class MissionControl:
             raise ValueError("MissionControl: targets_by_territory=True needs frontier_targets=True")
         if targets_by_territory and targets_by_path:
             raise ValueError("MissionControl: targets_by_territory=True excludes targets_by_path=True")
+        if targets_by_gain and not frontier_targets:
+            raise ValueError("MissionControl: targets_by_gain=True needs frontier_targets=True")
+        if targets_by_gain and (targets_by_path or targets_by_territory):
+            raise ValueError("MissionControl: targets_by_gain=True excludes targets_by_path and targets_by_territory")
         if match_sweeps and not sweeps:
             raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
         self.sweep_graph = sweep_graph is not False and sweep_graph is not None      # ({} is on, with the defaults)
@@ -83,6 +91,8 @@ class MissionControl:
         self.plan_paths = plan_paths
         self.targets_by_path = targets_by_path
         self.targets_by_territory = targets_by_territory
+        self.targets_by_gain = targets_by_gain
+        self.gain_params = dict(gain_params or {})
         self.territory = {}
         self.plan_params = dict(plan_params or {})
         self.plan_stats = {"waypoint": 0, "centroid": 0}
@@ -243,7 +253,7 @@ class MissionControl:
         if not states:
             return {}
         sent = {}
-        if self.targets_by_path:
+        if self.targets_by_path or self.targets_by_gain:
             targets = self._targets_by_path(states)
         elif self.targets_by_territory:
             targets = self._targets_by_territory(states)
@@ -276,11 +286,12 @@ class MissionControl:
         return out
 
     def _targets_by_path(self, states):
-        """One call that ranks the centroids by path cost: the centroids of the assigned bots, or (plan_paths) their
-        waypoints, which always exist; counted in plan_stats as _waypoints counts them."""
+        """One call that ranks the centroids by path cost (targets_by_gain: by gain over path cost): the centroids of the
+        assigned bots, or (plan_paths) their waypoints, which always exist; counted in plan_stats as _waypoints counts them."""
+        kw = dict(by_gain=True, **self.plan_params, **self.gain_params) if self.targets_by_gain else dict(by_path=True, **self.plan_params)
         if not self.plan_paths:
-            return sorted(self.mapper.assign_frontier_targets(states, by_path=True, **self.plan_params).items())
-        _, wps = self.mapper.assign_frontier_targets(states, by_path=True, return_waypoints=True, **self.plan_params)
+            return sorted(self.mapper.assign_frontier_targets(states, **kw).items())
+        _, wps = self.mapper.assign_frontier_targets(states, return_waypoints=True, **kw)
         self.plan_stats["waypoint"] += len(wps)
         return sorted(wps.items())
 

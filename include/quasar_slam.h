@@ -600,6 +600,45 @@ int qs_frontier_targets_by_path(qs_ctx *ctx, int32_t min_cluster, double separat
                                 uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
                                 double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8]);
 
+/* ---- frontier gain: clusters ranked by the unknown area a bot would see from them (this build's own rules) -----------------
+ * The three target calls rank a cluster by how far away it is.  The gain of a cluster is what a bot would learn there: the
+ * UNKNOWN cells in sensor range of a cell of the cluster that no OCCUPIED cell hides.  All rules are integer, so the device and
+ * a CPU restatement agree bit for bit.
+ *  G1 Clusters: the list and order of qs_frontier_clusters(min_cluster).
+ *  G2 Viewpoint: for a cluster of n cells with sums sx, sy let cx = sx / n and cy = sy / n by integer division.  The viewpoint
+ *     is the member cell minimising ((gx-cx)^2 + (gy-cy)^2, gy*size + gx), compared as a pair.  It is a FREE interior cell.
+ *  G3 Visible: a target cell t != v inside the grid with dx*dx + dy*dy <= range^2 is visible from v when no cell of the
+ *     reference's _bresenham(v, t) (:158-179) other than t itself is OCCUPIED.  The walk goes from v to t (it is not
+ *     reversal-symmetric).  UNKNOWN and FREE cells do not block; cells outside the grid are neither targets nor counted.
+ *  G4 Gain: gain[k] is the number of visible UNKNOWN targets (stamp 0).  A frontier cell has an UNKNOWN 4-neighbour, so
+ *     gain >= 1 for every range >= 1.
+ *  G5 Range: 1 <= range <= QS_GAIN_MAX_RANGE cells.  The default, 24, is the 1.20 m sensor range at 0.05 m per cell.
+ *  G6 Order: for bot b, centroid k1 comes before k2 when (cost1 + bias) * gain2 < (cost2 + bias) * gain1 in exact 64-bit
+ *     products; ties go to the smaller cost, then the lower k.  cost is rule 3 of "frontier targets by path cost".
+ *     bias <= QS_GAIN_MAX_BIAS; the default, 120, is 24 orthogonal steps (a build choice).  A bias of 0 is the pure ratio: a bot
+ *     standing on a centroid's cell has cost 0 there and takes that centroid.
+ *  G7 Assignment: exactly rules 1-6 of "frontier targets by path cost" with "smallest (cost, k)" replaced by "first in G6's
+ *     order".  Cells, snap, eligibility (finite cost, not taken, the fp64 separation test) and statuses are unchanged; the
+ *     waypoint equals qs_plan_paths(bot, centroid) with the same cost; the call writes no session state.  The target position
+ *     stays the centroid: the viewpoint only scores it.
+ * qs_frontier_gain: viewpoint_xy (n x 2: gx, gy) and gain for the first cap clusters; both NULL queries the count.
+ * qs_frontier_targets_by_gain: every argument of qs_frontier_targets_by_path, in its order, with gain_params (NULL = the
+ * defaults) after params, and target_gain (n_bots, 0 when unassigned) before stats.  stats as for _by_path; entry 7 is the sum
+ * of all gains.  A range outside G5, a bias above QS_GAIN_MAX_BIAS or a nonzero reserved: QS_E_INVAL.  n_bots == 0, a map
+ * without clusters and a map without FREE cells are valid. */
+#define QS_GAIN_MAX_RANGE 64
+#define QS_GAIN_DEFAULT_RANGE 24
+#define QS_GAIN_DEFAULT_BIAS 120u
+#define QS_GAIN_MAX_BIAS 0x80000000u
+typedef struct qs_gain_params { int32_t range; uint32_t bias; int32_t reserved[2]; } qs_gain_params;
+int qs_frontier_gain(qs_ctx *ctx, int32_t min_cluster, int32_t range, int32_t *viewpoint_xy, int32_t *gain, size_t cap,
+                     size_t *n_out);
+int qs_frontier_targets_by_gain(qs_ctx *ctx, int32_t min_cluster, double separation, const qs_plan_params *params,
+                                const qs_gain_params *gain_params, const double *bot_xy, size_t n_bots, int64_t *target_idx,
+                                double *target_xy, uint32_t *cost, int32_t *status, int32_t *wp_cell_xy, double *wp_xy,
+                                double *centroids_xy, size_t cap, size_t *n_centroids, int32_t *target_gain,
+                                uint64_t stats[8]);
+
 /* ---- territories: the mapped free space partitioned among the bots by path cost (this build's own rules) ------------------
  * qs_frontier_targets_by_path pays one shortest-path field per bot and assigns greedily in bot order.  Here every bot is
  * a seed of ONE field and each cell keeps the smallest (cost, bot): who is nearest by path to every free cell and every

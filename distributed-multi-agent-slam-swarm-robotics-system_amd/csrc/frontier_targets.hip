@@ -17,6 +17,7 @@
 // A key that is NaN or +inf (a NaN / inf / far-outlier bot) never enters a list: `NaN < inf` and `inf < inf` are false.
 // The sorted list, the blocked test, the greedy walk and the host's stop / resume loop are assign_common.h's, shared with
 // targets_by_path.hip; here are the entry they order by, the producer of the chunk lists and the fallback's key.
+// qs_count_centroids is how every call over the centroids starts (here, targets_by_path.hip, territory.hip, gain.hip).
 #include "assign_common.h"
 #include "compact.h"
 
@@ -52,6 +53,21 @@ hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, i
     // no cap on the writes: d_cent holds the total phase 0 counted
     return qs_compact(c->stream, FtKeep{F.cnt, min_cluster}, c->cells, phase != 0,
                       FtEmitCentroid{F.cnt, F.sumx, F.sumy, c->cfg.res, c->cfg.ox, c->cfg.oy, d_cent}, ~(size_t)0, F.chunk, F.total);
+}
+
+int qs_count_centroids(qs_ctx *c, int32_t min_cluster, void *&fws, size_t &n_cent)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
+    fws = c->frontier_ws.p;
+    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    n_cent = (size_t)total;
+    return QS_OK;
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------
@@ -191,16 +207,10 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
     if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets: n_bots above QS_FT_MAX_BOTS");
     ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy));
     ARGCHK(c, cap == 0 || centroids_xy);
-    HIPCHK(c, hipSetDevice(c->device));
-    SYNCCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
-    void *fws = c->frontier_ws.p;
-    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
-    unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t n_cent = (size_t)total;
+    void *fws;
+    size_t n_cent;
+    int rc = qs_count_centroids(c, min_cluster, fws, n_cent);
+    if (rc != QS_OK) return rc;
     HIPCHK(c, c->ft_ws.reserve(qs_ft_layout(nullptr, n_cent, n_bots).bytes, c->stream));
     const QsFtLayout F = qs_ft_layout(c->ft_ws.p, n_cent, n_bots);
     HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, F.cent));
@@ -219,7 +229,7 @@ extern "C" int qs_frontier_targets(qs_ctx *c, int32_t min_cluster, double separa
         hipLaunchKernelGGL(qs_ft_topk_merge_kernel, dim3(gy), dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream,
                            (int)n_bots, nch, cpart, F.list_idx, F.list_len);
         int m;
-        const int rc = as_run_greedy(c, "qs_frontier_targets: greedy pass made no progress", F.st, n_bots,
+        rc = as_run_greedy(c, "qs_frontier_targets: greedy pass made no progress", F.st, n_bots,
             [&](int start, int m, int pending) {
                 hipLaunchKernelGGL(qs_ft_greedy_kernel, dim3(1), dim3(64), 0, c->stream, F.cent, (int)n_bots, r2_sep, F.list_idx,
                                    F.list_len, start, m, pending, cfb, nfb, F.asg_xy, F.asg_idx, F.tgt_idx, F.tgt_xy, F.st);

@@ -151,23 +151,18 @@ extern "C" int qs_frontier_gain(qs_ctx *c, int32_t min_cluster, int32_t range, i
 {
     ARGCHK(c, c != nullptr && n_out != nullptr);
     ARGCHK(c, (viewpoint_xy == nullptr) == (gain == nullptr));
-    const int rc = gain_range(c, range, "qs_frontier_gain");
+    int rc = gain_range(c, range, "qs_frontier_gain");
     if (rc != QS_OK) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    SYNCCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
-    void *fws = c->frontier_ws.p;
-    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
-    unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n_out = (size_t)total;
-    const size_t n = (size_t)total < cap ? (size_t)total : cap;
+    void *fws;
+    size_t n_cent;
+    rc = qs_count_centroids(c, min_cluster, fws, n_cent);
+    if (rc != QS_OK) return rc;
+    *n_out = n_cent;
+    const size_t n = n_cent < cap ? n_cent : cap;
     if (!gain || !n) return QS_OK;
-    HIPCHK(c, c->gain_ws.reserve(qs_gain_layout(nullptr, (size_t)total).bytes, c->stream));
-    const QsGainLayout G = qs_gain_layout(c->gain_ws.p, (size_t)total);
-    HIPCHK(c, qs_launch_gain(c, fws, min_cluster, range, (size_t)total, G));
+    HIPCHK(c, c->gain_ws.reserve(qs_gain_layout(nullptr, n_cent).bytes, c->stream));
+    const QsGainLayout G = qs_gain_layout(c->gain_ws.p, n_cent);
+    HIPCHK(c, qs_launch_gain(c, fws, min_cluster, range, n_cent, G));
     HIPCHK(c, hipMemcpyAsync(viewpoint_xy, G.view, n * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(gain, G.gain, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

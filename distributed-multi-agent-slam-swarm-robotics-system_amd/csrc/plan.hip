@@ -560,13 +560,19 @@ int plan_fields(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], co
     return plan_rounds_of(c, L, bbox, L.fields, gn);
 }
 
-// ... then the walk
-static int plan_group(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], size_t n, size_t g0, size_t gn,
-                      int lookahead, size_t path_cap)
+// the waypoint stage (plan_common.h): per group the fields, then the walk
+int plan_waypoints(qs_ctx *c, const char *who, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
+                   const long long *goal, size_t m, int lookahead, size_t path_cap, uint64_t &groups, int4 *out4)
 {
-    int rc = plan_fields(c, L, bbox, L.cell, L.cell + n, g0, gn);
-    if (rc != QS_OK) return rc;
-    if (lookahead > 0) HIPCHK(c, qs_launch_plan_walk(c, L, bbox, L.cell, L.cell + n, g0, gn, lookahead, path_cap));
+    const size_t g = qs_plan_group(L, bbox, m);
+    if (g == 0) return qs_fail(c, QS_E_STATE, (std::string(who) + ": workspace holds no field").c_str());
+    for (size_t g0 = 0; g0 < m; g0 += g, groups++) {
+        const size_t gn = std::min(g, m - g0);
+        const int rc = plan_fields(c, L, bbox, start, goal, g0, gn);
+        if (rc != QS_OK) return rc;
+        HIPCHK(c, qs_launch_plan_walk(c, L, bbox, start, goal, g0, gn, lookahead, path_cap));
+    }
+    HIPCHK(c, hipMemcpyAsync(out4, L.out4, m * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
     return QS_OK;
 }
 
@@ -603,7 +609,7 @@ extern "C" int qs_plan_field(qs_ctx *c, const qs_plan_params *params, const doub
     const double xy[4] = {goal_xy[0], goal_xy[1], goal_xy[0], goal_xy[1]};   // (start = goal: only the field is wanted)
     HIPCHK(c, hipMemcpyAsync(L.xy, xy, sizeof xy, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, qs_launch_plan_snap(c, L, L.xy, L.cell, 2, p.snap_radius, L.stats + 3));
-    rc = plan_group(c, L, bbox, 1, 0, 1, 0, 0);
+    rc = plan_fields(c, L, bbox, L.cell, L.cell + 1, 0, 1);
     if (rc != QS_OK) return rc;
     // the bounding box's cells that lie on the grid, rows of the field into rows of the host array
     const size_t x0 = (size_t)bbox[0] * 64, y0 = (size_t)bbox[1] * 64, fw = (size_t)(bbox[2] - bbox[0] + 1) * 64;
@@ -639,13 +645,8 @@ extern "C" int qs_plan_paths(qs_ctx *c, const qs_plan_params *params, const doub
         memcpy(xy.data() + 2 * n, goal_xy, 2 * n * sizeof(double));
         HIPCHK(c, hipMemcpyAsync(L.xy, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, qs_launch_plan_snap(c, L, L.xy, L.cell, 2 * n, p.snap_radius, L.stats + 3));
-        const size_t g = qs_plan_group(L, bbox, n);
-        if (g == 0) return qs_fail(c, QS_E_STATE, "qs_plan_paths: workspace holds no field");
-        for (size_t g0 = 0; g0 < n; g0 += g, groups++) {
-            rc = plan_group(c, L, bbox, n, g0, std::min(g, n - g0), p.lookahead, path_cap);
-            if (rc != QS_OK) return rc;
-        }
-        HIPCHK(c, hipMemcpyAsync(out.data(), L.out4, n * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+        rc = plan_waypoints(c, "qs_plan_paths", L, bbox, L.cell, L.cell + n, n, p.lookahead, path_cap, groups, out.data());
+        if (rc != QS_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(plen.data(), L.plen, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         if (path_cap) HIPCHK(c, hipMemcpyAsync(path_xy, L.path, n * path_cap * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(st, L.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));

@@ -1,7 +1,9 @@
 // plan_common.h -- what plan.hip (path planning) shares with targets_by_path.hip (§4.12) and
-// territory.hip (§4.16): the tile geometry, the planner's workspace and the launchers of its kernels.  The kernels
-// themselves stay in plan.hip.
+// territory.hip (§4.16): the tile geometry, the planner's workspace, the launchers of its kernels and the waypoint stage.
+// The kernels themselves stay in plan.hip.  Below that: the host frame those two files' target calls share.
 #pragma once
+#include <math.h>
+
 #include "qs_internal.h"
 
 #define PL_T 64                       // tile edge (cells)
@@ -40,7 +42,7 @@ static inline PlBox pl_box(const unsigned int bbox[4])
     return B;
 }
 
-// ---- host side of plan.hip that targets_by_path.hip calls ---------------------------------------------------------------
+// ---- host side of plan.hip that targets_by_path.hip and territory.hip call -----------------------------------------------
 QsPlanLayout qs_plan_layout(void *ws, int size, size_t n, size_t path_cap);
 // params (NULL = the defaults) checked into out; QS_E_INVAL with a message otherwise
 int plan_params(qs_ctx *c, const qs_plan_params *p, qs_plan_params &out);
@@ -60,3 +62,57 @@ int plan_rounds_key64(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[
 // the walks of requests g0 .. g0 + gn over the group's fields: L.out4, L.plen, L.path
 hipError_t qs_launch_plan_walk(qs_ctx *c, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
                                const long long *goal, size_t g0, size_t gn, int lookahead, size_t path_cap);
+// the waypoint stage of `who`: the fields and walks of the m requests start[i] -> goal[i] (cells on the device) in groups
+// that fit the workspace, counted in groups; then the copy of L.out4[0 .. m) to out4 is enqueued (the caller synchronises)
+int plan_waypoints(qs_ctx *c, const char *who, const QsPlanLayout &L, const unsigned int bbox[4], const long long *start,
+                   const long long *goal, size_t m, int lookahead, size_t path_cap, uint64_t &groups, int4 *out4);
+
+// ---- what the path-cost target calls share (qs_frontier_targets_by_path / _by_gain / _by_territory) ---------------------
+#define TP_NOCELL 0xffffffffu         // coff of a centroid without a cell
+
+// the part of their workspaces that both carve alike
+struct QsTgtLayout {
+    unsigned long long *count;            // [4] centroids with a cell, bots with a cell; territory.hip: centroids with an owner, assigned bots
+    double2 *xy;                          // [n_cent + n_bots] centroids, then bots
+    long long *cell;                      // [n_cent + n_bots] their cells (gy * size + gx), -1 = none
+    unsigned int *coff;                   // [n_cent] offset of the centroid's cell in a field, TP_NOCELL = none
+    long long *tgt_idx;                   // [n_bots] per bot: the centroid or -1
+    unsigned int *tgt_cost;               // [n_bots]
+    int *tgt_status;                      // [n_bots]
+    long long *pair;                      // [2 n_bots] start cells of the assigned bots (in assignment order), then their goals
+    int *pair_bot;                        // [n_bots] the bot of each pair
+};
+
+static inline QsTgtLayout qs_tgt_layout(Carve &k, size_t n_cent, size_t n_bots)
+{
+    QsTgtLayout L;
+    L.count = k.take<unsigned long long>(4);
+    L.xy = k.take<double2>(n_cent + n_bots);
+    L.cell = k.take<long long>(n_cent + n_bots);
+    L.coff = k.take<unsigned int>(n_cent);
+    L.tgt_idx = k.take<long long>(n_bots);
+    L.tgt_cost = k.take<unsigned int>(n_bots);
+    L.tgt_status = k.take<int>(n_bots);
+    L.pair = k.take<long long>(2 * n_bots);
+    L.pair_bot = k.take<int>(n_bots);
+    return L;
+}
+
+// the per-bot arrays such a call fills (the C ABI's); wp_cell_xy and wp_xy both or neither
+struct QsTargetsOut { int64_t *target_idx; double *target_xy; uint32_t *cost; int32_t *status; int32_t *wp_cell_xy; double *wp_xy; };
+
+// host copies of what the call's kernels left: per bot, then per assigned pair in assignment order (pair_bot, the walk's out4)
+struct QsTargetsHost {
+    std::vector<long long> idx; std::vector<double2> xy; std::vector<unsigned int> cost; std::vector<int> status;
+    std::vector<int> pair_bot; std::vector<int4> out4;
+    explicit QsTargetsHost(size_t n_bots)
+        : idx(n_bots, -1), xy(n_bots, make_double2(NAN, NAN)), cost(n_bots, PL_INF), status(n_bots, QS_PLAN_NO_START),
+          pair_bot(n_bots, -1), out4(n_bots, make_int4(0, -1, -1, -1)) {}
+};
+
+// targets_by_path.hip.  The arguments the three entry points share, in the order they are refused, then params into p
+int tbp_check_args(qs_ctx *c, const char *who, size_t n_bots, const double *bot_xy, const QsTargetsOut &o,
+                   const double *centroids_xy, size_t cap, const qs_plan_params *params, qs_plan_params &p);
+// H into the caller's arrays: every bot's target, cost and status, and (o.wp_xy) the waypoints of the first m pairs, each
+// walk checked against the cost `whose` ("assignment's", "partition's") kernels found for its bot
+int tbp_finish(qs_ctx *c, const char *who, const char *whose, const QsTargetsHost &H, size_t m, const QsTargetsOut &o);

@@ -452,6 +452,9 @@ hipError_t qs_launch_frontier_label(qs_ctx *c, void *ws, bool with_clusters);
 // frontier_targets.hip: the centroids of the clusters of a labelled frontier workspace with >= min_cluster cells, in first-cell
 // order.  phase 0 counts them (QsFrLayout::total); phase 1 writes them all to d_cent, which holds that many
 hipError_t qs_launch_ft_centroids(qs_ctx *c, void *fr_ws, int32_t min_cluster, int phase, double2 *d_cent);
+// what every call over those centroids starts with: the sync point, the frontier workspace reserved (-> fws) and labelled,
+// phase 0, and one wait for the count (-> n_cent)
+int qs_count_centroids(qs_ctx *c, int32_t min_cluster, void *&fws, size_t &n_cent);
 // targets_by_path.hip: cell[0 .. n_cent) of the centroids -> their offsets in a field over the census box bbox (0xffffffff =
 // no cell); count[0] += centroids with a cell, count[1] += cells among cell[n_cent .. n_cent + n_bots), the bots'
 hipError_t qs_launch_tbp_offsets(qs_ctx *c, const long long *cell, size_t n_cent, size_t n_bots, const unsigned int bbox[4],

@@ -16,12 +16,13 @@
 //              the key the rule orders by, so its first eligible entry is the minimum over every eligible centroid.  When a
 //              full list is entirely ineligible the pass stops: the host recomputes that bot's field, a whole-GPU scan over
 //              all centroids finds its pick, and the pass resumes (counted in stats);
-//   waypoints: the body of qs_plan_paths for the assigned pairs: fields seeded at the assigned centroids' cells, the walk.
+//   waypoints: plan.hip's waypoint stage for the assigned pairs: fields seeded at the assigned centroids' cells, the walk.
 // No device-side waits, no grid-wide barriers, no graphs.
 // The sorted list, the blocked test, the greedy walk and the host's stop / resume loop are assign_common.h's, shared with
 // frontier_targets.hip; here are the entry they order by, the gather that produces the chunk lists and the fallback's key.
 // The stages are written over that entry, so qs_frontier_targets_by_gain (§4.17) is the same call with another order: its
 // entry carries (cost + bias, gain, centroid), and the gains come from gain.hip before the mask is built.
+// The argument check and the per-bot epilogue ahead of the call also serve qs_frontier_targets_by_territory (§4.16).
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
@@ -30,27 +31,18 @@
 #include "plan_common.h"
 
 #define TP_NOKEY 0xffffffffffffffffull
-#define TP_NOCELL 0xffffffffu
 
 // the workspace of one call, carved from ws (nullptr: only the bytes the block needs)
 template <typename E>
 struct QsTbpLayout {
     QsAssignState *st;
-    unsigned long long *count;            // [2] centroids, bots with a cell
-    double2 *xy;                          // [n_cent + n_bots] centroids, then bots
-    long long *cell;                      // [n_cent + n_bots] their cells (gy * size + gx), -1 = none
-    unsigned int *coff;                   // [n_cent] offset of the centroid's cell in a field, TP_NOCELL = none
+    QsTgtLayout tg;                       // what territory.hip's workspace holds too (plan_common.h)
     long long *fcell;                     // [n_bots] the cells of the bots that have one, in bot order ...
     int *fbot;                            // [n_bots] ... and their bots
     typename E::Item *part;               // [n_bots][n_chunks][K] chunk lists
     typename E::Item *list;               // [n_bots][K] the top-K of a bot (by bot)
     int *list_len;                        // [n_bots]
     double2 *asg_xy; int *asg_idx;        // [n_bots] the targets so far: centroid position, index
-    long long *tgt_idx;                   // [n_bots] per bot: the centroid or -1
-    unsigned int *tgt_cost;               // [n_bots]
-    int *tgt_status;                      // [n_bots]
-    long long *pair;                      // [2 n_bots] start cells of the assigned bots (in assignment order), then their goals
-    int *pair_bot;                        // [n_bots] the bot of each pair
     typename E::Item *fb_key;             // [n_fb] per-block minima of a fallback scan
     size_t bytes;
 };
@@ -61,10 +53,7 @@ static QsTbpLayout<E> qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
     QsTbpLayout<E> L;
     Carve k(ws);
     L.st = k.take<QsAssignState>(1);
-    L.count = k.take<unsigned long long>(2);
-    L.xy = k.take<double2>(n_cent + n_bots);
-    L.cell = k.take<long long>(n_cent + n_bots);
-    L.coff = k.take<unsigned int>(n_cent);
+    L.tg = qs_tgt_layout(k, n_cent, n_bots);
     L.fcell = k.take<long long>(n_bots);
     L.fbot = k.take<int>(n_bots);
     L.part = k.take<typename E::Item>(n_bots * as_chunks(n_cent) * AS_K);
@@ -72,11 +61,6 @@ static QsTbpLayout<E> qs_tbp_layout(void *ws, size_t n_cent, size_t n_bots)
     L.list_len = k.take<int>(n_bots);
     L.asg_xy = k.take<double2>(n_bots);
     L.asg_idx = k.take<int>(n_bots);
-    L.tgt_idx = k.take<long long>(n_bots);
-    L.tgt_cost = k.take<unsigned int>(n_bots);
-    L.tgt_status = k.take<int>(n_bots);
-    L.pair = k.take<long long>(2 * n_bots);
-    L.pair_bot = k.take<int>(n_bots);
     L.fb_key = k.take<typename E::Item>(as_fb_blocks(n_cent));
     L.bytes = k.bytes;
     return L;
@@ -274,37 +258,73 @@ qs_tbp_fallback_kernel(const unsigned int *__restrict__ fld, const unsigned int 
     as_fallback_block<E>(e.valid(), j, q, m, r2_sep, asg_xy, asg_idx, fb_key, [&] { return e; });
 }
 
+// ---- what the three path-cost entry points share (plan_common.h) ----------------------------------------------------------
+int tbp_check_args(qs_ctx *c, const char *who, size_t n_bots, const double *bot_xy, const QsTargetsOut &o,
+                   const double *centroids_xy, size_t cap, const qs_plan_params *params, qs_plan_params &p)
+{
+    const auto [target_idx, target_xy, cost, status, wp_cell_xy, wp_xy] = o;
+    ARGCHK(c, c != nullptr);
+    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, (std::string(who) + ": n_bots above QS_FT_MAX_BOTS").c_str());
+    ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy && cost && status));
+    ARGCHK(c, (wp_cell_xy == nullptr) == (wp_xy == nullptr));
+    ARGCHK(c, cap == 0 || centroids_xy);
+    return plan_params(c, params, p);
+}
+
+int tbp_finish(qs_ctx *c, const char *who, const char *whose, const QsTargetsHost &H, size_t m, const QsTargetsOut &o)
+{
+    const size_t n_bots = H.idx.size();
+    for (size_t b = 0; b < n_bots; b++) {
+        o.target_idx[b] = H.idx[b];
+        o.target_xy[2 * b] = H.xy[b].x; o.target_xy[2 * b + 1] = H.xy[b].y;
+        o.cost[b] = H.cost[b];
+        o.status[b] = H.status[b];
+        if (o.wp_xy) {
+            o.wp_cell_xy[2 * b] = o.wp_cell_xy[2 * b + 1] = -1;
+            o.wp_xy[2 * b] = o.wp_xy[2 * b + 1] = NAN;
+        }
+    }
+    for (size_t i = 0; i < m; i++) {
+        const int b = H.pair_bot[i];
+        if (b < 0 || b >= (int)n_bots || H.idx[b] < 0)
+            return qs_fail(c, QS_E_STATE, (std::string(who) + ": assignment list is inconsistent").c_str());
+        if (!o.wp_xy) continue;
+        const int4 w = H.out4[i];
+        // both ends have cells and the cost is finite: the walk cannot fail, and its cost is the bot's (symmetric moves)
+        if (w.x != QS_PLAN_OK || (unsigned int)w.w != H.cost[b]) {
+            char msg[192];
+            snprintf(msg, sizeof msg, "%s: bot %d: the waypoint's path (status %d, cost %u) disagrees with the %s cost %u", who, b,
+                     w.x, (unsigned int)w.w, whose, H.cost[b]);
+            return qs_fail(c, QS_E_STATE, msg);
+        }
+        o.wp_cell_xy[2 * b] = w.y; o.wp_cell_xy[2 * b + 1] = w.z;
+        o.wp_xy[2 * b] = c->cfg.ox + (w.y + 0.5) * c->cfg.res;        // grid_to_world :127-131
+        o.wp_xy[2 * b + 1] = c->cfg.oy + (w.z + 0.5) * c->cfg.res;
+    }
+    return QS_OK;
+}
+
 // ---- the call, over the entry E its rule orders by ----------------------------------------------------------------------
 // rank(fws, n_cent, aux), called once the frontier workspace is labelled and the n_cent centroids are counted, enqueues what
 // the rule needs beside the fields and fills aux (QS_OK or the call's failure).  stats[7] is left 0 for the caller.
 template <typename E, typename Rank>
-static int tbp_run(qs_ctx *c, const std::string &who, int32_t min_cluster, double separation, const qs_plan_params *params,
-                   Rank rank, const double *bot_xy, size_t n_bots, int64_t *target_idx, double *target_xy, uint32_t *cost,
-                   int32_t *status, int32_t *wp_cell_xy, double *wp_xy, double *centroids_xy, size_t cap, size_t *n_centroids,
-                   uint64_t stats[8])
+static int tbp_run(qs_ctx *c, const char *who, int32_t min_cluster, double separation, const qs_plan_params *params, Rank rank,
+                   const double *bot_xy, size_t n_bots, const QsTargetsOut &o, double *centroids_xy, size_t cap,
+                   size_t *n_centroids, uint64_t stats[8])
 {
-    ARGCHK(c, c != nullptr);
-    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, (who + ": n_bots above QS_FT_MAX_BOTS").c_str());
-    ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy && cost && status));
-    ARGCHK(c, (wp_cell_xy == nullptr) == (wp_xy == nullptr));
-    ARGCHK(c, cap == 0 || centroids_xy);
     qs_plan_params p;
-    int rc = plan_params(c, params, p);
+    int rc = tbp_check_args(c, who, n_bots, bot_xy, o, centroids_xy, cap, params, p);
     if (rc != QS_OK) return rc;
     // the centroids (frontier_targets.hip's), counted first
-    HIPCHK(c, hipSetDevice(c->device));
-    SYNCCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
-    void *fws = c->frontier_ws.p;
-    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
-    unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t n_cent = (size_t)total, n_end = n_cent + n_bots;
+    void *fws;
+    size_t n_cent;
+    rc = qs_count_centroids(c, min_cluster, fws, n_cent);
+    if (rc != QS_OK) return rc;
+    const size_t n_end = n_cent + n_bots;
     HIPCHK(c, c->tbp_ws.reserve(qs_tbp_layout<E>(nullptr, n_cent, n_bots).bytes, c->stream));
     const QsTbpLayout<E> T = qs_tbp_layout<E>(c->tbp_ws.p, n_cent, n_bots);
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, T.xy));
+    const QsTgtLayout &S = T.tg;
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, S.xy));
     typename E::Aux aux{};
     rc = rank(fws, n_cent, aux);
     if (rc != QS_OK) return rc;
@@ -314,23 +334,22 @@ static int tbp_run(qs_ctx *c, const std::string &who, int32_t min_cluster, doubl
     rc = plan_begin(c, p.clearance, n_bots, 0, L, bbox);
     if (rc != QS_OK) return rc;
     const bool any_trav = bbox[0] <= bbox[2];
+    const std::string name(who);
     uint64_t groups = 0, fallbacks = 0;
     unsigned long long count[2] = {0, 0}, st[4] = {0, 0, 0, 0};
-    std::vector<long long> tidx(n_bots, -1), bcell(n_bots, -1);
-    std::vector<unsigned int> tcost(n_bots, PL_INF);
-    std::vector<int> tstat(n_bots, QS_PLAN_NO_START);
-    std::vector<int4> out(n_bots, make_int4(0, -1, -1, -1));
+    std::vector<long long> bcell(n_bots, -1);
+    QsTargetsHost H(n_bots);
     int m = 0;
     if (n_bots && any_trav) {
         const PlBox B = pl_box(bbox);
         const size_t fcells = (size_t)B.fw * B.fh;
-        HIPCHK(c, hipMemcpyAsync(T.xy + n_cent, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync(T.count, 0, 2 * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.xy + n_cent, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(S.count, 0, 2 * sizeof(unsigned long long), c->stream));
         HIPCHK(c, hipMemsetAsync(T.list_len, 0, n_bots * sizeof(int), c->stream));
-        HIPCHK(c, qs_launch_plan_snap(c, L, T.xy, T.cell, n_end, p.snap_radius, L.stats + 3));
-        HIPCHK(c, qs_launch_tbp_offsets(c, T.cell, n_cent, n_bots, bbox, T.coff, T.count));
-        HIPCHK(c, hipMemcpyAsync(bcell.data(), T.cell + n_cent, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, qs_launch_plan_snap(c, L, S.xy, S.cell, n_end, p.snap_radius, L.stats + 3));
+        HIPCHK(c, qs_launch_tbp_offsets(c, S.cell, n_cent, n_bots, bbox, S.coff, S.count));
+        HIPCHK(c, hipMemcpyAsync(bcell.data(), S.cell + n_cent, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(count, S.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         // one field per bot with a cell, in groups; each group's costs gathered into chunk lists while it is resident
         std::vector<long long> fcell;
@@ -343,14 +362,14 @@ static int tbp_run(qs_ctx *c, const std::string &who, int32_t min_cluster, doubl
             HIPCHK(c, hipMemcpyAsync(T.fcell, fcell.data(), n_live * sizeof(long long), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(T.fbot, fbot.data(), n_live * sizeof(int), hipMemcpyHostToDevice, c->stream));
             const size_t g = qs_plan_group(L, bbox, n_live);
-            if (g == 0) return qs_fail(c, QS_E_STATE, (who + ": workspace holds no field").c_str());
+            if (g == 0) return qs_fail(c, QS_E_STATE, (name + ": workspace holds no field").c_str());
             for (size_t g0 = 0; g0 < n_live; g0 += g, groups++) {
                 const size_t gn = std::min(g, n_live - g0);
                 rc = plan_fields(c, L, bbox, T.fcell, T.fcell, g0, gn);
                 if (rc != QS_OK) return rc;
                 const unsigned int gy = (unsigned int)((gn + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK);
                 hipLaunchKernelGGL(qs_tbp_gather_kernel<E>, dim3((unsigned int)nch, gy), dim3(64 * AS_BOTS_PER_BLOCK), 0, c->stream,
-                                   L.fields, fcells, T.coff, (int)n_cent, T.fbot, (int)g0, (int)gn, nch, aux, T.part);
+                                   L.fields, fcells, S.coff, (int)n_cent, T.fbot, (int)g0, (int)gn, nch, aux, T.part);
                 HIPCHK(c, hipGetLastError());
             }
             hipLaunchKernelGGL(qs_tbp_merge_kernel<E>, dim3((unsigned int)((n_live + AS_BOTS_PER_BLOCK - 1) / AS_BOTS_PER_BLOCK)),
@@ -360,78 +379,48 @@ static int tbp_run(qs_ctx *c, const std::string &who, int32_t min_cluster, doubl
         // the greedy pass; a bot whose full list is ineligible gets its field again and a scan of every centroid
         const double r2_sep = r2_threshold_for(separation);        // s < r2_sep <=> sqrt(s) < separation
         const int nfb = (int)as_fb_blocks(n_cent);
-        rc = as_run_greedy(c, (who + ": greedy pass made no progress").c_str(), T.st, n_bots,
+        rc = as_run_greedy(c, (name + ": greedy pass made no progress").c_str(), T.st, n_bots,
             [&](int start, int m, int pending) {
-                hipLaunchKernelGGL(qs_tbp_greedy_kernel<E>, dim3(1), dim3(64), 0, c->stream, T.xy, T.cell, T.cell + n_cent, (int)n_bots,
-                                   r2_sep, aux, T.list, T.list_len, start, m, pending, T.fb_key, nfb, T.asg_xy, T.asg_idx, T.pair,
-                                   T.pair_bot, T.tgt_idx, T.tgt_cost, T.tgt_status, T.st);
+                hipLaunchKernelGGL(qs_tbp_greedy_kernel<E>, dim3(1), dim3(64), 0, c->stream, S.xy, S.cell, S.cell + n_cent, (int)n_bots,
+                                   r2_sep, aux, T.list, T.list_len, start, m, pending, T.fb_key, nfb, T.asg_xy, T.asg_idx, S.pair,
+                                   S.pair_bot, S.tgt_idx, S.tgt_cost, S.tgt_status, T.st);
                 return hipGetLastError();
             },
             [&](int bot, int m) {                                   // the bot's field again, then every centroid for it
                 groups++;
-                const int rcf = plan_fields(c, L, bbox, T.cell + n_cent, T.cell + n_cent, (size_t)bot, 1);
+                const int rcf = plan_fields(c, L, bbox, S.cell + n_cent, S.cell + n_cent, (size_t)bot, 1);
                 if (rcf != QS_OK) return rcf;
-                hipLaunchKernelGGL(qs_tbp_fallback_kernel<E>, dim3((unsigned int)nfb), dim3(AS_FB_BLOCK), 0, c->stream, L.fields, T.coff,
-                                   T.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, aux, T.fb_key);
+                hipLaunchKernelGGL(qs_tbp_fallback_kernel<E>, dim3((unsigned int)nfb), dim3(AS_FB_BLOCK), 0, c->stream, L.fields, S.coff,
+                                   S.xy, (int)n_cent, m, r2_sep, T.asg_xy, T.asg_idx, aux, T.fb_key);
                 HIPCHK(c, hipGetLastError());
                 return (int)QS_OK;
             }, m, fallbacks);
         if (rc != QS_OK) return rc;
-        // waypoints: qs_plan_paths' fields and walks for the m assigned pairs (starts pair[0..m), goals pair[n_bots ..))
-        if (wp_xy && m) {
-            const size_t g = qs_plan_group(L, bbox, (size_t)m);
-            for (size_t g0 = 0; g0 < (size_t)m; g0 += g, groups++) {
-                const size_t gn = std::min(g, (size_t)m - g0);
-                rc = plan_fields(c, L, bbox, T.pair, T.pair + n_bots, g0, gn);
-                if (rc != QS_OK) return rc;
-                HIPCHK(c, qs_launch_plan_walk(c, L, bbox, T.pair, T.pair + n_bots, g0, gn, p.lookahead, 0));
-            }
-            HIPCHK(c, hipMemcpyAsync(out.data(), L.out4, (size_t)m * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+        // waypoints for the m assigned pairs (starts pair[0..m), goals pair[n_bots ..))
+        if (o.wp_xy && m) {
+            rc = plan_waypoints(c, who, L, bbox, S.pair, S.pair + n_bots, (size_t)m, p.lookahead, 0, groups, H.out4.data());
+            if (rc != QS_OK) return rc;
         }
-        HIPCHK(c, hipMemcpyAsync(tidx.data(), T.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(tcost.data(), T.tgt_cost, n_bots * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(tstat.data(), T.tgt_status, n_bots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.idx.data(), S.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.cost.data(), S.tgt_cost, n_bots * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.status.data(), S.tgt_status, n_bots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(st, L.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
     } else if (any_trav && n_cent) {                     // no bots: the centroids' cells are still counted
-        HIPCHK(c, hipMemsetAsync(T.count, 0, 2 * sizeof(unsigned long long), c->stream));
-        HIPCHK(c, qs_launch_plan_snap(c, L, T.xy, T.cell, n_cent, p.snap_radius, L.stats + 3));
-        HIPCHK(c, qs_launch_tbp_offsets(c, T.cell, n_cent, 0, bbox, T.coff, T.count));
-        HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemsetAsync(S.count, 0, 2 * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, qs_launch_plan_snap(c, L, S.xy, S.cell, n_cent, p.snap_radius, L.stats + 3));
+        HIPCHK(c, qs_launch_tbp_offsets(c, S.cell, n_cent, 0, bbox, S.coff, S.count));
+        HIPCHK(c, hipMemcpyAsync(count, S.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
     }   // (no traversable cell: nothing snaps, every bot is QS_PLAN_NO_START, what the snap kernel would say)
     const size_t nc = n_cent < cap ? n_cent : cap;
-    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, T.xy, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, S.xy, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     std::vector<double2> axy((size_t)m);
     if (m) HIPCHK(c, hipMemcpyAsync(axy.data(), T.asg_xy, (size_t)m * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-    std::vector<int> abot((size_t)m);
-    if (m) HIPCHK(c, hipMemcpyAsync(abot.data(), T.pair_bot, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (m) HIPCHK(c, hipMemcpyAsync(H.pair_bot.data(), S.pair_bot, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < n_bots; b++) {
-        target_idx[b] = tidx[b];
-        target_xy[2 * b] = target_xy[2 * b + 1] = NAN;
-        cost[b] = tcost[b];
-        status[b] = tstat[b];
-        if (wp_xy) {
-            wp_cell_xy[2 * b] = wp_cell_xy[2 * b + 1] = -1;
-            wp_xy[2 * b] = wp_xy[2 * b + 1] = NAN;
-        }
-    }
-    for (int i = 0; i < m; i++) {
-        const int b = abot[i];
-        if (b < 0 || b >= (int)n_bots || tidx[b] < 0) return qs_fail(c, QS_E_STATE, (who + ": assignment list is inconsistent").c_str());
-        target_xy[2 * b] = axy[i].x; target_xy[2 * b + 1] = axy[i].y;
-        if (!wp_xy) continue;
-        const int4 o = out[i];
-        // both ends have cells and the cost is finite: the walk cannot fail, and its cost is the bot field's (symmetric moves)
-        if (o.x != QS_PLAN_OK || (unsigned int)o.w != tcost[b]) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "%s: bot %d: the waypoint's path (status %d, cost %u) disagrees "
-                     "with the assignment's cost %u", who.c_str(), b, o.x, (unsigned int)o.w, tcost[b]);
-            return qs_fail(c, QS_E_STATE, msg);
-        }
-        wp_cell_xy[2 * b] = o.y; wp_cell_xy[2 * b + 1] = o.z;
-        wp_xy[2 * b] = c->cfg.ox + (o.y + 0.5) * c->cfg.res;        // grid_to_world :127-131
-        wp_xy[2 * b + 1] = c->cfg.oy + (o.z + 0.5) * c->cfg.res;
-    }
+    for (int i = 0; i < m; i++)                          // the targets' positions into bot order (tbp_finish refuses a bot out of range)
+        if (H.pair_bot[i] >= 0 && H.pair_bot[i] < (int)n_bots) H.xy[H.pair_bot[i]] = axy[i];
+    rc = tbp_finish(c, who, "assignment's", H, (size_t)m, o);
+    if (rc != QS_OK) return rc;
     if (n_centroids) *n_centroids = n_cent;
     if (stats) {
         stats[0] = n_cent; stats[1] = count[0]; stats[2] = count[1]; stats[3] = groups;
@@ -447,8 +436,8 @@ extern "C" int qs_frontier_targets_by_path(qs_ctx *c, int32_t min_cluster, doubl
                                            double *centroids_xy, size_t cap, size_t *n_centroids, uint64_t stats[8])
 {
     return tbp_run<TpEntry>(c, "qs_frontier_targets_by_path", min_cluster, separation, params,
-                            [](void *, size_t, TpNoAux &) { return (int)QS_OK; }, bot_xy, n_bots, target_idx, target_xy, cost, status,
-                            wp_cell_xy, wp_xy, centroids_xy, cap, n_centroids, stats);
+                            [](void *, size_t, TpNoAux &) { return (int)QS_OK; }, bot_xy, n_bots,
+                            {target_idx, target_xy, cost, status, wp_cell_xy, wp_xy}, centroids_xy, cap, n_centroids, stats);
 }
 
 // §4.17: the same stages ordered by G6; the gains (gain.hip) are computed while the frontier workspace is still labelled
@@ -476,7 +465,7 @@ extern "C" int qs_frontier_targets_by_gain(qs_ctx *c, int32_t min_cluster, doubl
             if (n_cent) HIPCHK(c, hipMemcpyAsync(hgain.data(), G.gain, n_cent * sizeof(int), hipMemcpyDeviceToHost, c->stream));
             aux = GnAux{G.gain, g.bias};
             return (int)QS_OK;
-        }, bot_xy, n_bots, target_idx, target_xy, cost, status, wp_cell_xy, wp_xy, centroids_xy, cap, n_centroids, stats);
+        }, bot_xy, n_bots, {target_idx, target_xy, cost, status, wp_cell_xy, wp_xy}, centroids_xy, cap, n_centroids, stats);
     if (rc != QS_OK) return rc;
     for (size_t b = 0; b < n_bots; b++) target_gain[b] = target_idx[b] >= 0 ? hgain[(size_t)target_idx[b]] : 0;
     if (stats) for (int v : hgain) stats[7] += (uint64_t)v;

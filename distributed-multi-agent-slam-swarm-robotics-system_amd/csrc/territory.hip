@@ -1,7 +1,7 @@
 // territory.hip -- the mapped free space partitioned among the bots by path cost.
 // The rules are this build's own (include/quasar_slam.h, "territories"), all integer.  The mask, the census, the snap, the
-// worklist ring and the waypoint stage are plan.hip's (plan_common.h); the centroids are frontier_targets.hip's and their
-// field offsets targets_by_path.hip's.  New here:
+// worklist ring and the waypoint stage are plan.hip's (plan_common.h); the centroids are frontier_targets.hip's, their field
+// offsets, the argument check and the per-bot epilogue targets_by_path.hip's.  New here:
 //
 //   seed     : ONE field over the bounding box of the census, of 64-bit keys (cost << 32) | bot.  Every bot with a cell
 //              writes key = bot at its cell by atomicMin (bots that share a cell: the lowest stays) and enters its tile,
@@ -16,10 +16,9 @@
 //              issues one 64-bit atomicAdd and four atomicMin / atomicMax.  Integer atomics: the result is exact;
 //   centroids: gather key at each centroid's field offset; atomicMin of (cost << 32) | k into the owner's slot; one wave
 //              turns the slots into targets and the (start, goal) pairs of the assigned bots, in bot order;
-//   waypoints: the body of qs_plan_paths for those pairs, as qs_frontier_targets_by_path runs it.
+//   waypoints: plan.hip's waypoint stage for those pairs, as qs_frontier_targets_by_path runs it.
 // No device-side waits, no grid-wide barriers, no graphs.
 #include <math.h>
-#include <stdio.h>
 #include <algorithm>
 
 #include "territory_layout.h"
@@ -27,7 +26,6 @@
 static_assert(PL_T == QS_WAVE, "one lane per cell of a tile row");
 
 #define TK_INF 0xffffffffffffffffull
-#define TK_NOCELL 0xffffffffu         // targets_by_path.hip's TP_NOCELL
 
 // ---- per-bot state of a call: empty slot, no cells, the empty box as the identities of min and max ------------------
 __global__ void __launch_bounds__(PL_BLOCK)
@@ -113,7 +111,7 @@ qs_terr_gather_kernel(const unsigned long long *__restrict__ key, const unsigned
     unsigned long long v = TK_INF;
     if (k < n_cent) {
         const unsigned int o = coff[k];
-        if (o != TK_NOCELL) v = key[o];
+        if (o != TP_NOCELL) v = key[o];
         cent_owner[k] = v == TK_INF ? -1 : (int)(unsigned int)v;
         cent_cost[k] = v == TK_INF ? PL_INF : (unsigned int)(v >> 32);
         if (v != TK_INF) atomicMin(&slot[(unsigned int)v], (v & 0xffffffff00000000ull) | (unsigned int)k);
@@ -157,15 +155,16 @@ qs_terr_targets_kernel(const unsigned long long *__restrict__ slot, const double
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-// What both entry points share: the mask and the census, the cells of the centroids (T.xy[0 .. n_cent), already on the
+// What both entry points share: the mask and the census, the cells of the centroids (T.tg.xy[0 .. n_cent), already on the
 // device) and of the bots, the partition, and area / box / owner / cost.  bcell: the bots' cells, on the host.
 static int terr_partition(qs_ctx *c, const qs_plan_params &p, const QsTerrLayout &T, const double *bot_xy, size_t n_cent,
                           size_t n_bots, QsPlanLayout &L, unsigned int bbox[4], std::vector<long long> &bcell)
 {
     int rc = plan_begin(c, p.clearance, std::max(n_bots, (size_t)1), 0, L, bbox);
     if (rc != QS_OK) return rc;
+    const QsTgtLayout &S = T.tg;
     const size_t cells = (size_t)c->cfg.size * c->cfg.size, n_end = n_cent + n_bots;
-    HIPCHK(c, hipMemsetAsync(T.count, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.count, 0, 4 * sizeof(unsigned long long), c->stream));
     if (T.owner) HIPCHK(c, hipMemsetAsync(T.owner, 0xff, cells * sizeof(short), c->stream));            // -1
     if (T.cost) HIPCHK(c, hipMemsetAsync(T.cost, 0xff, cells * sizeof(unsigned int), c->stream));       // unreached
     if (n_bots) {
@@ -180,16 +179,16 @@ static int terr_partition(qs_ctx *c, const qs_plan_params &p, const QsTerrLayout
     if (fcells > T.field_cells || tiles > L.item_cap) return qs_fail(c, QS_E_STATE, "territories: the census box exceeds the workspace");
     HIPCHK(c, hipMemsetAsync(T.key, 0xff, fcells * sizeof(unsigned long long), c->stream));
     if (n_end) {
-        if (n_bots) HIPCHK(c, hipMemcpyAsync(T.xy + n_cent, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, qs_launch_plan_snap(c, L, T.xy, T.cell, n_end, p.snap_radius, L.stats + 3));
-        HIPCHK(c, qs_launch_tbp_offsets(c, T.cell, n_cent, n_bots, bbox, T.coff, T.count));
+        if (n_bots) HIPCHK(c, hipMemcpyAsync(S.xy + n_cent, bot_xy, n_bots * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, qs_launch_plan_snap(c, L, S.xy, S.cell, n_end, p.snap_radius, L.stats + 3));
+        HIPCHK(c, qs_launch_tbp_offsets(c, S.cell, n_cent, n_bots, bbox, S.coff, S.count));
     }
     if (!n_bots) return QS_OK;
-    HIPCHK(c, hipMemcpyAsync(bcell.data(), T.cell + n_cent, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(bcell.data(), S.cell + n_cent, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemsetAsync(L.marks, 0, tiles * sizeof(unsigned int), c->stream));
     HIPCHK(c, hipMemsetAsync(L.cnt, 0, 3 * sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(qs_terr_seed_kernel, dim3((unsigned int)((n_bots + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, c->stream,
-                       T.cell + n_cent, (int)n_bots, c->cfg.size, B, L.tile_any, L.gtx, T.key, L.list1, L.cnt, L.marks);
+                       S.cell + n_cent, (int)n_bots, c->cfg.size, B, L.tile_any, L.gtx, T.key, L.list1, L.cnt, L.marks);
     HIPCHK(c, hipGetLastError());
     rc = plan_rounds_key64(c, L, bbox, T.key);
     if (rc != QS_OK) return rc;
@@ -247,7 +246,7 @@ extern "C" int qs_territories(qs_ctx *c, const qs_plan_params *params, const dou
     if (owner_host) HIPCHK(c, hipMemcpyAsync(owner_host, T.owner, cells * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     if (cost_host) HIPCHK(c, hipMemcpyAsync(cost_host, T.cost, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(st, L.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, T.tg.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
     uint64_t owned = 0;
     rc = terr_per_bot(c, T, bcell, bbox[0] <= bbox[2], status, area, box, owned);
     if (rc != QS_OK) return rc;
@@ -264,28 +263,21 @@ extern "C" int qs_frontier_targets_by_territory(qs_ctx *c, int32_t min_cluster, 
                                                 double *centroids_xy, int32_t *centroid_owner, size_t cap, size_t *n_centroids,
                                                 uint64_t stats[8])
 {
-    ARGCHK(c, c != nullptr);
-    if (n_bots > QS_FT_MAX_BOTS) return qs_fail(c, QS_E_INVAL, "qs_frontier_targets_by_territory: n_bots above QS_FT_MAX_BOTS");
-    ARGCHK(c, n_bots == 0 || (bot_xy && target_idx && target_xy && cost && status && area && box));
-    ARGCHK(c, (wp_cell_xy == nullptr) == (wp_xy == nullptr));
-    ARGCHK(c, cap == 0 || centroids_xy);
+    static const char who[] = "qs_frontier_targets_by_territory";
+    const QsTargetsOut o{target_idx, target_xy, cost, status, wp_cell_xy, wp_xy};
     qs_plan_params p;
-    int rc = plan_params(c, params, p);
+    int rc = tbp_check_args(c, who, n_bots, bot_xy, o, centroids_xy, cap, params, p);
     if (rc != QS_OK) return rc;
+    ARGCHK(c, n_bots == 0 || (area && box));
     // the centroids (frontier_targets.hip's), counted first
-    HIPCHK(c, hipSetDevice(c->device));
-    SYNCCHK(c);
-    HIPCHK(c, c->frontier_ws.reserve(qs_frontier_layout(c, nullptr).bytes, c->stream));
-    void *fws = c->frontier_ws.p;
-    HIPCHK(c, qs_launch_frontier_label(c, fws, true));
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 0, nullptr));
-    unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, qs_frontier_layout(c, fws).total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t n_cent = (size_t)total;
+    void *fws;
+    size_t n_cent;
+    rc = qs_count_centroids(c, min_cluster, fws, n_cent);
+    if (rc != QS_OK) return rc;
     HIPCHK(c, c->terr_ws.reserve(qs_terr_layout(nullptr, c->cfg.size, n_cent, n_bots, false, false).bytes, c->stream));
     const QsTerrLayout T = qs_terr_layout(c->terr_ws.p, c->cfg.size, n_cent, n_bots, false, false);
-    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, T.xy));
+    const QsTgtLayout &S = T.tg;
+    HIPCHK(c, qs_launch_ft_centroids(c, fws, min_cluster, 1, S.xy));
     // the partition, then who owns each centroid and each bot's cheapest
     QsPlanLayout L;
     unsigned int bbox[4];
@@ -295,15 +287,10 @@ extern "C" int qs_frontier_targets_by_territory(qs_ctx *c, int32_t min_cluster, 
     const bool any_trav = bbox[0] <= bbox[2];
     const size_t nc = n_cent < cap ? n_cent : cap;
     unsigned long long count[4] = {0, 0, 0, 0}, st[4] = {0, 0, 0, 0};
-    std::vector<long long> tidx(n_bots, -1);
-    std::vector<unsigned int> tcost(n_bots, PL_INF);
-    std::vector<int> tstat(n_bots, QS_PLAN_NO_START), abot;
-    std::vector<double2> txy(n_bots, make_double2(NAN, NAN));
-    std::vector<int4> out;
-    size_t m = 0;
+    QsTargetsHost H(n_bots);
     if (any_trav && n_cent) {
         hipLaunchKernelGGL(qs_terr_gather_kernel, dim3((unsigned int)((n_cent + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0,
-                           c->stream, T.key, T.coff, (int)n_cent, T.cent_owner, T.cent_cost, T.slot, T.count);
+                           c->stream, T.key, S.coff, (int)n_cent, T.cent_owner, T.cent_cost, T.slot, S.count);
         HIPCHK(c, hipGetLastError());
         if (centroid_owner && nc)
             HIPCHK(c, hipMemcpyAsync(centroid_owner, T.cent_owner, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -311,63 +298,32 @@ extern "C" int qs_frontier_targets_by_territory(qs_ctx *c, int32_t min_cluster, 
         std::fill(centroid_owner, centroid_owner + nc, -1);
     }
     if (any_trav && n_bots) {
-        hipLaunchKernelGGL(qs_terr_targets_kernel, dim3(1), dim3(64), 0, c->stream, T.slot, T.xy, T.cell, (int)n_cent, (int)n_bots,
-                           T.tgt_idx, T.tgt_xy, T.tgt_cost, T.tgt_status, T.pair, T.pair_bot, T.count);
+        hipLaunchKernelGGL(qs_terr_targets_kernel, dim3(1), dim3(64), 0, c->stream, T.slot, S.xy, S.cell, (int)n_cent, (int)n_bots,
+                           S.tgt_idx, T.tgt_xy, S.tgt_cost, S.tgt_status, S.pair, S.pair_bot, S.count);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(tidx.data(), T.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(tcost.data(), T.tgt_cost, n_bots * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(tstat.data(), T.tgt_status, n_bots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(txy.data(), T.tgt_xy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.idx.data(), S.tgt_idx, n_bots * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.cost.data(), S.tgt_cost, n_bots * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.status.data(), S.tgt_status, n_bots * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.xy.data(), T.tgt_xy, n_bots * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     }
-    if (any_trav) HIPCHK(c, hipMemcpyAsync(count, T.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    if (any_trav) HIPCHK(c, hipMemcpyAsync(count, S.count, sizeof count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    m = (size_t)count[3];
+    const size_t m = (size_t)count[3];
     if (m > n_bots) return qs_fail(c, QS_E_STATE, "qs_frontier_targets_by_territory: assignment list is inconsistent");
-    // waypoints: qs_plan_paths' fields and walks for the m assigned pairs (starts pair[0..m), goals pair[n_bots ..))
-    if (wp_xy && m) {
-        out.assign(m, make_int4(0, -1, -1, -1));
-        abot.assign(m, -1);
-        const size_t g = qs_plan_group(L, bbox, m);
-        if (g == 0) return qs_fail(c, QS_E_STATE, "qs_frontier_targets_by_territory: workspace holds no field");
-        for (size_t g0 = 0; g0 < m; g0 += g) {
-            const size_t gn = std::min(g, m - g0);
-            rc = plan_fields(c, L, bbox, T.pair, T.pair + n_bots, g0, gn);
-            if (rc != QS_OK) return rc;
-            HIPCHK(c, qs_launch_plan_walk(c, L, bbox, T.pair, T.pair + n_bots, g0, gn, p.lookahead, 0));
-        }
-        HIPCHK(c, hipMemcpyAsync(out.data(), L.out4, m * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(abot.data(), T.pair_bot, m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    const bool walk = wp_xy && m;
+    if (walk) {
+        uint64_t groups = 0;                              // (not among this call's stats)
+        rc = plan_waypoints(c, who, L, bbox, S.pair, S.pair + n_bots, m, p.lookahead, 0, groups, H.out4.data());
+        if (rc != QS_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(H.pair_bot.data(), S.pair_bot, m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     }
-    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, T.xy, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    if (nc) HIPCHK(c, hipMemcpyAsync(centroids_xy, S.xy, nc * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(st, L.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
     uint64_t owned = 0;
     rc = terr_per_bot(c, T, bcell, any_trav, nullptr, area, box, owned);
     if (rc != QS_OK) return rc;
-    for (size_t b = 0; b < n_bots; b++) {
-        target_idx[b] = tidx[b];
-        target_xy[2 * b] = txy[b].x; target_xy[2 * b + 1] = txy[b].y;
-        cost[b] = tcost[b];
-        status[b] = tstat[b];
-        if (wp_xy) {
-            wp_cell_xy[2 * b] = wp_cell_xy[2 * b + 1] = -1;
-            wp_xy[2 * b] = wp_xy[2 * b + 1] = NAN;
-        }
-    }
-    for (size_t i = 0; i < out.size(); i++) {
-        const int b = abot[i];
-        if (b < 0 || b >= (int)n_bots || tidx[b] < 0) return qs_fail(c, QS_E_STATE, "qs_frontier_targets_by_territory: assignment list is inconsistent");
-        const int4 o = out[i];
-        // both ends have cells and the cost is finite: the walk cannot fail, and its cost is the partition's (symmetric moves)
-        if (o.x != QS_PLAN_OK || (unsigned int)o.w != tcost[b]) {
-            char msg[176];
-            snprintf(msg, sizeof msg, "qs_frontier_targets_by_territory: bot %d: the waypoint's path (status %d, cost %u) disagrees "
-                     "with the partition's cost %u", b, o.x, (unsigned int)o.w, tcost[b]);
-            return qs_fail(c, QS_E_STATE, msg);
-        }
-        wp_cell_xy[2 * b] = o.y; wp_cell_xy[2 * b + 1] = o.z;
-        wp_xy[2 * b] = c->cfg.ox + (o.y + 0.5) * c->cfg.res;        // grid_to_world :127-131
-        wp_xy[2 * b + 1] = c->cfg.oy + (o.z + 0.5) * c->cfg.res;
-    }
+    rc = tbp_finish(c, who, "partition's", H, walk ? m : 0, o);      // (no walk: the pairs' bots stayed on the device)
+    if (rc != QS_OK) return rc;
     if (n_centroids) *n_centroids = n_cent;
     if (stats) {
         stats[0] = st[0]; stats[1] = st[1]; stats[2] = count[1]; stats[3] = owned;

@@ -9,6 +9,7 @@ marshals buffers (numpy <-> C ABI).
 import ctypes as C
 import os
 import struct
+import types
 import zlib
 
 import numpy as np
@@ -897,23 +898,34 @@ class QuasarMapper:
             out.append((self.ox + (ax + 0.5) * self.res, self.oy + (ay + 0.5) * self.res))
         return out
 
+    def _bot_array(self, who, bot_xy):
+        """bot_xy as float64 [n, 2]; more than QS_FT_MAX_BOTS bots are refused in the name of `who`."""
+        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        if len(b) > _lib.QS_FT_MAX_BOTS:
+            raise ValueError(f"{who}: at most {_lib.QS_FT_MAX_BOTS} bots per call")
+        return b
+
+    def _centroid_buffer(self, min_cluster, wanted):
+        """(float64 [k, 2], k) for a target call asked to hand back the centroids, else (None, 0).  The count comes first: a
+        second call would observe the same map."""
+        if not wanted:
+            return None, 0
+        k = C.c_size_t()
+        self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
+        return np.zeros((k.value, 2), dtype=np.float64), k.value
+
     def frontier_targets(self, bot_xy, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
                          return_centroids=False):
         """The greedy frontier assignment of dual_bot_mapper.py:958-992 on the device.  bot_xy: [n, 2] positions in
         greedy order.  Returns (idx int64 [n]: index into frontier_centroids(min_cluster), -1 = no target;
         xy float64 [n, 2]: that centroid, NaN where idx is -1), plus (centroids float64 [k, 2], stats dict) on request."""
-        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        b = self._bot_array("frontier_targets", bot_xy)
         n = len(b)
-        if n > _lib.QS_FT_MAX_BOTS:
-            raise ValueError(f"frontier_targets: at most {_lib.QS_FT_MAX_BOTS} bots per call")
         idx = np.full(n, -1, dtype=np.int64)
         xy = np.full((n, 2), np.nan, dtype=np.float64)
         st = np.zeros(4, dtype=np.uint64)
         k = C.c_size_t()
-        cents, cap = None, 0
-        if return_centroids:       # the count first: a second call would observe the same map
-            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
-            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
+        cents, cap = self._centroid_buffer(min_cluster, return_centroids)
         self._chk(self._L.qs_frontier_targets(self._h, min_cluster, float(separation), _ptr(b), n, _ptr(idx), _ptr(xy),
                                               _ptr(cents) if cap else None, cap, C.byref(k), _ptr(st)),
                   "qs_frontier_targets")
@@ -937,36 +949,64 @@ class QuasarMapper:
             raise ValueError("assign_frontier_targets: by_path, by_territory and by_gain exclude each other")
         if return_territory and not by_territory:
             raise ValueError("assign_frontier_targets: return_territory needs by_territory=True")
-        if by_territory:
-            bots = sorted(bot_states)
-            res = self.frontier_targets_by_territory([bot_states[b] for b in bots], min_cluster, waypoints=return_waypoints,
-                                                     **plan_params) if bots else None
-            got = [(i, b) for i, b in enumerate(bots) if res["idx"][i] >= 0]
-            out = [{b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}]
-            if return_waypoints:
-                out.append({b: (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1])) for i, b in got})
-            if return_territory:
-                out.append({b: (int(res["area"][i]), tuple(int(v) for v in res["box"][i]) if res["area"][i] else None)
-                            for i, b in enumerate(bots)})
-            return out[0] if len(out) == 1 else tuple(out)
-        if not by_path and not by_gain:
-            if return_waypoints or plan_params:
-                raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True or by_gain=True")
-            bots = sorted(bot_states)
-            if not bots:
-                return {}
-            idx, xy = self.frontier_targets([bot_states[b] for b in bots], separation, min_cluster)
-            return {b: (float(xy[i, 0]), float(xy[i, 1])) for i, b in enumerate(bots) if idx[i] >= 0}
+        plain = not (by_path or by_territory or by_gain)
+        if plain and (return_waypoints or plan_params):
+            raise ValueError("assign_frontier_targets: waypoints and plan parameters need by_path=True or by_gain=True")
         bots = sorted(bot_states)
+        pos = [bot_states[b] for b in bots]
         if not bots:
-            return ({}, {}) if return_waypoints else {}
-        call = self.frontier_targets_by_gain if by_gain else self.frontier_targets_by_path
-        res = call([bot_states[b] for b in bots], separation, min_cluster, waypoints=return_waypoints, **plan_params)
+            res = None                 # (no call: nothing below looks at it)
+        elif plain:
+            res = dict(zip(("idx", "xy"), self.frontier_targets(pos, separation, min_cluster)))
+        elif by_territory:
+            res = self.frontier_targets_by_territory(pos, min_cluster, waypoints=return_waypoints, **plan_params)
+        else:
+            call = self.frontier_targets_by_gain if by_gain else self.frontier_targets_by_path
+            res = call(pos, separation, min_cluster, waypoints=return_waypoints, **plan_params)
         got = [(i, b) for i, b in enumerate(bots) if res["idx"][i] >= 0]
-        targets = {b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}
-        if not return_waypoints:
-            return targets
-        return targets, {b: (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1])) for i, b in got}
+        out = [{b: (float(res["xy"][i, 0]), float(res["xy"][i, 1])) for i, b in got}]
+        if return_waypoints:
+            out.append({b: (float(res["waypoint"][i, 0]), float(res["waypoint"][i, 1])) for i, b in got})
+        if return_territory:
+            out.append({b: (int(res["area"][i]), tuple(int(v) for v in res["box"][i]) if res["area"][i] else None)
+                        for i, b in enumerate(bots)})
+        return out[0] if len(out) == 1 else tuple(out)
+
+    _PATH_STATS = ("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits", "fallbacks")
+    _TERRITORY_STATS = ("rounds", "tile_visits", "bot_cells", "owned_cells", "n_centroids", "centroid_cells", "centroids_owned",
+                        "reserved")
+
+    def _path_cost_targets(self, who, call, bot_xy, min_cluster, plan, return_centroids, waypoints, stat_names,
+                           per_bot=(), per_centroid=()):
+        """What frontier_targets_by_path, _by_gain and _by_territory do alike round their one C call: the bots, the plan
+        parameters (clearance, snap_radius, lookahead), the per-bot output arrays, the centroid buffers on request, then
+        call(a) and the result dict.  a holds the C call's arguments: prm, bots (bot_xy, n, then the six per-bot arrays,
+        the two waypoint ones None without waypoints), cents, cap, k, st, and one pointer for each name in per_bot
+        {name: (dtype, fill, shape after n)} and per_centroid {name: (dtype, fill)}, which also become keys of the result."""
+        b = self._bot_array(who, bot_xy)
+        n = len(b)
+        prm = self._plan_params(*plan)
+        out = dict(idx=np.full(n, -1, dtype=np.int64), xy=np.full((n, 2), np.nan, dtype=np.float64),
+                   cost=np.full(n, 0xFFFFFFFF, dtype=np.uint32), status=np.zeros(n, dtype=np.int32),
+                   waypoint_cell=np.full((n, 2), -1, dtype=np.int32), waypoint=np.full((n, 2), np.nan, dtype=np.float64))
+        a = types.SimpleNamespace(prm=C.byref(prm), bots=[_ptr(b), n] + [_ptr(out[key]) for key in ("idx", "xy", "cost", "status")])
+        a.bots += [_ptr(out[key]) if waypoints else None for key in ("waypoint_cell", "waypoint")]
+        for name, (dtype, fill, shape) in dict(per_bot).items():
+            out[name] = np.full((n,) + shape, fill, dtype=dtype)
+            setattr(a, name, _ptr(out[name]))
+        st = np.zeros(8, dtype=np.uint64)
+        k = C.c_size_t()
+        cents, cap = self._centroid_buffer(min_cluster, return_centroids)
+        per_c = {name: np.full(cap, fill, dtype=dtype) for name, (dtype, fill) in dict(per_centroid).items()}
+        a.cents, a.cap, a.k, a.st = _ptr(cents) if cap else None, cap, C.byref(k), _ptr(st)
+        for name, arr in per_c.items():
+            setattr(a, name, _ptr(arr) if cap else None)
+        self._chk(call(a), "qs_" + who)
+        out["stats"] = dict(zip(stat_names, (int(v) for v in st)))
+        if return_centroids:
+            out["centroids"] = cents[:k.value]
+            out.update((name, arr[:k.value]) for name, arr in per_c.items())
+        return out
 
     def frontier_targets_by_path(self, bot_xy, separation=P.FRONTIER_SEPARATION, min_cluster=P.FRONTIER_MIN_CLUSTER,
                                  clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS, lookahead=P.PLAN_LOOKAHEAD,
@@ -977,33 +1017,10 @@ class QuasarMapper:
         (NaN where none), cost uint32 [n], status int32 [n] (QS_PLAN_OK / _NO_START / _UNREACHABLE), waypoint_cell int32
         [n, 2] and waypoint float64 [n, 2] (what plan_paths(bot, target) returns; -1 / NaN where none or with
         waypoints=False, which skips that stage), stats; with return_centroids also centroids float64 [k, 2]."""
-        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
-        n = len(b)
-        if n > _lib.QS_FT_MAX_BOTS:
-            raise ValueError(f"frontier_targets_by_path: at most {_lib.QS_FT_MAX_BOTS} bots per call")
-        prm = self._plan_params(clearance, snap_radius, lookahead)
-        idx = np.full(n, -1, dtype=np.int64)
-        xy = np.full((n, 2), np.nan, dtype=np.float64)
-        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
-        status = np.zeros(n, dtype=np.int32)
-        wc = np.full((n, 2), -1, dtype=np.int32)
-        wxy = np.full((n, 2), np.nan, dtype=np.float64)
-        st = np.zeros(8, dtype=np.uint64)
-        k = C.c_size_t()
-        cents, cap = None, 0
-        if return_centroids:       # the count first: a second call would observe the same map
-            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
-            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
-        self._chk(self._L.qs_frontier_targets_by_path(
-            self._h, min_cluster, float(separation), C.byref(prm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost), _ptr(status),
-            _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(cents) if cap else None, cap,
-            C.byref(k), _ptr(st)), "qs_frontier_targets_by_path")
-        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy,
-                   stats=dict(zip(("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits",
-                                   "fallbacks", "reserved"), (int(v) for v in st))))
-        if return_centroids:
-            out["centroids"] = cents[:k.value]
-        return out
+        return self._path_cost_targets(
+            "frontier_targets_by_path", lambda a: self._L.qs_frontier_targets_by_path(
+                self._h, min_cluster, float(separation), a.prm, *a.bots, a.cents, a.cap, a.k, a.st),
+            bot_xy, min_cluster, (clearance, snap_radius, lookahead), return_centroids, waypoints, self._PATH_STATS + ("reserved",))
 
     # -- frontier gain (include/quasar_slam.h, "frontier gain"; no reference counterpart) --------------------------
     def frontier_gain(self, min_cluster=P.FRONTIER_MIN_CLUSTER, range=_lib.QS_GAIN_DEFAULT_RANGE):
@@ -1025,35 +1042,12 @@ class QuasarMapper:
         """frontier_targets_by_path with the centroids ordered by gain over cost (include/quasar_slam.h, "frontier gain",
         G6): a bot takes the eligible centroid k with the smallest (cost + gain_bias) / gain[k].  Returns that call's dict
         plus gain int32 [n] (the gain of each bot's target, 0 where none); stats["gain_sum"] is the sum of all gains."""
-        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
-        n = len(b)
-        if n > _lib.QS_FT_MAX_BOTS:
-            raise ValueError(f"frontier_targets_by_gain: at most {_lib.QS_FT_MAX_BOTS} bots per call")
-        prm = self._plan_params(clearance, snap_radius, lookahead)
         gprm = _lib.QsGainParams(int(gain_range), int(gain_bias), (0, 0))
-        idx = np.full(n, -1, dtype=np.int64)
-        xy = np.full((n, 2), np.nan, dtype=np.float64)
-        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
-        status = np.zeros(n, dtype=np.int32)
-        wc = np.full((n, 2), -1, dtype=np.int32)
-        wxy = np.full((n, 2), np.nan, dtype=np.float64)
-        gain = np.zeros(n, dtype=np.int32)
-        st = np.zeros(8, dtype=np.uint64)
-        k = C.c_size_t()
-        cents, cap = None, 0
-        if return_centroids:       # the count first: a second call would observe the same map
-            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
-            cents, cap = np.zeros((k.value, 2), dtype=np.float64), k.value
-        self._chk(self._L.qs_frontier_targets_by_gain(
-            self._h, min_cluster, float(separation), C.byref(prm), C.byref(gprm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost),
-            _ptr(status), _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(cents) if cap else None, cap,
-            C.byref(k), _ptr(gain), _ptr(st)), "qs_frontier_targets_by_gain")
-        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy, gain=gain,
-                   stats=dict(zip(("n_centroids", "centroid_cells", "bot_cells", "groups", "rounds", "tile_visits",
-                                   "fallbacks", "gain_sum"), (int(v) for v in st))))
-        if return_centroids:
-            out["centroids"] = cents[:k.value]
-        return out
+        return self._path_cost_targets(
+            "frontier_targets_by_gain", lambda a: self._L.qs_frontier_targets_by_gain(
+                self._h, min_cluster, float(separation), a.prm, C.byref(gprm), *a.bots, a.cents, a.cap, a.k, a.gain, a.st),
+            bot_xy, min_cluster, (clearance, snap_radius, lookahead), return_centroids, waypoints, self._PATH_STATS + ("gain_sum",),
+            per_bot=dict(gain=(np.int32, 0, ())))
 
     # -- territories (include/quasar_slam.h, "territories"; no reference counterpart) ----------------------------
     def territories(self, bot_xy, clearance=P.PLAN_CLEARANCE, snap_radius=P.PLAN_SNAP_RADIUS, return_owner=False,
@@ -1063,10 +1057,8 @@ class QuasarMapper:
         owned), box int32 [n, 4] (min gx, min gy, max gx, max gy; -1 where area is 0), stats; with return_owner also owner
         int16 [size, size] indexed [gy, gx] (-1 = nobody's), with return_cost also cost uint32 [size, size] (0xFFFFFFFF
         there)."""
-        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
+        b = self._bot_array("territories", bot_xy)
         n = len(b)
-        if n > _lib.QS_FT_MAX_BOTS:
-            raise ValueError(f"territories: at most {_lib.QS_FT_MAX_BOTS} bots per call")
         prm = self._plan_params(clearance, snap_radius, P.PLAN_LOOKAHEAD)
         status = np.zeros(n, dtype=np.int32)
         area = np.zeros(n, dtype=np.int64)
@@ -1077,17 +1069,12 @@ class QuasarMapper:
         self._chk(self._L.qs_territories(self._h, C.byref(prm), _ptr(b), n, _ptr(owner) if return_owner else None,
                                          _ptr(cost) if return_cost else None, _ptr(status), _ptr(area), _ptr(box), _ptr(st)),
                   "qs_territories")
-        out = dict(status=status, area=area, box=box, stats=self._territory_stats(st))
+        out = dict(status=status, area=area, box=box, stats=dict(zip(self._TERRITORY_STATS, (int(v) for v in st))))
         if return_owner:
             out["owner"] = owner
         if return_cost:
             out["cost"] = cost
         return out
-
-    @staticmethod
-    def _territory_stats(st):
-        return dict(zip(("rounds", "tile_visits", "bot_cells", "owned_cells", "n_centroids", "centroid_cells",
-                         "centroids_owned", "reserved"), (int(v) for v in st)))
 
     def frontier_targets_by_territory(self, bot_xy, min_cluster=P.FRONTIER_MIN_CLUSTER, clearance=P.PLAN_CLEARANCE,
                                       snap_radius=P.PLAN_SNAP_RADIUS, lookahead=P.PLAN_LOOKAHEAD, return_centroids=False,
@@ -1096,36 +1083,11 @@ class QuasarMapper:
         smallest (cost, index) among those whose cell it owns; there is no separation rule.  Returns the keys of
         frontier_targets_by_path (idx, xy, cost, status, waypoint_cell, waypoint, stats) plus area int64 [n] and box int32
         [n, 4]; with return_centroids also centroids float64 [k, 2] and centroid_owner int32 [k] (-1 = nobody's)."""
-        b = np.ascontiguousarray(bot_xy, dtype=np.float64).reshape(-1, 2)
-        n = len(b)
-        if n > _lib.QS_FT_MAX_BOTS:
-            raise ValueError(f"frontier_targets_by_territory: at most {_lib.QS_FT_MAX_BOTS} bots per call")
-        prm = self._plan_params(clearance, snap_radius, lookahead)
-        idx = np.full(n, -1, dtype=np.int64)
-        xy = np.full((n, 2), np.nan, dtype=np.float64)
-        cost = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
-        status = np.zeros(n, dtype=np.int32)
-        wc = np.full((n, 2), -1, dtype=np.int32)
-        wxy = np.full((n, 2), np.nan, dtype=np.float64)
-        area = np.zeros(n, dtype=np.int64)
-        box = np.full((n, 4), -1, dtype=np.int32)
-        st = np.zeros(8, dtype=np.uint64)
-        k = C.c_size_t()
-        cents, cown, cap = None, None, 0
-        if return_centroids:       # the count first: a second call would observe the same map
-            self._chk(self._L.qs_frontier_clusters(self._h, min_cluster, None, 0, C.byref(k)), "qs_frontier_clusters")
-            cents, cown, cap = np.zeros((k.value, 2), dtype=np.float64), np.full(k.value, -1, dtype=np.int32), k.value
-        self._chk(self._L.qs_frontier_targets_by_territory(
-            self._h, min_cluster, C.byref(prm), _ptr(b), n, _ptr(idx), _ptr(xy), _ptr(cost), _ptr(status),
-            _ptr(wc) if waypoints else None, _ptr(wxy) if waypoints else None, _ptr(area), _ptr(box),
-            _ptr(cents) if cap else None, _ptr(cown) if cap else None, cap, C.byref(k), _ptr(st)),
-            "qs_frontier_targets_by_territory")
-        out = dict(idx=idx, xy=xy, cost=cost, status=status, waypoint_cell=wc, waypoint=wxy, area=area, box=box,
-                   stats=self._territory_stats(st))
-        if return_centroids:
-            out["centroids"] = cents[:k.value]
-            out["centroid_owner"] = cown[:k.value]
-        return out
+        return self._path_cost_targets(
+            "frontier_targets_by_territory", lambda a: self._L.qs_frontier_targets_by_territory(
+                self._h, min_cluster, a.prm, *a.bots, a.area, a.box, a.cents, a.centroid_owner, a.cap, a.k, a.st),
+            bot_xy, min_cluster, (clearance, snap_radius, lookahead), return_centroids, waypoints, self._TERRITORY_STATS,
+            per_bot=dict(area=(np.int64, 0, ()), box=(np.int32, -1, (4,))), per_centroid=dict(centroid_owner=(np.int32, -1)))
 
     # -- path planning (include/quasar_slam.h, "path planning"; no reference counterpart) ----------------------
     def traversable(self, clearance=P.PLAN_CLEARANCE):

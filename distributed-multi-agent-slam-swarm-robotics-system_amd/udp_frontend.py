@@ -62,18 +62,12 @@ class MissionControl:
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
                  targets_by_territory=False, targets_by_gain=False, gain_params=None):
-        if plan_paths and not frontier_targets:
-            raise ValueError("MissionControl: plan_paths=True needs frontier_targets=True")
-        if targets_by_path and not frontier_targets:
-            raise ValueError("MissionControl: targets_by_path=True needs frontier_targets=True")
-        if targets_by_territory and not frontier_targets:
-            raise ValueError("MissionControl: targets_by_territory=True needs frontier_targets=True")
-        if targets_by_territory and targets_by_path:
-            raise ValueError("MissionControl: targets_by_territory=True excludes targets_by_path=True")
-        if targets_by_gain and not frontier_targets:
-            raise ValueError("MissionControl: targets_by_gain=True needs frontier_targets=True")
-        if targets_by_gain and (targets_by_path or targets_by_territory):
-            raise ValueError("MissionControl: targets_by_gain=True excludes targets_by_path and targets_by_territory")
+        by = [k for k, on in (("targets_by_path", targets_by_path), ("targets_by_territory", targets_by_territory),
+                              ("targets_by_gain", targets_by_gain)) if on]
+        if not frontier_targets and (plan_paths or by):         # each of them refines frontier_targets
+            raise ValueError(f"MissionControl: {by[0] if by else 'plan_paths'}=True needs frontier_targets=True")
+        if len(by) > 1:                                         # and at most one ranking is in force
+            raise ValueError(f"MissionControl: {by[-1]}=True excludes {' and '.join(by[:-1])}")
         if match_sweeps and not sweeps:
             raise ValueError("MissionControl: match_sweeps=True needs sweeps=True")
         self.sweep_graph = sweep_graph is not False and sweep_graph is not None      # ({} is on, with the defaults)
@@ -253,10 +247,8 @@ class MissionControl:
         if not states:
             return {}
         sent = {}
-        if self.targets_by_path or self.targets_by_gain:
-            targets = self._targets_by_path(states)
-        elif self.targets_by_territory:
-            targets = self._targets_by_territory(states)
+        if self.targets_by_path or self.targets_by_gain or self.targets_by_territory:
+            targets = self._targets_by_cost(states)
         else:
             targets = sorted(self.mapper.assign_frontier_targets(states).items())
             if self.plan_paths and targets:
@@ -285,27 +277,25 @@ class MissionControl:
                 self.plan_stats["centroid"] += 1
         return out
 
-    def _targets_by_path(self, states):
-        """One call that ranks the centroids by path cost (targets_by_gain: by gain over path cost): the centroids of the
-        assigned bots, or (plan_paths) their waypoints, which always exist; counted in plan_stats as _waypoints counts them."""
-        kw = dict(by_gain=True, **self.plan_params, **self.gain_params) if self.targets_by_gain else dict(by_path=True, **self.plan_params)
-        if not self.plan_paths:
-            return sorted(self.mapper.assign_frontier_targets(states, **kw).items())
-        _, wps = self.mapper.assign_frontier_targets(states, return_waypoints=True, **kw)
-        self.plan_stats["waypoint"] += len(wps)
-        return sorted(wps.items())
-
-    def _targets_by_territory(self, states):
-        """One call that partitions the free space among the bots and gives each the cheapest centroid of its share: the
-        centroids of the assigned bots, or (plan_paths) their waypoints, counted in plan_stats as _targets_by_path counts
-        them.  Keeps territory = {bot: (cells owned, world box or None)}."""
-        res = self.mapper.assign_frontier_targets(states, by_territory=True, return_waypoints=self.plan_paths,
-                                                  return_territory=True, **self.plan_params)
-        m = self.mapper
-        self.territory = {
-            b: (area, None if box is None else (m.ox + box[0] * m.res, m.oy + box[1] * m.res,
-                                                m.ox + (box[2] + 1) * m.res, m.oy + (box[3] + 1) * m.res))
-            for b, (area, box) in res[-1].items()}
+    def _targets_by_cost(self, states):
+        """One call that ranks the centroids by path cost (targets_by_gain: by gain over path cost; targets_by_territory: within
+        each bot's share of the partitioned free space): the centroids of the assigned bots, or (plan_paths) their
+        waypoints, which always exist; counted in plan_stats as _waypoints counts them.  targets_by_territory keeps
+        territory = {bot: (cells owned, world box or None)}."""
+        if self.targets_by_territory:
+            kw = dict(by_territory=True, return_territory=True, **self.plan_params)
+        elif self.targets_by_gain:
+            kw = dict(by_gain=True, **self.plan_params, **self.gain_params)
+        else:
+            kw = dict(by_path=True, **self.plan_params)
+        res = self.mapper.assign_frontier_targets(states, return_waypoints=self.plan_paths, **kw)
+        res = res if isinstance(res, tuple) else (res,)
+        if self.targets_by_territory:
+            m = self.mapper
+            self.territory = {
+                b: (area, None if box is None else (m.ox + box[0] * m.res, m.oy + box[1] * m.res,
+                                                    m.ox + (box[2] + 1) * m.res, m.oy + (box[3] + 1) * m.res))
+                for b, (area, box) in res[-1].items()}
         if not self.plan_paths:
             return sorted(res[0].items())
         self.plan_stats["waypoint"] += len(res[1])

@@ -16,19 +16,20 @@ struct Piece { const char *name; char *p; size_t bytes; };
 static int check(int size, size_t n_cent, size_t n_bots, bool want_owner, bool want_cost)
 {
     const QsTerrLayout Q = qs_terr_layout(nullptr, size, n_cent, n_bots, want_owner, want_cost);
-    if (Q.key || Q.slot || Q.owner || Q.cost || Q.pair_bot) { fprintf(stderr, "sizing pass handed out a pointer\n"); return 1; }
+    if (Q.key || Q.slot || Q.owner || Q.cost || Q.tg.pair_bot) { fprintf(stderr, "sizing pass handed out a pointer\n"); return 1; }
     char *ws = (char *)aligned_alloc(256, Q.bytes ? Q.bytes : 256);
     if (!ws) { fprintf(stderr, "no memory for %zu bytes\n", Q.bytes); return 1; }
     const QsTerrLayout L = qs_terr_layout(ws, size, n_cent, n_bots, want_owner, want_cost);
     const size_t cells = (size_t)size * size, n_end = n_cent + n_bots;
+    const QsTgtLayout &S = L.tg;
     const Piece pc[] = {
         {"key", (char *)L.key, L.field_cells * 8}, {"slot", (char *)L.slot, n_bots * 8}, {"area", (char *)L.area, n_bots * 8},
-        {"box", (char *)L.box, n_bots * 16}, {"count", (char *)L.count, 32}, {"xy", (char *)L.xy, n_end * 16},
-        {"cell", (char *)L.cell, n_end * 8}, {"coff", (char *)L.coff, n_cent * 4}, {"cent_owner", (char *)L.cent_owner, n_cent * 4},
-        {"cent_cost", (char *)L.cent_cost, n_cent * 4}, {"tgt_idx", (char *)L.tgt_idx, n_bots * 8},
-        {"tgt_xy", (char *)L.tgt_xy, n_bots * 16}, {"tgt_cost", (char *)L.tgt_cost, n_bots * 4},
-        {"tgt_status", (char *)L.tgt_status, n_bots * 4}, {"pair", (char *)L.pair, n_bots * 16},
-        {"pair_bot", (char *)L.pair_bot, n_bots * 4}, {"owner", (char *)L.owner, want_owner ? cells * 2 : 0},
+        {"box", (char *)L.box, n_bots * 16}, {"count", (char *)S.count, 32}, {"xy", (char *)S.xy, n_end * 16},
+        {"cell", (char *)S.cell, n_end * 8}, {"coff", (char *)S.coff, n_cent * 4}, {"tgt_idx", (char *)S.tgt_idx, n_bots * 8},
+        {"tgt_cost", (char *)S.tgt_cost, n_bots * 4}, {"tgt_status", (char *)S.tgt_status, n_bots * 4},
+        {"pair", (char *)S.pair, n_bots * 16}, {"pair_bot", (char *)S.pair_bot, n_bots * 4},
+        {"cent_owner", (char *)L.cent_owner, n_cent * 4}, {"cent_cost", (char *)L.cent_cost, n_cent * 4},
+        {"tgt_xy", (char *)L.tgt_xy, n_bots * 16}, {"owner", (char *)L.owner, want_owner ? cells * 2 : 0},
         {"cost", (char *)L.cost, want_cost ? cells * 4 : 0}};
     int bad = 0;
     if (L.bytes != Q.bytes) { fprintf(stderr, "bytes differ between the passes: %zu, %zu\n", Q.bytes, L.bytes); bad = 1; }

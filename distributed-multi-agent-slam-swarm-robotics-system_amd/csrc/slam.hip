@@ -859,15 +859,21 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
 // reference's workloads nearly every query finds a match laps old, so:
 //   owner waves (one per agent)  run their agent's recurrence at their own pace: the agent's next event that may close (:304),
 //                  its pose, a query of the index (entries up to the committer's frontier), the closure, next.  An owner hands
-//                  over its DECISIONS only (closing node, matched landmark, correction: an LDS ring) and how far it has decided.
-//   the committer (one wave)     takes events in NODE order as far as every agent has decided, up to 64 at a time: it keeps every
-//                  agent's drift as the decisions it has passed leave it (the owner's additions in the owner's order), poses
-//                  the events, writes closure records (:317), the landmark log (:288), the bucket index; then -- its stores
-//                  complete -- moves the frontier: the node index up to which the index is complete and visible.
+//                  over its CLOSURES only -- matched landmark, correction and the agent's drift after the closure, in an LDS
+//                  ring indexed by the closing event's position in the event list -- and how far it has decided.
+//   the committer (one wave)     takes events in NODE order as far as every agent has decided, up to 64 at a time, a lane each:
+//                  a lane reads its event's slot of the ring; the drift in force at an event is the one its agent's last
+//                  closure before it left (a lower lane of the batch, or what the batches before left behind).  It adds
+//                  nothing up itself: the drifts are the owners' own doubles.  It poses the events, writes closure records
+//                  (:317), the landmark log (:288), the bucket index; then -- its stores complete -- moves the frontier: the
+//                  node index up to which the index is complete and visible.
 // An owner that finds no match below the frontier while the frontier is still short of its limit waits for the committer and asks
 // again; the owner with the oldest pending event never waits for anyone (everything older is final), so the scheme cannot
-// lock up; a full decision ring holds its owner back until the committer -- which then has work -- drains it.
-#define FR_RING 64
+// lock up.  The ring adds one wait, at the top of a chunk of 64 events in which the owner has events: until the committer is
+// within FR_HAND - 64 events of the chunk's end, so that every slot of the chunk has been read and cleared for its previous
+// holder.  The owner enters it with its progress word already at the chunk's first node, and what it waits for are events at
+// least FR_HAND - 64 positions older than that, all of them decided by owners that nothing newer can hold back: it ends too.
+#define FR_HAND 512            // closure hand-over ring of the free-running kernel (events; a power of two)
 #define FR_PEND 256            // pending-pose ring of the free-running kernel (events)
 // Every wait of this kernel ends by the argument above.  A kernel that never ends would take the GPU with it, so the waits are
 // bounded all the same (~1 s): a wave that runs out of patience leaves a mark in QS_CNT_SLAM_ROUNDS (bit 40) and goes on --
@@ -1028,19 +1034,21 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
     constexpr int AGW = WAVES - 3, INS = WAVES - 1, THREADS = WAVES * QS_WAVE;   // owner waves 1 .. AGW; the committer
     const int n_ow = min(AGW, nb);                  // owner waves in use
     constexpr int NA = AGW;                         // (graphs with more agents: qs_slam_chain_dyn_kernel)
-    constexpr int RD = FR_RING;                     // decisions an agent can be ahead of the committer
+    constexpr unsigned int HD = FR_HAND;            // events an owner can be ahead of the committer (less one chunk)
 
-    // An owner hands the committer its DECISIONS only -- (closing node, matched landmark, correction), in the agent's order, in a
-    // ring of RD slots -- and how far it has decided (s_prog).  Everything else about an event follows from those: the
-    // committer walks the events in node order, keeps every agent's drift as the decisions it has passed leave it (the same
-    // additions in the same order as the owner's: the same doubles), and poses, logs, indexes and records from that.
-    __shared__ long long q_idx[NA][RD], q_midx[NA][RD];                         // closing node; matched landmark's node
-    __shared__ double q_cdx[NA][RD], q_cdy[NA][RD];                             // the closure's correction (:314-315)
-    __shared__ unsigned int s_push[NA], s_cons[NA];                             // decisions pushed by the owner / taken by the committer
+    // An owner hands the committer its CLOSURES only, in the slot of the closing event's position in the event list (r % HD, r
+    // counted from e0), and how far it has decided (s_prog).  Everything else about an event follows from those: the committer
+    // walks the events in node order, a lane each, reads every event's slot, takes the drift in force at an event from its
+    // agent's last closure before it (the owner's own doubles: nothing is added up again), and poses, logs, indexes and
+    // records from that.  A slot is written payload first, then d_midx, then s_prog; the committer reads s_prog before the
+    // slots, and clears a closing slot before it moves s_comm, which an owner reads before it writes the slot's next holder.
+    __shared__ long long d_midx[HD];                                            // matched landmark's node; LL_MAX: this event closes nothing
+    __shared__ double d_cdx[HD], d_cdy[HD];                                     // the closure's correction (:314-315)
+    __shared__ double d_ax[HD], d_ay[HD];                                       // the agent's drift AFTER this closure (:911-914)
     __shared__ long long s_prog[AGW];          // every event of the owner's agents with a node index below this is decided (LL_MAX: all)
     __shared__ long long s_frontier;              // every landmark with node index <= this is in the index, complete and visible
     __shared__ long long s_nmisc, s_nlms;         // side-list / log entries that go with that frontier
-    // committer's own: every agent's drift as of the events it has passed, and where the agent's next closure record goes
+    // committer's own: every agent's drift as of the batches it has passed, and where the agent's next closure record goes
     __shared__ double c_ddx[NA], c_ddy[NA];
     __shared__ unsigned int c_apos[NA];
     // Landmarks that are decided about but not in the index yet: every owner posts the pose each of its events' landmarks is appended
@@ -1053,8 +1061,8 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
 
     const unsigned int e0 = sb.ev_base[g], e1 = sb.ev_base[g + 1];
     if (POST) for (int t = tid; t < FR_PEND; t += THREADS) p_node[t] = -LL_MAX - 1;
+    for (unsigned int t = tid; t < HD; t += THREADS) d_midx[t] = LL_MAX;
     for (int t = tid; t < NA; t += THREADS) {
-        s_push[t] = 0; s_cons[t] = 0;
         if (t < nb) { c_ddx[t] = drift[2 * (bot0 + t)]; c_ddy[t] = drift[2 * (bot0 + t) + 1]; c_apos[t] = sb.agent_ev[bot0 + t]; }
     }
     if (tid < AGW) s_prog[tid] = tid < n_ow ? (e0 < e1 ? sb.ev_node[e0] : LL_MAX) : LL_MAX;
@@ -1070,12 +1078,11 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         const bool my_valid = my_agent < nb;
         double c_dx = my_valid ? drift[2 * (bot0 + my_agent)] : 0, c_dy = my_valid ? drift[2 * (bot0 + my_agent) + 1] : 0;
         long long c_last = my_valid ? last_closure[bot0 + my_agent] : 0;
-        unsigned int pushed = 0, cons_c = 0;
         const QsNodeG g_nodes = (QsNodeG)Gp->nodes;
         const QsU32G g_next = (QsU32G)Gp->nd_next;
         unsigned long long st_misc = 0, st_wait = 0;
         auto publish_prog = [&](long long nxt) {
-            // what is handed over is the decision ring (LDS), written by this wave just before: the LDS unit takes a wave's
+            // what is handed over is the closure ring (LDS), written by this wave just before: the LDS unit takes a wave's
             // operations in the order they were issued, so all that is needed is that the compiler keeps that order
             LDS_CBAR();
             if (lane == 0) LDS_ST_RLX(&s_prog[a], nxt);
@@ -1112,8 +1119,10 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                 if ((m >> lane) & 1) LDS_ST_RLX(&p_node[(q0 - e0 + (unsigned int)lane) % FR_PEND], idx);
                 posted |= m;
             };
-            // (a slot's last holder is long committed)
-            if (POST && own) FR_SPIN(q0 - e0 + QS_WAVE > LDS_RLX(&s_comm) + (unsigned int)(FR_PEND - QS_WAVE));
+            // the chunk's slots of the closure ring (and, with POST, of the shorter pending ring, which then sets the distance):
+            // their last holders are committed, read and cleared.  s_prog stands at this chunk's first node here.
+            static_assert(FR_PEND <= FR_HAND && (FR_HAND & (FR_HAND - 1)) == 0, "ring depths");
+            if (own) FR_SPIN(q0 - e0 + QS_WAVE > LDS_RLX(&s_comm) + ((POST ? (unsigned int)FR_PEND : HD) - QS_WAVE));
             // the events that may close a loop (:304: their agent is past its cool-down); the ones before the first need no decision
             auto eligible = [&]() -> unsigned long long {
                 return own & ~done & __ballot(idx - c_last >= min_between);
@@ -1143,7 +1152,6 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             };
             if (elig) start_decision(elig);
             while (elig) {
-                const int qa = a;
                 const long long qidx_c = qidx;                                      // (this decision's: start_decision below moves on)
                 const double qx_c = qx, qy_c = qy;
                 const int f_c = f, qtype_c = qtype;
@@ -1214,22 +1222,11 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                 if (elig) start_decision(elig);
                 // ... and this one handed over
                 if (gbest != LL_MAX) {
-                    // the agent's decision ring: a slot must be free
-                    unsigned int pq = pushed, cq = cons_c;
-                    if (pq - cq >= (unsigned int)RD) {                              // looks full
-                        cq = lds_ld32(&s_cons[qa]);
-                        if (pq - cq >= (unsigned int)RD) {
-                            publish_prog(qidx_c);
-                            FR_SPIN(pq - (cq = lds_ld32(&s_cons[qa])) >= (unsigned int)RD);
-                        }
-                    }
-                    if (lane == 0) {
-                        const unsigned int sl = pq % RD;
-                        q_idx[qa][sl] = qidx_c; q_midx[qa][sl] = gbest; q_cdx[qa][sl] = cdx; q_cdy[qa][sl] = cdy;
-                    }
-                    pushed = pq + 1; cons_c = cq;
+                    // the closing event's slot (free since the top of the chunk): the payload, then the word that says "closes"
+                    const unsigned int sl = (q0 - e0 + (unsigned int)f_c) % HD;
+                    if (lane == 0) { d_cdx[sl] = cdx; d_cdy[sl] = cdy; d_ax[sl] = c_dx; d_ay[sl] = c_dy; }
                     LDS_CBAR();
-                    if (lane == 0) LDS_ST_RLX(&s_push[qa], pq + 1);
+                    if (lane == 0) LDS_ST_RLX(&d_midx[sl], gbest);
                 }
                 // decided: everything of this owner below its next event that may close (or, failing one in this chunk, below the
                 // next chunk's first event)
@@ -1289,44 +1286,39 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             const bool inw = lane < k;
             const int type = inw ? type_l : 0;
             const double px = inw ? px_l : 0, py = inw ? py_l : 0;
-            // ---- every agent of the batch: its drift along its events, its decisions that fall into the batch ----
-            double dx = 0, dy = 0, cdx = 0, cdy = 0;
-            long long midx = LL_MAX;
-            for (unsigned long long rem = __ballot(inw); rem;) {
-                const int ld = __ffsll((long long)rem) - 1;
-                const int aa = __builtin_amdgcn_readlane(ag, ld);
-                const unsigned long long La = __ballot(inw && ag == aa);
-                rem &= ~La;
-                double cur_dx = c_ddx[aa], cur_dy = c_ddy[aa];
-                unsigned int dc = s_cons[aa];
-                const unsigned int dp = LDS_RLX(&s_push[aa]);
-                LDS_CBAR();
-                unsigned int apos = c_apos[aa];
-                unsigned long long left = La;                                        // lanes of aa not yet given their drift
-                while (dc != dp) {
-                    const unsigned int sl = dc % RD;
-                    const long long qi = q_idx[aa][sl];
-                    const unsigned long long lm = La & __ballot(node == qi);
-                    if (!lm) break;                                                  // the agent's next decision is about a later event
-                    const int lc = __ffsll((long long)lm) - 1;
-                    const unsigned long long upto = left & ((2ull << lc) - 1);       // the closing event and the agent's events before it
-                    if ((upto >> lane) & 1) { dx = cur_dx; dy = cur_dy; }            // matched / stored at the pose BEFORE the closure (:288, :308)
-                    const double ecx = q_cdx[aa][sl], ecy = q_cdy[aa][sl];
-                    if (lane == lc) { midx = q_midx[aa][sl]; cdx = ecx; cdy = ecy; }
-                    cur_dx += ecx; cur_dy += ecy;                                    // drift_correction[agent] += ...  :911-914
-                    if (lane == lc) { sb.acl_node[apos] = qi; sb.acl_dx[apos] = cur_dx; sb.acl_dy[apos] = cur_dy; }
-                    apos++;
-                    left &= ~upto;
-                    dc++;
+            // ---- every event's slot of the closure ring, and its agent's state as the batches before left it ----
+            // (read by every lane, masked afterwards: one LDS round trip)
+            const unsigned int sl = (e - e0 + (unsigned int)lane) % HD;
+            const long long midx = LDS_RLX(&d_midx[sl]);
+            const double cdx = d_cdx[sl], cdy = d_cdy[sl], ax = d_ax[sl], ay = d_ay[sl];
+            double dx = c_ddx[ag], dy = c_ddy[ag];
+            const unsigned int apos0 = c_apos[ag];
+            const bool closes = inw && midx != LL_MAX;
+            if (closes) LDS_ST_RLX(&d_midx[sl], LL_MAX);                             // (free for its next holder once s_comm has passed it)
+            const unsigned long long cmask = __ballot(closes);
+            // ---- the drift in force at an event: the one its agent's last closure STRICTLY before it left -- the closing event
+            // itself is matched / stored at the pose before its closure (:288, :308) ----
+            int src = -1;
+            unsigned int nrank = 0;                                                  // the agent's closures of the batch before this lane
+            for (unsigned long long rem = cmask; rem;) {                             // every agent that closes in the batch
+                const int aa = __builtin_amdgcn_readlane(ag, __ffsll((long long)rem) - 1);
+                const unsigned long long Ca = cmask & __ballot(ag == aa);
+                rem &= ~Ca;
+                if (ag == aa) {
+                    const unsigned long long prev = Ca & ((1ull << lane) - 1);
+                    if (prev) src = 63 - __builtin_clzll(prev);
+                    nrank = (unsigned int)__popcll(prev);
+                    // what the batch leaves behind: the drift after the agent's last closure  (:911-914)
+                    if (lane == 63 - __builtin_clzll(Ca)) { c_ddx[aa] = ax; c_ddy[aa] = ay; c_apos[aa] = apos0 + (unsigned int)__popcll(Ca); }
                 }
-                if ((left >> lane) & 1) { dx = cur_dx; dy = cur_dy; }
-                LDS_CBAR();
-                if (lane == ld) { c_ddx[aa] = cur_dx; c_ddy[aa] = cur_dy; c_apos[aa] = apos; LDS_ST_RLX(&s_cons[aa], dc); }
             }
+            if (cmask) {
+                const double sx = __shfl(ax, src < 0 ? lane : src), sy = __shfl(ay, src < 0 ? lane : src);
+                if (src >= 0) { dx = sx; dy = sy; }
+            }
+            if (closes) { sb.acl_node[apos0 + nrank] = node; sb.acl_dx[apos0 + nrank] = ax; sb.acl_dy[apos0 + nrank] = ay; }
             const double x = raw_pose ? px : px + dx, y = raw_pose ? py : py + dy;   // rx += cdx, ry += cdy  :856-857
             // ---- closure records, in node order  (:317) ----
-            const bool closes = inw && midx != LL_MAX;
-            const unsigned long long cmask = __ballot(closes);
             if (closes) {
                 const long long slot = n_cls + __popcll(cmask & ((1ull << lane) - 1));
                 if (slot < G.cap_cls) {
@@ -1373,7 +1365,8 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
 // order.  An agent's decisions still happen one after the other: its state (drift, last closure: :911-914, :318) lives in LDS
 // with a word saying up to which of its events it is decided, and whoever holds the agent's next event waits for that word.
 // Which event that is -- the previous event of the same agent -- is worked out by wave 0 (the dispatcher), ahead of the owners.
-// The committer is the one of qs_slam_chain_free_kernel; "ready" = below the oldest event any owner is working on.
+// The committer has the role it has in qs_slam_chain_free_kernel, but takes an agent's decisions from a ring per agent, in the
+// agent's order (below); "ready" = below the oldest event any owner is working on.
 // Waits point at OLDER events only (the agent's previous event, the frontier at q - MIN_POSES_BETWEEN, a ring slot held by an
 // older decision of the agent; the dispatcher at events committed), so the oldest undecided event can always go on.
 #define DY_RING 512             // dispatcher -> owners: per event, the node index of the agent's previous event

@@ -344,6 +344,25 @@ extern "C" int qs_chain_form(qs_ctx *c)
     return !c->chain_last_free ? QS_CHAIN_WINDOW : c->chain_last_posting ? QS_CHAIN_FREE_POSTING : QS_CHAIN_FREE;
 }
 
+extern "C" int qs_set_chain_lean(qs_ctx *c, int32_t mode, int64_t limit)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, mode == QS_CHAIN_LEAN_AUTO || mode == QS_CHAIN_LEAN_OFF);
+    c->chain_lean_mode = mode;
+    c->chain_lean_limit = limit > 0 && limit < 0x7f7f7f7fll ? limit : 0x7f7f7f7fll;
+    return QS_OK;
+}
+
+extern "C" int qs_chain_lean(qs_ctx *c)
+{
+    if (!c) return QS_E_INVAL;
+    if (!c->chain_last_lean_asked) return 0;
+    unsigned int refused = 0;
+    HIPCHK(c, hipMemcpyAsync(&refused, c->d_flags.p + QS_FLAG_CHAIN_FULL, sizeof refused, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return refused != c->chain_lean_seq ? 1 : 0;
+}
+
 extern "C" int qs_sync(qs_ctx *c)
 {
     ARGCHK(c, c != nullptr);

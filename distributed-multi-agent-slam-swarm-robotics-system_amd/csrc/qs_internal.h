@@ -109,6 +109,7 @@ __device__ inline bool qs_block_cell(unsigned int bid, int lane, int pitch, int 
 enum { QS_FLAG_EDGE_N = 0,        // exact-trig mode: edge rays waiting for the host
        QS_FLAG_PILE = 1,          // a landmark pile has formed (slam.hip, DENSE)
        QS_FLAG_EDGE_OVF = 2,      // edge rays that found the waiting list full
+       QS_FLAG_CHAIN_FULL = 3,    // free-running chain: the number of the last launch in which a graph was refused the lean owner
        // loop-closure chain, running totals (never cleared; the host looks at differences -- qs_api.hip, chain_stats_poll):
        QS_FLAG_CHAIN_MISS = 4,    // free-running form: decisions that waited for the frontier ...
        QS_FLAG_CHAIN_HIT = 5,     // ... and its closures
@@ -307,6 +308,10 @@ struct qs_ctx {
                                                  // owners posting their landmarks' poses (slam.hip, qs_launch_slam)
     bool chain_windowed = false;                 // ... and beyond that: the per-window kernel (even with posted poses most queries find nothing)
     bool chain_last_free = true, chain_last_posting = false;   // the form the last launch used
+    int chain_lean_mode = 0;                     // QS_CHAIN_LEAN_AUTO / _OFF (qs_set_chain_lean) ...
+    long long chain_lean_limit = 0x7f7f7f7fll;   // ... and the node count below which the kernel allows it (the empty marker's low word, or less)
+    unsigned int chain_lean_seq = 0;             // launches of the free-running kernel so far (what a refused graph leaves in QS_FLAG_CHAIN_FULL)
+    bool chain_last_lean_asked = false;          // the last launch was that kernel with the lean owner on offer
     unsigned int *h_chain_stat = nullptr;        // pinned: [0..3] the four running totals as copied last, [4..7] as consumed last
     hipEvent_t ev_chain_stat = nullptr;          // ... complete when the copy has landed
     bool chain_stat_pending = false;

@@ -1025,13 +1025,25 @@ __global__ void __launch_bounds__(WAVES * QS_WAVE)
 qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGeom bg, int bots_per_graph,
                           int max_agent, int min_between, double r2thr, double corr,
                           double *__restrict__ drift, long long *__restrict__ last_closure,
-                          unsigned long long *__restrict__ counters, int raw_pose, unsigned int *__restrict__ pile_flag)
+                          unsigned long long *__restrict__ counters, int raw_pose, unsigned int *__restrict__ pile_flag,
+                          long long lean_limit, unsigned int lean_seq)
 {
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     QsGraphDev *const Gp = graphs + g;
     const int bot0 = g * bots_per_graph + 1;
     const int nb = min(bots_per_graph, max_agent - bot0 + 1);
     constexpr int AGW = WAVES - 3, INS = WAVES - 1, THREADS = WAVES * QS_WAVE;   // owner waves 1 .. AGW; the committer
+    // The lean owner (below: 32-bit node indices, a decision settled by its first rows alone): allowed while every node index
+    // this launch can meet is below the low word of the empty-slot marker (lean_limit: that word, or less -- qs_set_chain_lean;
+    // 0: off), the node table's byte offsets fit 32 bits, the cool-down cannot overflow a 32-bit difference, and poses get
+    // their drift.  Worked out here, by every wave for itself, from what is on the device at launch (the committer moves n_nodes
+    // only at its end, long after this read).
+    // (Not in the instantiations that post poses, nor in the 8-wave DENSE one: the second owner loop costs <false, 16, true> scratch
+    // and the 8-wave ones a wave of occupancy.  They run the general owner as before.)
+    constexpr bool LEAN_OK = !POST && !(DENSE && WAVES == 8);
+    const bool lean = LEAN_OK && lean_limit > 0 && Gp->n_nodes + (long long)sb.acc_total[g] < lean_limit
+                      && (unsigned long long)Gp->node_cap * sizeof(QsLmNode) < (1ull << 32) && min_between < (1 << 30) && raw_pose == 0;
+    if (LEAN_OK && tid == 0 && lean_limit > 0 && !lean && pile_flag) atomicMax(pile_flag + QS_FLAG_CHAIN_FULL - QS_FLAG_PILE, lean_seq);
     const int n_ow = min(AGW, nb);                  // owner waves in use
     constexpr int NA = AGW;                         // (graphs with more agents: qs_slam_chain_dyn_kernel)
     constexpr unsigned int HD = FR_HAND;            // events an owner can be ahead of the committer (less one chunk)
@@ -1080,7 +1092,16 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         long long c_last = my_valid ? last_closure[bot0 + my_agent] : 0;
         const QsNodeG g_nodes = (QsNodeG)Gp->nodes;
         const QsU32G g_next = (QsU32G)Gp->nd_next;
-        unsigned long long st_misc = 0, st_wait = 0;
+        unsigned long long st_misc = 0, st_wait = 0, st_slow = 0;
+        // the lean owner's per-lane constants: the lane's bucket of the 3 x 3 (lane 63: none) as its share of the hash -- the
+        // centre cell is the same in every lane, and (cx + d) * K == cx * K + d * K in 32-bit arithmetic --, its entry's byte offset
+        // in a node row, and the last lanes of the nine lane groups
+        const int l_nbk = lane / QS_NODE_CAP;
+        const unsigned int l_hx = (unsigned int)((l_nbk % 3) - 1) * 0x9E3779B1u, l_hy = (unsigned int)((l_nbk / 3) - 1) * 0x85EBCA77u;
+        const unsigned int l_se8 = (unsigned int)(lane % QS_NODE_CAP) * 8u;
+        const bool l_in9 = lane < 9 * QS_NODE_CAP;
+        constexpr unsigned long long L_LAST9 = 0x4081020408102040ull;                  // bits 6, 13, .. 62
+        static_assert(QS_NODE_CAP == 7 && offsetof(QsLmNode, x) == 64 && offsetof(QsLmNode, y) == 128 && sizeof(QsLmNode) == 192, "lean row loads");
         auto publish_prog = [&](long long nxt) {
             // what is handed over is the closure ring (LDS), written by this wave just before: the LDS unit takes a wave's
             // operations in the order they were issued, so all that is needed is that the compiler keeps that order
@@ -1099,141 +1120,16 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         };
         int ag_n = -1, type_n = 0; long long idx_n = LL_MAX, nf_n = LL_MAX; double px_n = 0, py_n = 0;
         if (e0 < e1) load_chunk(e0, ag_n, idx_n, type_n, px_n, py_n, nf_n);
-        for (unsigned int q0 = e0; q0 < e1; q0 += QS_WAVE) {
-            const int ag = ag_n, type = type_n;
-            const long long idx = idx_n, next_first = nf_n;
-            const double px = px_n, py = py_n;
-            if (q0 + QS_WAVE < e1) load_chunk(q0 + QS_WAVE, ag_n, idx_n, type_n, px_n, py_n, nf_n);
-            const unsigned long long own = __ballot(ag == a);
-            unsigned long long done = 0;                                            // own lanes decided so far
-            unsigned long long posted = 0;                                          // own lanes whose landmark pose is in the pending ring
-            // own events up to lane hi (with the agent's drift as it is now: the events since its last closure)
-            auto post_upto = [&](int hi) {
-                if (!POST) return;
-                const unsigned long long m = own & ~posted & ((2ull << hi) - 1);
-                if ((m >> lane) & 1) {
-                    const unsigned int ps = (q0 - e0 + (unsigned int)lane) % FR_PEND;
-                    p_x[ps] = raw_pose ? px : px + c_dx; p_y[ps] = raw_pose ? py : py + c_dy;   // rx += cdx  :856-857
-                }
-                LDS_CBAR();
-                if ((m >> lane) & 1) LDS_ST_RLX(&p_node[(q0 - e0 + (unsigned int)lane) % FR_PEND], idx);
-                posted |= m;
-            };
-            // the chunk's slots of the closure ring (and, with POST, of the shorter pending ring, which then sets the distance):
-            // their last holders are committed, read and cleared.  s_prog stands at this chunk's first node here.
-            static_assert(FR_PEND <= FR_HAND && (FR_HAND & (FR_HAND - 1)) == 0, "ring depths");
-            if (own) FR_SPIN(q0 - e0 + QS_WAVE > LDS_RLX(&s_comm) + ((POST ? (unsigned int)FR_PEND : HD) - QS_WAVE));
-            // the events that may close a loop (:304: their agent is past its cool-down); the ones before the first need no decision
-            auto eligible = [&]() -> unsigned long long {
-                return own & ~done & __ballot(idx - c_last >= min_between);
-            };
-            unsigned long long elig = eligible();
-            // A decision: (event f of the chunk, its pose with the agent's drift as it is NOW, the first nodes of its nine buckets,
-            // their rows on the way).  The rows of the NEXT decision are asked for as soon as this one's closure is known -- before
-            // the hand-over to the committer, whose LDS traffic then runs in the shadow of the loads.
-            int f = 0, qtype = 0;
-            long long qidx = 0, fr_rows = 0;
-            double qx = 0, qy = 0;
-            unsigned int node0 = 0;
-            FqRows rows = {LL_MAX, LL_MAX, 0, 0, 0u};
-            auto start_decision = [&](unsigned long long e_) {
-                // (the frontier first: the rows are asked for after it is read -- an older value is only more cautious)
-                fr_rows = LDS_RLX(&s_frontier);
-                f = __ffsll((long long)e_) - 1;
-                post_upto(f);
-                qidx = rl64(idx, f);
-                const double spx = rlf64(px, f), spy = rlf64(py, f);
-                qx = raw_pose ? spx : spx + c_dx; qy = raw_pose ? spy : spy + c_dy;               // rx += cdx  :856-857
-                qtype = __builtin_amdgcn_readlane(type, f);
-                int qcx, qcy;
-                node0 = fq_node0(bg, qx, qy, qtype, lane, qcx, qcy);
-                __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                fq_load(g_nodes, g_next, node0, lane, rows);
-            };
-            if (elig) start_decision(elig);
-            while (elig) {
-                const long long qidx_c = qidx;                                      // (this decision's: start_decision below moves on)
-                const double qx_c = qx, qy_c = qy;
-                const int f_c = f, qtype_c = qtype;
-                // :300 -- and a node never sees its own landmark (appended after the check, :288): with MIN_POSES_BETWEEN < 1
-                // the newest landmark a query can see is still the one before it
-                const long long limit = qidx_c - (min_between > 1 ? min_between : 1);
-                long long gbest; double wx, wy;
-                {
-                    bool pre = true;
-                    for (long long fr = fr_rows;;) {
-                        const long long nm = s_nmisc, nl = DENSE ? s_nlms : 0;
-                        gbest = free_query<DENSE>(Gp, g_nodes, g_next, bg, qx_c, qy_c, qtype_c, fr < limit ? fr : limit, r2thr, nm, nl, lane, wx, wy, st_misc,
-                                                  node0, pre, rows);
-                        if (gbest != LL_MAX || fr >= limit) break;                  // a match below the frontier is final; so is "none" once all are in
-                        pre = false;
-                        // Nothing in the index up to fr.  The landmarks with fr < node <= limit are events the committer has not got
-                        // to: their poses are in the pending ring once their owners have passed them.  64 events a round, youngest
-                        // first; the OLDEST match is the reference's first match.
-                        st_wait++;
-                        publish_prog(qidx_c);                                       // (the committer has to get past this owner's older events)
-                        if (!POST) {                                                // wait until it has everything up to the limit in the index
-                            if (lds_ld64(&s_frontier) <= fr) FR_SPIN(lds_ld64(&s_frontier) < limit);
-                            fr = lds_ld64(&s_frontier);
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");    // the index as of that frontier, not older
-                            continue;
-                        }
-                        bool stale = false;
-                        const unsigned int r_me = q0 - e0 + (unsigned int)f_c;      // this event's place in the list
-                        for (unsigned int back = 0; back < r_me; back += QS_WAVE) {
-                            const long long jr = (long long)r_me - 1 - (long long)back - lane;
-                            const bool hv = jr >= 0;
-                            const long long nd = hv ? sb.ev_node[e0 + (unsigned int)jr] : -LL_MAX - 1;
-                            const int ty = hv ? (int)sb.ev_type[e0 + (unsigned int)jr] : 0;
-                            const bool inr = hv && nd > fr && nd <= limit;
-                            const unsigned int ps = hv ? (unsigned int)jr % FR_PEND : 0u;
-                            // posted -- or, if the committer overtook it meanwhile (its slot may have a new holder), in the index by now
-                            FR_SPIN(__ballot(inr && LDS_RLX(&p_node[ps]) != nd && LDS_RLX(&s_frontier) < nd) != 0);
-                            LDS_CBAR();
-                            if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }
-                            bool hit = false;
-                            double lx = 0, ly = 0;
-                            if (inr && ty == qtype_c) {
-                                lx = p_x[ps]; ly = p_y[ps];
-                                const double dx = qx_c - lx, dy = qy_c - ly;
-                                hit = dx * dx + dy * dy < r2thr;                    // :308-309
-                            }
-                            LDS_CBAR();
-                            if (__ballot(inr && LDS_RLX(&p_node[ps]) != nd)) { stale = true; break; }
-                            const unsigned long long hm = __ballot(hit);
-                            if (hm) { const int w = 63 - __builtin_clzll(hm); gbest = rl64(nd, w); wx = rlf64(lx, w); wy = rlf64(ly, w); }
-                            if (!__ballot(hv && lane == QS_WAVE - 1 && nd > fr)) break;  // the round's oldest event is in the index already
-                        }
-                        if (!stale) break;                                          // match or none: final (index up to fr, events up to limit)
-                        gbest = LL_MAX;                                             // the index has grown under the scan: once more, from it
-                        fr = lds_ld64(&s_frontier);
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");        // the index as of that frontier, not older
-                    }
-                }
-                done |= (2ull << f_c) - 1;                                          // (lanes up to f: decided)
-                double cdx = 0, cdy = 0;
-                if (gbest != LL_MAX) {
-                    const double ex = wx - qx_c, ey = wy - qy_c;                    // :311-312
-                    cdx = ex * corr; cdy = ey * corr;                               // :314-315
-                    c_dx += cdx; c_dy += cdy; c_last = qidx_c;                      // :911-914, :318
-                }
-                // the next decision, its rows on the way ...
-                elig = eligible();
-                if (elig) start_decision(elig);
-                // ... and this one handed over
-                if (gbest != LL_MAX) {
-                    // the closing event's slot (free since the top of the chunk): the payload, then the word that says "closes"
-                    const unsigned int sl = (q0 - e0 + (unsigned int)f_c) % HD;
-                    if (lane == 0) { d_cdx[sl] = cdx; d_cdy[sl] = cdy; d_ax[sl] = c_dx; d_ay[sl] = c_dy; }
-                    LDS_CBAR();
-                    if (lane == 0) LDS_ST_RLX(&d_midx[sl], gbest);
-                }
-                // decided: everything of this owner below its next event that may close (or, failing one in this chunk, below the
-                // next chunk's first event)
-                publish_prog(elig ? qidx : next_first);
-            }
-            post_upto(QS_WAVE - 1);                                                 // (the agent's events after its last decision of the chunk)
-            publish_prog(next_first);
+        // The chunks, once for the lean owner and once for the general one (which of the two: known at the kernel's start): two
+        // loops from one text, so that neither carries the other's registers -- a value live in both would be copied where they
+        // meet, behind a wait for the row loads just issued.  (Included twice, not a generic lambda called twice: that changed
+        // the register allocation of the instantiations that have no lean owner, and cost them 3 %.)
+        if (lean) {
+            constexpr bool LEAN = true;
+#include "slam_chain_owner.inc"
+        } else {
+            constexpr bool LEAN = false;
+#include "slam_chain_owner.inc"
         }
         publish_prog(LL_MAX);
         if (my_valid && lane == 0) {
@@ -1241,6 +1137,7 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         }
         if (lane == 0) {
             if (st_misc) atomicAdd(&counters[QS_CNT_SLAM_MISC_ITERS], st_misc);
+            if (st_slow) atomicAdd(&counters[QS_CNT_SLAM_NODE_ITERS], st_slow);   // lean decisions not settled by their first rows
             if (st_wait) { atomicAdd(&counters[QS_CNT_SLAM_ROUNDS], st_wait); if (pile_flag) atomicAdd(pile_flag + QS_FLAG_CHAIN_MISS - QS_FLAG_PILE, (unsigned int)st_wait); }
         }
     } else if (wave == INS) {
@@ -1833,16 +1730,22 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     const bool free_mode = c->chain_form != QS_CHAIN_WINDOW && !(c->chain_form == QS_CHAIN_AUTO && one && c->chain_windowed);
     c->chain_last_posting = false;
     c->chain_last_free = free_mode;
+    c->chain_last_lean_asked = false;
 #define FR_LAUNCH(DENSE_, WAVES_, POST_) hipLaunchKernelGGL((qs_slam_chain_free_kernel<DENSE_, WAVES_, POST_>), dim3(G), dim3(WAVES_ * QS_WAVE), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
-                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
+                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE, \
+                           c->chain_lean_mode == QS_CHAIN_LEAN_OFF ? 0ll : c->chain_lean_limit, c->chain_lean_seq)
 #define DY_LAUNCH(DENSE_) hipLaunchKernelGGL((qs_slam_chain_dyn_kernel<DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
     if (free_mode) {
         if (one) {
             const bool post = c->chain_form == QS_CHAIN_FREE_POSTING || (c->chain_form == QS_CHAIN_AUTO && c->chain_posting);
+            // (the lean owner: the kernel decides per graph, from what is on the device -- a graph that was refused leaves this launch's
+            // number in a device word, which is all qs_chain_lean looks at)
+            c->chain_lean_seq++;
             const int sel = (c->pile_mode ? 4 : 0) | (c->bots_per_graph <= 5 ? 2 : 0) | (post ? 1 : 0);
+            c->chain_last_lean_asked = c->chain_lean_mode != QS_CHAIN_LEAN_OFF && !post && sel != 6;   // (LEAN_OK of the instantiation)
             switch (sel) {
             case 0: FR_LAUNCH(false, 16, false); break;  case 1: FR_LAUNCH(false, 16, true); break;
             case 2: FR_LAUNCH(false, 8, false); break;   case 3: FR_LAUNCH(false, 8, true); break;

@@ -765,6 +765,19 @@ class QuasarMapper:
         """The form the last ingest used: "free", "free_posting" or "window"."""
         return {1: "free", 2: "window", 3: "free_posting"}[self._L.qs_chain_form(self._h)]
 
+    def set_chain_lean(self, mode="auto", limit=0):
+        """The lean owner of the free-running chain (32-bit node indices, decisions settled by their first rows): "auto"
+        (default: wherever a launch's graph allows it) or "off".  limit: the node count at which it stops (0: the largest
+        possible, 0x7f7f7f7f).  Same results either way."""
+        self._chk(self._L.qs_set_chain_lean(self._h, {"auto": 0, "off": 1}[mode], int(limit)), "qs_set_chain_lean")
+
+    def chain_lean(self):
+        """Whether every graph of the last ingest ran the lean owner (waits for the stream)."""
+        r = self._L.qs_chain_lean(self._h)
+        if r < 0:
+            self._chk(r, "qs_chain_lean")
+        return bool(r)
+
     def mfma_f64_rate(self):
         """Measured dense fp64 MFMA rate of this GPU in TFLOP/s (diagnostic)."""
         v = C.c_double()

@@ -421,6 +421,21 @@ int qs_nn_search(qs_ctx *ctx, const double *src_xy, size_t n_src, const double *
 #define QS_CHAIN_FREE_POSTING 3
 int qs_set_chain_form(qs_ctx *ctx, int form);
 int qs_chain_form(qs_ctx *ctx);
+/* The owner waves of the free-running form for graphs of up to 13 bots have a lean variant: 32-bit node indices, and a decision
+ * settled by the first node of each of its nine buckets where those already hold the match (buckets that have to be walked
+ * further are walked on the same 32-bit terms); every other decision goes through the general query.  It exists in the
+ * instantiations without posted poses (not the 8-wave one of a graph with a landmark pile); the others run the general owner.
+ * Same closures, landmarks and drifts bit for bit.  Every
+ * launch decides on the device, per graph, whether it applies: the graph's node count after the launch below `limit`, the node
+ * table below 4 GiB, MIN_POSES_BETWEEN below 2^30, poses that get their drift (not qs_slam_add_poses).
+ * mode QS_CHAIN_LEAN_AUTO (default) or QS_CHAIN_LEAN_OFF (the general owner always); limit: node count at which the lean owner
+ * stops, <= 0 or above 0x7f7f7f7f: 0x7f7f7f7f (the low word of the empty-slot marker of the index).
+ * qs_chain_lean: 1 if every graph of the last ingest ran the lean owner, else 0 (waits for the stream); < 0: error.
+ * The counter slam_node_iters counts the lean owner's decisions that were not settled by those first nodes alone. */
+#define QS_CHAIN_LEAN_AUTO 0
+#define QS_CHAIN_LEAN_OFF 1
+int qs_set_chain_lean(qs_ctx *ctx, int32_t mode, int64_t limit);
+int qs_chain_lean(qs_ctx *ctx);
 
 /* diagnostic: measured dense fp64 MFMA rate of this GPU (TFLOP/s), the ceiling qs_nn_search mode 2 is priced against */
 int qs_diag_mfma_f64_rate(qs_ctx *ctx, double *tflops);

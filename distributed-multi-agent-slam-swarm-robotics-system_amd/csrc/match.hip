@@ -162,7 +162,7 @@ qs_match_kernel(QsSweepArgs a, QsGeom geo, QsMatchArgs m)
         hit[q] = false; bx[q] = 0.0; by[q] = 0.0;
         if (i < QS_SWEEP_BEAMS) {
             const double d = (double)__uint_as_float(sw_u32(s_rec, mis, a.ranges_off + 4u * (unsigned int)i));
-            hit[q] = (a.smin < d) && (d <= a.smax);
+            hit[q] = qs_range_rule(d, a.smin, a.smax).valid;
             bx[q] = d * m.tab[i];
             by[q] = d * m.tab[QS_SWEEP_BEAMS + i];
         }

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "qs_internal.h"
+#include "raycast_common.h"
 
 static thread_local std::string g_create_err;
 
@@ -626,12 +627,10 @@ int sync_host_state(qs_ctx *c, bool host_waits)
         const int sensor = (int)(((r.key_free >> 1) - 1) & 3);                                 // ordinal = 4 * arrival index + sensor + 1
         const double a = sweep ? r.yaw + (double)(r.beam - 90) * (kPi / 180.0)                 // math.radians(i - 90)
                                : r.yaw + off[sensor];                                          // :887
-        const double lo = sweep ? c->sweep_min : c->cfg.min_dist, hi = sweep ? c->sweep_max : c->cfg.max_dist;
-        const bool valid = (lo < dd) && (dd <= hi);                                            // :888
-        const double range = valid ? dd : ((dd > lo) ? ((hi < dd) ? hi : dd) : hi);            // :900
-        h[4 * e] = r.rx + range * cos(a);                                                      // :890 / :901
-        h[4 * e + 1] = r.ry + range * sin(a);                                                  // :891 / :902
-        h[4 * e + 2] = valid ? 1.0 : 0.0;
+        const QsRange g = sweep ? qs_range_rule(dd, c->sweep_min, c->sweep_max) : qs_range_rule(dd, c->cfg.min_dist, c->cfg.max_dist);
+        h[4 * e] = r.rx + g.range * cos(a);                                                    // :890 / :901 (libm: what this mode is for)
+        h[4 * e + 1] = r.ry + g.range * sin(a);                                                // :891 / :902
+        h[4 * e + 2] = g.valid ? 1.0 : 0.0;
         h[4 * e + 3] = 0.0;
     }
     HIPCHK(c, hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, c->stream));

@@ -23,16 +23,16 @@ qs_raycast_direct_kernel(size_t n, QsBatch b, QsGeom geo, unsigned int *__restri
                          unsigned long long *__restrict__ counters)
 {
     __shared__ double s_zone[QS_MAX_AGENT + 1][4];
-    __shared__ unsigned int s_cnt[3];
+    __shared__ unsigned int s_cnt[QS_TALLY_WORDS];
     const int tid = threadIdx.x;
     for (int t = tid; t <= max_agent; t += RC_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
-    if (tid < 3) s_cnt[tid] = 0;
+    qs_tally_init(s_cnt, tid);
     __syncthreads();
 
     const size_t r = (size_t)blockIdx.x * RC_BLOCK + tid;   // ray id: 4 per datagram
     const size_t i = r >> 2;
     const int s = (int)(r & 3);
-    unsigned int my_cells = 0, my_ray = 0, my_hit = 0;
+    QsTally my;
     if (i < n && b.map_ok[i]) {
         const double rx = b.rx[i], ry = b.ry[i], yaw = b.yaw[i];
         const float4 d4 = b.dist[i];
@@ -41,57 +41,23 @@ qs_raycast_direct_kernel(size_t n, QsBatch b, QsGeom geo, unsigned int *__restri
         QsRay ray = qs_project_ray(rx, ry, yaw, (double)df, s, geo);
         if (s == 0) qs_zone_point(s_zone, agent, rx, ry);                          // paths[agent].append  :878-879
         if (ray.valid) qs_zone_point(s_zone, agent, ray.ex, ray.ey);               // point_clouds[..].append  :892
-        my_hit = ray.valid ? 1u : 0u;
-        my_ray = 1;
-        const unsigned int key_free = (unsigned int)((ord_base + ord_stride * i + s + 1) << 1);
-        QsLine ln;
-        if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, rx, ry, yaw, df, key_free)) {
-            // the host decides this ray's cells (qs_api.hip: sync_host_state)
-        } else if (qs_line_setup(ray, rx, ry, geo, ln)) {
-            int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
-            for (;;) {
-                const bool last = (x == ln.x1 && y == ln.y1);
-                if ((!last || ray.valid) && x >= 0 && x < geo.size && y >= 0 && y < geo.size) {
-                    const size_t c = (size_t)y * geo.size + x;
-                    atomicMax(&stamps[c], key_free | (last ? 1u : 0u));
-                    qs_mark_dirty(geo, x, y);
-                    if (COUNTS) atomicAdd(&counts[c], last ? (1ull << 32) : 1ull);
-                    my_cells++;
-                }
-                if (last) break;
-                const int e2 = 2 * err;
-                if (e2 > -ln.dy) { err -= ln.dy; x += ln.sx; }
-                if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
-            }
-        }
+        my.hits = ray.valid ? 1u : 0u;
+        my.rays = 1;
+        my.cells = qs_ray_direct<COUNTS>(ray, rx, ry, yaw, df, qs_stamp_key(ord_base + ord_stride * i + s), -1, b, geo, stamps, counts);
     }
     // block-level counters and zone flush
-    if (my_ray) atomicAdd(&s_cnt[0], my_ray);
-    if (my_cells) atomicAdd(&s_cnt[1], my_cells);
-    if (my_hit) atomicAdd(&s_cnt[2], my_hit);
+    qs_tally_fold(my, s_cnt);
     __syncthreads();
     for (int t = tid; t <= max_agent; t += RC_BLOCK) qs_zone_commit(s_zone, t, zone);
-    if (tid == 0) {
-        if (s_cnt[0]) atomicAdd(&counters[QS_CNT_RAYS], (unsigned long long)s_cnt[0]);
-        if (s_cnt[1]) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)s_cnt[1]);
-        if (s_cnt[2]) atomicAdd(&counters[QS_CNT_HITS], (unsigned long long)s_cnt[2]);
-    }
+    if (tid == 0) qs_tally_flush(s_cnt, counters);
 }
 
 hipError_t qs_launch_raycast_direct(qs_ctx *c, size_t n, uint64_t seq0)
 {
     if (n == 0) return hipSuccess;
     const unsigned int blocks = (unsigned int)((4 * n + RC_BLOCK - 1) / RC_BLOCK);
-    const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
-    const unsigned long long ord_stride = 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1);
-    if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_raycast_direct_kernel<true>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n,
-                           c->b, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p,
-                           c->cfg.max_agent, c->d_counters.p);
-    else
-        hipLaunchKernelGGL(qs_raycast_direct_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n,
-                           c->b, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p,
-                           c->cfg.max_agent, c->d_counters.p);
+    qs_launch_counts(c, qs_raycast_direct_kernel<true>, qs_raycast_direct_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, n, c->b, c->geom,
+                     c->d_stamps.p, c->d_counts.p, qs_ord_base(c, seq0), qs_ord_stride(c), c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
     return hipGetLastError();
 }
 
@@ -108,7 +74,7 @@ qs_update_rays_kernel(size_t n, const double *__restrict__ rx, const double *__r
     const size_t k = (size_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     if (k >= n) return;
     QsRay ray; ray.ex = hx[k]; ray.ey = hy[k]; ray.valid = valid[k] != 0;
-    const unsigned int key_free = (unsigned int)((ord_base + k + 1) << 1);
+    const unsigned int key_free = qs_stamp_key(ord_base + k);
     QsLine ln;
     unsigned int cells = 0;
     if (isfinite(rx[k]) && isfinite(ry[k]) && isfinite(ray.ex) && isfinite(ray.ey) &&
@@ -123,13 +89,8 @@ hipError_t qs_launch_update_rays(qs_ctx *c, const double *rx, const double *ry, 
 {
     if (n == 0) return hipSuccess;
     const unsigned int blocks = (unsigned int)((n + RC_BLOCK - 1) / RC_BLOCK);
-    const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
-    if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_update_rays_kernel<true>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n, rx, ry,
-                           hx, hy, valid, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, c->d_counters.p);
-    else
-        hipLaunchKernelGGL(qs_update_rays_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, c->stream, n, rx, ry,
-                           hx, hy, valid, c->geom, c->d_stamps.p, c->d_counts.p, ord_base, c->d_counters.p);
+    qs_launch_counts(c, qs_update_rays_kernel<true>, qs_update_rays_kernel<false>, dim3(blocks), dim3(RC_BLOCK), 0, n, rx, ry, hx, hy, valid,
+                     c->geom, c->d_stamps.p, c->d_counts.p, qs_ord_base(c, seq0), c->d_counters.p);
     return hipGetLastError();
 }
 
@@ -152,12 +113,8 @@ __global__ void qs_edge_cast_kernel(unsigned int n_edge, const QsEdgeRec *__rest
 }
 hipError_t qs_launch_edge_cast(qs_ctx *c, unsigned int n_edge, const double *d_in)
 {
-    if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_edge_cast_kernel<true>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge.p, d_in, c->geom,
-                           c->d_stamps.p, c->d_counts.p, c->d_counters.p);
-    else
-        hipLaunchKernelGGL(qs_edge_cast_kernel<false>, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, n_edge, c->d_edge.p, d_in, c->geom,
-                           c->d_stamps.p, c->d_counts.p, c->d_counters.p);
+    qs_launch_counts(c, qs_edge_cast_kernel<true>, qs_edge_cast_kernel<false>, dim3((n_edge + 255) / 256), dim3(256), 0, n_edge, c->d_edge.p,
+                     d_in, c->geom, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     return hipGetLastError();
 }
 

@@ -47,30 +47,50 @@ __device__ inline void qs_mark_dirty(const QsGeom &geo, int x, int y)
 
 struct QsRay { double ex, ey; bool valid; };
 
+// Stamp of a ray's free cells: (ordinal << 1) | 0 with ordinal = the ray's arrival index + 1 (bit 0: the occupied bit of a cell
+// stamp).  Packets: arrival index ord_base + ord_stride * packet + sensor; sweeps: ord_base + ray slot.
+__host__ __device__ inline unsigned int qs_stamp_key(unsigned long long arrival) { return (unsigned int)((arrival + 1) << 1); }
+// the arrival index of sequence number seq0's first ray in the current stamp epoch, and the step from one packet to the next
+inline unsigned long long qs_ord_base(const qs_ctx *c, uint64_t seq0) { return 4ull * (seq0 - c->epoch_base); }
+inline unsigned long long qs_ord_stride(const qs_ctx *c) { return 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1); }
+
 // sin and cos of a ray heading: the device library's fp64 sincos (one argument reduction for both;
 // same bits as its separate sin and cos).  A Cody-Waite + fdlibm-kernel version for |a| < 1e5 was
 // measured at -2 us per 1 M packets on this pass and dropped: not worth a second implementation of a
 // value that decides cells.
 __device__ inline void qs_sincos(double x, double *sn, double *cs) { sincos(x, sn, cs); }
 
-// dual_bot_mapper.py:886-903: sensor order front(0), left(+pi/2), back(pi), right(-pi/2);
-// hit_valid = MIN < d <= MAX; invalid rays extend to min(d, MAX) if d > MIN else MAX and
-// only clear cells.  NaN compares false everywhere, which gives the reference's behaviour
-// (a 1.2 m free ray) without a special case.
+// The range rule of dual_bot_mapper.py:888 / :900 for the trust filter lo < d <= hi: hit_valid = lo < d <= hi; invalid rays
+// extend to min(d, hi) if d > lo else hi and only clear cells.  NaN compares false everywhere, which gives the reference's
+// behaviour (a full-length free ray) without a special case.  The host's exact-trig loop (qs_api.hip) applies the same rule.
+struct QsRange { bool valid; double range; };
+__host__ __device__ inline QsRange qs_range_rule(double d, double lo, double hi)
+{
+    QsRange g;
+    g.valid = (lo < d) && (d <= hi);                                                   // :888
+    g.range = g.valid ? d : ((d > lo) ? ((hi < d) ? hi : d) : hi);                     // :900
+    return g;
+}
+
+// end point of the ray of that range from (rx, ry) at heading a: one multiply and one add per axis (no FMA: the library is
+// built with -ffp-contract=off)
+__device__ inline QsRay qs_ray_end(double rx, double ry, double a, const QsRange &g)
+{
+    double sa, ca;
+    qs_sincos(a, &sa, &ca);
+    QsRay r;
+    r.valid = g.valid;
+    r.ex = rx + g.range * ca;                                                         // :890 / :901
+    r.ey = ry + g.range * sa;                                                         // :891 / :902
+    return r;
+}
+
+// dual_bot_mapper.py:886-903: sensor order front(0), left(+pi/2), back(pi), right(-pi/2)
 __device__ inline QsRay qs_project_ray(double rx, double ry, double yaw, double d, int s, const QsGeom &geo)
 {
     const double kPi = 3.141592653589793;   // math.pi
     const double ang = s == 0 ? 0.0 : (s == 1 ? kPi / 2 : (s == 2 ? kPi : -kPi / 2));   // :61-66
-    const double a = yaw + ang;                                                       // :887
-    QsRay r;
-    r.valid = (geo.min_dist < d) && (d <= geo.max_dist);                               // :888
-    const double range = r.valid ? d
-                       : ((d > geo.min_dist) ? ((geo.max_dist < d) ? geo.max_dist : d) : geo.max_dist);  // :900
-    double sa, ca;
-    qs_sincos(a, &sa, &ca);
-    r.ex = rx + range * ca;                                                           // :890 / :901
-    r.ey = ry + range * sa;                                                           // :891 / :902
-    return r;
+    return qs_ray_end(rx, ry, yaw + ang, qs_range_rule(d, geo.min_dist, geo.max_dist));   // :887
 }
 
 // Exact-trig mode.  The device library's sin / cos may differ from glibc's (the reference's math.cos / math.sin) in
@@ -147,6 +167,63 @@ __device__ inline unsigned int qs_cast_line(const QsLine &ln, bool valid, unsign
         if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
     }
     return cells;
+}
+
+// What every raycast kernel does with a projected ray before its cells.  Exact-trig mode: a ray on a cell edge is left to the
+// host (qs_edge_defer); otherwise the Bresenham set-up.  true: ln holds a line to walk or bin.
+// d: the raw range (the host projects from it again); beam: a sweep's beam index, -1 for the four rays of a QuasarPacket
+__device__ inline bool qs_ray_line(const QsRay &ray, double rx, double ry, double yaw, float d, unsigned int key_free, int beam,
+                                   const QsBatch &b, const QsGeom &geo, QsLine &ln)
+{
+    if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, rx, ry, yaw, d, key_free, beam))
+        return false;                                      // the host decides this ray's cells (qs_api.hip: sync_host_state)
+    return qs_line_setup(ray, rx, ry, geo, ln);
+}
+
+// The direct sink of a projected ray: deferred, or cast with one global atomic per cell; returns the cells written.
+template <bool COUNTS>
+__device__ inline unsigned int qs_ray_direct(const QsRay &ray, double rx, double ry, double yaw, float d, unsigned int key_free, int beam,
+                                             const QsBatch &b, const QsGeom &geo, unsigned int *__restrict__ stamps,
+                                             unsigned long long *__restrict__ counts)
+{
+    QsLine ln;
+    if (!qs_ray_line(ray, rx, ry, yaw, d, key_free, beam, b, geo, ln)) return 0;
+    return qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
+}
+
+// A thread's counts of what it cast, folded into the workgroup's LDS words s_cnt[QS_TALLY_WORDS] (zeroed by qs_tally_init before
+// a barrier) and, after another barrier, flushed by one thread with one atomic per counter.  accepted: the sweep kernels' accepted
+// records (the packet path's datagrams and accepted packets are the decoder's to count).
+#define QS_TALLY_WORDS 4
+struct QsTally { unsigned int rays = 0, cells = 0, hits = 0, accepted = 0; };
+
+__device__ inline void qs_tally_init(unsigned int *s_cnt, int tid) { if (tid < QS_TALLY_WORDS) s_cnt[tid] = 0; }
+__device__ inline void qs_tally_fold(const QsTally &t, unsigned int *s_cnt)
+{
+    if (t.rays) atomicAdd(&s_cnt[0], t.rays);
+    if (t.cells) atomicAdd(&s_cnt[1], t.cells);
+    if (t.hits) atomicAdd(&s_cnt[2], t.hits);
+    if (t.accepted) atomicAdd(&s_cnt[3], t.accepted);
+}
+__device__ inline void qs_tally_flush(const unsigned int *s_cnt, unsigned long long *__restrict__ counters)
+{
+    if (s_cnt[0]) atomicAdd(&counters[QS_CNT_RAYS], (unsigned long long)s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)s_cnt[1]);
+    if (s_cnt[2]) atomicAdd(&counters[QS_CNT_HITS], (unsigned long long)s_cnt[2]);
+}
+// the sweep kernels' form: the workgroup's records are datagrams that no decoder has counted
+__device__ inline void qs_tally_flush(const unsigned int *s_cnt, unsigned long long *__restrict__ counters, unsigned long long datagrams)
+{
+    atomicAdd(&counters[QS_CNT_DATAGRAMS], datagrams);
+    if (s_cnt[3]) atomicAdd(&counters[QS_CNT_ACCEPTED], (unsigned long long)s_cnt[3]);
+    qs_tally_flush(s_cnt, counters);
+}
+
+// Host side: launches the COUNTS = true or the COUNTS = false instantiation of a kernel, as the context was created.
+template <typename... P, typename... A>
+inline void qs_launch_counts(const qs_ctx *c, void (*on)(P...), void (*off)(P...), dim3 grid, dim3 block, size_t lds, A... args)
+{
+    hipLaunchKernelGGL(c->cfg.enable_counts ? on : off, grid, block, lds, c->stream, args...);
 }
 
 // Bounding box of a bot's hit points and path (compute_bounding_box, dual_bot_mapper.py:702-706),

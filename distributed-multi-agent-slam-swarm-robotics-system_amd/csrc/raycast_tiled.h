@@ -2,7 +2,7 @@
 // passes B1 / C / D over any array of ray slots.  Pass A has two producers: qs_rays_kernel (4 rays per packet,
 // raycast_tiled.hip) and qs_sweep_rays_kernel (184 ray slots per servo sweep, sweep.hip).
 #pragma once
-#include "qs_internal.h"
+#include "raycast_common.h"
 
 #define QT_TILE 64                       // tile edge in cells: 64 x 64 x u32 = 16 KiB of LDS
 #define QT_TILE_SHIFT 6
@@ -51,11 +51,38 @@ __device__ inline void qt_tile_range(int x0, int y0, int x1, int y1, int size, i
     ty_lo = ylo >> QT_TILE_SHIFT; ty_hi = yhi >> QT_TILE_SHIFT;
 }
 
+// The tiled sink of a projected ray (pass A; arguments as qs_ray_direct's): deferred to the host, or binned -- its cells lie in
+// at most 2 x 2 tiles, each of which gets one record in pass C, counted here in the workgroup's histogram s_hist -- or, when
+// it is longer than a tile (fine resolutions), cast directly, its cells added to `cells`.  Returns the ray-slot record.
+template <bool COUNTS>
+__device__ inline uint2 qt_ray_bin(const QsRay &ray, double rx, double ry, double yaw, float d, unsigned int key_free, int beam,
+                                   const QsBatch &b, const QsGeom &geo, const QtWorkspace &ws, unsigned int *s_hist,
+                                   unsigned int *__restrict__ stamps, unsigned long long *__restrict__ counts, unsigned int &cells)
+{
+    QsLine ln;
+    if (!qs_ray_line(ray, rx, ry, yaw, d, key_free, beam, b, geo, ln)) return make_uint2((unsigned int)QT_NO_RAY & 0xffffu, 0u);
+    if (ln.dx >= QT_TILE || ln.dy >= QT_TILE) {
+        cells += qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
+        return make_uint2((unsigned int)QT_NO_RAY & 0xffffu, 0u);
+    }
+    int tx_lo, tx_hi, ty_lo, ty_hi;
+    qt_tile_range(ln.x0, ln.y0, ln.x1, ln.y1, geo.size, tx_lo, tx_hi, ty_lo, ty_hi);
+    const int t00 = ty_lo * ws.tiles_x + tx_lo;
+    const bool wx = tx_hi > tx_lo, wy = ty_hi > ty_lo;      // dx, dy < 64: at most one boundary each
+    atomicAdd(&s_hist[t00], 1u);
+    if (wx) atomicAdd(&s_hist[t00 + 1], 1u);
+    if (wy) atomicAdd(&s_hist[t00 + ws.tiles_x], 1u);
+    if (wx && wy) atomicAdd(&s_hist[t00 + ws.tiles_x + 1], 1u);
+    return make_uint2(((unsigned int)ln.x0 & 0xffffu) | ((unsigned int)ln.y0 << 16),
+                      ((unsigned int)ln.x1 & 0xffffu) | ((unsigned int)ln.y1 << 16));
+}
+
 // host side (raycast_tiled.hip).  qt_workspace: grows the context's workspace for up to cap_rays ray slots and carves it;
 // the caller fills nwg, pk_per_wg / rays_per_wg.  qt_dyn_lds: bytes of pass A / C's LDS histogram (large grids raise the
-// kernels' limit: `kernels` lists the pass-A kernels beside qs_scatter_kernel).  qt_launch_sort_raster: passes B1, C, D
-// over ray slots [0, n_rays) whose hit flags are hit_valid[r] and whose stamps are (ord_base + ord_stride * (r >> 2) + (r & 3) + 1) << 1.
+// kernels' limit: on / off are the two instantiations of the pass-A kernel beside qs_scatter_kernel).  qt_launch_sort_raster:
+// passes B1, C, D over ray slots [0, n_rays) whose hit flags are hit_valid[r] and whose stamps are
+// qs_stamp_key(ord_base + ord_stride * (r >> 2) + (r & 3)).
 hipError_t qt_workspace(qs_ctx *c, size_t cap_rays, QtWorkspace &ws);
-hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *const *kernels, int n_kernels, size_t &lds);
+hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *on, const void *off, size_t &lds);
 hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays, const unsigned char *hit_valid,
                                  unsigned long long ord_base, unsigned long long ord_stride, size_t lds);

@@ -38,18 +38,18 @@ qs_rays_kernel(size_t n, QsBatch b, QsGeom geo, QtWorkspace ws, unsigned int *__
 {
     extern __shared__ unsigned int s_hist[];                       // [n_tiles]
     __shared__ double s_zone[QS_MAX_AGENT + 1][4];
-    __shared__ unsigned int s_cnt[3];
+    __shared__ unsigned int s_cnt[QS_TALLY_WORDS];
     const int tid = threadIdx.x;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) s_hist[t] = 0;
     for (int t = tid; t <= max_agent; t += QT_BIN_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
-    if (tid < 3) s_cnt[tid] = 0;
+    qs_tally_init(s_cnt, tid);
     __syncthreads();
 
     // one THREAD per ray (4 per packet): small per-thread state, so twice the waves of a
     // thread-per-packet form fit a SIMD, and every store of the pass is a full coalesced row
     const size_t r0 = 4 * (size_t)blockIdx.x * ws.pk_per_wg;
     const size_t r1 = (r0 + 4 * ws.pk_per_wg < 4 * n) ? r0 + 4 * ws.pk_per_wg : 4 * n;
-    unsigned int my_cells = 0, my_rays = 0, my_hits = 0;
+    QsTally my;
     // the inputs of the NEXT ray are requested before the current one is processed: a thread's rays
     // are 256 packets apart, so every iteration would otherwise start with a full HBM round trip
     unsigned char acc_n = 0, agent_n = 0;
@@ -80,61 +80,20 @@ qs_rays_kernel(size_t n, QsBatch b, QsGeom geo, QtWorkspace ws, unsigned int *__
             // compute_bounding_box over hits U path (:702-706, :930-940): exact min/max, any order
             if (s == 0) qs_zone_point(s_zone, agent, rx, ry);                // paths[agent].append  :878-879
             if (valid) qs_zone_point(s_zone, agent, ray.ex, ray.ey);         // point_clouds[..].append  :892
-            my_hits += valid ? 1u : 0u;
-            my_rays++;
-            QsLine ln;
-            if (b.edge && qs_edge_ray(ray, geo) &&
-                qs_edge_defer(b, rx, ry, yaw, df, (unsigned int)((ord_base + ord_stride * i + s + 1) << 1))) {
-                // the host decides this ray's cells (qs_api.hip: sync_host_state)
-            } else if (qs_line_setup(ray, rx, ry, geo, ln)) {
-                if (ln.dx < QT_TILE && ln.dy < QT_TILE) {
-                    // the ray's cells lie in at most 2 x 2 tiles
-                    int tx_lo, tx_hi, ty_lo, ty_hi;
-                    qt_tile_range(ln.x0, ln.y0, ln.x1, ln.y1, geo.size, tx_lo, tx_hi, ty_lo, ty_hi);
-                    const int t00 = ty_lo * ws.tiles_x + tx_lo;
-                    const bool wx = tx_hi > tx_lo, wy = ty_hi > ty_lo;      // dx, dy < 64: at most one boundary each
-                    atomicAdd(&s_hist[t00], 1u);
-                    if (wx) atomicAdd(&s_hist[t00 + 1], 1u);
-                    if (wy) atomicAdd(&s_hist[t00 + ws.tiles_x], 1u);
-                    if (wx && wy) atomicAdd(&s_hist[t00 + ws.tiles_x + 1], 1u);
-                    rec = make_uint2(((unsigned int)ln.x0 & 0xffffu) | ((unsigned int)ln.y0 << 16),
-                                     ((unsigned int)ln.x1 & 0xffffu) | ((unsigned int)ln.y1 << 16));
-                } else {
-                    // long ray (fine resolution): direct global atomics, as raycast.hip
-                    const unsigned int key_free = (unsigned int)((ord_base + ord_stride * i + s + 1) << 1);
-                    int x = ln.x0, y = ln.y0, err = ln.dx - ln.dy;
-                    for (;;) {
-                        const bool last = (x == ln.x1 && y == ln.y1);
-                        if ((!last || valid) && x >= 0 && x < geo.size && y >= 0 && y < geo.size) {
-                            const size_t c = (size_t)y * geo.size + x;
-                            atomicMax(&stamps[c], key_free | (last ? 1u : 0u));
-                            qs_mark_dirty(geo, x, y);
-                            if (COUNTS) atomicAdd(&counts[c], last ? (1ull << 32) : 1ull);
-                            my_cells++;
-                        }
-                        if (last) break;
-                        const int e2 = 2 * err;
-                        if (e2 > -ln.dy) { err -= ln.dy; x += ln.sx; }
-                        if (e2 < ln.dx) { err += ln.dx; y += ln.sy; }
-                    }
-                }
-            }
+            my.hits += valid ? 1u : 0u;
+            my.rays++;
+            rec = qt_ray_bin<COUNTS>(ray, rx, ry, yaw, df, qs_stamp_key(ord_base + ord_stride * i + s), -1, b, geo, ws, s_hist,
+                                     stamps, counts, my.cells);
         }
         ws.rays[r] = rec;
         b.hit_valid[r] = valid ? 1 : 0;
     }
-    if (my_rays) atomicAdd(&s_cnt[0], my_rays);
-    if (my_cells) atomicAdd(&s_cnt[1], my_cells);
-    if (my_hits) atomicAdd(&s_cnt[2], my_hits);
+    qs_tally_fold(my, s_cnt);
     __syncthreads();
     unsigned int *row = ws.table + (size_t)blockIdx.x * ws.n_tiles;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) row[t] = s_hist[t];
     for (int t = tid; t <= max_agent; t += QT_BIN_BLOCK) qs_zone_commit(s_zone, t, zone);
-    if (tid == 0) {
-        if (s_cnt[0]) atomicAdd(&counters[QS_CNT_RAYS], (unsigned long long)s_cnt[0]);
-        if (s_cnt[1]) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)s_cnt[1]);
-        if (s_cnt[2]) atomicAdd(&counters[QS_CNT_HITS], (unsigned long long)s_cnt[2]);
-    }
+    if (tid == 0) qs_tally_flush(s_cnt, counters);
 }
 
 // ---- pass B1: per tile, exclusive scan of its table column over the workgroups -------------------
@@ -472,16 +431,17 @@ hipError_t qt_workspace(qs_ctx *c, size_t cap_rays, QtWorkspace &ws)
     return hipSuccess;
 }
 
-hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *const *kernels, int n_kernels, size_t &lds)
+hipError_t qt_dyn_lds(const QtWorkspace &ws, const void *on, const void *off, size_t &lds)
 {
     lds = (size_t)ws.n_tiles * sizeof(unsigned int);
     if (lds <= 32 * 1024) return hipSuccess;
     // large grids (up to 8192^2: 16384 tiles) need more dynamic LDS than the 64 KiB default allows
     // next to the static arrays; the CU has 160 KiB
-    hipError_t ea = hipFuncSetAttribute((const void *)qs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    for (int k = 0; k < n_kernels && ea == hipSuccess; k++)
-        ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return ea;
+    for (const void *k : {(const void *)qs_scatter_kernel, on, off}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays, const unsigned char *hit_valid,
@@ -501,12 +461,8 @@ hipError_t qt_launch_sort_raster(qs_ctx *c, const QtWorkspace &ws, size_t n_rays
     static const int env_wgs = [] { const char *e = getenv("QS_RASTER_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : QT_RASTER_WGS; }();
     const unsigned int raster_wgs = (unsigned int)(max_items < (size_t)env_wgs ? max_items : (size_t)env_wgs);
     StageTimer t_raster(c, QS_STAGE_RC_RASTER);
-    if (c->cfg.enable_counts)
-        hipLaunchKernelGGL(qs_raster_kernel<true>, dim3(raster_wgs), dim3(QT_BLOCK), 0, c->stream, ws,
-                           c->cfg.size, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
-    else
-        hipLaunchKernelGGL(qs_raster_kernel<false>, dim3(raster_wgs), dim3(QT_BLOCK), 0, c->stream, ws,
-                           c->cfg.size, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
+    qs_launch_counts(c, qs_raster_kernel<true>, qs_raster_kernel<false>, dim3(raster_wgs), dim3(QT_BLOCK), 0, ws, c->cfg.size,
+                     c->d_stamps.p, c->d_counts.p, c->d_counters.p);
     t_raster.stop();
     return hipGetLastError();
 }
@@ -525,20 +481,13 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
     ws.rays_per_wg = 4 * per;
     ws.nwg = (int)((n + per - 1) / per);
 
-    const unsigned long long ord_base = 4ull * (seq0 - c->epoch_base);
-    const unsigned long long ord_stride = 4ull * (unsigned long long)(c->cfg.seq_stride > 0 ? c->cfg.seq_stride : 1);
-    const void *pass_a[2] = {(const void *)qs_rays_kernel<true>, (const void *)qs_rays_kernel<false>};
+    const unsigned long long ord_base = qs_ord_base(c, seq0), ord_stride = qs_ord_stride(c);
     size_t lds = 0;
-    e = qt_dyn_lds(ws, pass_a, 2, lds);
+    e = qt_dyn_lds(ws, (const void *)qs_rays_kernel<true>, (const void *)qs_rays_kernel<false>, lds);
     if (e != hipSuccess) return e;
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
-    if (c->cfg.enable_counts) {
-        hipLaunchKernelGGL(qs_rays_kernel<true>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
-    } else {
-        hipLaunchKernelGGL(qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, n, c->b, c->geom, ws,
-                           c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
-    }
+    qs_launch_counts(c, qs_rays_kernel<true>, qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, n, c->b, c->geom, ws,
+                     c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
     t_rays.stop();
     return qt_launch_sort_raster(c, ws, 4 * n, c->b.hit_valid, ord_base, ord_stride, lds);
 }

@@ -35,15 +35,7 @@
 __device__ inline QsRay sw_beam(const SwHead &h, int i, double d, double smin, double smax)
 {
     const double kRad = 3.141592653589793 / 180.0;
-    const double a = h.yaw + (double)(i - 90) * kRad;
-    QsRay r;
-    r.valid = (smin < d) && (d <= smax);
-    const double range = r.valid ? d : ((d > smin) ? ((smax < d) ? smax : d) : smax);
-    double sa, ca;
-    qs_sincos(a, &sa, &ca);
-    r.ex = h.rx + range * ca;
-    r.ey = h.ry + range * sa;
-    return r;
+    return qs_ray_end(h.rx, h.ry, h.yaw + (double)(i - 90) * kRad, qs_range_rule(d, smin, smax));
 }
 
 __device__ inline void sw_out(const QsSweepArgs &a, size_t k, const SwHead &h)
@@ -91,15 +83,15 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
     constexpr int NW = QT_BIN_BLOCK / QS_WAVE;
     extern __shared__ unsigned int s_hist[];                       // [n_tiles]
     __shared__ unsigned int s_rec[NW][SW_DW];
-    __shared__ unsigned int s_cnt[4];
+    __shared__ unsigned int s_cnt[QS_TALLY_WORDS];
     __shared__ double s_zone[GRAPH ? QS_MAX_AGENT + 1 : 1][4];
     const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) s_hist[t] = 0;
     if (GRAPH) for (int t = tid; t <= a.max_agent; t += QT_BIN_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
-    if (tid < 4) s_cnt[tid] = 0;
+    qs_tally_init(s_cnt, tid);
     const size_t k0 = (size_t)blockIdx.x * ws.pk_per_wg;
     const size_t k1 = (k0 + ws.pk_per_wg < a.n) ? k0 + ws.pk_per_wg : a.n;
-    unsigned int my_cells = 0, my_rays = 0, my_hits = 0, my_acc = 0;
+    QsTally my;
     for (size_t kb = k0; kb < k1; kb += NW) {                     // (uniform over the workgroup)
         const size_t k = kb + wave;
         __syncthreads();                                           // the previous round's records are parsed
@@ -110,7 +102,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
         SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
-        if (lane == 0) { sw_out(a, k, h); my_acc += h.ok ? 1u : 0u; }
+        if (lane == 0) { sw_out(a, k, h); my.accepted += h.ok ? 1u : 0u; }
         SwBox box = sw_box(h);
         #pragma unroll
         for (int q = 0; q < 3; q++) {
@@ -124,49 +116,22 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
                 const QsRay ray = sw_beam(h, i, (double)df, a.smin, a.smax);
                 valid = ray.valid;
                 if (GRAPH && valid) sw_box_point(box, ray.ex, ray.ey);         // point_clouds[..].append  :892
-                my_hits += valid ? 1u : 0u;
-                my_rays++;
-                const unsigned int key_free = (unsigned int)((a.ord_base + r + 1) << 1);
-                QsLine ln;
-                if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, h.rx, h.ry, h.yaw, df, key_free, i)) {
-                    // the host decides this beam's cells (qs_api.hip: sync_host_state)
-                } else if (qs_line_setup(ray, h.rx, h.ry, geo, ln)) {
-                    if (ln.dx < QT_TILE && ln.dy < QT_TILE) {
-                        int tx_lo, tx_hi, ty_lo, ty_hi;
-                        qt_tile_range(ln.x0, ln.y0, ln.x1, ln.y1, geo.size, tx_lo, tx_hi, ty_lo, ty_hi);
-                        const int t00 = ty_lo * ws.tiles_x + tx_lo;
-                        const bool wx = tx_hi > tx_lo, wy = ty_hi > ty_lo;
-                        atomicAdd(&s_hist[t00], 1u);
-                        if (wx) atomicAdd(&s_hist[t00 + 1], 1u);
-                        if (wy) atomicAdd(&s_hist[t00 + ws.tiles_x], 1u);
-                        if (wx && wy) atomicAdd(&s_hist[t00 + ws.tiles_x + 1], 1u);
-                        rec = make_uint2(((unsigned int)ln.x0 & 0xffffu) | ((unsigned int)ln.y0 << 16),
-                                         ((unsigned int)ln.x1 & 0xffffu) | ((unsigned int)ln.y1 << 16));
-                    } else {
-                        my_cells += qs_cast_line<COUNTS>(ln, valid, key_free, geo, stamps, counts);   // long ray (fine resolution)
-                    }
-                }
+                my.hits += valid ? 1u : 0u;
+                my.rays++;
+                rec = qt_ray_bin<COUNTS>(ray, h.rx, h.ry, h.yaw, df, qs_stamp_key(a.ord_base + r), i, b, geo, ws, s_hist, stamps, counts,
+                                         my.cells);
             }
             ws.rays[r] = rec;
             hit_valid[r] = valid ? 1 : 0;
         }
         if (GRAPH && h.ok) sw_box_commit(box, s_zone, h.agent, lane);
     }
-    if (my_rays) atomicAdd(&s_cnt[0], my_rays);
-    if (my_cells) atomicAdd(&s_cnt[1], my_cells);
-    if (my_hits) atomicAdd(&s_cnt[2], my_hits);
-    if (my_acc) atomicAdd(&s_cnt[3], my_acc);
+    qs_tally_fold(my, s_cnt);
     __syncthreads();
     unsigned int *row = ws.table + (size_t)blockIdx.x * ws.n_tiles;
     for (int t = tid; t < ws.n_tiles; t += QT_BIN_BLOCK) row[t] = s_hist[t];
     if (GRAPH) for (int t = tid; t <= a.max_agent; t += QT_BIN_BLOCK) qs_zone_commit(s_zone, t, a.zone);
-    if (tid == 0) {
-        atomicAdd(&counters[QS_CNT_DATAGRAMS], (unsigned long long)(k1 - k0));
-        if (s_cnt[3]) atomicAdd(&counters[QS_CNT_ACCEPTED], (unsigned long long)s_cnt[3]);
-        if (s_cnt[0]) atomicAdd(&counters[QS_CNT_RAYS], (unsigned long long)s_cnt[0]);
-        if (s_cnt[1]) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)s_cnt[1]);
-        if (s_cnt[2]) atomicAdd(&counters[QS_CNT_HITS], (unsigned long long)s_cnt[2]);
-    }
+    if (tid == 0) qs_tally_flush(s_cnt, counters, (unsigned long long)(k1 - k0));
 }
 
 // ---- direct form: one wave per record, every cell one global atomic --------------------------------------------------------
@@ -177,21 +142,21 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 {
     constexpr int NW = SW_DIRECT_BLOCK / QS_WAVE;
     __shared__ unsigned int s_rec[NW][SW_DW];
-    __shared__ unsigned int s_cnt[4];
+    __shared__ unsigned int s_cnt[QS_TALLY_WORDS];
     __shared__ double s_zone[GRAPH ? QS_MAX_AGENT + 1 : 1][4];
     const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
-    if (tid < 4) s_cnt[tid] = 0;
+    qs_tally_init(s_cnt, tid);
     if (GRAPH) for (int t = tid; t <= a.max_agent; t += SW_DIRECT_BLOCK) QS_ZONE_LDS_INIT(s_zone, t);
     const size_t k = (size_t)blockIdx.x * NW + wave;
     sw_stage(a, k, s_rec[wave], lane);
     __syncthreads();
-    unsigned int my_cells = 0, my_rays = 0, my_hits = 0;
+    QsTally my;
     if (k < a.n) {
         const unsigned int *s = s_rec[wave];
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
         SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
-        if (lane == 0) { sw_out(a, k, h); if (h.ok) atomicAdd(&s_cnt[3], 1u); }
+        if (lane == 0) { sw_out(a, k, h); my.accepted = h.ok ? 1u : 0u; }
         if (h.ok) {
             SwBox box = sw_box(h);
             #pragma unroll
@@ -201,31 +166,20 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
                 const float df = __uint_as_float(sw_u32(s, mis, a.ranges_off + 4u * (unsigned int)i));
                 const QsRay ray = sw_beam(h, i, (double)df, a.smin, a.smax);
                 if (GRAPH && ray.valid) sw_box_point(box, ray.ex, ray.ey);     // point_clouds[..].append  :892
-                my_hits += ray.valid ? 1u : 0u;
-                my_rays++;
-                const unsigned int key_free = (unsigned int)((a.ord_base + QS_SWEEP_SLOTS * k + i + 1) << 1);
-                QsLine ln;
-                if (b.edge && qs_edge_ray(ray, geo) && qs_edge_defer(b, h.rx, h.ry, h.yaw, df, key_free, i)) {
-                    // the host decides this beam's cells (qs_api.hip: sync_host_state)
-                } else if (qs_line_setup(ray, h.rx, h.ry, geo, ln)) {
-                    my_cells += qs_cast_line<COUNTS>(ln, ray.valid, key_free, geo, stamps, counts);
-                }
+                my.hits += ray.valid ? 1u : 0u;
+                my.rays++;
+                my.cells += qs_ray_direct<COUNTS>(ray, h.rx, h.ry, h.yaw, df, qs_stamp_key(a.ord_base + QS_SWEEP_SLOTS * k + i), i, b, geo,
+                                                  stamps, counts);
             }
             if (GRAPH) sw_box_commit(box, s_zone, h.agent, lane);
         }
     }
-    if (my_rays) atomicAdd(&s_cnt[0], my_rays);
-    if (my_cells) atomicAdd(&s_cnt[1], my_cells);
-    if (my_hits) atomicAdd(&s_cnt[2], my_hits);
+    qs_tally_fold(my, s_cnt);
     __syncthreads();
     if (GRAPH) for (int t = tid; t <= a.max_agent; t += SW_DIRECT_BLOCK) qs_zone_commit(s_zone, t, a.zone);
     if (tid == 0) {
         const size_t k0 = (size_t)blockIdx.x * NW;
-        atomicAdd(&counters[QS_CNT_DATAGRAMS], (unsigned long long)(a.n - k0 < (size_t)NW ? a.n - k0 : (size_t)NW));
-        if (s_cnt[3]) atomicAdd(&counters[QS_CNT_ACCEPTED], (unsigned long long)s_cnt[3]);
-        if (s_cnt[0]) atomicAdd(&counters[QS_CNT_RAYS], (unsigned long long)s_cnt[0]);
-        if (s_cnt[1]) atomicAdd(&counters[QS_CNT_CELLS], (unsigned long long)s_cnt[1]);
-        if (s_cnt[2]) atomicAdd(&counters[QS_CNT_HITS], (unsigned long long)s_cnt[2]);
+        qs_tally_flush(s_cnt, counters, (unsigned long long)(a.n - k0 < (size_t)NW ? a.n - k0 : (size_t)NW));
     }
 }
 
@@ -236,12 +190,8 @@ static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, 
 {
     if (!tiled || !qs_tiled_supported(c)) {
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
-        if (c->cfg.enable_counts)
-            hipLaunchKernelGGL((qs_sweep_direct_kernel<true, CORR, GRAPH>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
-                               c->d_stamps.p, c->d_counts.p, c->d_counters.p);
-        else
-            hipLaunchKernelGGL((qs_sweep_direct_kernel<false, CORR, GRAPH>), dim3(blocks), dim3(SW_DIRECT_BLOCK), 0, c->stream, a, c->b, c->geom,
-                               c->d_stamps.p, c->d_counts.p, c->d_counters.p);
+        qs_launch_counts(c, qs_sweep_direct_kernel<true, CORR, GRAPH>, qs_sweep_direct_kernel<false, CORR, GRAPH>, dim3(blocks),
+                         dim3(SW_DIRECT_BLOCK), 0, a, c->b, c->geom, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         return hipGetLastError();
     }
     QtWorkspace ws;
@@ -254,19 +204,15 @@ static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, 
     ws.pk_per_wg = per;
     ws.rays_per_wg = QS_SWEEP_SLOTS * per;
     ws.nwg = (int)((n + per - 1) / per);
-    const void *pass_a[2] = {(const void *)qs_sweep_rays_kernel<true, CORR, GRAPH>, (const void *)qs_sweep_rays_kernel<false, CORR, GRAPH>};
+    const auto on = qs_sweep_rays_kernel<true, CORR, GRAPH>, off = qs_sweep_rays_kernel<false, CORR, GRAPH>;
     size_t lds = 0;
-    e = qt_dyn_lds(ws, pass_a, 2, lds);
+    e = qt_dyn_lds(ws, (const void *)on, (const void *)off, lds);
     if (e != hipSuccess) return e;
     StageTimer t_rays(c, QS_STAGE_RC_RAYS);
-    if (c->cfg.enable_counts)
-        hipLaunchKernelGGL((qs_sweep_rays_kernel<true, CORR, GRAPH>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
-                           hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
-    else
-        hipLaunchKernelGGL((qs_sweep_rays_kernel<false, CORR, GRAPH>), dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, c->stream, a, c->b, c->geom, ws,
-                           hit_valid, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
+    qs_launch_counts(c, on, off, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, a, c->b, c->geom, ws, hit_valid, c->d_stamps.p, c->d_counts.p,
+                     c->d_counters.p);
     t_rays.stop();
-    // slot r = 184 k + i has stamp ordinal ord_base + 4 (r >> 2) + (r & 3) + 1 = ord_base + r + 1: the 4-ray layout's
+    // slot r = 184 k + i has arrival index ord_base + 4 (r >> 2) + (r & 3) = ord_base + r: the 4-ray layout's
     return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);
 }
 
@@ -299,7 +245,7 @@ static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_
     QsSweepArgs a;
     qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     a.accept = accept; a.pose = pose;
-    a.ord_base = 4ull * (seq0 - c->epoch_base);
+    a.ord_base = qs_ord_base(c, seq0);
     a.corr = corr;
     if (a.g_accept) return corr ? qs_launch_sweeps_t<true, true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, true>(c, a, n, tiled, hit_valid);
     return corr ? qs_launch_sweeps_t<true, false>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, false>(c, a, n, tiled, hit_valid);
@@ -333,7 +279,7 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 
 // records [k0, k0 + m) of the call, at d_pkts (already offset to record k0); graph: the call runs in graph mode
 static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0,
-                        bool graph, const qs_sweep_match *corr = nullptr)
+                        bool graph, const qs_sweep_match *corr)
 {
     const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
     int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
@@ -348,83 +294,79 @@ static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t strid
     return QS_OK;
 }
 
-// Graph mode (qs_set_sweep_graph): before any chunk is mapped or matched, the pass over the whole call that decides every record,
-// adds the nodes and runs the chain (sweep_graph.hip).  Every later launch of the call is then told which record of the call its
-// records start at (graph_k0), and reads acceptance, agent and pose from that slice of the batch
-static int sweeps_graph_pass(qs_ctx *c, const uint8_t *pkts, bool host, size_t n, size_t stride, const uint16_t *lens, bool &graph)
+// The four entry points' one routine.  host: pkts / lens are the caller's host buffers, staged one chunk at a time into the one
+// staging block (stream-ordered: the previous chunk's kernels have read theirs), and the call ends by waiting for the GPU.
+// matched: the matched ingest (semantics in include/quasar_slam.h, "sweep matching"; params as qs_match_setup takes them): every
+// record of the call is matched against the map as it stands before the call (match.hip), then the records are mapped chunk by
+// chunk from their corrected poses.
+static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params, const uint8_t *pkts, bool host, size_t n, size_t stride,
+                         const uint16_t *lens, uint64_t seq0)
 {
-    graph = c->sweep_graph;
-    return graph ? qs_sweep_graph_pass(c, pkts, host, n, stride, lens, QS_SWEEP_CHUNK) : QS_OK;
-}
-
-static void sweeps_end(qs_ctx *c, size_t n, uint64_t seq0, bool graph)
-{
+    QsMatchSetup setup;
+    const QsMatchSetup *ms = matched ? &setup : nullptr;
+    int rc = matched ? qs_match_setup(c, params, "qs_ingest_sweeps_matched", setup) : QS_OK;
+    if (rc != QS_OK) return rc;
+    rc = sweeps_begin(c, n, stride, seq0);
+    if (rc != QS_OK || n == 0) return rc;
+    if (ms) {
+        HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
+        SYNCCHK(c);                                        // the matcher reads the map: waiting edge beams go in first
+    }
+    // Graph mode (qs_set_sweep_graph): before any chunk is mapped or matched, the pass over the whole call that decides every
+    // record, adds the nodes and runs the chain (sweep_graph.hip; a host call stages every chunk for it once more).  Every later
+    // launch of the call is then told which record of the call its records start at, and reads acceptance, agent and pose from
+    // that slice of the batch -- the match starts from the chain's poses
+    const bool graph = c->sweep_graph;
+    if (graph) {
+        rc = qs_sweep_graph_pass(c, pkts, host, n, stride, lens, QS_SWEEP_CHUNK);
+        if (rc != QS_OK) return rc;
+    }
+    qs_sweep_match *corr = ms ? c->match_out.p : nullptr;
+    if (ms && !host) HIPCHK(c, qs_launch_match(c, *ms, pkts, n, stride, lens, corr, nullptr, graph ? 0 : QS_SWEEP_NO_GRAPH));
+    // host and matched: the staging block holds one chunk, so a call of several chunks stages each of them twice, first (pass 0)
+    // to match them all against the map nobody has written yet, then (pass 1, the only one otherwise) to map them
+    const bool one = n <= QS_SWEEP_CHUNK;
+    for (int pass = (ms && host && !one) ? 0 : 1; pass < 2; pass++)
+        for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
+            const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
+            const uint8_t *d_pkts = pkts + k0 * stride;
+            const uint16_t *d_lens = lens ? lens + k0 : nullptr;
+            if (host) {
+                Staging s;
+                rc = reserve_staging(c, m * stride, s);
+                if (rc != QS_OK) return rc;
+                HIPCHK(c, hipMemcpyAsync(s.pkts, d_pkts, m * stride, hipMemcpyHostToDevice, c->stream));
+                if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, d_lens, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+                d_pkts = s.pkts; d_lens = lens ? s.lens : nullptr;
+                if (ms && (pass == 0 || one))
+                    HIPCHK(c, qs_launch_match(c, *ms, d_pkts, m, stride, d_lens, corr + k0, nullptr, graph ? k0 : QS_SWEEP_NO_GRAPH));
+            }
+            if (pass == 1) {
+                rc = sweeps_chunk(c, d_pkts, m, stride, d_lens, seq0, k0, graph, ms ? corr + k0 : nullptr);
+                if (rc != QS_OK) return rc;
+            }
+        }
     c->last_sweep_graph = graph;
     if (c->b.edge) c->edge_maybe = true;                   // resolved at the next point the map is observed (sync_host_state)
     c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
     c->last_sweeps = true; c->last_sweeps_n = n;
+    if (ms) { c->last_matches = true; c->last_matches_n = n; }
+    // host, as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
+    return host ? sync_host_state(c, true) : QS_OK;
 }
 
 extern "C" int qs_ingest_sweeps_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stride, const uint16_t *d_lens, uint64_t seq0)
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || d_pkts != nullptr);
-    int rc = sweeps_begin(c, n, stride, seq0);
-    if (rc != QS_OK || n == 0) return rc;
-    bool graph;
-    rc = sweeps_graph_pass(c, d_pkts, false, n, stride, d_lens, graph);
-    if (rc != QS_OK) return rc;
-    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
-        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, graph);
-        if (rc != QS_OK) return rc;
-    }
-    sweeps_end(c, n, seq0, graph);
-    return QS_OK;
+    return sweeps_ingest(c, false, nullptr, d_pkts, false, n, stride, d_lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0)
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || pkts != nullptr);
-    int rc = sweeps_begin(c, n, stride, seq0);
-    if (rc != QS_OK || n == 0) return rc;
-    // graph mode: every chunk is staged twice (the signature pass sees them all first)
-    bool graph;
-    rc = sweeps_graph_pass(c, pkts, true, n, stride, lens, graph);
-    if (rc != QS_OK) return rc;
-    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
-        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        Staging s;
-        rc = reserve_staging(c, m * stride, s);            // (stream-ordered: the previous chunk's kernels have read theirs)
-        if (rc != QS_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
-        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, graph);
-        if (rc != QS_OK) return rc;
-    }
-    sweeps_end(c, n, seq0, graph);
-    // as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
-    return sync_host_state(c, true);
-}
-
-// ---- matched ingest (semantics in include/quasar_slam.h, "sweep matching"): every record of the call is matched against the
-// map as it stands before the call (match.hip), then the records are mapped chunk by chunk from their corrected poses
-static int matched_begin(qs_ctx *c, const qs_match_params *params, size_t n, size_t stride, uint64_t &seq0, QsMatchSetup &ms)
-{
-    int rc = qs_match_setup(c, params, "qs_ingest_sweeps_matched", ms);
-    if (rc != QS_OK) return rc;
-    rc = sweeps_begin(c, n, stride, seq0);
-    if (rc != QS_OK || n == 0) return rc;
-    HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
-    SYNCCHK(c);                                            // the matcher reads the map: waiting edge beams go in first
-    return QS_OK;
-}
-
-static void matched_end(qs_ctx *c, size_t n, uint64_t seq0, bool graph)
-{
-    sweeps_end(c, n, seq0, graph);
-    c->last_matches = true; c->last_matches_n = n;
+    return sweeps_ingest(c, false, nullptr, pkts, true, n, stride, lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
@@ -432,20 +374,7 @@ extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params 
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || d_pkts != nullptr);
-    QsMatchSetup ms;
-    int rc = matched_begin(c, params, n, stride, seq0, ms);
-    if (rc != QS_OK || n == 0) return rc;
-    bool graph;                                            // graph mode: signature, chain, then the match from the chain's poses
-    rc = sweeps_graph_pass(c, d_pkts, false, n, stride, d_lens, graph);
-    if (rc != QS_OK) return rc;
-    HIPCHK(c, qs_launch_match(c, ms, d_pkts, n, stride, d_lens, c->match_out.p, nullptr, graph ? 0 : QS_SWEEP_NO_GRAPH));
-    for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
-        const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-        rc = sweeps_chunk(c, d_pkts + k0 * stride, m, stride, d_lens ? d_lens + k0 : nullptr, seq0, k0, graph, c->match_out.p + k0);
-        if (rc != QS_OK) return rc;
-    }
-    matched_end(c, n, seq0, graph);
-    return QS_OK;
+    return sweeps_ingest(c, true, params, d_pkts, false, n, stride, d_lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
@@ -453,33 +382,7 @@ extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || pkts != nullptr);
-    QsMatchSetup ms;
-    int rc = matched_begin(c, params, n, stride, seq0, ms);
-    if (rc != QS_OK || n == 0) return rc;
-    bool graph;                                            // graph mode: signature, chain, then the match from the chain's poses
-    rc = sweeps_graph_pass(c, pkts, true, n, stride, lens, graph);
-    if (rc != QS_OK) return rc;
-    // the staging block holds one chunk: a call of several chunks stages each of them twice, first to match them all against
-    // the map nobody has written yet, then to map them
-    const bool one = n <= QS_SWEEP_CHUNK;
-    for (int pass = one ? 1 : 0; pass < 2; pass++)
-        for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
-            const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
-            Staging s;
-            rc = reserve_staging(c, m * stride, s);        // (stream-ordered: the previous chunk's kernels have read theirs)
-            if (rc != QS_OK) return rc;
-            HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, m * stride, hipMemcpyHostToDevice, c->stream));
-            if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, m * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-            if (pass == 0 || one)
-                HIPCHK(c, qs_launch_match(c, ms, s.pkts, m, stride, lens ? s.lens : nullptr, c->match_out.p + k0, nullptr,
-                                          graph ? k0 : QS_SWEEP_NO_GRAPH));
-            if (pass == 1) {
-                rc = sweeps_chunk(c, s.pkts, m, stride, lens ? s.lens : nullptr, seq0, k0, graph, c->match_out.p + k0);
-                if (rc != QS_OK) return rc;
-            }
-        }
-    matched_end(c, n, seq0, graph);
-    return sync_host_state(c, true);
+    return sweeps_ingest(c, true, params, pkts, true, n, stride, lens, seq0);
 }
 
 extern "C" int qs_last_sweeps(qs_ctx *c, uint8_t *accepted, double *pose, size_t n)

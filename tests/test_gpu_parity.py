@@ -801,6 +801,36 @@ def test_odd_geometries_adversarial(pkg, size, res, span, mode):
         assert (m.frontier_cells() == orc.frontier_cells(o.grid)).all()
 
 
+@pytest.mark.parametrize("size,res,span", [(68, 0.05, 2.5), (132, 0.013, 1.2)], ids=["short_rays", "long_rays"])
+def test_counts_off_equals_counts_on(pkg, size, res, span):
+    """enable_counts=False selects the COUNTS = false instantiation of every raycast kernel (and the raster's other way of
+    counting written cells).  On two of test_odd_geometries_adversarial's geometries -- short rays on a grid that is no
+    multiple of the tile, long rays inside the tiled pipeline -- and its stream, direct and tiled, counts on and off, all
+    give the oracle's grid, one stamps array and the same ray / cell / hit / edge-ray counters."""
+    from test_gpu_sweeps import _stamps
+    replay = _replay(pkg)
+    origin = -size * res / 2
+    stream = replay.adversarial_stream(3000, seed=size * 7 + 1, lo=-span, hi=span)
+    rec = stream.view(pkg.protocol.PACKET_DTYPE).reshape(-1)
+    k = np.random.default_rng(size).integers(0, 3000, 200)
+    rec["front"][k[:50]] = np.nan; rec["left"][k[50:100]] = np.inf; rec["back"][k[100:150]] = 0.05; rec["right"][k[150:]] = 1.2
+    o = orc.OracleMapper(size, res, origin, origin, 0.0)
+    o.feed_stream(stream)
+    runs = {}
+    for mode in (1, 2):
+        for counts in (True, False):
+            with pkg.QuasarMapper(size, res, origin, origin, raycast_mode=mode, enable_counts=counts) as m:
+                m.ingest_array(stream[:1111]); m.ingest_array(stream[1111:])
+                assert (m.grid_i8() == o.grid).all(), (mode, counts)
+                c = m.counters()
+                runs[mode, counts] = (_stamps(pkg, m), {key: c[key] for key in ("rays", "cells", "hits", "edge_rays")})
+    first = runs[1, True]
+    assert first[1]["cells"] == o.n_cells_written
+    for key, (stamps, cnt) in runs.items():
+        assert (stamps == first[0]).all(), f"{key}: {(stamps != first[0]).sum()} stamps differ from (1, True)"
+        assert cnt == first[1], (key, cnt, first[1])
+
+
 def test_raster_long_runs_flush_and_tile_changes(pkg):
     """The persistent raster workgroups accumulate consecutive work items of a tile in LDS (16-bit counters:
     forced merge every 31 items) and merge when the tile changes.  With the default 1024 workgroups a run is

@@ -109,6 +109,37 @@ def test_random_sweeps_equal_the_oracle_and_direct_equals_tiled(pkg):
     assert stamps[0].max() <= 2 * 4 * 46 * n + 1
 
 
+def test_long_beams_take_the_direct_branch_of_the_tiled_pass(pkg):
+    """At 13 mm a 1.2 m beam spans 92 cells, more than a 64-cell tile: most beams of pass A leave the binning for the
+    direct walk.  Direct and tiled, counts on and off, equal the oracle; so does the matched ingest on the empty map
+    (nothing to match against: zero corrections), which runs the corrected instantiation of the same pass."""
+    P = _P(pkg)
+    n, G, res = 64, 260, 0.013
+    half = G * res / 2
+    buf = _random_sweeps(P, n, seed=13, lo=-0.9 * half, hi=0.9 * half)
+    o = orc.OracleMapper(G, res, -half, -half, 0.0)
+    o.update_rays(*_beams(_records(P, buf)))
+    stamps, cells = {}, {}
+    for mode in (1, 2):
+        for counts in (True, False):
+            with pkg.QuasarMapper(G, res, -half, -half, raycast_mode=mode, enable_counts=counts) as m:
+                m.ingest_sweeps(buf)
+                assert (m.grid_i8() == o.grid).all(), f"mode {mode}, counts {counts}: {(m.grid_i8() != o.grid).sum()} cells differ"
+                if counts:
+                    _same_map(m, o, f"mode {mode}")
+                    stamps[mode] = _stamps(pkg, m)
+                cells[mode, counts] = m.counters()["cells"]
+    assert (stamps[1] == stamps[2]).all(), f"{(stamps[1] != stamps[2]).sum()} stamps differ between direct and tiled"
+    assert len(set(cells.values())) == 1 and cells[1, True] == o.n_cells_written, cells
+    d_buf = torch.from_numpy(buf).cuda()
+    with pkg.QuasarMapper(G, res, -half, -half, raycast_mode=2) as m:
+        m.ingest_sweeps_matched_device(d_buf.data_ptr(), n, buf.shape[1])
+        m.sync()
+        mt = m.last_sweep_matches()
+        assert not (mt["dx"].any() or mt["dy"].any() or mt["dyaw"].any())
+        _same_map(m, o, "matched, device")
+
+
 def test_interleaved_with_packets_closures_and_separation(pkg):
     P = _P(pkg)
     g = np.load(os.path.join(GOLDEN, "session_sep_512.npz"), allow_pickle=False)

@@ -34,6 +34,15 @@ class QsGainParams(C.Structure):
 QS_GAIN_MAX_RANGE, QS_GAIN_DEFAULT_RANGE, QS_GAIN_DEFAULT_BIAS = 64, 24, 120     # include/quasar_slam.h, "frontier gain"
 
 
+class QsSenseParams(C.Structure):
+    """struct qs_sense_params (include/quasar_slam.h)."""
+    _fields_ = [("max_range", C.c_double), ("noise_amp", C.c_double), ("no_return", C.c_float), ("dropout_q16", C.c_uint32),
+                ("seed", C.c_uint64), ("first_record", C.c_uint64), ("reserved", C.c_int32 * 2)]
+
+
+QS_SENSE_MAX_CELLS = 255                                                         # include/quasar_slam.h, "sensing a world"
+
+
 class QsMatchParams(C.Structure):
     """struct qs_match_params (include/quasar_slam.h)."""
     _fields_ = [("radius", C.c_int32), ("window", C.c_int32), ("angle_steps", C.c_int32), ("min_hits", C.c_int32),
@@ -143,6 +152,12 @@ SIGNATURES = {
     "qs_ingest_sweeps_matched": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_ingest_sweeps_matched_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_last_sweep_matches": (_i32, [_vp, _vp, _sz]),
+    "qs_sense_ranges": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
+    "qs_sense_ranges_device": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
+    "qs_sense_sweeps": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
+    "qs_sense_sweeps_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
+    "qs_sense_packets": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "qs_sense_packets_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_last_hits": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),

@@ -464,6 +464,97 @@ class QuasarMapper:
         """Trust filter of sweep beams: a hit when smin < d <= smax (default: the reference's 0.1 < d <= 1.2)."""
         self._chk(self._L.qs_set_sweep_filter(self._h, float(smin), float(smax)), "qs_set_sweep_filter")
 
+    # -- sensing a world (include/quasar_slam.h, "sensing a world") -----------------------------------------------------------
+    @staticmethod
+    def sense_params(max_range=P.MAX_DIST_M, noise_amp=0.0, dropout=0.0, seed=0, first_record=0, no_return=0.0):
+        """A qs_sense_params: max_range and noise_amp in metres, dropout the share of hit beams that report no return (kept as
+        round(dropout * 65536) / 65536), seed and first_record the noise's stream, no_return what a beam without a hit reports."""
+        p = _lib.QsSenseParams()
+        p.max_range, p.noise_amp, p.no_return = float(max_range), float(noise_amp), float(no_return)
+        q = dropout * 65536.0
+        p.dropout_q16 = int(round(q)) if 0.0 <= q <= 65536.0 else 0xFFFFFFFF          # (the library refuses the rest)
+        p.seed, p.first_record = int(seed) & UINT64_MAX, int(first_record) & UINT64_MAX
+        return p
+
+    @staticmethod
+    def _sense_poses(pose_xyyaw):
+        pose = np.ascontiguousarray(pose_xyyaw, dtype=np.float32)
+        if pose.ndim != 2 or pose.shape[1] != 3:
+            raise ValueError("poses must be [n, 3]: x, y, yaw")
+        return pose
+
+    @staticmethod
+    def _sense_field(v, n, dtype, name):
+        if v is None:
+            return None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (n,)))
+        if a.shape != (n,):
+            raise ValueError(f"{name} must have one entry per pose")
+        return a
+
+    def sense_ranges(self, pose_xyyaw, beams=P.SWEEP_BEAMS, return_cells=False, **params):
+        """What each beam returns from each pose in this context's map -> float32 [n, beams] (beams: 181, a sweep, or 4, a
+        packet's sensors); with return_cells also int32 [n, beams], the hit cell gy * size + gx or -1.  Poses are world poses
+        float32 [n, 3]; keywords as sense_params.  Reads the map, writes nothing."""
+        pose = self._sense_poses(pose_xyyaw)
+        n = len(pose)
+        prm = self.sense_params(**params)
+        ranges = np.empty((n, int(beams)), dtype=np.float32)
+        cells = np.empty((n, int(beams)), dtype=np.int32) if return_cells else None
+        self._chk(self._L.qs_sense_ranges(self._h, _ptr(pose), n, int(beams), C.byref(prm), _ptr(ranges), _ptr(cells)), "qs_sense_ranges")
+        return (ranges, cells) if return_cells else ranges
+
+    def sense_ranges_device(self, d_pose, n, d_ranges, beams=P.SWEEP_BEAMS, d_cells=0, **params):
+        """sense_ranges with device-resident float32 poses and outputs (addresses or torch tensors); asynchronous."""
+        prm = self.sense_params(**params)
+        cells = _dev_addr(d_cells)
+        self._chk(self._L.qs_sense_ranges_device(self._h, C.c_void_p(_dev_addr(d_pose)), n, int(beams), C.byref(prm),
+                                                 C.c_void_p(_dev_addr(d_ranges)), C.c_void_p(cells) if cells else None),
+                  "qs_sense_ranges_device")
+
+    def sense_sweeps(self, pose_xyyaw, agent, enc=None, v2v=None, odometry=True, **params):
+        """The sweep packets bots at these poses would send -> uint8 [n, 751] (odometry) or [n, 743]: exactly
+        protocol.pack_sweeps of the same fields with the ranges of sense_ranges."""
+        pose = self._sense_poses(pose_xyyaw)
+        n = len(pose)
+        stride = P.PACKET_SIZE_V0_ODO if odometry else P.PACKET_SIZE_V0
+        prm = self.sense_params(**params)
+        out = np.empty((n, stride), dtype=np.uint8)
+        self._chk(self._L.qs_sense_sweeps(self._h, _ptr(pose), _ptr(self._sense_field(agent, n, np.uint8, "agent")),
+                                          _ptr(self._sense_field(enc, n, np.int32, "enc")), _ptr(self._sense_field(v2v, n, np.uint32, "v2v")),
+                                          n, C.byref(prm), _ptr(out), stride), "qs_sense_sweeps")
+        return out
+
+    def sense_sweeps_device(self, d_pose, d_agent, n, d_out, stride=P.PACKET_SIZE_V0_ODO, d_enc=0, d_v2v=0, **params):
+        """sense_sweeps with device-resident inputs and output (d_out: n * stride bytes at any address); asynchronous on the
+        context's stream.  What it writes is what ingest_sweeps_device of another context reads."""
+        prm = self.sense_params(**params)
+        opt = lambda a: C.c_void_p(_dev_addr(a)) if _dev_addr(a) else None
+        self._chk(self._L.qs_sense_sweeps_device(self._h, C.c_void_p(_dev_addr(d_pose)), C.c_void_p(_dev_addr(d_agent)), opt(d_enc),
+                                                 opt(d_v2v), n, C.byref(prm), C.c_void_p(_dev_addr(d_out)), int(stride)),
+                  "qs_sense_sweeps_device")
+
+    def sense_packets(self, pose_xyyaw, agent, enc=None, v2v=None, landmark=None, **params):
+        """The 42-byte packets bots at these poses would send -> uint8 [n, 42]: exactly protocol.pack_packets of the same fields
+        with the four ranges of sense_ranges(beams=4)."""
+        pose = self._sense_poses(pose_xyyaw)
+        n = len(pose)
+        prm = self.sense_params(**params)
+        out = np.empty((n, P.PACKET_SIZE), dtype=np.uint8)
+        self._chk(self._L.qs_sense_packets(self._h, _ptr(pose), _ptr(self._sense_field(agent, n, np.uint8, "agent")),
+                                           _ptr(self._sense_field(enc, n, np.int32, "enc")), _ptr(self._sense_field(v2v, n, np.uint32, "v2v")),
+                                           _ptr(self._sense_field(landmark, n, np.uint8, "landmark")), n, C.byref(prm), _ptr(out)),
+                  "qs_sense_packets")
+        return out
+
+    def sense_packets_device(self, d_pose, d_agent, n, d_out, d_enc=0, d_v2v=0, d_landmark=0, **params):
+        """sense_packets with device-resident inputs and output (n * 42 bytes); asynchronous on the context's stream."""
+        prm = self.sense_params(**params)
+        opt = lambda a: C.c_void_p(_dev_addr(a)) if _dev_addr(a) else None
+        self._chk(self._L.qs_sense_packets_device(self._h, C.c_void_p(_dev_addr(d_pose)), C.c_void_p(_dev_addr(d_agent)), opt(d_enc),
+                                                  opt(d_v2v), opt(d_landmark), n, C.byref(prm), C.c_void_p(_dev_addr(d_out))),
+                  "qs_sense_packets_device")
+
     # -- grid ---------------------------------------------------------------------------------
     def grid_i8(self):
         out = np.empty((self.size, self.size), dtype=np.int8)

@@ -694,6 +694,73 @@ int qs_frontier_targets_by_territory(qs_ctx *ctx, int32_t min_cluster, const qs_
                                      int32_t *box, double *centroids_xy, int32_t *centroid_owner, size_t cap,
                                      size_t *n_centroids, uint64_t stats[8]);
 
+/* ---- sensing a world: the sweeps and packets a bot would send from a pose in a mapped world (this build's own rules) --------
+ * The inverse of the raycast: given the context's map and n poses, what does each beam return?  Any context is a world (a
+ * maze painted through qs_update_rays, a restored checkpoint, a session's map); the records that come out are what
+ * qs_ingest_sweeps_device / qs_ingest_device of ANOTHER context (or of this one) take.  All rules are integer apart from the
+ * far point, so the device and a CPU restatement (tests/sense_rules.py) agree bit for bit away from S4's edge band.
+ *  S1 Map: a cell is OCCUPIED when its stamp is odd.  The call observes the map as qs_grid_i8_device does (waiting exact-trig
+ *     edge rays are resolved first) and writes no session state: no stamps, counters, sequence numbers or dirty bits, nothing a
+ *     checkpoint holds.  A checkpoint before equals one after.
+ *  S2 Pose: float32 x, y, yaw per record, the pose a packet can carry.  rx = f64(x), ry = f64(y); NO bot offset and NO drift
+ *     are applied: the caller passes world poses.  Start cell (x0, y0) = world_to_grid(rx), world_to_grid(ry) (:121-125).  A
+ *     pose that is not finite, or whose cell is beyond +-9e15 cells (CPython's int() would raise or walk forever): every beam is
+ *     a no-return.  A start cell outside the grid is legal.
+ *  S3 Beams: sweeps -- beam i of 181 has a = f64(yaw) + (i - 90) * (pi / 180), exactly qs_ingest_sweeps' rule.  Packets -- four
+ *     beams a = f64(yaw) + {0, pi/2, pi, -pi/2} in sensor order front, left, back, right (:61-66, :887).
+ *  S4 Far point: (rx + R cos a, ry + R sin a) with R = max_range: one multiply and one add per axis, no FMA, the device's
+ *     sincos.  The far cell (x1, y1) is world_to_grid of it.  exact_trig has NO effect on this call: the far point is within one
+ *     ulp of libm's, and only a far point that close to a cell boundary can move (x1, y1).
+ *  S5 Walk: the cells of the reference's _bresenham((x0, y0), (x1, y1)) (:158-179) in order, from the pose outward (the walk is
+ *     not reversal-symmetric).  Cell 0, the bot's own, never blocks; cells outside the grid are skipped, as update_ray skips
+ *     them; UNKNOWN and FREE cells do not block.  The first OCCUPIED cell (hx, hy) is the hit.
+ *  S6 Range: d = res * sqrt(f64(dx*dx + dy*dy)) with dx = hx - x0, dy = hy - y0: centre to centre, no trigonometry.  Noise (S7)
+ *     is added, then the result is rounded to float32.  The beam returns that value when f64(f32(d)) <= R; otherwise, and when
+ *     nothing was hit, it returns no_return (default 0.0f, which both ingest rules read as a full-length free ray).
+ *     hit_cell = hy * size + hx, or -1 for no return.
+ *     NOTE for whoever ingests the result: a wall in the neighbouring cell returns d = res, which the default trust filters
+ *     (smin = 0.1, min_dist = 0.05 at res = 0.05) read as "too close" and answer with a full-length FREE ray through the wall.
+ *     A mapper fed from this call wants a lower bound below one cell: qs_set_sweep_filter(0.02, R), min_dist = 0.02.
+ *  S7 Noise (off when noise_amp == 0 and dropout_q16 == 0), stateless, in uncontracted fp64, 64-bit wrapping arithmetic; k is
+ *     the record's index within the call:
+ *         z  = seed + 0x9E3779B97F4A7C15 * (1 + (first_record + k) * 256 + beam)
+ *         z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *         u  = (z >> 40) + ((z >> 16) & 0xFFFFFF)
+ *         d' = d + noise_amp * (f64(u) * 2^-24 - 1.0)            (noise_amp in metres; |d' - d| < noise_amp, triangular)
+ *         dropout when (z & 0xFFFF) < dropout_q16                 (reports no_return and hit_cell -1)
+ *     Beams with no hit draw nothing.  first_record makes one call of n records equal two calls of n / 2.
+ *  S8 Limits: 0 < R finite and ceil(R / res) + 1 <= QS_SENSE_MAX_CELLS; noise_amp >= 0 finite; dropout_q16 <= 65536; stride
+ *     743 or 751 for sweeps (42 for packets is implied); beams 181 or 4; reserved zero.  Anything else: QS_E_INVAL.  n == 0 is
+ *     valid; any n is accepted (host calls are chunked internally).
+ * qs_sense_ranges: ranges (n x beams float32) and, optionally, hit_cell (n x beams int32).
+ * qs_sense_sweeps: n sweep records of `stride` bytes, magic 'QSRL', scan_count 181, exactly the bytes protocol.pack_sweeps
+ *     makes of the same fields.  qs_sense_packets: n 42-byte QuasarPacket v2 records, as protocol.pack_packets.
+ *     agent (uint8 [n]) is required; enc (int32), v2v (uint32), landmark (uint8) are copied through, NULL = 0.
+ * The _device twins take device pointers (pkts_out at any byte address) and are asynchronous on the context's stream.
+ * Out of scope: Gaussian noise (a device log / cos would cost the bit-equality), spurious echoes, beam width, a residual
+ * between a received sweep and the predicted one, anything fed to the pose graph, sensing across ranks. */
+#define QS_SENSE_MAX_CELLS 255   /* patch radius C = ceil(R / res) + 1: (2 C + 1)^2 bits in rows of 64-bit words, 32 704 bytes of LDS */
+typedef struct qs_sense_params {
+    double   max_range, noise_amp;
+    float    no_return;
+    uint32_t dropout_q16;
+    uint64_t seed, first_record;
+    int32_t  reserved[2];
+} qs_sense_params;
+int qs_sense_ranges(qs_ctx *ctx, const float *pose_xyyaw, size_t n, int32_t beams, const qs_sense_params *params,
+                    float *ranges, int32_t *hit_cell);
+int qs_sense_ranges_device(qs_ctx *ctx, const float *d_pose_xyyaw, size_t n, int32_t beams, const qs_sense_params *params,
+                           float *d_ranges, int32_t *d_hit_cell);
+int qs_sense_sweeps(qs_ctx *ctx, const float *pose_xyyaw, const uint8_t *agent, const int32_t *enc, const uint32_t *v2v,
+                    size_t n, const qs_sense_params *params, uint8_t *pkts_out, size_t stride);
+int qs_sense_sweeps_device(qs_ctx *ctx, const float *d_pose_xyyaw, const uint8_t *d_agent, const int32_t *d_enc,
+                           const uint32_t *d_v2v, size_t n, const qs_sense_params *params, uint8_t *d_pkts_out, size_t stride);
+int qs_sense_packets(qs_ctx *ctx, const float *pose_xyyaw, const uint8_t *agent, const int32_t *enc, const uint32_t *v2v,
+                     const uint8_t *landmark, size_t n, const qs_sense_params *params, uint8_t *pkts_out);
+int qs_sense_packets_device(qs_ctx *ctx, const float *d_pose_xyyaw, const uint8_t *d_agent, const int32_t *d_enc,
+                            const uint32_t *d_v2v, const uint8_t *d_landmark, size_t n, const qs_sense_params *params,
+                            uint8_t *d_pkts_out);
+
 /* ---- map view: the "Mission Control" map, MapRenderer  dual_bot_mapper.py:380-668 -------------------------------------------
  * One call renders a frame of the map for any pan and zoom on the device and hands back only the frame: [height][width][4]
  * bytes R, G, B, 255, row 0 at the top.  The layers are the reference's (:433-468) as far as its own Python pins their pixels

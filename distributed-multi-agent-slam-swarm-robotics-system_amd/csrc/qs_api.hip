@@ -364,6 +364,20 @@ extern "C" int qs_chain_lean(qs_ctx *c)
     return refused != c->chain_lean_seq ? 1 : 0;
 }
 
+extern "C" int qs_set_chain_plan(qs_ctx *c, int32_t on)
+{
+    ARGCHK(c, c != nullptr);
+    c->chain_plan = on != 0;
+    return QS_OK;
+}
+
+extern "C" int qs_chain_plan(qs_ctx *c)
+{
+    if (!c) return QS_E_INVAL;
+    if (!c->chain_last_plan) return 0;
+    return qs_chain_lean(c);                     // (a plan was built: walked by every graph that ran the lean owner)
+}
+
 extern "C" int qs_sync(qs_ctx *c)
 {
     ARGCHK(c, c != nullptr);
@@ -435,6 +449,8 @@ static size_t batch_layout(const qs_ctx *c, void *base, size_t cap, QsBatch &b, 
     sb.agent_ev = k.take<unsigned int>(nb); sb.acl_cnt = k.take<unsigned int>(nb);
     sb.acl_node = k.take<long long>(cap); sb.acl_dx = k.take<double>(cap); sb.acl_dy = k.take<double>(cap);
     sb.drift_start = k.take<double>(2 * nb);
+    sb.pl_rec = k.take<QsPlanRec>(cap); sb.pl_blk = k.take<unsigned int>(nb * (size_t)qs_slam_plan_blocks(cap));
+    sb.pl_first = k.take<unsigned int>(nb);
     return k.bytes;
 }
 

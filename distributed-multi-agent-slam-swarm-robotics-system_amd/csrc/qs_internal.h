@@ -65,6 +65,14 @@ struct QsGraphDev {
 };
 
 // ---- per-batch scratch of the SLAM stage ---------------------------------------------------
+// one event of an agent's plan: what the lean owner needs to start a decision on it, and where it goes on after a closure there
+struct alignas(32) QsPlanRec {
+    int node;              // node index (low word: the lean owner's graphs stay below 0x7f7f7f7f)
+    unsigned int r;        // position in the graph's event list, from ev_base[g]
+    int type;              // landmark type
+    unsigned int skip;     // own index of the agent's first later event with node - this node >= MIN_POSES_BETWEEN (none: the count)
+    double px, py;         // pose before drift
+};
 struct QsSlamBatch {
     long long *node;                       // [n] node index of each record (-1: rejected)
     long long *ev_node;                    // [n] landmark events, grouped by graph, in node order
@@ -79,6 +87,12 @@ struct QsSlamBatch {
     unsigned int *acl_cnt;                 // [max_agent + 1] closures per bot in this batch
     double *drift_start;                   // [(max_agent + 1) * 2] drift at batch start
     int n_blocks;
+    // the plan (slam.hip, plan kernels): every bot's own events in list order, bot b's at pl_rec[agent_ev[b] ..
+    // agent_ev[b + 1]) -- the regions its closures have in acl_*.  pl_rec == nullptr: this launch has no plan.
+    QsPlanRec *pl_rec;                     // [n]
+    unsigned int *pl_blk;                  // [max_agent + 1][pl_blocks] events of the bot per block of QS_SLAM_PLAN_BLOCK events -> offsets
+    unsigned int *pl_first;                // [max_agent + 1] own index of the bot's first event past its cool-down (none: its count)
+    int pl_blocks;
 };
 
 // ---- geometry / constants passed by value to kernels ------------------------------------
@@ -312,6 +326,8 @@ struct qs_ctx {
     long long chain_lean_limit = 0x7f7f7f7fll;   // ... and the node count below which the kernel allows it (the empty marker's low word, or less)
     unsigned int chain_lean_seq = 0;             // launches of the free-running kernel so far (what a refused graph leaves in QS_FLAG_CHAIN_FULL)
     bool chain_last_lean_asked = false;          // the last launch was that kernel with the lean owner on offer
+    bool chain_plan = true;                      // the lean owner walks a per-agent plan of its events (qs_set_chain_plan) ...
+    bool chain_last_plan = false;                // ... and the last launch had one built for it
     unsigned int *h_chain_stat = nullptr;        // pinned: [0..3] the four running totals as copied last, [4..7] as consumed last
     hipEvent_t ev_chain_stat = nullptr;          // ... complete when the copy has landed
     bool chain_stat_pending = false;
@@ -398,6 +414,8 @@ hipError_t qs_launch_slam_reset_index(qs_ctx *c);              // empties the bu
 struct QsIndexLog { const double *x, *y; const long long *idx; const unsigned char *type; long long n, n_nodes, n_cls; };
 hipError_t qs_launch_slam_rebuild_index(qs_ctx *c, const QsIndexLog *d_logs);   // [n_graphs], into graphs just reset
 int qs_slam_blocks(size_t n);
+#define QS_SLAM_PLAN_BLOCK 256   // events per block of the plan kernels
+int qs_slam_plan_blocks(size_t n);
 // raycast.hip
 #define QS_DIRECT_MAX_BATCH 256   // raycast_mode auto: batches up to this size take the direct kernel
 hipError_t qs_launch_raycast_direct(qs_ctx *c, size_t n, uint64_t seq0);

@@ -149,6 +149,133 @@ qs_slam_index_kernel(size_t n, QsBatch b, QsSlamBatch sb, const QsGraphDev *__re
     }
 }
 
+// ---- the plan: every bot's own events in list order, and where each leads after a closure ------------------------------
+// For the lean owner of qs_slam_chain_free_kernel (slam_chain_plan_owner.inc).  Which event an agent queries next is a pure
+// function of the event list but for one bit per decision: after a closure at own event j, the agent's first own event k > j
+// with node[k] - node[j] >= MIN_POSES_BETWEEN (:304; skip[j], a search in the agent's own list: the nodes ascend),
+// without one j + 1.  A stable partition of the whole event list by bot -- the bots of a graph are consecutive and so are its
+// events, hence bot b's list starts at agent_ev[b], the prefix its closure region has too --: counts per block of
+// PLAN_BLOCK events and bot, their scan per bot, the scatter, then the searches.  O(log n) per event whatever the stream.
+#define PLAN_BLOCK QS_SLAM_PLAN_BLOCK
+#define PLAN_WAVES (PLAN_BLOCK / QS_WAVE)
+int qs_slam_plan_blocks(size_t n) { return (int)((n + PLAN_BLOCK - 1) / PLAN_BLOCK); }
+
+// the graph of event e of the whole list: the last g with ev_base[g] <= e (graphs without events share their base with the next)
+__device__ inline int plan_graph_of(const unsigned int *__restrict__ ev_base, int n_graphs, unsigned int e)
+{
+    int lo = 0, hi = n_graphs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ev_base[mid] <= e) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// plan pass 1: per block, the events of every bot
+__global__ void __launch_bounds__(PLAN_BLOCK)
+qs_slam_plan_count_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent)
+{
+    __shared__ unsigned int s_cnt[QS_MAX_AGENT + 1];
+    const int tid = threadIdx.x;
+    const unsigned int n_ev = sb.ev_base[n_graphs], e = blockIdx.x * PLAN_BLOCK + tid;
+    if (blockIdx.x * PLAN_BLOCK >= n_ev) return;
+    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) s_cnt[t] = 0;
+    __syncthreads();
+    if (e < n_ev) atomicAdd(&s_cnt[plan_graph_of(sb.ev_base, n_graphs, e) * bots_per_graph + 1 + sb.ev_agent[e]], 1u);
+    __syncthreads();
+    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) sb.pl_blk[(size_t)t * sb.pl_blocks + blockIdx.x] = s_cnt[t];
+}
+
+// plan pass 2: per bot, exclusive scan of its block counts (the blocks that hold events)
+__global__ void __launch_bounds__(256)
+qs_slam_plan_scan_kernel(QsSlamBatch sb, int n_graphs)
+{
+    __shared__ unsigned int s_c[256];
+    const int tid = threadIdx.x;
+    const int used = (int)((sb.ev_base[n_graphs] + PLAN_BLOCK - 1) / PLAN_BLOCK);
+    unsigned int *cnt = sb.pl_blk + (size_t)blockIdx.x * sb.pl_blocks;
+    const int per = (used + 255) / 256;
+    const int lo = min(tid * per, used), hi = min(lo + per, used);
+    unsigned int c = 0;
+    for (int k = lo; k < hi; k++) c += cnt[k];
+    s_c[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {                 // inclusive scan of the 256 partial sums
+        const unsigned int v = tid >= d ? s_c[tid - d] : 0u;
+        __syncthreads();
+        s_c[tid] += v;
+        __syncthreads();
+    }
+    unsigned int run = s_c[tid] - c;
+    for (int k = lo; k < hi; k++) { const unsigned int v = cnt[k]; cnt[k] = run; run += v; }
+}
+
+// plan pass 3: every event's record into its bot's list (stable: ranks inside the wave in lane order, waves in order, blocks by the scan)
+__global__ void __launch_bounds__(PLAN_BLOCK)
+qs_slam_plan_scatter_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent)
+{
+    __shared__ unsigned int s_w[PLAN_WAVES][QS_MAX_AGENT + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned int n_ev = sb.ev_base[n_graphs], e = blockIdx.x * PLAN_BLOCK + tid;
+    if (blockIdx.x * PLAN_BLOCK >= n_ev) return;
+    for (int t = tid; t < PLAN_WAVES * (QS_MAX_AGENT + 1); t += PLAN_BLOCK) (&s_w[0][0])[t] = 0;
+    __syncthreads();
+    const bool have = e < n_ev;
+    int g = 0, bot = -1;
+    if (have) { g = plan_graph_of(sb.ev_base, n_graphs, e); bot = g * bots_per_graph + 1 + sb.ev_agent[e]; }
+    unsigned int rank = 0;
+    unsigned long long remaining = __ballot(have);
+    while (remaining) {
+        const int k = __shfl(bot, __ffsll((long long)remaining) - 1);
+        const unsigned long long grp = __ballot(have && bot == k);
+        if (have && bot == k) {
+            rank = __popcll(grp & ((1ull << lane) - 1));
+            if (rank == 0) s_w[wave][k] = __popcll(grp);
+        }
+        remaining &= ~grp;
+    }
+    __syncthreads();
+    if (have && bot <= max_agent) {
+        unsigned int off = sb.pl_blk[(size_t)bot * sb.pl_blocks + blockIdx.x] + rank;
+        for (int w = 0; w < wave; w++) off += s_w[w][bot];
+        QsPlanRec rec;
+        rec.node = (int)sb.ev_node[e]; rec.r = e - sb.ev_base[g]; rec.type = sb.ev_type[e]; rec.skip = 0;
+        rec.px = sb.ev_px[e]; rec.py = sb.ev_py[e];
+        sb.pl_rec[sb.agent_ev[bot] + off] = rec;
+    }
+}
+
+// the first k in [from, n_own) of a bot's list with node[k] >= bound (n_own: none).  It is usually a few records on, so the
+// search gallops from `from` (probes 1, 2, 4 ... further on) and halves what the last two probes enclose: O(log n) at the worst.
+__device__ inline unsigned int plan_first_at_least(const QsPlanRec *pl, unsigned int from, unsigned int n_own, long long bound)
+{
+    unsigned int lo = from, hi = n_own, step = 1;   // every k in [from, lo) has node[k] < bound; node[hi] >= bound, or hi == n_own
+    while (lo < n_own) {
+        const unsigned int p = step - 1 < n_own - 1 - lo ? lo + step - 1 : n_own - 1;
+        if ((long long)pl[p].node >= bound) { hi = p; break; }
+        lo = p + 1;
+        if (step < (1u << 30)) step <<= 1;
+    }
+    while (lo < hi) { const unsigned int mid = lo + ((hi - lo) >> 1); if ((long long)pl[mid].node >= bound) hi = mid; else lo = mid + 1; }
+    return lo;
+}
+
+// plan pass 4: skip of every record, and every bot's first candidate of this launch: its first own event with
+// node - last_closure >= MIN_POSES_BETWEEN (last_closure can be far negative: 64 bits; the bot's own count: none).  The
+// searches compare the records' nodes, the low words: the plan of a graph whose nodes do not fit them means nothing, and
+// nobody reads it -- the lean owner is refused there (qs_slam_chain_free_kernel, the predicate).
+__global__ void __launch_bounds__(256)
+qs_slam_plan_skip_kernel(QsSlamBatch sb, int n_graphs, int max_agent, int min_between, const long long *__restrict__ last_closure)
+{
+    const unsigned int n_ev = sb.ev_base[n_graphs], s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_ev) return;
+    int lo = 0, hi = max_agent;                      // the slot's bot: the last one whose list starts at or before it
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (sb.agent_ev[mid] <= s) lo = mid; else hi = mid - 1; }
+    const int bot = lo;
+    if (bot < 1) return;
+    const unsigned int base = sb.agent_ev[bot], n_own = sb.agent_ev[bot + 1] - base, j = s - base;
+    const QsPlanRec *const pl = sb.pl_rec + base;
+    sb.pl_rec[base + j].skip = plan_first_at_least(pl, j + 1, n_own, (long long)pl[j].node + (long long)min_between);
+    if (j == 0) sb.pl_first[bot] = plan_first_at_least(pl, 0, n_own, last_closure[bot] + (long long)min_between);
+}
+
 // ---- the chain: one workgroup (CH_WAVES waves) per pose graph ------------------------------------
 // The graph's landmark events are walked in windows of < MIN_POSES_BETWEEN nodes: a query never sees a
 // landmark of its own window (:300), and an agent closes at most once per window (:304), so the
@@ -1014,6 +1141,14 @@ __device__ inline void lds_st64(long long *p, long long v) { __hip_atomic_store(
 __device__ inline unsigned int lds_ld32(const unsigned int *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ inline void lds_st32(unsigned int *p, unsigned int v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
+// one record of a plan, by a read that names the global address space (32 bytes, aligned: two loads)
+__device__ inline QsPlanRec plan_rec(const QS_GLOBAL QsPlanRec *p)
+{
+    QsPlanRec r;
+    r.node = p->node; r.r = p->r; r.type = p->type; r.skip = p->skip; r.px = p->px; r.py = p->py;
+    return r;
+}
+
 // WAVES: 16, or 8 for graphs of up to 5 agents -- half the waves per SIMD is twice the registers per wave (256), and the owner keeps
 // two chunks of events and two decisions' bucket rows in registers.
 // POST: the owners post their events' landmark poses for the others' queries (below).  It costs every decision ~240 cycles, and a
@@ -1124,7 +1259,11 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         // loops from one text, so that neither carries the other's registers -- a value live in both would be copied where they
         // meet, behind a wait for the row loads just issued.  (Included twice, not a generic lambda called twice: that changed
         // the register allocation of the instantiations that have no lean owner, and cost them 3 %.)
-        if (lean) {
+        // (And a third, the lean owner's where the launch has a plan of every agent's events: slam_chain_plan_owner.inc.  Not in
+        // the DENSE instantiation, which it costs two spilled VGPRs: the host builds no plan for it.)
+        if (!DENSE && lean && sb.pl_rec) {
+#include "slam_chain_plan_owner.inc"
+        } else if (lean) {
             constexpr bool LEAN = true;
 #include "slam_chain_owner.inc"
         } else {
@@ -1717,17 +1856,34 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     hipLaunchKernelGGL(qs_slam_prefix_kernel, dim3(1), dim3(256), 0, c->stream, sb, G, c->cfg.max_agent, c->d_drift.p);
     hipLaunchKernelGGL(qs_slam_index_kernel, dim3(sb.n_blocks), dim3(IDX_BLOCK), (size_t)IDX_WAVES * G * 2 * sizeof(unsigned int),
                        c->stream, n, c->b, sb, c->d_graphs.p, c->bots_per_graph, G);
-    StageTimer t_chain(c, QS_STAGE_SLAM_CHAIN);
-#define CH_LAUNCH(ONE_, DENSE_) hipLaunchKernelGGL((qs_slam_chain_kernel<ONE_, DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
-                           c->bots_per_graph, c->cfg.max_agent, c->win, c->cfg.min_poses_between, c->r2_threshold,                          \
-                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
-    const bool one = c->bots_per_graph <= CH_AGW;
     // which form (qs_set_chain_form; QS_CHAIN_MODE at qs_create).  Left to itself the library runs the free-running form; for
     // graphs of up to CH_AGW agents without the posting of poses until a batch had more than 1 decision in 8 wait for the
     // committer -- a stream whose queries mostly find nothing in the index --, with it until fewer than 1 in 16 need it, and the
     // per-window kernel while even so there are more scans than closures
     // (chain_stats_poll in qs_api.hip reads the counts, without waiting for anything).  Same results either way.
+    const bool one = c->bots_per_graph <= CH_AGW;
     const bool free_mode = c->chain_form != QS_CHAIN_WINDOW && !(c->chain_form == QS_CHAIN_AUTO && one && c->chain_windowed);
+    const bool post = c->chain_form == QS_CHAIN_FREE_POSTING || (c->chain_form == QS_CHAIN_AUTO && c->chain_posting);
+    const int sel = (c->pile_mode ? 4 : 0) | (c->bots_per_graph <= 5 ? 2 : 0) | (post ? 1 : 0);   // the free-running kernel's instantiation
+    const bool lean_asked = free_mode && one && c->chain_lean_mode != QS_CHAIN_LEAN_OFF && !post && sel != 6;   // (its LEAN_OK)
+    // the plan of every agent's events, for the lean owner (qs_set_chain_plan): with the index kernels, ahead of the chain
+    const bool plan = lean_asked && c->chain_plan && !raw_pose && !c->pile_mode;
+    c->chain_last_plan = plan;
+    if (plan) {
+        sb.pl_blocks = qs_slam_plan_blocks(n);
+        const int nbots = c->cfg.max_agent + 1;
+        hipLaunchKernelGGL(qs_slam_plan_count_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent);
+        hipLaunchKernelGGL(qs_slam_plan_scan_kernel, dim3(nbots), dim3(256), 0, c->stream, sb, G);
+        hipLaunchKernelGGL(qs_slam_plan_scatter_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent);
+        hipLaunchKernelGGL(qs_slam_plan_skip_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, c->stream, sb, G,
+                           c->cfg.max_agent, c->cfg.min_poses_between, c->d_last_closure.p);
+    } else {
+        sb.pl_rec = nullptr;
+    }
+    StageTimer t_chain(c, QS_STAGE_SLAM_CHAIN);
+#define CH_LAUNCH(ONE_, DENSE_) hipLaunchKernelGGL((qs_slam_chain_kernel<ONE_, DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
+                           c->bots_per_graph, c->cfg.max_agent, c->win, c->cfg.min_poses_between, c->r2_threshold,                          \
+                           c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
     c->chain_last_posting = false;
     c->chain_last_free = free_mode;
     c->chain_last_lean_asked = false;
@@ -1740,12 +1896,10 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
     if (free_mode) {
         if (one) {
-            const bool post = c->chain_form == QS_CHAIN_FREE_POSTING || (c->chain_form == QS_CHAIN_AUTO && c->chain_posting);
             // (the lean owner: the kernel decides per graph, from what is on the device -- a graph that was refused leaves this launch's
             // number in a device word, which is all qs_chain_lean looks at)
             c->chain_lean_seq++;
-            const int sel = (c->pile_mode ? 4 : 0) | (c->bots_per_graph <= 5 ? 2 : 0) | (post ? 1 : 0);
-            c->chain_last_lean_asked = c->chain_lean_mode != QS_CHAIN_LEAN_OFF && !post && sel != 6;   // (LEAN_OK of the instantiation)
+            c->chain_last_lean_asked = lean_asked;
             switch (sel) {
             case 0: FR_LAUNCH(false, 16, false); break;  case 1: FR_LAUNCH(false, 16, true); break;
             case 2: FR_LAUNCH(false, 8, false); break;   case 3: FR_LAUNCH(false, 8, true); break;

@@ -869,6 +869,18 @@ class QuasarMapper:
             self._chk(r, "qs_chain_lean")
         return bool(r)
 
+    def set_chain_plan(self, on=True):
+        """The lean owner walks a per-agent plan of its events, built on the device ahead of the chain (default), or streams
+        the graph's whole event list as the general owner does (on=False).  Same results either way."""
+        self._chk(self._L.qs_set_chain_plan(self._h, 1 if on else 0), "qs_set_chain_plan")
+
+    def chain_plan(self):
+        """Whether the last ingest had a plan and every graph's lean owner walked it (waits for the stream)."""
+        r = self._L.qs_chain_plan(self._h)
+        if r < 0:
+            self._chk(r, "qs_chain_plan")
+        return bool(r)
+
     def mfma_f64_rate(self):
         """Measured dense fp64 MFMA rate of this GPU in TFLOP/s (diagnostic)."""
         v = C.c_double()

@@ -437,6 +437,15 @@ int qs_chain_form(qs_ctx *ctx);
 int qs_set_chain_lean(qs_ctx *ctx, int32_t mode, int64_t limit);
 int qs_chain_lean(qs_ctx *ctx);
 
+/* The lean owner finds its agent's next event in a plan: every agent's own events in list order, each with the agent's first
+ * later event past the cool-down of a closure there, built by parallel kernels ahead of every launch that has the lean owner on
+ * offer.  qs_set_chain_plan: on != 0 (default) builds and walks it, 0 has the lean owner stream the graph's whole event list in
+ * chunks of 64 as the general owner does.  Same closures, landmarks and drifts bit for bit.
+ * qs_chain_plan: 1 if the last ingest had a plan and every graph ran the lean owner, which then walked it, else 0 (waits for
+ * the stream); < 0: error. */
+int qs_set_chain_plan(qs_ctx *ctx, int32_t on);
+int qs_chain_plan(qs_ctx *ctx);
+
 /* diagnostic: measured dense fp64 MFMA rate of this GPU (TFLOP/s), the ceiling qs_nn_search mode 2 is priced against */
 int qs_diag_mfma_f64_rate(qs_ctx *ctx, double *tflops);
 /* diagnostic: latencies of the primitives one loop-closure decision chains together, measured on this GPU by ONE workgroup

@@ -39,5 +39,6 @@ for b in range(1, na + 1): h.update(m.drift(b).tobytes())
 res = {"workload": wl, "lib": os.path.basename(ROOT), "form": form, "chain_ms": out,
        "batches": c["slam_windows"], "closures": c["closures"], "rounds": c["slam_rounds"], "digest": h.hexdigest()[:16],
        "lean": m.chain_lean() if hasattr(m, "chain_lean") else None,
+       "plan": m.chain_plan() if hasattr(m, "chain_plan") else None,
        "chain_form": m.chain_form()}
 print(json.dumps(res), flush=True)

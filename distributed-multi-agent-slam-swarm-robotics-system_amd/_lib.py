@@ -61,6 +61,21 @@ class QsSweepMatch(C.Structure):
                 ("dx", C.c_double), ("dy", C.c_double), ("dyaw", C.c_double)]
 
 
+class QsRelocParams(C.Structure):
+    """struct qs_reloc_params (include/quasar_slam.h)."""
+    _fields_ = [("radius", C.c_int32), ("n_rot", C.c_int32), ("sep", C.c_int32), ("sep_rot", C.c_int32), ("min_hits", C.c_int32),
+                ("min_percent", C.c_int32), ("min_margin", C.c_int32), ("use_box", C.c_int32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
+class QsSweepReloc(C.Structure):
+    """struct qs_sweep_reloc (include/quasar_slam.h)."""
+    _fields_ = [("gx", C.c_int32), ("gy", C.c_int32), ("j", C.c_int32), ("score", C.c_int32), ("hits", C.c_int32),
+                ("gx2", C.c_int32), ("gy2", C.c_int32), ("j2", C.c_int32), ("score2", C.c_int32), ("status", C.c_int32),
+                ("accepted_record", C.c_uint8), ("accepted", C.c_uint8), ("pad", C.c_uint8 * 6),
+                ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
+
+
 class QsMergeResult(C.Structure):
     """struct qs_merge_result (include/quasar_slam.h)."""
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_local", C.c_uint64), ("n_global", C.c_uint64),
@@ -152,6 +167,8 @@ SIGNATURES = {
     "qs_ingest_sweeps_matched": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_ingest_sweeps_matched_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_last_sweep_matches": (_i32, [_vp, _vp, _sz]),
+    "qs_relocalise_sweeps": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "qs_relocalise_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "qs_sense_ranges": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_ranges_device": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_sweeps": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),

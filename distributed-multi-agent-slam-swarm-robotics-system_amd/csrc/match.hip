@@ -8,7 +8,8 @@
 //      cells -- is read from the stamps as bytes (OCCUPIED = odd stamp -> R + 1, anything else and off-grid -> 0) and grown
 //      by R rounds of a separable 3-wide max that loses 1 per round: L = max(0, R + 1 - Chebyshev distance).  The rounds work
 //      on dwords (four cells a lane); a patch that hangs over the grid's edge is cut back to the grid afterwards.  No
-//      whole-grid field exists: nothing persistent, nothing to invalidate;
+//      whole-grid field exists: nothing persistent, nothing to invalidate.  The routine is field_patch.h's, shared with the
+//      relocaliser (reloc.hip);
 //   3. every wave holds all 181 beams (three a lane: d, hit flag, d * cos, d * sin of the beam angle, the trig from the
 //      host's table) and takes rotations wave, wave + 4, ...: one sincos per rotation, the end-point cells of the hit beams,
 //      compacted by ballot into the rotation's list of 16-bit patch offsets (the offset of candidate ix = iy = -W);
@@ -23,6 +24,7 @@
 #include <algorithm>
 
 #include "sweep_common.h"
+#include "field_patch.h"
 
 #define MT_BLOCK 256
 #define MT_NW (MT_BLOCK / QS_WAVE)
@@ -41,37 +43,6 @@ struct QsMatchArgs {
     qs_sweep_match *out;          // [n]
     double *rot;                  // [n][2 T + 1][2] or nullptr
 };
-
-__device__ inline bool mt_occupied(unsigned int stamp) { return (stamp & 1u) != 0; }     // (UNKNOWN is 0: even)
-
-// bytewise max of three dwords
-__device__ inline unsigned int mt_max3_u8x4(unsigned int a, unsigned int b, unsigned int c)
-{
-    unsigned int r = 0;
-    #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned int s = 8u * j;
-        r |= max(max((a >> s) & 255u, (b >> s) & 255u), (c >> s) & 255u) << s;
-    }
-    return r;
-}
-// one round's new value per byte: max(old, m - 1) with m - 1 saturating at 0
-__device__ inline unsigned int mt_grow_u8x4(unsigned int old, unsigned int m)
-{
-    unsigned int r = 0;
-    #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned int s = 8u * j, v = (m >> s) & 255u;
-        r |= max((old >> s) & 255u, v ? v - 1u : 0u) << s;
-    }
-    return r;
-}
-
-// four adjacent field bytes from byte offset a of the patch
-__device__ inline unsigned int mt_look(const unsigned int *p, unsigned int a)
-{
-    return __builtin_amdgcn_alignbyte(p[(a >> 2) + 1], p[a >> 2], a & 3u);
-}
 
 __global__ void __launch_bounds__(MT_BLOCK)
 qs_match_kernel(QsSweepArgs a, QsGeom geo, QsMatchArgs m)
@@ -101,55 +72,7 @@ qs_match_kernel(QsSweepArgs a, QsGeom geo, QsMatchArgs m)
     c0ok = qs_w2g_i32(h.ry, geo.oy, geo, c0y) && c0ok;
     if (!c0ok) { c0x = 0; c0y = 0; }                               // (no beam of such a pose has a cell: nothing reads the patch)
     const int gx0 = c0x - m.half - m.R, gy0 = c0y - m.half - m.R;  // grid cell of patch byte (0, 0); |c0| <= 2^30
-    const int pd = m.pitch >> 2, nd = m.SA * pd;
-    const unsigned int seed = (unsigned int)m.R + 1u;
-    for (int i = tid; i < nd + 4; i += MT_BLOCK) {                 // (+ 4 dwords: a look-up reads one dword ahead)
-        unsigned int v = 0;
-        if (i < nd) {
-            const int y = i / pd, x4 = 4 * (i - y * pd), gy = gy0 + y;
-            if (gy >= 0 && gy < geo.size) {
-                const unsigned int *row = m.stamps + (size_t)gy * geo.size;
-                #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int x = x4 + j, gx = gx0 + x;
-                    if (x < m.SA && gx >= 0 && gx < geo.size && mt_occupied(row[gx])) v |= seed << (8 * j);
-                }
-            }
-        }
-        A[i] = v;
-    }
-    __syncthreads();
-    for (int r = 0; r < m.R; r++) {
-        for (int i = tid; i < nd; i += MT_BLOCK) {                 // along x: A -> B
-            const int y = i / pd, xd = i - y * pd;
-            const unsigned int cur = A[i], prev = xd > 0 ? A[i - 1] : 0u, next = xd < pd - 1 ? A[i + 1] : 0u;
-            B[i] = mt_max3_u8x4(__builtin_amdgcn_alignbyte(cur, prev, 3), cur, __builtin_amdgcn_alignbyte(next, cur, 1));
-        }
-        __syncthreads();
-        for (int i = tid; i < nd; i += MT_BLOCK) {                 // along y, minus one: B -> A
-            const unsigned int up = i >= pd ? B[i - pd] : 0u, dn = i + pd < nd ? B[i + pd] : 0u;
-            A[i] = mt_grow_u8x4(A[i], mt_max3_u8x4(up, B[i], dn));
-        }
-        __syncthreads();
-    }
-
-    if (m.R > 0 && (gx0 < 0 || gy0 < 0 || gx0 + m.SA > geo.size || gy0 + m.SA > geo.size)) {   // (uniform)
-        // the patch hangs over the grid's edge: L is 0 out there, whatever the rounds grew into it (a shortest Chebyshev
-        // path between two cells of the grid never needs to leave it, so the cells inside are already right)
-        for (int i = tid; i < nd; i += MT_BLOCK) {
-            const int y = i / pd, x4 = 4 * (i - y * pd), gy = gy0 + y;
-            unsigned int keep = 0;
-            if (gy >= 0 && gy < geo.size) {
-                #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int gx = gx0 + x4 + j;
-                    if (gx >= 0 && gx < geo.size) keep |= 0xffu << (8 * j);
-                }
-            }
-            A[i] &= keep;
-        }
-        __syncthreads();
-    }
+    mt_build_patch(A, B, m.stamps, geo.size, gx0, gy0, m.SA, m.pitch, m.R, tid, MT_BLOCK);
 
     // ---- beams, and per rotation the patch offsets of the hit beams' cells ---------------------------------------------------
     unsigned short *OFF = (unsigned short *)B;

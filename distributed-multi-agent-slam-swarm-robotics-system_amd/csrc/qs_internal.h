@@ -301,6 +301,9 @@ struct qs_ctx {
     DevBuf<qs_sweep_match> match_out;            //   ... the matches of the last matched ingest (qs_last_sweep_matches)
     size_t last_matches_n = 0;
     bool last_matches = false;
+    DevBuf<double> reloc_rot;                    // relocalisation (reloc.hip): sin, cos, yaw of the reloc_nrot rotation steps, host's libm
+    int reloc_nrot = 0;
+    DevBuf<char> reloc_ws;                       //   ... census, score tables and picks of one chunk of sweeps (qs_reloc_layout)
 
     // map merge session (merge.hip): the merger node's state.  qs_reset and checkpoints leave it alone
     DevBuf<double2> mg_cloud;                    // the global cloud; grown by allocate-new-and-move (a failed growth keeps it)

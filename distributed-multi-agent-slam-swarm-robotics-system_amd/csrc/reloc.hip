@@ -1,0 +1,517 @@
+// reloc.hip -- a sweep located against the whole map (include/quasar_slam.h, "relocalisation"): every FREE cell of the search
+// box and every rotation step is a candidate pose, scored on the matcher's likelihood field; the best candidate, the best rival
+// away from it and a gate on their margin are the answer.  No coarse level: the search is exhaustive and therefore exact.
+//
+// The unit of work is (sweep, 16 x 16-cell tile):
+//   1. a census lists the tiles of the box that hold a FREE cell inside it (compact.h), once per call;
+//   2. qs_reloc_score_kernel, one workgroup (4 waves) per (sweep, listed tile): the field patch of the tile plus the sweep's
+//      reach all round in LDS (field_patch.h, the matcher's patch); every wave holds all 181 beams and takes rotations wave,
+//      wave + 4, ...: the hit beams' cell offsets compacted by ballot into 16-bit patch offsets, then the WHOLE tile in one
+//      pass, a lane per (row, four adjacent columns): per beam two dword reads and an align, byte sums spilled to 16-bit
+//      halves.  The order of the rule is one 64-bit key; the tile's best goes to table[sweep][slot].  No atomics;
+//   3. qs_reloc_pick_kernel: a workgroup per sweep reduces its table row to the best candidate;
+//   4. the scoring kernel's EXCL instantiation over the at most 9 tiles that meet the square +-sep round the best, without the
+//      candidates rule G6 excludes;
+//   5. qs_reloc_final_kernel: rival = max of the table entries of all other tiles (wholly outside the square, so their stored
+//      best is eligible) and the re-scored ones; gate; outputs.
+// Sweeps run in chunks of RL_CHUNK through one workspace (qs_reloc_layout).
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+
+#include "sweep_common.h"
+#include "field_patch.h"
+#include "compact.h"
+
+#define RL_BLOCK 256
+#define RL_NW (RL_BLOCK / QS_WAVE)
+#define RL_TILE 16
+#define RL_OFFP 184               // 16-bit offsets per wave: >= 181, a multiple of 8 (16-byte reads)
+#define RL_CHUNK 64               // sweeps per launch
+
+// key: (score + 1) << 41 | (511 - j) << 32 | (65535 - gy) << 16 | (65535 - gx): larger is earlier in the order of G5; 0 = none
+__device__ inline unsigned long long rl_key(unsigned int score, int j, unsigned int low)
+{
+    return ((unsigned long long)(score + 1u) << 41) | ((unsigned long long)(511 - j) << 32) | low;
+}
+__device__ inline int rl_key_score(unsigned long long k) { return (int)(k >> 41) - 1; }
+__device__ inline int rl_key_j(unsigned long long k) { return 511 - (int)((k >> 32) & 511u); }
+__device__ inline int rl_key_gy(unsigned long long k) { return 65535 - (int)((k >> 16) & 0xffffu); }
+__device__ inline int rl_key_gx(unsigned long long k) { return 65535 - (int)(k & 0xffffu); }
+__device__ inline bool rl_free(unsigned int stamp) { return stamp != 0 && !(stamp & 1u); }
+
+struct QsRelocArgs {
+    int R, n_rot, sep, sep_rot, min_hits, min_percent, min_margin;
+    int bx0, by0, bx1, by1;       // the search box clipped to the grid (empty: bx1 <= bx0 or by1 <= by0)
+    int tx0, ty0, ntx, nty;       // the tiles it meets
+    int M;                        // cells a beam's end can lie from the robot's cell: ceil(smax / res) + 1
+    int SA, pitch;                // patch side 16 + 2 (M + R) and bytes per row (16 x an odd number)
+    unsigned int off_b;           // byte offset of the second LDS region (dilation scratch, then the waves' offset lists)
+    const double *tab;            // [2][181] cos, sin of the beam angles (the matcher's table)
+    const double *rot;            // [n_rot][3] sin, cos of th_j and the yaw reported for it, the host's libm
+    const unsigned int *stamps;
+    const unsigned int *list;     // census: box-tile indices (ty - ty0) * ntx + (tx - tx0), ascending
+    const unsigned long long *count;
+    unsigned long long *table;    // [RL_CHUNK][table_pitch] best key per (sweep, listed tile)
+    size_t table_pitch;
+    unsigned long long *best;     // [RL_CHUNK]
+    unsigned long long *excl;     // [RL_CHUNK][9]
+    qs_sweep_reloc *out;          // [n] of this chunk
+};
+
+// ---- census ------------------------------------------------------------------------------------------------------------------
+struct RlTilePred {
+    const unsigned int *stamps;
+    int size, bx0, by0, bx1, by1, tx0, ty0, ntx;
+    __device__ bool marked(size_t i) const
+    {
+        const int tx = tx0 + (int)(i % (size_t)ntx), ty = ty0 + (int)(i / (size_t)ntx);
+        const int x0 = max(tx * RL_TILE, bx0), x1 = min(tx * RL_TILE + RL_TILE, bx1);
+        const int y0 = max(ty * RL_TILE, by0), y1 = min(ty * RL_TILE + RL_TILE, by1);
+        for (int y = y0; y < y1; y++)
+            for (int x = x0; x < x1; x++)
+                if (rl_free(stamps[(size_t)y * size + x])) return true;
+        return false;
+    }
+};
+struct RlTileEmit {
+    unsigned int *list;
+    __device__ void put(size_t slot, size_t i) const { list[slot] = (unsigned int)i; }
+};
+
+// the 181 beams of a staged record, three a lane: hit flags, d * cos, d * sin; returns H (every wave computes all of it)
+__device__ inline int rl_beams(const QsSweepArgs &a, const unsigned int *s_rec, unsigned int mis, const double *tab, int lane,
+                               bool hit[3], double bx[3], double by[3])
+{
+    int H = 0;
+    #pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const int i = lane + QS_WAVE * q;
+        hit[q] = false; bx[q] = 0.0; by[q] = 0.0;
+        if (i < QS_SWEEP_BEAMS) {
+            const double d = (double)__uint_as_float(sw_u32(s_rec, mis, a.ranges_off + 4u * (unsigned int)i));
+            hit[q] = qs_range_rule(d, a.smin, a.smax).valid;
+            bx[q] = d * tab[i];
+            by[q] = d * tab[QS_SWEEP_BEAMS + i];
+        }
+        H += __popcll(__ballot(hit[q]));
+    }
+    return H;
+}
+
+// the tiles that meet the square +-sep round (gx, gy): [tlx, thx] x [tly, thy] (at most 3 x 3; may reach outside the grid)
+__device__ inline void rl_square_tiles(int gx, int gy, int sep, int &tlx, int &tly, int &thx, int &thy)
+{
+    tlx = (gx - sep) >> 4; thx = (gx + sep) >> 4;                  // (arithmetic shift: floor for negatives)
+    tly = (gy - sep) >> 4; thy = (gy + sep) >> 4;
+}
+
+// ---- scores of one (sweep, tile) -------------------------------------------------------------------------------------------------
+template <bool EXCL>
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
+{
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    __shared__ unsigned int s_rec[SW_DW];
+    __shared__ unsigned long long s_key[RL_NW];
+    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
+    const size_t k = blockIdx.y;
+    unsigned long long *dst = EXCL ? m.excl + k * 9 + blockIdx.x : m.table + k * m.table_pitch + blockIdx.x;
+    int tx, ty, bgx = 0, bgy = 0, bj = 0;
+    if (EXCL) {
+        const unsigned long long bk = m.best[k];
+        if (bk == 0) { if (tid == 0) *dst = 0; return; }           // (no candidate at all: nothing to exclude)
+        bgx = rl_key_gx(bk); bgy = rl_key_gy(bk); bj = rl_key_j(bk);
+        int tlx, tly, thx, thy;
+        rl_square_tiles(bgx, bgy, m.sep, tlx, tly, thx, thy);
+        tx = tlx + (int)(blockIdx.x % 3u); ty = tly + (int)(blockIdx.x / 3u);
+        if (tx > thx || ty > thy || tx < m.tx0 || tx >= m.tx0 + m.ntx || ty < m.ty0 || ty >= m.ty0 + m.nty) {
+            if (tid == 0) *dst = 0;
+            return;
+        }
+    } else {
+        if ((unsigned long long)blockIdx.x >= *m.count) return;    // (the grid is sized for every tile of the box)
+        const int ti = (int)m.list[blockIdx.x];
+        tx = m.tx0 + ti % m.ntx; ty = m.ty0 + ti / m.ntx;
+    }
+    if (wave == 0) sw_stage(a, k, s_rec, lane);
+    __syncthreads();
+    const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
+    int agent;
+    bool hit[3];
+    double bx[3], by[3];
+    const bool ok = sw_accept(a, k, s_rec, mis, agent);
+    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    if (!ok || H == 0) { if (tid == 0) *dst = 0; return; }         // (uniform over the workgroup)
+
+    // ---- the patch of the field: the tile and M + R cells all round --------------------------------------------------------------
+    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.off_b);
+    const int apron = m.M + m.R;
+    mt_build_patch(A, B, m.stamps, geo.size, tx * RL_TILE - apron, ty * RL_TILE - apron, m.SA, m.pitch, m.R, tid, RL_BLOCK);
+
+    // ---- the lane's candidates: row `row`, columns 4 cg .. 4 cg + 3 of the tile ------------------------------------------------------
+    const int row = lane >> 2, cg = lane & 3;
+    const int gy = ty * RL_TILE + row, gxb = tx * RL_TILE + 4 * cg;
+    unsigned int mask = 0, sq = 0, low[4];
+    #pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int gx = gxb + e;
+        low[e] = ((unsigned int)(65535 - gy) << 16) | (unsigned int)(65535 - gx);
+        if (gx >= m.bx0 && gx < m.bx1 && gy >= m.by0 && gy < m.by1 && rl_free(m.stamps[(size_t)gy * geo.size + gx])) mask |= 1u << e;
+        if (EXCL && abs(gx - bgx) <= m.sep && abs(gy - bgy) <= m.sep) sq |= 1u << e;
+    }
+    const unsigned int lane_off = (unsigned int)(row * m.pitch + 4 * cg);
+    unsigned short *o = (unsigned short *)B + wave * RL_OFFP;      // this wave's list (the dilation is done with B)
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int span = (255 / (m.R + 1)) & ~7;                       // beams whose byte sums cannot overflow (16-byte list reads)
+    unsigned long long best = 0;
+    const int rounds = (m.n_rot + RL_NW - 1) / RL_NW;
+    for (int r = 0; r < rounds; r++) {
+        const int j = r * RL_NW + wave;
+        const bool live = j < m.n_rot;                             // (uniform over the wave)
+        int cnt = 0;
+        if (live) {
+            const double s = m.rot[3 * j], c = m.rot[3 * j + 1];
+            #pragma unroll
+            for (int q = 0; q < 3; q++) {
+                bool in = false;
+                unsigned int off = 0;
+                if (hit[q]) {
+                    const double ex = c * bx[q] - s * by[q], ey = s * bx[q] + c * by[q];
+                    const int ax = (int)floor(ex / geo.res + 0.5), ay = (int)floor(ey / geo.res + 0.5);
+                    in = ax >= -m.M && ax <= m.M && ay >= -m.M && ay <= m.M;       // (|e| <= smax: always)
+                    off = (unsigned int)((ay + apron) * m.pitch + (ax + apron));
+                }
+                const unsigned long long bal = __ballot(in);
+                if (in) o[cnt + __popcll(bal & lt)] = (unsigned short)off;
+                cnt += __popcll(bal);
+            }
+        }
+        __syncthreads();                                           // (every wave runs every round: the list is written)
+        if (live) {
+            cnt = __builtin_amdgcn_readfirstlane(cnt);             // (the same in every lane: the loops below are scalar)
+            unsigned int lo = 0, hi = 0;
+            for (int b0 = 0; b0 < cnt; b0 += span) {
+                const int b1 = min(b0 + span, cnt);
+                unsigned int acc = 0;
+                int b = b0;
+                for (; b + 8 <= b1; b += 8) {                      // eight beams: one 16-byte read of offsets, sixteen dword reads in flight
+                    const uint4 q = *(const uint4 *)(o + b);
+                    acc += mt_look(A, lane_off + (q.x & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.x >> 16));
+                    acc += mt_look(A, lane_off + (q.y & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.y >> 16));
+                    acc += mt_look(A, lane_off + (q.z & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.z >> 16));
+                    acc += mt_look(A, lane_off + (q.w & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.w >> 16));
+                }
+                for (; b + 4 <= b1; b += 4) {
+                    const uint2 q = *(const uint2 *)(o + b);
+                    acc += mt_look(A, lane_off + (q.x & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.x >> 16));
+                    acc += mt_look(A, lane_off + (q.y & 0xffffu));
+                    acc += mt_look(A, lane_off + (q.y >> 16));
+                }
+                for (; b < b1; b++) acc += mt_look(A, lane_off + o[b]);
+                lo += acc & 0x00ff00ffu;
+                hi += (acc >> 8) & 0x00ff00ffu;
+            }
+            const unsigned int sc[4] = {lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16};
+            unsigned int use = mask;
+            if (EXCL) {
+                const int dj = abs(j - bj);
+                if (min(dj, m.n_rot - dj) <= m.sep_rot) use &= ~sq;                  // G6: too close to the best on every axis
+            }
+            #pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const unsigned long long key = rl_key(sc[e], j, low[e]);
+                if (((use >> e) & 1u) && key > best) best = key;
+            }
+        }
+        __syncthreads();                                           // (the list is read: the next round may overwrite it)
+    }
+    #pragma unroll
+    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
+        const unsigned long long other = __shfl_xor(best, d);
+        best = other > best ? other : best;
+    }
+    if (lane == 0) s_key[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < RL_NW; w++) best = s_key[w] > best ? s_key[w] : best;
+        *dst = best;
+    }
+}
+
+// max of v over the workgroup, in every thread
+__device__ inline unsigned long long rl_block_max(unsigned long long v, unsigned long long *s_key, int tid)
+{
+    #pragma unroll
+    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
+        const unsigned long long other = __shfl_xor(v, d);
+        v = other > v ? other : v;
+    }
+    if ((tid & (QS_WAVE - 1)) == 0) s_key[tid >> 6] = v;
+    __syncthreads();
+    v = s_key[0];
+    for (int w = 1; w < RL_NW; w++) v = s_key[w] > v ? s_key[w] : v;
+    __syncthreads();
+    return v;
+}
+
+// ---- the best of a sweep's table row --------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_pick_kernel(QsRelocArgs m)
+{
+    __shared__ unsigned long long s_key[RL_NW];
+    const size_t k = blockIdx.x, cnt = (size_t)*m.count;
+    const unsigned long long *row = m.table + k * m.table_pitch;
+    unsigned long long best = 0;
+    for (size_t i = threadIdx.x; i < cnt; i += RL_BLOCK) best = row[i] > best ? row[i] : best;
+    best = rl_block_max(best, s_key, threadIdx.x);
+    if (threadIdx.x == 0) m.best[k] = best;
+}
+
+// ---- rival, gate, outputs ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
+{
+    __shared__ unsigned int s_rec[SW_DW];
+    __shared__ unsigned long long s_key[RL_NW];
+    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
+    const size_t k = blockIdx.x;
+    if (wave == 0) sw_stage(a, k, s_rec, lane);
+    __syncthreads();
+    const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
+    int agent;
+    bool hit[3];
+    double bx[3], by[3];
+    const bool ok = sw_accept(a, k, s_rec, mis, agent);
+    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    qs_sweep_reloc r;
+    memset(&r, 0, sizeof r);
+    if (!ok) {                                                     // (uniform over the workgroup)
+        r.status = QS_RELOC_NO_RECORD;
+        if (tid == 0) m.out[k] = r;
+        return;
+    }
+    const unsigned long long bk = m.best[k];
+    unsigned long long rival = 0;
+    if (bk != 0) {
+        int tlx, tly, thx, thy;
+        rl_square_tiles(rl_key_gx(bk), rl_key_gy(bk), m.sep, tlx, tly, thx, thy);
+        const size_t cnt = (size_t)*m.count;
+        const unsigned long long *row = m.table + k * m.table_pitch;
+        for (size_t i = tid; i < cnt; i += RL_BLOCK) {
+            const int ti = (int)m.list[i], tx = m.tx0 + ti % m.ntx, ty = m.ty0 + ti / m.ntx;
+            if (tx >= tlx && tx <= thx && ty >= tly && ty <= thy) continue;          // re-scored without the excluded candidates
+            rival = row[i] > rival ? row[i] : rival;
+        }
+        if (tid < 9) rival = max(rival, m.excl[k * 9 + tid]);
+    }
+    rival = rl_block_max(rival, s_key, tid);
+    if (tid != 0) return;
+    r.accepted_record = 1;
+    r.hits = H;
+    r.gx = r.gy = r.j = r.gx2 = r.gy2 = r.j2 = -1;
+    if (bk == 0) {                                                 // no FREE cell in the box, or H = 0
+        r.status = QS_RELOC_NO_CANDIDATE;
+        m.out[k] = r;
+        return;
+    }
+    r.status = QS_RELOC_OK;
+    r.gx = rl_key_gx(bk); r.gy = rl_key_gy(bk); r.j = rl_key_j(bk); r.score = rl_key_score(bk);
+    if (rival != 0) { r.gx2 = rl_key_gx(rival); r.gy2 = rl_key_gy(rival); r.j2 = rl_key_j(rival); r.score2 = rl_key_score(rival); }
+    const long long full = (long long)H * (m.R + 1);
+    r.accepted = H >= m.min_hits && (long long)r.score * 100 >= (long long)m.min_percent * full
+                 && (long long)(r.score - r.score2) * 100 >= (long long)m.min_margin * full;
+    r.x = geo.ox + ((double)r.gx + 0.5) * geo.res;
+    r.y = geo.oy + ((double)r.gy + 0.5) * geo.res;
+    r.yaw = m.rot[3 * r.j + 2];
+    m.out[k] = r;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+struct QsRelocSetup { qs_reloc_params p; int M; };
+
+static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who, QsRelocSetup &rs)
+{
+    qs_reloc_params p = {2, 180, 4, 2, 40, 70, 5, 0, 0, 0, 0, 0};
+    if (params) p = *params;
+    char msg[256];
+    const char *bad = nullptr;
+    if (p.radius < 0 || p.radius > QS_MATCH_MAX_RADIUS) bad = "radius must lie in [0, QS_MATCH_MAX_RADIUS]";
+    else if (p.n_rot < 1 || p.n_rot > QS_RELOC_MAX_ROT) bad = "n_rot must lie in [1, 360]";
+    else if (p.sep < 0 || p.sep > QS_RELOC_MAX_SEP) bad = "sep must lie in [0, 16]";
+    else if (p.sep_rot < 0 || p.sep_rot >= p.n_rot) bad = "sep_rot must lie in [0, n_rot)";
+    else if (p.min_hits < 0) bad = "min_hits must not be negative";
+    else if (p.min_percent < 0 || p.min_percent > 100) bad = "min_percent must lie in [0, 100]";
+    else if (p.min_margin < 0 || p.min_margin > 100) bad = "min_margin must lie in [0, 100]";
+    const double reach = ceil(c->sweep_max / c->cfg.res);
+    if (!bad && !(RL_TILE + 2 * (reach + p.radius + 1) <= 255))
+        bad = "the sweep filter's smax is too large for this resolution: 16 + 2 * (ceil(smax / res) + radius + 1) exceeds 255";
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
+    if (!p.use_box) { p.x0 = 0; p.y0 = 0; p.x1 = c->cfg.size; p.y1 = c->cfg.size; }
+    rs.p = p;
+    rs.M = (int)reach + 1;
+    return QS_OK;
+}
+
+static int reloc_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
+{
+    char msg[256];
+    const char *bad = nullptr;
+    if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO) bad = "stride must be 743 (v0) or 751 (v0 + odometry)";
+    else if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0) bad = "sharded contexts (seq_stride > 1, shard_bots > 0) do not take sweeps";
+    else if (n >= ((size_t)1 << 31)) bad = "at most 2^31 - 1 records per call";
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
+    return QS_OK;
+}
+
+// the workspace of one call over n_tiles box tiles, carved from ws (nullptr: only the bytes the block needs)
+struct QsRelocLayout { unsigned int *chunk, *list; unsigned long long *count, *table, *best, *excl; size_t bytes; };
+static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles)
+{
+    Carve cv(ws);
+    QsRelocLayout L;
+    L.chunk = cv.take<unsigned int>(qs_compact_chunks(n_tiles) + 1);
+    L.list = cv.take<unsigned int>(n_tiles + 1);
+    L.count = cv.take<unsigned long long>(1);
+    L.table = cv.take<unsigned long long>((size_t)RL_CHUNK * (n_tiles + 1));
+    L.best = cv.take<unsigned long long>(RL_CHUNK);
+    L.excl = cv.take<unsigned long long>((size_t)RL_CHUNK * 9);
+    L.bytes = cv.bytes;
+    return L;
+}
+
+// n device-resident records against the map as the stream finds it, into d_out; everything enqueued, nothing waited for
+// (but a workspace that has to grow waits for the stream first)
+static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned char *d_pkts, size_t n, size_t stride,
+                               const unsigned short *d_lens, qs_sweep_reloc *d_out)
+{
+    if (n == 0) return hipSuccess;
+    const qs_reloc_params &p = rs.p;
+    static const double kRad = 3.141592653589793 / 180.0, kTwoPi = 2.0 * 3.141592653589793;
+    if (!c->match_tab.p) {                                         // the beam angles' cos / sin: libm's, once per context (as match.hip)
+        double tab[2 * QS_SWEEP_BEAMS];
+        for (int i = 0; i < QS_SWEEP_BEAMS; i++) {
+            const double b = (double)(i - 90) * kRad;
+            tab[i] = cos(b); tab[QS_SWEEP_BEAMS + i] = sin(b);
+        }
+        HIPRET(c->match_tab.alloc(2 * QS_SWEEP_BEAMS));
+        HIPRET(hipMemcpy(c->match_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    }
+    if (c->reloc_nrot != p.n_rot) {                                // G2: the rotations' sin / cos and reported yaw, libm's
+        std::vector<double> rot(3 * (size_t)QS_RELOC_MAX_ROT, 0.0);
+        const double step = kTwoPi / (double)p.n_rot;
+        for (int j = 0; j < p.n_rot; j++) {
+            const double th = (double)j * step;
+            rot[3 * j] = sin(th); rot[3 * j + 1] = cos(th); rot[3 * j + 2] = th > 3.141592653589793 ? th - kTwoPi : th;
+        }
+        if (!c->reloc_rot.p) HIPRET(c->reloc_rot.alloc(3 * (size_t)QS_RELOC_MAX_ROT));
+        HIPRET(hipStreamSynchronize(c->stream));                   // (an earlier call may still read the old table)
+        c->reloc_nrot = 0;
+        HIPRET(hipMemcpy(c->reloc_rot.p, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice));
+        c->reloc_nrot = p.n_rot;
+    }
+    const int size = c->cfg.size;
+    QsRelocArgs m;
+    m.R = p.radius; m.n_rot = p.n_rot; m.sep = p.sep; m.sep_rot = p.sep_rot;
+    m.min_hits = p.min_hits; m.min_percent = p.min_percent; m.min_margin = p.min_margin;
+    m.bx0 = std::max(p.x0, 0); m.by0 = std::max(p.y0, 0); m.bx1 = std::min(p.x1, size); m.by1 = std::min(p.y1, size);
+    const bool empty = m.bx1 <= m.bx0 || m.by1 <= m.by0;
+    if (empty) { m.bx0 = m.by0 = m.bx1 = m.by1 = 0; }
+    m.tx0 = m.bx0 / RL_TILE; m.ty0 = m.by0 / RL_TILE;
+    m.ntx = empty ? 0 : (m.bx1 - 1) / RL_TILE - m.tx0 + 1;
+    m.nty = empty ? 0 : (m.by1 - 1) / RL_TILE - m.ty0 + 1;
+    const size_t n_tiles = (size_t)m.ntx * m.nty;
+    m.M = rs.M;
+    m.SA = RL_TILE + 2 * (m.M + m.R);                              // <= 255 (reloc_setup)
+    // rows of 4 x (an odd number) dwords: the 8 rows x 4 dwords a lane group of the scoring pass reads fall on 32 different banks
+    m.pitch = (m.SA + 15) & ~15;
+    if (!((m.pitch >> 4) & 1)) m.pitch += 16;
+    const size_t a_bytes = ((size_t)m.SA * m.pitch + 16 + 15) & ~(size_t)15;
+    const size_t b_bytes = std::max((size_t)m.SA * m.pitch, (size_t)RL_NW * RL_OFFP * sizeof(unsigned short));
+    m.off_b = (unsigned int)a_bytes;
+    const size_t lds = a_bytes + ((b_bytes + 15) & ~(size_t)15);
+    m.tab = c->match_tab.p; m.rot = c->reloc_rot.p; m.stamps = c->d_stamps.p;
+
+    HIPRET(c->reloc_ws.reserve(qs_reloc_layout(nullptr, n_tiles).bytes, c->stream, (size_t)1 << 16));
+    const QsRelocLayout L = qs_reloc_layout(c->reloc_ws.p, n_tiles);
+    m.list = L.list; m.count = L.count; m.table = L.table; m.table_pitch = n_tiles + 1; m.best = L.best; m.excl = L.excl;
+    if (n_tiles == 0) HIPRET(hipMemsetAsync(L.count, 0, sizeof(unsigned long long), c->stream));
+    else {
+        const RlTilePred pred{c->d_stamps.p, size, m.bx0, m.by0, m.bx1, m.by1, m.tx0, m.ty0, m.ntx};
+        const RlTileEmit emit{L.list};
+        HIPRET(qs_compact(c->stream, pred, n_tiles, false, emit, n_tiles, L.chunk, L.count));
+        HIPRET(qs_compact(c->stream, pred, n_tiles, true, emit, n_tiles, L.chunk, L.count));
+    }
+    if (lds > 32 * 1024) {                                         // long reaches: up to 2 x 65 KiB of the CU's 160
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    for (size_t k0 = 0; k0 < n; k0 += RL_CHUNK) {
+        const unsigned int nk = (unsigned int)std::min((size_t)RL_CHUNK, n - k0);
+        QsSweepArgs a;
+        qs_sweep_args(c, d_pkts + k0 * stride, nk, stride, d_lens ? d_lens + k0 : nullptr, QS_SWEEP_NO_GRAPH, a);
+        m.out = d_out + k0;
+        if (n_tiles) {
+            hipLaunchKernelGGL(qs_reloc_score_kernel<false>, dim3((unsigned int)n_tiles, nk), dim3(RL_BLOCK), lds, c->stream, a, c->geom, m);
+            HIPRET(hipGetLastError());
+        }
+        hipLaunchKernelGGL(qs_reloc_pick_kernel, dim3(nk), dim3(RL_BLOCK), 0, c->stream, m);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_score_kernel<true>, dim3(9, nk), dim3(RL_BLOCK), lds, c->stream, a, c->geom, m);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_final_kernel, dim3(nk), dim3(RL_BLOCK), 0, c->stream, a, c->geom, m);
+        HIPRET(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+// ---- C ABI: relocalisation (semantics in include/quasar_slam.h) ------------------------------------------------------------------
+extern "C" int qs_relocalise_sweeps_device(qs_ctx *c, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                           const uint16_t *d_lens, qs_sweep_reloc *d_out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || (d_pkts != nullptr && d_out != nullptr));
+    QsRelocSetup rs;
+    int rc = reloc_setup(c, params, "qs_relocalise_sweeps", rs);
+    if (rc != QS_OK) return rc;
+    rc = reloc_call_ok(c, n, stride, "qs_relocalise_sweeps");
+    if (rc != QS_OK || n == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, reloc_launch(c, rs, d_pkts, n, stride, d_lens, d_out));
+    return QS_OK;
+}
+
+extern "C" int qs_relocalise_sweeps(qs_ctx *c, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                                    const uint16_t *lens, qs_sweep_reloc *out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || (pkts != nullptr && out != nullptr));
+    QsRelocSetup rs;
+    int rc = reloc_setup(c, params, "qs_relocalise_sweeps", rs);
+    if (rc != QS_OK) return rc;
+    rc = reloc_call_ok(c, n, stride, "qs_relocalise_sweeps");
+    if (rc != QS_OK || n == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    const size_t chunk = (size_t)1 << 12;                          // records staged per round trip
+    for (size_t k0 = 0; k0 < n; k0 += chunk) {
+        const size_t nk = std::min(chunk, n - k0);
+        Staging s;
+        rc = reserve_staging(c, nk * stride, s);
+        if (rc != QS_OK) return rc;
+        HIPCHK(c, c->io_ws.reserve(nk * sizeof(qs_sweep_reloc), c->stream, QS_IO_WS_FLOOR));
+        qs_sweep_reloc *d_out = (qs_sweep_reloc *)c->io_ws.p;
+        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, nk * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, nk * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, reloc_launch(c, rs, s.pkts, nk, stride, lens ? s.lens : nullptr, d_out));
+        HIPCHK(c, hipMemcpyAsync(out + k0, d_out, nk * sizeof(qs_sweep_reloc), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return QS_OK;
+}

@@ -114,6 +114,7 @@ class QuasarMapper:
         self.bots_per_graph = bots_per_graph if bots_per_graph > 0 else max_agent
         self.n_graphs = (max_agent + self.bots_per_graph - 1) // self.bots_per_graph
         self._last_n = 0
+        self._bot_offset = {2: float(separation)} if max_agent >= 2 else {}
         self._map_version = 0          # bumped by everything that can change a cell: the look-alike's .grid cache key
         self.occ_grid = OccupancyGrid._attached(self)
         self.slam = PoseGraphSLAM._attached(self)
@@ -206,6 +207,13 @@ class QuasarMapper:
 
     def set_bot_offset(self, bot, off_x):
         self._chk(self._L.qs_set_bot_offset(self._h, bot, off_x), "qs_set_bot_offset")
+        self._bot_offset[int(bot)] = float(off_x)
+
+    def sweep_pose_shift(self, bot):
+        """(sx, sy): what a sweep ingest adds to the packet's x, y to form the pose it casts from -- the bot's offset (the
+        separation for bot 2, or set_bot_offset through this object) plus its closure drift as it stands."""
+        d = self.drift(bot)
+        return self._bot_offset.get(int(bot), 0.0) + float(d[0]), float(d[1])
 
     # -- ingest: dual_bot_mapper.py:826-919 ---------------------------------------------------
     def ingest(self, datagrams, recv_time=None, seq0=None):
@@ -450,6 +458,46 @@ class QuasarMapper:
         out = np.zeros(n or 0, dtype=P.MATCH_DTYPE)
         self._chk(self._L.qs_last_sweep_matches(self._h, _ptr(out) if n else None, n or 0), "qs_last_sweep_matches")
         return out
+
+    # -- relocalisation (include/quasar_slam.h, "relocalisation") -------------------------------------------------------------
+    @staticmethod
+    def relocalise_params(params=None, **kw):
+        """A qs_reloc_params from None / True (the defaults of protocol.RELOC_*), a dict of its fields, or one already built.
+        box = (x0, y0, x1, y1) searches the cells [x0, x1) x [y0, y1) only (clipped to the grid); None: the whole grid."""
+        if isinstance(params, _lib.QsRelocParams):
+            return params
+        d = dict(radius=P.RELOC_RADIUS, n_rot=P.RELOC_N_ROT, sep=P.RELOC_SEP, sep_rot=P.RELOC_SEP_ROT, min_hits=P.RELOC_MIN_HITS,
+                 min_percent=P.RELOC_MIN_PERCENT, min_margin=P.RELOC_MIN_MARGIN, box=None)
+        if isinstance(params, dict):
+            d.update(params)
+        elif params not in (None, True):
+            raise TypeError("relocalisation parameters: None, True, a dict or a QsRelocParams")
+        d.update(kw)
+        box = d.pop("box")
+        x0, y0, x1, y1 = (int(v) for v in box) if box is not None else (0, 0, 0, 0)
+        return _lib.QsRelocParams(use_box=int(box is not None), x0=x0, y0=y0, x1=x1, y1=y1, **{k: int(v) for k, v in d.items()})
+
+    def relocalise_sweeps(self, datagrams, lengths=None, params=None):
+        """Locate sweeps (as ingest_sweeps takes them) against the whole map, whatever pose they carry: a structured array of
+        protocol.RELOC_DTYPE, one entry per record -- the best pose, the best rival away from it, and whether the gate on
+        hits, score and margin accepts.  Reads the map, changes nothing."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        prm = self.relocalise_params(params)
+        out = np.zeros(n, dtype=P.RELOC_DTYPE)
+        self._chk(self._L.qs_relocalise_sweeps(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                               _ptr(out) if n else None), "qs_relocalise_sweeps")
+        return out
+
+    def relocalise_sweeps_device(self, d_pkts, n, stride, d_out, d_lens=0, params=None):
+        """Device-resident form (raw device addresses as ints; d_out: n records of protocol.RELOC_DTYPE); asynchronous."""
+        prm = self.relocalise_params(params)
+        self._chk(self._L.qs_relocalise_sweeps_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                      C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_out)),
+                  "qs_relocalise_sweeps_device")
 
     def last_sweeps(self):
         """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after

@@ -140,6 +140,20 @@ MATCH_MIN_PERCENT = 50       # ... nor one whose best score is under this share 
 MATCH_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("it", "<i4"), ("score", "<i4"), ("score0", "<i4"), ("hits", "<i4"),
                         ("accepted_record", "u1"), ("accepted_match", "u1"), ("pad", "u1", (6,)),
                         ("dx", "<f8"), ("dy", "<f8"), ("dyaw", "<f8")])
+# relocalisation (include/quasar_slam.h, "relocalisation"): build choices taken from a CPU prototype of the rule
+RELOC_RADIUS = 2             # the likelihood field's reach, as MATCH_RADIUS
+RELOC_N_ROT = 180            # rotation steps over the full turn
+RELOC_SEP = 4                # a rival lies more than this many cells from the best on an axis ...
+RELOC_SEP_ROT = 2            # ... or more than this many rotation steps
+RELOC_MIN_HITS = 40
+RELOC_MIN_PERCENT = 70       # the best score against hits * (radius + 1)
+RELOC_MIN_MARGIN = 5         # ... and its lead over the rival, in the same percent
+RELOC_MAX_ROT, RELOC_MAX_SEP = 360, 16
+RELOC_OK, RELOC_NO_RECORD, RELOC_NO_CANDIDATE = 0, 1, 2
+RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("score", "<i4"), ("hits", "<i4"),
+                        ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
+                        ("accepted_record", "u1"), ("accepted", "u1"), ("pad", "u1", (6,)),
+                        ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8")])
 
 
 # ---- map view (include/quasar_slam.h, "map view"): the renderer's constants, dual_bot_mapper.py:346-377, :383-397 ----------

@@ -39,6 +39,13 @@ last_matches holds the matches of the latest run.
 With sweep_graph=True or a dict of half_width / close / open (opt-in, needs sweeps=True) the mapper is put into graph mode at
 construction (QuasarMapper.set_sweep_graph): sweeps become pose-graph nodes, close loops and feed their bot's zone box, so
 zone_tick sends a sweep bot's partner a real box.
+With relocalise=True or a dict of relocalisation parameters (opt-in, needs sweeps=True, excludes sweep_graph: drift would move
+under the transform) the first accepted sweep of a bot that was offline, or was never seen, is located against the whole map
+before it is mapped (QuasarMapper.relocalise_sweeps).  When the gate accepts, the front-end keeps a rigid transform for that bot,
+from the pose the ingest would have formed (the packet's pose plus QuasarMapper.sweep_pose_shift) to the found pose, and
+rewrites the f32 x / y / yaw fields of that bot's sweep records from then on, the triggering one included, in its own buffer
+before they are ingested.  relocalised[bot] holds the latest accepted result, reloc_stats counts tried / accepted / rewritten.
+A relocalisation the gate does not accept changes nothing.
 With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
 point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
 poses; mapper.MapView.frame draws them.
@@ -61,7 +68,7 @@ class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
-                 targets_by_territory=False, targets_by_gain=False, gain_params=None):
+                 targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False):
         by = [k for k, on in (("targets_by_path", targets_by_path), ("targets_by_territory", targets_by_territory),
                               ("targets_by_gain", targets_by_gain)) if on]
         if not frontier_targets and (plan_paths or by):         # each of them refines frontier_targets
@@ -73,8 +80,17 @@ class MissionControl:
         self.sweep_graph = sweep_graph is not False and sweep_graph is not None      # ({} is on, with the defaults)
         if self.sweep_graph and not sweeps:
             raise ValueError("MissionControl: sweep_graph needs sweeps=True")
+        self.relocalise = relocalise is not False and relocalise is not None          # ({} is on, with the defaults)
+        if self.relocalise and not sweeps:
+            raise ValueError("MissionControl: relocalise needs sweeps=True")
+        if self.relocalise and self.sweep_graph:
+            raise ValueError("MissionControl: relocalise excludes sweep_graph (a closure's drift would move under the transform)")
         if self.sweep_graph:
             mapper.set_sweep_graph(True, **(dict(sweep_graph) if isinstance(sweep_graph, dict) else {}))
+        self.reloc_params = dict(relocalise) if isinstance(relocalise, dict) else True
+        self.relocalised = {}                        # bot -> the accepted result (a record of protocol.RELOC_DTYPE) in force
+        self.reloc_stats = {"tried": 0, "accepted": 0, "rewritten": 0}
+        self._reloc_T = {}                           # bot -> (cos, sin, dyaw, ingest x, y, found x, y, shift x, y)
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
         self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
@@ -155,6 +171,8 @@ class MissionControl:
                 if self.track_view:
                     self._track(i0, accepted, pose)
             else:
+                if self.relocalise:
+                    self._relocalise_run(self._buf[i0:i1, :kind], lens)
                 if self.match_sweeps:
                     self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens, match=self.match_params)
                     self.last_matches = self.mapper.last_sweep_matches()
@@ -172,6 +190,40 @@ class MissionControl:
         starts = np.concatenate(([0], cuts))
         ends = np.concatenate((cuts, [n]))
         return [(int(a), int(b), int(kind[a])) for a, b in zip(starts, ends)]
+
+    def _relocalise_run(self, run, lens):
+        """relocalise: one run of sweeps (a view of the receive buffer) before its ingest.  The bots whose first acceptable
+        record of the run finds them offline are relocalised on that record; then the records of every bot with a transform
+        in force get their pose fields rewritten in place."""
+        ok = ((lens == run.shape[1]) & (run[:, :4] == np.frombuffer(b"QSRL", dtype=np.uint8)).all(axis=1)
+              & (run[:, 4] >= 1) & (run[:, 4] <= self.max_agent))
+        idx = np.nonzero(ok)[0]
+        first = {}
+        for j in idx:
+            a = int(run[j, 4])
+            if not self.online[a] and a not in first:
+                first[a] = int(j)
+        shift_of = getattr(self.mapper, "sweep_pose_shift", None)
+        for a, j in first.items():
+            r = self.mapper.relocalise_sweeps(run[j:j + 1], lens[j:j + 1], params=self.reloc_params)[0]
+            self.reloc_stats["tried"] += 1
+            if not r["accepted"]:
+                continue
+            x, y, yaw = (float(v) for v in run[j, 5:17].view("<f4"))
+            sx, sy = (float(v) for v in shift_of(a)) if shift_of else (0.0, 0.0)
+            dyaw = float(r["yaw"]) - yaw
+            self._reloc_T[a] = (np.cos(dyaw), np.sin(dyaw), dyaw, x + sx, y + sy, float(r["x"]), float(r["y"]), sx, sy)
+            self.relocalised[a] = r.copy()
+            self.reloc_stats["accepted"] += 1
+        for j in idx:
+            T = self._reloc_T.get(int(run[j, 4]))
+            if T is None:
+                continue
+            c, s, dyaw, ix, iy, fx, fy, sx, sy = T
+            f = run[j, 5:17].view("<f4")
+            qx, qy = float(f[0]) + sx - ix, float(f[1]) + sy - iy
+            f[:] = (fx + (c * qx - s * qy) - sx, fy + (s * qx + c * qy) - sy, float(f[2]) + dyaw)
+            self.reloc_stats["rewritten"] += 1
 
     def _mark(self, i0, accepted, pose, now, keep_pose):
         """Bookkeeping of the accepted records of one ingest whose first datagram is slot i0 (:846-848, :860-864)."""

@@ -262,6 +262,61 @@ int qs_ingest_sweeps_matched_device(qs_ctx *ctx, const qs_match_params *params, 
                                     size_t stride, const uint16_t *d_lens, uint64_t seq0);
 int qs_last_sweep_matches(qs_ctx *ctx, qs_sweep_match *out, size_t n);
 
+/* ---- relocalisation (no reference counterpart: this build's own rule) ------------------------------------------------------
+ * A sweep whose pose is unknown (a bot that rebooted, was carried, or joins a map another bot drew) is located against the
+ * whole map: every FREE cell of a search box and every rotation step is a candidate pose, scored on the likelihood field of
+ * sweep matching.  There is no coarse level: the search is exhaustive.  Everything is integer or uncontracted fp64 and there
+ * is no device trigonometry, so the device and the CPU restatement (tests/reloc_rules.py) agree bit for bit.
+ *  G1. Field: sweep-matching rule 1 with radius R: L = max(0, R + 1 - Chebyshev distance to the nearest OCCUPIED cell), 0
+ *      off the grid.
+ *  G2. Rotations: n_rot in 1..360; th_j = j * (2 pi / n_rot) (one divide, one multiply).  (S_j, C_j) = (sin, cos)(th_j)
+ *      from the HOST's libm, uploaded as the 181 beam CB / SB are.
+ *  G3. Beams: record acceptance, hit beams (smin < d <= smax, the context's sweep filter), H, bx_i = d_i * CB[i] and
+ *      by_i = d_i * SB[i] exactly as in sweep-matching rule 3.  The packet's pose, the bot's offset and its drift are NOT
+ *      used.  For rotation j: ex = C_j * bx_i - S_j * by_i, ey = S_j * bx_i + C_j * by_i, in this association; cell offset
+ *      ax = (int)floor(ex / res + 0.5), ay likewise: the robot stands at the centre of its cell.
+ *  G4. Candidates (gx, gy, j): (gx, gy) inside the search box [x0, x1) x [y0, y1) clipped to the grid, the cell FREE (0 in
+ *      qs_grid_i8).  use_box = 0: the whole grid.  score = sum over hit beams of L[gy + ay_i][gx + ax_i].
+ *  G5. Order: higher score first, then smaller j, then smaller gy, then smaller gx.  The best is first in this order.
+ *  G6. Rival: the first candidate in the same order among those with |gx - bx*| > sep or |gy - by*| > sep or a circular
+ *      rotation distance min(|j - j*|, n_rot - |j - j*|) > sep_rot, (bx*, by*, j*) the best.  None qualifies: score2 = 0,
+ *      gx2 = gy2 = j2 = -1.
+ *  G7. Gate: accepted when H >= min_hits and score * 100 >= min_percent * H * (R + 1) and
+ *      (score - score2) * 100 >= min_margin * H * (R + 1).
+ *  G8. Pose: x = ox + (gx + 0.5) * res, y likewise, yaw = th_j, minus 2 pi when th_j > pi.  Reported whether or not the
+ *      gate accepts.
+ *  G9. Status: QS_RELOC_OK; QS_RELOC_NO_RECORD: the record is rejected, all other fields are zero; QS_RELOC_NO_CANDIDATE:
+ *      the box holds no FREE cell, or H = 0 (accepted_record = 1, hits = H, the six cell fields -1, the rest zero).  An
+ *      empty map gives score 0 and is never accepted (min_percent, min_margin > 0).
+ * params NULL = radius 2, n_rot 180, sep 4, sep_rot 2, min_hits 40, min_percent 70, min_margin 5, the whole grid.
+ * Limits: radius <= QS_MATCH_MAX_RADIUS, 16 + 2 * (ceil(smax / res) + radius + 1) <= 255, sep <= QS_RELOC_MAX_SEP,
+ * sep_rot < n_rot, min_hits >= 0, min_percent and min_margin in 0..100.  QS_E_INVAL beyond any of them; the text names the
+ * quantity.  Stride, lengths and refusals as qs_match_sweeps.
+ * The calls read the map (waiting exact-trig rays are flushed first) and write nothing to the context: a checkpoint taken
+ * before equals one taken after. */
+#define QS_RELOC_MAX_ROT 360
+#define QS_RELOC_MAX_SEP 16
+#define QS_RELOC_OK 0
+#define QS_RELOC_NO_RECORD 1
+#define QS_RELOC_NO_CANDIDATE 2
+typedef struct qs_reloc_params {
+    int32_t radius, n_rot, sep, sep_rot, min_hits, min_percent, min_margin, use_box;
+    int32_t x0, y0, x1, y1;
+} qs_reloc_params;
+typedef struct qs_sweep_reloc {
+    int32_t gx, gy, j, score, hits;
+    int32_t gx2, gy2, j2, score2;
+    int32_t status;
+    uint8_t accepted_record, accepted, pad[6];
+    double x, y, yaw;
+} qs_sweep_reloc;
+int qs_relocalise_sweeps(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                         const uint16_t *lens, qs_sweep_reloc *out);
+/* same with device-resident pkts / lens / out; asynchronous on the context's stream (a call with another n_rot than the
+ * last one, or one whose workspace has to grow, waits for the stream first) */
+int qs_relocalise_sweeps_device(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                const uint16_t *d_lens, qs_sweep_reloc *d_out);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

@@ -218,6 +218,8 @@ SIGNATURES = {
     "qs_chain_form": (_i32, [_vp]),
     "qs_set_chain_lean": (_i32, [_vp, _i32, _i64]),
     "qs_chain_lean": (_i32, [_vp]),
+    "qs_set_chain_lookahead": (_i32, [_vp, _i32]),
+    "qs_chain_lookahead": (_i32, [_vp]),
     "qs_set_chain_plan": (_i32, [_vp, _i32]),
     "qs_chain_plan": (_i32, [_vp]),
     "qs_voxel_downsample": (_i32, [_vp, _vp, _sz, _f64, _vp, _sz, C.POINTER(_sz)]),

@@ -378,6 +378,19 @@ extern "C" int qs_chain_plan(qs_ctx *c)
     return qs_chain_lean(c);                     // (a plan was built: walked by every graph that ran the lean owner)
 }
 
+extern "C" int qs_set_chain_lookahead(qs_ctx *c, int32_t on)
+{
+    ARGCHK(c, c != nullptr);
+    c->chain_lookahead = on != 0;
+    return QS_OK;
+}
+
+extern "C" int qs_chain_lookahead(qs_ctx *c)
+{
+    if (!c) return QS_E_INVAL;
+    return c->chain_lookahead ? 1 : 0;
+}
+
 extern "C" int qs_sync(qs_ctx *c)
 {
     ARGCHK(c, c != nullptr);

@@ -39,6 +39,10 @@ struct QsNcclId { char internal[QS_RCCL_ID_BYTES]; };     // ncclUniqueId (rccl.
 // the 3x3 buckets around it; the first match in list order is the lowest node index among them.
 #define QS_NTYPES 5               // landmark types 1..5 are indexed (LM_CORNER_L..LM_OPEN, :68-74)
 #define QS_NODE_CAP 7
+// The eighth index slot is the node's look-ahead word: idx[QS_NODE_LOOKAHEAD] of node n holds the index of entry 0 of n's successor
+// node once that entry exists, the empty marker until then.  chain_insert_lanes (slam.hip) writes it with that entry, in the
+// same batch; entries are in insertion order, so nothing in the successor chain lies below it.  x[7] and y[7] stay unused.
+#define QS_NODE_LOOKAHEAD QS_NODE_CAP
 struct alignas(64) QsLmNode { long long idx[8]; double x[8]; double y[8]; };   // idx 0x7f7f.. = empty slot
 struct QsDirEntry { unsigned int head, tail, tail_cnt, pad; };                  // head 0 = empty bucket (insert-side bookkeeping)
 struct QsBucketGeom { double bx0, by0, cell, inv_cell; unsigned int hmask, pad; };   // hmask + 1 = table entries per type
@@ -331,6 +335,7 @@ struct qs_ctx {
     bool chain_last_lean_asked = false;          // the last launch was that kernel with the lean owner on offer
     bool chain_plan = true;                      // the lean owner walks a per-agent plan of its events (qs_set_chain_plan) ...
     bool chain_last_plan = false;                // ... and the last launch had one built for it
+    bool chain_lookahead = true;                 // the lean owner tests a node's look-ahead word before it walks on (qs_set_chain_lookahead)
     unsigned int *h_chain_stat = nullptr;        // pinned: [0..3] the four running totals as copied last, [4..7] as consumed last
     hipEvent_t ev_chain_stat = nullptr;          // ... complete when the copy has landed
     bool chain_stat_pending = false;

@@ -411,6 +411,10 @@ __device__ inline void chain_insert_lanes(const QsGraphDev &G, bool inw, int ran
         const unsigned int sl = p < QS_NODE_CAP ? p : (p - QS_NODE_CAP) % QS_NODE_CAP;
         QS_GLOBAL QsLmNode *np = nodes + nd;
         np->idx[sl] = idx; np->x[sl] = x; np->y[sl] = y;
+        // entry 0 of a new pool node: also the look-ahead word of the node before it (qs_internal.h) -- the chain's tail for the
+        // batch's first new node, nd - 1 for further ones (a bucket's new nodes of one batch are consecutive).  With the entry,
+        // in the same batch: complete before whoever called waits for its stores and lets anybody see the entry.
+        if (p >= QS_NODE_CAP && sl == 0) nodes[nd == base ? tail : nd - 1].idx[QS_NODE_LOOKAHEAD] = idx;
         if (ldr == lane) {
             QsDirEntry upd;
             upd.head = 1u + key; upd.tail = tail; upd.tail_cnt = total; upd.pad = de.head ? de.pad + nn : nn;     // pad: pool nodes of this chain
@@ -1161,7 +1165,7 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                           int max_agent, int min_between, double r2thr, double corr,
                           double *__restrict__ drift, long long *__restrict__ last_closure,
                           unsigned long long *__restrict__ counters, int raw_pose, unsigned int *__restrict__ pile_flag,
-                          long long lean_limit, unsigned int lean_seq)
+                          long long lean_limit, unsigned int lean_seq, unsigned int la_off)
 {
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     QsGraphDev *const Gp = graphs + g;
@@ -1173,6 +1177,9 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
     // 0: off), the node table's byte offsets fit 32 bits, the cool-down cannot overflow a 32-bit difference, and poses get
     // their drift.  Worked out here, by every wave for itself, from what is on the device at launch (the committer moves n_nodes
     // only at its end, long after this read).
+    // la_off: the byte offset in a node of the word the lean owner tests before it walks a bucket on -- the look-ahead word
+    // (qs_internal.h), or, with the look-ahead switched off, the node's last entry.  A launch argument, the same in every lane:
+    // the choice is made here and costs the decisions' loop no branch.
     // (Not in the instantiations that post poses, nor in the 8-wave DENSE one: the second owner loop costs <false, 16, true> scratch
     // and the 8-wave ones a wave of occupancy.  They run the general owner as before.)
     constexpr bool LEAN_OK = !POST && !(DENSE && WAVES == 8);
@@ -1890,7 +1897,8 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
 #define FR_LAUNCH(DENSE_, WAVES_, POST_) hipLaunchKernelGGL((qs_slam_chain_free_kernel<DENSE_, WAVES_, POST_>), dim3(G), dim3(WAVES_ * QS_WAVE), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE, \
-                           c->chain_lean_mode == QS_CHAIN_LEAN_OFF ? 0ll : c->chain_lean_limit, c->chain_lean_seq)
+                           c->chain_lean_mode == QS_CHAIN_LEAN_OFF ? 0ll : c->chain_lean_limit, c->chain_lean_seq,                          \
+                           (unsigned int)((c->chain_lookahead ? QS_NODE_LOOKAHEAD : QS_NODE_CAP - 1) * sizeof(long long)))
 #define DY_LAUNCH(DENSE_) hipLaunchKernelGGL((qs_slam_chain_dyn_kernel<DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)

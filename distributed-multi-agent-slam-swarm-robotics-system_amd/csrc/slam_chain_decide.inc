@@ -11,10 +11,17 @@
                 // The lean owner's decision by the first rows alone -- what free_query's first round works out, on 32-bit indices:
                 // who is within the limit (eff = min(frontier as read before the rows, limit); negative: nobody) and within the
                 // radius, the lowest index among them, and whether any bucket would have to be walked further: one whose node is
-                // full within the limit, has a successor, and ends below the match (a bucket with a hit of its own ends at or
-                // above the match, so "has no hit" needs no term).  A match and no such bucket: decided -- free_query would
-                // leave its loop after this round with the same match, and with an empty side list return it.  Anything else:
-                // free_query, from the same rows, as if nothing had been looked at.
+                // full within the limit, has a successor, and whose successor starts below the match.  A match and no such
+                // bucket: decided -- free_query would find nothing lower behind it, and with an empty side list return the same
+                // match.  Anything else: free_query, from the same rows, as if nothing had been looked at.
+                // "Starts below the match" is read from the node's look-ahead word (rla32: QsLmNode, qs_internal.h), and is exact:
+                // a chain's entries are in insertion order, so all of a successor chain lies at or above its first entry, and a
+                // chain whose first entry is not below the match cannot lower the minimum.  An empty word reads 0x7f7f7f7f, above
+                // every index and every eff: nothing to go on to.  It cannot read empty while a successor entry at or below eff
+                // exists: that entry's batch, the look-ahead store included, was complete before the frontier that was read
+                // ahead of the loads.  (With the look-ahead switched off -- la_off, qs_set_chain_lookahead -- the same load
+                // brings the node's last entry: "ends below the match", free_query's rule; a bucket with a hit of its own ends
+                // at or above the match, so "has no hit" needs no term.)
                 bool fast = false;
                 if constexpr (LEAN) {
                     if (nm_rows == 0) {
@@ -24,7 +31,7 @@
                         const bool hit = inlim && dx * dx + dy * dy < r2thr;                  // :308-309
                         if (__ballot(hit)) {
                             const unsigned int g32 = wave_min_u32(hit ? (unsigned int)rid32 : 0xffffffffu);
-                            const unsigned long long more = __ballot(inlim) & ~__ballot(rid32 >= (int)g32) & __ballot(rows.nxt != 0) & L_LAST9;
+                            const unsigned long long more = __ballot(inlim) & ~__ballot(rla32 >= (int)g32) & __ballot(rows.nxt != 0) & L_LAST9;
                             if (more == 0) {
                                 const int w = __ffsll((long long)__ballot(hit && rid32 == (int)g32)) - 1;
                                 gbest = (long long)g32; wx = rlf64(rows.nx, w); wy = rlf64(rows.ny, w);
@@ -32,18 +39,20 @@
                             } else if (!DENSE) {
                                 // A match, and buckets to walk further: free_query's loop from its second round on, on the low
                                 // words -- a lane keeps its first hit, a bucket goes on while it has no hit, its node is full
-                                // within the limit and ends below the best match so far, and has a successor.  (DENSE counts
-                                // rounds towards its scan of the log: it takes the general query from the start.)
+                                // within the limit, has a successor, and that successor starts below the best match so far (the
+                                // round's node's look-ahead word, as above).  (DENSE counts rounds towards its scan of the log:
+                                // it takes the general query from the start.)
                                 st_slow++;
                                 const int l_last = min(l_nbk * QS_NODE_CAP + QS_NODE_CAP - 1, 63);
                                 unsigned int node = ((more >> l_last) & 1ull) ? rows.nxt : 0u, g = g32;
                                 int best32 = hit ? rid32 : 0x7fffffff;
                                 double bx = rows.nx, by = rows.ny;
                                 while (__ballot(node != 0)) {
-                                    int id = 0x7fffffff; double nx = 0, ny = 0; unsigned int nxt = 0;
+                                    int id = 0x7fffffff, la = 0x7fffffff; double nx = 0, ny = 0; unsigned int nxt = 0;
                                     if (node) {
                                         const QS_GLOBAL char *const row = (const QS_GLOBAL char *)g_nodes + (node * (unsigned int)sizeof(QsLmNode) + l_se8);
                                         id = *(const QS_GLOBAL int *)row;
+                                        la = *(const QS_GLOBAL int *)((const QS_GLOBAL char *)g_nodes + (node * (unsigned int)sizeof(QsLmNode) + la_off));
                                         nx = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, x));
                                         ny = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, y));
                                         nxt = g_next[node];
@@ -56,7 +65,7 @@
                                     }
                                     if (__ballot(newhit)) { const unsigned int v = wave_min_u32(newhit ? (unsigned int)id : 0xffffffffu); g = v < g ? v : g; }
                                     const unsigned long long hitm = __ballot(best32 != 0x7fffffff);
-                                    const unsigned long long goon = __ballot(inl) & ~__ballot(id >= (int)g);
+                                    const unsigned long long goon = __ballot(inl) & ~__ballot(la >= (int)g);
                                     const bool b_hit = ((hitm >> (l_nbk * QS_NODE_CAP)) & 0x7full) != 0;
                                     if (node) node = (b_hit || !((goon >> l_last) & 1ull) || nxt == 0) ? 0u : nxt;
                                 }

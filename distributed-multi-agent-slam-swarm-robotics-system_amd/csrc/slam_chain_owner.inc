@@ -64,7 +64,7 @@
             // is; no node: INT_MAX), no second load for the node's last index (the decision takes it from a ballot), one 32-bit
             // byte offset from the table's base, the hash from the lane's constants.  And the side list's length as of the
             // frontier just read (read after it: not older): a decision is only settled by its first rows while that is 0.
-            int rid32 = 0x7fffffff;
+            int rid32 = 0x7fffffff, rla32 = 0x7fffffff;                              // (rla32: the node's look-ahead word, slam_chain_decide.inc)
             long long nm_rows = 0;
             auto start_decision_lean = [&](unsigned long long e_) {
                 fr_rows = LDS_RLX(&s_frontier);
@@ -82,10 +82,11 @@
                 h ^= h >> 15;
                 node0 = (indexed && l_in9) ? 1u + (unsigned int)(qtype - 1) * (bg.hmask + 1u) + (h & bg.hmask) : 0u;
                 __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                rid32 = 0x7fffffff; rows.nx = 0; rows.ny = 0; rows.nxt = 0;
+                rid32 = 0x7fffffff; rla32 = 0x7fffffff; rows.nx = 0; rows.ny = 0; rows.nxt = 0;
                 if (node0) {
                     const QS_GLOBAL char *const row = (const QS_GLOBAL char *)g_nodes + (node0 * (unsigned int)sizeof(QsLmNode) + l_se8);
                     rid32 = *(const QS_GLOBAL int *)row;
+                    rla32 = *(const QS_GLOBAL int *)((const QS_GLOBAL char *)g_nodes + (node0 * (unsigned int)sizeof(QsLmNode) + la_off));
                     rows.nx = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, x));
                     rows.ny = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, y));
                     rows.nxt = g_next[node0];

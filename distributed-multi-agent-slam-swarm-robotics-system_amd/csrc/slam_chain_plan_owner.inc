@@ -36,7 +36,7 @@
             double qx = 0, qy = 0;
             unsigned int node0 = 0;
             FqRows rows = {LL_MAX, LL_MAX, 0, 0, 0u};
-            int rid32 = 0x7fffffff;
+            int rid32 = 0x7fffffff, rla32 = 0x7fffffff;
             long long nm_rows = 0;
             int eff32_n = -1;
             auto lean_eff32 = [&](long long) -> int { return eff32_n; };
@@ -59,10 +59,11 @@
                 h ^= h >> 15;
                 node0 = (indexed && l_in9) ? 1u + (unsigned int)(qtype - 1) * (bg.hmask + 1u) + (h & bg.hmask) : 0u;
                 __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                rid32 = 0x7fffffff; rows.nx = 0; rows.ny = 0; rows.nxt = 0;
+                rid32 = 0x7fffffff; rla32 = 0x7fffffff; rows.nx = 0; rows.ny = 0; rows.nxt = 0;
                 if (node0) {
                     const QS_GLOBAL char *const row = (const QS_GLOBAL char *)g_nodes + (node0 * (unsigned int)sizeof(QsLmNode) + l_se8);
                     rid32 = *(const QS_GLOBAL int *)row;
+                    rla32 = *(const QS_GLOBAL int *)((const QS_GLOBAL char *)g_nodes + (node0 * (unsigned int)sizeof(QsLmNode) + la_off));
                     rows.nx = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, x));
                     rows.ny = *(const QS_GLOBAL double *)(row + offsetof(QsLmNode, y));
                     rows.nxt = g_next[node0];

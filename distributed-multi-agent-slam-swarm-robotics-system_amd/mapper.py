@@ -929,6 +929,19 @@ class QuasarMapper:
             self._chk(r, "qs_chain_plan")
         return bool(r)
 
+    def set_chain_lookahead(self, on=True):
+        """The lean owner walks a bucket on only if its node's look-ahead word -- the index of the successor node's first
+        entry -- lies below the match it has (default), or by the node's own last entry as the general query does
+        (on=False).  Same results either way; fewer walks with it on."""
+        self._chk(self._L.qs_set_chain_lookahead(self._h, 1 if on else 0), "qs_set_chain_lookahead")
+
+    def chain_lookahead(self):
+        """Whether the lean owner tests the look-ahead word."""
+        r = self._L.qs_chain_lookahead(self._h)
+        if r < 0:
+            self._chk(r, "qs_chain_lookahead")
+        return bool(r)
+
     def mfma_f64_rate(self):
         """Measured dense fp64 MFMA rate of this GPU in TFLOP/s (diagnostic)."""
         v = C.c_double()

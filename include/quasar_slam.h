@@ -501,6 +501,15 @@ int qs_chain_lean(qs_ctx *ctx);
 int qs_set_chain_plan(qs_ctx *ctx, int32_t on);
 int qs_chain_plan(qs_ctx *ctx);
 
+/* Every node of a bucket chain carries, beside its seven entries, the node index of its successor node's first entry (the
+ * look-ahead word; written always).  The lean owner walks a bucket on only if that index lies below the match it has: entries
+ * are in insertion order, so a successor chain that starts at or above the match cannot hold an older one.
+ * qs_set_chain_lookahead: on != 0 (default) tests the look-ahead word, 0 the node's own last entry, as the general query does --
+ * the same instructions on another word of the node, chosen per launch.  Same closures, landmarks and drifts bit for bit; with
+ * it on, fewer decisions walk (slam_node_iters).  qs_chain_lookahead: the setting, 1 or 0; < 0: error. */
+int qs_set_chain_lookahead(qs_ctx *ctx, int32_t on);
+int qs_chain_lookahead(qs_ctx *ctx);
+
 /* diagnostic: measured dense fp64 MFMA rate of this GPU (TFLOP/s), the ceiling qs_nn_search mode 2 is priced against */
 int qs_diag_mfma_f64_rate(qs_ctx *ctx, double *tflops);
 /* diagnostic: latencies of the primitives one loop-closure decision chains together, measured on this GPU by ONE workgroup

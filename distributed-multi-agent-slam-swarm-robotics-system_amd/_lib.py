@@ -76,6 +76,19 @@ class QsSweepReloc(C.Structure):
                 ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
 
 
+class QsRelocRel(C.Structure):
+    """struct qs_reloc_rel (include/quasar_slam.h)."""
+    _fields_ = [("tx", C.c_double), ("ty", C.c_double), ("s", C.c_double), ("c", C.c_double)]
+
+
+class QsGroupReloc(C.Structure):
+    """struct qs_group_reloc (include/quasar_slam.h)."""
+    _fields_ = [("gx", C.c_int32), ("gy", C.c_int32), ("j", C.c_int32), ("score", C.c_int32), ("hits", C.c_int32),
+                ("gx2", C.c_int32), ("gy2", C.c_int32), ("j2", C.c_int32), ("score2", C.c_int32), ("status", C.c_int32),
+                ("records", C.c_uint8), ("accepted", C.c_uint8), ("pad", C.c_uint8 * 6),
+                ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
+
+
 class QsMergeResult(C.Structure):
     """struct qs_merge_result (include/quasar_slam.h)."""
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_local", C.c_uint64), ("n_global", C.c_uint64),
@@ -169,6 +182,8 @@ SIGNATURES = {
     "qs_last_sweep_matches": (_i32, [_vp, _vp, _sz]),
     "qs_relocalise_sweeps": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "qs_relocalise_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "qs_relocalise_groups": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.c_double, _vp]),
+    "qs_relocalise_groups_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.c_double, _vp]),
     "qs_sense_ranges": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_ranges_device": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_sweeps": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),

@@ -15,6 +15,18 @@
 //   5. qs_reloc_final_kernel: rival = max of the table entries of all other tiles (wholly outside the square, so their stored
 //      best is eligible) and the re-scored ones; gate; outputs.
 // Sweeps run in chunks of RL_CHUNK through one workspace (qs_reloc_layout).
+//
+// A GROUP of sweeps ("relocalisation of a group", J1-J8) is located the same way from the points of all its records in the
+// group's frame:
+//   0. qs_reloc_points_kernel, one wave per group, stages each record of the group in turn and ballot-compacts the hit points
+//      (px, py doubles) into the group's slice of the workspace, with H and the number of counting records behind them;
+//   2'. qs_reloc_group_score_kernel is step 2 with the offsets formed from that list (read through L2, the same for every
+//      tile's workgroup) instead of a staged record; the pass over the offsets (rl_sum_list) and the choice of the keys
+//      (rl_take) are the single sweep's own routines.  A wave's offset list holds up to 16 x 181 offsets, so the second LDS
+//      region is sized for four such lists (23 KiB) where the patch is smaller: one pass over one list, as for one sweep,
+//      rather than a walk in pieces that would rebuild the offsets or keep partial sums per piece;
+//   3-5. pick as it is; the EXCL instantiation and the final step in their group forms.
+// Groups run RL_CHUNK to a launch; their first records travel as a kernel argument (RlGroupArgs::start).
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -27,7 +39,11 @@
 #define RL_NW (RL_BLOCK / QS_WAVE)
 #define RL_TILE 16
 #define RL_OFFP 184               // 16-bit offsets per wave: >= 181, a multiple of 8 (16-byte reads)
-#define RL_CHUNK 64               // sweeps per launch
+#define RL_CHUNK 64               // sweeps, or groups, per launch
+// points of a group: QS_RELOC_MAX_GROUP records of 181 beams.  With R = 7 the largest score is 2896 x 8 = 23 168: it fits the
+// 16-bit halves the byte sums are spilled to and the 23 bits of the key's score field
+#define RL_GPTS (QS_RELOC_MAX_GROUP * QS_SWEEP_BEAMS)
+#define RL_GOFFP ((RL_GPTS + 7) / 8 * 8 + 8)   // 16-bit offsets per wave of the group form: 2 904
 
 // key: (score + 1) << 41 | (511 - j) << 32 | (65535 - gy) << 16 | (65535 - gx): larger is earlier in the order of G5; 0 = none
 __device__ inline unsigned long long rl_key(unsigned int score, int j, unsigned int low)
@@ -44,7 +60,7 @@ struct QsRelocArgs {
     int R, n_rot, sep, sep_rot, min_hits, min_percent, min_margin;
     int bx0, by0, bx1, by1;       // the search box clipped to the grid (empty: bx1 <= bx0 or by1 <= by0)
     int tx0, ty0, ntx, nty;       // the tiles it meets
-    int M;                        // cells a beam's end can lie from the robot's cell: ceil(smax / res) + 1
+    int M;                        // cells a beam's end can lie from the robot's cell: ceil(smax / res) + 1 (a group's frame: smax + travel)
     int SA, pitch;                // patch side 16 + 2 (M + R) and bytes per row (16 x an odd number)
     unsigned int off_b;           // byte offset of the second LDS region (dilation scratch, then the waves' offset lists)
     const double *tab;            // [2][181] cos, sin of the beam angles (the matcher's table)
@@ -57,6 +73,16 @@ struct QsRelocArgs {
     unsigned long long *best;     // [RL_CHUNK]
     unsigned long long *excl;     // [RL_CHUNK][9]
     qs_sweep_reloc *out;          // [n] of this chunk
+};
+
+// what the group form adds, per chunk of at most RL_CHUNK groups; records are counted from the chunk's first
+struct RlGroupArgs {
+    const qs_reloc_rel *rel;      // [records of the chunk]
+    double travel;
+    double *pts;                  // [RL_CHUNK][2][RL_GPTS] px, py of the groups' hit points
+    unsigned int *meta;           // [RL_CHUNK][2] H, counting records
+    qs_group_reloc *out;          // [groups of the chunk]
+    unsigned int start[RL_CHUNK + 1];   // group g's records are [start[g], start[g + 1])
 };
 
 // ---- census ------------------------------------------------------------------------------------------------------------------
@@ -106,6 +132,112 @@ __device__ inline void rl_square_tiles(int gx, int gy, int sep, int &tlx, int &t
     tly = (gy - sep) >> 4; thy = (gy + sep) >> 4;
 }
 
+// the tile of workgroup bx for sweep / group k: 0 = none and nothing to write, 1 = none, the slot gets 0, 2 = (tx, ty); EXCL: the
+// best (bgx, bgy, bj) round which the tiles are re-scored
+template <bool EXCL>
+__device__ __forceinline__ int rl_tile(const QsRelocArgs &m, size_t k, unsigned int bx, int &tx, int &ty, int &bgx, int &bgy, int &bj)
+{
+    if (EXCL) {
+        const unsigned long long bk = m.best[k];
+        if (bk == 0) return 1;                                     // (no candidate at all: nothing to exclude)
+        bgx = rl_key_gx(bk); bgy = rl_key_gy(bk); bj = rl_key_j(bk);
+        int tlx, tly, thx, thy;
+        rl_square_tiles(bgx, bgy, m.sep, tlx, tly, thx, thy);
+        tx = tlx + (int)(bx % 3u); ty = tly + (int)(bx / 3u);
+        if (tx > thx || ty > thy || tx < m.tx0 || tx >= m.tx0 + m.ntx || ty < m.ty0 || ty >= m.ty0 + m.nty) return 1;
+    } else {
+        if ((unsigned long long)bx >= *m.count) return 0;          // (the grid is sized for every tile of the box)
+        const int ti = (int)m.list[bx];
+        tx = m.tx0 + ti % m.ntx; ty = m.ty0 + ti / m.ntx;
+    }
+    return 2;
+}
+
+// the lane's four candidates, row `row` and columns 4 cg .. 4 cg + 3 of tile (tx, ty): which are candidates (mask), which lie in
+// the square round the best (sq, EXCL), and the low halves of their keys
+template <bool EXCL>
+__device__ __forceinline__ void rl_lane_cells(const QsRelocArgs &m, int size, int tx, int ty, int row, int cg, int bgx, int bgy,
+                                              unsigned int &mask, unsigned int &sq, unsigned int low[4])
+{
+    const int gy = ty * RL_TILE + row, gxb = tx * RL_TILE + 4 * cg;
+    mask = 0; sq = 0;
+    #pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int gx = gxb + e;
+        low[e] = ((unsigned int)(65535 - gy) << 16) | (unsigned int)(65535 - gx);
+        if (gx >= m.bx0 && gx < m.bx1 && gy >= m.by0 && gy < m.by1 && rl_free(m.stamps[(size_t)gy * size + gx])) mask |= 1u << e;
+        if (EXCL && abs(gx - bgx) <= m.sep && abs(gy - bgy) <= m.sep) sq |= 1u << e;
+    }
+}
+
+// the field bytes of the lane's four cells summed over the cnt offsets of list o (cnt the same in every lane), into the 16-bit
+// halves lo (cells 0, 2) and hi (cells 1, 3); span = offsets whose byte sums cannot overflow
+__device__ __forceinline__ void rl_sum_list(const unsigned int *A, const unsigned short *o, int cnt, int span, unsigned int lane_off,
+                                            unsigned int &lo, unsigned int &hi)
+{
+    lo = 0; hi = 0;
+    for (int b0 = 0; b0 < cnt; b0 += span) {
+        const int b1 = min(b0 + span, cnt);
+        unsigned int acc = 0;
+        int b = b0;
+        for (; b + 8 <= b1; b += 8) {                              // eight beams: one 16-byte read of offsets, sixteen dword reads in flight
+            const uint4 q = *(const uint4 *)(o + b);
+            acc += mt_look(A, lane_off + (q.x & 0xffffu));
+            acc += mt_look(A, lane_off + (q.x >> 16));
+            acc += mt_look(A, lane_off + (q.y & 0xffffu));
+            acc += mt_look(A, lane_off + (q.y >> 16));
+            acc += mt_look(A, lane_off + (q.z & 0xffffu));
+            acc += mt_look(A, lane_off + (q.z >> 16));
+            acc += mt_look(A, lane_off + (q.w & 0xffffu));
+            acc += mt_look(A, lane_off + (q.w >> 16));
+        }
+        for (; b + 4 <= b1; b += 4) {
+            const uint2 q = *(const uint2 *)(o + b);
+            acc += mt_look(A, lane_off + (q.x & 0xffffu));
+            acc += mt_look(A, lane_off + (q.x >> 16));
+            acc += mt_look(A, lane_off + (q.y & 0xffffu));
+            acc += mt_look(A, lane_off + (q.y >> 16));
+        }
+        for (; b < b1; b++) acc += mt_look(A, lane_off + o[b]);
+        lo += acc & 0x00ff00ffu;
+        hi += (acc >> 8) & 0x00ff00ffu;
+    }
+}
+
+// the lane's four scores under rotation j against its best key so far
+template <bool EXCL>
+__device__ __forceinline__ void rl_take(const QsRelocArgs &m, unsigned int lo, unsigned int hi, unsigned int mask, unsigned int sq,
+                                        const unsigned int low[4], int j, int bj, unsigned long long &best)
+{
+    const unsigned int sc[4] = {lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16};
+    unsigned int use = mask;
+    if (EXCL) {
+        const int dj = abs(j - bj);
+        if (min(dj, m.n_rot - dj) <= m.sep_rot) use &= ~sq;        // G6: too close to the best on every axis
+    }
+    #pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const unsigned long long key = rl_key(sc[e], j, low[e]);
+        if (((use >> e) & 1u) && key > best) best = key;
+    }
+}
+
+// the workgroup's best key into *dst
+__device__ __forceinline__ void rl_store_best(unsigned long long best, unsigned long long *s_key, unsigned long long *dst, int tid)
+{
+    #pragma unroll
+    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
+        const unsigned long long other = __shfl_xor(best, d);
+        best = other > best ? other : best;
+    }
+    if ((tid & (QS_WAVE - 1)) == 0) s_key[tid >> 6] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < RL_NW; w++) best = s_key[w] > best ? s_key[w] : best;
+        *dst = best;
+    }
+}
+
 // ---- scores of one (sweep, tile) -------------------------------------------------------------------------------------------------
 template <bool EXCL>
 __global__ void __launch_bounds__(RL_BLOCK)
@@ -118,22 +250,8 @@ qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
     const size_t k = blockIdx.y;
     unsigned long long *dst = EXCL ? m.excl + k * 9 + blockIdx.x : m.table + k * m.table_pitch + blockIdx.x;
     int tx, ty, bgx = 0, bgy = 0, bj = 0;
-    if (EXCL) {
-        const unsigned long long bk = m.best[k];
-        if (bk == 0) { if (tid == 0) *dst = 0; return; }           // (no candidate at all: nothing to exclude)
-        bgx = rl_key_gx(bk); bgy = rl_key_gy(bk); bj = rl_key_j(bk);
-        int tlx, tly, thx, thy;
-        rl_square_tiles(bgx, bgy, m.sep, tlx, tly, thx, thy);
-        tx = tlx + (int)(blockIdx.x % 3u); ty = tly + (int)(blockIdx.x / 3u);
-        if (tx > thx || ty > thy || tx < m.tx0 || tx >= m.tx0 + m.ntx || ty < m.ty0 || ty >= m.ty0 + m.nty) {
-            if (tid == 0) *dst = 0;
-            return;
-        }
-    } else {
-        if ((unsigned long long)blockIdx.x >= *m.count) return;    // (the grid is sized for every tile of the box)
-        const int ti = (int)m.list[blockIdx.x];
-        tx = m.tx0 + ti % m.ntx; ty = m.ty0 + ti / m.ntx;
-    }
+    const int go = rl_tile<EXCL>(m, k, blockIdx.x, tx, ty, bgx, bgy, bj);
+    if (go != 2) { if (go == 1 && tid == 0) *dst = 0; return; }
     if (wave == 0) sw_stage(a, k, s_rec, lane);
     __syncthreads();
     const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
@@ -151,15 +269,8 @@ qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
 
     // ---- the lane's candidates: row `row`, columns 4 cg .. 4 cg + 3 of the tile ------------------------------------------------------
     const int row = lane >> 2, cg = lane & 3;
-    const int gy = ty * RL_TILE + row, gxb = tx * RL_TILE + 4 * cg;
-    unsigned int mask = 0, sq = 0, low[4];
-    #pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const int gx = gxb + e;
-        low[e] = ((unsigned int)(65535 - gy) << 16) | (unsigned int)(65535 - gx);
-        if (gx >= m.bx0 && gx < m.bx1 && gy >= m.by0 && gy < m.by1 && rl_free(m.stamps[(size_t)gy * geo.size + gx])) mask |= 1u << e;
-        if (EXCL && abs(gx - bgx) <= m.sep && abs(gy - bgy) <= m.sep) sq |= 1u << e;
-    }
+    unsigned int mask, sq, low[4];
+    rl_lane_cells<EXCL>(m, geo.size, tx, ty, row, cg, bgx, bgy, mask, sq, low);
     const unsigned int lane_off = (unsigned int)(row * m.pitch + 4 * cg);
     unsigned short *o = (unsigned short *)B + wave * RL_OFFP;      // this wave's list (the dilation is done with B)
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -190,58 +301,118 @@ qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
         __syncthreads();                                           // (every wave runs every round: the list is written)
         if (live) {
             cnt = __builtin_amdgcn_readfirstlane(cnt);             // (the same in every lane: the loops below are scalar)
-            unsigned int lo = 0, hi = 0;
-            for (int b0 = 0; b0 < cnt; b0 += span) {
-                const int b1 = min(b0 + span, cnt);
-                unsigned int acc = 0;
-                int b = b0;
-                for (; b + 8 <= b1; b += 8) {                      // eight beams: one 16-byte read of offsets, sixteen dword reads in flight
-                    const uint4 q = *(const uint4 *)(o + b);
-                    acc += mt_look(A, lane_off + (q.x & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.x >> 16));
-                    acc += mt_look(A, lane_off + (q.y & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.y >> 16));
-                    acc += mt_look(A, lane_off + (q.z & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.z >> 16));
-                    acc += mt_look(A, lane_off + (q.w & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.w >> 16));
-                }
-                for (; b + 4 <= b1; b += 4) {
-                    const uint2 q = *(const uint2 *)(o + b);
-                    acc += mt_look(A, lane_off + (q.x & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.x >> 16));
-                    acc += mt_look(A, lane_off + (q.y & 0xffffu));
-                    acc += mt_look(A, lane_off + (q.y >> 16));
-                }
-                for (; b < b1; b++) acc += mt_look(A, lane_off + o[b]);
-                lo += acc & 0x00ff00ffu;
-                hi += (acc >> 8) & 0x00ff00ffu;
-            }
-            const unsigned int sc[4] = {lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16};
-            unsigned int use = mask;
-            if (EXCL) {
-                const int dj = abs(j - bj);
-                if (min(dj, m.n_rot - dj) <= m.sep_rot) use &= ~sq;                  // G6: too close to the best on every axis
-            }
-            #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const unsigned long long key = rl_key(sc[e], j, low[e]);
-                if (((use >> e) & 1u) && key > best) best = key;
-            }
+            unsigned int lo, hi;
+            rl_sum_list(A, o, cnt, span, lane_off, lo, hi);
+            rl_take<EXCL>(m, lo, hi, mask, sq, low, j, bj, best);
         }
         __syncthreads();                                           // (the list is read: the next round may overwrite it)
     }
-    #pragma unroll
-    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(best, d);
-        best = other > best ? other : best;
+    rl_store_best(best, s_key, dst, tid);
+}
+
+// ---- a group's points (J3, J4) ------------------------------------------------------------------------------------------------
+// one wave per group of the chunk: its records in turn, the hit points of those that count compacted behind one another
+__global__ void __launch_bounds__(QS_WAVE)
+qs_reloc_points_kernel(QsSweepArgs a, QsRelocArgs m, RlGroupArgs g)
+{
+    __shared__ unsigned int s_rec[SW_DW];
+    const int lane = threadIdx.x;
+    const size_t k = blockIdx.x;
+    double *px = g.pts + k * 2 * RL_GPTS, *py = px + RL_GPTS;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const double reach2 = g.travel * g.travel;
+    int H = 0, records = 0;                                        // (the same in every lane)
+    for (size_t r = g.start[k]; r < g.start[k + 1]; r++) {         // at most QS_RELOC_MAX_GROUP records: H <= RL_GPTS
+        __syncthreads();                                           // (the record before is read)
+        sw_stage(a, r, s_rec, lane);
+        __syncthreads();
+        const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + r * a.stride) & 3ull);
+        int agent;
+        const qs_reloc_rel rel = g.rel[r];
+        const bool counts = sw_accept(a, r, s_rec, mis, agent) && isfinite(rel.tx) && isfinite(rel.ty) && isfinite(rel.s) && isfinite(rel.c)
+                            && rel.tx * rel.tx + rel.ty * rel.ty <= reach2;
+        if (!counts) continue;                                     // (uniform)
+        records++;
+        bool hit[3];
+        double bx[3], by[3];
+        rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+        #pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const unsigned long long bal = __ballot(hit[q]);
+            if (hit[q]) {
+                const int i = H + __popcll(bal & lt);
+                px[i] = rel.tx + (rel.c * bx[q] - rel.s * by[q]);
+                py[i] = rel.ty + (rel.s * bx[q] + rel.c * by[q]);
+            }
+            H += __popcll(bal);
+        }
     }
-    if (lane == 0) s_key[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < RL_NW; w++) best = s_key[w] > best ? s_key[w] : best;
-        *dst = best;
+    if (lane == 0) { g.meta[2 * k] = (unsigned int)H; g.meta[2 * k + 1] = (unsigned int)records; }
+}
+
+// ---- scores of one (group, tile) ----------------------------------------------------------------------------------------------
+template <bool EXCL>
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_group_score_kernel(QsGeom geo, QsRelocArgs m, RlGroupArgs g)
+{
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    __shared__ unsigned long long s_key[RL_NW];
+    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
+    const size_t k = blockIdx.y;
+    unsigned long long *dst = EXCL ? m.excl + k * 9 + blockIdx.x : m.table + k * m.table_pitch + blockIdx.x;
+    int tx, ty, bgx = 0, bgy = 0, bj = 0;
+    const int go = rl_tile<EXCL>(m, k, blockIdx.x, tx, ty, bgx, bgy, bj);
+    if (go != 2) { if (go == 1 && tid == 0) *dst = 0; return; }
+    const int H = (int)g.meta[2 * k];
+    if (H == 0) { if (tid == 0) *dst = 0; return; }                // (uniform over the workgroup; no counting record: H = 0)
+    const double *px = g.pts + k * 2 * RL_GPTS, *py = px + RL_GPTS;
+
+    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.off_b);
+    const int apron = m.M + m.R;
+    mt_build_patch(A, B, m.stamps, geo.size, tx * RL_TILE - apron, ty * RL_TILE - apron, m.SA, m.pitch, m.R, tid, RL_BLOCK);
+
+    const int row = lane >> 2, cg = lane & 3;
+    unsigned int mask, sq, low[4];
+    rl_lane_cells<EXCL>(m, geo.size, tx, ty, row, cg, bgx, bgy, mask, sq, low);
+    const unsigned int lane_off = (unsigned int)(row * m.pitch + 4 * cg);
+    unsigned short *o = (unsigned short *)B + wave * RL_GOFFP;     // this wave's list: up to RL_GPTS offsets
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int span = (255 / (m.R + 1)) & ~7;
+    const double reach = (double)m.M;
+    unsigned long long best = 0;
+    const int rounds = (m.n_rot + RL_NW - 1) / RL_NW;
+    for (int r = 0; r < rounds; r++) {
+        const int j = r * RL_NW + wave;
+        const bool live = j < m.n_rot;                             // (uniform over the wave)
+        int cnt = 0;
+        if (live) {
+            const double s = m.rot[3 * j], c = m.rot[3 * j + 1];
+            for (int p0 = 0; p0 < H; p0 += QS_WAVE) {
+                const int i = p0 + lane;
+                bool in = false;
+                unsigned int off = 0;
+                if (i < H) {
+                    const double x = px[i], y = py[i];
+                    const double ex = c * x - s * y, ey = s * x + c * y;
+                    const double fx = floor(ex / geo.res + 0.5), fy = floor(ey / geo.res + 0.5);
+                    in = fx >= -reach && fx <= reach && fy >= -reach && fy <= reach;   // J5 (false for a NaN)
+                    if (in) off = (unsigned int)(((int)fy + apron) * m.pitch + ((int)fx + apron));
+                }
+                const unsigned long long bal = __ballot(in);
+                if (in) o[cnt + __popcll(bal & lt)] = (unsigned short)off;
+                cnt += __popcll(bal);
+            }
+        }
+        __syncthreads();                                           // (every wave runs every round: the list is written)
+        if (live) {
+            cnt = __builtin_amdgcn_readfirstlane(cnt);
+            unsigned int lo, hi;
+            rl_sum_list(A, o, cnt, span, lane_off, lo, hi);
+            rl_take<EXCL>(m, lo, hi, mask, sq, low, j, bj, best);
+        }
+        __syncthreads();                                           // (the list is read: the next round may overwrite it)
     }
+    rl_store_best(best, s_key, dst, tid);
 }
 
 // max of v over the workgroup, in every thread
@@ -274,26 +445,20 @@ qs_reloc_pick_kernel(QsRelocArgs m)
 }
 
 // ---- rival, gate, outputs ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RL_BLOCK)
-qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
+__device__ inline void rl_set_records(qs_sweep_reloc &r, int n) { r.accepted_record = (unsigned char)n; }
+__device__ inline void rl_set_records(qs_group_reloc &r, int n) { r.records = (unsigned char)n; }
+
+// sweep or group k with H hit points from `records` counting records: rival = max of the table entries of all tiles outside the
+// square round the best and of the re-scored ones; G7-G9.  Every thread of the workgroup calls it
+template <typename OUT>
+__device__ __forceinline__ void rl_finish(const QsGeom &geo, const QsRelocArgs &m, size_t k, int records, int H, OUT *out,
+                                          unsigned long long *s_key, int tid)
 {
-    __shared__ unsigned int s_rec[SW_DW];
-    __shared__ unsigned long long s_key[RL_NW];
-    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
-    const size_t k = blockIdx.x;
-    if (wave == 0) sw_stage(a, k, s_rec, lane);
-    __syncthreads();
-    const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
-    int agent;
-    bool hit[3];
-    double bx[3], by[3];
-    const bool ok = sw_accept(a, k, s_rec, mis, agent);
-    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
-    qs_sweep_reloc r;
+    OUT r;
     memset(&r, 0, sizeof r);
-    if (!ok) {                                                     // (uniform over the workgroup)
+    if (records == 0) {                                            // (uniform over the workgroup)
         r.status = QS_RELOC_NO_RECORD;
-        if (tid == 0) m.out[k] = r;
+        if (tid == 0) *out = r;
         return;
     }
     const unsigned long long bk = m.best[k];
@@ -312,12 +477,12 @@ qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
     }
     rival = rl_block_max(rival, s_key, tid);
     if (tid != 0) return;
-    r.accepted_record = 1;
+    rl_set_records(r, records);
     r.hits = H;
     r.gx = r.gy = r.j = r.gx2 = r.gy2 = r.j2 = -1;
     if (bk == 0) {                                                 // no FREE cell in the box, or H = 0
         r.status = QS_RELOC_NO_CANDIDATE;
-        m.out[k] = r;
+        *out = r;
         return;
     }
     r.status = QS_RELOC_OK;
@@ -329,13 +494,40 @@ qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
     r.x = geo.ox + ((double)r.gx + 0.5) * geo.res;
     r.y = geo.oy + ((double)r.gy + 0.5) * geo.res;
     r.yaw = m.rot[3 * r.j + 2];
-    m.out[k] = r;
+    *out = r;
+}
+
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
+{
+    __shared__ unsigned int s_rec[SW_DW];
+    __shared__ unsigned long long s_key[RL_NW];
+    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
+    const size_t k = blockIdx.x;
+    if (wave == 0) sw_stage(a, k, s_rec, lane);
+    __syncthreads();
+    const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
+    int agent;
+    bool hit[3];
+    double bx[3], by[3];
+    const bool ok = sw_accept(a, k, s_rec, mis, agent);
+    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    rl_finish(geo, m, k, ok ? 1 : 0, H, m.out + k, s_key, tid);
+}
+
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_group_final_kernel(QsGeom geo, QsRelocArgs m, RlGroupArgs g)
+{
+    __shared__ unsigned long long s_key[RL_NW];
+    const size_t k = blockIdx.x;
+    rl_finish(geo, m, k, (int)g.meta[2 * k + 1], (int)g.meta[2 * k], g.out + k, s_key, threadIdx.x);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 struct QsRelocSetup { qs_reloc_params p; int M; };
 
-static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who, QsRelocSetup &rs)
+// travel: the group form's (J8); 0 for a single sweep, whose limit and text are G's
+static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who, QsRelocSetup &rs, double travel = 0.0, bool group = false)
 {
     qs_reloc_params p = {2, 180, 4, 2, 40, 70, 5, 0, 0, 0, 0, 0};
     if (params) p = *params;
@@ -348,9 +540,12 @@ static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who
     else if (p.min_hits < 0) bad = "min_hits must not be negative";
     else if (p.min_percent < 0 || p.min_percent > 100) bad = "min_percent must lie in [0, 100]";
     else if (p.min_margin < 0 || p.min_margin > 100) bad = "min_margin must lie in [0, 100]";
-    const double reach = ceil(c->sweep_max / c->cfg.res);
-    if (!bad && !(RL_TILE + 2 * (reach + p.radius + 1) <= 255))
-        bad = "the sweep filter's smax is too large for this resolution: 16 + 2 * (ceil(smax / res) + radius + 1) exceeds 255";
+    else if (!(travel >= 0.0) || !std::isfinite(travel)) bad = "travel must be finite and not negative";
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
+    const double reach = ceil((c->sweep_max + travel) / c->cfg.res);          // (travel 0: smax + 0 is smax)
+    if (!(RL_TILE + 2 * (reach + p.radius + 1) <= 255))
+        bad = group ? "smax + travel is too large for this resolution: 16 + 2 * (ceil((smax + travel) / res) + radius + 1) exceeds 255"
+                    : "the sweep filter's smax is too large for this resolution: 16 + 2 * (ceil(smax / res) + radius + 1) exceeds 255";
     if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
     if (!p.use_box) { p.x0 = 0; p.y0 = 0; p.x1 = c->cfg.size; p.y1 = c->cfg.size; }
     rs.p = p;
@@ -369,9 +564,26 @@ static int reloc_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
     return QS_OK;
 }
 
-// the workspace of one call over n_tiles box tiles, carved from ws (nullptr: only the bytes the block needs)
-struct QsRelocLayout { unsigned int *chunk, *list; unsigned long long *count, *table, *best, *excl; size_t bytes; };
-static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles)
+// J1
+static int reloc_groups_ok(qs_ctx *c, size_t n, const int32_t *gsize, size_t n_groups, const char *who)
+{
+    char msg[256];
+    size_t sum = 0;
+    for (size_t g = 0; g < n_groups; g++) {
+        if (gsize[g] < 1 || gsize[g] > QS_RELOC_MAX_GROUP) {
+            snprintf(msg, sizeof msg, "%s: gsize[%zu] must lie in [1, QS_RELOC_MAX_GROUP]", who, g);
+            return qs_fail(c, QS_E_INVAL, msg);
+        }
+        sum += (size_t)gsize[g];
+    }
+    if (sum != n) { snprintf(msg, sizeof msg, "%s: the group sizes must sum to n", who); return qs_fail(c, QS_E_INVAL, msg); }
+    return QS_OK;
+}
+
+// the workspace of one call over n_tiles box tiles, carved from ws (nullptr: only the bytes the block needs); groups: with the
+// point lists of a chunk of groups
+struct QsRelocLayout { unsigned int *chunk, *list; unsigned long long *count, *table, *best, *excl; double *pts; unsigned int *meta; size_t bytes; };
+static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles, bool groups)
 {
     Carve cv(ws);
     QsRelocLayout L;
@@ -381,16 +593,17 @@ static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles)
     L.table = cv.take<unsigned long long>((size_t)RL_CHUNK * (n_tiles + 1));
     L.best = cv.take<unsigned long long>(RL_CHUNK);
     L.excl = cv.take<unsigned long long>((size_t)RL_CHUNK * 9);
+    L.pts = groups ? cv.take<double>((size_t)RL_CHUNK * 2 * RL_GPTS) : nullptr;
+    L.meta = groups ? cv.take<unsigned int>((size_t)RL_CHUNK * 2) : nullptr;
     L.bytes = cv.bytes;
     return L;
 }
 
-// n device-resident records against the map as the stream finds it, into d_out; everything enqueued, nothing waited for
-// (but a workspace that has to grow waits for the stream first)
-static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned char *d_pkts, size_t n, size_t stride,
-                               const unsigned short *d_lens, qs_sweep_reloc *d_out)
+// what every launch of a call shares: the tables, the box and its tiles, the patch and the LDS it takes (offp: 16-bit offsets a
+// wave lists), the workspace, the census.  Everything enqueued (but a workspace that has to grow waits for the stream first)
+struct QsRelocPlan { QsRelocArgs m; QsRelocLayout L; size_t n_tiles, lds; };
+static hipError_t reloc_prepare(qs_ctx *c, const QsRelocSetup &rs, size_t offp, bool groups, QsRelocPlan &pl)
 {
-    if (n == 0) return hipSuccess;
     const qs_reloc_params &p = rs.p;
     static const double kRad = 3.141592653589793 / 180.0, kTwoPi = 2.0 * 3.141592653589793;
     if (!c->match_tab.p) {                                         // the beam angles' cos / sin: libm's, once per context (as match.hip)
@@ -416,7 +629,7 @@ static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned
         c->reloc_nrot = p.n_rot;
     }
     const int size = c->cfg.size;
-    QsRelocArgs m;
+    QsRelocArgs &m = pl.m;
     m.R = p.radius; m.n_rot = p.n_rot; m.sep = p.sep; m.sep_rot = p.sep_rot;
     m.min_hits = p.min_hits; m.min_percent = p.min_percent; m.min_margin = p.min_margin;
     m.bx0 = std::max(p.x0, 0); m.by0 = std::max(p.y0, 0); m.bx1 = std::min(p.x1, size); m.by1 = std::min(p.y1, size);
@@ -425,20 +638,21 @@ static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned
     m.tx0 = m.bx0 / RL_TILE; m.ty0 = m.by0 / RL_TILE;
     m.ntx = empty ? 0 : (m.bx1 - 1) / RL_TILE - m.tx0 + 1;
     m.nty = empty ? 0 : (m.by1 - 1) / RL_TILE - m.ty0 + 1;
-    const size_t n_tiles = (size_t)m.ntx * m.nty;
+    const size_t n_tiles = pl.n_tiles = (size_t)m.ntx * m.nty;
     m.M = rs.M;
     m.SA = RL_TILE + 2 * (m.M + m.R);                              // <= 255 (reloc_setup)
     // rows of 4 x (an odd number) dwords: the 8 rows x 4 dwords a lane group of the scoring pass reads fall on 32 different banks
     m.pitch = (m.SA + 15) & ~15;
     if (!((m.pitch >> 4) & 1)) m.pitch += 16;
     const size_t a_bytes = ((size_t)m.SA * m.pitch + 16 + 15) & ~(size_t)15;
-    const size_t b_bytes = std::max((size_t)m.SA * m.pitch, (size_t)RL_NW * RL_OFFP * sizeof(unsigned short));
+    const size_t b_bytes = std::max((size_t)m.SA * m.pitch, (size_t)RL_NW * offp * sizeof(unsigned short));
     m.off_b = (unsigned int)a_bytes;
-    const size_t lds = a_bytes + ((b_bytes + 15) & ~(size_t)15);
+    pl.lds = a_bytes + ((b_bytes + 15) & ~(size_t)15);
     m.tab = c->match_tab.p; m.rot = c->reloc_rot.p; m.stamps = c->d_stamps.p;
+    m.out = nullptr;
 
-    HIPRET(c->reloc_ws.reserve(qs_reloc_layout(nullptr, n_tiles).bytes, c->stream, (size_t)1 << 16));
-    const QsRelocLayout L = qs_reloc_layout(c->reloc_ws.p, n_tiles);
+    HIPRET(c->reloc_ws.reserve(qs_reloc_layout(nullptr, n_tiles, groups).bytes, c->stream, (size_t)1 << 16));
+    const QsRelocLayout L = pl.L = qs_reloc_layout(c->reloc_ws.p, n_tiles, groups);
     m.list = L.list; m.count = L.count; m.table = L.table; m.table_pitch = n_tiles + 1; m.best = L.best; m.excl = L.excl;
     if (n_tiles == 0) HIPRET(hipMemsetAsync(L.count, 0, sizeof(unsigned long long), c->stream));
     else {
@@ -447,6 +661,19 @@ static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned
         HIPRET(qs_compact(c->stream, pred, n_tiles, false, emit, n_tiles, L.chunk, L.count));
         HIPRET(qs_compact(c->stream, pred, n_tiles, true, emit, n_tiles, L.chunk, L.count));
     }
+    return hipSuccess;
+}
+
+// n device-resident records against the map as the stream finds it, into d_out; everything enqueued, nothing waited for
+// (but a workspace that has to grow waits for the stream first)
+static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned char *d_pkts, size_t n, size_t stride,
+                               const unsigned short *d_lens, qs_sweep_reloc *d_out)
+{
+    if (n == 0) return hipSuccess;
+    QsRelocPlan pl;
+    HIPRET(reloc_prepare(c, rs, RL_OFFP, false, pl));
+    QsRelocArgs &m = pl.m;
+    const size_t n_tiles = pl.n_tiles, lds = pl.lds;
     if (lds > 32 * 1024) {                                         // long reaches: up to 2 x 65 KiB of the CU's 160
         HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -466,6 +693,48 @@ static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned
         HIPRET(hipGetLastError());
         hipLaunchKernelGGL(qs_reloc_final_kernel, dim3(nk), dim3(RL_BLOCK), 0, c->stream, a, c->geom, m);
         HIPRET(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+// the same for n_groups groups (gsize: host, already checked against J1) of device-resident records
+static hipError_t reloc_group_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned char *d_pkts, size_t stride, const unsigned short *d_lens,
+                                     const qs_reloc_rel *d_rel, const int32_t *gsize, size_t n_groups, double travel, qs_group_reloc *d_out)
+{
+    if (n_groups == 0) return hipSuccess;
+    QsRelocPlan pl;
+    HIPRET(reloc_prepare(c, rs, RL_GOFFP, true, pl));
+    const QsRelocArgs &m = pl.m;
+    const size_t n_tiles = pl.n_tiles, lds = pl.lds;
+    if (lds > 32 * 1024) {                                         // up to 2 x 69 KiB of the CU's 160
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_group_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_group_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    size_t rec0 = 0;
+    for (size_t g0 = 0; g0 < n_groups; g0 += RL_CHUNK) {
+        const unsigned int ng = (unsigned int)std::min((size_t)RL_CHUNK, n_groups - g0);
+        RlGroupArgs g;
+        g.rel = d_rel + rec0; g.travel = travel; g.pts = pl.L.pts; g.meta = pl.L.meta; g.out = d_out + g0;
+        unsigned int nr = 0;
+        for (unsigned int i = 0; i <= RL_CHUNK; i++) {
+            g.start[i] = nr;
+            if (i < ng) nr += (unsigned int)gsize[g0 + i];
+        }
+        QsSweepArgs a;
+        qs_sweep_args(c, d_pkts + rec0 * stride, nr, stride, d_lens ? d_lens + rec0 : nullptr, QS_SWEEP_NO_GRAPH, a);
+        hipLaunchKernelGGL(qs_reloc_points_kernel, dim3(ng), dim3(QS_WAVE), 0, c->stream, a, m, g);
+        HIPRET(hipGetLastError());
+        if (n_tiles) {
+            hipLaunchKernelGGL(qs_reloc_group_score_kernel<false>, dim3((unsigned int)n_tiles, ng), dim3(RL_BLOCK), lds, c->stream, c->geom, m, g);
+            HIPRET(hipGetLastError());
+        }
+        hipLaunchKernelGGL(qs_reloc_pick_kernel, dim3(ng), dim3(RL_BLOCK), 0, c->stream, m);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_group_score_kernel<true>, dim3(9, ng), dim3(RL_BLOCK), lds, c->stream, c->geom, m, g);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_group_final_kernel, dim3(ng), dim3(RL_BLOCK), 0, c->stream, c->geom, m, g);
+        HIPRET(hipGetLastError());
+        rec0 += nr;
     }
     return hipSuccess;
 }
@@ -512,6 +781,71 @@ extern "C" int qs_relocalise_sweeps(qs_ctx *c, const qs_reloc_params *params, co
         HIPCHK(c, reloc_launch(c, rs, s.pkts, nk, stride, lens ? s.lens : nullptr, d_out));
         HIPCHK(c, hipMemcpyAsync(out + k0, d_out, nk * sizeof(qs_sweep_reloc), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return QS_OK;
+}
+
+// ---- C ABI: relocalisation of a group -------------------------------------------------------------------------------------------
+static int reloc_groups_check(qs_ctx *c, const qs_reloc_params *params, size_t n, size_t stride, const int32_t *gsize, size_t n_groups,
+                              double travel, QsRelocSetup &rs)
+{
+    int rc = reloc_setup(c, params, "qs_relocalise_groups", rs, travel, true);
+    if (rc != QS_OK) return rc;
+    rc = reloc_call_ok(c, n, stride, "qs_relocalise_groups");
+    if (rc != QS_OK) return rc;
+    return reloc_groups_ok(c, n, gsize, n_groups, "qs_relocalise_groups");
+}
+
+extern "C" int qs_relocalise_groups_device(qs_ctx *c, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                           const uint16_t *d_lens, const qs_reloc_rel *d_rel, const int32_t *gsize, size_t n_groups,
+                                           double travel, qs_group_reloc *d_out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || (d_pkts != nullptr && d_rel != nullptr));
+    ARGCHK(c, n_groups == 0 || (gsize != nullptr && d_out != nullptr));
+    QsRelocSetup rs;
+    const int rc = reloc_groups_check(c, params, n, stride, gsize, n_groups, travel, rs);
+    if (rc != QS_OK || n_groups == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, reloc_group_launch(c, rs, d_pkts, stride, d_lens, d_rel, gsize, n_groups, travel, d_out));
+    return QS_OK;
+}
+
+extern "C" int qs_relocalise_groups(qs_ctx *c, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                                    const uint16_t *lens, const qs_reloc_rel *rel, const int32_t *gsize, size_t n_groups, double travel,
+                                    qs_group_reloc *out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || (pkts != nullptr && rel != nullptr));
+    ARGCHK(c, n_groups == 0 || (gsize != nullptr && out != nullptr));
+    QsRelocSetup rs;
+    int rc = reloc_groups_check(c, params, n, stride, gsize, n_groups, travel, rs);
+    if (rc != QS_OK || n_groups == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    const size_t chunk = (size_t)1 << 12;                          // records staged per round trip: whole groups, one at least
+    size_t k0 = 0;
+    for (size_t g0 = 0; g0 < n_groups;) {
+        size_t g1 = g0, nk = 0;
+        while (g1 < n_groups && (g1 == g0 || nk + (size_t)gsize[g1] <= chunk)) nk += (size_t)gsize[g1++];
+        const size_t ng = g1 - g0;
+        Staging s;
+        rc = reserve_staging(c, nk * stride, s);
+        if (rc != QS_OK) return rc;
+        Carve cv(nullptr);
+        cv.take<qs_group_reloc>(ng); cv.take<qs_reloc_rel>(nk);
+        HIPCHK(c, c->io_ws.reserve(cv.bytes, c->stream, QS_IO_WS_FLOOR));
+        Carve io(c->io_ws.p);
+        qs_group_reloc *d_out = io.take<qs_group_reloc>(ng);
+        qs_reloc_rel *d_rel = io.take<qs_reloc_rel>(nk);
+        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, nk * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, nk * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_rel, rel + k0, nk * sizeof(qs_reloc_rel), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, reloc_group_launch(c, rs, s.pkts, stride, lens ? s.lens : nullptr, d_rel, gsize + g0, ng, travel, d_out));
+        HIPCHK(c, hipMemcpyAsync(out + g0, d_out, ng * sizeof(qs_group_reloc), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        g0 = g1; k0 += nk;
     }
     return QS_OK;
 }

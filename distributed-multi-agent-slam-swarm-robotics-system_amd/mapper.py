@@ -499,6 +499,45 @@ class QuasarMapper:
                                                       C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_out)),
                   "qs_relocalise_sweeps_device")
 
+    def relocalise_groups(self, datagrams, gsize, lengths=None, rel=None, travel=P.RELOC_TRAVEL, params=None):
+        """Locate groups of sweeps against the whole map, the sweeps of a group scored jointly (include/quasar_slam.h,
+        "relocalisation of a group"): records [sum(gsize)] in runs of gsize[g], a structured array of protocol.GROUP_RELOC_DTYPE,
+        one entry per group -- the pose of the group's frame.  rel (protocol.RELOC_REL_DTYPE, one per record): each record's pose
+        in its group's frame; None: from the packets' poses, the first record of each group the frame (protocol.reloc_rel).
+        Reads the map, changes nothing."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        if rel is None:
+            if (gs < 0).any() or int(gs.sum()) != n:
+                raise ValueError("the group sizes must sum to the number of records")
+            pose = buf[:, 5:17].copy().view("<f4") if n else np.zeros((0, 3), np.float32)
+            ends = np.cumsum(gs)
+            rel = np.concatenate([P.reloc_rel(*pose[e - g:e].T) for g, e in zip(gs.tolist(), ends.tolist())]
+                                 + [np.zeros(0, dtype=P.RELOC_REL_DTYPE)])
+        rel = np.ascontiguousarray(rel, dtype=P.RELOC_REL_DTYPE).reshape(-1)
+        if len(rel) != n:
+            raise ValueError("rel must have one entry per record")
+        prm = self.relocalise_params(params)
+        out = np.zeros(len(gs), dtype=P.GROUP_RELOC_DTYPE)
+        self._chk(self._L.qs_relocalise_groups(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                               _ptr(rel) if n else None, _ptr(gs) if len(gs) else None, len(gs), float(travel),
+                                               _ptr(out) if len(gs) else None), "qs_relocalise_groups")
+        return out
+
+    def relocalise_groups_device(self, d_pkts, n, stride, d_rel, gsize, d_out, d_lens=0, travel=P.RELOC_TRAVEL, params=None):
+        """Device-resident form (raw device addresses as ints; d_rel: n records of protocol.RELOC_REL_DTYPE, d_out: len(gsize)
+        records of protocol.GROUP_RELOC_DTYPE; gsize a host array); asynchronous."""
+        prm = self.relocalise_params(params)
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        self._chk(self._L.qs_relocalise_groups_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                      C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_rel),
+                                                      _ptr(gs) if len(gs) else None, len(gs), float(travel), C.c_void_p(d_out)),
+                  "qs_relocalise_groups_device")
+
     def last_sweeps(self):
         """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after
         offset and drift, yaw); NaN for rejected records."""

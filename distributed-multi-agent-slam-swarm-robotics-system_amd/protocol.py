@@ -154,6 +154,30 @@ RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("score", "<
                         ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
                         ("accepted_record", "u1"), ("accepted", "u1"), ("pad", "u1", (6,)),
                         ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8")])
+# relocalisation of a group (include/quasar_slam.h, J1-J8)
+RELOC_MAX_GROUP = 16
+RELOC_TRAVEL = 2.0           # metres a record of a group may lie from the group's frame
+RELOC_REL_DTYPE = np.dtype([("tx", "<f8"), ("ty", "<f8"), ("s", "<f8"), ("c", "<f8")])
+GROUP_RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("score", "<i4"), ("hits", "<i4"),
+                              ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
+                              ("records", "u1"), ("accepted", "u1"), ("pad", "u1", (6,)),
+                              ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8")])
+
+
+def reloc_rel(x, y, yaw, anchor=0):
+    """The relative poses (J2) of the records of ONE group from their poses x, y, yaw (the packets' f32 fields, or anything
+    array-like), RELOC_REL_DTYPE [n]: the group's frame is the pose of record `anchor`.  Formed in fp64 with libm: (dx, dy)
+    from the anchor, turned into the anchor's heading, then the sin / cos of yaw - yaw0."""
+    x, y, yaw = (np.asarray(v, dtype=np.float32).astype(np.float64).reshape(-1) for v in (x, y, yaw))
+    out = np.zeros(len(x), dtype=RELOC_REL_DTYPE)
+    if len(x) == 0:
+        return out
+    c0, s0 = math.cos(float(yaw[anchor])), math.sin(float(yaw[anchor]))
+    for k in range(len(x)):
+        dx, dy = float(x[k]) - float(x[anchor]), float(y[k]) - float(y[anchor])
+        d = float(yaw[k]) - float(yaw[anchor])
+        out[k] = (c0 * dx + s0 * dy, c0 * dy - s0 * dx, math.sin(d), math.cos(d))
+    return out
 
 
 # ---- map view (include/quasar_slam.h, "map view"): the renderer's constants, dual_bot_mapper.py:346-377, :383-397 ----------

@@ -46,6 +46,12 @@ from the pose the ingest would have formed (the packet's pose plus QuasarMapper.
 rewrites the f32 x / y / yaw fields of that bot's sweep records from then on, the triggering one included, in its own buffer
 before they are ingested.  relocalised[bot] holds the latest accepted result, reloc_stats counts tried / accepted / rewritten.
 A relocalisation the gate does not accept changes nothing.
+With relocalise={"group": K, "travel": m, ...} (K in 2..RELOC_MAX_GROUP; travel defaults to RELOC_TRAVEL) a bot that comes online
+without a transform is located from several sweeps scored jointly (QuasarMapper.relocalise_groups): copies of its accepted sweeps
+are kept, up to K, those whose pose lies within `travel` of the first kept one; after each run that adds one the kept records are
+relocalised as one group whose frame is the first kept record.  On acceptance the transform is set from that record's ingest
+pose, as above, and the copies are dropped; after K records without acceptance the front-end gives up on that bot until it is
+next found offline.  Sweeps are ingested meanwhile as they arrive.  reloc_stats then also counts group_tried / gave_up.
 With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
 point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
 poses; mapper.MapView.frame draws them.
@@ -88,8 +94,19 @@ class MissionControl:
         if self.sweep_graph:
             mapper.set_sweep_graph(True, **(dict(sweep_graph) if isinstance(sweep_graph, dict) else {}))
         self.reloc_params = dict(relocalise) if isinstance(relocalise, dict) else True
+        self.reloc_group = self.reloc_travel = None
+        if isinstance(relocalise, dict) and "group" in relocalise:
+            self.reloc_group = int(self.reloc_params.pop("group"))
+            self.reloc_travel = float(self.reloc_params.pop("travel", P.RELOC_TRAVEL))
+            if not 2 <= self.reloc_group <= P.RELOC_MAX_GROUP:
+                raise ValueError("MissionControl: relocalise['group'] must lie in [2, RELOC_MAX_GROUP]")
+        elif isinstance(relocalise, dict) and "travel" in relocalise:
+            raise ValueError("MissionControl: relocalise['travel'] needs 'group'")
+        self._reloc_kept = {}                        # bot -> copies of its kept sweeps (group mode, while it is being located)
         self.relocalised = {}                        # bot -> the accepted result (a record of protocol.RELOC_DTYPE) in force
         self.reloc_stats = {"tried": 0, "accepted": 0, "rewritten": 0}
+        if self.reloc_group:
+            self.reloc_stats.update(group_tried=0, gave_up=0)
         self._reloc_T = {}                           # bot -> (cos, sin, dyaw, ingest x, y, found x, y, shift x, y)
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
@@ -204,12 +221,17 @@ class MissionControl:
             if not self.online[a] and a not in first:
                 first[a] = int(j)
         shift_of = getattr(self.mapper, "sweep_pose_shift", None)
-        for a, j in first.items():
-            r = self.mapper.relocalise_sweeps(run[j:j + 1], lens[j:j + 1], params=self.reloc_params)[0]
-            self.reloc_stats["tried"] += 1
-            if not r["accepted"]:
-                continue
-            x, y, yaw = (float(v) for v in run[j, 5:17].view("<f4"))
+        located = []                                 # (bot, the record whose ingest pose the transform starts from, the result)
+        if self.reloc_group:
+            located = self._relocalise_groups(run, idx, first)
+        else:
+            for a, j in first.items():
+                r = self.mapper.relocalise_sweeps(run[j:j + 1], lens[j:j + 1], params=self.reloc_params)[0]
+                self.reloc_stats["tried"] += 1
+                if r["accepted"]:
+                    located.append((a, run[j], r))
+        for a, rec, r in located:
+            x, y, yaw = (float(v) for v in rec[5:17].view("<f4"))
             sx, sy = (float(v) for v in shift_of(a)) if shift_of else (0.0, 0.0)
             dyaw = float(r["yaw"]) - yaw
             self._reloc_T[a] = (np.cos(dyaw), np.sin(dyaw), dyaw, x + sx, y + sy, float(r["x"]), float(r["y"]), sx, sy)
@@ -224,6 +246,42 @@ class MissionControl:
             qx, qy = float(f[0]) + sx - ix, float(f[1]) + sy - iy
             f[:] = (fx + (c * qx - s * qy) - sx, fy + (s * qx + c * qy) - sy, float(f[2]) + dyaw)
             self.reloc_stats["rewritten"] += 1
+
+    def _relocalise_groups(self, run, idx, first):
+        """Group mode: keep this run's sweeps of the bots that are being located and relocalise each bot that got one more.
+        first: the bots this run finds offline (they start anew unless they have a transform or are already being located)."""
+        for a in first:
+            if a not in self._reloc_T and a not in self._reloc_kept:
+                self._reloc_kept[a] = []
+        grew = set()
+        for j in idx:
+            a = int(run[j, 4])
+            kept = self._reloc_kept.get(a)
+            if kept is None or len(kept) >= self.reloc_group:
+                continue
+            if kept:
+                if len(kept[0]) != run.shape[1]:
+                    continue                          # (the other sweep format: one stride per call)
+                x0, y0 = (float(v) for v in kept[0][5:13].view("<f4"))
+                x, y = (float(v) for v in run[j, 5:13].view("<f4"))
+                if not (x - x0) * (x - x0) + (y - y0) * (y - y0) <= self.reloc_travel * self.reloc_travel:
+                    continue
+            kept.append(run[j].copy())
+            grew.add(a)
+        located = []
+        for a in sorted(grew):
+            kept = self._reloc_kept[a]
+            recs = np.stack(kept)
+            r = self.mapper.relocalise_groups(recs, [len(kept)], np.full(len(kept), recs.shape[1], dtype=np.uint16),
+                                              travel=self.reloc_travel, params=self.reloc_params)[0]
+            self.reloc_stats["group_tried"] += 1
+            if r["accepted"]:
+                located.append((a, kept[0], r))
+                del self._reloc_kept[a]
+            elif len(kept) >= self.reloc_group:
+                self.reloc_stats["gave_up"] += 1
+                del self._reloc_kept[a]
+        return located
 
     def _mark(self, i0, accepted, pose, now, keep_pose):
         """Bookkeeping of the accepted records of one ingest whose first datagram is slot i0 (:846-848, :860-864)."""

@@ -317,6 +317,50 @@ int qs_relocalise_sweeps(qs_ctx *ctx, const qs_reloc_params *params, const uint8
 int qs_relocalise_sweeps_device(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
                                 const uint16_t *d_lens, qs_sweep_reloc *d_out);
 
+/* ---- relocalisation of a group (no reference counterpart: this build's own rule) ------------------------------------------
+ * One sweep is often ambiguous: a straight wall, a symmetric corner or an open floor has many equally good poses.  Several
+ * sweeps of one bot, each with its pose in the bot's own (odometric) frame, form one rigid constellation of hit points; it is
+ * located by the rule above, scored jointly.  The device and the CPU restatement (tests/reloc_group_rules.py) agree bit for bit.
+ *  J1. Groups: the n records of a call are split into n_groups runs of consecutive records; gsize[g] lies in
+ *      1..QS_RELOC_MAX_GROUP and the sizes sum to n.  QS_E_INVAL otherwise.
+ *  J2. Relative poses: one qs_reloc_rel per record, the position (tx, ty) of that record's robot in the group's frame and the
+ *      sin / cos (s, c) of its heading relative to that frame.  They are inputs: no device trigonometry, as in G2.  The
+ *      packets' pose, the bot's offset and its drift are not read.
+ *  J3. A record counts when G3's acceptance rule accepts it, its four rel values are finite and
+ *      tx * tx + ty * ty <= travel * travel (uncontracted).  `records` is the number of counting records of the group.
+ *  J4. Hit beams and bx, by as in G3.  Points in the group's frame: px = tx + (c * bx - s * by), py = ty + (s * bx + c * by),
+ *      in this association.  H = the number of hit points over all counting records of the group.
+ *  J5. Under rotation j: ex = C_j * px - S_j * py, ey = S_j * px + C_j * py; ax = floor(ex / res + 0.5), ay likewise.  With
+ *      M = ceil((smax + travel) / res) + 1, a point whose |ax| or |ay| exceeds M, or is not a number, scores 0 under that
+ *      rotation (an honest (s, c), s * s + c * c = 1, never gets there).  score = sum over the H points of L[gy + ay][gx + ax].
+ *  J6. Candidates, order, rival and gate: G4-G8 unchanged, with this H; qs_reloc_params is the same.  The reported pose is
+ *      the pose of the group's frame.
+ *  J7. Status: QS_RELOC_NO_RECORD when records = 0 (all other fields zero); QS_RELOC_NO_CANDIDATE when H = 0 or the box
+ *      holds no FREE cell; QS_RELOC_OK otherwise.  Field conventions as in G9.
+ *  J8. Limits: those of the rule above with 16 + 2 * (ceil((smax + travel) / res) + radius + 1) <= 255; travel finite and
+ *      >= 0.  QS_E_INVAL beyond them; the text names the quantity.
+ * A group of one record with rel = (0, 0, 0, 1) and travel 0 gives the bytes of qs_relocalise_sweeps for that record
+ * (1 * bx - 0 * by and 0 + bx are exact).
+ * gsize is read by the HOST in both forms: it shapes the launches and J1 is refused before anything is enqueued.  Stride,
+ * lengths and refusals as qs_relocalise_sweeps.  The calls read the map and write nothing to the context. */
+#define QS_RELOC_MAX_GROUP 16   /* 16 records of 181 beams score at most 2896 * 8 = 23 168 with radius 7 (csrc/reloc.hip: RL_GPTS) */
+typedef struct qs_reloc_rel { double tx, ty, s, c; } qs_reloc_rel;
+typedef struct qs_group_reloc {
+    int32_t gx, gy, j, score, hits;
+    int32_t gx2, gy2, j2, score2;
+    int32_t status;
+    uint8_t records, accepted, pad[6];      /* pad is zero */
+    double x, y, yaw;
+} qs_group_reloc;
+int qs_relocalise_groups(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                         const uint16_t *lens, const qs_reloc_rel *rel, const int32_t *gsize, size_t n_groups, double travel,
+                         qs_group_reloc *out);
+/* same with device-resident pkts / lens / rel / out (gsize stays a host array, see above); asynchronous on the context's
+ * stream, with the exceptions of qs_relocalise_sweeps_device */
+int qs_relocalise_groups_device(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                const uint16_t *d_lens, const qs_reloc_rel *d_rel, const int32_t *gsize, size_t n_groups,
+                                double travel, qs_group_reloc *d_out);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

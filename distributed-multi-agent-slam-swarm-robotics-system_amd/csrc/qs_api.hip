@@ -378,6 +378,29 @@ extern "C" int qs_chain_plan(qs_ctx *c)
     return qs_chain_lean(c);                     // (a plan was built: walked by every graph that ran the lean owner)
 }
 
+// diagnostic: bot's part of the plan the last launch built (the batch arrays keep it until the next ingest writes them again)
+extern "C" int qs_chain_plan_read(qs_ctx *c, int32_t bot, int32_t *node, uint32_t *r, uint32_t *skip, size_t cap, size_t *n_own,
+                                  uint32_t *first)
+{
+    ARGCHK(c, c != nullptr && n_own && first);
+    ARGCHK(c, (node && r && skip) || (!node && !r && !skip));
+    if (bot < 1 || bot > c->cfg.max_agent) return qs_fail(c, QS_E_RANGE, "qs_chain_plan_read: bot out of range");
+    if (!c->chain_last_plan) return qs_fail(c, QS_E_STATE, "qs_chain_plan_read: the last ingest had no plan");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned int range[2] = {0, 0}, f = 0;
+    HIPCHK(c, hipMemcpyAsync(range, c->sb.agent_ev + bot, sizeof range, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&f, c->sb.pl_first + bot, sizeof f, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = range[1] - range[0];
+    *n_own = n; *first = f;
+    if (!node) return QS_OK;
+    if (n > cap) return qs_fail(c, QS_E_RANGE, "qs_chain_plan_read: capacity too small");
+    std::vector<QsPlanRec> rec(n);
+    if (n) HIPCHK(c, hipMemcpy(rec.data(), c->sb.pl_rec + range[0], n * sizeof(QsPlanRec), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { node[i] = rec[i].node; r[i] = rec[i].r; skip[i] = rec[i].skip; }
+    return QS_OK;
+}
+
 extern "C" int qs_set_chain_lookahead(qs_ctx *c, int32_t on)
 {
     ARGCHK(c, c != nullptr);

@@ -94,6 +94,7 @@ __global__ void qs_slam_prefix_kernel(QsSlamBatch sb, int n_graphs, int max_agen
     }
     for (int t = threadIdx.x; t <= max_agent; t += blockDim.x) {
         sb.acl_cnt[t] = 0;
+        sb.pl_first[t] = 0;              // (counted up by qs_slam_plan_count_kernel where the launch has a plan)
         sb.drift_start[2 * t] = drift[2 * t];
         sb.drift_start[2 * t + 1] = drift[2 * t + 1];
     }
@@ -152,10 +153,11 @@ qs_slam_index_kernel(size_t n, QsBatch b, QsSlamBatch sb, const QsGraphDev *__re
 // ---- the plan: every bot's own events in list order, and where each leads after a closure ------------------------------
 // For the lean owner of qs_slam_chain_free_kernel (slam_chain_plan_owner.inc).  Which event an agent queries next is a pure
 // function of the event list but for one bit per decision: after a closure at own event j, the agent's first own event k > j
-// with node[k] - node[j] >= MIN_POSES_BETWEEN (:304; skip[j], a search in the agent's own list: the nodes ascend),
-// without one j + 1.  A stable partition of the whole event list by bot -- the bots of a graph are consecutive and so are its
-// events, hence bot b's list starts at agent_ev[b], the prefix its closure region has too --: counts per block of
-// PLAN_BLOCK events and bot, their scan per bot, the scatter, then the searches.  O(log n) per event whatever the stream.
+// with node[k] - node[j] >= MIN_POSES_BETWEEN (:304; skip[j]), without one j + 1.  A stable partition of the whole event list
+// by bot -- the bots of a graph are consecutive and so are its events, hence bot b's list starts at agent_ev[b], the prefix its
+// closure region has too --: counts per block of PLAN_BLOCK events and bot, their scan per bot, the scatter.  skip[j] is a
+// count over the few list entries behind the event, taken by the scatter from the list itself (no record is read back, none
+// written twice); only a cool-down longer than the scatter's halo is searched for in the finished lists, by a fourth kernel.
 #define PLAN_BLOCK QS_SLAM_PLAN_BLOCK
 #define PLAN_WAVES (PLAN_BLOCK / QS_WAVE)
 int qs_slam_plan_blocks(size_t n) { return (int)((n + PLAN_BLOCK - 1) / PLAN_BLOCK); }
@@ -168,19 +170,29 @@ __device__ inline int plan_graph_of(const unsigned int *__restrict__ ev_base, in
     return lo;
 }
 
-// plan pass 1: per block, the events of every bot
+// plan pass 1: per block, the events of every bot; and every bot's first candidate of this launch, pl_first: its first own
+// event with node - last_closure >= MIN_POSES_BETWEEN (none: its count) -- its nodes ascend, so that is the number of its events
+// below that bound, a count like the other (last_closure can be far negative: 64 bits; qs_slam_prefix_kernel left pl_first at 0)
 __global__ void __launch_bounds__(PLAN_BLOCK)
-qs_slam_plan_count_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent)
+qs_slam_plan_count_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent, int min_between,
+                          const long long *__restrict__ last_closure)
 {
-    __shared__ unsigned int s_cnt[QS_MAX_AGENT + 1];
+    __shared__ unsigned int s_cnt[QS_MAX_AGENT + 1], s_cool[QS_MAX_AGENT + 1];
     const int tid = threadIdx.x;
     const unsigned int n_ev = sb.ev_base[n_graphs], e = blockIdx.x * PLAN_BLOCK + tid;
     if (blockIdx.x * PLAN_BLOCK >= n_ev) return;
-    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) s_cnt[t] = 0;
+    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) { s_cnt[t] = 0; s_cool[t] = 0; }
     __syncthreads();
-    if (e < n_ev) atomicAdd(&s_cnt[plan_graph_of(sb.ev_base, n_graphs, e) * bots_per_graph + 1 + sb.ev_agent[e]], 1u);
+    if (e < n_ev) {
+        const int bot = plan_graph_of(sb.ev_base, n_graphs, e) * bots_per_graph + 1 + sb.ev_agent[e];
+        atomicAdd(&s_cnt[bot], 1u);
+        if (bot <= max_agent && sb.ev_node[e] < last_closure[bot] + (long long)min_between) atomicAdd(&s_cool[bot], 1u);
+    }
     __syncthreads();
-    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) sb.pl_blk[(size_t)t * sb.pl_blocks + blockIdx.x] = s_cnt[t];
+    for (int t = tid; t <= max_agent; t += PLAN_BLOCK) {
+        sb.pl_blk[(size_t)t * sb.pl_blocks + blockIdx.x] = s_cnt[t];
+        if (s_cool[t]) atomicAdd(&sb.pl_first[t], s_cool[t]);
+    }
 }
 
 // plan pass 2: per bot, exclusive scan of its block counts (the blocks that hold events)
@@ -207,19 +219,31 @@ qs_slam_plan_scan_kernel(QsSlamBatch sb, int n_graphs)
     for (int k = lo; k < hi; k++) { const unsigned int v = cnt[k]; cnt[k] = run; run += v; }
 }
 
-// plan pass 3: every event's record into its bot's list (stable: ranks inside the wave in lane order, waves in order, blocks by the scan)
+// plan pass 3: every event's record into its bot's list (stable: ranks inside the wave in lane order, waves in order, blocks by
+// the scan), its skip with it where the cool-down's window is short (window = max(MIN_POSES_BETWEEN, 1) <= PLAN_HALO; else
+// window = 0: skip is written 0 and qs_slam_plan_skip_kernel searches for it).  The window rule: let p be the first position
+// after event e of its graph's list with node >= node[e] + MIN_POSES_BETWEEN, the graph's end without one; the bot's first own
+// event at or after p is its own event number j + 1 + (its events at positions in (e, p)), which is its count if it has none
+// there.  The list's nodes are distinct and ascend, so p <= e + window: a count over at most window - 1 entries of the list as
+// it came in, which the block stages with a halo of the next PLAN_HALO events.  An event looks no further than its own graph's
+// end: the next graph's events carry the same local agent numbers.
+#define PLAN_HALO 256
 __global__ void __launch_bounds__(PLAN_BLOCK)
-qs_slam_plan_scatter_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent)
+qs_slam_plan_scatter_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, int max_agent, int min_between, int window)
 {
     __shared__ unsigned int s_w[PLAN_WAVES][QS_MAX_AGENT + 1];
+    __shared__ long long s_node[PLAN_BLOCK + PLAN_HALO];
+    __shared__ unsigned char s_agent[PLAN_BLOCK + PLAN_HALO];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned int n_ev = sb.ev_base[n_graphs], e = blockIdx.x * PLAN_BLOCK + tid;
-    if (blockIdx.x * PLAN_BLOCK >= n_ev) return;
+    const unsigned int n_ev = sb.ev_base[n_graphs], e0 = blockIdx.x * PLAN_BLOCK, e = e0 + tid;
+    if (e0 >= n_ev) return;
     for (int t = tid; t < PLAN_WAVES * (QS_MAX_AGENT + 1); t += PLAN_BLOCK) (&s_w[0][0])[t] = 0;
+    for (int t = tid; t < PLAN_BLOCK + (window ? PLAN_HALO : 0); t += PLAN_BLOCK)
+        if (e0 + t < n_ev) { s_node[t] = sb.ev_node[e0 + t]; s_agent[t] = sb.ev_agent[e0 + t]; }
     __syncthreads();
     const bool have = e < n_ev;
     int g = 0, bot = -1;
-    if (have) { g = plan_graph_of(sb.ev_base, n_graphs, e); bot = g * bots_per_graph + 1 + sb.ev_agent[e]; }
+    if (have) { g = plan_graph_of(sb.ev_base, n_graphs, e); bot = g * bots_per_graph + 1 + s_agent[tid]; }
     unsigned int rank = 0;
     unsigned long long remaining = __ballot(have);
     while (remaining) {
@@ -235,8 +259,20 @@ qs_slam_plan_scatter_kernel(QsSlamBatch sb, int bots_per_graph, int n_graphs, in
     if (have && bot <= max_agent) {
         unsigned int off = sb.pl_blk[(size_t)bot * sb.pl_blocks + blockIdx.x] + rank;
         for (int w = 0; w < wave; w++) off += s_w[w][bot];
+        unsigned int skip = 0;
+        if (window) {
+            // p: the first position of (e, end) with node >= bound, end = the graph's end or e + window, whichever comes first
+            // (staged slots tid + 1 .. hi - 1, all below n_ev and inside the halo: window <= PLAN_HALO)
+            const long long bound = s_node[tid] + (long long)min_between;
+            const unsigned int end = min(sb.ev_base[g + 1], e + (unsigned int)window);
+            int lo = tid + 1, hi = (int)(end - e0);
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_node[mid] >= bound) hi = mid; else lo = mid + 1; }
+            const unsigned char own = s_agent[tid];
+            skip = off + 1;
+            for (int q = tid + 1; q < lo; q++) skip += s_agent[q] == own;
+        }
         QsPlanRec rec;
-        rec.node = (int)sb.ev_node[e]; rec.r = e - sb.ev_base[g]; rec.type = sb.ev_type[e]; rec.skip = 0;
+        rec.node = (int)s_node[tid]; rec.r = e - sb.ev_base[g]; rec.type = sb.ev_type[e]; rec.skip = skip;
         rec.px = sb.ev_px[e]; rec.py = sb.ev_py[e];
         sb.pl_rec[sb.agent_ev[bot] + off] = rec;
     }
@@ -257,12 +293,12 @@ __device__ inline unsigned int plan_first_at_least(const QsPlanRec *pl, unsigned
     return lo;
 }
 
-// plan pass 4: skip of every record, and every bot's first candidate of this launch: its first own event with
-// node - last_closure >= MIN_POSES_BETWEEN (last_closure can be far negative: 64 bits; the bot's own count: none).  The
-// searches compare the records' nodes, the low words: the plan of a graph whose nodes do not fit them means nothing, and
-// nobody reads it -- the lean owner is refused there (qs_slam_chain_free_kernel, the predicate).
+// plan pass 4, only where the cool-down's window is longer than the scatter's halo (MIN_POSES_BETWEEN > PLAN_HALO): skip of
+// every record, a search in the bot's own list.  It compares the records' nodes, the low words: the plan of a graph whose
+// nodes do not fit them means nothing, and nobody reads it -- the lean owner is refused there (qs_slam_chain_free_kernel, the
+// predicate).
 __global__ void __launch_bounds__(256)
-qs_slam_plan_skip_kernel(QsSlamBatch sb, int n_graphs, int max_agent, int min_between, const long long *__restrict__ last_closure)
+qs_slam_plan_skip_kernel(QsSlamBatch sb, int n_graphs, int max_agent, int min_between)
 {
     const unsigned int n_ev = sb.ev_base[n_graphs], s = blockIdx.x * 256 + threadIdx.x;
     if (s >= n_ev) return;
@@ -273,7 +309,6 @@ qs_slam_plan_skip_kernel(QsSlamBatch sb, int n_graphs, int max_agent, int min_be
     const unsigned int base = sb.agent_ev[bot], n_own = sb.agent_ev[bot + 1] - base, j = s - base;
     const QsPlanRec *const pl = sb.pl_rec + base;
     sb.pl_rec[base + j].skip = plan_first_at_least(pl, j + 1, n_own, (long long)pl[j].node + (long long)min_between);
-    if (j == 0) sb.pl_first[bot] = plan_first_at_least(pl, 0, n_own, last_closure[bot] + (long long)min_between);
 }
 
 // ---- the chain: one workgroup (CH_WAVES waves) per pose graph ------------------------------------
@@ -1879,11 +1914,16 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     if (plan) {
         sb.pl_blocks = qs_slam_plan_blocks(n);
         const int nbots = c->cfg.max_agent + 1;
-        hipLaunchKernelGGL(qs_slam_plan_count_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent);
+        // (the scatter works every skip out itself from a window of the event list; a cool-down longer than its halo is searched for)
+        const int mb = c->cfg.min_poses_between, window = mb > PLAN_HALO ? 0 : mb > 1 ? mb : 1;
+        hipLaunchKernelGGL(qs_slam_plan_count_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent,
+                           mb, c->d_last_closure.p);
         hipLaunchKernelGGL(qs_slam_plan_scan_kernel, dim3(nbots), dim3(256), 0, c->stream, sb, G);
-        hipLaunchKernelGGL(qs_slam_plan_scatter_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent);
-        hipLaunchKernelGGL(qs_slam_plan_skip_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, c->stream, sb, G,
-                           c->cfg.max_agent, c->cfg.min_poses_between, c->d_last_closure.p);
+        hipLaunchKernelGGL(qs_slam_plan_scatter_kernel, dim3(sb.pl_blocks), dim3(PLAN_BLOCK), 0, c->stream, sb, c->bots_per_graph, G, c->cfg.max_agent,
+                           mb, window);
+        if (!window)
+            hipLaunchKernelGGL(qs_slam_plan_skip_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, c->stream, sb, G,
+                               c->cfg.max_agent, mb);
     } else {
         sb.pl_rec = nullptr;
     }

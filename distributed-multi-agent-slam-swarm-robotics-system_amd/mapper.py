@@ -968,6 +968,19 @@ class QuasarMapper:
             self._chk(r, "qs_chain_plan")
         return bool(r)
 
+    def chain_plan_read(self, bot):
+        """Diagnostic: bot's part of the plan of the last ingest, valid until the next one: dict(node int32 [n_own], r uint32,
+        skip uint32, first int) -- its events in list order (node index, position in the graph's event list, own index it goes
+        on at after a closure there) and the own index of its first event past the cool-down it came with.  Raises if the
+        last ingest had no plan."""
+        n, first = C.c_size_t(0), C.c_uint32(0)
+        self._chk(self._L.qs_chain_plan_read(self._h, bot, None, None, None, 0, C.byref(n), C.byref(first)), "qs_chain_plan_read")
+        node = np.empty(n.value, dtype=np.int32); r = np.empty(n.value, dtype=np.uint32); skip = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            self._chk(self._L.qs_chain_plan_read(self._h, bot, _ptr(node), _ptr(r), _ptr(skip), n.value, C.byref(n), C.byref(first)),
+                      "qs_chain_plan_read")
+        return {"node": node, "r": r, "skip": skip, "first": int(first.value)}
+
     def set_chain_lookahead(self, on=True):
         """The lean owner walks a bucket on only if its node's look-ahead word -- the index of the successor node's first
         entry -- lies below the match it has (default), or by the node's own last entry as the general query does

@@ -544,6 +544,14 @@ int qs_chain_lean(qs_ctx *ctx);
  * the stream); < 0: error. */
 int qs_set_chain_plan(qs_ctx *ctx, int32_t on);
 int qs_chain_plan(qs_ctx *ctx);
+/* diagnostic: bot's part of the plan of the last ingest, valid until the next one (waits for the stream).  n_own: the number of
+ * its events in that launch; first: the own index of its first event past the cool-down it came with (none: n_own); for each
+ * of them, in list order, node (the node index's low word), r (the position in its graph's event list) and skip (the own
+ * index of its first later event past the cool-down of a closure there; none: n_own).  node, r, skip: arrays of cap >= n_own
+ * entries, or all three NULL to ask for n_own and first alone.  QS_E_STATE if the last ingest had no plan, QS_E_RANGE if cap is
+ * too small (n_own and first are set even so). */
+int qs_chain_plan_read(qs_ctx *ctx, int32_t bot, int32_t *node, uint32_t *r, uint32_t *skip, size_t cap, size_t *n_own,
+                       uint32_t *first);
 
 /* Every node of a bucket chain carries, beside its seven entries, the node index of its successor node's first entry (the
  * look-ahead word; written always).  The lean owner walks a bucket on only if that index lies below the match it has: entries

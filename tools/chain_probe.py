@@ -26,17 +26,18 @@ else:
     ng = 1 if wl == "one64" else 32
 if form: m.set_chain_form(form)
 m.reset(); m.ingest_device(d.data_ptr(), B, 42, 0, 0, seq0=0); m.sync()
-out = []
+out, head = [], []
 for r in range(reps):
     m.reset(); m.stage_times(reset=True); m.timing_enable(True); m.ingest_device(d.data_ptr(), B, 42, 0, 0, seq0=0); m.sync()
     c = m.counters(); st = m.stage_times()
     out.append(round(st["slam_chain"][0], 3))
+    head.append(round(st["slam"][0] - st["slam_chain"][0], 3))     # the index and plan kernels ahead of the chain, and the pose kernel
 h = hashlib.sha1()
 for g in range(ng):
     idx, corr = m.closures(g); xy, ti = m.landmarks(g)
     for a in (idx, corr, xy, ti): h.update(a.tobytes())
 for b in range(1, na + 1): h.update(m.drift(b).tobytes())
-res = {"workload": wl, "lib": os.path.basename(ROOT), "form": form, "chain_ms": out,
+res = {"workload": wl, "lib": os.path.basename(ROOT), "form": form, "chain_ms": out, "head_ms": head,
        "batches": c["slam_windows"], "closures": c["closures"], "rounds": c["slam_rounds"], "digest": h.hexdigest()[:16],
        "lean": m.chain_lean() if hasattr(m, "chain_lean") else None,
        "plan": m.chain_plan() if hasattr(m, "chain_plan") else None,

@@ -237,6 +237,8 @@ SIGNATURES = {
     "qs_chain_lookahead": (_i32, [_vp]),
     "qs_set_chain_plan": (_i32, [_vp, _i32]),
     "qs_chain_plan": (_i32, [_vp]),
+    "qs_set_chain_scout": (_i32, [_vp, _i32]),
+    "qs_chain_scout": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "qs_chain_plan_read": (_i32, [_vp, _i32, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
     "qs_voxel_downsample": (_i32, [_vp, _vp, _sz, _f64, _vp, _sz, C.POINTER(_sz)]),
     "qs_voxel_downsample_device": (_i32, [_vp, _vp, _sz, _f64, _vp, _sz, C.POINTER(_sz)]),

@@ -215,9 +215,12 @@ extern "C" int qs_create(const qs_config *cfg, qs_ctx **out)
     CREATE_CHK(c->d_ekf_prev.alloc((size_t)nb * 4));
     CREATE_CHK(c->d_flags.alloc(QS_N_FLAGS));
     CREATE_CHK(hipMemset(c->d_flags.p, 0, QS_N_FLAGS * sizeof(unsigned int)));
+    CREATE_CHK(c->d_scout.alloc(2));
+    CREATE_CHK(hipMemset(c->d_scout.p, 0, 2 * sizeof(unsigned int)));
     CREATE_CHK(hipHostMalloc((void **)&c->h_chain_stat, 8 * sizeof(unsigned int), hipHostMallocDefault));
     memset(c->h_chain_stat, 0, 8 * sizeof(unsigned int));
     CREATE_CHK(hipEventCreateWithFlags(&c->ev_chain_stat, hipEventDisableTiming));
+    if (const char *e = getenv("QS_CHAIN_SCOUT")) c->chain_scout = strcmp(e, "1") == 0;          // (qs_set_chain_scout's default, for A/B runs)
     if (const char *e = getenv("QS_CHAIN_MODE")) c->chain_form = strcmp(e, "window") == 0 ? QS_CHAIN_WINDOW : strcmp(e, "free") == 0 ? QS_CHAIN_FREE : strcmp(e, "free_posting") == 0 ? QS_CHAIN_FREE_POSTING : QS_CHAIN_AUTO;
     CREATE_CHK(c->d_graphs.alloc((size_t)c->n_graphs));
     CREATE_CHK(hipMemset(c->d_graphs.p, 0, (size_t)c->n_graphs * sizeof(QsGraphDev)));
@@ -412,6 +415,26 @@ extern "C" int qs_chain_lookahead(qs_ctx *c)
 {
     if (!c) return QS_E_INVAL;
     return c->chain_lookahead ? 1 : 0;
+}
+
+extern "C" int qs_set_chain_scout(qs_ctx *c, int32_t on)
+{
+    ARGCHK(c, c != nullptr);
+    c->chain_scout = on != 0;
+    return QS_OK;
+}
+
+extern "C" int qs_chain_scout(qs_ctx *c, uint64_t *staged, uint64_t *fallback)
+{
+    ARGCHK(c, c != nullptr && staged && fallback);
+    *staged = 0; *fallback = 0;
+    if (!c->chain_last_scout) return QS_OK;      // (no launch yet, or one without scouts)
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned int cnt[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(cnt, c->d_scout.p, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *staged = cnt[0]; *fallback = cnt[1];
+    return QS_OK;
 }
 
 extern "C" int qs_sync(qs_ctx *c)

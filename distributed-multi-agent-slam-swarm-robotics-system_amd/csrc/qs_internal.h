@@ -336,6 +336,9 @@ struct qs_ctx {
     bool chain_plan = true;                      // the lean owner walks a per-agent plan of its events (qs_set_chain_plan) ...
     bool chain_last_plan = false;                // ... and the last launch had one built for it
     bool chain_lookahead = true;                 // the lean owner tests a node's look-ahead word before it walks on (qs_set_chain_lookahead)
+    bool chain_scout = false;                    // scout waves stage the plan owner's rows in LDS (qs_set_chain_scout; graphs of <= 2 agents) ...
+    bool chain_last_scout = false;               // ... and the last launch ran the kernel that has them, with a plan
+    DevBuf<unsigned int> d_scout;                // [2] the last launch's decisions settled from a stage / by the owner's own loads
     unsigned int *h_chain_stat = nullptr;        // pinned: [0..3] the four running totals as copied last, [4..7] as consumed last
     hipEvent_t ev_chain_stat = nullptr;          // ... complete when the copy has landed
     bool chain_stat_pending = false;

@@ -1051,6 +1051,32 @@ qs_slam_chain_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBucketGe
         if ((sp_ & 63u) == 0 && (__hip_atomic_load(&counters[QS_CNT_SLAM_ROUNDS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 40)) break;         \
         __builtin_amdgcn_s_sleep(1); } } while (0)
 
+// The scouts of the 8-wave kernel (slam_chain_scout.inc): the window of bucket cells a scout stages (FR_SC_W x FR_SC_W; 4 or 5), the
+// staged entries a lane of the owner holds (7 entries a bucket over 64 lanes), the waves that scout for owners 0 and 1 (waves
+// go to the four SIMDs round robin: 0 and 4 share SIMD 0, which no owner and no committer uses), and how often the owner asks again
+// for a stage that is not ready before it loads its rows itself (measured: profiles/chain_scout/variants.txt).
+#ifndef FR_SC_W
+#define FR_SC_W 4
+#endif
+#define FR_SC_K ((FR_SC_W * FR_SC_W * QS_NODE_CAP + QS_WAVE - 1) / QS_WAVE)
+// FR_SC_SPLIT scout waves an owner share a stage between them, FR_SC_K / FR_SC_SPLIT entries a lane each (1: waves 0 and 4; 2: the
+// second scouts on waves 3 and 5, beside the committer and beside owner 0 -- measured slower, profiles/chain_scout/variants.txt)
+#ifndef FR_SC_SPLIT
+#define FR_SC_SPLIT 1
+#endif
+#define FR_SC_KW (FR_SC_K / FR_SC_SPLIT)
+static_assert(FR_SC_K % FR_SC_SPLIT == 0, "the scouts of an owner take the same number of slots");
+#ifndef FR_SC_WAVE
+#if FR_SC_SPLIT == 2
+#define FR_SC_WAVE(o, q) ((o) == 0 ? ((q) == 0 ? 0 : 3) : ((q) == 0 ? 4 : 5))
+#else
+#define FR_SC_WAVE(o, q) ((o) == 0 ? 0 : 4)
+#endif
+#endif
+#ifndef FR_SC_WAIT
+#define FR_SC_WAIT 32
+#endif
+
 // one query: the reference's first match among the landmarks of type qtype with node index <= eff, within the radius of
 // (qx, qy); lane = (bucket of the 3 x 3 neighbourhood, entry of that bucket's current node).  LL_MAX: none.
 // (the pieces of a query's first round, so that an owner can have the NEXT decision's rows on their way while it works on this one)
@@ -1200,13 +1226,17 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                           int max_agent, int min_between, double r2thr, double corr,
                           double *__restrict__ drift, long long *__restrict__ last_closure,
                           unsigned long long *__restrict__ counters, int raw_pose, unsigned int *__restrict__ pile_flag,
-                          long long lean_limit, unsigned int lean_seq, unsigned int la_off)
+                          long long lean_limit, unsigned int lean_seq, unsigned int la_off, unsigned int *__restrict__ scout_cnt)
 {
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     QsGraphDev *const Gp = graphs + g;
     const int bot0 = g * bots_per_graph + 1;
     const int nb = min(bots_per_graph, max_agent - bot0 + 1);
     constexpr int AGW = WAVES - 3, INS = WAVES - 1, THREADS = WAVES * QS_WAVE;   // owner waves 1 .. AGW; the committer
+    // The scouts (slam_chain_scout.inc): in the 8-wave instantiation a graph of up to two agents leaves five waves and a SIMD
+    // idle; one wave per owner stages the rows of the decision after next in LDS.  scout_cnt: the launch's pair of counts
+    // (decisions settled from a stage, decisions by the owner's own loads); nullptr: no scouts (qs_set_chain_scout).
+    constexpr bool SCOUT_OK = !DENSE && WAVES == 8 && !POST;
     // The lean owner (below: 32-bit node indices, a decision settled by its first rows alone): allowed while every node index
     // this launch can meet is below the low word of the empty-slot marker (lean_limit: that word, or less -- qs_set_chain_lean;
     // 0: off), the node table's byte offsets fit 32 bits, the cool-down cannot overflow a 32-bit difference, and poses get
@@ -1222,6 +1252,7 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
                       && (unsigned long long)Gp->node_cap * sizeof(QsLmNode) < (1ull << 32) && min_between < (1 << 30) && raw_pose == 0;
     if (LEAN_OK && tid == 0 && lean_limit > 0 && !lean && pile_flag) atomicMax(pile_flag + QS_FLAG_CHAIN_FULL - QS_FLAG_PILE, lean_seq);
     const int n_ow = min(AGW, nb);                  // owner waves in use
+    const bool scout = SCOUT_OK && scout_cnt != nullptr && lean && sb.pl_rec && nb <= 2;
     constexpr int NA = AGW;                         // (graphs with more agents: qs_slam_chain_dyn_kernel)
     constexpr unsigned int HD = FR_HAND;            // events an owner can be ahead of the committer (less one chunk)
 
@@ -1247,6 +1278,19 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
     __shared__ long long p_node[POST ? FR_PEND : 1];   // the event that has the slot (its node index), written after ...
     __shared__ double p_x[POST ? FR_PEND : 1], p_y[POST ? FR_PEND : 1];   // ... its pose
     __shared__ unsigned int s_comm;               // events committed (count from e0): where the frontier stands in the list
+    // owner -> scout: the post's number (written last; ~0: the owner has left), and by its parity the next candidate and the drift;
+    // scout -> owner: by the post's parity the staged entries, a slot each ((look-ahead word << 32) | index low word, x, y), the
+    // candidate they are for (~0: none), the window's base cell, the limit on indices, and last the number of the post they answer
+    constexpr int SC_N = SCOUT_OK ? 2 : 1, SC_SLOTS = SCOUT_OK ? FR_SC_K * QS_WAVE : 1;
+    __shared__ unsigned int sc_word[SC_N], sc_j[SC_N][2];
+    __shared__ double sc_dx[SC_N][2], sc_dy[SC_N][2];
+    __shared__ long long sg_idla[SC_N][2][SC_SLOTS];
+    __shared__ double sg_x[SC_N][2][SC_SLOTS], sg_y[SC_N][2][SC_SLOTS];
+    __shared__ unsigned int sg_ready[SC_N][2][FR_SC_SPLIT], sg_tag[SC_N][2][FR_SC_SPLIT];          // (a set per scout wave of the owner)
+    __shared__ int sg_bcx[SC_N][2][FR_SC_SPLIT], sg_bcy[SC_N][2][FR_SC_SPLIT], sg_eff[SC_N][2][FR_SC_SPLIT];
+    __shared__ int sg_rnode[SC_N][2], sg_rtype[SC_N][2];                          // the candidate's record (QsPlanRec), by the owner's first scout
+    __shared__ unsigned int sg_rr[SC_N][2], sg_rskip[SC_N][2];
+    __shared__ double sg_rpx[SC_N][2], sg_rpy[SC_N][2];
 
     const unsigned int e0 = sb.ev_base[g], e1 = sb.ev_base[g + 1];
     if (POST) for (int t = tid; t < FR_PEND; t += THREADS) p_node[t] = -LL_MAX - 1;
@@ -1256,6 +1300,10 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
     }
     if (tid < AGW) s_prog[tid] = tid < n_ow ? (e0 < e1 ? sb.ev_node[e0] : LL_MAX) : LL_MAX;
     if (tid == 0) { s_frontier = e0 < e1 ? sb.ev_node[e0] - 1 : LL_MAX; s_nmisc = Gp->n_misc; s_nlms = Gp->n_lms; s_comm = 0; }
+    if constexpr (SCOUT_OK) {
+        if (tid < SC_N) sc_word[tid] = 0;
+        if (tid < SC_N * 2 * FR_SC_SPLIT) (&sg_ready[0][0][0])[tid] = ~0u;
+    }
     __syncthreads();
 
     if (wave >= 1 && wave <= n_ow) {
@@ -1303,7 +1351,16 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
         // the register allocation of the instantiations that have no lean owner, and cost them 3 %.)
         // (And a third, the lean owner's where the launch has a plan of every agent's events: slam_chain_plan_owner.inc.  Not in
         // the DENSE instantiation, which it costs two spilled VGPRs: the host builds no plan for it.)
-        if (!DENSE && lean && sb.pl_rec) {
+        // (And a fourth, the plan's walk with the decisions' rows staged by a scout wave: slam_chain_scout_owner.inc.)
+        bool scouted = false;
+        if constexpr (SCOUT_OK) {
+            if (scout) {
+                scouted = true;
+#include "slam_chain_scout_owner.inc"
+            }
+        }
+        if (scouted) {
+        } else if (!DENSE && lean && sb.pl_rec) {
 #include "slam_chain_plan_owner.inc"
         } else if (lean) {
             constexpr bool LEAN = true;
@@ -1434,6 +1491,15 @@ qs_slam_chain_free_kernel(QsGraphDev *__restrict__ graphs, QsSlamBatch sb, QsBuc
             if (pile && pile_flag) *pile_flag = 1u;
         }
         for (int t = lane; t < nb; t += QS_WAVE) sb.acl_cnt[bot0 + t] = c_apos[t] - sb.agent_ev[bot0 + t];
+    } else if constexpr (SCOUT_OK) {
+        int sc_o = -1, sc_q = 0;
+        for (int o = 0; o < 2; o++)
+            for (int q = 0; q < FR_SC_SPLIT; q++)
+                if (wave == FR_SC_WAVE(o, q)) { sc_o = o; sc_q = q; }
+        if (scout && sc_o >= 0 && sc_o < n_ow) {
+            // =================================== a scout of owner sc_o ===================================
+#include "slam_chain_scout.inc"
+        }
     }
 }
 
@@ -1934,11 +2000,13 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
     c->chain_last_posting = false;
     c->chain_last_free = free_mode;
     c->chain_last_lean_asked = false;
+    c->chain_last_scout = false;
 #define FR_LAUNCH(DENSE_, WAVES_, POST_) hipLaunchKernelGGL((qs_slam_chain_free_kernel<DENSE_, WAVES_, POST_>), dim3(G), dim3(WAVES_ * QS_WAVE), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE, \
                            c->chain_lean_mode == QS_CHAIN_LEAN_OFF ? 0ll : c->chain_lean_limit, c->chain_lean_seq,                          \
-                           (unsigned int)((c->chain_lookahead ? QS_NODE_LOOKAHEAD : QS_NODE_CAP - 1) * sizeof(long long)))
+                           (unsigned int)((c->chain_lookahead ? QS_NODE_LOOKAHEAD : QS_NODE_CAP - 1) * sizeof(long long)),                  \
+                           c->chain_last_scout ? c->d_scout.p : nullptr)
 #define DY_LAUNCH(DENSE_) hipLaunchKernelGGL((qs_slam_chain_dyn_kernel<DENSE_>), dim3(G), dim3(CH_THREADS), 0, c->stream, c->d_graphs.p, sb, c->bg, \
                            c->bots_per_graph, c->cfg.max_agent, c->cfg.min_poses_between, c->r2_threshold,                                  \
                            c->cfg.closure_correction, c->d_drift.p, c->d_last_closure.p, c->d_counters.p, raw_pose ? 1 : 0, c->d_flags.p + QS_FLAG_PILE)
@@ -1948,6 +2016,9 @@ hipError_t qs_launch_slam(qs_ctx *c, size_t n, bool raw_pose)
             // number in a device word, which is all qs_chain_lean looks at)
             c->chain_lean_seq++;
             c->chain_last_lean_asked = lean_asked;
+            // the scouts: only the 8-wave instantiation without posting has them, and only for owners that walk a plan
+            c->chain_last_scout = c->chain_scout && plan && sel == 2;
+            if (c->chain_last_scout) hipMemsetAsync(c->d_scout.p, 0, 2 * sizeof(unsigned int), c->stream);
             switch (sel) {
             case 0: FR_LAUNCH(false, 16, false); break;  case 1: FR_LAUNCH(false, 16, true); break;
             case 2: FR_LAUNCH(false, 8, false); break;   case 3: FR_LAUNCH(false, 8, true); break;

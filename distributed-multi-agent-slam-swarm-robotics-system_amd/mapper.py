@@ -994,6 +994,19 @@ class QuasarMapper:
             self._chk(r, "qs_chain_lookahead")
         return bool(r)
 
+    def set_chain_scout(self, on=True):
+        """In graphs of up to two agents a scout wave per owner stages the rows of the decision after next in LDS, and the
+        owner settles from them the decisions it can (on=True), or every decision is made from the owner's own loads
+        (the default: the scouts measured slower).  Same results either way."""
+        self._chk(self._L.qs_set_chain_scout(self._h, 1 if on else 0), "qs_set_chain_scout")
+
+    def chain_scout(self):
+        """(staged, fallback) of the last ingest: the owners' decisions settled from a scout's stage and those made from their
+        own loads; (0, 0) if the launch had no scouts (waits for the stream)."""
+        s, f = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.qs_chain_scout(self._h, C.byref(s), C.byref(f)), "qs_chain_scout")
+        return int(s.value), int(f.value)
+
     def mfma_f64_rate(self):
         """Measured dense fp64 MFMA rate of this GPU in TFLOP/s (diagnostic)."""
         v = C.c_double()

@@ -562,6 +562,20 @@ int qs_chain_plan_read(qs_ctx *ctx, int32_t bot, int32_t *node, uint32_t *r, uin
 int qs_set_chain_lookahead(qs_ctx *ctx, int32_t on);
 int qs_chain_lookahead(qs_ctx *ctx);
 
+/* In a graph of up to two agents the 8-wave free-running kernel has waves to spare.  One of them per owner, its scout, reads
+ * ahead of the owner: after every decision it takes the candidate the plan gives after the owner's next one, the pose that
+ * candidate will be queried at but for one closure's correction, and stages the first nodes of a 4 x 4 window of buckets around
+ * it in LDS.  The owner settles a decision from its stage when the stage is for its candidate, holds the 3 x 3 buckets of the
+ * real pose and shows a match with no bucket to walk further; any other decision it makes from its own loads, as without scouts.
+ * Same closures, landmarks and drifts bit for bit.
+ * qs_set_chain_scout: on != 0 runs the scouts wherever a launch has a plan, 0 (default) never; the environment's QS_CHAIN_SCOUT=1
+ * at qs_create turns them on for that context.  Off by default because it measured slower: the owner's path through a stage is
+ * longer in instructions than the round trip of the loads it saves (profiles/chain_scout/).
+ * qs_chain_scout: of the last ingest, the owners' decisions settled from a stage and those made from their own loads (both 0
+ * if that launch had no scouts: another instantiation, no plan, more than two agents a graph); waits for the stream. */
+int qs_set_chain_scout(qs_ctx *ctx, int32_t on);
+int qs_chain_scout(qs_ctx *ctx, uint64_t *staged, uint64_t *fallback);
+
 /* diagnostic: measured dense fp64 MFMA rate of this GPU (TFLOP/s), the ceiling qs_nn_search mode 2 is priced against */
 int qs_diag_mfma_f64_rate(qs_ctx *ctx, double *tflops);
 /* diagnostic: latencies of the primitives one loop-closure decision chains together, measured on this GPU by ONE workgroup

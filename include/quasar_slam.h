@@ -1016,15 +1016,21 @@ int qs_ekf_state(qs_ctx *ctx, int32_t bot, double x[6], double P[36]);
  *   SCALARS    u64 next_seq, epoch_base, n_rebases, edge_rays, edge_overflow; f64 sweep_min, sweep_max;
  *              u32 dirty_since_fuse, counts_view_fused, n_graphs, n_bots (= max_agent + 1)                        72 bytes
  *   BOTS       n_bots x: f64 offset; f64 drift[2]; i64 last_closure; u64 zone[4]; f64 ekf[44]; f64 ekf_prev[4], as six
- *              arrays in that order (all bots' offsets, then all drifts, ...)
- *   COUNTERS   u64[QS_CNT_N] as the device holds them (QS_CNT_REBASES / EDGE_* come from SCALARS)
+ *              arrays in that order (all bots' offsets, then all drifts, ...); slot 0 is no bot.  zone = min x, min y, max x,
+ *              max y of the box qs_zone reports, each f64 as the u64 that orders as the number does: its bits inverted if
+ *              the sign bit is set, else with the sign bit set; a bot without points holds 2^64 - 1, 2^64 - 1, 0, 0.
+ *              ekf = x[6], P[36] row-major (what qs_ekf_state reports), the time of the last step, initialised (0.0 / 1.0);
+ *              ekf_prev = the bot's previous packet: time, yaw, encoder count, seen (0.0 / 1.0)
+ *   COUNTERS  u64[QS_CNT_N] as the device holds them (QS_CNT_REBASES / EDGE_* come from SCALARS)
  *   GRAPHS     n_graphs x {i64 n_nodes, n_landmarks, n_closures}, then per graph: landmark log f64 x[L], f64 y[L],
  *              i64 node[L], u8 type[L] (padded to 8), closure log i64 landmark[C], i64 node[C], f64 dx[C], f64 dy[C],
  *              u8 agent[C] (padded to 8)
  *   BLOCK_IDS  u32[n_blocks], ascending: block (bx, by) is by * 32 * pitch + bx, pitch = ceil(ceil(size / 16) / 32)
  *   BLOCKS     per block, cells row-major (lane = 16 * row + column): u32 stamps[64]; enable_counts: u64 counters[64];
- *              enable_counts and dirty_tracking: u64 sent[64], u64 fused[64].  Cells beyond the grid's edge are 0.
- *   DIRTY      dirty_tracking only: u32[ceil(size / 4) * pitch], the live dirty bitmap
+ *              enable_counts and dirty_tracking: u64 sent[64], u64 fused[64].  Cells beyond the grid's edge are 0.  A
+ *              counter word is hits << 32 | misses (the int32 pair of qs_device_buffers, misses first).
+ *   DIRTY      dirty_tracking only: u32[ceil(size / 4) * pitch], the live dirty bitmap: bit (id % 32) of word (id / 32) is
+ *              block id; the bits of a row beyond its last block mean nothing
  * A version the library does not know is refused. */
 #define QS_CKPT_MAGIC "QSCK"
 #define QS_CKPT_VERSION 1

@@ -43,6 +43,24 @@ class QsSenseParams(C.Structure):
 QS_SENSE_MAX_CELLS = 255                                                         # include/quasar_slam.h, "sensing a world"
 
 
+class QsCheckParams(C.Structure):
+    """struct qs_check_params (include/quasar_slam.h)."""
+    _fields_ = [("tol", C.c_double), ("min_checked", C.c_int32), ("max_bad_percent", C.c_int32), ("count_missed", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class QsSweepCheck(C.Structure):
+    """struct qs_sweep_check (include/quasar_slam.h)."""
+    _fields_ = [("agree", C.c_int32), ("nearer", C.c_int32), ("farther", C.c_int32), ("missed", C.c_int32), ("unseen", C.c_int32),
+                ("checked", C.c_int32), ("bad", C.c_int32), ("status", C.c_int32), ("accepted_record", C.c_uint8),
+                ("pad", C.c_uint8 * 7), ("sin_yaw", C.c_double), ("cos_yaw", C.c_double)]
+
+
+# include/quasar_slam.h, "sweep check"
+QS_BEAM_AGREE, QS_BEAM_NEARER, QS_BEAM_FARTHER, QS_BEAM_MISSED, QS_BEAM_UNSEEN, QS_BEAM_NO_RECORD = 0, 1, 2, 3, 4, 255
+QS_CHECK_OK, QS_CHECK_NO_RECORD, QS_CHECK_UNDECIDED, QS_CHECK_CONTRADICTS = 0, 1, 2, 3
+
+
 class QsMatchParams(C.Structure):
     """struct qs_match_params (include/quasar_slam.h)."""
     _fields_ = [("radius", C.c_int32), ("window", C.c_int32), ("angle_steps", C.c_int32), ("min_hits", C.c_int32),
@@ -190,6 +208,11 @@ SIGNATURES = {
     "qs_sense_sweeps_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "qs_sense_packets": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "qs_sense_packets_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "qs_check_sweeps": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "qs_check_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "qs_ingest_sweeps_checked": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_ingest_sweeps_checked_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
+    "qs_last_sweep_checks": (_i32, [_vp, _vp, _sz]),
     "qs_last_hits": (_i32, [_vp, _vp, _vp, _sz]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),

@@ -225,7 +225,7 @@ int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, Qs
     return QS_OK;
 }
 
-static int match_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
+int qs_sweep_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
 {
     char msg[256];
     const char *bad = nullptr;
@@ -236,20 +236,24 @@ static int match_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
     return QS_OK;
 }
 
+hipError_t qs_beam_table(qs_ctx *c)
+{
+    if (c->match_tab.p) return hipSuccess;                         // the beam angles' cos / sin: libm's, once per context
+    static const double kRad = 3.141592653589793 / 180.0;
+    double tab[2 * QS_SWEEP_BEAMS];
+    for (int i = 0; i < QS_SWEEP_BEAMS; i++) {
+        const double b = (double)(i - 90) * kRad;
+        tab[i] = cos(b); tab[QS_SWEEP_BEAMS + i] = sin(b);
+    }
+    HIPRET(c->match_tab.alloc(2 * QS_SWEEP_BEAMS));
+    return hipMemcpy(c->match_tab.p, tab, sizeof tab, hipMemcpyHostToDevice);
+}
+
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,
                            const unsigned short *d_lens, qs_sweep_match *out, double *rot, size_t graph_k0)
 {
     if (n == 0) return hipSuccess;
-    if (!c->match_tab.p) {                                         // the beam angles' cos / sin: libm's, once per context
-        static const double kRad = 3.141592653589793 / 180.0;
-        double tab[2 * QS_SWEEP_BEAMS];
-        for (int i = 0; i < QS_SWEEP_BEAMS; i++) {
-            const double b = (double)(i - 90) * kRad;
-            tab[i] = cos(b); tab[QS_SWEEP_BEAMS + i] = sin(b);
-        }
-        HIPRET(c->match_tab.alloc(2 * QS_SWEEP_BEAMS));
-        HIPRET(hipMemcpy(c->match_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
-    }
+    HIPRET(qs_beam_table(c));
     QsSweepArgs a;
     qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     QsMatchArgs m;
@@ -296,7 +300,7 @@ extern "C" int qs_match_sweeps_device(qs_ctx *c, const qs_match_params *params, 
     QsMatchSetup ms;
     int rc = qs_match_setup(c, params, "qs_match_sweeps", ms);
     if (rc != QS_OK) return rc;
-    rc = match_call_ok(c, n, stride, "qs_match_sweeps");
+    rc = qs_sweep_call_ok(c, n, stride, "qs_match_sweeps");
     if (rc != QS_OK || n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SYNCCHK(c);
@@ -312,7 +316,7 @@ extern "C" int qs_match_sweeps(qs_ctx *c, const qs_match_params *params, const u
     QsMatchSetup ms;
     int rc = qs_match_setup(c, params, "qs_match_sweeps", ms);
     if (rc != QS_OK) return rc;
-    rc = match_call_ok(c, n, stride, "qs_match_sweeps");
+    rc = qs_sweep_call_ok(c, n, stride, "qs_match_sweeps");
     if (rc != QS_OK || n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SYNCCHK(c);

@@ -153,6 +153,7 @@ int reset_state(qs_ctx *c)
     for (int g = 0; g < c->n_graphs; g++) { c->lms_upper[g] = 0; c->cls_upper[g] = 0; }
     c->next_seq = 0; c->epoch_base = 0; c->last_n = 0; c->last_has_poses = false; c->n_rebases = 0; c->edge_rays_total = 0;
     c->last_sweeps = false; c->last_sweeps_n = 0; c->last_matches = false; c->last_matches_n = 0;
+    c->last_checks = false; c->last_checks_n = 0;
     c->pile_mode = false;
     c->edge_maybe = false; c->edge_overflow_total = 0;      // (rays still waiting belonged to the old session: the flags are cleared above)
     return QS_OK;
@@ -740,7 +741,7 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
                          const double *d_time, uint64_t seq0)
 {
     if (seq0 == UINT64_MAX) seq0 = c->next_seq;
-    c->last_n = n; c->last_has_poses = true; c->last_sweeps = false; c->last_matches = false;
+    c->last_n = n; c->last_has_poses = true; c->last_sweeps = false; c->last_matches = false; c->last_checks = false;
     if (n == 0) return QS_OK;
     int rc = qs_batch_prepare(c, n);
     if (rc != QS_OK) return rc;
@@ -889,7 +890,7 @@ extern "C" int qs_update_rays(qs_ctx *c, const double *rx, const double *ry, con
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dirty_since_fuse = true;
     c->next_seq = seq0 + n_seq;
-    c->last_has_poses = false; c->last_sweeps = false; c->last_matches = false;
+    c->last_has_poses = false; c->last_sweeps = false; c->last_matches = false; c->last_checks = false;
     return QS_OK;
 }
 

@@ -305,7 +305,10 @@ struct qs_ctx {
     DevBuf<qs_sweep_match> match_out;            //   ... the matches of the last matched ingest (qs_last_sweep_matches)
     size_t last_matches_n = 0;
     bool last_matches = false;
-    DevBuf<double> reloc_rot;                    // relocalisation (reloc.hip): sin, cos, yaw of the reloc_nrot rotation steps, host's libm
+    DevBuf<qs_sweep_check> check_out;            // sweep check (check.hip): the checks of the last guarded ingest (qs_last_sweep_checks)
+    size_t last_checks_n = 0;
+    bool last_checks = false;
+    DevBuf<double> reloc_rot;                   // relocalisation (reloc.hip): sin, cos, yaw of the reloc_nrot rotation steps, host's libm
     int reloc_nrot = 0;
     DevBuf<char> reloc_ws;                       //   ... census, score tables and picks of one chunk of sweeps (qs_reloc_layout)
 
@@ -453,6 +456,16 @@ int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, Qs
 // graph_k0 as qs_sweep_args takes it (sweep_common.h): QS_SWEEP_NO_GRAPH, or the record of a graph-mode call the n records start at
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,
                            const unsigned short *d_lens, qs_sweep_match *out, double *rot, size_t graph_k0);
+// c->match_tab, filled on first use: cos, sin of the 181 beam angles (i - 90) * (pi / 180) from the host's libm
+hipError_t qs_beam_table(qs_ctx *c);
+// what every call that reads sweeps without mapping them refuses: another stride, a sharded context, 2^31 records or more
+int qs_sweep_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who);
+// check.hip: the parameters of one checking call, checked against the context's sweep filter and resolution
+struct QsCheckSetup { int C, min_checked, max_bad_percent, count_missed; double tol; };
+int qs_check_setup(qs_ctx *c, const qs_check_params *params, const char *who, QsCheckSetup &cs);
+// n device-resident records checked against the map as the stream finds it; cls (optional): [n][181] the beams' classes
+hipError_t qs_launch_check(qs_ctx *c, const QsCheckSetup &cs, const unsigned char *d_pkts, size_t n, size_t stride,
+                           const unsigned short *d_lens, qs_sweep_check *out, unsigned char *cls);
 // grid_ops.hip
 hipError_t qs_launch_rebase(qs_ctx *c);
 hipError_t qs_launch_fuse(qs_ctx *c, const unsigned int *const *d_src_stamps,

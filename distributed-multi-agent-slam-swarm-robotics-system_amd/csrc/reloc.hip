@@ -605,16 +605,8 @@ struct QsRelocPlan { QsRelocArgs m; QsRelocLayout L; size_t n_tiles, lds; };
 static hipError_t reloc_prepare(qs_ctx *c, const QsRelocSetup &rs, size_t offp, bool groups, QsRelocPlan &pl)
 {
     const qs_reloc_params &p = rs.p;
-    static const double kRad = 3.141592653589793 / 180.0, kTwoPi = 2.0 * 3.141592653589793;
-    if (!c->match_tab.p) {                                         // the beam angles' cos / sin: libm's, once per context (as match.hip)
-        double tab[2 * QS_SWEEP_BEAMS];
-        for (int i = 0; i < QS_SWEEP_BEAMS; i++) {
-            const double b = (double)(i - 90) * kRad;
-            tab[i] = cos(b); tab[QS_SWEEP_BEAMS + i] = sin(b);
-        }
-        HIPRET(c->match_tab.alloc(2 * QS_SWEEP_BEAMS));
-        HIPRET(hipMemcpy(c->match_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
-    }
+    static const double kTwoPi = 2.0 * 3.141592653589793;
+    HIPRET(qs_beam_table(c));                                      // the beam angles' cos / sin (match.hip)
     if (c->reloc_nrot != p.n_rot) {                                // G2: the rotations' sin / cos and reported yaw, libm's
         std::vector<double> rot(3 * (size_t)QS_RELOC_MAX_ROT, 0.0);
         const double step = kTwoPi / (double)p.n_rot;

@@ -20,6 +20,8 @@
 // and these kernels' GRAPH instantiations take acceptance and pose from the batch it left (sw_head_t) and add the zone points.
 // The matched ingest (qs_ingest_sweeps_matched*, at the end of this file) runs match.hip's kernel over the whole call and then
 // these kernels' CORR instantiations, which add each record's correction to its pose before anything else.
+// The guarded ingest (qs_ingest_sweeps_checked*, same place) runs check.hip's kernel over the whole call and then these kernels'
+// VETO instantiations, which treat a record its check contradicts as a rejected one.
 #include <math.h>
 #include <algorithm>
 
@@ -74,7 +76,8 @@ __device__ inline void sw_box_commit(SwBox b, double (*s_zone)[4], int agent, in
 // round, and writes ray slots [184 * that range) plus its row of the tile table.
 // CORR: the matched ingest's instantiation (every pose gets its record's correction first); the plain ingest's is CORR = false
 // GRAPH: graph mode's (acceptance and pose from the batch slice; path and cloud points into the bots' zone boxes)
-template <bool COUNTS, bool CORR, bool GRAPH>
+// VETO: the guarded ingest's (a record its check contradicts is a rejected record)
+template <bool COUNTS, bool CORR, bool GRAPH, bool VETO>
 __global__ void __launch_bounds__(QT_BIN_BLOCK)
 qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsigned char *__restrict__ hit_valid,
                      unsigned int *__restrict__ stamps, unsigned long long *__restrict__ counts,
@@ -102,6 +105,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
         SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
+        if (VETO) sw_veto(a, k, h);
         if (lane == 0) { sw_out(a, k, h); my.accepted += h.ok ? 1u : 0u; }
         SwBox box = sw_box(h);
         #pragma unroll
@@ -135,7 +139,7 @@ qs_sweep_rays_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, QtWorkspace ws, unsig
 }
 
 // ---- direct form: one wave per record, every cell one global atomic --------------------------------------------------------
-template <bool COUNTS, bool CORR, bool GRAPH>
+template <bool COUNTS, bool CORR, bool GRAPH, bool VETO>
 __global__ void __launch_bounds__(SW_DIRECT_BLOCK)
 qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__restrict__ stamps,
                        unsigned long long *__restrict__ counts, unsigned long long *__restrict__ counters)
@@ -156,6 +160,7 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
         const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
         SwHead h = sw_head_t<GRAPH>(a, k, s, mis);
         if (CORR) sw_correct(a, k, h);
+        if (VETO) sw_veto(a, k, h);
         if (lane == 0) { sw_out(a, k, h); my.accepted = h.ok ? 1u : 0u; }
         if (h.ok) {
             SwBox box = sw_box(h);
@@ -185,12 +190,12 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
-template <bool CORR, bool GRAPH>
+template <bool CORR, bool GRAPH, bool VETO = false>
 static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, bool tiled, unsigned char *hit_valid)
 {
     if (!tiled || !qs_tiled_supported(c)) {
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
-        qs_launch_counts(c, qs_sweep_direct_kernel<true, CORR, GRAPH>, qs_sweep_direct_kernel<false, CORR, GRAPH>, dim3(blocks),
+        qs_launch_counts(c, qs_sweep_direct_kernel<true, CORR, GRAPH, VETO>, qs_sweep_direct_kernel<false, CORR, GRAPH, VETO>, dim3(blocks),
                          dim3(SW_DIRECT_BLOCK), 0, a, c->b, c->geom, c->d_stamps.p, c->d_counts.p, c->d_counters.p);
         return hipGetLastError();
     }
@@ -204,7 +209,7 @@ static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, 
     ws.pk_per_wg = per;
     ws.rays_per_wg = QS_SWEEP_SLOTS * per;
     ws.nwg = (int)((n + per - 1) / per);
-    const auto on = qs_sweep_rays_kernel<true, CORR, GRAPH>, off = qs_sweep_rays_kernel<false, CORR, GRAPH>;
+    const auto on = qs_sweep_rays_kernel<true, CORR, GRAPH, VETO>, off = qs_sweep_rays_kernel<false, CORR, GRAPH, VETO>;
     size_t lds = 0;
     e = qt_dyn_lds(ws, (const void *)on, (const void *)off, lds);
     if (e != hipSuccess) return e;
@@ -227,7 +232,7 @@ void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_
     a.offset = c->d_offset.p; a.drift = c->d_drift.p;
     a.smin = c->sweep_min; a.smax = c->sweep_max;
     a.accept = nullptr; a.pose = nullptr; a.ord_base = 0; a.corr = nullptr;
-    a.g_accept = a.g_agent = nullptr; a.g_rx = a.g_ry = nullptr; a.zone = nullptr;
+    a.g_accept = a.g_agent = nullptr; a.g_rx = a.g_ry = nullptr; a.zone = nullptr; a.veto = nullptr;
     if (graph_k0 != QS_SWEEP_NO_GRAPH) {
         a.g_accept = c->b.accept + graph_k0; a.g_agent = c->b.agent + graph_k0;
         a.g_rx = c->b.rx + graph_k0; a.g_ry = c->b.ry + graph_k0;
@@ -236,17 +241,19 @@ void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_
 }
 
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]; corr: the
-// matched ingest's corrections of these records, nullptr for the plain ingest; graph_k0 as qs_sweep_args takes it
+// matched ingest's corrections of these records, nullptr for the plain ingest; veto: the guarded ingest's checks of them (never
+// with corr or in graph mode), nullptr otherwise; graph_k0 as qs_sweep_args takes it
 static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
                                    uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid,
-                                   const qs_sweep_match *corr, size_t graph_k0)
+                                   const qs_sweep_match *corr, const qs_sweep_check *veto, size_t graph_k0)
 {
     if (n == 0) return hipSuccess;
     QsSweepArgs a;
     qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     a.accept = accept; a.pose = pose;
     a.ord_base = qs_ord_base(c, seq0);
-    a.corr = corr;
+    a.corr = corr; a.veto = veto;
+    if (veto) return qs_launch_sweeps_t<false, false, true>(c, a, n, tiled, hit_valid);
     if (a.g_accept) return corr ? qs_launch_sweeps_t<true, true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, true>(c, a, n, tiled, hit_valid);
     return corr ? qs_launch_sweeps_t<true, false>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, false>(c, a, n, tiled, hit_valid);
 }
@@ -259,6 +266,7 @@ static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
 static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 {
     c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
+    c->last_checks = false; c->last_checks_n = 0;          // qs_last_sweep_checks: only after a guarded ingest
     c->last_sweep_graph = false;                           // qs_last_sweep_nodes: only after an ingest in graph mode
     if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
@@ -279,7 +287,7 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 
 // records [k0, k0 + m) of the call, at d_pkts (already offset to record k0); graph: the call runs in graph mode
 static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0,
-                        bool graph, const qs_sweep_match *corr)
+                        bool graph, const qs_sweep_match *corr, const qs_sweep_check *veto)
 {
     const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
     int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
@@ -288,7 +296,7 @@ static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t strid
     const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
     StageTimer t(c, QS_STAGE_RAYCAST);
     HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p,
-                               corr, graph ? k0 : QS_SWEEP_NO_GRAPH));
+                               corr, veto, graph ? k0 : QS_SWEEP_NO_GRAPH));
     t.stop();
     c->dirty_since_fuse = true;
     return QS_OK;
@@ -299,19 +307,27 @@ static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t strid
 // matched: the matched ingest (semantics in include/quasar_slam.h, "sweep matching"; params as qs_match_setup takes them): every
 // record of the call is matched against the map as it stands before the call (match.hip), then the records are mapped chunk by
 // chunk from their corrected poses.
-static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params, const uint8_t *pkts, bool host, size_t n, size_t stride,
-                         const uint16_t *lens, uint64_t seq0)
+// checked: the guarded ingest ("sweep check"; cparams as qs_check_setup takes them; never together with matched): every record of the
+// call is checked against the map as it stands before the call (check.hip), then the chunks are mapped by kernels that treat a
+// contradicted record as a rejected one.
+static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params, bool checked, const qs_check_params *cparams,
+                         const uint8_t *pkts, bool host, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0)
 {
     QsMatchSetup setup;
+    QsCheckSetup csetup;
     const QsMatchSetup *ms = matched ? &setup : nullptr;
+    const QsCheckSetup *cs = checked ? &csetup : nullptr;
     int rc = matched ? qs_match_setup(c, params, "qs_ingest_sweeps_matched", setup) : QS_OK;
+    if (rc == QS_OK && checked) rc = qs_check_setup(c, cparams, "qs_ingest_sweeps_checked", csetup);
     if (rc != QS_OK) return rc;
+    if (checked && c->sweep_graph)
+        return qs_fail(c, QS_E_STATE, "qs_ingest_sweeps_checked: not in graph mode (a withheld sweep would still be a pose-graph node)");
     rc = sweeps_begin(c, n, stride, seq0);
     if (rc != QS_OK || n == 0) return rc;
-    if (ms) {
-        HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
-        SYNCCHK(c);                                        // the matcher reads the map: waiting edge beams go in first
-    }
+    if (ms) HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
+    if (cs) HIPCHK(c, c->check_out.reserve(n, c->stream, 1024));
+    const bool pre = ms || cs;                             // a pass over the whole call before any of it is mapped
+    if (pre) SYNCCHK(c);                                   // it reads the map: waiting edge beams go in first
     // Graph mode (qs_set_sweep_graph): before any chunk is mapped or matched, the pass over the whole call that decides every
     // record, adds the nodes and runs the chain (sweep_graph.hip; a host call stages every chunk for it once more).  Every later
     // launch of the call is then told which record of the call its records start at, and reads acceptance, agent and pose from
@@ -322,11 +338,13 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
         if (rc != QS_OK) return rc;
     }
     qs_sweep_match *corr = ms ? c->match_out.p : nullptr;
+    qs_sweep_check *veto = cs ? c->check_out.p : nullptr;
     if (ms && !host) HIPCHK(c, qs_launch_match(c, *ms, pkts, n, stride, lens, corr, nullptr, graph ? 0 : QS_SWEEP_NO_GRAPH));
-    // host and matched: the staging block holds one chunk, so a call of several chunks stages each of them twice, first (pass 0)
-    // to match them all against the map nobody has written yet, then (pass 1, the only one otherwise) to map them
+    if (cs && !host) HIPCHK(c, qs_launch_check(c, *cs, pkts, n, stride, lens, veto, nullptr));
+    // host and matched or guarded: the staging block holds one chunk, so a call of several chunks stages each of them twice, first
+    // (pass 0) to match or check them all against the map nobody has written yet, then (pass 1, the only one otherwise) to map them
     const bool one = n <= QS_SWEEP_CHUNK;
-    for (int pass = (ms && host && !one) ? 0 : 1; pass < 2; pass++)
+    for (int pass = (pre && host && !one) ? 0 : 1; pass < 2; pass++)
         for (size_t k0 = 0; k0 < n; k0 += QS_SWEEP_CHUNK) {
             const size_t m = std::min(QS_SWEEP_CHUNK, n - k0);
             const uint8_t *d_pkts = pkts + k0 * stride;
@@ -340,9 +358,10 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
                 d_pkts = s.pkts; d_lens = lens ? s.lens : nullptr;
                 if (ms && (pass == 0 || one))
                     HIPCHK(c, qs_launch_match(c, *ms, d_pkts, m, stride, d_lens, corr + k0, nullptr, graph ? k0 : QS_SWEEP_NO_GRAPH));
+                if (cs && (pass == 0 || one)) HIPCHK(c, qs_launch_check(c, *cs, d_pkts, m, stride, d_lens, veto + k0, nullptr));
             }
             if (pass == 1) {
-                rc = sweeps_chunk(c, d_pkts, m, stride, d_lens, seq0, k0, graph, ms ? corr + k0 : nullptr);
+                rc = sweeps_chunk(c, d_pkts, m, stride, d_lens, seq0, k0, graph, ms ? corr + k0 : nullptr, cs ? veto + k0 : nullptr);
                 if (rc != QS_OK) return rc;
             }
         }
@@ -351,6 +370,7 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
     c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
     c->last_sweeps = true; c->last_sweeps_n = n;
     if (ms) { c->last_matches = true; c->last_matches_n = n; }
+    if (cs) { c->last_checks = true; c->last_checks_n = n; }
     // host, as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now
     return host ? sync_host_state(c, true) : QS_OK;
 }
@@ -359,14 +379,14 @@ extern "C" int qs_ingest_sweeps_device(qs_ctx *c, const uint8_t *d_pkts, size_t 
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || d_pkts != nullptr);
-    return sweeps_ingest(c, false, nullptr, d_pkts, false, n, stride, d_lens, seq0);
+    return sweeps_ingest(c, false, nullptr, false, nullptr, d_pkts, false, n, stride, d_lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps(qs_ctx *c, const uint8_t *pkts, size_t n, size_t stride, const uint16_t *lens, uint64_t seq0)
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || pkts != nullptr);
-    return sweeps_ingest(c, false, nullptr, pkts, true, n, stride, lens, seq0);
+    return sweeps_ingest(c, false, nullptr, false, nullptr, pkts, true, n, stride, lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
@@ -374,7 +394,7 @@ extern "C" int qs_ingest_sweeps_matched_device(qs_ctx *c, const qs_match_params 
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || d_pkts != nullptr);
-    return sweeps_ingest(c, true, params, d_pkts, false, n, stride, d_lens, seq0);
+    return sweeps_ingest(c, true, params, false, nullptr, d_pkts, false, n, stride, d_lens, seq0);
 }
 
 extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
@@ -382,7 +402,23 @@ extern "C" int qs_ingest_sweeps_matched(qs_ctx *c, const qs_match_params *params
 {
     ARGCHK(c, c != nullptr);
     ARGCHK(c, n == 0 || pkts != nullptr);
-    return sweeps_ingest(c, true, params, pkts, true, n, stride, lens, seq0);
+    return sweeps_ingest(c, true, params, false, nullptr, pkts, true, n, stride, lens, seq0);
+}
+
+extern "C" int qs_ingest_sweeps_checked_device(qs_ctx *c, const qs_check_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                               const uint16_t *d_lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || d_pkts != nullptr);
+    return sweeps_ingest(c, false, nullptr, true, params, d_pkts, false, n, stride, d_lens, seq0);
+}
+
+extern "C" int qs_ingest_sweeps_checked(qs_ctx *c, const qs_check_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                                        const uint16_t *lens, uint64_t seq0)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || pkts != nullptr);
+    return sweeps_ingest(c, false, nullptr, true, params, pkts, true, n, stride, lens, seq0);
 }
 
 extern "C" int qs_last_sweeps(qs_ctx *c, uint8_t *accepted, double *pose, size_t n)

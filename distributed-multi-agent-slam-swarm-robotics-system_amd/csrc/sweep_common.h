@@ -23,6 +23,7 @@ struct QsSweepArgs {
     const unsigned char *g_accept, *g_agent;
     const double *g_rx, *g_ry;
     unsigned long long *zone;     // the bots' zone boxes (the kernels' GRAPH instantiations)
+    const qs_sweep_check *veto;   // [n] guarded ingest only (the kernels' VETO instantiations): the check of each record
 };
 
 // sweep.hip: everything of a that comes from the context (filter, offsets, drift); outputs and corr empty.  graph_k0: QS_SWEEP_NO_GRAPH,
@@ -108,4 +109,10 @@ __device__ inline void sw_correct(const QsSweepArgs &a, size_t k, SwHead &h)
     if (!h.ok) return;
     const qs_sweep_match &m = a.corr[k];
     h.rx = h.rx + m.dx; h.ry = h.ry + m.dy; h.yaw = h.yaw + m.dyaw;
+}
+
+// guarded ingest: a record whose check says CONTRADICTS is withheld -- from here on it is a rejected record
+__device__ inline void sw_veto(const QsSweepArgs &a, size_t k, SwHead &h)
+{
+    if (h.ok && a.veto[k].status == QS_CHECK_CONTRADICTS) h.ok = false;
 }

@@ -274,14 +274,19 @@ class QuasarMapper:
         return xy, valid
 
     # -- servo sweeps (v0 '<4sBfffH181f' / v0 + odometry '<4sBfffiIH181f'; include/quasar_slam.h) --------------------------
-    def ingest_sweeps(self, datagrams, lengths=None, seq0=None, match=None):
+    def ingest_sweeps(self, datagrams, lengths=None, seq0=None, match=None, check=None):
         """Map servo-sweep packets: a list of bytes objects (one format: 743 or 751 bytes; other lengths are dropped) or a
         uint8 [n, 743 | 751] array with optional uint16 lengths.  Sweep k uses sequence numbers seq0 + 46 k ... + 45.
         match: True (default parameters) or what match_params takes -- every sweep of the call is first matched against
         the map as it stands and mapped from its corrected pose (qs_ingest_sweeps_matched); last_sweep_matches() has the
-        matches.  None or False: the plain ingest."""
+        matches.  None or False: the plain ingest.
+        check: True (default parameters) or what check_params takes -- every sweep of the call is first checked against the
+        map as it stands and withheld from it when it contradicts it (qs_ingest_sweeps_checked); last_sweep_checks() has the
+        checks.  Not together with match."""
+        if match not in (None, False) and check not in (None, False):
+            raise ValueError("ingest_sweeps: match and check cannot be combined")
         buf, lengths = self._sweep_buffer(datagrams, lengths)
-        return self._sweeps_call(buf, lengths, seq0, match)
+        return self._sweeps_call(buf, lengths, seq0, match, check)
 
     @staticmethod
     def _sweep_buffer(datagrams, lengths):
@@ -304,13 +309,20 @@ class QuasarMapper:
             lengths[i] = min(len(d), 65535)
         return buf, lengths
 
-    def _sweeps_call(self, buf, lengths, seq0, match=None):
+    def _sweeps_call(self, buf, lengths, seq0, match=None, check=None):
         n, stride = buf.shape
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
         if lens is not None and len(lens) != n:
             raise ValueError("lengths must have one entry per record")
         seq = UINT64_MAX if seq0 is None else int(seq0)
-        if match is None or match is False:
+        self._last_checks_n = None
+        if check is not None and check is not False:
+            prm = self.check_params(check)
+            self._chk(self._L.qs_ingest_sweeps_checked(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens), seq),
+                      "qs_ingest_sweeps_checked")
+            self._last_matches_n = None
+            self._last_checks_n = n
+        elif match is None or match is False:
             self._chk(self._L.qs_ingest_sweeps(self._h, _ptr(buf) if n else None, n, stride, _ptr(lens), seq), "qs_ingest_sweeps")
             self._last_matches_n = None
         else:
@@ -332,6 +344,7 @@ class QuasarMapper:
         self._last_n = 0
         self._last_sweeps_n = n
         self._last_matches_n = None
+        self._last_checks_n = None
 
     # -- sweeps in the pose graph (include/quasar_slam.h, "sweeps in the pose graph") ---------------------------------------------
     @staticmethod
@@ -451,12 +464,73 @@ class QuasarMapper:
         self._last_n = 0
         self._last_sweeps_n = n
         self._last_matches_n = n
+        self._last_checks_n = None
 
     def last_sweep_matches(self):
         """The matches of the last matched sweep ingest (protocol.MATCH_DTYPE [n]); an error after any other ingest."""
         n = getattr(self, "_last_matches_n", None)
         out = np.zeros(n or 0, dtype=P.MATCH_DTYPE)
         self._chk(self._L.qs_last_sweep_matches(self._h, _ptr(out) if n else None, n or 0), "qs_last_sweep_matches")
+        return out
+
+    # -- sweep check (include/quasar_slam.h, "sweep check") -------------------------------------------------------------------
+    def check_params(self, params=None, **kw):
+        """A qs_check_params from None / True (the defaults of protocol.CHECK_*; tol = CHECK_TOL_CELLS cells of this grid), a dict
+        of its fields, or one already built."""
+        if isinstance(params, _lib.QsCheckParams):
+            return params
+        d = dict(tol=P.CHECK_TOL_CELLS * self.res, min_checked=P.CHECK_MIN_CHECKED, max_bad_percent=P.CHECK_MAX_BAD_PERCENT,
+                 count_missed=P.CHECK_COUNT_MISSED)
+        if isinstance(params, dict):
+            d.update(params)
+        elif params not in (None, True):
+            raise TypeError("check parameters: None, True, a dict or a QsCheckParams")
+        d.update(kw)
+        return _lib.QsCheckParams(tol=float(d["tol"]), min_checked=int(d["min_checked"]), max_bad_percent=int(d["max_bad_percent"]),
+                                  count_missed=int(d["count_missed"]), reserved=int(d.get("reserved", 0)))
+
+    def check_sweeps(self, datagrams, lengths=None, params=None, classes=False):
+        """Check sweeps (as ingest_sweeps takes them) against the map without mapping them or changing anything: a structured
+        array of protocol.CHECK_DTYPE, one entry per record; with classes also every beam's class, uint8 [n, 181]
+        (protocol.BEAM_*; BEAM_NO_RECORD throughout for a record that is not accepted)."""
+        buf, lengths = self._sweep_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        prm = self.check_params(params)
+        out = np.zeros(n, dtype=P.CHECK_DTYPE)
+        cls = np.zeros((n, P.SWEEP_BEAMS), dtype=np.uint8) if classes else None
+        self._chk(self._L.qs_check_sweeps(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                          _ptr(out) if n else None, _ptr(cls) if classes and n else None), "qs_check_sweeps")
+        return (out, cls) if classes else out
+
+    def check_sweeps_device(self, d_pkts, n, stride, d_out, d_lens=0, d_cls=0, params=None):
+        """Device-resident check (raw device addresses as ints; d_out: n records of protocol.CHECK_DTYPE, d_cls: n x 181
+        bytes); asynchronous."""
+        prm = self.check_params(params)
+        self._chk(self._L.qs_check_sweeps_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                 C.c_void_p(d_lens) if d_lens else None, C.c_void_p(d_out),
+                                                 C.c_void_p(d_cls) if d_cls else None), "qs_check_sweeps_device")
+
+    def ingest_sweeps_checked_device(self, d_pkts, n, stride, d_lens=0, seq0=None, params=None):
+        """Device-resident guarded ingest (raw device addresses as ints); asynchronous."""
+        prm = self.check_params(params)
+        self._chk(self._L.qs_ingest_sweeps_checked_device(self._h, C.byref(prm), C.c_void_p(d_pkts), n, stride,
+                                                          C.c_void_p(d_lens) if d_lens else None,
+                                                          UINT64_MAX if seq0 is None else int(seq0)),
+                  "qs_ingest_sweeps_checked_device")
+        self._map_version += 1
+        self._last_n = 0
+        self._last_sweeps_n = n
+        self._last_matches_n = None
+        self._last_checks_n = n
+
+    def last_sweep_checks(self):
+        """The checks of the last guarded sweep ingest (protocol.CHECK_DTYPE [n]); an error after any other ingest."""
+        n = getattr(self, "_last_checks_n", None)
+        out = np.zeros(n or 0, dtype=P.CHECK_DTYPE)
+        self._chk(self._L.qs_last_sweep_checks(self._h, _ptr(out) if n else None, n or 0), "qs_last_sweep_checks")
         return out
 
     # -- relocalisation (include/quasar_slam.h, "relocalisation") -------------------------------------------------------------

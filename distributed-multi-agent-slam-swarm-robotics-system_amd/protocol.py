@@ -162,6 +162,17 @@ GROUP_RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("scor
                               ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
                               ("records", "u1"), ("accepted", "u1"), ("pad", "u1", (6,)),
                               ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8")])
+# sweep check (include/quasar_slam.h, "sweep check"): build choices taken from a CPU prototype of the rule
+CHECK_TOL_CELLS = 2          # tol defaults to this many cells
+CHECK_MIN_CHECKED = 20       # a sweep with fewer decided beams is UNDECIDED
+CHECK_MAX_BAD_PERCENT = 30   # more than this share of the decided beams contradicting the map: CONTRADICTS
+CHECK_COUNT_MISSED = 0       # a wall the sweep did not return is not held against it (glass, dropouts)
+CHECK_LOST_AFTER = 5         # MissionControl: consecutive contradicted sweeps after which a bot counts as lost
+BEAM_AGREE, BEAM_NEARER, BEAM_FARTHER, BEAM_MISSED, BEAM_UNSEEN, BEAM_NO_RECORD = 0, 1, 2, 3, 4, 255
+CHECK_OK, CHECK_NO_RECORD, CHECK_UNDECIDED, CHECK_CONTRADICTS = 0, 1, 2, 3
+CHECK_DTYPE = np.dtype([("agree", "<i4"), ("nearer", "<i4"), ("farther", "<i4"), ("missed", "<i4"), ("unseen", "<i4"),
+                        ("checked", "<i4"), ("bad", "<i4"), ("status", "<i4"), ("accepted_record", "u1"), ("pad", "u1", (7,)),
+                        ("sin_yaw", "<f8"), ("cos_yaw", "<f8")])
 
 
 def reloc_rel(x, y, yaw, anchor=0):

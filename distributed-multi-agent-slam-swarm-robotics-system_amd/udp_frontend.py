@@ -52,6 +52,13 @@ are kept, up to K, those whose pose lies within `travel` of the first kept one; 
 relocalised as one group whose frame is the first kept record.  On acceptance the transform is set from that record's ingest
 pose, as above, and the copies are dropped; after K records without acceptance the front-end gives up on that bot until it is
 next found offline.  Sweeps are ingested meanwhile as they arrive.  reloc_stats then also counts group_tried / gave_up.
+With check_sweeps=True or a dict of check parameters plus lost_after (opt-in, needs sweeps=True, excludes sweep_graph and
+match_sweeps) a run of sweeps goes through the guarded ingest (QuasarMapper.ingest_sweeps(check=...)): a sweep that contradicts
+the map is withheld from it.  last_checks holds the checks of the latest run, check_stats counts checked / withheld / undecided,
+suspect[bot] is the bot's run of consecutive contradicted sweeps (an OK sweep resets it, an undecided one leaves it).  A withheld
+sweep still counts for the heartbeat; it does not move the bot's pose.  With relocalise also on, a bot whose run reaches
+lost_after (default CHECK_LOST_AFTER) loses its transform and is relocalised from its next sweep on exactly as a bot found
+offline is, group mode included, until a relocalisation is accepted.
 With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
 point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
 poses; mapper.MapView.frame draws them.
@@ -74,7 +81,7 @@ class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
-                 targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False):
+                 targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False, check_sweeps=False):
         by = [k for k, on in (("targets_by_path", targets_by_path), ("targets_by_territory", targets_by_territory),
                               ("targets_by_gain", targets_by_gain)) if on]
         if not frontier_targets and (plan_paths or by):         # each of them refines frontier_targets
@@ -91,6 +98,18 @@ class MissionControl:
             raise ValueError("MissionControl: relocalise needs sweeps=True")
         if self.relocalise and self.sweep_graph:
             raise ValueError("MissionControl: relocalise excludes sweep_graph (a closure's drift would move under the transform)")
+        self.check_sweeps = check_sweeps is not False and check_sweeps is not None      # ({} is on, with the defaults)
+        if self.check_sweeps and not sweeps:
+            raise ValueError("MissionControl: check_sweeps needs sweeps=True")
+        if self.check_sweeps and self.sweep_graph:
+            raise ValueError("MissionControl: check_sweeps excludes sweep_graph (a withheld sweep would still be a node)")
+        if self.check_sweeps and match_sweeps:
+            raise ValueError("MissionControl: check_sweeps excludes match_sweeps (the guarded and the matched ingest do not combine)")
+        self.check_params = dict(check_sweeps) if isinstance(check_sweeps, dict) else True
+        self.lost_after = int(self.check_params.pop("lost_after")) if self.check_params is not True and "lost_after" in self.check_params \
+            else P.CHECK_LOST_AFTER
+        if self.lost_after < 1:
+            raise ValueError("MissionControl: check_sweeps['lost_after'] must be at least 1")
         if self.sweep_graph:
             mapper.set_sweep_graph(True, **(dict(sweep_graph) if isinstance(sweep_graph, dict) else {}))
         self.reloc_params = dict(relocalise) if isinstance(relocalise, dict) else True
@@ -108,6 +127,10 @@ class MissionControl:
         if self.reloc_group:
             self.reloc_stats.update(group_tried=0, gave_up=0)
         self._reloc_T = {}                           # bot -> (cos, sin, dyaw, ingest x, y, found x, y, shift x, y)
+        self.check_stats = {"checked": 0, "withheld": 0, "undecided": 0}
+        self.suspect = {b: 0 for b in range(1, max_agent + 1)}     # bot -> its run of consecutive contradicted sweeps
+        self._lost = set()                           # bots whose run reached lost_after: relocalised as a bot found offline is
+        self.last_checks = None
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
         self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
@@ -193,11 +216,37 @@ class MissionControl:
                 if self.match_sweeps:
                     self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens, match=self.match_params)
                     self.last_matches = self.mapper.last_sweep_matches()
+                elif self.check_sweeps:
+                    self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens, check=self.check_params)
+                    self.last_checks = self.mapper.last_sweep_checks()
                 else:
                     self.mapper.ingest_sweeps(self._buf[i0:i1, :kind], lens)
                 accepted, pose = self.mapper.last_sweeps()
                 self._mark(i0, accepted, pose, now, pose is not None)
+                if self.check_sweeps:
+                    self._note_checks(i0, self.last_checks, now)
         return n
+
+    def _note_checks(self, i0, checks, now):
+        """check_sweeps: the checks of one guarded ingest whose first datagram is slot i0, in arrival order.  A withheld sweep
+        still shows that its bot is there (address, heartbeat) but leaves its pose alone; a bot whose run of contradicted sweeps
+        reaches lost_after loses its transform and is relocalised from its next sweep on, as a bot found offline is."""
+        status = np.asarray(checks["status"])
+        self._mark(i0, status == P.CHECK_CONTRADICTS, None, now, False)
+        for j in np.nonzero(status != P.CHECK_NO_RECORD)[0]:
+            a = int(self._buf[i0 + int(j), 4])
+            self.check_stats["checked"] += 1
+            if status[j] == P.CHECK_UNDECIDED:
+                self.check_stats["undecided"] += 1
+            elif status[j] == P.CHECK_OK:
+                self.suspect[a] = 0
+            else:
+                self.check_stats["withheld"] += 1
+                self.suspect[a] += 1
+                if self.relocalise and self.suspect[a] >= self.lost_after and a not in self._lost:
+                    self._lost.add(a)
+                    self._reloc_T.pop(a, None)
+                    self._reloc_kept.pop(a, None)
 
     def _runs(self, n):
         """Maximal runs of one kind in arrival order: (first, end, 0 for packets | the sweep stride)."""
@@ -218,7 +267,7 @@ class MissionControl:
         first = {}
         for j in idx:
             a = int(run[j, 4])
-            if not self.online[a] and a not in first:
+            if (not self.online[a] or a in self._lost) and a not in first:
                 first[a] = int(j)
         shift_of = getattr(self.mapper, "sweep_pose_shift", None)
         located = []                                 # (bot, the record whose ingest pose the transform starts from, the result)
@@ -237,6 +286,9 @@ class MissionControl:
             self._reloc_T[a] = (np.cos(dyaw), np.sin(dyaw), dyaw, x + sx, y + sy, float(r["x"]), float(r["y"]), sx, sy)
             self.relocalised[a] = r.copy()
             self.reloc_stats["accepted"] += 1
+            if a in self._lost:                      # (check_sweeps) located again: its run starts anew
+                self._lost.discard(a)
+                self.suspect[a] = 0
         for j in idx:
             T = self._reloc_T.get(int(run[j, 4]))
             if T is None:

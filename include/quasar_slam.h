@@ -900,6 +900,80 @@ int qs_sense_packets_device(qs_ctx *ctx, const float *d_pose_xyyaw, const uint8_
                             const uint32_t *d_v2v, const uint8_t *d_landmark, size_t n, const qs_sense_params *params,
                             uint8_t *d_pkts_out);
 
+/* ---- sweep check: does a sweep fit the map it is about to be written into? (no reference counterpart: this build's own rule) ----
+ * Every beam of a sweep is predicted from the map by the walk of "sensing a world" and compared with the range the sweep carries;
+ * a sweep most of whose decided beams contradict the map can be withheld from it (qs_ingest_sweeps_checked).  All comparisons
+ * are integer or uncontracted fp64, so a NumPy restatement (tests/check_rules.py) agrees bit for bit once it is given the one
+ * sincos the device takes per record.
+ *  V1 Map: stamp 0 is UNKNOWN, an odd stamp OCCUPIED, anything else FREE; a cell outside the grid reads UNKNOWN.  The call
+ *     observes the map (waiting exact-trig rays are resolved first) and writes nothing to the context: no stamps, counters,
+ *     dirty blocks or sequence numbers; a checkpoint before equals one after.
+ *  V2 Record and pose: acceptance is qs_ingest_sweeps' rule; rx, ry, yaw are formed exactly as that ingest forms them (offset
+ *     first, then the bot's drift, read on the device; graph mode does not change them).  The pose is usable when all three are
+ *     finite and both start cells (x0, y0) = world_to_grid(rx), world_to_grid(ry) exist (S2's bound).  Otherwise all 181 beams
+ *     are UNSEEN and sin_yaw = cos_yaw = 0.
+ *  V3 Directions: (s, c) = the device's sincos(yaw), once per record, reported as sin_yaw, cos_yaw.  Beam i points along
+ *     c_i = c * CB[i] - s * SB[i], s_i = s * CB[i] + c * SB[i]; CB, SB are the host-libm tables of sweep-matching rule 3.
+ *  V4 Prediction: far point (rx + smax * c_i, ry + smax * s_i), one multiply and one add per axis; its cell (x1, y1) is
+ *     world_to_grid of it.  No cell, or a cell more than C = ceil(smax / res) + 1 cells from the start cell on either axis (only
+ *     rounding at astronomic coordinates can do that): the beam is UNSEEN.  Otherwise walk the cells of the reference's
+ *     _bresenham((x0, y0), (x1, y1)) (:158-179) after cell 0, from the pose outward.  The first cell that is not FREE ends the
+ *     walk: OCCUPIED gives "hit at p", UNKNOWN (off-grid included) gives "unknown at p", with
+ *     p = res * sqrt(f64(dx*dx + dy*dy)), centre to centre.  A walk that reaches the far cell over FREE cells only is "clear".
+ *  V5 Measurement: d = the f32 range widened.  It is a return when smin < d <= smax (the context's sweep filter), otherwise none.
+ *  V6 Class of a beam (each test is one fp64 operation followed by one compare; tol in metres):
+ *         prediction      return d                                             none
+ *         hit at p        d < p - tol: NEARER;  d > p + tol: FARTHER;          MISSED if smin + tol < p and p <= smax - tol,
+ *                         else AGREE                                           else UNSEEN
+ *         clear           NEARER                                               AGREE
+ *         unknown at p    d < p - tol: NEARER;  else UNSEEN                    UNSEEN
+ *  V7 Summary: the five counts sum to 181; checked = agree + nearer + farther + missed;
+ *     bad = nearer + farther + (count_missed ? missed : 0).  status: QS_CHECK_NO_RECORD for a rejected record (every field of
+ *     the result is zero); QS_CHECK_UNDECIDED when checked < min_checked; QS_CHECK_CONTRADICTS when
+ *     bad * 100 > max_bad_percent * checked; QS_CHECK_OK otherwise.
+ *  V8 Parameters: NULL = tol 2 * res, min_checked 20, max_bad_percent 30, count_missed 0.  Limits: tol finite and >= 0,
+ *     min_checked in 0..181, max_bad_percent in 0..100, count_missed 0 or 1, reserved 0, and
+ *     ceil(smax / res) + 1 <= QS_SENSE_MAX_CELLS for the context's sweep filter; QS_E_INVAL otherwise, the text names the field.
+ *     Stride, lengths and refusals are those of qs_match_sweeps (a sharded context refuses).  n == 0 is valid; any n is accepted
+ *     (host calls are chunked internally).
+ *  V9 Result: one qs_sweep_check per record (pad is zero) and, optionally, cls_out uint8 [n][181]: the class of every beam,
+ *     255 throughout for a rejected record.
+ * qs_ingest_sweeps_checked*: ALL records of the call are checked (parameters as above) against the map as it stood before the
+ * call, however the call is chunked.  A record whose status is QS_CHECK_CONTRADICTS is WITHHELD: from there on it is treated
+ * exactly as a rejected record -- it writes nothing, keeps its 46 sequence numbers, counts in QS_CNT_DATAGRAMS but not in
+ * QS_CNT_ACCEPTED, and qs_last_sweeps shows accepted = 0 and a NaN pose.  OK and UNDECIDED records are mapped by
+ * qs_ingest_sweeps' rules (an empty map decides nothing, so it withholds nothing).  qs_last_sweep_checks returns the checks
+ * (n = the call's n; QS_E_INVAL after any other ingest).  In graph mode the guarded ingest refuses with QS_E_STATE (a withheld
+ * sweep would still be a node); qs_check_sweeps itself works in either mode.
+ * Not built: a guarded AND matched ingest, a check of the 42-byte packets' four beams, beam width, any use of the hit / miss
+ * counters (the stamp's latest word decides, as everywhere else). */
+#define QS_BEAM_AGREE 0
+#define QS_BEAM_NEARER 1
+#define QS_BEAM_FARTHER 2
+#define QS_BEAM_MISSED 3
+#define QS_BEAM_UNSEEN 4
+#define QS_BEAM_NO_RECORD 255
+#define QS_CHECK_OK 0
+#define QS_CHECK_NO_RECORD 1
+#define QS_CHECK_UNDECIDED 2
+#define QS_CHECK_CONTRADICTS 3
+typedef struct qs_check_params { double tol; int32_t min_checked, max_bad_percent, count_missed, reserved; } qs_check_params;
+typedef struct qs_sweep_check {
+    int32_t agree, nearer, farther, missed, unseen, checked, bad, status;
+    uint8_t accepted_record, pad[7];
+    double  sin_yaw, cos_yaw;
+} qs_sweep_check;
+int qs_check_sweeps(qs_ctx *ctx, const qs_check_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                    const uint16_t *lens, qs_sweep_check *out, uint8_t *cls_out);
+/* same with device-resident pkts / lens / out / cls_out; asynchronous on the context's stream */
+int qs_check_sweeps_device(qs_ctx *ctx, const qs_check_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                           const uint16_t *d_lens, qs_sweep_check *d_out, uint8_t *d_cls_out);
+int qs_ingest_sweeps_checked(qs_ctx *ctx, const qs_check_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                             const uint16_t *lens, uint64_t seq0);
+int qs_ingest_sweeps_checked_device(qs_ctx *ctx, const qs_check_params *params, const uint8_t *d_pkts, size_t n,
+                                    size_t stride, const uint16_t *d_lens, uint64_t seq0);
+int qs_last_sweep_checks(qs_ctx *ctx, qs_sweep_check *out, size_t n);
+
 /* ---- map view: the "Mission Control" map, MapRenderer  dual_bot_mapper.py:380-668 -------------------------------------------
  * One call renders a frame of the map for any pan and zoom on the device and hands back only the frame: [height][width][4]
  * bytes R, G, B, 255, row 0 at the top.  The layers are the reference's (:433-468) as far as its own Python pins their pixels

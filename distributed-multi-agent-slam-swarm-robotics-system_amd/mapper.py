@@ -315,21 +315,20 @@ class QuasarMapper:
         if lens is not None and len(lens) != n:
             raise ValueError("lengths must have one entry per record")
         seq = UINT64_MAX if seq0 is None else int(seq0)
-        self._last_checks_n = None
+        # (what the last ingest was changes only once the library has taken the call: a refused one leaves it)
         if check is not None and check is not False:
             prm = self.check_params(check)
             self._chk(self._L.qs_ingest_sweeps_checked(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens), seq),
                       "qs_ingest_sweeps_checked")
-            self._last_matches_n = None
-            self._last_checks_n = n
+            self._last_matches_n, self._last_checks_n = None, n
         elif match is None or match is False:
             self._chk(self._L.qs_ingest_sweeps(self._h, _ptr(buf) if n else None, n, stride, _ptr(lens), seq), "qs_ingest_sweeps")
-            self._last_matches_n = None
+            self._last_matches_n, self._last_checks_n = None, None
         else:
             prm = self.match_params(match)
             self._chk(self._L.qs_ingest_sweeps_matched(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens), seq),
                       "qs_ingest_sweeps_matched")
-            self._last_matches_n = n
+            self._last_matches_n, self._last_checks_n = n, None
         self._map_version += 1
         self._last_n = 0
         self._last_sweeps_n = n

@@ -12,24 +12,7 @@ import time
 import numpy as np
 
 from conftest import PKG_NAME, ROOT
-
-
-def greedy(cents, bots, sep):
-    """dual_bot_mapper.py:958-992 restated: bots in order; skip taken centroids and those within `sep` of an earlier
-    target; the smallest sqrt distance by strict `<` from inf wins (ties: lowest index)."""
-    targets, out = [], []
-    for bx, by in bots:
-        best, bi = math.inf, -1
-        for i, (cx, cy) in enumerate(cents):
-            if any(i == ti or math.sqrt((cx - tx) * (cx - tx) + (cy - ty) * (cy - ty)) < sep for ti, tx, ty in targets):
-                continue
-            d = math.sqrt((bx - cx) * (bx - cx) + (by - cy) * (by - cy))
-            if d < best:
-                best, bi = d, i
-        out.append(bi)
-        if bi >= 0:
-            targets.append((bi, cents[bi][0], cents[bi][1]))
-    return out
+from walk_ops import greedy
 
 
 class StubMapper:

@@ -15,6 +15,7 @@ import torch  # before the HIP library: torch bundles its own HIP runtime, and w
 import match_rules as MR
 from conftest import GOLDEN, load_pkg
 from oracle import oracle as orc
+from walk_ops import corrected as _corrected
 
 pytestmark = pytest.mark.gpu
 
@@ -217,14 +218,6 @@ def test_match_writes_nothing(pkg):
         assert len(acc) == 5
         with pytest.raises(pkg.QuasarError):
             m.last_sweep_matches()
-
-
-def _corrected(pose, acc, mt):
-    out = pose.copy()
-    out[:, 0] = pose[:, 0] + mt["dx"]
-    out[:, 1] = pose[:, 1] + mt["dy"]
-    out[:, 2] = pose[:, 2] + mt["dyaw"]
-    return out[acc]
 
 
 def _same_map(m, o, tag):

@@ -12,6 +12,7 @@ import torch  # before the HIP library: torch bundles its own HIP runtime, and w
 
 from conftest import GOLDEN, load_pkg
 from oracle import oracle as orc
+from walk_ops import sweep_beams as _beams
 
 pytestmark = pytest.mark.gpu
 SMIN, SMAX = 0.1, 1.2
@@ -29,29 +30,6 @@ def _P(pkg):
 def _records(P, buf):
     dt = P.PACKET_DTYPE_V0 if buf.shape[1] == P.PACKET_SIZE_V0 else P.PACKET_DTYPE_V0_ODO
     return np.ascontiguousarray(buf).view(dt).reshape(-1)
-
-
-def _beams(recs, offset=None, drift=None, smin=SMIN, smax=SMAX, max_agent=2):
-    """(rx, ry, hx, hy, valid) of every beam of every acceptable record, in order -- the reference's arithmetic in Python."""
-    offset = offset or {}
-    drift = drift or {}
-    out = ([], [], [], [], [])
-    for r in recs:
-        a_id = int(r["agent"])
-        if r["magic"] != b"QSRL" or not 1 <= a_id <= max_agent:
-            continue
-        dx, dy = drift.get(a_id, (0.0, 0.0))
-        px = float(r["x"]) + offset.get(a_id, 0.0) + dx
-        py = float(r["y"]) + dy
-        yaw = float(r["yaw"])
-        for i, d in enumerate(r["ranges"].tolist()):
-            a = yaw + math.radians(i - 90)
-            ok = smin < d <= smax
-            L = d if ok else (min(d, smax) if d > smin else smax)
-            out[0].append(px); out[1].append(py)
-            out[2].append(px + L * math.cos(a)); out[3].append(py + L * math.sin(a))
-            out[4].append(1 if ok else 0)
-    return [np.array(v, dtype=np.float64) for v in out[:4]] + [np.array(out[4], dtype=np.uint8)]
 
 
 def _same_map(m, o, tag):

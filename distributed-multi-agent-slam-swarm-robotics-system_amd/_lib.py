@@ -107,6 +107,17 @@ class QsGroupReloc(C.Structure):
                 ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
 
 
+class QsTrailMatch(C.Structure):
+    """struct qs_trail_match (include/quasar_slam.h)."""
+    _fields_ = [("ix", C.c_int32), ("iy", C.c_int32), ("it", C.c_int32), ("score", C.c_int32), ("score0", C.c_int32),
+                ("hits", C.c_int32), ("records", C.c_int32), ("anchor", C.c_int32), ("agent", C.c_uint8),
+                ("accepted_match", C.c_uint8), ("pad", C.c_uint8 * 6),
+                ("ax", C.c_double), ("ay", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("dyaw", C.c_double)]
+
+
+QS_TRAIL_MAX_RECORDS = 64                                                        # include/quasar_slam.h, "trail matching"
+
+
 class QsMergeResult(C.Structure):
     """struct qs_merge_result (include/quasar_slam.h)."""
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_local", C.c_uint64), ("n_global", C.c_uint64),
@@ -202,6 +213,8 @@ SIGNATURES = {
     "qs_relocalise_sweeps_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "qs_relocalise_groups": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.c_double, _vp]),
     "qs_relocalise_groups_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.c_double, _vp]),
+    "qs_match_trails": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
+    "qs_match_trails_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
     "qs_sense_ranges": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_ranges_device": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_sweeps": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),

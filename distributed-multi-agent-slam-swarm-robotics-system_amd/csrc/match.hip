@@ -123,6 +123,7 @@ qs_match_kernel(QsSweepArgs a, QsGeom geo, QsMatchArgs m)
     __syncthreads();
 
     // ---- scores: a lane per (rotation, iy, four ix) --------------------------------------------------------------------------
+    // (qs_trail_kernel, trail.hip, restates this loop over a trail's points: a change here belongs there too)
     const int ny = 2 * m.W + 1, G = (ny + 3) >> 2, per_rot = ny * G, NI = nrot * per_rot;
     const int span = (255 / (m.R + 1)) & ~3;                       // beams whose byte sums cannot overflow
     unsigned long long best = 0;
@@ -202,18 +203,24 @@ qs_match_field_kernel(const unsigned int *__restrict__ stamps, int size, int R, 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
+const char *qs_match_params_check(const qs_match_params *params, qs_match_params &p)
+{
+    p = qs_match_params{2, 6, 10, 20, 50, 0, 3.141592653589793 / 180.0};
+    if (params) p = *params;
+    if (p.radius < 0 || p.radius > QS_MATCH_MAX_RADIUS) return "radius must lie in [0, QS_MATCH_MAX_RADIUS]";
+    if (p.window < 0) return "window must not be negative";
+    if (p.angle_steps < 0 || p.angle_steps > QS_MATCH_MAX_ANGLE_STEPS) return "angle_steps must lie in [0, QS_MATCH_MAX_ANGLE_STEPS]";
+    if (p.min_hits < 0) return "min_hits must not be negative";
+    if (p.min_percent < 0 || p.min_percent > 100) return "min_percent must lie in [0, 100]";
+    if (!(isfinite(p.angle_step) && p.angle_step >= 0)) return "angle_step must be finite and not negative";
+    return nullptr;
+}
+
 int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, QsMatchSetup &ms)
 {
-    qs_match_params p = {2, 6, 10, 20, 50, 0, 3.141592653589793 / 180.0};
-    if (params) p = *params;
+    qs_match_params p;
     char msg[256];
-    const char *bad = nullptr;
-    if (p.radius < 0 || p.radius > QS_MATCH_MAX_RADIUS) bad = "radius must lie in [0, QS_MATCH_MAX_RADIUS]";
-    else if (p.window < 0) bad = "window must not be negative";
-    else if (p.angle_steps < 0 || p.angle_steps > QS_MATCH_MAX_ANGLE_STEPS) bad = "angle_steps must lie in [0, QS_MATCH_MAX_ANGLE_STEPS]";
-    else if (p.min_hits < 0) bad = "min_hits must not be negative";
-    else if (p.min_percent < 0 || p.min_percent > 100) bad = "min_percent must lie in [0, 100]";
-    else if (!(isfinite(p.angle_step) && p.angle_step >= 0)) bad = "angle_step must be finite and not negative";
+    const char *bad = qs_match_params_check(params, p);
     const double reach = ceil(c->sweep_max / c->cfg.res);
     if (!bad && !(reach + p.radius + 2 <= QS_MATCH_MAX_REACH))
         bad = "the sweep filter's smax is too large for this resolution: ceil(smax / res) + radius + 2 exceeds QS_MATCH_MAX_REACH";

@@ -452,6 +452,9 @@ int qs_sweep_graph_pass(qs_ctx *c, const uint8_t *pkts, bool host, size_t n, siz
 // match.hip: the parameters of one matching call, checked against the context's sweep filter and resolution
 struct QsMatchSetup { int R, W, T, min_hits, min_percent, reach; double step; };
 int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, QsMatchSetup &ms);
+// the limits of qs_match_params alone, shared with trail matching (trail.hip): p = *params or the defaults; the text of the
+// first limit broken, or nullptr
+const char *qs_match_params_check(const qs_match_params *params, qs_match_params &p);
 // n device-resident records matched against the map as the stream finds it; rot (optional): [n][2 T + 1][2] the (sin, cos) used;
 // graph_k0 as qs_sweep_args takes it (sweep_common.h): QS_SWEEP_NO_GRAPH, or the record of a graph-mode call the n records start at
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,

@@ -611,6 +611,45 @@ class QuasarMapper:
                                                       _ptr(gs) if len(gs) else None, len(gs), float(travel), C.c_void_p(d_out)),
                   "qs_relocalise_groups_device")
 
+    # -- trail matching (include/quasar_slam.h, "trail matching") ---------------------------------------------------------------
+    def match_trails(self, datagrams, gsize, lengths=None, travel=P.TRAIL_TRAVEL, params=None, rotations=False):
+        """Match trails of 42-byte packets against the map without mapping them or changing anything: packets (as ingest /
+        ingest_array take them) in runs of gsize[g], each run the last packets of one bot in arrival order; a structured array
+        of protocol.TRAIL_MATCH_DTYPE, one entry per trail (protocol.trail_move applies one).  params: what match_params
+        takes.  With rotations also the (sin, cos) of each record's yaw as the device formed them, float64 [n, 2]."""
+        if isinstance(datagrams, np.ndarray):
+            buf = np.ascontiguousarray(datagrams, dtype=np.uint8)
+            if buf.ndim != 2:
+                raise ValueError("packets must be [n, stride]")
+        elif len(datagrams) == 0:
+            buf = np.zeros((0, P.PACKET_SIZE), np.uint8)
+        elif all(len(d) == P.PACKET_SIZE for d in datagrams):
+            buf = np.frombuffer(b"".join(datagrams), dtype=np.uint8).reshape(-1, P.PACKET_SIZE)
+        else:
+            buf, lengths = P.pack_datagrams(datagrams)
+        n, stride = buf.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
+        if lens is not None and len(lens) != n:
+            raise ValueError("lengths must have one entry per record")
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        prm = self.match_params(params)
+        out = np.zeros(len(gs), dtype=P.TRAIL_MATCH_DTYPE)
+        rot = np.zeros((n, 2), dtype=np.float64) if rotations else None
+        self._chk(self._L.qs_match_trails(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                          _ptr(gs) if len(gs) else None, len(gs), float(travel), _ptr(out) if len(gs) else None,
+                                          _ptr(rot) if rotations and n else None), "qs_match_trails")
+        return (out, rot) if rotations else out
+
+    def match_trails_device(self, d_pkts, n, stride, gsize, d_out, d_lens=0, d_rot=0, travel=P.TRAIL_TRAVEL, params=None):
+        """Device-resident form (raw device addresses as ints; d_out: len(gsize) records of protocol.TRAIL_MATCH_DTYPE, d_rot:
+        float64 [n, 2] or 0; gsize a host array); asynchronous."""
+        prm = self.match_params(params)
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        self._chk(self._L.qs_match_trails_device(self._h, C.byref(prm), C.c_void_p(d_pkts) if d_pkts else None, n, stride,
+                                                 C.c_void_p(d_lens) if d_lens else None, _ptr(gs) if len(gs) else None, len(gs),
+                                                 float(travel), C.c_void_p(d_out) if d_out else None,
+                                                 C.c_void_p(d_rot) if d_rot else None), "qs_match_trails_device")
+
     def last_sweeps(self):
         """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after
         offset and drift, yaw); NaN for rejected records."""

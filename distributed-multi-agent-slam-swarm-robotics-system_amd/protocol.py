@@ -162,6 +162,13 @@ GROUP_RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("scor
                               ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
                               ("records", "u1"), ("accepted", "u1"), ("pad", "u1", (6,)),
                               ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8")])
+# trail matching (include/quasar_slam.h, T1-T8): the last packets of one bot matched against the map as one rigid constellation
+TRAIL_MAX_RECORDS = 64
+TRAIL_TRAVEL = 4.0           # metres a record of a trail may lie from the trail's last pose
+TRAIL_MATCH_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("it", "<i4"), ("score", "<i4"), ("score0", "<i4"), ("hits", "<i4"),
+                              ("records", "<i4"), ("anchor", "<i4"), ("agent", "u1"), ("accepted_match", "u1"), ("pad", "u1", (6,)),
+                              ("ax", "<f8"), ("ay", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dyaw", "<f8")])
+assert TRAIL_MATCH_DTYPE.itemsize == 80
 # sweep check (include/quasar_slam.h, "sweep check"): build choices taken from a CPU prototype of the rule
 CHECK_TOL_CELLS = 2          # tol defaults to this many cells
 CHECK_MIN_CHECKED = 20       # a sweep with fewer decided beams is UNDECIDED
@@ -189,6 +196,18 @@ def reloc_rel(x, y, yaw, anchor=0):
         d = float(yaw[k]) - float(yaw[anchor])
         out[k] = (c0 * dx + s0 * dy, c0 * dy - s0 * dx, math.sin(d), math.cos(d))
     return out
+
+
+def trail_move(match, x, y, yaw):
+    """Rule T7's transform: where a pose (x, y, yaw) of the matched bot -- in the frame of T3, offset and drift included --
+    lies after the correction of `match` (one TRAIL_MATCH_DTYPE record, or anything with ax, ay, dx, dy, dyaw): the turn by dyaw
+    about the anchor (ax, ay), then the shift.  Scalars or arrays; fp64 with libm.  An unaccepted match (dx = dy = dyaw = 0)
+    leaves the pose where it is."""
+    ax, ay, dx, dy, dyaw = (float(match[k]) for k in ("ax", "ay", "dx", "dy", "dyaw"))
+    s, c = math.sin(dyaw), math.cos(dyaw)
+    x, y, yaw = (np.asarray(v, dtype=np.float64) for v in (x, y, yaw))
+    qx, qy = x - ax, y - ay
+    return ax + (c * qx - s * qy) + dx, ay + (s * qx + c * qy) + dy, yaw + dyaw
 
 
 # ---- map view (include/quasar_slam.h, "map view"): the renderer's constants, dual_bot_mapper.py:346-377, :383-397 ----------

@@ -59,6 +59,19 @@ suspect[bot] is the bot's run of consecutive contradicted sweeps (an OK sweep re
 sweep still counts for the heartbeat; it does not move the bot's pose.  With relocalise also on, a bot whose run reaches
 lost_after (default CHECK_LOST_AFTER) loses its transform and is relocalised from its next sweep on exactly as a bot found
 offline is, group mode included, until a relocalisation is accepted.
+With match_packets=True or a dict (opt-in; works with and without sweeps=True) the 42-byte packets are matched against the map
+as TRAILS before they are mapped (QuasarMapper.match_trails; include/quasar_slam.h, "trail matching").  A trail matched after its
+own packets are in the map agrees with its own hits at zero displacement, so the front-end holds packets back: a packet datagram
+that passes the host-side pre-check (length 42 / 41, magic, agent range) is copied to its bot's pending list instead of being
+ingested; it still shows that its bot is there (address, heartbeat).  Every other datagram goes to the ingest at once.  After a
+poll's runs a bot flushes when its list holds `trail` records (default and at most TRAIL_MAX_RECORDS) or its oldest is `hold`
+seconds old (default 5.0): the flushing bots' records, rewritten by their transforms in force, are matched in ONE match_trails
+call, one group per bot (`travel`, default TRAIL_TRAVEL; every other key of the dict is a match parameter).  An accepted match
+with a non-zero candidate is composed into that bot's rigid transform (rule T7, formed with QuasarMapper.sweep_pose_shift at
+match time; a later closure's drift is not turned with it), which rewrites the f32 x / y / yaw fields of the bot's packets from
+then on, the trail's own included.  Then all flushed records go, in arrival order, through ONE ingest_array, as a poll's packets
+do.  flush_trails() flushes everything pending (close() calls it); trail_matches[bot] holds the bot's latest result, trail_stats
+counts held / tried / accepted / moved / rewritten.  A bot that delivers more than `trail` packets to one poll flushes in rounds.
 With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
 point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
 poses; mapper.MapView.frame draws them.
@@ -81,7 +94,8 @@ class MissionControl:
     def __init__(self, mapper, port=8888, bind_addr="0.0.0.0", max_batch=65536, sock=None, max_agent=2,
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
-                 targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False, check_sweeps=False):
+                 targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False, check_sweeps=False,
+                 match_packets=False):
         by = [k for k, on in (("targets_by_path", targets_by_path), ("targets_by_territory", targets_by_territory),
                               ("targets_by_gain", targets_by_gain)) if on]
         if not frontier_targets and (plan_paths or by):         # each of them refines frontier_targets
@@ -131,6 +145,18 @@ class MissionControl:
         self.suspect = {b: 0 for b in range(1, max_agent + 1)}     # bot -> its run of consecutive contradicted sweeps
         self._lost = set()                           # bots whose run reached lost_after: relocalised as a bot found offline is
         self.last_checks = None
+        self.match_packets = match_packets is not False and match_packets is not None      # ({} is on, with the defaults)
+        self.trail_params = dict(match_packets) if isinstance(match_packets, dict) else {}
+        self.trail = int(self.trail_params.pop("trail", P.TRAIL_MAX_RECORDS))
+        self.trail_hold = float(self.trail_params.pop("hold", 5.0))
+        self.trail_travel = float(self.trail_params.pop("travel", P.TRAIL_TRAVEL))
+        if not 1 <= self.trail <= P.TRAIL_MAX_RECORDS:
+            raise ValueError("MissionControl: match_packets['trail'] must lie in [1, TRAIL_MAX_RECORDS]")
+        self._pending = {b: [] for b in range(1, max_agent + 1)}   # bot -> held packets (arrival number, record, length, time, address)
+        self._trail_seq = 0
+        self._trail_T = {}                           # bot -> (cos, sin, angle, tx, ty): field (x, y) -> R (x, y) + t, yaw + angle
+        self.trail_matches = {}                      # bot -> its latest result (a record of protocol.TRAIL_MATCH_DTYPE)
+        self.trail_stats = {"held": 0, "tried": 0, "accepted": 0, "moved": 0, "rewritten": 0}
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
         self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
@@ -192,24 +218,27 @@ class MissionControl:
             self._times[n] = now
             self._addrs[n] = addr
             n += 1
-        if n == 0:
-            return 0
-        self.datagrams += n
-        if not self.sweeps:
-            self.mapper.ingest_array(self._buf[:n], self._lens[:n], self._times[:n])
-            accepted, pose = self.mapper.last_batch()
-            self._mark(0, accepted, pose, now, self.frontier_targets and pose is not None)
-            if self.track_view:
-                self._track(0, accepted, pose)
+        if not self.match_packets:
+            if n:
+                self.datagrams += n
+                self._ingest_runs(n, now)
             return n
+        self.datagrams += n
+        rest = self._hold(n, now) if n else 0
+        if rest:
+            self._ingest_runs(rest, now)
+        self._flush_trails(now, False)
+        return n
+
+    def _ingest_runs(self, n, now):
+        """The first n slots of the receive buffer through the mapper: one ingest, or (sweeps) one per run of a kind."""
+        if not self.sweeps:
+            self._ingest_packets(0, n, now)
+            return
         for i0, i1, kind in self._runs(n):
             lens = self._lens[i0:i1]
             if kind == 0:
-                self.mapper.ingest_array(self._buf[i0:i1, :SLOT], lens, self._times[i0:i1])
-                accepted, pose = self.mapper.last_batch()
-                self._mark(i0, accepted, pose, now, self.frontier_targets and pose is not None)
-                if self.track_view:
-                    self._track(i0, accepted, pose)
+                self._ingest_packets(i0, i1, now)
             else:
                 if self.relocalise:
                     self._relocalise_run(self._buf[i0:i1, :kind], lens)
@@ -225,7 +254,120 @@ class MissionControl:
                 self._mark(i0, accepted, pose, now, pose is not None)
                 if self.check_sweeps:
                     self._note_checks(i0, self.last_checks, now)
-        return n
+
+    def _ingest_packets(self, i0, i1, now, held=None):
+        """Slots i0 .. i1 of the receive buffer as one packet ingest, and its bookkeeping.  held (match_packets): the flushed
+        records (buf, lens, times, addrs) in their place; they showed at arrival that their bots are there, so mapping them now
+        does not count for the heartbeat."""
+        buf, lens, times, addrs = held if held is not None else (self._buf, self._lens, self._times, self._addrs)
+        self.mapper.ingest_array(buf[i0:i1, :SLOT], lens[i0:i1], times[i0:i1])
+        accepted, pose = self.mapper.last_batch()
+        self._mark(i0, accepted, pose, now, self.frontier_targets and pose is not None, buf, addrs, heartbeat=held is None)
+        if self.track_view:
+            self._track(i0, accepted, pose, buf)
+
+    # ---- match_packets: packets held back, matched as trails, then mapped ----------------------------------------------------
+    def _hold(self, n, now):
+        """The packet datagrams among the first n slots that pass the pre-check move to their bots' pending lists; the other
+        datagrams close ranks in the receive buffer.  Returns how many those are."""
+        buf, lens = self._buf[:n], self._lens[:n]
+        ok = (((lens == P.PACKET_SIZE) | (lens == P.PACKET_SIZE_V1)) & (buf[:, :4] == np.frombuffer(b"QSRL", dtype=np.uint8)).all(axis=1)
+              & (buf[:, 4] >= 1) & (buf[:, 4] <= self.max_agent))
+        held = np.nonzero(ok)[0]
+        if len(held) == 0:
+            return n
+        for i in held:
+            a = int(buf[i, 4])
+            self._pending[a].append((self._trail_seq, buf[i, :SLOT].copy(), int(lens[i]), float(self._times[i]), self._addrs[i]))
+            self._trail_seq += 1
+            self.bot_addrs[a] = (self._addrs[i][0], self.bot_ports[a])      # the bot is there, as a withheld sweep shows it
+            self.last_packet_time[a] = now
+            self.online[a] = True
+            self.seen[a] = True
+        self.trail_stats["held"] += len(held)
+        rest = np.nonzero(~ok)[0]
+        m = len(rest)
+        if m:
+            self._buf[:m] = self._buf[rest]
+            self._lens[:m] = self._lens[rest]
+            self._times[:m] = self._times[rest]
+            self._addrs[:m] = [self._addrs[i] for i in rest]
+        return m
+
+    @staticmethod
+    def _trail_rewrite(recs, T):
+        """The f32 x / y / yaw fields of packet records (uint8 [K, SLOT], in place) moved by the rigid transform T."""
+        c, s, th, tx, ty = T
+        for rec in recs:
+            f = rec[5:17].view("<f4")
+            x, y = float(f[0]), float(f[1])
+            f[:] = (tx + (c * x - s * y), ty + (s * x + c * y), float(f[2]) + th)
+
+    def _trail_compose(self, bot, r, shift):
+        """The correction of match r (rule T7; its anchor in the frame of T3, `shift` = the offset and drift that frame adds to
+        the fields) composed onto the bot's transform of the packet fields."""
+        sx, sy = shift
+        cm, sm = np.cos(float(r["dyaw"])), np.sin(float(r["dyaw"]))
+        ax, ay = float(r["ax"]) - sx, float(r["ay"]) - sy             # the anchor in field coordinates
+        mx, my = ax + float(r["dx"]) - (cm * ax - sm * ay), ay + float(r["dy"]) - (sm * ax + cm * ay)
+        _, _, th, tx, ty = self._trail_T.get(bot, (1.0, 0.0, 0.0, 0.0, 0.0))
+        th = th + float(r["dyaw"])
+        self._trail_T[bot] = (np.cos(th), np.sin(th), th, (cm * tx - sm * ty) + mx, (sm * tx + cm * ty) + my)
+
+    def _flush_trails(self, now, everything):
+        """Flush in rounds, each round one trail per due bot: ONE match_trails call, then ONE ingest of the round's records in
+        arrival order.  everything: every bot with a pending packet is due."""
+        while True:
+            due = {}
+            for b, pend in self._pending.items():
+                if len(pend) >= self.trail:
+                    due[b] = self.trail
+                elif pend and (everything or now - pend[0][3] >= self.trail_hold):
+                    due[b] = len(pend)
+            if not due:
+                return
+            groups = {}
+            for b, k in sorted(due.items()):
+                groups[b], self._pending[b] = self._pending[b][:k], self._pending[b][k:]
+            # matched as the transforms in force would map them
+            trial = []
+            for b, g in groups.items():
+                recs = np.stack([p[1] for p in g])
+                if b in self._trail_T:
+                    self._trail_rewrite(recs, self._trail_T[b])
+                trial.append(recs)
+            lens = np.array([p[2] for g in groups.values() for p in g], dtype=np.uint16)
+            shift_of = getattr(self.mapper, "sweep_pose_shift", None)
+            shifts = {b: tuple(float(v) for v in shift_of(b)) if shift_of else (0.0, 0.0) for b in groups}
+            res = self.mapper.match_trails(np.concatenate(trial), [len(g) for g in groups.values()], lens,
+                                           travel=self.trail_travel, params=self.trail_params or None)
+            for b, r in zip(groups, res):
+                self.trail_matches[b] = r.copy()
+                self.trail_stats["tried"] += 1
+                if r["accepted_match"]:
+                    self.trail_stats["accepted"] += 1
+                    if int(r["ix"]) or int(r["iy"]) or int(r["it"]):
+                        self.trail_stats["moved"] += 1
+                        self._trail_compose(b, r, shifts[b])
+            # mapped, in arrival order, as the transforms now in force map them (the trail's own records included)
+            flat = sorted((p for g in groups.values() for p in g), key=lambda p: p[0])
+            m = len(flat)
+            buf = np.zeros((m, self.slot), dtype=np.uint8)
+            for j, p in enumerate(flat):
+                buf[j, :SLOT] = p[1]
+                T = self._trail_T.get(int(p[1][4]))
+                if T is not None:
+                    self._trail_rewrite(buf[j:j + 1], T)
+                    self.trail_stats["rewritten"] += 1
+            # through the ingest and bookkeeping of a poll's packets; when they arrived is what the heartbeat goes by, not when
+            # they are mapped
+            self._ingest_packets(0, m, now, held=(buf, np.array([p[2] for p in flat], dtype=np.uint16),
+                                                  np.array([p[3] for p in flat], dtype=np.float64), [p[4] for p in flat]))
+
+    def flush_trails(self, now=None):
+        """match_packets: match and map everything pending, whatever its count or age."""
+        if self.match_packets:
+            self._flush_trails(time.time() if now is None else now, True)
 
     def _note_checks(self, i0, checks, now):
         """check_sweeps: the checks of one guarded ingest whose first datagram is slot i0, in arrival order.  A withheld sweep
@@ -335,24 +477,29 @@ class MissionControl:
                 del self._reloc_kept[a]
         return located
 
-    def _mark(self, i0, accepted, pose, now, keep_pose):
-        """Bookkeeping of the accepted records of one ingest whose first datagram is slot i0 (:846-848, :860-864)."""
+    def _mark(self, i0, accepted, pose, now, keep_pose, buf=None, addrs=None, heartbeat=True):
+        """Bookkeeping of the accepted records of one ingest whose first datagram is slot i0 (:846-848, :860-864) of the receive
+        buffer, or of buf / addrs.  heartbeat=False (held packets, mapped later than they arrived): the count and the pose only."""
+        buf = self._buf if buf is None else buf
+        addrs = self._addrs if addrs is None else addrs
         for j in np.nonzero(accepted)[0]:
             i = i0 + int(j)
-            a = int(self._buf[i, 4])
-            self.bot_addrs[a] = (self._addrs[i][0], self.bot_ports[a])                # :846
-            self.last_packet_time[a] = now                                            # :847
+            a = int(buf[i, 4])
             self.pkt_counts[a] += 1                                                   # :848
-            self.online[a] = True                                                     # :860-864
-            self.seen[a] = True
+            if heartbeat:
+                self.bot_addrs[a] = (addrs[i][0], self.bot_ports[a])                  # :846
+                self.last_packet_time[a] = now                                        # :847
+                self.online[a] = True                                                 # :860-864
+                self.seen[a] = True
             if keep_pose:
                 self.bot_pose[a] = (float(pose[j, 0]), float(pose[j, 1]))
 
-    def _track(self, i0, accepted, pose):
+    def _track(self, i0, accepted, pose, buf=None):
         """track_view: the renderer's inputs of the accepted packets of one ingest (:878-879 the path, :892 the clouds)."""
+        buf = self._buf if buf is None else buf
         xy, valid = self.mapper.last_hits()
         for j in np.nonzero(accepted)[0]:
-            a = int(self._buf[i0 + int(j), 4])
+            a = int(buf[i0 + int(j), 4])
             self.paths[a][0].append(float(pose[j, 0]))
             self.paths[a][1].append(float(pose[j, 1]))
             for s, name in enumerate(P.SENSOR_NAMES):
@@ -480,4 +627,8 @@ class MissionControl:
                 time.sleep(idle_sleep)
 
     def close(self):
+        """match_packets: what is pending is matched and mapped first, so close the front-end BEFORE its mapper; held packets of
+        a mapper that is already closed (QuasarMapper: no handle left) are dropped."""
+        if getattr(self.mapper, "_h", True):
+            self.flush_trails()
         self.sock.close()

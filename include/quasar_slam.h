@@ -361,6 +361,59 @@ int qs_relocalise_groups_device(qs_ctx *ctx, const qs_reloc_params *params, cons
                                 const uint16_t *d_lens, const qs_reloc_rel *d_rel, const int32_t *gsize, size_t n_groups,
                                 double travel, qs_group_reloc *d_out);
 
+/* ---- trail matching (no reference counterpart: this build's own rule) ------------------------------------------------------
+ * The reference's robots send 42-byte packets: a pose and four sonar ranges (front, left, back, right).  One packet cannot
+ * locate itself -- four points do not fix a pose -- but a TRAIL can: the last K packets of one bot, held together rigidly by the
+ * bot's own odometry, whose hit points trace the walls the bot drove along.  A trail is matched against the map as a sweep is
+ * ("sweep matching" above): a window of candidate corrections scored on the likelihood field, the rotation about the trail's
+ * last pose.  Everything after the per-record (sin, cos) is integer or uncontracted fp64, so the device and the CPU restatement
+ * (tests/trail_rules.py) agree bit for bit once they share those.
+ *  T1. Groups: the n records are n_groups consecutive groups of gsize[g] records in arrival order, 1 <= gsize[g] <=
+ *      QS_TRAIL_MAX_RECORDS, the sizes sum to n.  gsize is a HOST array in both entry points (as for qs_relocalise_groups).
+ *  T2. Acceptance of a record is qs_ingest's own rule: length 42 or 41 and <= stride, magic, agent in 1..max_agent, and x, y,
+ *      yaw finite.  The group's ANCHOR is its last accepted record; the group's bot is the anchor's agent.
+ *  T3. Pose of accepted record k: rx = (f64(x) + offset[bot]) + drift_x[bot], ry = f64(y) + drift_y[bot], the bot's drift as all
+ *      earlier calls on the context's stream left it (read on the device).  ONE drift is used for the whole trail: odometry is
+ *      locally rigid, and a closure in the middle of a trail is a jump of the correction, not of the robot.  (ax, ay) is the
+ *      anchor's pose.
+ *  T4. A record counts when it is accepted, its agent is the group's bot, and (rx - ax)^2 + (ry - ay)^2 <= travel^2
+ *      (uncontracted).  `records` is the number of counting records.  With none counting the output has anchor = -1 and every
+ *      other field zero.
+ *  T5. Points: (s, c) = the device's sincos(f64(yaw)), one per record, reported in rot_out[k] = (s, c) (zeros for records that
+ *      do not count).  Sensor directions in sensor order are exact sign flips of those two numbers: front (c, s), left (-s, c),
+ *      back (-c, -s), right (s, -c).  The range d is the f32 widened; it is a hit when min_dist < d <= max_dist (the context's
+ *      trust filter, dual_bot_mapper.py:888).  Only hits score; H is their number over the group.  px = rx + d * ux,
+ *      py = ry + d * uy (one multiply, one add, no FMA); qx = px - ax, qy = py - ay.
+ *  T6. Candidates (ix, iy, it), |ix|, |iy| <= window, |it| <= angle_steps.  (S, C) = (sin, cos) of it * angle_step (one
+ *      multiply) from the HOST's libm, uploaded (as relocalisation rule G2 does).  The trail turns about the anchor:
+ *      ex = ax + (C * qx - S * qy), ey = ay + (S * qx + C * qy), in this association; the cell (cx, cy) by world_to_grid, with
+ *      sweep-matching rule 3's treatment of quotients that are not finite or beyond 2^30.  The translation shifts the look-up:
+ *      score = sum over the H points of L[cy + iy][cx + ix], L sweep-matching rule 1 with `radius`.
+ *  T7. Order and gate: sweep-matching rules 4 and 5 unchanged, with this H; score0 is the score of (0, 0, 0).  On acceptance
+ *      dx = ix * res, dy = iy * res, dyaw = it * angle_step; otherwise all three are zero.  What the correction means: a pose
+ *      (x, y, yaw) of that bot in the frame of T3 moves to
+ *        (ax + (C (x - ax) - S (y - ay)) + dx,  ay + (S (x - ax) + C (y - ay)) + dy,  yaw + dyaw),  (S, C) of dyaw.
+ *  T8. Limits: those of qs_match_params; travel finite and >= 0; ceil((max_dist + travel) / res) + window + radius + 2 <=
+ *      QS_MATCH_MAX_REACH, so that the patch about the anchor stays within 255 cells a side; stride >= 41.  QS_E_INVAL beyond
+ *      any of them, and the text names the quantity.  A sharded context refuses, as qs_match_sweeps does.  params NULL = the
+ *      sweep-matching defaults.
+ * The calls read the map (waiting exact-trig rays are flushed first) and write nothing to the context: a checkpoint taken
+ * before equals one taken after. */
+#define QS_TRAIL_MAX_RECORDS 64     /* 256 points score at most 256 * 8 = 2048 */
+typedef struct qs_trail_match {      /* 80 bytes */
+    int32_t ix, iy, it, score, score0, hits;
+    int32_t records, anchor;         /* anchor: index within the group, -1 when records == 0 */
+    uint8_t agent, accepted_match, pad[6];   /* pad is zero */
+    double ax, ay, dx, dy, dyaw;
+} qs_trail_match;
+int qs_match_trails(qs_ctx *ctx, const qs_match_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                    const uint16_t *lens, const int32_t *gsize, size_t n_groups, double travel, qs_trail_match *out,
+                    double *rot_out /* n x 2, optional */);
+/* same with device-resident pkts / lens / out / rot_out (gsize stays a host array); asynchronous on the context's stream */
+int qs_match_trails_device(qs_ctx *ctx, const qs_match_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                           const uint16_t *d_lens, const int32_t *gsize, size_t n_groups, double travel,
+                           qs_trail_match *d_out, double *d_rot_out);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

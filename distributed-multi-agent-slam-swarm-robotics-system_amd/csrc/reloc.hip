@@ -666,7 +666,7 @@ static hipError_t reloc_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned
     HIPRET(reloc_prepare(c, rs, RL_OFFP, false, pl));
     QsRelocArgs &m = pl.m;
     const size_t n_tiles = pl.n_tiles, lds = pl.lds;
-    if (lds > 32 * 1024) {                                         // long reaches: up to 2 x 65 KiB of the CU's 160
+    if (lds > 32 * 1024) {                                         // long reaches: up to 2 x 69 088 B (SA 254, rows of 272) of the CU's 160 KiB
         HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIPRET(hipFuncSetAttribute((const void *)qs_reloc_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }

@@ -5,7 +5,8 @@ exact integer or uncontracted fp64 arithmetic and the rotations' (sin, cos) are 
 this bit for bit.  Two forms: `reloc_one`, vectorised (per rotation and distinct beam offset one shifted add of the padded
 field), and `reloc_one_brute`, word for word, for small grids.
 
-Also here: the world the recovery and GPU tests share, its query poses, and the rays that paint a grid into a mapper."""
+Also here: the world the recovery and GPU tests share, the small world whose free cells touch the grid's border, query poses, and
+the rays that paint a grid into a mapper."""
 import math
 
 import numpy as np
@@ -223,6 +224,17 @@ def world():
     g[130:133, 60:88] = 100
     g[50:53, 140:143] = 100
     g[72, 150:171] = 100
+    return g
+
+
+def small_world():
+    """68 x 68, every cell FREE up to the grid's border but for an L-shaped wall, a bar and two pillars (nothing symmetric)."""
+    g = np.zeros((68, 68), dtype=np.int8)
+    g[10, 8:40] = 100
+    g[10:30, 8] = 100
+    g[50, 30:60] = 100
+    g[40:44, 20] = 100
+    g[25, 50] = g[33, 58] = 100
     return g
 
 

@@ -47,23 +47,12 @@ def W(pkg):
     m.close()
 
 
-def small_world():
-    """68 x 68, every cell FREE up to the grid's border but for an L-shaped wall, a bar and two pillars (nothing symmetric)."""
-    g = np.zeros((68, 68), dtype=np.int8)
-    g[10, 8:40] = 100
-    g[10:30, 8] = 100
-    g[50, 30:60] = 100
-    g[40:44, 20] = 100
-    g[25, 50] = g[33, 58] = 100
-    return g
-
-
 SMALL_GEOM = (0.05, -1.7, -1.7)
 
 
 @pytest.fixture(scope="module")
 def S(pkg):
-    grid = small_world()
+    grid = RR.small_world()
     m = _painted(pkg, grid, *SMALL_GEOM)
     cells = np.array([(3, 3), (64, 2), (1, 66), (66, 66), (30, 30), (45, 20)])
     # headings towards the middle of the grid, so that every sweep sees something (33 to 136 hit beams at 3.0 m)

@@ -50,21 +50,10 @@ def W(pkg):
     m.close()
 
 
-def small_world():
-    """68 x 68, every cell FREE up to the grid's border but for an L-shaped wall, a bar and two pillars (nothing symmetric)."""
-    g = np.zeros((68, 68), dtype=np.int8)
-    g[10, 8:40] = 100
-    g[10:30, 8] = 100
-    g[50, 30:60] = 100
-    g[40:44, 20] = 100
-    g[25, 50] = g[33, 58] = 100
-    return g
-
-
 @pytest.fixture(scope="module")
 def S(pkg):
     """The small world and 3 groups of 2 sweeps sensed in it at 3.0 m, the second 0.3 m ahead of the first."""
-    grid = small_world()
+    grid = RR.small_world()
     m = _painted(pkg, grid, *SMALL_GEOM)
     cells = np.array([(3, 3), (64, 2), (30, 30)])
     yaw = np.arctan2(34 - cells[:, 1], 34 - cells[:, 0]) + np.array([0.1, -0.2, 2.0])

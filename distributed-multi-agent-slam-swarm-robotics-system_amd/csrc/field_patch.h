@@ -1,5 +1,6 @@
 // field_patch.h -- a square patch of the likelihood field (include/quasar_slam.h, "sweep matching", rule 1) built in LDS by one
-// workgroup, and the look-up of four adjacent cells of it: shared by the sweep matcher (match.hip) and the relocaliser (reloc.hip).
+// workgroup, the look-up of four adjacent cells of it, and the workgroup's maximum of a 64-bit key: shared by the window search of
+// the sweep and trail matchers (window_match.h) and the relocaliser (reloc.hip).
 #pragma once
 #include "qs_internal.h"
 
@@ -32,6 +33,22 @@ __device__ inline unsigned int mt_grow_u8x4(unsigned int old, unsigned int m)
 __device__ inline unsigned int mt_look(const unsigned int *p, unsigned int a)
 {
     return __builtin_amdgcn_alignbyte(p[(a >> 2) + 1], p[a >> 2], a & 3u);
+}
+
+// max of v over the workgroup's nw waves, returned in thread 0 (other threads get their wave's): shuffles within the wave,
+// s_key[nw] across the waves.  Every thread calls it, once per s_key; it holds one barrier
+__device__ __forceinline__ unsigned long long mt_block_max(unsigned long long v, unsigned long long *s_key, int tid, int nw)
+{
+    #pragma unroll
+    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
+        const unsigned long long other = __shfl_xor(v, d);
+        v = other > v ? other : v;
+    }
+    if ((tid & (QS_WAVE - 1)) == 0) s_key[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < nw; w++) v = s_key[w] > v ? s_key[w] : v;
+    return v;
 }
 
 // The patch whose byte (0, 0) is grid cell (gx0, gy0): SA cells a side, rows of `pitch` bytes (a multiple of 4), into A; B is

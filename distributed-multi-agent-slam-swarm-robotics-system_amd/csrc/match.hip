@@ -2,186 +2,79 @@
 // of candidate poses (ix, iy cells, it angle steps) around the packet's pose, scored on a likelihood field of the occupied
 // cells; the best candidate is the sweep's correction.
 //
-// One WORKGROUP (4 waves) per sweep, everything it touches in LDS:
+// One WORKGROUP (4 waves) per sweep, everything it touches in LDS.  The window search is window_match.h's, shared with the trail
+// matcher (trail.hip); what is the sweep's own:
 //   1. wave 0 stages the record as the sweep mapper does (sweep_common.h);
-//   2. the patch of the field the sweep can reach -- the robot's cell +- (ceil(smax / res) + 1 + W) cells, plus an apron of R
-//      cells -- is read from the stamps as bytes (OCCUPIED = odd stamp -> R + 1, anything else and off-grid -> 0) and grown
-//      by R rounds of a separable 3-wide max that loses 1 per round: L = max(0, R + 1 - Chebyshev distance).  The rounds work
-//      on dwords (four cells a lane); a patch that hangs over the grid's edge is cut back to the grid afterwards.  No
-//      whole-grid field exists: nothing persistent, nothing to invalidate.  The routine is field_patch.h's, shared with the
-//      relocaliser (reloc.hip);
-//   3. every wave holds all 181 beams (three a lane: d, hit flag, d * cos, d * sin of the beam angle, the trig from the
-//      host's table) and takes rotations wave, wave + 4, ...: one sincos per rotation, the end-point cells of the hit beams,
-//      compacted by ballot into the rotation's list of 16-bit patch offsets (the offset of candidate ix = iy = -W);
-//   4. a lane takes (rotation, iy, FOUR adjacent ix): per beam two dword reads and a v_alignbyte give the four look-ups,
-//      which are summed as bytes (255 / (R + 1) beams at a time cannot overflow one) and spilled into 16-bit sums; the
-//      offsets are read four beams at a time (one 8-byte read).  Per four look-ups: 2.25 LDS reads and about six VALU
-//      instructions;
-//   5. the total order of the rule is one 64-bit key: max by shuffles within the wave, LDS across the four waves.
-// qs_match_field_kernel is the plain whole-grid form of step 2 for tests and tools.
+//   2. the patch of the field the sweep can reach about the robot's cell, half = ceil(smax / res) + 1 + W (wm_build_patch).  No
+//      whole-grid field exists: nothing persistent, nothing to invalidate;
+//   3. every wave holds all 181 beams (sw_beams: the trig from the host's table) and takes rotations wave, wave + 4, ...: one
+//      sincos per rotation, reported in `rot`, and the end points of the hit beams into the rotation's list (wm_list);
+//   4. scores, the best key and the gate (wm_best, wm_result).
+// qs_match_field_kernel is the plain whole-grid form of the field for tests and tools.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 
 #include "sweep_common.h"
-#include "field_patch.h"
+#include "window_match.h"
 
-#define MT_BLOCK 256
-#define MT_NW (MT_BLOCK / QS_WAVE)
 #define MT_OFFP 184               // 16-bit offsets per rotation: >= 181, a multiple of 4 (8-byte reads)
-#define MT_NROT_MAX (2 * QS_MATCH_MAX_ANGLE_STEPS + 1)
 #define MT_CHUNK ((size_t)1 << 16)   // records per launch of the host-side call (its results and rotations travel per chunk)
 
 struct QsMatchArgs {
-    int R, W, T, min_hits, min_percent;
-    int half;                     // patch: the robot's cell +- half, half = reach + 1 + W
-    int SA, pitch;                // side with the apron (2 (half + R) + 1) and bytes per row (a multiple of 4, an odd number of dwords)
-    unsigned int off_b;           // byte offset of the second LDS region (dilation scratch, then the offset lists)
-    double step;
+    WmArgs w;
     const double *tab;            // [2][181] cos, sin of (i - 90) * (pi / 180), the host's libm
-    const unsigned int *stamps;
     qs_sweep_match *out;          // [n]
     double *rot;                  // [n][2 T + 1][2] or nullptr
 };
 
-__global__ void __launch_bounds__(MT_BLOCK)
+__global__ void __launch_bounds__(WM_BLOCK)
 qs_match_kernel(QsSweepArgs a, QsGeom geo, QsMatchArgs m)
 {
     extern __shared__ __align__(16) unsigned char s_dyn[];
     __shared__ unsigned int s_rec[SW_DW];
-    __shared__ int s_cnt[MT_NROT_MAX];
-    __shared__ unsigned long long s_key[MT_NW];
+    __shared__ int s_cnt[WM_NROT_MAX];
+    __shared__ unsigned long long s_key[WM_NW];
     __shared__ int s_score0;
     const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
     const size_t k = blockIdx.x;
-    const int nrot = 2 * m.T + 1;
+    const int nrot = 2 * m.w.T + 1;
     if (wave == 0) sw_stage(a, k, s_rec, lane);
     __syncthreads();
     const unsigned int mis = (unsigned int)(((unsigned long long)a.pkts + k * a.stride) & 3ull);
     const SwHead h = sw_head(a, k, s_rec, mis);
     if (!h.ok) {                                                   // (uniform over the workgroup)
         if (tid == 0) { qs_sweep_match z; memset(&z, 0, sizeof z); m.out[k] = z; }
-        if (m.rot) for (int j = tid; j < 2 * nrot; j += MT_BLOCK) m.rot[k * 2 * (size_t)nrot + j] = 0.0;
+        if (m.rot) for (int j = tid; j < 2 * nrot; j += WM_BLOCK) m.rot[k * 2 * (size_t)nrot + j] = 0.0;
         return;
     }
-
-    // ---- the patch of the field ------------------------------------------------------------------------------------------
-    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.off_b);
-    int c0x = 0, c0y = 0;
-    bool c0ok = qs_w2g_i32(h.rx, geo.ox, geo, c0x);
-    c0ok = qs_w2g_i32(h.ry, geo.oy, geo, c0y) && c0ok;
-    if (!c0ok) { c0x = 0; c0y = 0; }                               // (no beam of such a pose has a cell: nothing reads the patch)
-    const int gx0 = c0x - m.half - m.R, gy0 = c0y - m.half - m.R;  // grid cell of patch byte (0, 0); |c0| <= 2^30
-    mt_build_patch(A, B, m.stamps, geo.size, gx0, gy0, m.SA, m.pitch, m.R, tid, MT_BLOCK);
+    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.w.off_b);
+    const WmPatch p = wm_build_patch(m.w, geo, h.rx, h.ry, m.w.half, A, B, tid);
 
     // ---- beams, and per rotation the patch offsets of the hit beams' cells ---------------------------------------------------
     unsigned short *OFF = (unsigned short *)B;
     bool hit[3];
     double bx[3], by[3];
-    int H = 0;
-    #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const int i = lane + QS_WAVE * q;
-        hit[q] = false; bx[q] = 0.0; by[q] = 0.0;
-        if (i < QS_SWEEP_BEAMS) {
-            const double d = (double)__uint_as_float(sw_u32(s_rec, mis, a.ranges_off + 4u * (unsigned int)i));
-            hit[q] = qs_range_rule(d, a.smin, a.smax).valid;
-            bx[q] = d * m.tab[i];
-            by[q] = d * m.tab[QS_SWEEP_BEAMS + i];
-        }
-        H += __popcll(__ballot(hit[q]));
-    }
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const int lo_ok = m.R + m.W, hi_ok = m.SA - 1 - m.R - m.W;     // a cell every shift of which stays inside the exact part
-    for (int ti = wave; ti < nrot; ti += MT_NW) {
-        const double th = h.yaw + (double)(ti - m.T) * m.step;
+    const int H = sw_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    for (int ti = wave; ti < nrot; ti += WM_NW) {
+        const double th = h.yaw + (double)(ti - m.w.T) * m.w.step;
         double s, c;
         qs_sincos(th, &s, &c);
         if (m.rot && lane == 0) { double *o = m.rot + (k * (size_t)nrot + ti) * 2; o[0] = s; o[1] = c; }
         int cnt = 0;
         #pragma unroll
-        for (int q = 0; q < 3; q++) {
-            bool in = false;
-            unsigned int off = 0;
-            if (hit[q]) {
-                const double ex = h.rx + (c * bx[q] - s * by[q]), ey = h.ry + (s * bx[q] + c * by[q]);
-                int cx, cy;
-                bool ok = qs_w2g_i32(ex, geo.ox, geo, cx);
-                ok = qs_w2g_i32(ey, geo.oy, geo, cy) && ok;
-                if (ok && c0ok) {
-                    const long long ax = (long long)cx - gx0, ay = (long long)cy - gy0;
-                    in = ax >= lo_ok && ax <= hi_ok && ay >= lo_ok && ay <= hi_ok;
-                    off = (unsigned int)((ay - m.W) * m.pitch + (ax - m.W));
-                }
-            }
-            const unsigned long long bal = __ballot(in);
-            if (in) OFF[ti * MT_OFFP + cnt + __popcll(bal & lt)] = (unsigned short)off;
-            cnt += __popcll(bal);
-        }
+        for (int q = 0; q < 3; q++)
+            wm_list(p, geo, hit[q], h.rx + (c * bx[q] - s * by[q]), h.ry + (s * bx[q] + c * by[q]), OFF + ti * MT_OFFP, cnt, lane);
         if (lane == 0) s_cnt[ti] = cnt;
     }
     __syncthreads();
 
-    // ---- scores: a lane per (rotation, iy, four ix) --------------------------------------------------------------------------
-    // (qs_trail_kernel, trail.hip, restates this loop over a trail's points: a change here belongs there too)
-    const int ny = 2 * m.W + 1, G = (ny + 3) >> 2, per_rot = ny * G, NI = nrot * per_rot;
-    const int span = (255 / (m.R + 1)) & ~3;                       // beams whose byte sums cannot overflow
-    unsigned long long best = 0;
-    for (int j = tid; j < NI; j += MT_BLOCK) {
-        const int ti = j / per_rot, rem = j - ti * per_rot, yi = rem / G, g = rem - yi * G;
-        const unsigned int lane_off = (unsigned int)(yi * m.pitch + 4 * g);
-        const unsigned short *o = OFF + ti * MT_OFFP;
-        const int cnt = s_cnt[ti];
-        unsigned int lo = 0, hi = 0;
-        for (int b0 = 0; b0 < cnt; b0 += span) {
-            const int b1 = min(b0 + span, cnt);
-            unsigned int acc = 0;
-            int b = b0;
-            for (; b + 4 <= b1; b += 4) {
-                const uint2 q = *(const uint2 *)(o + b);
-                acc += mt_look(A, lane_off + (q.x & 0xffffu));
-                acc += mt_look(A, lane_off + (q.x >> 16));
-                acc += mt_look(A, lane_off + (q.y & 0xffffu));
-                acc += mt_look(A, lane_off + (q.y >> 16));
-            }
-            for (; b < b1; b++) acc += mt_look(A, lane_off + o[b]);
-            lo += acc & 0x00ff00ffu;
-            hi += (acc >> 8) & 0x00ff00ffu;
-        }
-        const unsigned int sc[4] = {lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16};
-        const int it = ti - m.T, iy = yi - m.W;
-        #pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int ix = 4 * g + e - m.W;
-            if (ix > m.W) break;
-            // score, then small ix^2 + iy^2, small |it|, small it, small iy, small ix: every field "larger is better"
-            const unsigned long long key = ((unsigned long long)sc[e] << 45) | ((unsigned long long)(32767 - (ix * ix + iy * iy)) << 30)
-                                         | ((unsigned long long)(m.T - abs(it)) << 23) | ((unsigned long long)(m.T - it) << 16)
-                                         | ((unsigned long long)(m.W - iy) << 8) | (unsigned long long)(m.W - ix);
-            best = key > best ? key : best;
-            if (it == 0 && iy == 0 && ix == 0) s_score0 = (int)sc[e];
-        }
-    }
-    #pragma unroll
-    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(best, d);
-        best = other > best ? other : best;
-    }
-    if (lane == 0) s_key[wave] = best;
-    __syncthreads();
+    const unsigned long long best = wm_best(p, A, OFF, MT_OFFP, s_cnt, s_key, &s_score0, tid);
     if (tid == 0) {
-        for (int w = 1; w < MT_NW; w++) best = s_key[w] > best ? s_key[w] : best;
         qs_sweep_match r;
         memset(&r, 0, sizeof r);
-        r.ix = m.W - (int)(best & 255u);
-        r.iy = m.W - (int)((best >> 8) & 255u);
-        r.it = m.T - (int)((best >> 16) & 127u);
-        r.score = (int)(best >> 45);
-        r.score0 = s_score0;
-        r.hits = H;
+        wm_result(m.w, geo.res, best, s_score0, H, r);
         r.accepted_record = 1;
-        r.accepted_match = H >= m.min_hits && (long long)r.score * 100 >= (long long)m.min_percent * H * (m.R + 1);
-        if (r.accepted_match) { r.dx = (double)r.ix * geo.res; r.dy = (double)r.iy * geo.res; r.dyaw = (double)r.it * m.step; }
         m.out[k] = r;
     }
 }
@@ -216,20 +109,28 @@ const char *qs_match_params_check(const qs_match_params *params, qs_match_params
     return nullptr;
 }
 
+int qs_match_reach_setup(qs_ctx *c, const char *who, const qs_match_params &p, double reach, const char *what, const char *expr,
+                         QsMatchSetup &ms)
+{
+    char msg[256];
+    if (!(reach + p.radius + 2 <= QS_MATCH_MAX_REACH))
+        snprintf(msg, sizeof msg, "%s: %s is too large for this resolution: ceil(%s / res) + radius + 2 exceeds QS_MATCH_MAX_REACH", who, what, expr);
+    else if (reach + p.window + p.radius + 2 > QS_MATCH_MAX_REACH)
+        snprintf(msg, sizeof msg, "%s: window is too large: ceil(%s / res) + window + radius + 2 exceeds QS_MATCH_MAX_REACH", who, expr);
+    else {
+        ms = QsMatchSetup{p.radius, p.window, p.angle_steps, p.min_hits, p.min_percent, (int)reach, p.angle_step};
+        return QS_OK;
+    }
+    return qs_fail(c, QS_E_INVAL, msg);
+}
+
 int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, QsMatchSetup &ms)
 {
     qs_match_params p;
     char msg[256];
     const char *bad = qs_match_params_check(params, p);
-    const double reach = ceil(c->sweep_max / c->cfg.res);
-    if (!bad && !(reach + p.radius + 2 <= QS_MATCH_MAX_REACH))
-        bad = "the sweep filter's smax is too large for this resolution: ceil(smax / res) + radius + 2 exceeds QS_MATCH_MAX_REACH";
-    else if (!bad && reach + p.window + p.radius + 2 > QS_MATCH_MAX_REACH)
-        bad = "window is too large: ceil(smax / res) + window + radius + 2 exceeds QS_MATCH_MAX_REACH";
     if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
-    ms.R = p.radius; ms.W = p.window; ms.T = p.angle_steps; ms.min_hits = p.min_hits; ms.min_percent = p.min_percent;
-    ms.reach = (int)reach; ms.step = p.angle_step;
-    return QS_OK;
+    return qs_match_reach_setup(c, who, p, ceil(c->sweep_max / c->cfg.res), "the sweep filter's smax", "smax", ms);
 }
 
 int qs_sweep_call_ok(qs_ctx *c, size_t n, size_t stride, const char *who)
@@ -264,20 +165,10 @@ hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned cha
     QsSweepArgs a;
     qs_sweep_args(c, d_pkts, n, stride, d_lens, graph_k0, a);
     QsMatchArgs m;
-    m.R = ms.R; m.W = ms.W; m.T = ms.T; m.min_hits = ms.min_hits; m.min_percent = ms.min_percent;
-    m.half = ms.reach + 1 + ms.W;
-    m.SA = 2 * (m.half + ms.R) + 1;                               // <= 255 (qs_match_setup)
-    m.pitch = (m.SA + 3) & ~3;
-    if (!((m.pitch >> 2) & 1)) m.pitch += 4;                       // an odd number of dwords a row: rows start on different banks
-    const size_t a_bytes = ((size_t)m.SA * m.pitch + 16 + 15) & ~(size_t)15;
-    const size_t b_bytes = std::max((size_t)m.SA * m.pitch, (size_t)(2 * ms.T + 1) * MT_OFFP * sizeof(unsigned short));
-    m.off_b = (unsigned int)a_bytes;
-    m.step = ms.step;
-    m.tab = c->match_tab.p; m.stamps = c->d_stamps.p; m.out = out; m.rot = rot;
-    const size_t lds = a_bytes + ((b_bytes + 15) & ~(size_t)15);
-    if (lds > 32 * 1024)                                           // the largest windows: up to 2 x 65 KiB of the CU's 160
-        HIPRET(hipFuncSetAttribute((const void *)qs_match_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qs_match_kernel, dim3((unsigned int)n), dim3(MT_BLOCK), lds, c->stream, a, c->geom, m);
+    size_t lds;
+    HIPRET(wm_args(c, ms, (const void *)qs_match_kernel, MT_OFFP, m.w, lds));
+    m.tab = c->match_tab.p; m.out = out; m.rot = rot;
+    hipLaunchKernelGGL(qs_match_kernel, dim3((unsigned int)n), dim3(WM_BLOCK), lds, c->stream, a, c->geom, m);
     return hipGetLastError();
 }
 

@@ -455,6 +455,10 @@ int qs_match_setup(qs_ctx *c, const qs_match_params *params, const char *who, Qs
 // the limits of qs_match_params alone, shared with trail matching (trail.hip): p = *params or the defaults; the text of the
 // first limit broken, or nullptr
 const char *qs_match_params_check(const qs_match_params *params, qs_match_params &p);
+// the reach limit of both, reach = ceil(. / res) cells: the patch, then the window, within QS_MATCH_MAX_REACH; fills ms from p.
+// The refusal opens with `what` ("the sweep filter's smax") and names the length as `expr` ("smax")
+int qs_match_reach_setup(qs_ctx *c, const char *who, const qs_match_params &p, double reach, const char *what, const char *expr,
+                         QsMatchSetup &ms);
 // n device-resident records matched against the map as the stream finds it; rot (optional): [n][2 T + 1][2] the (sin, cos) used;
 // graph_k0 as qs_sweep_args takes it (sweep_common.h): QS_SWEEP_NO_GRAPH, or the record of a graph-mode call the n records start at
 hipError_t qs_launch_match(qs_ctx *c, const QsMatchSetup &ms, const unsigned char *d_pkts, size_t n, size_t stride,

@@ -105,26 +105,6 @@ struct RlTileEmit {
     __device__ void put(size_t slot, size_t i) const { list[slot] = (unsigned int)i; }
 };
 
-// the 181 beams of a staged record, three a lane: hit flags, d * cos, d * sin; returns H (every wave computes all of it)
-__device__ inline int rl_beams(const QsSweepArgs &a, const unsigned int *s_rec, unsigned int mis, const double *tab, int lane,
-                               bool hit[3], double bx[3], double by[3])
-{
-    int H = 0;
-    #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const int i = lane + QS_WAVE * q;
-        hit[q] = false; bx[q] = 0.0; by[q] = 0.0;
-        if (i < QS_SWEEP_BEAMS) {
-            const double d = (double)__uint_as_float(sw_u32(s_rec, mis, a.ranges_off + 4u * (unsigned int)i));
-            hit[q] = qs_range_rule(d, a.smin, a.smax).valid;
-            bx[q] = d * tab[i];
-            by[q] = d * tab[QS_SWEEP_BEAMS + i];
-        }
-        H += __popcll(__ballot(hit[q]));
-    }
-    return H;
-}
-
 // the tiles that meet the square +-sep round (gx, gy): [tlx, thx] x [tly, thy] (at most 3 x 3; may reach outside the grid)
 __device__ inline void rl_square_tiles(int gx, int gy, int sep, int &tlx, int &tly, int &thx, int &thy)
 {
@@ -222,22 +202,6 @@ __device__ __forceinline__ void rl_take(const QsRelocArgs &m, unsigned int lo, u
     }
 }
 
-// the workgroup's best key into *dst
-__device__ __forceinline__ void rl_store_best(unsigned long long best, unsigned long long *s_key, unsigned long long *dst, int tid)
-{
-    #pragma unroll
-    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(best, d);
-        best = other > best ? other : best;
-    }
-    if ((tid & (QS_WAVE - 1)) == 0) s_key[tid >> 6] = best;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < RL_NW; w++) best = s_key[w] > best ? s_key[w] : best;
-        *dst = best;
-    }
-}
-
 // ---- scores of one (sweep, tile) -------------------------------------------------------------------------------------------------
 template <bool EXCL>
 __global__ void __launch_bounds__(RL_BLOCK)
@@ -259,7 +223,7 @@ qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
     bool hit[3];
     double bx[3], by[3];
     const bool ok = sw_accept(a, k, s_rec, mis, agent);
-    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    const int H = sw_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
     if (!ok || H == 0) { if (tid == 0) *dst = 0; return; }         // (uniform over the workgroup)
 
     // ---- the patch of the field: the tile and M + R cells all round --------------------------------------------------------------
@@ -307,7 +271,8 @@ qs_reloc_score_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
         }
         __syncthreads();                                           // (the list is read: the next round may overwrite it)
     }
-    rl_store_best(best, s_key, dst, tid);
+    best = mt_block_max(best, s_key, tid, RL_NW);
+    if (tid == 0) *dst = best;
 }
 
 // ---- a group's points (J3, J4) ------------------------------------------------------------------------------------------------
@@ -335,7 +300,7 @@ qs_reloc_points_kernel(QsSweepArgs a, QsRelocArgs m, RlGroupArgs g)
         records++;
         bool hit[3];
         double bx[3], by[3];
-        rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+        sw_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
         #pragma unroll
         for (int q = 0; q < 3; q++) {
             const unsigned long long bal = __ballot(hit[q]);
@@ -412,23 +377,8 @@ qs_reloc_group_score_kernel(QsGeom geo, QsRelocArgs m, RlGroupArgs g)
         }
         __syncthreads();                                           // (the list is read: the next round may overwrite it)
     }
-    rl_store_best(best, s_key, dst, tid);
-}
-
-// max of v over the workgroup, in every thread
-__device__ inline unsigned long long rl_block_max(unsigned long long v, unsigned long long *s_key, int tid)
-{
-    #pragma unroll
-    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(v, d);
-        v = other > v ? other : v;
-    }
-    if ((tid & (QS_WAVE - 1)) == 0) s_key[tid >> 6] = v;
-    __syncthreads();
-    v = s_key[0];
-    for (int w = 1; w < RL_NW; w++) v = s_key[w] > v ? s_key[w] : v;
-    __syncthreads();
-    return v;
+    best = mt_block_max(best, s_key, tid, RL_NW);
+    if (tid == 0) *dst = best;
 }
 
 // ---- the best of a sweep's table row --------------------------------------------------------------------------------------------
@@ -440,7 +390,7 @@ qs_reloc_pick_kernel(QsRelocArgs m)
     const unsigned long long *row = m.table + k * m.table_pitch;
     unsigned long long best = 0;
     for (size_t i = threadIdx.x; i < cnt; i += RL_BLOCK) best = row[i] > best ? row[i] : best;
-    best = rl_block_max(best, s_key, threadIdx.x);
+    best = mt_block_max(best, s_key, threadIdx.x, RL_NW);
     if (threadIdx.x == 0) m.best[k] = best;
 }
 
@@ -475,7 +425,7 @@ __device__ __forceinline__ void rl_finish(const QsGeom &geo, const QsRelocArgs &
         }
         if (tid < 9) rival = max(rival, m.excl[k * 9 + tid]);
     }
-    rival = rl_block_max(rival, s_key, tid);
+    rival = mt_block_max(rival, s_key, tid, RL_NW);
     if (tid != 0) return;
     rl_set_records(r, records);
     r.hits = H;
@@ -511,7 +461,7 @@ qs_reloc_final_kernel(QsSweepArgs a, QsGeom geo, QsRelocArgs m)
     bool hit[3];
     double bx[3], by[3];
     const bool ok = sw_accept(a, k, s_rec, mis, agent);
-    const int H = rl_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
+    const int H = sw_beams(a, s_rec, mis, m.tab, lane, hit, bx, by);
     rl_finish(geo, m, k, ok ? 1 : 0, H, m.out + k, s_key, tid);
 }
 

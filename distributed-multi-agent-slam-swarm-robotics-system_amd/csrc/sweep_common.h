@@ -1,5 +1,5 @@
-// sweep_common.h -- a servo-sweep record on the device: staging and header parse shared by the sweep mapper (sweep.hip) and
-// the sweep matcher (match.hip).
+// sweep_common.h -- a servo-sweep record on the device: staging, header parse and beams shared by the sweep mapper (sweep.hip),
+// the sweep matcher (match.hip) and the relocaliser (reloc.hip).
 #pragma once
 #include "raycast_common.h"
 
@@ -100,6 +100,27 @@ __device__ inline SwHead sw_head_t(const QsSweepArgs &a, size_t k, const unsigne
 __device__ inline SwHead sw_head(const QsSweepArgs &a, size_t k, const unsigned int *s, unsigned int mis)
 {
     return a.g_accept ? sw_head_t<true>(a, k, s, mis) : sw_head_t<false>(a, k, s, mis);
+}
+
+// the 181 beams of a staged record, three a lane: hit flags, d * cos, d * sin of the beam angle (tab: [2][181], the host's
+// table, qs_beam_table); returns H (every wave computes all of it)
+__device__ inline int sw_beams(const QsSweepArgs &a, const unsigned int *s_rec, unsigned int mis, const double *tab, int lane,
+                               bool hit[3], double bx[3], double by[3])
+{
+    int H = 0;
+    #pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const int i = lane + QS_WAVE * q;
+        hit[q] = false; bx[q] = 0.0; by[q] = 0.0;
+        if (i < QS_SWEEP_BEAMS) {
+            const double d = (double)__uint_as_float(sw_u32(s_rec, mis, a.ranges_off + 4u * (unsigned int)i));
+            hit[q] = qs_range_rule(d, a.smin, a.smax).valid;
+            bx[q] = d * tab[i];
+            by[q] = d * tab[QS_SWEEP_BEAMS + i];
+        }
+        H += __popcll(__ballot(hit[q]));
+    }
+    return H;
 }
 
 // matched ingest: the pose the sweep is cast from, rx' = rx + dx, ry' = ry + dy, yaw' = yaw + dyaw (one add each; a match

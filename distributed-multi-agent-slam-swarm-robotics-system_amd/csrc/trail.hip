@@ -9,26 +9,21 @@
 //      per lane;
 //   2. wave 0, a lane per record: parse and accept (qs_ingest's rule), the anchor by a ballot, the bot's drift and offset from
 //      the device, one sincos per record, four points; the hits are compacted by ballot into an LDS list of (qx, qy);
-//   3. the patch of the field about the anchor's cell by field_patch.h's routine, as the sweep matcher builds it.  The launch
-//      sizes the LDS for +- (ceil((max_dist + travel) / res) + 1 + W) cells plus an apron of R; a trail builds only what its own
-//      points can reach, +- (ceil(rmax / res) + 1 + W), rmax the largest distance of a point from the anchor;
-//   4. every wave takes rotations wave, wave + 4, ...: the points turned about the anchor by the host's (S, C), their cells,
-//      compacted by ballot into the rotation's list of 16-bit patch offsets;
-//   5. a lane takes (rotation, iy, FOUR adjacent ix): the scoring loop of qs_match_kernel (match.hip) -- two dword reads and a
-//      v_alignbyte per point, packed byte sums spilled every 255 / (R + 1) points.  The loop is restated here, not shared through
-//      a header: match.hip stays as it compiles today;
-//   6. the total order of the rule is one 64-bit key: max by shuffles within the wave, LDS across the four waves.  No atomics.
+//   3. the patch of the field about the anchor's cell (wm_build_patch).  The launch sizes the LDS for +- (ceil((max_dist +
+//      travel) / res) + 1 + W) cells plus an apron of R; a trail builds only what its own points can reach, +- (ceil(rmax / res)
+//      + 1 + W), rmax the largest distance of a point from the anchor;
+//   4. every wave takes rotations wave, wave + 4, ...: the points turned about the anchor by the host's (S, C), into the
+//      rotation's list (wm_list);
+//   5. scores, the best key and the gate (wm_best, wm_result).  No atomics.
+// Steps 3 to 5 are the window search of window_match.h, shared with the sweep matcher (match.hip).
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 
 #include "raycast_common.h"
-#include "field_patch.h"
+#include "window_match.h"
 
-#define TR_BLOCK 256
-#define TR_NW (TR_BLOCK / QS_WAVE)
 #define TR_PTS (4 * QS_TRAIL_MAX_RECORDS)    // points of one trail, and 16-bit offsets per rotation (a multiple of 4: 8-byte reads)
-#define TR_NROT_MAX (2 * QS_MATCH_MAX_ANGLE_STEPS + 1)
 #define TR_MAX_STRIDE 64                     // records are staged through LDS when stride <= 64 bytes
 #define TR_CHUNK 512                         // trails per launch: their first records travel in the kernel's arguments
 
@@ -38,28 +33,13 @@ struct QsTrailArgs {
     size_t stride, nrec;
     const double *offset, *drift; // [max_agent + 1], [max_agent + 1][2]
     int max_agent;
-    int R, W, T, min_hits, min_percent;
-    int half;                     // the largest patch: the anchor's cell +- half, half = reach + 1 + W (a trail builds what its points reach)
-    int SA, pitch;                // side with the apron (2 (half + R) + 1) and bytes per row (a multiple of 4, an odd number of dwords)
-    unsigned int off_b;           // byte offset of the second LDS region (dilation scratch, then the offset lists)
-    double step, travel2;
-    const unsigned int *stamps;
+    WmArgs w;
+    double travel2;
     qs_trail_match *out;          // [groups of the launch]
     double *rot;                  // [nrec][2] or nullptr
     unsigned short start[TR_CHUNK + 1];       // first record of each group of the launch (at most 512 x 64 = 2^15 records)
-    double sc[TR_NROT_MAX][2];    // (S, C) of it * angle_step, it = -T .. T, the host's libm
+    double sc[WM_NROT_MAX][2];    // (S, C) of it * angle_step, it = -T .. T, the host's libm
 };
-
-// Bytes per row of a patch SA cells a side: a multiple of 4 and an odd number of dwords, so that rows start on different banks
-// -- unless the largest offset a rotation's list can hold would then pass 16 bits.  A listed cell lies in [R + W, SA - 1 - R - W]
-// on both axes and its offset is that of candidate ix = iy = -W, so the largest is (SA - 1 - R - 2 W) (pitch + 1).  Only the
-// widest patches with R = W = 0 get there (SA 253: 252 * 261 = 65 772); they keep the unpadded pitch (252 * 257 = 64 764, and
-// SA <= 255 always fits).  The kernel and the launch both ask here, so the LDS the launch sizes is what the kernel lays out.
-__host__ __device__ inline int tr_pitch(int SA, int R, int W)
-{
-    const int flat = (SA + 3) & ~3, odd = ((flat >> 2) & 1) ? flat : flat + 4;
-    return (SA - 1 - R - 2 * W) * (odd + 1) <= 0xffff ? odd : flat;
-}
 
 // the record's 42 bytes as eleven dwords from LDS (the record starts at any byte): twelve aligned reads shifted into place
 __device__ inline void tr_record_lds(const unsigned int *s_raw, unsigned int off, unsigned int r[11])
@@ -72,14 +52,14 @@ __device__ inline void tr_record_lds(const unsigned int *s_raw, unsigned int off
     for (int q = 0; q < 11; q++) r[q] = __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh);
 }
 
-__global__ void __launch_bounds__(TR_BLOCK)
+__global__ void __launch_bounds__(WM_BLOCK)
 qs_trail_kernel(QsTrailArgs m, QsGeom geo)
 {
     extern __shared__ __align__(16) unsigned char s_dyn[];
     __shared__ unsigned int s_raw[QS_TRAIL_MAX_RECORDS * TR_MAX_STRIDE / 4 + 2];
     __shared__ double2 s_q[TR_PTS];
-    __shared__ int s_cnt[TR_NROT_MAX];
-    __shared__ unsigned long long s_key[TR_NW];
+    __shared__ int s_cnt[WM_NROT_MAX];
+    __shared__ unsigned long long s_key[WM_NW];
     __shared__ double s_anchor[4];                                  // ax, ay, the largest |q|^2 of a point, unused
     __shared__ int s_head[4];                                      // H, records, anchor, agent
     __shared__ int s_score0;
@@ -87,7 +67,7 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
     const unsigned int grp = blockIdx.x;
     const size_t rec0 = m.start[grp];
     const int K = (int)m.start[grp + 1] - (int)m.start[grp];       // 1 .. 64
-    const int nrot = 2 * m.T + 1;
+    const int nrot = 2 * m.w.T + 1;
     const bool staged = m.stride <= TR_MAX_STRIDE;
 
     // ---- stage: the byte range of the group's records widened to dword boundaries -------------------------------------------------
@@ -98,7 +78,7 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
         const unsigned int *src = (const unsigned int *)(addr0 - mis);
         const unsigned int ndw = (mis + (unsigned int)K * (unsigned int)m.stride + 3u) / 4u;       // <= 1025
         const unsigned long long buf0 = (unsigned long long)m.pkts, buf1 = buf0 + m.nrec * m.stride;
-        for (unsigned int k = tid; k < ndw; k += TR_BLOCK) {
+        for (unsigned int k = tid; k < ndw; k += WM_BLOCK) {
             const unsigned long long a = (unsigned long long)(src + k);
             unsigned int v;
             if (a >= buf0 && a + 4 <= buf1) v = src[k];
@@ -112,7 +92,7 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
         }
         // (a record's twelve-dword window may reach one dword past the staged range: its bytes are never looked at, but the
         // read stays inside s_raw, which holds 1026 dwords)
-        for (unsigned int k = ndw + tid; k < ndw + 12u && k < sizeof s_raw / 4; k += TR_BLOCK) s_raw[k] = 0u;
+        for (unsigned int k = ndw + tid; k < ndw + 12u && k < sizeof s_raw / 4; k += WM_BLOCK) s_raw[k] = 0u;
     }
     __syncthreads();
 
@@ -198,117 +178,41 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
     // ---- the patch of the field about the anchor's cell ---------------------------------------------------------------------------
     // The launch sizes the LDS for the reach travel allows; THIS trail's points lie within rmax of its anchor under every
     // rotation, so the patch it builds is +- (ceil(rmax / res) + 1 + W) cells plus the apron, never more than the launch's.
-    int half = m.half;
-    const double need = ceil(sqrt(s_anchor[2]) / geo.res) + 1.0 + (double)m.W;
+    int half = m.w.half;
+    const double need = ceil(sqrt(s_anchor[2]) / geo.res) + 1.0 + (double)m.w.W;
     if (need < (double)half) half = (int)need;                     // (not a number: the launch's)
-    const int SA = 2 * (half + m.R) + 1;
-    const int pitch = tr_pitch(SA, m.R, m.W);
-    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.off_b);
-    int c0x = 0, c0y = 0;
-    bool c0ok = qs_w2g_i32(ax, geo.ox, geo, c0x);
-    c0ok = qs_w2g_i32(ay, geo.oy, geo, c0y) && c0ok;
-    if (!c0ok) { c0x = 0; c0y = 0; }                               // (no point of such a trail has a cell: nothing reads the patch)
-    const int gx0 = c0x - half - m.R, gy0 = c0y - half - m.R;  // grid cell of patch byte (0, 0); |c0| <= 2^30
-    mt_build_patch(A, B, m.stamps, geo.size, gx0, gy0, SA, pitch, m.R, tid, TR_BLOCK);
+    unsigned int *A = (unsigned int *)s_dyn, *B = (unsigned int *)(s_dyn + m.w.off_b);
+    const WmPatch p = wm_build_patch(m.w, geo, ax, ay, half, A, B, tid);
 
     // ---- per rotation the patch offsets of the points' cells ------------------------------------------------------------------------
     unsigned short *OFF = (unsigned short *)B;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const int lo_ok = m.R + m.W, hi_ok = SA - 1 - m.R - m.W;     // a cell every shift of which stays inside the exact part
-    for (int ti = wave; ti < nrot; ti += TR_NW) {
+    for (int ti = wave; ti < nrot; ti += WM_NW) {
         const double S = m.sc[ti][0], C = m.sc[ti][1];
         int cnt = 0;
         for (int p0 = 0; p0 < H; p0 += QS_WAVE) {
-            bool in = false;
-            unsigned int off = 0;
-            if (p0 + lane < H) {
-                const double2 q = s_q[p0 + lane];
-                const double ex = ax + (C * q.x - S * q.y), ey = ay + (S * q.x + C * q.y);
-                int cx, cy;
-                bool ok = qs_w2g_i32(ex, geo.ox, geo, cx);
-                ok = qs_w2g_i32(ey, geo.oy, geo, cy) && ok;
-                if (ok && c0ok) {
-                    const long long px = (long long)cx - gx0, py = (long long)cy - gy0;
-                    in = px >= lo_ok && px <= hi_ok && py >= lo_ok && py <= hi_ok;
-                    off = (unsigned int)((py - m.W) * pitch + (px - m.W));
-                }
-            }
-            const unsigned long long bal = __ballot(in);
-            if (in) OFF[ti * TR_PTS + cnt + __popcll(bal & lt)] = (unsigned short)off;
-            cnt += __popcll(bal);
+            const bool live = p0 + lane < H;
+            const double2 q = live ? s_q[p0 + lane] : make_double2(0.0, 0.0);
+            wm_list(p, geo, live, ax + (C * q.x - S * q.y), ay + (S * q.x + C * q.y), OFF + ti * TR_PTS, cnt, lane);
         }
         if (lane == 0) s_cnt[ti] = cnt;
     }
     __syncthreads();
 
-    // ---- scores: a lane per (rotation, iy, four ix) --------------------------------------------------------------------------------
-    const int ny = 2 * m.W + 1, G = (ny + 3) >> 2, per_rot = ny * G, NI = nrot * per_rot;
-    const int span = (255 / (m.R + 1)) & ~3;                       // points whose byte sums cannot overflow
-    unsigned long long best = 0;
-    for (int j = tid; j < NI; j += TR_BLOCK) {
-        const int ti = j / per_rot, rem = j - ti * per_rot, yi = rem / G, g = rem - yi * G;
-        const unsigned int lane_off = (unsigned int)(yi * pitch + 4 * g);
-        const unsigned short *o = OFF + ti * TR_PTS;
-        const int cnt = s_cnt[ti];
-        unsigned int lo = 0, hi = 0;
-        for (int b0 = 0; b0 < cnt; b0 += span) {
-            const int b1 = min(b0 + span, cnt);
-            unsigned int acc = 0;
-            int b = b0;
-            for (; b + 4 <= b1; b += 4) {
-                const uint2 q = *(const uint2 *)(o + b);
-                acc += mt_look(A, lane_off + (q.x & 0xffffu));
-                acc += mt_look(A, lane_off + (q.x >> 16));
-                acc += mt_look(A, lane_off + (q.y & 0xffffu));
-                acc += mt_look(A, lane_off + (q.y >> 16));
-            }
-            for (; b < b1; b++) acc += mt_look(A, lane_off + o[b]);
-            lo += acc & 0x00ff00ffu;
-            hi += (acc >> 8) & 0x00ff00ffu;
-        }
-        const unsigned int sc[4] = {lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16};
-        const int it = ti - m.T, iy = yi - m.W;
-        #pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int ix = 4 * g + e - m.W;
-            if (ix > m.W) break;
-            // score, then small ix^2 + iy^2, small |it|, small it, small iy, small ix: every field "larger is better"
-            const unsigned long long key = ((unsigned long long)sc[e] << 45) | ((unsigned long long)(32767 - (ix * ix + iy * iy)) << 30)
-                                         | ((unsigned long long)(m.T - abs(it)) << 23) | ((unsigned long long)(m.T - it) << 16)
-                                         | ((unsigned long long)(m.W - iy) << 8) | (unsigned long long)(m.W - ix);
-            best = key > best ? key : best;
-            if (it == 0 && iy == 0 && ix == 0) s_score0 = (int)sc[e];
-        }
-    }
-    #pragma unroll
-    for (int d = QS_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long other = __shfl_xor(best, d);
-        best = other > best ? other : best;
-    }
-    if (lane == 0) s_key[wave] = best;
-    __syncthreads();
+    const unsigned long long best = wm_best(p, A, OFF, TR_PTS, s_cnt, s_key, &s_score0, tid);
     if (tid == 0) {
-        for (int w = 1; w < TR_NW; w++) best = s_key[w] > best ? s_key[w] : best;
         qs_trail_match r;
         memset(&r, 0, sizeof r);
-        r.ix = m.W - (int)(best & 255u);
-        r.iy = m.W - (int)((best >> 8) & 255u);
-        r.it = m.T - (int)((best >> 16) & 127u);
-        r.score = (int)(best >> 45);
-        r.score0 = s_score0;
-        r.hits = H;
+        wm_result(m.w, geo.res, best, s_score0, H, r);
         r.records = records;
         r.anchor = s_head[2];
         r.agent = (uint8_t)s_head[3];
-        r.accepted_match = H >= m.min_hits && (long long)r.score * 100 >= (long long)m.min_percent * H * (m.R + 1);
         r.ax = ax; r.ay = ay;
-        if (r.accepted_match) { r.dx = (double)r.ix * geo.res; r.dy = (double)r.iy * geo.res; r.dyaw = (double)r.it * m.step; }
         m.out[grp] = r;
     }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-struct QsTrailSetup { int R, W, T, min_hits, min_percent, reach; double step, travel; };
+struct QsTrailSetup : QsMatchSetup { double travel; };
 
 // T8 and T1: the limits of qs_match_params, the travel, the reach of the patch, the context, the groups
 static int trail_setup(qs_ctx *c, const qs_match_params *params, size_t n, size_t stride, const int32_t *gsize, size_t n_groups,
@@ -319,14 +223,13 @@ static int trail_setup(qs_ctx *c, const qs_match_params *params, size_t n, size_
     char msg[256];
     const char *bad = qs_match_params_check(params, p);            // the limits of qs_match_params: match.hip's
     if (!bad && !(isfinite(travel) && travel >= 0)) bad = "travel must be finite and not negative";
-    const double reach = bad ? 0.0 : ceil((c->cfg.max_dist + travel) / c->cfg.res);
-    if (!bad && !(reach + p.radius + 2 <= QS_MATCH_MAX_REACH))
-        bad = "max_dist + travel is too large for this resolution: ceil((max_dist + travel) / res) + radius + 2 exceeds QS_MATCH_MAX_REACH";
-    else if (!bad && reach + p.window + p.radius + 2 > QS_MATCH_MAX_REACH)
-        bad = "window is too large: ceil((max_dist + travel) / res) + window + radius + 2 exceeds QS_MATCH_MAX_REACH";
-    else if (!bad && stride < QS_PACKET_SIZE_V1) bad = "stride must be at least 41";
-    else if (!bad && (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)) bad = "sharded contexts (seq_stride > 1, shard_bots > 0) do not match trails";
-    else if (!bad && n >= ((size_t)1 << 31)) bad = "at most 2^31 - 1 records per call";
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
+    const int rc = qs_match_reach_setup(c, who, p, ceil((c->cfg.max_dist + travel) / c->cfg.res), "max_dist + travel", "(max_dist + travel)", ts);
+    if (rc != QS_OK) return rc;
+    ts.travel = travel;
+    if (stride < QS_PACKET_SIZE_V1) bad = "stride must be at least 41";
+    else if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0) bad = "sharded contexts (seq_stride > 1, shard_bots > 0) do not match trails";
+    else if (n >= ((size_t)1 << 31)) bad = "at most 2^31 - 1 records per call";
     if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
     size_t sum = 0;
     for (size_t g = 0; g < n_groups; g++) {
@@ -337,8 +240,6 @@ static int trail_setup(qs_ctx *c, const qs_match_params *params, size_t n, size_
         sum += (size_t)gsize[g];
     }
     if (sum != n) { snprintf(msg, sizeof msg, "%s: the group sizes must sum to n", who); return qs_fail(c, QS_E_INVAL, msg); }
-    ts.R = p.radius; ts.W = p.window; ts.T = p.angle_steps; ts.min_hits = p.min_hits; ts.min_percent = p.min_percent;
-    ts.reach = (int)reach; ts.step = p.angle_step; ts.travel = travel;
     return QS_OK;
 }
 
@@ -352,22 +253,13 @@ static hipError_t trail_launch(qs_ctx *c, const QsTrailSetup &ts, const unsigned
     memset(&m, 0, sizeof m);
     m.stride = stride;
     m.offset = c->d_offset.p; m.drift = c->d_drift.p; m.max_agent = c->cfg.max_agent;
-    m.R = ts.R; m.W = ts.W; m.T = ts.T; m.min_hits = ts.min_hits; m.min_percent = ts.min_percent;
-    m.half = ts.reach + 1 + ts.W;
-    m.SA = 2 * (m.half + ts.R) + 1;                               // <= 253 (trail_setup)
-    m.pitch = tr_pitch(m.SA, ts.R, ts.W);
-    const size_t a_bytes = ((size_t)m.SA * m.pitch + 16 + 15) & ~(size_t)15;
-    const size_t b_bytes = std::max((size_t)m.SA * m.pitch, (size_t)(2 * ts.T + 1) * TR_PTS * sizeof(unsigned short));
-    m.off_b = (unsigned int)a_bytes;
-    m.step = ts.step; m.travel2 = ts.travel * ts.travel;
-    m.stamps = c->d_stamps.p;
+    size_t lds;
+    HIPRET(wm_args(c, ts, (const void *)qs_trail_kernel, TR_PTS, m.w, lds));
+    m.travel2 = ts.travel * ts.travel;
     for (int it = -ts.T; it <= ts.T; it++) {                       // T6: the host's libm
         const double th = (double)it * ts.step;
         m.sc[it + ts.T][0] = sin(th); m.sc[it + ts.T][1] = cos(th);
     }
-    const size_t lds = a_bytes + ((b_bytes + 15) & ~(size_t)15);
-    if (lds > 32 * 1024)                                           // the largest windows: up to 2 x 65 KiB of the CU's 160
-        HIPRET(hipFuncSetAttribute((const void *)qs_trail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     size_t rec0 = 0;
     for (size_t g0 = 0; g0 < n_groups; g0 += TR_CHUNK) {
         const unsigned int ng = (unsigned int)std::min((size_t)TR_CHUNK, n_groups - g0);
@@ -378,7 +270,7 @@ static hipError_t trail_launch(qs_ctx *c, const QsTrailSetup &ts, const unsigned
         }
         m.pkts = d_pkts + rec0 * stride; m.lens = d_lens ? d_lens + rec0 : nullptr; m.nrec = nr;
         m.out = d_out + g0; m.rot = d_rot ? d_rot + 2 * rec0 : nullptr;
-        hipLaunchKernelGGL(qs_trail_kernel, dim3(ng), dim3(TR_BLOCK), lds, c->stream, m, c->geom);
+        hipLaunchKernelGGL(qs_trail_kernel, dim3(ng), dim3(WM_BLOCK), lds, c->stream, m, c->geom);
         HIPRET(hipGetLastError());
         rec0 += nr;
     }

@@ -61,8 +61,10 @@ def _sweeps(grid, geom, cells, n=3):
 
 
 @GEOMETRY
-@RADIUS
+@pytest.mark.parametrize("radius", [0, 2, 7])
 def test_match_sweeps_at_the_limit(pkg, rooms, name, radius):
+    """Radius 0 with window 0 is the widest patch there is: 125 cells of reach, 253 cells a side, the one shape whose rows go
+    unpadded (window_match.h: wm_pitch) and whose 16-bit patch offsets are fullest."""
     m, grid = rooms[name]
     geom = SK.GEOMETRIES[name]
     res = geom[0]

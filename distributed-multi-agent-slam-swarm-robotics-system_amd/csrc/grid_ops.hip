@@ -207,7 +207,10 @@ qs_reset_small_kernel(double *__restrict__ drift, int n_drift, unsigned long lon
                       double *__restrict__ ekf, int n_ekf, double *__restrict__ ekf_prev, int n_prev, unsigned int *__restrict__ flags)
 {
     const int stride = gridDim.x * 256;
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < n_ekf; t += stride) ekf[t] = 0.0;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < n_ekf; t += stride) {
+        const int e = t % 44;                              // a filter before its init is the constructed object: x = 0, P = I  ekf.cpp:5-13
+        ekf[t] = (e >= 6 && e < 42 && (e - 6) % 7 == 0) ? 1.0 : 0.0;
+    }
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n_prev; t += stride) ekf_prev[t] = 0.0;
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n_drift; t += stride) drift[t] = 0.0;
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n_gb; t += stride) graph_batch[t] = 0ull;

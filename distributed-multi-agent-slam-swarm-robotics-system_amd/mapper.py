@@ -1022,7 +1022,8 @@ class QuasarMapper:
                   "qs_rasterise")
         return grid, origin
 
-    # -- ICP / voxel down-sample: map_merger.py:45-60 (Open3D semantics, parity unpinned) ---------
+    # -- ICP / voxel down-sample: map_merger.py:45-60 (Open3D semantics: N3, parity unpinned; grid_to_pcd and rasterise
+    #    above are pinned against the reference's own methods, tests/golden/merger_calls.npz) ---------
     def icp(self, src_xy, dst_xy, max_dist=1.0, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
         """registration_icp(source, target, max_dist, I, PointToPoint, max_iteration) on planar clouds.
         Returns (T 3x3, fitness, inlier_rmse, iterations)."""

@@ -1101,7 +1101,10 @@ int qs_render_view_device(qs_ctx *ctx, const qs_view_params *params, const qs_vi
  * relative), smaller ones step by step.  QS_CNT_EKF_WRAP_CLAMP counts chunks whose heading-wrap count
  * had to be clamped (a sign of absurd inputs; 0 on every stream seen). */
 /* batched over bots: for k in 0..n: predict(omega_m[k], t[k]) then update(z_v[k], z_omega[k])
- * on bot_ids[k] (each bot at most once per call); do_update == 0: predict only */
+ * on bot_ids[k] (each bot at most once per call); do_update == 0: predict only.  qs_ekf_init is the constructor plus
+ * EKF::init (P = I again).  Before a bot's first init, predict and update do nothing and qs_ekf_state reports the
+ * constructed object: x = 0, P = I (qs_create and qs_reset store that).  A checkpoint written before they did holds
+ * all zeros for such a bot and restores them: P = 0 until the bot's first init. */
 int qs_ekf_init(qs_ctx *ctx, int32_t bot, double t, const double x0[6]);
 int qs_ekf_step(qs_ctx *ctx, const int32_t *bot_ids, const double *omega_m, const double *t,
                 const double *z_v, const double *z_omega, size_t n, int32_t do_update);

@@ -8,9 +8,11 @@
  * Parity status: PINNED for the mapper path (rows A1-A6, A8-A10 of SURVEY.md section 8)
  * against fixtures produced by importing the reference's own Python in the build
  * container (tests/golden/make_golden.py -> the .npz files and kat.json under tests/golden).
- * PARITY UNPINNED for the EKF (A7: reference is Arduino/Eigen C++, not buildable here,
- * no vectors exist) and for map_merger's rasterise (A11: needs rclpy/open3d, absent);
- * those two are restated from the source text and checked with hand-derived cases.
+ * PINNED for the EKF (A7) by tests/golden/ekf_ref.npz: the firmware's own ekf.cpp, compiled unmodified against the
+ * stand-in Arduino / Eigen headers of oracle/ref/stub, on the streams of tests/golden/make_ekf_golden.py; x and P are
+ * bit-equal (tests/test_ekf_reference_cpu.py).  PINNED for map_merger's grid_to_pcd / publish_global_map (A11) by
+ * tests/golden/merger_calls.npz: the reference's own methods, loaded with stand-in rclpy / nav_msgs / open3d modules
+ * (tests/test_merger_reference_cpu.py).  What Open3D computes (ICP, voxel rounding: N3) stays unpinned.
  *
  * All citations are into /root/reference/.  Plain C, fp64, libm cos/sin/sqrt/pow --
  * the same libm CPython's math module calls.  Compile with -O2 -ffp-contract=off.
@@ -295,7 +297,10 @@ void qso_ekf_packet(double *f, double *prev, double t, double x, double y, doubl
 void qso_enable_ekf(mapper_t *m, double metres_per_tick)
 {
     m->ekf_on = 1; m->ekf_mpt = metres_per_tick;
-    if (!m->ekf) { m->ekf = calloc((size_t)(m->max_agent + 1) * 44, sizeof(double)); m->ekf_prev = calloc((size_t)(m->max_agent + 1) * 4, sizeof(double)); }
+    if (!m->ekf) {
+        m->ekf = calloc((size_t)(m->max_agent + 1) * 44, sizeof(double)); m->ekf_prev = calloc((size_t)(m->max_agent + 1) * 4, sizeof(double));
+        for (int b = 0; b <= m->max_agent; b++) for (int i = 0; i < 6; i++) m->ekf[(size_t)b * 44 + 6 + 7 * i] = 1.0;   /* EKF::EKF: P = I  ekf.cpp:7 */
+    }
 }
 const double *qso_ekf_state(const mapper_t *m, int bot) { return m->ekf + (size_t)bot * 44; }
 

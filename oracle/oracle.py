@@ -2,7 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg, never by the product package.  See oracle.c for the parity status
-(mapper path pinned by tests/golden; EKF and map_merger rasterise "parity unpinned").
+(mapper path, EKF and map_merger's grid_to_pcd / rasterise pinned by tests/golden; ICP and voxel rounding against Open3D
+unpinned).  build() also installs oracle/ref/Makefile as oracle/_ref/Makefile where the reference tree exists: the recipe of
+oracle/_ref/ekf_ref, the firmware's own ekf.cpp behind oracle/ref/ekf_driver.cpp.
 """
 import ctypes as C
 import os
@@ -12,12 +14,34 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "liboracle.so")
+REFERENCE = "/root/reference"                      # present in the build container only
+REF_DIR = os.path.join(_HERE, "_ref")              # reference binaries (never committed)
+EKF_REF = os.path.join(REF_DIR, "ekf_ref")         # the firmware's own ekf.cpp behind oracle/ref/ekf_driver.cpp
+
+
+def _install_ref_recipe():
+    """Where the reference tree exists: oracle/ref/Makefile -> oracle/_ref/Makefile, which __graft_entry__.build() runs."""
+    if not os.path.isdir(REFERENCE):
+        return
+    with open(os.path.join(_HERE, "ref", "Makefile"), "rb") as f:
+        recipe = f.read()
+    dst = os.path.join(REF_DIR, "Makefile")
+    try:
+        with open(dst, "rb") as f:
+            if f.read() == recipe:
+                return
+    except OSError:
+        pass
+    os.makedirs(REF_DIR, exist_ok=True)
+    with open(dst, "wb") as f:
+        f.write(recipe)
 
 
 def build(force=False):
     src = os.path.join(_HERE, "oracle.c")
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
         subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
+    _install_ref_recipe()
     return _SO
 
 
@@ -278,6 +302,7 @@ class OracleEKF:
 
     def __init__(self, n_bots):
         self.f = np.zeros((n_bots, self.STRIDE), dtype=np.float64)
+        self.f[:, 6:42] = np.eye(6).reshape(36)    # EKF::EKF (ekf.cpp:5-13): P = I from construction, before any init
         self.prev = np.zeros((n_bots, 4), dtype=np.float64)
 
     def init(self, b, t, x0):

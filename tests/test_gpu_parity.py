@@ -199,9 +199,9 @@ def _oracle_ekf_over_stream(g, metres_per_tick=0.0107):
 
 
 def test_ekf_ingest_matches_oracle(pkg):
-    """EKF (A7) is "parity unpinned" against the reference (Arduino/Eigen, no vectors exist): the HIP
-    filter is checked against the build's own CPU restatement of ekf.cpp, tolerance 1e-5 (north_star),
-    expected ~1e-12."""
+    """EKF (A7): the HIP filter against the build's CPU restatement of ekf.cpp (itself bit-equal to the firmware's
+    own ekf.cpp on tests/golden/ekf_ref.npz: tests/test_ekf_reference_cpu.py; the kernels against that file:
+    tests/test_gpu_ekf_reference.py), tolerance 1e-5 (north_star), expected ~1e-12."""
     g = load("session_512")
     ek = _oracle_ekf_over_stream(g)
     with make_mapper(pkg, g, enable_ekf=True) as m:
@@ -355,9 +355,9 @@ def test_stamp_epoch_rebase_keeps_order(pkg):
 
 
 def test_map_merger_ops_match_oracle(pkg):
-    """A11: MapMerger.grid_to_pcd / publish_global_map restated (map_merger.py:64-127).  Parity
-    unpinned against the reference (needs rclpy/open3d); checked against the CPU restatement and a
-    hand-built 4x4 case."""
+    """A11: MapMerger.grid_to_pcd / publish_global_map restated (map_merger.py:64-127), against the CPU
+    restatement and a hand-built 4x4 case.  Pinned against the reference's own methods by
+    tests/golden/merger_calls.npz (tests/test_merger_reference_cpu.py, tests/test_gpu_merger_reference.py)."""
     small = np.full((4, 4), -1, dtype=np.int8); small[1, 2] = 100; small[3, 0] = 51; small[0, 0] = 50
     with pkg.QuasarMapper() as m:
         xy = m.grid_to_pcd(small, 0.5, -1.0, 2.0)

@@ -115,7 +115,15 @@ class QsTrailMatch(C.Structure):
                 ("ax", C.c_double), ("ay", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("dyaw", C.c_double)]
 
 
-QS_TRAIL_MAX_RECORDS = 64                                                        # include/quasar_slam.h, "trail matching"
+class QsTrailReloc(C.Structure):
+    """struct qs_trail_reloc (include/quasar_slam.h)."""
+    _fields_ = [("gx", C.c_int32), ("gy", C.c_int32), ("j", C.c_int32), ("score", C.c_int32), ("hits", C.c_int32),
+                ("gx2", C.c_int32), ("gy2", C.c_int32), ("j2", C.c_int32), ("score2", C.c_int32), ("status", C.c_int32),
+                ("records", C.c_uint8), ("accepted", C.c_uint8), ("agent", C.c_uint8), ("pad", C.c_uint8), ("anchor", C.c_int32),
+                ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("ax", C.c_double), ("ay", C.c_double)]
+
+
+QS_TRAIL_MAX_RECORDS = 64                                                     # include/quasar_slam.h, "trail matching"
 
 
 class QsMergeResult(C.Structure):
@@ -215,6 +223,8 @@ SIGNATURES = {
     "qs_relocalise_groups_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.c_double, _vp]),
     "qs_match_trails": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
     "qs_match_trails_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
+    "qs_relocalise_trails": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
+    "qs_relocalise_trails_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_double, _vp, _vp]),
     "qs_sense_ranges": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_ranges_device": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     "qs_sense_sweeps": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),

@@ -27,11 +27,20 @@
 //      rather than a walk in pieces that would rebuild the offsets or keep partial sums per piece;
 //   3-5. pick as it is; the EXCL instantiation and the final step in their group forms.
 // Groups run RL_CHUNK to a launch; their first records travel as a kernel argument (RlGroupArgs::start).
+//
+// A TRAIL of 42-byte packets ("trail relocalisation", K1-K8) is a group whose points come from the packets themselves:
+//   0. qs_reloc_trail_points_kernel, one wave per trail and a lane per record: the records staged and parsed as the trail matcher
+//      does (trail_common.h), the anchor by a ballot, one sincos per counting record, four points a record about the anchor,
+//      the hits ballot-compacted into the trail's slice of the group workspace; anchor, agent and the anchor's fields behind;
+//   2'-4. the group form's scoring kernel, pick and EXCL instantiation as they are, over that list;
+//   5. qs_reloc_trail_final_kernel: rl_finish, then the trail's own fields.
+// Trails run RL_CHUNK to a launch (RlTrailArgs::start).
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 
 #include "sweep_common.h"
+#include "trail_common.h"
 #include "field_patch.h"
 #include "compact.h"
 
@@ -83,6 +92,19 @@ struct RlGroupArgs {
     unsigned int *meta;           // [RL_CHUNK][2] H, counting records
     qs_group_reloc *out;          // [groups of the chunk]
     unsigned int start[RL_CHUNK + 1];   // group g's records are [start[g], start[g + 1])
+};
+
+// what the trail form adds, per chunk of at most RL_CHUNK trails; records are counted from the chunk's first.  The points and
+// H / counting records go where the group form keeps them (RlGroupArgs::pts, meta)
+struct RlTrailArgs {
+    TrRecords r;                  // the chunk's records
+    int max_agent;
+    double travel2;
+    double *rot;                  // [records of the chunk][2] or nullptr
+    int *who;                     // [RL_CHUNK][2] anchor (index within the trail, -1: none), agent
+    double *at;                   // [RL_CHUNK][2] X_a, Y_a
+    qs_trail_reloc *out;          // [trails of the chunk]
+    unsigned int start[RL_CHUNK + 1];   // trail t's records are [start[t], start[t + 1])
 };
 
 // ---- census ------------------------------------------------------------------------------------------------------------------
@@ -315,6 +337,61 @@ qs_reloc_points_kernel(QsSweepArgs a, QsRelocArgs m, RlGroupArgs g)
     if (lane == 0) { g.meta[2 * k] = (unsigned int)H; g.meta[2 * k + 1] = (unsigned int)records; }
 }
 
+// ---- a trail's points (K2-K4) ---------------------------------------------------------------------------------------------------
+// one wave per trail of the chunk, a lane per record: at most 4 x 64 = 256 points, the head of the RL_GPTS a slice holds
+__global__ void __launch_bounds__(QS_WAVE)
+qs_reloc_trail_points_kernel(RlTrailArgs t, QsGeom geo, double *pts, unsigned int *meta)
+{
+    __shared__ unsigned int s_raw[TR_RAW_DW];
+    const int lane = threadIdx.x;
+    const size_t k = blockIdx.x;
+    const size_t rec0 = t.start[k];
+    const int K = (int)(t.start[k + 1] - t.start[k]);               // 1 .. 64
+    const bool staged = t.r.stride <= TR_MAX_STRIDE;
+    const unsigned int mis = staged ? tr_stage(t.r, rec0, K, s_raw, lane, QS_WAVE) : 0u;
+    __syncthreads();
+
+    bool ok = false;
+    int agent = 0;
+    float x = 0.f, y = 0.f, yaw = 0.f, dist[4] = {0.f, 0.f, 0.f, 0.f};
+    if (lane < K)
+        ok = tr_parse(t.r, t.max_agent, rec0 + lane, staged, s_raw, mis + (unsigned int)lane * (unsigned int)t.r.stride, agent, x, y, yaw, dist);
+    const unsigned long long acc = __ballot(ok);
+    const int anchor = acc ? 63 - __clzll((long long)acc) : -1;    // K2: the last accepted record
+    const int src = anchor >= 0 ? anchor : 0;
+    const int bot = anchor >= 0 ? __shfl(agent, src) : 0;
+    const double X = ok ? (double)x : 0.0, Y = ok ? (double)y : 0.0;
+    const double ax = anchor >= 0 ? __shfl(X, src) : 0.0, ay = anchor >= 0 ? __shfl(Y, src) : 0.0;
+    const double dx = X - ax, dy = Y - ay;
+    const bool counts = ok && agent == bot && dx * dx + dy * dy <= t.travel2;     // K3
+    const unsigned long long cb = __ballot(counts);
+    double s = 0.0, c = 0.0;
+    if (counts) qs_sincos((double)yaw, &s, &c);
+    if (t.rot && lane < K) { double *o = t.rot + (rec0 + lane) * 2; o[0] = s; o[1] = c; }
+    // T5: front (c, s), left (-s, c), back (-c, -s), right (s, -c)
+    const double ux[4] = {c, -s, -c, s}, uy[4] = {s, c, -s, -c};
+    double *px = pts + k * 2 * RL_GPTS, *py = px + RL_GPTS;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int H = 0;                                                     // (the same in every lane)
+    #pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double d = (double)dist[j];
+        const bool hit = counts && geo.min_dist < d && d <= geo.max_dist;
+        const unsigned long long bal = __ballot(hit);
+        if (hit) {
+            const int i = H + __popcll(bal & lt);                  // < 256
+            px[i] = dx + d * ux[j];
+            py[i] = dy + d * uy[j];
+        }
+        H += __popcll(bal);
+    }
+    if (lane == 0) {
+        meta[2 * k] = (unsigned int)H; meta[2 * k + 1] = (unsigned int)__popcll(cb);
+        t.who[2 * k] = anchor; t.who[2 * k + 1] = bot;
+        t.at[2 * k] = ax; t.at[2 * k + 1] = ay;
+    }
+}
+
 // ---- scores of one (group, tile) ----------------------------------------------------------------------------------------------
 template <bool EXCL>
 __global__ void __launch_bounds__(RL_BLOCK)
@@ -397,6 +474,7 @@ qs_reloc_pick_kernel(QsRelocArgs m)
 // ---- rival, gate, outputs ---------------------------------------------------------------------------------------------------------
 __device__ inline void rl_set_records(qs_sweep_reloc &r, int n) { r.accepted_record = (unsigned char)n; }
 __device__ inline void rl_set_records(qs_group_reloc &r, int n) { r.records = (unsigned char)n; }
+__device__ inline void rl_set_records(qs_trail_reloc &r, int n) { r.records = (unsigned char)n; }
 
 // sweep or group k with H hit points from `records` counting records: rival = max of the table entries of all tiles outside the
 // square round the best and of the re-scored ones; G7-G9.  Every thread of the workgroup calls it
@@ -473,11 +551,28 @@ qs_reloc_group_final_kernel(QsGeom geo, QsRelocArgs m, RlGroupArgs g)
     rl_finish(geo, m, k, (int)g.meta[2 * k + 1], (int)g.meta[2 * k], g.out + k, s_key, threadIdx.x);
 }
 
+// K7: the group form's result, then what a trail adds (thread 0 wrote the result and completes it)
+__global__ void __launch_bounds__(RL_BLOCK)
+qs_reloc_trail_final_kernel(QsGeom geo, QsRelocArgs m, RlTrailArgs t, const unsigned int *meta)
+{
+    __shared__ unsigned long long s_key[RL_NW];
+    const size_t k = blockIdx.x;
+    const int records = (int)meta[2 * k + 1];
+    rl_finish(geo, m, k, records, (int)meta[2 * k], t.out + k, s_key, threadIdx.x);
+    if (threadIdx.x != 0) return;
+    qs_trail_reloc *r = t.out + k;
+    if (records == 0) { r->anchor = -1; return; }
+    r->anchor = t.who[2 * k]; r->agent = (uint8_t)t.who[2 * k + 1];
+    r->ax = t.at[2 * k]; r->ay = t.at[2 * k + 1];
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 struct QsRelocSetup { qs_reloc_params p; int M; };
 
-// travel: the group form's (J8); 0 for a single sweep, whose limit and text are G's
-static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who, QsRelocSetup &rs, double travel = 0.0, bool group = false)
+// travel: the group form's (J8) and the trail form's (K8, whose ranges end at max_dist); 0 for a single sweep, whose limit and
+// text are G's
+enum { RL_SWEEP, RL_GROUP, RL_TRAIL };
+static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who, QsRelocSetup &rs, double travel = 0.0, int form = RL_SWEEP)
 {
     qs_reloc_params p = {2, 180, 4, 2, 40, 70, 5, 0, 0, 0, 0, 0};
     if (params) p = *params;
@@ -492,10 +587,11 @@ static int reloc_setup(qs_ctx *c, const qs_reloc_params *params, const char *who
     else if (p.min_margin < 0 || p.min_margin > 100) bad = "min_margin must lie in [0, 100]";
     else if (!(travel >= 0.0) || !std::isfinite(travel)) bad = "travel must be finite and not negative";
     if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
-    const double reach = ceil((c->sweep_max + travel) / c->cfg.res);          // (travel 0: smax + 0 is smax)
+    const double reach = ceil(((form == RL_TRAIL ? c->cfg.max_dist : c->sweep_max) + travel) / c->cfg.res);      // (travel 0: smax + 0 is smax)
     if (!(RL_TILE + 2 * (reach + p.radius + 1) <= 255))
-        bad = group ? "smax + travel is too large for this resolution: 16 + 2 * (ceil((smax + travel) / res) + radius + 1) exceeds 255"
-                    : "the sweep filter's smax is too large for this resolution: 16 + 2 * (ceil(smax / res) + radius + 1) exceeds 255";
+        bad = form == RL_TRAIL ? "max_dist + travel is too large for this resolution: 16 + 2 * (ceil((max_dist + travel) / res) + radius + 1) exceeds 255"
+            : form == RL_GROUP ? "smax + travel is too large for this resolution: 16 + 2 * (ceil((smax + travel) / res) + radius + 1) exceeds 255"
+                               : "the sweep filter's smax is too large for this resolution: 16 + 2 * (ceil(smax / res) + radius + 1) exceeds 255";
     if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
     if (!p.use_box) { p.x0 = 0; p.y0 = 0; p.x1 = c->cfg.size; p.y1 = c->cfg.size; }
     rs.p = p;
@@ -532,7 +628,11 @@ static int reloc_groups_ok(qs_ctx *c, size_t n, const int32_t *gsize, size_t n_g
 
 // the workspace of one call over n_tiles box tiles, carved from ws (nullptr: only the bytes the block needs); groups: with the
 // point lists of a chunk of groups
-struct QsRelocLayout { unsigned int *chunk, *list; unsigned long long *count, *table, *best, *excl; double *pts; unsigned int *meta; size_t bytes; };
+struct QsRelocLayout {
+    unsigned int *chunk, *list; unsigned long long *count, *table, *best, *excl; double *pts; unsigned int *meta;
+    double *at; int *who;         // a chunk of trails: the anchors' fields, anchor and agent (RlTrailArgs)
+    size_t bytes;
+};
 static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles, bool groups)
 {
     Carve cv(ws);
@@ -545,6 +645,8 @@ static QsRelocLayout qs_reloc_layout(void *ws, size_t n_tiles, bool groups)
     L.excl = cv.take<unsigned long long>((size_t)RL_CHUNK * 9);
     L.pts = groups ? cv.take<double>((size_t)RL_CHUNK * 2 * RL_GPTS) : nullptr;
     L.meta = groups ? cv.take<unsigned int>((size_t)RL_CHUNK * 2) : nullptr;
+    L.at = groups ? cv.take<double>((size_t)RL_CHUNK * 2) : nullptr;
+    L.who = groups ? cv.take<int>((size_t)RL_CHUNK * 2) : nullptr;
     L.bytes = cv.bytes;
     return L;
 }
@@ -731,7 +833,7 @@ extern "C" int qs_relocalise_sweeps(qs_ctx *c, const qs_reloc_params *params, co
 static int reloc_groups_check(qs_ctx *c, const qs_reloc_params *params, size_t n, size_t stride, const int32_t *gsize, size_t n_groups,
                               double travel, QsRelocSetup &rs)
 {
-    int rc = reloc_setup(c, params, "qs_relocalise_groups", rs, travel, true);
+    int rc = reloc_setup(c, params, "qs_relocalise_groups", rs, travel, RL_GROUP);
     if (rc != QS_OK) return rc;
     rc = reloc_call_ok(c, n, stride, "qs_relocalise_groups");
     if (rc != QS_OK) return rc;
@@ -788,6 +890,136 @@ extern "C" int qs_relocalise_groups(qs_ctx *c, const qs_reloc_params *params, co
         HIPCHK(c, hipMemcpyAsync(out + g0, d_out, ng * sizeof(qs_group_reloc), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         g0 = g1; k0 += nk;
+    }
+    return QS_OK;
+}
+
+// ---- trail relocalisation ------------------------------------------------------------------------------------------------------
+// K8 and K1, before anything is enqueued
+static int reloc_trails_check(qs_ctx *c, const qs_reloc_params *params, size_t n, size_t stride, const int32_t *gsize, size_t n_groups,
+                              double travel, QsRelocSetup &rs)
+{
+    static const char *who = "qs_relocalise_trails";
+    const int rc = reloc_setup(c, params, who, rs, travel, RL_TRAIL);
+    if (rc != QS_OK) return rc;
+    char msg[256];
+    const char *bad = nullptr;
+    if (stride < QS_PACKET_SIZE_V1) bad = "stride must be at least 41";
+    else if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0) bad = "sharded contexts (seq_stride > 1, shard_bots > 0) do not relocalise trails";
+    else if (n >= ((size_t)1 << 31)) bad = "at most 2^31 - 1 records per call";
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return qs_fail(c, QS_E_INVAL, msg); }
+    size_t sum = 0;
+    for (size_t g = 0; g < n_groups; g++) {
+        if (gsize[g] < 1 || gsize[g] > QS_TRAIL_MAX_RECORDS) {
+            snprintf(msg, sizeof msg, "%s: gsize[%zu] must lie in [1, QS_TRAIL_MAX_RECORDS]", who, g);
+            return qs_fail(c, QS_E_INVAL, msg);
+        }
+        sum += (size_t)gsize[g];
+    }
+    if (sum != n) { snprintf(msg, sizeof msg, "%s: the group sizes must sum to n", who); return qs_fail(c, QS_E_INVAL, msg); }
+    return QS_OK;
+}
+
+// n_groups trails (gsize: host, already checked against K1) of device-resident records against the map as the stream finds it;
+// d_rot (optional): [records][2].  Everything enqueued, nothing waited for (but see reloc_prepare).  The scoring kernel's lists
+// stand RL_GOFFP offsets apart whatever they hold, so the plan is the group form's
+static hipError_t reloc_trail_launch(qs_ctx *c, const QsRelocSetup &rs, const unsigned char *d_pkts, size_t stride, const unsigned short *d_lens,
+                                     const int32_t *gsize, size_t n_groups, double travel, qs_trail_reloc *d_out, double *d_rot)
+{
+    if (n_groups == 0) return hipSuccess;
+    QsRelocPlan pl;
+    HIPRET(reloc_prepare(c, rs, RL_GOFFP, true, pl));
+    const QsRelocArgs &m = pl.m;
+    const size_t n_tiles = pl.n_tiles, lds = pl.lds;
+    if (lds > 32 * 1024) {                                         // up to 2 x 69 KiB of the CU's 160
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_group_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPRET(hipFuncSetAttribute((const void *)qs_reloc_group_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    RlGroupArgs g;                                                 // what the scoring kernel reads of it: the lists and their lengths
+    memset(&g, 0, sizeof g);
+    g.travel = travel; g.pts = pl.L.pts; g.meta = pl.L.meta;
+    RlTrailArgs t;
+    memset(&t, 0, sizeof t);
+    t.r.stride = stride; t.max_agent = c->cfg.max_agent; t.travel2 = travel * travel;
+    t.who = pl.L.who; t.at = pl.L.at;
+    size_t rec0 = 0;
+    for (size_t g0 = 0; g0 < n_groups; g0 += RL_CHUNK) {
+        const unsigned int ng = (unsigned int)std::min((size_t)RL_CHUNK, n_groups - g0);
+        unsigned int nr = 0;
+        for (unsigned int i = 0; i <= RL_CHUNK; i++) {
+            t.start[i] = nr;
+            if (i < ng) nr += (unsigned int)gsize[g0 + i];
+        }
+        t.r.pkts = d_pkts + rec0 * stride; t.r.lens = d_lens ? d_lens + rec0 : nullptr; t.r.nrec = nr;
+        t.rot = d_rot ? d_rot + 2 * rec0 : nullptr; t.out = d_out + g0;
+        hipLaunchKernelGGL(qs_reloc_trail_points_kernel, dim3(ng), dim3(QS_WAVE), 0, c->stream, t, c->geom, pl.L.pts, pl.L.meta);
+        HIPRET(hipGetLastError());
+        if (n_tiles) {
+            hipLaunchKernelGGL(qs_reloc_group_score_kernel<false>, dim3((unsigned int)n_tiles, ng), dim3(RL_BLOCK), lds, c->stream, c->geom, m, g);
+            HIPRET(hipGetLastError());
+        }
+        hipLaunchKernelGGL(qs_reloc_pick_kernel, dim3(ng), dim3(RL_BLOCK), 0, c->stream, m);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_group_score_kernel<true>, dim3(9, ng), dim3(RL_BLOCK), lds, c->stream, c->geom, m, g);
+        HIPRET(hipGetLastError());
+        hipLaunchKernelGGL(qs_reloc_trail_final_kernel, dim3(ng), dim3(RL_BLOCK), 0, c->stream, c->geom, m, t, (const unsigned int *)pl.L.meta);
+        HIPRET(hipGetLastError());
+        rec0 += nr;
+    }
+    return hipSuccess;
+}
+
+// ---- C ABI: trail relocalisation (semantics in include/quasar_slam.h) -------------------------------------------------------------
+extern "C" int qs_relocalise_trails_device(qs_ctx *c, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                           const uint16_t *d_lens, const int32_t *gsize, size_t n_groups, double travel,
+                                           qs_trail_reloc *d_out, double *d_rot_out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || d_pkts != nullptr);
+    ARGCHK(c, n_groups == 0 || (gsize != nullptr && d_out != nullptr));
+    QsRelocSetup rs;
+    const int rc = reloc_trails_check(c, params, n, stride, gsize, n_groups, travel, rs);
+    if (rc != QS_OK || n_groups == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    HIPCHK(c, reloc_trail_launch(c, rs, d_pkts, stride, d_lens, gsize, n_groups, travel, d_out, d_rot_out));
+    return QS_OK;
+}
+
+extern "C" int qs_relocalise_trails(qs_ctx *c, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                                    const uint16_t *lens, const int32_t *gsize, size_t n_groups, double travel, qs_trail_reloc *out,
+                                    double *rot_out)
+{
+    ARGCHK(c, c != nullptr);
+    ARGCHK(c, n == 0 || pkts != nullptr);
+    ARGCHK(c, n_groups == 0 || (gsize != nullptr && out != nullptr));
+    QsRelocSetup rs;
+    int rc = reloc_trails_check(c, params, n, stride, gsize, n_groups, travel, rs);
+    if (rc != QS_OK || n_groups == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    SYNCCHK(c);
+    size_t k0 = 0;
+    for (size_t g0 = 0; g0 < n_groups; g0 += RL_CHUNK) {           // whole trails per round trip: one launch's worth
+        const size_t ng = std::min((size_t)RL_CHUNK, n_groups - g0);
+        size_t nk = 0;
+        for (size_t g = g0; g < g0 + ng; g++) nk += (size_t)gsize[g];
+        Staging s;
+        rc = reserve_staging(c, nk * stride, s);
+        if (rc != QS_OK) return rc;
+        Carve cv(nullptr);
+        cv.take<qs_trail_reloc>(ng);
+        if (rot_out) cv.take<double>(2 * nk);
+        HIPCHK(c, c->io_ws.reserve(cv.bytes, c->stream, QS_IO_WS_FLOOR));
+        Carve io(c->io_ws.p);
+        qs_trail_reloc *d_out = io.take<qs_trail_reloc>(ng);
+        double *d_rot = rot_out ? io.take<double>(2 * nk) : nullptr;
+        HIPCHK(c, hipMemcpyAsync(s.pkts, pkts + k0 * stride, nk * stride, hipMemcpyHostToDevice, c->stream));
+        if (lens) HIPCHK(c, hipMemcpyAsync(s.lens, lens + k0, nk * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, reloc_trail_launch(c, rs, s.pkts, stride, lens ? s.lens : nullptr, gsize + g0, ng, travel, d_out, d_rot));
+        HIPCHK(c, hipMemcpyAsync(out + g0, d_out, ng * sizeof(qs_trail_reloc), hipMemcpyDeviceToHost, c->stream));
+        if (rot_out) HIPCHK(c, hipMemcpyAsync(rot_out + 2 * k0, d_rot, 2 * nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        k0 += nk;
     }
     return QS_OK;
 }

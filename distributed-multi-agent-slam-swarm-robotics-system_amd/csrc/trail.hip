@@ -20,17 +20,14 @@
 #include <string.h>
 #include <algorithm>
 
-#include "raycast_common.h"
+#include "trail_common.h"
 #include "window_match.h"
 
 #define TR_PTS (4 * QS_TRAIL_MAX_RECORDS)    // points of one trail, and 16-bit offsets per rotation (a multiple of 4: 8-byte reads)
-#define TR_MAX_STRIDE 64                     // records are staged through LDS when stride <= 64 bytes
 #define TR_CHUNK 512                         // trails per launch: their first records travel in the kernel's arguments
 
 struct QsTrailArgs {
-    const unsigned char *pkts;    // the launch's records: nrec of them, `stride` bytes apart
-    const unsigned short *lens;   // or nullptr
-    size_t stride, nrec;
+    TrRecords r;                  // the launch's records
     const double *offset, *drift; // [max_agent + 1], [max_agent + 1][2]
     int max_agent;
     WmArgs w;
@@ -41,22 +38,11 @@ struct QsTrailArgs {
     double sc[WM_NROT_MAX][2];    // (S, C) of it * angle_step, it = -T .. T, the host's libm
 };
 
-// the record's 42 bytes as eleven dwords from LDS (the record starts at any byte): twelve aligned reads shifted into place
-__device__ inline void tr_record_lds(const unsigned int *s_raw, unsigned int off, unsigned int r[11])
-{
-    const unsigned int w0 = off >> 2, sh = off & 3u;
-    unsigned int d[12];
-    #pragma unroll
-    for (int q = 0; q < 12; q++) d[q] = s_raw[w0 + q];
-    #pragma unroll
-    for (int q = 0; q < 11; q++) r[q] = __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh);
-}
-
 __global__ void __launch_bounds__(WM_BLOCK)
 qs_trail_kernel(QsTrailArgs m, QsGeom geo)
 {
     extern __shared__ __align__(16) unsigned char s_dyn[];
-    __shared__ unsigned int s_raw[QS_TRAIL_MAX_RECORDS * TR_MAX_STRIDE / 4 + 2];
+    __shared__ unsigned int s_raw[TR_RAW_DW];
     __shared__ double2 s_q[TR_PTS];
     __shared__ int s_cnt[WM_NROT_MAX];
     __shared__ unsigned long long s_key[WM_NW];
@@ -68,32 +54,10 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
     const size_t rec0 = m.start[grp];
     const int K = (int)m.start[grp + 1] - (int)m.start[grp];       // 1 .. 64
     const int nrot = 2 * m.w.T + 1;
-    const bool staged = m.stride <= TR_MAX_STRIDE;
+    const bool staged = m.r.stride <= TR_MAX_STRIDE;
 
     // ---- stage: the byte range of the group's records widened to dword boundaries -------------------------------------------------
-    unsigned int mis = 0;
-    if (staged) {
-        const unsigned long long addr0 = (unsigned long long)m.pkts + rec0 * m.stride;
-        mis = (unsigned int)(addr0 & 3ull);
-        const unsigned int *src = (const unsigned int *)(addr0 - mis);
-        const unsigned int ndw = (mis + (unsigned int)K * (unsigned int)m.stride + 3u) / 4u;       // <= 1025
-        const unsigned long long buf0 = (unsigned long long)m.pkts, buf1 = buf0 + m.nrec * m.stride;
-        for (unsigned int k = tid; k < ndw; k += WM_BLOCK) {
-            const unsigned long long a = (unsigned long long)(src + k);
-            unsigned int v;
-            if (a >= buf0 && a + 4 <= buf1) v = src[k];
-            else {                                                 // a dword that straddles the caller's buffer: bytewise
-                v = 0;
-                const unsigned char *p = (const unsigned char *)a;
-                for (int q = 0; q < 4; q++)
-                    if (a + q >= buf0 && a + q < buf1) v |= (unsigned int)p[q] << (8 * q);
-            }
-            s_raw[k] = v;
-        }
-        // (a record's twelve-dword window may reach one dword past the staged range: its bytes are never looked at, but the
-        // read stays inside s_raw, which holds 1026 dwords)
-        for (unsigned int k = ndw + tid; k < ndw + 12u && k < sizeof s_raw / 4; k += WM_BLOCK) s_raw[k] = 0u;
-    }
+    const unsigned int mis = staged ? tr_stage(m.r, rec0, K, s_raw, tid, WM_BLOCK) : 0u;
     __syncthreads();
 
     // ---- wave 0: a lane per record ---------------------------------------------------------------------------------------------
@@ -101,32 +65,8 @@ qs_trail_kernel(QsTrailArgs m, QsGeom geo)
         bool ok = false;
         int agent = 0;
         float x = 0.f, y = 0.f, yaw = 0.f, dist[4] = {0.f, 0.f, 0.f, 0.f};
-        if (lane < K) {
-            const size_t i = rec0 + lane;
-            const int len = m.lens ? (int)m.lens[i] : (int)m.stride;
-            if ((len == QS_PACKET_SIZE || len == QS_PACKET_SIZE_V1) && (size_t)len <= m.stride) {
-                unsigned int r[11];
-                if (staged) tr_record_lds(s_raw, mis + (unsigned int)lane * (unsigned int)m.stride, r);
-                else {
-                    const unsigned char *p = m.pkts + i * m.stride;
-                    #pragma unroll
-                    for (int q = 0; q < 11; q++) {
-                        unsigned int v = 0;
-                        #pragma unroll
-                        for (int e = 0; e < 4; e++)
-                            if (4 * q + e < len) v |= (unsigned int)p[4 * q + e] << (8 * e);
-                        r[q] = v;
-                    }
-                }
-                #define TR_U32(p) ((p) % 4 == 0 ? r[(p) / 4] : __builtin_amdgcn_alignbyte(r[(p) / 4 + 1], r[(p) / 4], (p) % 4))
-                agent = (int)(r[1] & 0xffu);
-                x = __uint_as_float(TR_U32(5)); y = __uint_as_float(TR_U32(9)); yaw = __uint_as_float(TR_U32(13));
-                dist[0] = __uint_as_float(TR_U32(25)); dist[1] = __uint_as_float(TR_U32(29));
-                dist[2] = __uint_as_float(TR_U32(33)); dist[3] = __uint_as_float(TR_U32(37));
-                #undef TR_U32
-                ok = r[0] == 0x4c525351u && agent >= 1 && agent <= m.max_agent && isfinite(x) && isfinite(y) && isfinite(yaw);
-            }
-        }
+        if (lane < K)
+            ok = tr_parse(m.r, m.max_agent, rec0 + lane, staged, s_raw, mis + (unsigned int)lane * (unsigned int)m.r.stride, agent, x, y, yaw, dist);
         const unsigned long long acc = __ballot(ok);
         const int anchor = acc ? 63 - __clzll((long long)acc) : -1;
         const int bot = anchor >= 0 ? __shfl(agent, anchor) : 0;
@@ -251,7 +191,7 @@ static hipError_t trail_launch(qs_ctx *c, const QsTrailSetup &ts, const unsigned
     if (n_groups == 0) return hipSuccess;
     QsTrailArgs m;
     memset(&m, 0, sizeof m);
-    m.stride = stride;
+    m.r.stride = stride;
     m.offset = c->d_offset.p; m.drift = c->d_drift.p; m.max_agent = c->cfg.max_agent;
     size_t lds;
     HIPRET(wm_args(c, ts, (const void *)qs_trail_kernel, TR_PTS, m.w, lds));
@@ -268,7 +208,7 @@ static hipError_t trail_launch(qs_ctx *c, const QsTrailSetup &ts, const unsigned
             m.start[i] = (unsigned short)nr;
             if (i < ng) nr += (unsigned int)gsize[g0 + i];
         }
-        m.pkts = d_pkts + rec0 * stride; m.lens = d_lens ? d_lens + rec0 : nullptr; m.nrec = nr;
+        m.r.pkts = d_pkts + rec0 * stride; m.r.lens = d_lens ? d_lens + rec0 : nullptr; m.r.nrec = nr;
         m.out = d_out + g0; m.rot = d_rot ? d_rot + 2 * rec0 : nullptr;
         hipLaunchKernelGGL(qs_trail_kernel, dim3(ng), dim3(WM_BLOCK), lds, c->stream, m, c->geom);
         HIPRET(hipGetLastError());

@@ -612,11 +612,9 @@ class QuasarMapper:
                   "qs_relocalise_groups_device")
 
     # -- trail matching (include/quasar_slam.h, "trail matching") ---------------------------------------------------------------
-    def match_trails(self, datagrams, gsize, lengths=None, travel=P.TRAIL_TRAVEL, params=None, rotations=False):
-        """Match trails of 42-byte packets against the map without mapping them or changing anything: packets (as ingest /
-        ingest_array take them) in runs of gsize[g], each run the last packets of one bot in arrival order; a structured array
-        of protocol.TRAIL_MATCH_DTYPE, one entry per trail (protocol.trail_move applies one).  params: what match_params
-        takes.  With rotations also the (sin, cos) of each record's yaw as the device formed them, float64 [n, 2]."""
+    @staticmethod
+    def _trail_buffer(datagrams, lengths):
+        """(uint8 [n, stride], uint16 lengths or None) of the packets of a trail call: an array as it is, datagrams packed."""
         if isinstance(datagrams, np.ndarray):
             buf = np.ascontiguousarray(datagrams, dtype=np.uint8)
             if buf.ndim != 2:
@@ -627,10 +625,18 @@ class QuasarMapper:
             buf = np.frombuffer(b"".join(datagrams), dtype=np.uint8).reshape(-1, P.PACKET_SIZE)
         else:
             buf, lengths = P.pack_datagrams(datagrams)
-        n, stride = buf.shape
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint16)
-        if lens is not None and len(lens) != n:
+        if lens is not None and len(lens) != len(buf):
             raise ValueError("lengths must have one entry per record")
+        return buf, lens
+
+    def match_trails(self, datagrams, gsize, lengths=None, travel=P.TRAIL_TRAVEL, params=None, rotations=False):
+        """Match trails of 42-byte packets against the map without mapping them or changing anything: packets (as ingest /
+        ingest_array take them) in runs of gsize[g], each run the last packets of one bot in arrival order; a structured array
+        of protocol.TRAIL_MATCH_DTYPE, one entry per trail (protocol.trail_move applies one).  params: what match_params
+        takes.  With rotations also the (sin, cos) of each record's yaw as the device formed them, float64 [n, 2]."""
+        buf, lens = self._trail_buffer(datagrams, lengths)
+        n, stride = buf.shape
         gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
         prm = self.match_params(params)
         out = np.zeros(len(gs), dtype=P.TRAIL_MATCH_DTYPE)
@@ -649,6 +655,34 @@ class QuasarMapper:
                                                  C.c_void_p(d_lens) if d_lens else None, _ptr(gs) if len(gs) else None, len(gs),
                                                  float(travel), C.c_void_p(d_out) if d_out else None,
                                                  C.c_void_p(d_rot) if d_rot else None), "qs_match_trails_device")
+
+    # -- trail relocalisation (include/quasar_slam.h, "trail relocalisation") -----------------------------------------------------
+    def relocalise_trails(self, datagrams, gsize, lengths=None, travel=P.TRAIL_TRAVEL, params=None, rotations=False):
+        """Locate trails of 42-byte packets against the whole map, whatever frame their poses are in: packets (as match_trails
+        takes them) in runs of gsize[g]; a structured array of protocol.TRAIL_RELOC_DTYPE, one entry per trail
+        (protocol.trail_reloc_move applies one).  params: what relocalise_params takes.  With rotations also the (sin, cos)
+        of each counting record's yaw as the device formed them, float64 [n, 2].  Reads the map, changes nothing."""
+        buf, lens = self._trail_buffer(datagrams, lengths)
+        n, stride = buf.shape
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        prm = self.relocalise_params(params)
+        out = np.zeros(len(gs), dtype=P.TRAIL_RELOC_DTYPE)
+        rot = np.zeros((n, 2), dtype=np.float64) if rotations else None
+        self._chk(self._L.qs_relocalise_trails(self._h, C.byref(prm), _ptr(buf) if n else None, n, stride, _ptr(lens),
+                                               _ptr(gs) if len(gs) else None, len(gs), float(travel),
+                                               _ptr(out) if len(gs) else None, _ptr(rot) if rotations and n else None),
+                  "qs_relocalise_trails")
+        return (out, rot) if rotations else out
+
+    def relocalise_trails_device(self, d_pkts, n, stride, gsize, d_out, d_lens=0, d_rot=0, travel=P.TRAIL_TRAVEL, params=None):
+        """Device-resident form (raw device addresses as ints; d_out: len(gsize) records of protocol.TRAIL_RELOC_DTYPE, d_rot:
+        float64 [n, 2] or 0; gsize a host array); asynchronous."""
+        prm = self.relocalise_params(params)
+        gs = np.ascontiguousarray(gsize, dtype=np.int32).reshape(-1)
+        self._chk(self._L.qs_relocalise_trails_device(self._h, C.byref(prm), C.c_void_p(d_pkts) if d_pkts else None, n, stride,
+                                                      C.c_void_p(d_lens) if d_lens else None, _ptr(gs) if len(gs) else None,
+                                                      len(gs), float(travel), C.c_void_p(d_out) if d_out else None,
+                                                      C.c_void_p(d_rot) if d_rot else None), "qs_relocalise_trails_device")
 
     def last_sweeps(self):
         """(accepted uint8 [n], pose float64 [n, 3]) of the last sweep ingest: the pose each sweep was cast from (rx, ry after

@@ -169,6 +169,12 @@ TRAIL_MATCH_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("it", "<i4"), ("sco
                               ("records", "<i4"), ("anchor", "<i4"), ("agent", "u1"), ("accepted_match", "u1"), ("pad", "u1", (6,)),
                               ("ax", "<f8"), ("ay", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dyaw", "<f8")])
 assert TRAIL_MATCH_DTYPE.itemsize == 80
+# trail relocalisation (include/quasar_slam.h, "trail relocalisation"): GROUP_RELOC_DTYPE's fields where it has them
+TRAIL_RELOC_DTYPE = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("j", "<i4"), ("score", "<i4"), ("hits", "<i4"),
+                              ("gx2", "<i4"), ("gy2", "<i4"), ("j2", "<i4"), ("score2", "<i4"), ("status", "<i4"),
+                              ("records", "u1"), ("accepted", "u1"), ("agent", "u1"), ("pad", "u1"), ("anchor", "<i4"),
+                              ("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("ax", "<f8"), ("ay", "<f8")])
+assert TRAIL_RELOC_DTYPE.itemsize == 88
 # sweep check (include/quasar_slam.h, "sweep check"): build choices taken from a CPU prototype of the rule
 CHECK_TOL_CELLS = 2          # tol defaults to this many cells
 CHECK_MIN_CHECKED = 20       # a sweep with fewer decided beams is UNDECIDED
@@ -208,6 +214,17 @@ def trail_move(match, x, y, yaw):
     x, y, yaw = (np.asarray(v, dtype=np.float64) for v in (x, y, yaw))
     qx, qy = x - ax, y - ay
     return ax + (c * qx - s * qy) + dx, ay + (s * qx + c * qy) + dy, yaw + dyaw
+
+
+def trail_reloc_move(result, x, y, yaw):
+    """Rule K7's transform: where a pose (x, y, yaw) in the frame of the located bot's packet fields lies on the map, by
+    `result` (one TRAIL_RELOC_DTYPE record, or anything with x, y, yaw, ax, ay): the turn by yaw about the anchor's fields
+    (ax, ay), the anchor set down at (x, y).  Scalars or arrays; fp64 with libm."""
+    fx, fy, fyaw, ax, ay = (float(result[k]) for k in ("x", "y", "yaw", "ax", "ay"))
+    s, c = math.sin(fyaw), math.cos(fyaw)
+    x, y, yaw = (np.asarray(v, dtype=np.float64) for v in (x, y, yaw))
+    qx, qy = x - ax, y - ay
+    return fx + (c * qx - s * qy), fy + (s * qx + c * qy), yaw + fyaw
 
 
 # ---- map view (include/quasar_slam.h, "map view"): the renderer's constants, dual_bot_mapper.py:346-377, :383-397 ----------

@@ -72,6 +72,14 @@ match time; a later closure's drift is not turned with it), which rewrites the f
 then on, the trail's own included.  Then all flushed records go, in arrival order, through ONE ingest_array, as a poll's packets
 do.  flush_trails() flushes everything pending (close() calls it); trail_matches[bot] holds the bot's latest result, trail_stats
 counts held / tried / accepted / moved / rewritten.  A bot that delivers more than `trail` packets to one poll flushes in rounds.
+With match_packets={"relocalise": True or a dict of relocalisation parameters, "tries": 4, "bots": [...], ...} (opt-in inside the
+opt-in) a packet bot whose frame is unknown is first FOUND (QuasarMapper.relocalise_trails; include/quasar_slam.h, "trail
+relocalisation"): a bot that comes online, the first time or back from offline, without a transform -- any bot but the first one
+ever seen, whose frame is the map's, or those named in "bots" -- has its due trails located over the whole map instead of matched,
+and held instead of mapped.  On acceptance the found frame (rule K7, less sweep_pose_shift) becomes the bot's transform, all it
+held is rewritten by it and mapped in arrival order, and its later trails are matched as above; after "tries" refusals (or at
+flush_trails()) what it held is mapped as it is and the bot is left alone until it is next found offline.  trail_stats then
+also counts reloc_tried / reloc_accepted / reloc_gave_up; trail_relocs[bot] holds the latest result.
 With track_view=True (opt-in) the front-end keeps what the reference's renderer is handed each frame (:878-892):
 point_clouds[bot][sensor], the hit points of the accepted packets (QuasarMapper.last_hits), and paths[bot] = ([xs], [ys]), their
 poses; mapper.MapView.frame draws them.
@@ -150,6 +158,17 @@ class MissionControl:
         self.trail = int(self.trail_params.pop("trail", P.TRAIL_MAX_RECORDS))
         self.trail_hold = float(self.trail_params.pop("hold", 5.0))
         self.trail_travel = float(self.trail_params.pop("travel", P.TRAIL_TRAVEL))
+        # "relocalise": True or a dict of relocalisation parameters: bots that come online without a transform are first LOCATED
+        # over the whole map from their trails (QuasarMapper.relocalise_trails), at most "tries" trails each
+        reloc = self.trail_params.pop("relocalise", None)
+        self.trail_reloc = reloc is not None and reloc is not False
+        self.trail_reloc_params = dict(reloc) if isinstance(reloc, dict) else None
+        self.trail_reloc_tries = int(self.trail_params.pop("tries", 4)) if self.trail_reloc else 0
+        bots_ = self.trail_params.pop("bots", None) if self.trail_reloc else None
+        self.trail_reloc_bots = None if bots_ is None else {int(b) for b in bots_}
+        self._first_bot = None                       # the first bot ever seen: its frame is the map's, it is never located
+        self._locating = {}                          # bot -> [trails tried, its held packets]: not mapped until found or given up
+        self.trail_relocs = {}                       # bot -> its latest result (a record of protocol.TRAIL_RELOC_DTYPE)
         if not 1 <= self.trail <= P.TRAIL_MAX_RECORDS:
             raise ValueError("MissionControl: match_packets['trail'] must lie in [1, TRAIL_MAX_RECORDS]")
         self._pending = {b: [] for b in range(1, max_agent + 1)}   # bot -> held packets (arrival number, record, length, time, address)
@@ -157,6 +176,8 @@ class MissionControl:
         self._trail_T = {}                           # bot -> (cos, sin, angle, tx, ty): field (x, y) -> R (x, y) + t, yaw + angle
         self.trail_matches = {}                      # bot -> its latest result (a record of protocol.TRAIL_MATCH_DTYPE)
         self.trail_stats = {"held": 0, "tried": 0, "accepted": 0, "moved": 0, "rewritten": 0}
+        if self.trail_reloc:
+            self.trail_stats.update(reloc_tried=0, reloc_accepted=0, reloc_gave_up=0)
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
         self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
@@ -280,6 +301,8 @@ class MissionControl:
             a = int(buf[i, 4])
             self._pending[a].append((self._trail_seq, buf[i, :SLOT].copy(), int(lens[i]), float(self._times[i]), self._addrs[i]))
             self._trail_seq += 1
+            if self.trail_reloc:
+                self._note_arrival(a)
             self.bot_addrs[a] = (self._addrs[i][0], self.bot_ports[a])      # the bot is there, as a withheld sweep shows it
             self.last_packet_time[a] = now
             self.online[a] = True
@@ -293,6 +316,48 @@ class MissionControl:
             self._times[:m] = self._times[rest]
             self._addrs[:m] = [self._addrs[i] for i in rest]
         return m
+
+    def _note_arrival(self, bot):
+        """match_packets["relocalise"]: a bot that comes online -- the first time, or back from offline -- without a transform is
+        due to be located, unless it is the first bot ever seen (whose frame is the map's) or "bots" leaves it out."""
+        if self._first_bot is None:
+            self._first_bot = next((b for b in sorted(self.seen) if self.seen[b]), bot)
+        if self.online[bot] or bot in self._trail_T or bot in self._locating:
+            return
+        if bot in self.trail_reloc_bots if self.trail_reloc_bots is not None else bot != self._first_bot:
+            self._locating[bot] = [0, []]
+
+    def _trail_travel_of(self, recs):
+        """The travel a trail needs: the largest distance of a record from the last one, rounded up to the next 0.25 m and capped
+        at trail_travel, so that the patch the search stages is no larger than the trail."""
+        f = np.ascontiguousarray(recs[:, 5:13]).view("<f4").astype(np.float64)
+        d = np.hypot(f[:, 0] - f[-1, 0], f[:, 1] - f[-1, 1])
+        d = float(d[np.isfinite(d)].max()) if np.isfinite(d).any() else 0.0
+        return min(self.trail_travel, float(np.ceil(d / 0.25)) * 0.25)
+
+    def _trail_locate(self, bot, group, shift):
+        """One trail of a bot that is being located.  Returns the packets to map now: none while it is held; on acceptance
+        (rule K7's transform, less what the ingest adds itself, becomes the bot's) or after the last try, all it held."""
+        tried, held = self._locating[bot]
+        recs = np.stack([p[1] for p in group])
+        lens = np.array([p[2] for p in group], dtype=np.uint16)
+        r = self.mapper.relocalise_trails(recs, [len(group)], lens, travel=self._trail_travel_of(recs),
+                                          params=self.trail_reloc_params)[0]
+        self.trail_relocs[bot] = r.copy()
+        self.trail_stats["reloc_tried"] += 1
+        held.extend(group)
+        if r["accepted"]:
+            self.trail_stats["reloc_accepted"] += 1
+            th, ax, ay = float(r["yaw"]), float(r["ax"]), float(r["ay"])
+            c, s = np.cos(th), np.sin(th)
+            self._trail_T[bot] = (c, s, th, float(r["x"]) - (c * ax - s * ay) - shift[0], float(r["y"]) - (s * ax + c * ay) - shift[1])
+        elif tried + 1 < self.trail_reloc_tries:
+            self._locating[bot][0] = tried + 1
+            return []
+        else:
+            self.trail_stats["reloc_gave_up"] += 1
+        del self._locating[bot]
+        return held
 
     @staticmethod
     def _trail_rewrite(recs, T):
@@ -329,6 +394,10 @@ class MissionControl:
             groups = {}
             for b, k in sorted(due.items()):
                 groups[b], self._pending[b] = self._pending[b][:k], self._pending[b][k:]
+            shift_of = getattr(self.mapper, "sweep_pose_shift", None)
+            located = []                             # what the bots being located release: mapped with this round's records
+            for b in [b for b in groups if b in self._locating]:
+                located.extend(self._trail_locate(b, groups.pop(b), tuple(float(v) for v in shift_of(b)) if shift_of else (0.0, 0.0)))
             # matched as the transforms in force would map them
             trial = []
             for b, g in groups.items():
@@ -337,10 +406,9 @@ class MissionControl:
                     self._trail_rewrite(recs, self._trail_T[b])
                 trial.append(recs)
             lens = np.array([p[2] for g in groups.values() for p in g], dtype=np.uint16)
-            shift_of = getattr(self.mapper, "sweep_pose_shift", None)
             shifts = {b: tuple(float(v) for v in shift_of(b)) if shift_of else (0.0, 0.0) for b in groups}
             res = self.mapper.match_trails(np.concatenate(trial), [len(g) for g in groups.values()], lens,
-                                           travel=self.trail_travel, params=self.trail_params or None)
+                                           travel=self.trail_travel, params=self.trail_params or None) if groups else ()
             for b, r in zip(groups, res):
                 self.trail_matches[b] = r.copy()
                 self.trail_stats["tried"] += 1
@@ -350,8 +418,10 @@ class MissionControl:
                         self.trail_stats["moved"] += 1
                         self._trail_compose(b, r, shifts[b])
             # mapped, in arrival order, as the transforms now in force map them (the trail's own records included)
-            flat = sorted((p for g in groups.values() for p in g), key=lambda p: p[0])
+            flat = sorted([p for g in groups.values() for p in g] + located, key=lambda p: p[0])
             m = len(flat)
+            if m == 0:                               # (every due trail is held by a bot being located)
+                continue
             buf = np.zeros((m, self.slot), dtype=np.uint8)
             for j, p in enumerate(flat):
                 buf[j, :SLOT] = p[1]
@@ -367,7 +437,16 @@ class MissionControl:
     def flush_trails(self, now=None):
         """match_packets: match and map everything pending, whatever its count or age."""
         if self.match_packets:
-            self._flush_trails(time.time() if now is None else now, True)
+            now = time.time() if now is None else now
+            self._flush_trails(now, True)
+            for b in sorted(self._locating):         # still being located: what they hold is mapped as it is
+                flat = self._locating.pop(b)[1]
+                self.trail_stats["reloc_gave_up"] += 1
+                if flat:
+                    buf = np.zeros((len(flat), self.slot), dtype=np.uint8)
+                    buf[:, :SLOT] = np.stack([p[1] for p in flat])
+                    self._ingest_packets(0, len(flat), now, held=(buf, np.array([p[2] for p in flat], dtype=np.uint16),
+                                                                  np.array([p[3] for p in flat], dtype=np.float64), [p[4] for p in flat]))
 
     def _note_checks(self, i0, checks, now):
         """check_sweeps: the checks of one guarded ingest whose first datagram is slot i0, in arrival order.  A withheld sweep

@@ -414,6 +414,50 @@ int qs_match_trails_device(qs_ctx *ctx, const qs_match_params *params, const uin
                            const uint16_t *d_lens, const int32_t *gsize, size_t n_groups, double travel,
                            qs_trail_match *d_out, double *d_rot_out);
 
+/* ---- trail relocalisation (no reference counterpart: this build's own rule) ------------------------------------------------
+ * Trail matching corrects a packet bot inside a small window; it cannot FIND one.  A bot that reboots, is carried, or joins a
+ * map another bot drew reports poses in a frame of its own.  Its trail -- T1-T5's -- is located over the whole map as a group
+ * of sweeps is (G4-G8 / J5): every FREE cell of the search box is a candidate cell of the anchor, every rotation step a
+ * candidate turn of the packet fields' frame.  Apart from one device sincos per record, which the call reports, everything is
+ * integer or uncontracted fp64: fed those values the CPU restatement (tests/trail_reloc_rules.py) agrees bit for bit.
+ *  K1. Groups: as T1, gsize[g] in 1..QS_TRAIL_MAX_RECORDS, summing to n; a HOST array in both entry points, refused before
+ *      anything is enqueued.
+ *  K2. Acceptance and anchor: as T2 (qs_ingest's rule).  The anchor is the last accepted record, the bot the anchor's agent.
+ *  K3. A record counts when it is accepted, is the bot's, and (X_k - X_a)^2 + (Y_k - Y_a)^2 <= travel^2 (uncontracted),
+ *      X, Y the f32 fields widened to f64.  The bot's offset and drift are NOT read: they are common to every record of the
+ *      trail and cancel in K4.  With no counting record: status QS_RELOC_NO_RECORD, anchor = -1, every other field zero.
+ *  K4. Points: (s, c) = the device's sincos(f64(yaw)), one per counting record, reported in rot_out[k] (zeros for the other
+ *      records).  Sensor directions are T5's sign flips; a range is a hit when min_dist < d <= max_dist (the context's trust
+ *      filter).  qx = (X_k - X_a) + d * ux, qy likewise: one subtract, one multiply, one add, no FMA.  H = the hits of the trail.
+ *  K5. Rotations: under rotation j the offsets are J5's, applied to (qx, qy), with M = ceil((max_dist + travel) / res) + 1.  A
+ *      point beyond M on an axis, or one that is not a number, scores 0 under that rotation.
+ *  K6. Candidates, order, rival and gate: G4-G7 with this H.  qs_reloc_params is unchanged; NULL gives its defaults.
+ *  K7. Result: the anchor stands at the centre of cell (gx, gy) and the frame of the packet fields is turned by th_j.  x, y
+ *      are that cell centre, yaw is G8's, ax = X_a, ay = Y_a.  A pose (px, py, pyaw) in the packet fields' frame moves to
+ *        (x + (C (px - ax) - S (py - ay)),  y + (S (px - ax) + C (py - ay)),  pyaw + yaw),  (S, C) of yaw.
+ *      Statuses as J7; QS_RELOC_NO_CANDIDATE still reports records, hits, anchor, agent, ax and ay.
+ *  K8. Limits: those of qs_reloc_params; travel finite and >= 0; 16 + 2 * (ceil((max_dist + travel) / res) + radius + 1) <=
+ *      255; stride >= 41.  A sharded context refuses, as qs_match_trails does.  QS_E_INVAL beyond any of them, and the text
+ *      names the quantity.
+ * The calls read the map (waiting exact-trig rays are flushed first) and write nothing to the context: a checkpoint taken
+ * before equals one taken after. */
+typedef struct qs_trail_reloc {          /* 88 bytes; offsets 0..41 and 48..71 are qs_group_reloc's */
+    int32_t gx, gy, j, score, hits;
+    int32_t gx2, gy2, j2, score2;
+    int32_t status;
+    uint8_t records, accepted, agent, pad;   /* pad is zero */
+    int32_t anchor;                          /* index within the group, -1 when records == 0 */
+    double x, y, yaw, ax, ay;
+} qs_trail_reloc;
+int qs_relocalise_trails(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *pkts, size_t n, size_t stride,
+                         const uint16_t *lens, const int32_t *gsize, size_t n_groups, double travel, qs_trail_reloc *out,
+                         double *rot_out /* n x 2, optional */);
+/* same with device-resident pkts / lens / out / rot_out (gsize stays a host array); asynchronous on the context's stream, with
+ * the exceptions of qs_relocalise_sweeps_device */
+int qs_relocalise_trails_device(qs_ctx *ctx, const qs_reloc_params *params, const uint8_t *d_pkts, size_t n, size_t stride,
+                                const uint16_t *d_lens, const int32_t *gsize, size_t n_groups, double travel,
+                                qs_trail_reloc *d_out, double *d_rot_out);
+
 /* ---- OccupancyGrid object API ----------------------------------------------------------
  * batched OccupancyGrid.update_ray(robot_x, robot_y, hit_x, hit_y, hit_valid)  :136-156 */
 int qs_update_rays(qs_ctx *ctx, const double *rx, const double *ry, const double *hx,

@@ -237,6 +237,14 @@ SIGNATURES = {
     "qs_ingest_sweeps_checked_device": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _u64]),
     "qs_last_sweep_checks": (_i32, [_vp, _vp, _sz]),
     "qs_last_hits": (_i32, [_vp, _vp, _vp, _sz]),
+    "qs_set_bot_veil": (_i32, [_vp, _i32]),
+    "qs_bot_veil": (_i32, [_vp, C.POINTER(_i32)]),
+    "qs_bot_veil_place": (_i32, [_vp, _i32, _f64, _f64]),
+    "qs_bot_veil_forget": (_i32, [_vp, _i32]),
+    "qs_bot_veil_cells": (_i32, [_vp, _vp, _vp]),
+    "qs_last_veiled": (_i32, [_vp, _vp, _sz]),
+    "qs_bot_veil_stats": (_i32, [_vp, C.POINTER(_u64)]),
+    "qs_bot_veil_time": (_i32, [_vp, C.POINTER(_f64), C.POINTER(_u64), _i32]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),
     "qs_grid_i8": (_i32, [_vp, _vp]),

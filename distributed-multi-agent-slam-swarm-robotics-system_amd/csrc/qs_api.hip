@@ -156,6 +156,11 @@ int reset_state(qs_ctx *c)
     c->last_checks = false; c->last_checks_n = 0;
     c->pile_mode = false;
     c->edge_maybe = false; c->edge_overflow_total = 0;      // (rays still waiting belonged to the old session: the flags are cleared above)
+    if (c->veil_tab.p) {                                    // bot veil, V2: an empty table (the setting itself is kept)
+        HIPCHK(c, hipMemsetAsync(c->veil_tab.p, 0, c->veil_tab.cap * sizeof(int4), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->veil_total.p, 0, sizeof(unsigned long long), c->stream));
+    }
+    c->last_veil = false;
     return QS_OK;
 }
 
@@ -742,6 +747,7 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
 {
     if (seq0 == UINT64_MAX) seq0 = c->next_seq;
     c->last_n = n; c->last_has_poses = true; c->last_sweeps = false; c->last_matches = false; c->last_checks = false;
+    c->last_veil = c->veil_radius > 0 && n > 0;
     if (n == 0) return QS_OK;
     int rc = qs_batch_prepare(c, n);
     if (rc != QS_OK) return rc;
@@ -765,7 +771,8 @@ static int ingest_device(qs_ctx *c, const uint8_t *d_pkts, size_t n, size_t stri
         StageTimer t(c, QS_STAGE_RAYCAST);
         // auto (0): a handful of packets (the live UDP path: <= 20 per frame) is one direct kernel instead
         // of the four tiled passes -- same cells either way; 1 = always direct, 2 = always tiled
-        if (c->cfg.raycast_mode == 1 || (c->cfg.raycast_mode == 0 && n <= QS_DIRECT_MAX_BATCH))
+        // (a veiled context always takes the tiled form: the direct kernel writes the end cell before anything could veil it)
+        if (c->cfg.raycast_mode == 1 || (c->cfg.raycast_mode == 0 && n <= QS_DIRECT_MAX_BATCH && c->veil_radius == 0))
             HIPCHK(c, qs_launch_raycast_direct(c, n, seq0));
         else HIPCHK(c, qs_launch_raycast_tiled(c, n, seq0));
         t.stop();

@@ -311,6 +311,13 @@ struct qs_ctx {
     DevBuf<double> reloc_rot;                   // relocalisation (reloc.hip): sin, cos, yaw of the reloc_nrot rotation steps, host's libm
     int reloc_nrot = 0;
     DevBuf<char> reloc_ws;                       //   ... census, score tables and picks of one chunk of sweeps (qs_reloc_layout)
+    // bot veil (veil.hip): off unless qs_set_bot_veil turned it on; table and word exist from the first call that needs them
+    int veil_radius = 0;                         // cells; 0 = off
+    DevBuf<int4> veil_tab;                       // [256] cell[bot]: x, y, known (V2)
+    DevBuf<unsigned long long> veil_total;       // [1] rays veiled since the last reset
+    DevBuf<char> veil_ws;                        // cells, block rows and flags of one ingest (veil.hip: qs_veil_layout)
+    unsigned char *veil_flags = nullptr;         //   ... the flags of the last veiled ingest (qs_last_veiled)
+    bool last_veil = false;                      // the last packet ingest ran the veil stage
 
     // map merge session (merge.hip): the merger node's state.  qs_reset and checkpoints leave it alone
     DevBuf<double2> mg_cloud;                    // the global cloud; grown by allocate-new-and-move (a failed growth keeps it)
@@ -354,8 +361,8 @@ struct qs_ctx {
     struct Pending { int stage; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> ev_pool;
-    double stage_ms[QS_STAGE_N]{};
-    uint64_t stage_launches[QS_STAGE_N]{};
+    double stage_ms[QS_STAGE_N + 1]{};           // (+ 1: the veil stage's own pair of events, which is no QS_STAGE_* of the ABI)
+    uint64_t stage_launches[QS_STAGE_N + 1]{};
 };
 
 // ---- HIP-event timing of stages and of single kernels, on the stream they are launched on -------
@@ -366,6 +373,7 @@ static inline hipEvent_t qs_ev_get(qs_ctx *c)
     hipEventCreate(&e);
     return e;
 }
+#define QS_STAGE_VEIL_INTERNAL QS_STAGE_N        // qs_bot_veil_time reads it; qs_stage_times never reports it
 struct StageTimer {
     qs_ctx *c; int stage; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
     StageTimer(qs_ctx *c_, int s, hipStream_t st_ = nullptr) : c(c_), stage(s), st(st_ ? st_ : c_->stream)
@@ -442,6 +450,9 @@ hipError_t qs_launch_world_to_grid(qs_ctx *c, const double *w, size_t n, int axi
 // raycast_tiled.hip
 hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0);
 bool qs_tiled_supported(const qs_ctx *c);
+// veil.hip: the veil stage over the n packets whose ray slots pass A has just written to `rays`; *hit_valid becomes the array
+// of masked hit flags that passes C and D are to read
+hipError_t qs_launch_veil(qs_ctx *c, const uint2 *rays, size_t n, const unsigned char **hit_valid);
 // sweep_graph.hip: signature and acceptance of n device-resident sweep records.  lm_out == nullptr: into the batch arrays from
 // record k0 on (QsBatch fields, graph_batch, agent_ev); otherwise only lm_out[k] (255 = rejected), nothing of the context
 hipError_t qs_launch_sweep_signatures(qs_ctx *c, const qs_sweep_graph_params &p, const unsigned char *d_pkts, size_t n, size_t stride,

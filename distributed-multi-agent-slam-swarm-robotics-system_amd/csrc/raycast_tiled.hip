@@ -489,5 +489,10 @@ hipError_t qs_launch_raycast_tiled(qs_ctx *c, size_t n, uint64_t seq0)
     qs_launch_counts(c, qs_rays_kernel<true>, qs_rays_kernel<false>, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, n, c->b, c->geom, ws,
                      c->d_stamps.p, c->d_counts.p, ord_base, ord_stride, c->d_zone.p, c->cfg.max_agent, c->d_counters.p);
     t_rays.stop();
-    return qt_launch_sort_raster(c, ws, 4 * n, c->b.hit_valid, ord_base, ord_stride, lds);
+    const unsigned char *hit_valid = c->b.hit_valid;
+    if (c->veil_radius > 0) {                        // bot veil: passes C and D read hit_valid & !veiled instead
+        e = qs_launch_veil(c, ws.rays, n, &hit_valid);
+        if (e != hipSuccess) return e;
+    }
+    return qt_launch_sort_raster(c, ws, 4 * n, hit_valid, ord_base, ord_stride, lds);
 }

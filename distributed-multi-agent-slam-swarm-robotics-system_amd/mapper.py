@@ -273,6 +273,52 @@ class QuasarMapper:
         self._chk(self._L.qs_last_hits(self._h, _ptr(xy), _ptr(valid), n), "qs_last_hits")
         return xy, valid
 
+    # -- bot veil (include/quasar_slam.h, rules V1-V7) -----------------------------------------------------------------------
+    def set_bot_veil(self, radius=P.BOT_VEIL_RADIUS):
+        """Veil packet beams that end within `radius` cells (1..32) of the cell where another bot was last heard: they are cast
+        free, without their end cell.  0 turns the veil off; the table of bot cells is kept either way."""
+        self._chk(self._L.qs_set_bot_veil(self._h, int(radius)), "qs_set_bot_veil")
+
+    def bot_veil(self):
+        """The veil's radius in cells; 0 = off."""
+        r = C.c_int32()
+        self._chk(self._L.qs_bot_veil(self._h, C.byref(r)), "qs_bot_veil")
+        return r.value
+
+    def bot_veil_place(self, bot, x, y):
+        """cell[bot] from a world position: a sweep bot (sweep ingests do not feed the table), a charging dock given a spare id."""
+        self._chk(self._L.qs_bot_veil_place(self._h, int(bot), float(x), float(y)), "qs_bot_veil_place")
+
+    def bot_veil_forget(self, bot=None):
+        """Forget where `bot` was last heard (None: every bot)."""
+        self._chk(self._L.qs_bot_veil_forget(self._h, 0 if bot is None else int(bot)), "qs_bot_veil_forget")
+
+    def bot_veil_cells(self):
+        """(xy int32 [max_agent + 1, 2], known uint8 [max_agent + 1]): the cell where each bot was last heard; row 0 is unused."""
+        xy = np.zeros((self.max_agent + 1, 2), dtype=np.int32)
+        known = np.zeros(self.max_agent + 1, dtype=np.uint8)
+        self._chk(self._L.qs_bot_veil_cells(self._h, _ptr(xy), _ptr(known)), "qs_bot_veil_cells")
+        return xy, known
+
+    def last_veiled(self):
+        """uint8 [n, 4]: the rays of the last packet ingest that the veil cast without their end cell (zeros with the veil off)."""
+        n = self._last_n
+        v = np.zeros((n, 4), dtype=np.uint8)
+        self._chk(self._L.qs_last_veiled(self._h, _ptr(v), n), "qs_last_veiled")
+        return v
+
+    def bot_veil_stats(self):
+        """Rays veiled since the context was created or reset."""
+        t = C.c_uint64()
+        self._chk(self._L.qs_bot_veil_stats(self._h, C.byref(t)), "qs_bot_veil_stats")
+        return t.value
+
+    def bot_veil_time(self, reset=True):
+        """(ms, launches) of the veil stage alone since the last reset of the figure; needs timing_enable()."""
+        ms, k = C.c_double(), C.c_uint64()
+        self._chk(self._L.qs_bot_veil_time(self._h, C.byref(ms), C.byref(k), int(reset)), "qs_bot_veil_time")
+        return ms.value, k.value
+
     # -- servo sweeps (v0 '<4sBfffH181f' / v0 + odometry '<4sBfffiIH181f'; include/quasar_slam.h) --------------------------
     def ingest_sweeps(self, datagrams, lengths=None, seq0=None, match=None, check=None):
         """Map servo-sweep packets: a list of bytes objects (one format: 743 or 751 bytes; other lengths are dropped) or a

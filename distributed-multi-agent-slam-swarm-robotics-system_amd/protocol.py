@@ -122,6 +122,7 @@ PACKET_DTYPE_V0_ODO = np.dtype([("magic", "S4"), ("agent", "u1"), ("x", "<f4"), 
 assert PACKET_DTYPE_V0_ODO.itemsize == PACKET_SIZE_V0_ODO
 SWEEP_BEAMS = 181
 SWEEP_SEQS = 46              # sequence numbers one sweep uses in the mapper's stamp order (include/quasar_slam.h)
+BOT_VEIL_RADIUS = 3          # cells: default radius of the bot veil (include/quasar_slam.h, "bot veil")
 SWEEP_MIN_DIST_M = 0.1       # trust filter of the reference's sweep map, generate_topdown_map.py:51
 SWEEP_MAX_DIST_M = 1.2
 # sweeps in the pose graph (include/quasar_slam.h, "sweeps in the pose graph"): the signature rule's defaults and limits

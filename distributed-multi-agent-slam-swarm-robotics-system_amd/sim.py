@@ -17,6 +17,38 @@ from .mapper import QuasarMapper
 
 STRATEGIES = ("nearest", "by_path", "by_territory", "by_gain")
 SIM_MIN_DIST_M = 0.02           # the sim mapper's trust filters start below one cell: a wall in the next cell returns d = res
+SENSOR_ANGLES = (0.0, math.pi / 2, math.pi, -math.pi / 2)     # front, left, back, right (dual_bot_mapper.py:61-66)
+
+
+def body_ranges(pose, agent, ranges, radius_m, max_range):
+    """The four f32 ranges of each packet with the other bots' bodies in the way: float32 [n, 4].  pose float [n, 3] (x, y, yaw),
+    agent [n], ranges float32 [n, 4] as the world returned them.  Every bot is a disc of radius_m about its pose; a beam takes
+    the nearest intersection (ray-circle, fp64) with a disc of another agent when that is nearer than the world's return.  A
+    beam without a return within max_range (not 0 < d <= max_range) takes the body distance when that lies within max_range."""
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1, 3)
+    agent = np.asarray(agent).reshape(-1)
+    out = np.array(ranges, dtype=np.float32).reshape(-1, 4)
+    r2 = float(radius_m) ** 2
+    for i in range(len(pose)):
+        other = agent != agent[i]
+        if not other.any():
+            continue
+        cx, cy = pose[other, 0] - pose[i, 0], pose[other, 1] - pose[i, 1]
+        for s, ang in enumerate(SENSOR_ANGLES):
+            a = pose[i, 2] + ang
+            ux, uy = math.cos(a), math.sin(a)
+            tca = cx * ux + cy * uy                              # along the beam to the point nearest the disc's centre
+            off2 = cx * cx + cy * cy - tca * tca
+            t = tca - np.sqrt(np.maximum(r2 - off2, 0.0))        # the near intersection
+            t = t[(off2 <= r2) & (t > 0.0)]                      # (a disc behind the sensor, or around it, returns nothing)
+            if not len(t):
+                continue
+            body = float(t.min())
+            d = float(out[i, s])
+            world = d if 0.0 < d <= max_range else math.inf
+            if body < world and body <= max_range:
+                out[i, s] = np.float32(body)
+    return out
 
 
 class SwarmSim:
@@ -24,11 +56,18 @@ class SwarmSim:
 
     kind       "sweeps" (751-byte records, 181 beams over the front half plane) or "packets" (42-byte records, four beams)
     max_range  the sensor's reach R in metres; speed  metres per second in drive()
-    noise      noise_amp, dropout, seed of QuasarMapper.sense_params; record k of tick t draws as record t * n + k"""
+    noise      noise_amp, dropout, seed of QuasarMapper.sense_params; record k of tick t draws as record t * n + k
+    bodies     None, or the bots' body radius in metres (kind "packets" only): the bots see each other.  The tick then takes the
+               host path: the world's packets come to the host, body_ranges shortens the beams that end on another bot, and the
+               mapper ingests the host array"""
 
-    def __init__(self, world, mapper, poses, kind="sweeps", max_range=P.MAX_DIST_M, speed=0.5, **noise):
+    def __init__(self, world, mapper, poses, kind="sweeps", max_range=P.MAX_DIST_M, speed=0.5, bodies=None, **noise):
         if kind not in ("sweeps", "packets"):
             raise ValueError("kind must be 'sweeps' or 'packets'")
+        if bodies is not None and kind != "packets":
+            raise ValueError("bodies needs kind='packets'")
+        self.bodies = None if bodies is None else float(bodies)
+        self._h_pkts = None
         unknown = set(noise) - {"noise_amp", "dropout", "seed"}
         if unknown:
             raise ValueError(f"unknown noise parameters: {sorted(unknown)}")
@@ -66,6 +105,18 @@ class SwarmSim:
         """Cast every bot's record from the world and ingest it into the mapper; the records stay on the device.  Ordering
         between the two contexts' streams is by qs_sync: on the mapper before the buffer is overwritten (its last ingest has
         read it), on the world before the mapper is handed the buffer (the cast has written it)."""
+        if self.bodies is not None:
+            kw = dict(max_range=self.max_range, first_record=self.tick * self.n, **self.noise)
+            agent = np.arange(1, self.n + 1, dtype=np.uint8)
+            pk = self.world.sense_packets(self.poses, agent, enc=np.full(self.n, self.tick, dtype=np.int32), **kw)
+            rec = pk.view(P.PACKET_DTYPE).reshape(-1)
+            d4 = np.stack([rec[k] for k in ("front", "left", "back", "right")], axis=1)
+            d4 = body_ranges(self.poses, agent, d4, self.bodies, self.max_range)
+            for j, k in enumerate(("front", "left", "back", "right")):
+                rec[k] = d4[:, j]
+            self._h_pkts = pk
+            self.mapper.ingest_array(pk)
+            return
         self.mapper.sync()
         self._d_pose.copy_(torch.from_numpy(self.poses))   # a blocking copy: complete when it returns
         self._d_enc.fill_(self.tick)
@@ -84,6 +135,8 @@ class SwarmSim:
     def last_records(self):
         """uint8 [n, stride]: the records of the last sense() (a copy to the host, for inspection)."""
         self.mapper.sync()
+        if self._h_pkts is not None:
+            return self._h_pkts.copy()
         return self._d_pkts.cpu().numpy().reshape(self.n, self.stride)
 
     # -- drive: host only, deterministic ----------------------------------------------------------------------------------------

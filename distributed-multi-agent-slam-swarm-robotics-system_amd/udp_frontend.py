@@ -103,7 +103,7 @@ class MissionControl:
                  frontier_targets=False, sweeps=False, plan_paths=False, plan_params=None, match_sweeps=False,
                  match_params=None, targets_by_path=False, sweep_graph=False, track_view=False,
                  targets_by_territory=False, targets_by_gain=False, gain_params=None, relocalise=False, check_sweeps=False,
-                 match_packets=False):
+                 match_packets=False, bot_veil=False):
         by = [k for k, on in (("targets_by_path", targets_by_path), ("targets_by_territory", targets_by_territory),
                               ("targets_by_gain", targets_by_gain)) if on]
         if not frontier_targets and (plan_paths or by):         # each of them refines frontier_targets
@@ -178,6 +178,12 @@ class MissionControl:
         self.trail_stats = {"held": 0, "tried": 0, "accepted": 0, "moved": 0, "rewritten": 0}
         if self.trail_reloc:
             self.trail_stats.update(reloc_tried=0, reloc_accepted=0, reloc_gave_up=0)
+        # bot_veil=True or {"radius": r}: the mapper's bot veil (QuasarMapper.set_bot_veil) is turned on here; a bot found offline
+        # is forgotten (carried away, it must not leave a blind disc), and with sweeps=True every sweep bot is placed at the pose
+        # of its latest accepted sweep after each sweep ingest (sweep ingests do not feed the veil's table themselves)
+        self.bot_veil = bot_veil is not False and bot_veil is not None
+        if self.bot_veil:
+            mapper.set_bot_veil(**(dict(bot_veil) if isinstance(bot_veil, dict) else {}))
         self.track_view = track_view
         self.point_clouds = {b: {s: [] for s in P.SENSOR_NAMES} for b in range(1, max_agent + 1)}      # :768-771
         self.paths = {b: ([], []) for b in range(1, max_agent + 1)}                                    # :772
@@ -275,6 +281,10 @@ class MissionControl:
                 self._mark(i0, accepted, pose, now, pose is not None)
                 if self.check_sweeps:
                     self._note_checks(i0, self.last_checks, now)
+                if self.bot_veil and pose is not None:
+                    latest = {int(self._buf[i0 + int(j), 4]): int(j) for j in np.nonzero(accepted)[0]}
+                    for a, j in latest.items():
+                        self.mapper.bot_veil_place(a, float(pose[j, 0]), float(pose[j, 1]))
 
     def _ingest_packets(self, i0, i1, now, held=None):
         """Slots i0 .. i1 of the receive buffer as one packet ingest, and its bookkeeping.  held (match_packets): the flushed
@@ -594,6 +604,8 @@ class MissionControl:
                 if self.online[b]:
                     self.online[b] = False
                     went_offline.append(b)
+                    if self.bot_veil:
+                        self.mapper.bot_veil_forget(b)
         return went_offline
 
     def other_of(self, bot_id):

@@ -110,6 +110,51 @@ int qs_last_batch(qs_ctx *ctx, uint8_t *accepted, double *pose_xyyaw /* n x 3 */
  * only needs the rays' grid cells. */
 int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 4 */, size_t n);
 
+/* ---- bot veil (no reference counterpart: this build's own rule) --------------------------------------------------------------
+ * The bots of a swarm drive in the same rooms, and a beam that ends on another bot would leave an OCCUPIED cell in free space.
+ * With the veil on, a packet beam whose end cell lies within `radius` cells of the cell where another bot was last heard is
+ * cast as a free ray without its end cell: the space up to the bot is free, what lies at and behind it is not known from this
+ * beam.  Off by default; with it off every call, buffer and launch is what it is without this section.  All integer:
+ *   V1  The cell of an accepted packet is world_to_grid (int((w - o) / res), :121-125) of its pose after offset and drift, on
+ *       both axes -- the pose qs_last_batch reports.  A pose that is not finite, or whose cell on either axis does not lie
+ *       strictly inside +-2^30, has no cell.
+ *   V2  The context keeps a table cell[bot], bot 1..max_agent: unknown, or known with an (x, y).  qs_reset empties it;
+ *       qs_restore empties it (checkpoints do not carry it; their format does not know of it).
+ *   V3  For ray s of accepted packet i with agent a, and every bot b != a: the cell of the last accepted packet q < i of this
+ *       call with agent b that has a cell; failing that the table's entry for b as it stood when the call began; failing that
+ *       there is nothing to test for b.  Rejected packets and packets without a cell never count.
+ *   V4  The ray is VEILED when all of these hold: its hit flag is set (min_dist < d <= max_dist); the tiled raycast binned it
+ *       (it was not left to the host by the exact-trig rule and is shorter than 64 cells on both axes: a longer one is written
+ *       directly); its end cell (x1, y1) lies inside the grid (outside there is nothing to withhold); and for some b of V3
+ *       (x1 - bx)^2 + (y1 - by)^2 <= radius^2.
+ *   V5  A veiled ray's free cells are written as before; its end cell gets neither stamp nor counter.  Nothing else changes:
+ *       qs_last_hits, the zone boxes, QS_CNT_HITS / RAYS and the pose graph see the beam as the filter judged it.
+ *       (QS_CNT_CELLS counts cells written, so it is lower by one per veiled ray.)
+ *   V6  After the call cell[b] is the cell of b's last accepted packet with a cell; unchanged for bots the call did not hear.
+ *   V7  Never veiled: rays left to the host (exact_trig) and rays written directly (V4); qs_update_rays; every sweep entry
+ *       point (sweep bots reach the table through qs_bot_veil_place only).
+ * A veiled context casts every packet ingest in the tiled form, whatever n is (the direct kernel writes the end cell before
+ * anything could veil it); both forms write the same cells.
+ * qs_set_bot_veil: radius in cells, 1..QS_BOT_VEIL_MAX_RADIUS, 0 = off; the table is kept.  QS_E_INVAL (and the setting
+ * unchanged) beyond the range, for raycast_mode == 1, for a grid the tiled form does not support (more than 8192 cells a
+ * side), and for sharded contexts (seq_stride > 1 or shard_bots > 0).  Kept over qs_reset and qs_restore.
+ * qs_bot_veil_place: cell[bot] by V1 from a world position (a sweep bot, a charging dock given a spare id); QS_E_RANGE for a
+ * bot outside 1..max_agent or a position without a cell.  qs_bot_veil_forget: cell[bot] unknown; bot 0: all of them.
+ * qs_bot_veil_cells: the table; xy[2 b], xy[2 b + 1] and known[b] for b = 0..max_agent (entry 0 is never known).
+ * qs_last_veiled: the flags of the last packet ingest, 4 per record (n must match, as qs_last_hits); all zero after an ingest
+ * with the veil off.  qs_bot_veil_stats: rays veiled since qs_create / qs_reset.  qs_bot_veil_time: with qs_timing_enable, the
+ * veil stage's own milliseconds and launches (a part of QS_STAGE_RAYCAST; it is no stage of qs_stage_times). */
+#define QS_BOT_VEIL_DEFAULT_RADIUS 3
+#define QS_BOT_VEIL_MAX_RADIUS 32
+int qs_set_bot_veil(qs_ctx *ctx, int32_t radius_cells);
+int qs_bot_veil(qs_ctx *ctx, int32_t *radius_cells);
+int qs_bot_veil_place(qs_ctx *ctx, int32_t bot, double x, double y);
+int qs_bot_veil_forget(qs_ctx *ctx, int32_t bot);
+int qs_bot_veil_cells(qs_ctx *ctx, int32_t *xy /* (max_agent + 1) x 2 */, uint8_t *known /* max_agent + 1 */);
+int qs_last_veiled(qs_ctx *ctx, uint8_t *veiled /* n x 4 */, size_t n);
+int qs_bot_veil_stats(qs_ctx *ctx, uint64_t *veiled_total);
+int qs_bot_veil_time(qs_ctx *ctx, double *ms, uint64_t *launches, int32_t reset);
+
 /* ---- servo sweeps ("Quasar-Lite" packets) ----------------------------------------------------------------------------
  * A sweep carries a pose and 181 ranges swept from -90 to +90 degrees about the heading:
  *   v0              '<4sBfffH181f'   743 bytes  (esp32_firmware/src/main.cpp:33-41; udp_bridge.py:25-38)

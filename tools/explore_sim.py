@@ -3,7 +3,11 @@
 strategy (nearest, by_path, by_territory, by_gain), sensing on the device (sim.SwarmSim).  Prints one JSON line per strategy:
 the mapper's known cells after every --every ticks.
 
-    python tools/explore_sim.py [--size 400] [--bots 4] [--ticks 120] [--kind sweeps] [--seed 1]
+    python tools/explore_sim.py [--size 400] [--bots 4] [--ticks 120] [--kind sweeps] [--seed 1] [--bodies R] [--veil r]
+
+--bodies R (metres; --kind packets): the bots are discs of that radius and see each other (sim.SwarmSim(bodies=R)); --veil r
+turns the mapper's bot veil on with a radius of r cells.  Every line also carries "phantom": the cells OCCUPIED in the mapper
+and FREE in the world when the run ends -- walls that are not there.
 
 The world ("rooms"): a walled floor that leaves a 10-cell margin, cut into rooms of 60 cells by walls with a 12-cell door in
 every stretch, plus --seed's 30 random pillars of 2 to 5 cells.  The bots start together in the middle room, 0.3 m apart,
@@ -64,6 +68,8 @@ def main():
     ap.add_argument("--max-range", type=float, default=1.2)
     ap.add_argument("--speed", type=float, default=0.4)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--bodies", type=float, default=None, metavar="R", help="body radius in metres: the bots see each other (packets)")
+    ap.add_argument("--veil", type=int, default=0, metavar="r", help="radius of the mapper's bot veil in cells (0 = off)")
     a = ap.parse_args()
     res = 0.05
     half = a.size * res / 2
@@ -75,14 +81,18 @@ def main():
     starts = [(cx + 0.3 * math.cos(t), cx + 0.3 * math.sin(t), math.atan2(math.sin(t), math.cos(t))) for t in ring]
     with qa.QuasarMapper(a.size, res, -half, -half) as world:
         paint(world, occ, lo, hi)
-        floor = int((world.grid_i8() != -1).sum())
+        truth = world.grid_i8()
+        floor = int((truth != -1).sum())
         for strategy in sim.STRATEGIES:
             with sim.SwarmSim.make_mapper(world, max_agent=a.bots, max_range=a.max_range) as m:
-                s = sim.SwarmSim(world, m, starts, kind=a.kind, max_range=a.max_range, speed=a.speed)
+                if a.veil:
+                    m.set_bot_veil(a.veil)
+                s = sim.SwarmSim(world, m, starts, kind=a.kind, max_range=a.max_range, speed=a.speed, bodies=a.bodies)
                 for _ in range(a.ticks):
                     s.step(strategy)
                 print(json.dumps(dict(strategy=strategy, world="rooms", size=a.size, seed=a.seed, bots=a.bots, kind=a.kind,
                                       max_range=a.max_range, speed=a.speed, world_cells=floor, every=a.every,
+                                      bodies=a.bodies, veil=a.veil, phantom=int(((m.grid_i8() == 100) & (truth == 0)).sum()),
                                       known=s.history[a.every - 1::a.every], final=s.history[-1])), flush=True)
 
 

@@ -245,6 +245,9 @@ SIGNATURES = {
     "qs_last_veiled": (_i32, [_vp, _vp, _sz]),
     "qs_bot_veil_stats": (_i32, [_vp, C.POINTER(_u64)]),
     "qs_bot_veil_time": (_i32, [_vp, C.POINTER(_f64), C.POINTER(_u64), _i32]),
+    "qs_set_bot_veil_sweeps": (_i32, [_vp, _i32]),
+    "qs_bot_veil_sweeps": (_i32, [_vp, C.POINTER(_i32)]),
+    "qs_last_sweeps_veiled": (_i32, [_vp, _vp, _sz]),
     "qs_update_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u64]),
     "qs_world_to_grid": (_i32, [_vp, _vp, _sz, _i32, _vp]),
     "qs_grid_i8": (_i32, [_vp, _vp]),

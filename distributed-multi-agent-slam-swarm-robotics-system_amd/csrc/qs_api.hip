@@ -161,6 +161,7 @@ int reset_state(qs_ctx *c)
         HIPCHK(c, hipMemsetAsync(c->veil_total.p, 0, sizeof(unsigned long long), c->stream));
     }
     c->last_veil = false;
+    c->last_sveil = false;
     return QS_OK;
 }
 

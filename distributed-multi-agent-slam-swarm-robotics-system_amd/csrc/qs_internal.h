@@ -318,6 +318,10 @@ struct qs_ctx {
     DevBuf<char> veil_ws;                        // cells, block rows and flags of one ingest (veil.hip: qs_veil_layout)
     unsigned char *veil_flags = nullptr;         //   ... the flags of the last veiled ingest (qs_last_veiled)
     bool last_veil = false;                      // the last packet ingest ran the veil stage
+    bool veil_sweeps = false;                    // sweeps too (qs_set_bot_veil_sweeps, rules S0-S8); acts only while veil_radius > 0
+    DevBuf<char> sveil_ws;                       //   ... the sweep stage's workspace (veil.hip: qs_sveil_layout), laid out for
+    size_t sveil_cap = 0, sveil_n = 0;           //   sveil_cap sweeps a chunk and the sveil_n sweeps of the call whose flags it holds
+    bool last_sveil = false;                     //   the last sweep ingest ran the stage (qs_last_sweeps_veiled)
 
     // map merge session (merge.hip): the merger node's state.  qs_reset and checkpoints leave it alone
     DevBuf<double2> mg_cloud;                    // the global cloud; grown by allocate-new-and-move (a failed growth keeps it)
@@ -453,6 +457,11 @@ bool qs_tiled_supported(const qs_ctx *c);
 // veil.hip: the veil stage over the n packets whose ray slots pass A has just written to `rays`; *hit_valid becomes the array
 // of masked hit flags that passes C and D are to read
 hipError_t qs_launch_veil(qs_ctx *c, const uint2 *rays, size_t n, const unsigned char **hit_valid);
+// ... and the sweep stage: qs_sweep_veil_reserve once per call (chunks of at most chunk_cap sweeps, n_call sweeps in all), then
+// qs_launch_sweep_veil per chunk after the sweeps' pass A (accept, pose: the chunk's; k_call0: the record of the call its record 0 is)
+hipError_t qs_sweep_veil_reserve(qs_ctx *c, size_t chunk_cap, size_t n_call);
+hipError_t qs_launch_sweep_veil(qs_ctx *c, const unsigned char *d_pkts, size_t stride, const unsigned char *accept, const double *pose,
+                                const uint2 *rays, size_t n, size_t k_call0, const unsigned char **hit_valid);
 // sweep_graph.hip: signature and acceptance of n device-resident sweep records.  lm_out == nullptr: into the batch arrays from
 // record k0 on (QsBatch fields, graph_batch, agent_ev); otherwise only lm_out[k] (255 = rejected), nothing of the context
 hipError_t qs_launch_sweep_signatures(qs_ctx *c, const qs_sweep_graph_params &p, const unsigned char *d_pkts, size_t n, size_t stride,

@@ -22,6 +22,8 @@
 // these kernels' CORR instantiations, which add each record's correction to its pose before anything else.
 // The guarded ingest (qs_ingest_sweeps_checked*, same place) runs check.hip's kernel over the whole call and then these kernels'
 // VETO instantiations, which treat a record its check contradicts as a rejected one.
+// The bot veil for sweeps (veil.hip, rules S0-S8), while it acts, is a stage between pass A and the sort of every chunk: it reads what
+// pass A left (accept, pose, ray slots, hit flags) and hands passes C and D the flags with the veiled beams taken out.
 #include <math.h>
 #include <algorithm>
 
@@ -30,6 +32,7 @@
 #include "sweep_common.h"
 
 #define SW_DIRECT_BLOCK 256       // direct kernel: 4 records per workgroup
+#define QS_SWEEP_NO_VEIL ((size_t)-1)      // "the sweep veil is not acting" where a launch is told which record of the call it starts at
 
 // beam i: angle ryaw + math.radians(i - 90) -- CPython's radians is x * (pi / 180), one multiply and one add (no FMA: the
 // library is built with -ffp-contract=off); hit and free-ray rule as qs_project_ray's (A6): NaN, 0 and negative ranges give
@@ -189,9 +192,10 @@ qs_sweep_direct_kernel(QsSweepArgs a, QsBatch b, QsGeom geo, unsigned int *__res
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-// n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]
+// n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]; veil_k0: QS_SWEEP_NO_VEIL,
+// or (the sweep veil is acting, S0) the record of the call these records start at
 template <bool CORR, bool GRAPH, bool VETO = false>
-static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, bool tiled, unsigned char *hit_valid)
+static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, bool tiled, unsigned char *hit_valid, size_t veil_k0)
 {
     if (!tiled || !qs_tiled_supported(c)) {
         const unsigned int blocks = (unsigned int)((n + SW_DIRECT_BLOCK / QS_WAVE - 1) / (SW_DIRECT_BLOCK / QS_WAVE));
@@ -217,8 +221,13 @@ static hipError_t qs_launch_sweeps_t(qs_ctx *c, const QsSweepArgs &a, size_t n, 
     qs_launch_counts(c, on, off, dim3(ws.nwg), dim3(QT_BIN_BLOCK), lds, a, c->b, c->geom, ws, hit_valid, c->d_stamps.p, c->d_counts.p,
                      c->d_counters.p);
     t_rays.stop();
+    const unsigned char *hv = hit_valid;
+    if (veil_k0 != QS_SWEEP_NO_VEIL) {                     // bot veil, S3-S4: passes C and D read hit_valid & !veiled instead
+        e = qs_launch_sweep_veil(c, a.pkts, a.stride, a.accept, a.pose, ws.rays, n, veil_k0, &hv);
+        if (e != hipSuccess) return e;
+    }
     // slot r = 184 k + i has arrival index ord_base + 4 (r >> 2) + (r & 3) = ord_base + r: the 4-ray layout's
-    return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hit_valid, a.ord_base, 4ull, lds);
+    return qt_launch_sort_raster(c, ws, QS_SWEEP_SLOTS * n, hv, a.ord_base, 4ull, lds);
 }
 
 // what every sweep kernel reads of the context (match.hip fills its own with it too).  graph_k0: QS_SWEEP_NO_GRAPH, or the record of
@@ -242,10 +251,10 @@ void qs_sweep_args(const qs_ctx *c, const unsigned char *d_pkts, size_t n, size_
 
 // n records of one chunk; seq0 of record 0; outputs per record (accept [n], pose [n][3]), hit flags [184 n]; corr: the
 // matched ingest's corrections of these records, nullptr for the plain ingest; veto: the guarded ingest's checks of them (never
-// with corr or in graph mode), nullptr otherwise; graph_k0 as qs_sweep_args takes it
+// with corr or in graph mode), nullptr otherwise; graph_k0 as qs_sweep_args takes it; veil_k0 as qs_launch_sweeps_t takes it
 static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_t n, size_t stride, const unsigned short *d_lens,
                                    uint64_t seq0, bool tiled, unsigned char *accept, double *pose, unsigned char *hit_valid,
-                                   const qs_sweep_match *corr, const qs_sweep_check *veto, size_t graph_k0)
+                                   const qs_sweep_match *corr, const qs_sweep_check *veto, size_t graph_k0, size_t veil_k0)
 {
     if (n == 0) return hipSuccess;
     QsSweepArgs a;
@@ -253,9 +262,10 @@ static hipError_t qs_launch_sweeps(qs_ctx *c, const unsigned char *d_pkts, size_
     a.accept = accept; a.pose = pose;
     a.ord_base = qs_ord_base(c, seq0);
     a.corr = corr; a.veto = veto;
-    if (veto) return qs_launch_sweeps_t<false, false, true>(c, a, n, tiled, hit_valid);
-    if (a.g_accept) return corr ? qs_launch_sweeps_t<true, true>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, true>(c, a, n, tiled, hit_valid);
-    return corr ? qs_launch_sweeps_t<true, false>(c, a, n, tiled, hit_valid) : qs_launch_sweeps_t<false, false>(c, a, n, tiled, hit_valid);
+    if (veto) return qs_launch_sweeps_t<false, false, true>(c, a, n, tiled, hit_valid, veil_k0);
+    if (a.g_accept)
+        return corr ? qs_launch_sweeps_t<true, true>(c, a, n, tiled, hit_valid, veil_k0) : qs_launch_sweeps_t<false, true>(c, a, n, tiled, hit_valid, veil_k0);
+    return corr ? qs_launch_sweeps_t<true, false>(c, a, n, tiled, hit_valid, veil_k0) : qs_launch_sweeps_t<false, false>(c, a, n, tiled, hit_valid, veil_k0);
 }
 
 // ---- C ABI: servo sweeps (semantics in include/quasar_slam.h) --------------------------------------------------------
@@ -268,6 +278,7 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
     c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
     c->last_checks = false; c->last_checks_n = 0;          // qs_last_sweep_checks: only after a guarded ingest
     c->last_sweep_graph = false;                           // qs_last_sweep_nodes: only after an ingest in graph mode
+    c->last_sveil = false;                                 // qs_last_sweeps_veiled: zeros unless the sweep veil acted
     if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
     if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
@@ -287,16 +298,17 @@ static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 
 // records [k0, k0 + m) of the call, at d_pkts (already offset to record k0); graph: the call runs in graph mode
 static int sweeps_chunk(qs_ctx *c, const uint8_t *d_pkts, size_t m, size_t stride, const uint16_t *d_lens, uint64_t seq0, size_t k0,
-                        bool graph, const qs_sweep_match *corr, const qs_sweep_check *veto)
+                        bool graph, const qs_sweep_match *corr, const qs_sweep_check *veto, bool veil)
 {
     const uint64_t s0 = seq0 + (uint64_t)QS_SWEEP_SEQS * k0;
     int rc = ensure_epoch(c, s0, QS_SWEEP_SEQS * m);
     if (rc != QS_OK) return rc;
     // auto: by ray slots, as the 4-ray path decides by its 4 rays per packet
-    const bool tiled = c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
+    // (S6: with the sweep veil acting always the tiled form -- the direct kernel writes the end cell before anything could veil it)
+    const bool tiled = veil || c->cfg.raycast_mode == 2 || (c->cfg.raycast_mode == 0 && QS_SWEEP_SLOTS * m > 4 * (size_t)QS_DIRECT_MAX_BATCH);
     StageTimer t(c, QS_STAGE_RAYCAST);
     HIPCHK(c, qs_launch_sweeps(c, d_pkts, m, stride, d_lens, s0, tiled, c->sweep_acc.p + k0, c->sweep_pose.p + 3 * k0, c->sweep_hv.p,
-                               corr, veto, graph ? k0 : QS_SWEEP_NO_GRAPH));
+                               corr, veto, graph ? k0 : QS_SWEEP_NO_GRAPH, veil ? k0 : QS_SWEEP_NO_VEIL));
     t.stop();
     c->dirty_since_fuse = true;
     return QS_OK;
@@ -326,6 +338,9 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
     if (rc != QS_OK || n == 0) return rc;
     if (ms) HIPCHK(c, c->match_out.reserve(n, c->stream, 1024));
     if (cs) HIPCHK(c, c->check_out.reserve(n, c->stream, 1024));
+    // bot veil, S0: the sweep stage acts only with the switch on and a radius; otherwise nothing of it is touched
+    const bool veil = c->veil_sweeps && c->veil_radius > 0;
+    if (veil) HIPCHK(c, qs_sweep_veil_reserve(c, std::min(n, QS_SWEEP_CHUNK), n));
     const bool pre = ms || cs;                             // a pass over the whole call before any of it is mapped
     if (pre) SYNCCHK(c);                                   // it reads the map: waiting edge beams go in first
     // Graph mode (qs_set_sweep_graph): before any chunk is mapped or matched, the pass over the whole call that decides every
@@ -361,7 +376,7 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
                 if (cs && (pass == 0 || one)) HIPCHK(c, qs_launch_check(c, *cs, d_pkts, m, stride, d_lens, veto + k0, nullptr));
             }
             if (pass == 1) {
-                rc = sweeps_chunk(c, d_pkts, m, stride, d_lens, seq0, k0, graph, ms ? corr + k0 : nullptr, cs ? veto + k0 : nullptr);
+                rc = sweeps_chunk(c, d_pkts, m, stride, d_lens, seq0, k0, graph, ms ? corr + k0 : nullptr, cs ? veto + k0 : nullptr, veil);
                 if (rc != QS_OK) return rc;
             }
         }
@@ -369,6 +384,7 @@ static int sweeps_ingest(qs_ctx *c, bool matched, const qs_match_params *params,
     if (c->b.edge) c->edge_maybe = true;                   // resolved at the next point the map is observed (sync_host_state)
     c->next_seq = seq0 + (uint64_t)QS_SWEEP_SEQS * n;
     c->last_sweeps = true; c->last_sweeps_n = n;
+    c->last_sveil = veil;
     if (ms) { c->last_matches = true; c->last_matches_n = n; }
     if (cs) { c->last_checks = true; c->last_checks_n = n; }
     // host, as qs_ingest: the call waits for the GPU anyway, so the waiting edge beams are resolved now

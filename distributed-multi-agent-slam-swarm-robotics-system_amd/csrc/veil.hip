@@ -15,6 +15,8 @@
 //                         bot iff the bot has no packet in (q, p)) and at the entry row for the bots without a packet before
 //                         p; all of these are wave-uniform LDS reads (broadcast, no bank conflicts)
 // No global atomics but the one statistics word (one per workgroup that veiled anything), no wait for host or device.
+// Sweep beams are veiled by a stage of the same shape (rules S0-S8), further down: it shares the table, the statistics word and
+// the scan over blocks (qv_scan_bot) with the packet stage.
 #include "raycast_tiled.h"
 #include <cstring>
 #include <vector>
@@ -68,22 +70,23 @@ qs_veil_cells_kernel(size_t n, QsBatch b, QsGeom geo, QvWorkspace vw)
     vw.blk_last[(size_t)blockIdx.x * QV_BLOCK + tid] = (unsigned short)s_last[tid];
 }
 
-__global__ void __launch_bounds__(QV_BLOCK)
-qs_veil_scan_kernel(int n_blocks, QsBatch b, QsGeom geo, QvWorkspace vw, int4 *__restrict__ tab, int max_agent)
+// "latest cell" of one bot carried over the blocks, by one wave: what the packet stage and the sweep stage (below) share.  cell,
+// blk_last and blk_in are the stage's arrays of those names; pose_at(i, rx, ry) gives the pose record i of the call was cast from
+template <class PoseAt>
+__device__ inline void qv_scan_bot(int n_blocks, const unsigned int *__restrict__ cell, const unsigned short *__restrict__ blk_last,
+                                   unsigned int *__restrict__ blk_in, const QsGeom &geo, int4 *__restrict__ tab, int bot, int lane,
+                                   PoseAt pose_at)
 {
-    const int lane = threadIdx.x & (QS_WAVE - 1);
-    const int bot = 1 + blockIdx.x * (QV_BLOCK / QS_WAVE) + (threadIdx.x >> 6);
-    if (bot > max_agent) return;                                   // (wave-uniform)
     const int4 t = tab[bot];
     unsigned int carry = t.z ? qv_pack(t.x, t.y) : QV_NONE;
-    long long last_i = -1;                                         // the bot's last packet with a cell in this call
+    long long last_i = -1;                                         // the bot's last record with a cell in this call
     for (int b0 = 0; b0 < n_blocks; b0 += QS_WAVE) {
         const int blk = b0 + lane;
         unsigned int v = QV_NONE;
         long long mine = -1;
         if (blk < n_blocks) {
-            const unsigned int l = vw.blk_last[(size_t)blk * QV_BLOCK + bot];
-            if (l) { mine = (long long)blk * QV_BLOCK + (l - 1); v = vw.cell[mine]; }
+            const unsigned int l = blk_last[(size_t)blk * QV_BLOCK + bot];
+            if (l) { mine = (long long)blk * QV_BLOCK + (l - 1); v = cell[mine]; }
         }
         // inclusive scan of "the latest cell" over the 64 blocks (a (+) b = b unless b is none), the carry entering at lane 0
         unsigned int inc = (lane == 0 && qv_none(v)) ? carry : v;
@@ -93,7 +96,7 @@ qs_veil_scan_kernel(int n_blocks, QsBatch b, QsGeom geo, QvWorkspace vw, int4 *_
             if (lane >= off && qv_none(inc)) inc = u;
         }
         const unsigned int prev = __shfl_up(inc, 1);
-        if (blk < n_blocks) vw.blk_in[(size_t)blk * QV_BLOCK + bot] = lane == 0 ? carry : prev;
+        if (blk < n_blocks) blk_in[(size_t)blk * QV_BLOCK + bot] = lane == 0 ? carry : prev;
         carry = __shfl(inc, QS_WAVE - 1);
         #pragma unroll
         for (int off = 32; off > 0; off >>= 1) { const long long o = __shfl_xor(mine, off); mine = o > mine ? o : mine; }
@@ -101,9 +104,21 @@ qs_veil_scan_kernel(int n_blocks, QsBatch b, QsGeom geo, QvWorkspace vw, int4 *_
     }
     if (lane == 0 && last_i >= 0) {                                // V6, from the pose itself: the table holds unclamped cells
         int x = 0, y = 0;
-        qv_cell(b.rx[last_i], b.ry[last_i], geo, x, y);
+        double rx, ry;
+        pose_at(last_i, rx, ry);
+        qv_cell(rx, ry, geo, x, y);
         tab[bot] = make_int4(x, y, 1, 0);
     }
+}
+
+__global__ void __launch_bounds__(QV_BLOCK)
+qs_veil_scan_kernel(int n_blocks, QsBatch b, QsGeom geo, QvWorkspace vw, int4 *__restrict__ tab, int max_agent)
+{
+    const int lane = threadIdx.x & (QS_WAVE - 1);
+    const int bot = 1 + blockIdx.x * (QV_BLOCK / QS_WAVE) + (threadIdx.x >> 6);
+    if (bot > max_agent) return;                                   // (wave-uniform)
+    qv_scan_bot(n_blocks, vw.cell, vw.blk_last, vw.blk_in, geo, tab, bot, lane,
+                [&](long long i, double &rx, double &ry) { rx = b.rx[i]; ry = b.ry[i]; });
 }
 
 __global__ void __launch_bounds__(QV_BLOCK)
@@ -195,6 +210,190 @@ __global__ void qs_veil_table_kernel(int4 *tab, int bot, int x, int y, int known
     else tab[threadIdx.x] = make_int4(0, 0, 0, 0);
 }
 
+// ---- the sweep stage (rules S0-S8) ------------------------------------------------------------------------------------------
+// The same question per chunk of a sweep call, between the sweeps' pass A and the sort: pass A has left accept[k], pose[3 k ..],
+// the ray slots 184 k + i and their hit flags; the agent is byte 4 of the record.  Three kernels, as above:
+//   qs_sveil_cells_kernel  one thread per sweep: its cell (S1), its agent, the block rows
+//   qs_sveil_scan_kernel   qv_scan_bot over the chunk's blocks, seeded from and written back to the table: the next chunk of the call
+//                          and the next call find the bots where this chunk left them (S2, S5)
+//   qs_sveil_mark_kernel   one workgroup per block of QV_BLOCK sweeps, one WAVE per sweep, 16 consecutive sweeps a wave.  Per bot the
+//                          block keeps a bit row in LDS (bit q: sweep q of the block is the bot's and has a cell), so "b's last
+//                          sweep before p" is the highest bit below p of four 64-bit words -- four independent LDS reads and a
+//                          count of leading zeros, no walk and no search.  A wave asks that once, for the first sweep of its run:
+//                          the lanes take the bots, four a lane at most, and keep their cells in registers; after each sweep of
+//                          the run one lane replaces one register (the sweep's bot now speaks with the sweep's cell).  Per sweep
+//                          the lanes screen their bots by distance from the sweep's own cell (a binned beam ends less than 64
+//                          cells from it) and compact the survivors by ballot into the wave's list.  The list is usually empty:
+//                          then 46 lanes copy the sweep's 184 hit flags as dwords and the rays are never read.  Otherwise the
+//                          lanes take beams lane, lane + 64, lane + 128, as pass A does, and test their end cells against the
+//                          list (wave-uniform LDS reads).
+// The call's flags are kept as three 64-bit ballots per sweep.
+#define QSV_THREADS 1024
+#define QSV_WAVES (QSV_THREADS / QS_WAVE)
+#define QSV_RUN (QV_BLOCK / QSV_WAVES)         // consecutive sweeps of the block a wave takes
+#define QSV_BOT_ROUNDS (QV_BLOCK / QS_WAVE)    // bots a lane keeps: 1 + lane + 64 r
+#define QSV_HV_DWORDS (QS_SWEEP_SLOTS / 4)     // 184 hit flags of a sweep = 46 dwords
+static_assert(QSV_THREADS == 4 * QV_BLOCK, "the mark kernel clears its bit rows one 64-bit word a thread");
+static_assert(QS_SWEEP_SLOTS % 4 == 0 && QSV_HV_DWORDS <= QS_WAVE && QS_SWEEP_SLOTS <= 3 * QS_WAVE, "a sweep's flags: 46 dwords, three beams a lane");
+
+struct QsvWorkspace {
+    unsigned int *cell;                   // [cap] packed cell of an accepted sweep that has one, QV_NONE otherwise
+    unsigned char *agent;                 // [cap] its agent; 0: the sweep has no cell
+    unsigned short *blk_last;             // [blocks][QV_BLOCK] as QvWorkspace's
+    unsigned int *blk_in;                 // [blocks][QV_BLOCK]
+    unsigned char *hit;                   // [184 cap] hit_valid & !veiled of one chunk: what passes C and D see
+    unsigned long long *flags;            // [3 n_call] per sweep of the call: the ballots of its veiled beams 0..63, 64..127, 128..180
+};
+
+__global__ void __launch_bounds__(QV_BLOCK)
+qs_sveil_cells_kernel(size_t n, const unsigned char *__restrict__ pkts, size_t stride, const unsigned char *__restrict__ accept,
+                      const double *__restrict__ pose, QsGeom geo, int max_agent, QsvWorkspace vw)
+{
+    __shared__ unsigned int s_last[QV_BLOCK];
+    const int tid = threadIdx.x;
+    s_last[tid] = 0;
+    __syncthreads();
+    const size_t k = (size_t)blockIdx.x * QV_BLOCK + tid;
+    unsigned int cell = QV_NONE;
+    int agent = 0;
+    if (k < n && accept[k]) {                                      // S1: a rejected or withheld record has no cell
+        const int a = pkts[k * stride + 4];
+        int x, y;
+        if (a >= 1 && a <= max_agent && qv_cell(pose[3 * k], pose[3 * k + 1], geo, x, y)) {
+            cell = qv_pack(x, y);
+            agent = a;
+            atomicMax(&s_last[a], (unsigned int)tid + 1u);
+        }
+    }
+    if (k < n) { vw.cell[k] = cell; vw.agent[k] = (unsigned char)agent; }
+    __syncthreads();
+    vw.blk_last[(size_t)blockIdx.x * QV_BLOCK + tid] = (unsigned short)s_last[tid];
+}
+
+__global__ void __launch_bounds__(QV_BLOCK)
+qs_sveil_scan_kernel(int n_blocks, const double *__restrict__ pose, QsGeom geo, QsvWorkspace vw, int4 *__restrict__ tab, int max_agent)
+{
+    const int lane = threadIdx.x & (QS_WAVE - 1);
+    const int bot = 1 + blockIdx.x * (QV_BLOCK / QS_WAVE) + (threadIdx.x >> 6);
+    if (bot > max_agent) return;                                   // (wave-uniform)
+    qv_scan_bot(n_blocks, vw.cell, vw.blk_last, vw.blk_in, geo, tab, bot, lane,
+                [&](long long i, double &rx, double &ry) { rx = pose[3 * i]; ry = pose[3 * i + 1]; });
+}
+
+// k_call0: the record of the call this chunk's record 0 is (the flags are the call's)
+__global__ void __launch_bounds__(QSV_THREADS)
+qs_sveil_mark_kernel(size_t n, size_t k_call0, const uint2 *__restrict__ rays, const unsigned char *__restrict__ hit_valid, QsvWorkspace vw,
+                     int size, int radius, int max_agent, unsigned long long *__restrict__ total)
+{
+    __shared__ unsigned long long s_row[QV_BLOCK][4];   // per bot: which sweeps of the block are its own (and have a cell)
+    __shared__ unsigned int s_cell[QV_BLOCK];           // packed cell of sweep q
+    __shared__ unsigned int s_in[QV_BLOCK];             // per bot: the cell known at the block's entry
+    __shared__ unsigned int s_list[QSV_WAVES][QV_BLOCK];// per wave: the cells of the bots near its sweep
+    __shared__ unsigned char s_agent[QV_BLOCK];
+    __shared__ unsigned int s_tally;
+    const int tid = threadIdx.x, lane = tid & (QS_WAVE - 1), wave = tid >> 6;
+    const size_t k_blk = (size_t)blockIdx.x * QV_BLOCK;
+    (&s_row[0][0])[tid] = 0ull;                                     // (QSV_THREADS == 4 QV_BLOCK words)
+    if (tid == 0) s_tally = 0;
+    int my_agent = 0;
+    if (tid < QV_BLOCK) {
+        const size_t k = k_blk + tid;
+        s_cell[tid] = k < n ? vw.cell[k] : QV_NONE;
+        my_agent = k < n ? (int)vw.agent[k] : 0;
+        s_agent[tid] = (unsigned char)my_agent;
+        s_in[tid] = (tid >= 1 && tid <= max_agent) ? vw.blk_in[k_blk + tid] : QV_NONE;
+    }
+    __syncthreads();
+    if (my_agent) atomicOr(&s_row[my_agent][tid >> 6], 1ull << (tid & 63));
+    __syncthreads();
+
+    const int lim = QT_TILE + radius, r2 = radius * radius;        // a binned beam ends less than 64 cells from its pose on each axis
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    unsigned int *list = s_list[wave];
+    const unsigned int *hv32 = (const unsigned int *)hit_valid;     // (184 k is a multiple of 4: a sweep's flags are 46 aligned dwords)
+    unsigned int *out32 = (unsigned int *)vw.hit;
+    unsigned int cnt = 0;
+    // The wave takes QSV_RUN consecutive sweeps.  Lane l keeps in registers the cell bots 1 + l, 65 + l, 129 + l, 193 + l speak with
+    // (S2): looked up once, for the run's first sweep -- b's last sweep with a cell before it in this block is the highest bit below it
+    // in b's row, failing that the cell the block was entered with -- and then carried: after sweep p its bot speaks with p's cell.
+    const int p0 = wave * QSV_RUN;
+    unsigned int cur[QSV_BOT_ROUNDS];
+    #pragma unroll
+    for (int r = 0; r < QSV_BOT_ROUNDS; r++) {
+        const int b = 1 + QS_WAVE * r + lane;
+        cur[r] = QV_NONE;
+        if (b <= max_agent) {
+            const int pw = p0 >> 6;
+            const unsigned long long below = (1ull << (p0 & 63)) - 1ull;
+            int q = -1;
+            #pragma unroll
+            for (int j = 0; j < 4; j++) {
+                unsigned long long w = s_row[b][j];
+                w = j < pw ? w : (j == pw ? (w & below) : 0ull);
+                if (w) q = 64 * j + 63 - __clzll((long long)w);
+            }
+            cur[r] = q >= 0 ? s_cell[q] : s_in[b];
+        }
+    }
+    for (int p = p0; p < p0 + QSV_RUN; p++) {                      // (p and everything derived from it are wave-uniform)
+        const size_t k = k_blk + p;
+        if (k >= n) break;
+        const int agent = s_agent[p];
+        const unsigned int pc = s_cell[p];
+        const int px = (short)(pc & 0xffffu), py = (short)(pc >> 16);
+        int n_near = 0;
+        if (agent) {
+            #pragma unroll
+            for (int r = 0; r < QSV_BOT_ROUNDS; r++) {
+                if (QS_WAVE * r >= max_agent) break;
+                const unsigned int c = cur[r];
+                const int bx = (short)(c & 0xffffu), by = (short)(c >> 16);
+                const bool near = 1 + QS_WAVE * r + lane != agent && !qv_none(c) && abs(bx - px) <= lim && abs(by - py) <= lim;
+                const unsigned long long m = __ballot(near);
+                if (near) list[n_near + __popcll(m & lt)] = c;
+                n_near += __popcll(m);
+            }
+            #pragma unroll
+            for (int r = 0; r < QSV_BOT_ROUNDS; r++)               // from the next sweep on this bot speaks with this cell
+                if (agent - 1 == QS_WAVE * r + lane) cur[r] = pc;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (n_near == 0) {                                          // nobody near: the flags pass through, nothing is veiled
+            if (lane < QSV_HV_DWORDS) out32[QSV_HV_DWORDS * k + lane] = hv32[QSV_HV_DWORDS * k + lane];
+            if (lane < 3) vw.flags[3 * (k_call0 + k) + lane] = 0ull;
+            continue;
+        }
+        #pragma unroll
+        for (int s = 0; s < 3; s++) {
+            const int i = lane + QS_WAVE * s;
+            bool veil = false;
+            if (i < QS_SWEEP_SLOTS) {
+                const size_t r = QS_SWEEP_SLOTS * k + i;
+                const unsigned char hv = hit_valid[r];
+                if (hv && i < QS_SWEEP_BEAMS) {                     // S3: a hit ...
+                    const uint2 rec = rays[r];
+                    const int ex = (short)(rec.y & 0xffffu), ey = (short)(rec.y >> 16);
+                    if ((short)(rec.x & 0xffffu) != QT_NO_RAY       // ... that pass A binned ...
+                        && (unsigned int)ex < (unsigned int)size && (unsigned int)ey < (unsigned int)size)   // ... and that ends in the grid
+                        for (int j = 0; j < n_near; j++) {
+                            const unsigned int c = list[j];
+                            const int dx = ex - (short)(c & 0xffffu), dy = ey - (short)(c >> 16);
+                            veil |= dx * dx + dy * dy <= r2;
+                        }
+                }
+                vw.hit[r] = veil ? 0 : hv;                          // S4
+            }
+            const unsigned long long m = __ballot(veil);
+            if (lane == 0) vw.flags[3 * (k_call0 + k) + s] = m;
+            cnt += (unsigned int)__popcll(m);
+        }
+        __builtin_amdgcn_wave_barrier();                            // (the list is rewritten for the wave's next sweep)
+    }
+    if (lane == 0 && cnt) atomicAdd(&s_tally, cnt);                // (cnt is wave-uniform: it sums ballots)
+    __syncthreads();
+    if (tid == 0 && s_tally) atomicAdd(total, (unsigned long long)s_tally);
+}
+
 // ---- host side ------------------------------------------------------------------------------------
 static size_t qs_veil_layout(void *base, size_t cap, QvWorkspace &vw)
 {
@@ -238,6 +437,81 @@ hipError_t qs_launch_veil(qs_ctx *c, const uint2 *rays, size_t n, const unsigned
     c->veil_flags = vw.veiled;
     *hit_valid = vw.hit;
     return hipGetLastError();
+}
+
+// cap: the sweeps of one chunk at most; n_call: the sweeps of the whole call (its flags)
+static size_t qs_sveil_layout(void *base, size_t cap, size_t n_call, QsvWorkspace &vw)
+{
+    const size_t blocks = (cap + QV_BLOCK - 1) / QV_BLOCK;
+    Carve k(base);
+    vw.cell = k.take<unsigned int>(cap);
+    vw.agent = k.take<unsigned char>(cap);
+    vw.blk_last = k.take<unsigned short>(blocks * QV_BLOCK);
+    vw.blk_in = k.take<unsigned int>(blocks * QV_BLOCK);
+    vw.hit = k.take<unsigned char>(QS_SWEEP_SLOTS * cap);
+    vw.flags = k.take<unsigned long long>(3 * n_call);
+    return k.bytes;
+}
+
+hipError_t qs_sweep_veil_reserve(qs_ctx *c, size_t chunk_cap, size_t n_call)
+{
+    QsvWorkspace vw;
+    HIPRET(c->sveil_ws.reserve(qs_sveil_layout(nullptr, chunk_cap, n_call, vw), c->stream));
+    c->sveil_cap = chunk_cap; c->sveil_n = n_call;
+    return hipSuccess;
+}
+
+hipError_t qs_launch_sweep_veil(qs_ctx *c, const unsigned char *d_pkts, size_t stride, const unsigned char *accept, const double *pose,
+                                const uint2 *rays, size_t n, size_t k_call0, const unsigned char **hit_valid)
+{
+    if (n > c->sveil_cap || k_call0 + n > c->sveil_n) return hipErrorInvalidValue;      // (qs_sweep_veil_reserve sized it for the call)
+    QsvWorkspace vw;
+    qs_sveil_layout(c->sveil_ws.p, c->sveil_cap, c->sveil_n, vw);
+    const int blocks = (int)((n + QV_BLOCK - 1) / QV_BLOCK), per = QV_BLOCK / QS_WAVE;
+    StageTimer t(c, QS_STAGE_VEIL_INTERNAL);
+    hipLaunchKernelGGL(qs_sveil_cells_kernel, dim3(blocks), dim3(QV_BLOCK), 0, c->stream, n, d_pkts, stride, accept, pose, c->geom,
+                       c->cfg.max_agent, vw);
+    hipLaunchKernelGGL(qs_sveil_scan_kernel, dim3((c->cfg.max_agent + per - 1) / per), dim3(QV_BLOCK), 0, c->stream, blocks, pose, c->geom,
+                       vw, c->veil_tab.p, c->cfg.max_agent);
+    hipLaunchKernelGGL(qs_sveil_mark_kernel, dim3(blocks), dim3(QSV_THREADS), 0, c->stream, n, k_call0, rays, *hit_valid, vw, c->cfg.size,
+                       c->veil_radius, c->cfg.max_agent, c->veil_total.p);
+    t.stop();
+    *hit_valid = vw.hit;
+    return hipGetLastError();
+}
+
+extern "C" int qs_set_bot_veil_sweeps(qs_ctx *c, int32_t on)
+{
+    ARGCHK(c, c != nullptr);
+    c->veil_sweeps = on != 0;
+    return QS_OK;
+}
+
+extern "C" int qs_bot_veil_sweeps(qs_ctx *c, int32_t *on)
+{
+    ARGCHK(c, c != nullptr && on != nullptr);
+    *on = c->veil_sweeps ? 1 : 0;
+    return QS_OK;
+}
+
+extern "C" int qs_last_sweeps_veiled(qs_ctx *c, uint8_t *veiled, size_t n)
+{
+    ARGCHK(c, c != nullptr && veiled != nullptr);
+    if (!c->last_sweeps || n != c->last_sweeps_n)
+        return qs_fail(c, QS_E_INVAL, "qs_last_sweeps_veiled: n does not match the last sweep ingest");
+    if (n == 0) return QS_OK;
+    memset(veiled, 0, (size_t)QS_SWEEP_BEAMS * n);
+    if (!c->last_sveil) return QS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    QsvWorkspace vw;
+    qs_sveil_layout(c->sveil_ws.p, c->sveil_cap, c->sveil_n, vw);
+    std::vector<unsigned long long> f(3 * n);
+    HIPCHK(c, hipMemcpyAsync(f.data(), vw.flags, 3 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n; k++)
+        for (int i = 0; i < QS_SWEEP_BEAMS; i++)
+            veiled[(size_t)QS_SWEEP_BEAMS * k + i] = (uint8_t)((f[3 * k + (i >> 6)] >> (i & 63)) & 1ull);
+    return QS_OK;
 }
 
 extern "C" int qs_set_bot_veil(qs_ctx *c, int32_t radius_cells)

@@ -273,11 +273,28 @@ class QuasarMapper:
         self._chk(self._L.qs_last_hits(self._h, _ptr(xy), _ptr(valid), n), "qs_last_hits")
         return xy, valid
 
-    # -- bot veil (include/quasar_slam.h, rules V1-V7) -----------------------------------------------------------------------
-    def set_bot_veil(self, radius=P.BOT_VEIL_RADIUS):
+    # -- bot veil (include/quasar_slam.h, rules V1-V7 and S0-S8) -------------------------------------------------------------
+    def set_bot_veil(self, radius=P.BOT_VEIL_RADIUS, sweeps=None):
         """Veil packet beams that end within `radius` cells (1..32) of the cell where another bot was last heard: they are cast
-        free, without their end cell.  0 turns the veil off; the table of bot cells is kept either way."""
+        free, without their end cell.  0 turns the veil off; the table of bot cells is kept either way.  sweeps: True / False
+        sets the switch that extends the veil to sweep beams (sweeps then feed the table too); None leaves it as it is."""
         self._chk(self._L.qs_set_bot_veil(self._h, int(radius)), "qs_set_bot_veil")
+        if sweeps is not None:
+            self._chk(self._L.qs_set_bot_veil_sweeps(self._h, 1 if sweeps else 0), "qs_set_bot_veil_sweeps")
+
+    def bot_veil_sweeps(self):
+        """Is the sweep switch on?  (The sweep veil acts only while it is on and bot_veil() > 0.)"""
+        on = C.c_int32()
+        self._chk(self._L.qs_bot_veil_sweeps(self._h, C.byref(on)), "qs_bot_veil_sweeps")
+        return bool(on.value)
+
+    def last_sweeps_veiled(self):
+        """uint8 [n, 181]: the beams of the last sweep ingest that the veil cast without their end cell (zeros unless the sweep
+        veil was acting)."""
+        n = getattr(self, "_last_sweeps_n", 0)
+        v = np.zeros((n, P.SWEEP_BEAMS), dtype=np.uint8)
+        self._chk(self._L.qs_last_sweeps_veiled(self._h, _ptr(v), n), "qs_last_sweeps_veiled")
+        return v
 
     def bot_veil(self):
         """The veil's radius in cells; 0 = off."""
@@ -286,7 +303,8 @@ class QuasarMapper:
         return r.value
 
     def bot_veil_place(self, bot, x, y):
-        """cell[bot] from a world position: a sweep bot (sweep ingests do not feed the table), a charging dock given a spare id."""
+        """cell[bot] from a world position: a sweep bot (sweep ingests feed the table only under the sweep switch), a charging dock
+        given a spare id."""
         self._chk(self._L.qs_bot_veil_place(self._h, int(bot), float(x), float(y)), "qs_bot_veil_place")
 
     def bot_veil_forget(self, bot=None):

@@ -51,6 +51,36 @@ def body_ranges(pose, agent, ranges, radius_m, max_range):
     return out
 
 
+def body_sweep_ranges(pose, agent, ranges, radius_m, max_range):
+    """body_ranges for sweeps: the 181 f32 ranges of each sweep with the other bots' bodies in the way, float32 [n, 181].  pose
+    float [n, 3] (x, y, yaw), agent [n], ranges float32 [n, 181] as the world returned them; beam i points along
+    yaw + radians(i - 90).  Every bot is a disc of radius_m about its pose; a beam takes the nearest intersection (ray-circle,
+    fp64) with a disc of another agent when that is nearer than the world's return.  A beam without a return within max_range
+    (not 0 < d <= max_range) takes the body distance when that lies within max_range."""
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1, 3)
+    agent = np.asarray(agent).reshape(-1)
+    out = np.array(ranges, dtype=np.float32).reshape(-1, P.SWEEP_BEAMS)
+    r2 = float(radius_m) ** 2
+    beam = np.array([math.radians(i - 90) for i in range(P.SWEEP_BEAMS)])
+    for i in range(len(pose)):
+        other = agent != agent[i]
+        if not other.any():
+            continue
+        cx, cy = pose[other, 0] - pose[i, 0], pose[other, 1] - pose[i, 1]                # [m]
+        a = pose[i, 2] + beam
+        ux, uy = np.cos(a)[:, None], np.sin(a)[:, None]                                  # [181, 1]
+        tca = cx[None, :] * ux + cy[None, :] * uy                # along each beam to the point nearest each disc's centre
+        off2 = (cx * cx + cy * cy)[None, :] - tca * tca
+        t = tca - np.sqrt(np.maximum(r2 - off2, 0.0))            # the near intersection
+        t = np.where((off2 <= r2) & (t > 0.0), t, np.inf)        # (a disc behind the sensor, or around it, returns nothing)
+        body = t.min(axis=1)
+        d = out[i].astype(np.float64)
+        world = np.where((0.0 < d) & (d <= max_range), d, np.inf)
+        take = (body < world) & (body <= max_range)
+        out[i, take] = body[take].astype(np.float32)
+    return out
+
+
 class SwarmSim:
     """n bots at world poses float32 [n, 3] (x, y, yaw); bot k has agent id k + 1, so the mapper needs max_agent >= n.
 

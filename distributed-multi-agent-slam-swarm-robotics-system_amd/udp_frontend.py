@@ -180,8 +180,11 @@ class MissionControl:
             self.trail_stats.update(reloc_tried=0, reloc_accepted=0, reloc_gave_up=0)
         # bot_veil=True or {"radius": r}: the mapper's bot veil (QuasarMapper.set_bot_veil) is turned on here; a bot found offline
         # is forgotten (carried away, it must not leave a blind disc), and with sweeps=True every sweep bot is placed at the pose
-        # of its latest accepted sweep after each sweep ingest (sweep ingests do not feed the veil's table themselves)
+        # of its latest accepted sweep after each sweep ingest (sweep ingests do not feed the veil's table themselves) -- unless
+        # bot_veil={"radius": r, "sweeps": True} turns the mapper's sweep switch on: then the device veils sweep beams and feeds the
+        # table from the sweeps itself, and nothing is placed here
         self.bot_veil = bot_veil is not False and bot_veil is not None
+        self.bot_veil_sweeps = isinstance(bot_veil, dict) and bool(bot_veil.get("sweeps"))
         if self.bot_veil:
             mapper.set_bot_veil(**(dict(bot_veil) if isinstance(bot_veil, dict) else {}))
         self.track_view = track_view
@@ -281,7 +284,7 @@ class MissionControl:
                 self._mark(i0, accepted, pose, now, pose is not None)
                 if self.check_sweeps:
                     self._note_checks(i0, self.last_checks, now)
-                if self.bot_veil and pose is not None:
+                if self.bot_veil and not self.bot_veil_sweeps and pose is not None:
                     latest = {int(self._buf[i0 + int(j), 4]): int(j) for j in np.nonzero(accepted)[0]}
                     for a, j in latest.items():
                         self.mapper.bot_veil_place(a, float(pose[j, 0]), float(pose[j, 1]))

@@ -131,8 +131,9 @@ int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 
  *       qs_last_hits, the zone boxes, QS_CNT_HITS / RAYS and the pose graph see the beam as the filter judged it.
  *       (QS_CNT_CELLS counts cells written, so it is lower by one per veiled ray.)
  *   V6  After the call cell[b] is the cell of b's last accepted packet with a cell; unchanged for bots the call did not hear.
- *   V7  Never veiled: rays left to the host (exact_trig) and rays written directly (V4); qs_update_rays; every sweep entry
- *       point (sweep bots reach the table through qs_bot_veil_place only).
+ *   V7  Never veiled: rays left to the host (exact_trig) and rays written directly (V4); qs_update_rays.  Sweep beams are
+ *       veiled only under the sweep switch (S0-S8 below); without it no sweep entry point reads or feeds the table, and sweep
+ *       bots reach it through qs_bot_veil_place only.
  * A veiled context casts every packet ingest in the tiled form, whatever n is (the direct kernel writes the end cell before
  * anything could veil it); both forms write the same cells.
  * qs_set_bot_veil: radius in cells, 1..QS_BOT_VEIL_MAX_RADIUS, 0 = off; the table is kept.  QS_E_INVAL (and the setting
@@ -143,7 +144,32 @@ int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 
  * qs_bot_veil_cells: the table; xy[2 b], xy[2 b + 1] and known[b] for b = 0..max_agent (entry 0 is never known).
  * qs_last_veiled: the flags of the last packet ingest, 4 per record (n must match, as qs_last_hits); all zero after an ingest
  * with the veil off.  qs_bot_veil_stats: rays veiled since qs_create / qs_reset.  qs_bot_veil_time: with qs_timing_enable, the
- * veil stage's own milliseconds and launches (a part of QS_STAGE_RAYCAST; it is no stage of qs_stage_times). */
+ * veil stage's own milliseconds and launches (a part of QS_STAGE_RAYCAST; it is no stage of qs_stage_times).
+ *
+ * The veil for sweeps.  A sweep bot with another bot in front of it hits it with a fan of its 181 beams.  All integer, as V1-V7:
+ *   S0  qs_set_bot_veil_sweeps sets the switch, qs_bot_veil_sweeps reads it; off by default, kept across qs_set_bot_veil, qs_reset
+ *       and qs_restore.  The sweep veil ACTS only while the switch is on and the veil radius is greater than 0.  Otherwise every
+ *       sweep entry point does, launches and allocates exactly what it does without this section, and the table is neither read
+ *       nor fed by sweeps.  (No refusals of its own: qs_set_bot_veil has refused what the stage cannot serve.)
+ *   S1  The cell of an accepted sweep is V1's world_to_grid of the pose it is cast from -- the pose qs_last_sweeps reports: after
+ *       offset and drift in the plain ingest, after the correction in the matched ingest, the chain's pose in graph mode.  A pose
+ *       that is not finite or lies beyond +-2^30 cells has no cell.  A rejected record has no cell and does not speak; a record
+ *       the guarded ingest withholds counts as rejected.
+ *   S2  For a beam of accepted sweep k with agent a, every bot b != a speaks through its last accepted sweep with a cell before k
+ *       in the call -- over the whole call, across the 2^16-record chunks; failing that through the table as the call found it.
+ *       The table is V2's, the one packets use: a sweep bot veils packet beams of later packet ingests, and the other way round.
+ *   S3  The beam is VEILED when all of these hold: its hit flag is set (smin < d <= smax); the tiled raycast binned it (a beam of
+ *       64 cells or more on an axis is written directly, a beam the exact-trig rule leaves to the host is cast later: neither is
+ *       ever veiled); its end cell (x1, y1) lies inside the grid; (x1 - bx)^2 + (y1 - by)^2 <= radius^2 for some speaking b != a.
+ *   S4  A veiled beam's free cells are written; its end cell gets neither stamp nor counter.  QS_CNT_RAYS, QS_CNT_HITS, graph
+ *       mode's zone points and the landmark signature see the beam as the filter judged it; QS_CNT_CELLS is lower by one per
+ *       veiled beam.
+ *   S5  After the call the table holds the last cell of every bot heard in it, from the pose and unclamped, as V6.
+ *   S6  With the sweep veil acting every sweep ingest takes the tiled form, whatever n is; both forms write the same cells.
+ *   S7  qs_last_sweeps_veiled: the flags of the last sweep ingest, 181 per record (n must match, as qs_last_sweeps); all zero
+ *       after an ingest during which the sweep veil was not acting.
+ *   S8  Veiled sweep beams add to the word qs_bot_veil_stats reads; the stage's time adds to what qs_bot_veil_time reports.
+ * Not veiled: what qs_check_sweeps, the matchers and the relocalisers read (beams as the filter judged them). */
 #define QS_BOT_VEIL_DEFAULT_RADIUS 3
 #define QS_BOT_VEIL_MAX_RADIUS 32
 int qs_set_bot_veil(qs_ctx *ctx, int32_t radius_cells);
@@ -154,6 +180,9 @@ int qs_bot_veil_cells(qs_ctx *ctx, int32_t *xy /* (max_agent + 1) x 2 */, uint8_
 int qs_last_veiled(qs_ctx *ctx, uint8_t *veiled /* n x 4 */, size_t n);
 int qs_bot_veil_stats(qs_ctx *ctx, uint64_t *veiled_total);
 int qs_bot_veil_time(qs_ctx *ctx, double *ms, uint64_t *launches, int32_t reset);
+int qs_set_bot_veil_sweeps(qs_ctx *ctx, int32_t on);
+int qs_bot_veil_sweeps(qs_ctx *ctx, int32_t *on);
+int qs_last_sweeps_veiled(qs_ctx *ctx, uint8_t *veiled /* n x 181 */, size_t n);
 
 /* ---- servo sweeps ("Quasar-Lite" packets) ----------------------------------------------------------------------------
  * A sweep carries a pose and 181 ranges swept from -90 to +90 degrees about the heading:

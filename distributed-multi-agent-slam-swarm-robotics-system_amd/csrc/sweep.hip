@@ -275,14 +275,15 @@ static const size_t QS_SWEEP_CHUNK = (size_t)1 << 16;
 
 static int sweeps_begin(qs_ctx *c, size_t n, size_t stride, uint64_t &seq0)
 {
-    c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
-    c->last_checks = false; c->last_checks_n = 0;          // qs_last_sweep_checks: only after a guarded ingest
-    c->last_sweep_graph = false;                           // qs_last_sweep_nodes: only after an ingest in graph mode
-    c->last_sveil = false;                                 // qs_last_sweeps_veiled: zeros unless the sweep veil acted
+    // the refusals first: a refused ingest leaves what the last ingest was, all of it (qs_last_sweeps and the four calls below)
     if (stride != QS_SWEEP_SIZE_V0 && stride != QS_SWEEP_SIZE_V0_ODO)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: stride must be 743 (v0) or 751 (v0 + odometry)");
     if (c->cfg.seq_stride > 1 || c->cfg.shard_bots > 0)
         return qs_fail(c, QS_E_INVAL, "qs_ingest_sweeps: sharded contexts (seq_stride > 1, shard_bots > 0) do not take sweeps");
+    c->last_matches = false; c->last_matches_n = 0;        // qs_last_sweep_matches: only after a matched ingest
+    c->last_checks = false; c->last_checks_n = 0;          // qs_last_sweep_checks: only after a guarded ingest
+    c->last_sweep_graph = false;                           // qs_last_sweep_nodes: only after an ingest in graph mode
+    c->last_sveil = false;                                 // qs_last_sweeps_veiled: zeros unless the sweep veil acted
     HIPCHK(c, hipSetDevice(c->device));
     if (seq0 == UINT64_MAX) seq0 = c->next_seq;
     c->last_n = 0; c->last_has_poses = false;              // qs_last_batch / qs_last_hits: length mismatch from here on

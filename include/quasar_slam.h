@@ -143,7 +143,10 @@ int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 
  * bot outside 1..max_agent or a position without a cell.  qs_bot_veil_forget: cell[bot] unknown; bot 0: all of them.
  * qs_bot_veil_cells: the table; xy[2 b], xy[2 b + 1] and known[b] for b = 0..max_agent (entry 0 is never known).
  * qs_last_veiled: the flags of the last packet ingest, 4 per record (n must match, as qs_last_hits); all zero after an ingest
- * with the veil off.  qs_bot_veil_stats: rays veiled since qs_create / qs_reset.  qs_bot_veil_time: with qs_timing_enable, the
+ * with the veil off; QS_E_INVAL unless the last ingest was a packet ingest (after a sweep ingest, qs_update_rays, qs_reset,
+ * qs_restore).  qs_bot_veil_stats: rays veiled since qs_create / qs_reset / qs_restore -- a restore, into the same context too,
+ * starts the count at 0 as it empties the table: a checkpoint carries neither, and QS_CNT_CELLS, which it does carry, already
+ * tells what the restored map holds.  qs_bot_veil_time: with qs_timing_enable, the
  * veil stage's own milliseconds and launches (a part of QS_STAGE_RAYCAST; it is no stage of qs_stage_times).
  *
  * The veil for sweeps.  A sweep bot with another bot in front of it hits it with a fan of its 181 beams.  All integer, as V1-V7:
@@ -167,7 +170,9 @@ int qs_last_hits(qs_ctx *ctx, double *xy /* n x 4 x 2 */, uint8_t *valid /* n x 
  *   S5  After the call the table holds the last cell of every bot heard in it, from the pose and unclamped, as V6.
  *   S6  With the sweep veil acting every sweep ingest takes the tiled form, whatever n is; both forms write the same cells.
  *   S7  qs_last_sweeps_veiled: the flags of the last sweep ingest, 181 per record (n must match, as qs_last_sweeps); all zero
- *       after an ingest during which the sweep veil was not acting.
+ *       after an ingest during which the sweep veil was not acting.  A refused sweep ingest is no ingest: the flags of the one
+ *       before it stay (below).  QS_E_INVAL where qs_last_sweeps refuses: after a packet ingest, a sweep ingest with n = 0,
+ *       qs_update_rays, qs_reset, qs_restore.
  *   S8  Veiled sweep beams add to the word qs_bot_veil_stats reads; the stage's time adds to what qs_bot_veil_time reports.
  * Not veiled: what qs_check_sweeps, the matchers and the relocalisers read (beams as the filter judged them). */
 #define QS_BOT_VEIL_DEFAULT_RADIUS 3
@@ -209,7 +214,11 @@ int qs_last_sweeps_veiled(qs_ctx *ctx, uint8_t *veiled /* n x 181 */, size_t n);
  *   trig     exact_trig: beams whose end point lies in the 1e-9 edge band are resolved on the host with libm, as rays are.
  * Any n: the call is split into chunks internally.  QS_E_INVAL for another stride, seq_stride > 1 or shard_bots > 0
  * (sharded sweeps are not supported).  After a sweep call qs_last_batch / qs_last_hits refuse (length mismatch);
- * qs_last_sweeps returns per record the accepted flag and the pose used (NaN for rejected records). */
+ * qs_last_sweeps returns per record the accepted flag and the pose used (NaN for rejected records).
+ * A refused sweep ingest -- another stride, a sharded context, a bad parameter of the matched or guarded form, the guarded form
+ * in graph mode -- changes nothing: qs_last_sweeps, qs_last_sweep_matches, qs_last_sweep_checks, qs_last_sweep_nodes and
+ * qs_last_sweeps_veiled go on answering for the ingest before it, and qs_last_batch / qs_last_veiled if that was a packet ingest.
+ * A call with n = 0 is an ingest of nothing: the map stays, and after it all of these refuse. */
 #define QS_SWEEP_SIZE_V0 743
 #define QS_SWEEP_SIZE_V0_ODO 751
 #define QS_SWEEP_BEAMS 181

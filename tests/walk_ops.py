@@ -24,11 +24,15 @@ import match_rules as MR
 import maze_scenes as MZ
 import merge_rules as MG
 import plan_rules as PR
+import ray_scenes as RS
 import reloc_group_rules as RG
 import reloc_rules as RR
 import sense_rules as SR
 import sweep_graph_rules as SG
+import sweep_veil_rules as SV
 import territory_rules as TR
+import trail_reloc_rules as TRR
+import trail_rules as TL
 import view_rules as VR
 from conftest import PKG_NAME
 from oracle import oracle as orc
@@ -222,10 +226,25 @@ def refusing(call, errors):
 
 
 # ---- the model ----------------------------------------------------------------------------------------------------------------------
+class _Geo:
+    """The walk's grid as veil_rules and sweep_veil_rules take a geometry (ray_scenes.Geo's size, res, ox, oy and oracle)."""
+
+    def __init__(self, size):
+        self.size, self.res, self.ox, self.oy = geometry(size)
+
+    def oracle(self, max_agent=2):
+        return orc.OracleMapper(self.size, self.res, self.ox, self.oy, 0.0, max_agent=max_agent)
+
+
 class Model:
     """What a context must show: an orc.OracleMapper for the map and its counters, the settings (sweep filter, graph mode, dirty
     tracking), the number of pose-graph nodes, the merge session (merge_rules.Session over the oracle's grid_to_pcd,
-    voxel_downsample and rasterise and the registration given: the oracle's icp_planar by default) and what the last ingest was."""
+    voxel_downsample and rasterise and the registration given: the oracle's icp_planar by default) and what the last ingest was.
+
+    The bot veil (V1-V7, S0-S8) is sweep_veil_rules.SweepVeilModel's: its table, its running total and the flags it returns.
+    `o` is fed the bytes and goes on giving acceptance, poses, nodes and drift.  Until a veil first acts it is the map as well,
+    exactly as before; from then on (until a reset) the map is `mo`, a second oracle that has replayed the session so far and is
+    driven ray by ray with `valid & ~veiled` by the veil model, whether or not the veil acts in a later call."""
 
     def __init__(self, size, register=None):
         self.size = size
@@ -236,19 +255,31 @@ class Model:
         self.tracking = False
         self.session = MG.Session(orc.grid_to_pcd, register or orc.icp_planar, orc.voxel_downsample, orc.rasterise)
         self.merges = 0
+        self.veil_radius, self.veil_sweeps = 0, False      # kept over reset and restore (V2, S0)
+        self.min_margin = math.inf       # of the end points of the packets the veil model has cast, in cells (VeilModel.min_margin)
         self._new_map()
 
     def _new_map(self):
         self.o = orc.OracleMapper(*geometry(self.size), 0.0)
+        self.mo = None                   # the map once a veil has acted
+        self.log = []                    # ("stream", buf) | ("rays", batch): what mo replays when it is made
+        self.veil = SV.SweepVeilModel(_Geo(self.size), 2, 0)
+        self.veil_src = {}               # bot -> "place" | "packets" | "sweeps": who wrote its table entry
+        self.flags = None                # the veil flags of the last ingest, uint8 [n, 4] or [n, 181]
+        self.hits_judged = 0             # QS_CNT_HITS: beams the filter judged hits (V5, S4)
         self.graph_sweeps = 0            # accepted sweeps that became pose-graph nodes
         self.unfused = False
         self.last = None                 # None, ("packets", acc, pose), ("sweeps", form, graph, dict of arrays)
         self._grid = None
 
     @property
+    def mapo(self):
+        return self.o if self.mo is None else self.mo
+
+    @property
     def grid(self):
         if self._grid is None:
-            self._grid = np.array(self.o.grid, dtype=np.int8)
+            self._grid = np.array(self.mapo.grid, dtype=np.int8)
         return self._grid
 
     def wrote(self):
@@ -259,7 +290,43 @@ class Model:
         self._new_map()
 
     def restored(self):
-        self.last = None
+        """qs_restore: the table is emptied and the running total starts again, as after a reset (V2); the settings stay."""
+        self.last = self.flags = None
+        self.veil.forget()
+        self.veil.total = 0
+        self.veil_src = {}
+
+    def fork(self):
+        """A veil is about to act: from here on the map is driven ray by ray."""
+        if self.mo is None:
+            self.mo = self.veil.g.oracle(2)
+            for kind, what in self.log:
+                if kind == "stream":
+                    self.mo.feed_stream(what)
+                else:
+                    self.mo.update_rays(*what)
+            self.log = None
+
+    def cast(self, batch):
+        """update_rays of the op table: never veiled (V7)."""
+        self.o.update_rays(*batch)
+        if self.mo is None:
+            self.log.append(("rays", batch))
+        else:
+            self.mo.update_rays(*batch)
+
+    def veil_model(self):
+        """The veil model set to the context's settings and the model's oracles."""
+        v = self.veil
+        v.o, v.m = self.o, self.mo
+        v.radius, v.sweeps, (v.smin, v.smax) = self.veil_radius, self.veil_sweeps, self.filt
+        return v
+
+    def heard(self, kind, agents, flags):
+        """After an ingest the veil model ran: the flags of the last ingest and who fed the table."""
+        self.flags = flags
+        for b in agents:
+            self.veil_src[int(b)] = kind
 
     def nodes(self):
         return int(self.o.n_nodes(0)) + self.graph_sweeps
@@ -314,6 +381,17 @@ def model_sweeps(model, args, got):
                                      seed=int(args["seed"]), no_return=NO_RETURN), args)
 
 
+def with_odometry(buf):
+    """The records as uint8 [n, 751]: what sweep_veil_rules reads (a 743-byte record has no encoder and v2v fields: zeros)."""
+    if buf.shape[1] == 751:
+        return buf
+    src = MR.records_of(buf)
+    out = np.zeros(len(src), dtype=protocol().PACKET_DTYPE_V0_ODO)
+    for f in src.dtype.names:
+        out[f] = src[f]
+    return out.view(np.uint8).reshape(len(src), 751)
+
+
 def aux(got, key):
     return None if got is None or isinstance(got, Refused) else got[key]
 
@@ -342,7 +420,9 @@ def op(name, kind, sets, pred=None, twin=True):
 # -- writers --
 def packets_of(size, args):
     """uint8 [n, 42]: packets from poses in the world's open cells with the four ranges the world gives (restated once per n and
-    seed); no landmark, so no closure; from n = 16 on one record carries agent 9."""
+    seed); no landmark, so no closure; from n = 16 on one record carries agent 9.  With `clear` in the args (the veil walks) a
+    record is drawn again until the end points of its four rays keep more than ray_scenes.MARGIN of a cell from every cell edge:
+    the veil is decided by end cells, and never for a ray the exact-trig rule leaves to the host (V4)."""
     def make():
         rng = rng_of(args, 2)
         n = int(args["n"])
@@ -351,8 +431,28 @@ def packets_of(size, args):
         if n >= 16:
             agent[7] = 9
         w = cached(("world", size), lambda: world(size))
-        return SR.sense_packets(protocol(), w, *geometry(size)[1:], poses, agent, max_range=1.2, no_return=NO_RETURN)
-    return cached(("packets", size, int(args["n"]), int(args["seed"])), make)
+        sense = lambda k: SR.sense_packets(protocol(), w, *geometry(size)[1:], poses[k], agent[k], max_range=1.2, no_return=NO_RETURN)
+        buf = sense(slice(None))
+        while args.get("clear"):
+            near = packet_margins(size, buf) <= 2 * RS.MARGIN
+            if not near.any():
+                break
+            poses[near] = draw_poses(size, int(near.sum()), rng)
+            buf[near] = sense(near)                            # (a packet's ranges depend on its own pose alone)
+        return buf
+    return cached(("packets", size, int(args["n"]), int(args["seed"]), bool(args.get("clear"))), make)
+
+
+def packet_margins(size, buf):
+    """float64 [n]: per packet the least distance, in cells, of its four rays' end points from a cell edge (the reference's end
+    point formula, as veil_rules.VeilModel.ingest forms it)."""
+    rec = np.ascontiguousarray(buf).view(protocol().PACKET_DTYPE).reshape(-1)
+    d = np.stack([rec[k] for k in ("front", "left", "back", "right")], axis=1).astype(np.float64)
+    ok = (RS.MIN_D < d) & (d <= RS.MAX_D)
+    length = np.where(ok, d, np.where(d > RS.MIN_D, np.minimum(d, RS.MAX_D), RS.MAX_D))
+    a = rec["yaw"].astype(np.float64)[:, None] + np.array(RS.SENSOR_ANG)[None, :]
+    hx, hy = rec["x"].astype(np.float64)[:, None] + length * np.cos(a), rec["y"].astype(np.float64)[:, None] + length * np.sin(a)
+    return RS._margin(_Geo(size), hx, hy).min(axis=1)
 
 
 @op("ingest_packets", "writer", {"S": [dict(n=1), dict(n=16)], "L": [dict(n=5000)]}, pred="packets")
@@ -363,10 +463,23 @@ class _Packets:
 
     def expect(model, args, got):
         buf = packets_of(model.size, args)
-        model.o.feed_stream(buf)
-        model.wrote()
         rec = np.ascontiguousarray(buf).view(protocol().PACKET_DTYPE).reshape(-1)
         acc = ((rec["magic"] == b"QSRL") & (rec["agent"] >= 1) & (rec["agent"] <= 2)).astype(np.uint8)
+        acting = model.veil_radius > 0
+        if acting:
+            model.fork()
+        if model.mo is None:
+            model.o.feed_stream(buf)
+            model.log.append(("stream", buf))
+            model.flags = np.zeros((len(buf), 4), dtype=np.uint8)
+        else:                                                  # (the veil model feeds `o` the bytes itself)
+            model.veil.min_margin = math.inf
+            veiled, _ = model.veil_model().ingest(buf)
+            model.min_margin = min(model.min_margin, model.veil.min_margin)
+            model.heard("packets", np.unique(rec["agent"][acc == 1]) if acting else (), veiled)
+        d = np.stack([rec[k] for k in ("front", "left", "back", "right")], axis=1).astype(np.float64)[acc == 1]
+        model.hits_judged += int(((RS.MIN_D < d) & (d <= RS.MAX_D)).sum())
+        model.wrote()
         pose = np.stack([rec["x"].astype(np.float64), rec["y"].astype(np.float64), rec["yaw"].astype(np.float64)], axis=1)
         model.last = ("packets", acc, pose)
         return None
@@ -374,11 +487,14 @@ class _Packets:
 
 def _sweeps_run(form):
     def run(m, args, env):
-        buf = device_sweeps(m, env.size, args, env.filt[1])
+        if int(args["stride"]) not in (743, 751) or int(args["n"]) == 0:       # (a directed test's: no such record can be sensed)
+            buf = np.zeros((int(args["n"]), int(args["stride"])), dtype=np.uint8)
+        else:
+            buf = device_sweeps(m, env.size, args, env.filt[1])
         out = dict(buf=buf)
-        if form == "match":
+        if form == "match" and len(buf) and buf.shape[1] in (743, 751):
             out["rot"] = m.match_sweeps(buf, params=MATCH_PARAMS, rotations=True)[1]
-        if form == "check":
+        if form == "check" and len(buf) and buf.shape[1] in (743, 751):
             ck = m.check_sweeps(buf)
             out["sincos"] = np.stack([ck["sin_yaw"], ck["cos_yaw"]], axis=1)
         kw = {"match": dict(match=MATCH_PARAMS), "check": dict(check=True)}.get(form, {})
@@ -391,9 +507,15 @@ def _sweeps_expect(form):
     def expect(model, args, got):
         if form == "check" and model.graph_on:
             return Refused("graph mode")
+        if int(args["stride"]) not in (743, 751):              # refused before anything changes: the last ingest stays what it was
+            return Refused("stride")
+        if int(args["n"]) == 0:                                # a sweep ingest of nothing: the map stays, there is no last ingest
+            model.last = model.flags = None
+            return got if isinstance(got, dict) else None
         buf = model_sweeps(model, args, got)
         recs = MR.records_of(buf)
         acc, pose = MR.poses_of(recs, None, None, model.drift())
+        accepted = acc.copy()
         smin, smax = model.filt
         arrays = {}
         if form == "match":
@@ -408,8 +530,20 @@ def _sweeps_expect(form):
             arrays["checks"] = ck
             acc = acc & ~CR.withheld(ck)
             cast[~acc] = np.nan
-        if acc.any():
-            model.o.update_rays(*MR.beams_of_all(cast[acc], recs["ranges"][acc], smin, smax))
+        acting = model.veil_sweeps and model.veil_radius > 0                    # S0
+        if acting:
+            model.fork()
+        rays = MR.beams_of_all(cast[acc], recs["ranges"][acc], smin, smax) if acc.any() else None
+        if rays is not None:
+            model.o.update_rays(*rays)
+            model.hits_judged += int(rays[4].sum())
+        if model.mo is None:
+            if rays is not None:
+                model.log.append(("rays", rays))
+            model.flags = np.zeros((len(recs), MR.BEAMS), dtype=np.uint8)
+        else:                                                  # S1: cast from `cast`; a withheld record counts as rejected
+            veiled, _ = model.veil_model().ingest_sweeps(with_odometry(buf), withheld=tuple(np.nonzero(accepted & ~acc)[0].tolist()), poses=cast)
+            model.heard("sweeps", np.unique(recs["agent"][acc]) if acting else (), veiled)
         arrays["acc"], arrays["pose"] = acc.astype(np.uint8), cast
         if model.graph_on:
             assert not SG.signature(recs["ranges"][acc], **GRAPH_PARAMS).any(), "a sensed sweep with a landmark signature"
@@ -449,7 +583,7 @@ class _Rays:
 
     def expect(model, args, got):
         for batch in rays_of(model.size, args):
-            model.o.update_rays(*batch)
+            model.cast(batch)
         model.wrote()
         model.last = None
         return None
@@ -512,6 +646,76 @@ class _Restore:
         return None
 
 
+@op("set_bot_veil", "writer", {"-": [dict(radius=0, sweeps=None), dict(radius=3, sweeps=True), dict(radius=8, sweeps=None), dict(radius=32, sweeps=True),
+                                     dict(radius=3, sweeps=False)]})
+class _SetVeil:
+    def run(m, args, env):
+        m.set_bot_veil(args["radius"], sweeps=args["sweeps"])
+        return None
+
+    def expect(model, args, got):
+        model.veil_radius = int(args["radius"])
+        if args["sweeps"] is not None:
+            model.veil_sweeps = bool(args["sweeps"])
+        return None
+
+
+_SENSORS = ("front", "left", "back", "right")
+
+
+def beam_of(size, at, beam):
+    """(end x, end y, hit?) of beam `beam` of record 0 of the ingest op at = (name, n, seed): a packet's from its own bytes; a
+    sweep's from the static world as a sensor reports it there (the device senses the painted map with the same poses: the end it
+    maps lies within a cell or so of this one)."""
+    name, n, seed = at
+
+    def sensed():
+        poses, agent, _ = sweep_inputs(size, dict(n=n, seed=seed))
+        w = cached(("world", size), lambda: world(size))
+        return MR.records_of(SR.sense_sweeps(protocol(), w, *geometry(size)[1:], poses[:1], agent[:1], odometry=True, max_range=NEAR[1],
+                                             noise_amp=0.01, seed=seed, no_return=NO_RETURN))[0]
+    if name == "ingest_packets":
+        rec = np.ascontiguousarray(packets_of(size, dict(n=n, seed=seed, clear=True))).view(protocol().PACKET_DTYPE).reshape(-1)[0]
+        d, a, lo = float(rec[_SENSORS[beam]]), float(rec["yaw"]) + RS.SENSOR_ANG[beam], RS.MIN_D
+    else:
+        rec = cached(("record 0", size, at), sensed)
+        d, a, lo = float(rec["ranges"][beam]), float(rec["yaw"]) + math.radians(beam - 90), NEAR[0]
+    return float(rec["x"]) + d * math.cos(a), float(rec["y"]) + d * math.sin(a), lo < d <= NEAR[1]
+
+
+def _place_xy(size, args):
+    return beam_of(size, tuple(args["at"]), args["beam"])[:2] if args.get("at") else (args["x"], args["y"])
+
+
+@op("bot_veil_place", "writer", {"-": [dict(bot=2, x=0.26, y=-0.31, at=None, beam=None)]})
+class _Place:
+    """cell[bot] from a world position in the args, or from the end of beam `beam` of record 0 of the later ingest op `at` =
+    (name, n, seed), so that a call of one record has something to be veiled by and the list stays a literal."""
+
+    def run(m, args, env):
+        m.bot_veil_place(args["bot"], *_place_xy(env.size, args))
+        return None
+
+    def expect(model, args, got):
+        model.veil.o = model.o
+        model.veil.place(args["bot"], *_place_xy(model.size, args))
+        model.veil_src[int(args["bot"])] = "place"
+        return None
+
+
+@op("bot_veil_forget", "writer", {"-": [dict(bot=None), dict(bot=2)]})
+class _Forget:
+    def run(m, args, env):
+        m.bot_veil_forget(args["bot"])
+        return None
+
+    def expect(model, args, got):
+        model.veil.forget(args["bot"])
+        for b in ([args["bot"]] if args["bot"] is not None else list(model.veil_src)):
+            model.veil_src.pop(b, None)
+        return None
+
+
 # -- queries --
 @op("views", "query", {"-": [dict()]})
 class _Views:
@@ -520,7 +724,7 @@ class _Views:
         return dict(grid=m.grid_i8(), hits=h, misses=mi, logodds=m.logodds())
 
     def expect(model, args, got):
-        return dict(grid=model.grid, hits=np.array(model.o.hits), misses=np.array(model.o.misses), logodds=model.o.logodds())
+        return dict(grid=model.grid, hits=np.array(model.mapo.hits), misses=np.array(model.mapo.misses), logodds=model.mapo.logodds())
 
 
 def _goal(size, args):
@@ -896,6 +1100,96 @@ class _Last:
         return out
 
 
+TRAIL_STEP = 0.02               # metres between the packets of a trail: 64 of them fit the 68-cell world's room
+
+
+def trails_of(size, args, own_frame):
+    """(uint8 [trails * records, stride], gsize): seeded trails driven through the static world (trail_reloc_rules.drive, cast4
+    at the packet filter's 1.2 m).  own_frame: each trail reports in a frame of its own (the relocaliser's input); otherwise it
+    reports its true poses displaced rigidly by up to 2 cells and 2 angle steps (the matcher's).  Every third trail is bot 2's;
+    from 16 records on one record carries agent 9."""
+    def make():
+        rng = rng_of(args, 14)
+        w = cached(("world", size), lambda: world(size))
+        geom = geometry(size)[1:]
+        n, K = int(args["trails"]), int(args["records"])
+        true = np.stack([TRR.drive(w, geom, rng, K, step=TRAIL_STEP) for _ in range(n)])
+        ranges = np.stack([[TRR.cast4(w, geom, q, RS.MAX_D, rng, 0.01) for q in tr] for tr in true])
+        if own_frame:
+            pose = np.stack([TRR.reported(tr, rng.uniform(-math.pi, math.pi), rng.uniform(-10.0, 10.0, 2)) for tr in true])
+        else:
+            pose = np.stack([TL.displaced(tr, rng.integers(-2, 3, 3), RES) for tr in true])
+        agent = np.repeat(np.where(np.arange(n) % 3 == 2, 2, 1), K)
+        if n * K >= 16:
+            agent[n * K // 2] = 9
+        flat = pose.reshape(-1, 3)
+        return TL.pack(agent, flat[:, 0], flat[:, 1], flat[:, 2], ranges.reshape(-1, 4))
+    key = ("trails", size, own_frame, int(args["trails"]), int(args["records"]), int(args["seed"]))
+    buf = cached(key, make)
+    return np.ascontiguousarray(buf[:, :int(args["stride"])]), np.full(int(args["trails"]), int(args["records"]), dtype=np.int32)
+
+
+_TRAIL_MATCH_SETS = {"S": [dict(trails=1, records=1, stride=42, radius=2, travel=4.0), dict(trails=1, records=4, stride=41, radius=0, travel=0.5)],
+                     "L": [dict(trails=1, records=64, stride=42, radius=7, travel=4.0), dict(trails=65, records=4, stride=41, radius=2, travel=4.0)]}
+
+
+@op("match_trails", "query", _TRAIL_MATCH_SETS)
+class _MatchTrails:
+    def run(m, args, env):
+        buf, gs = trails_of(env.size, args, False)
+        p = dict(MATCH_PARAMS, radius=args["radius"], min_hits=8)
+        out, rot = m.match_trails(buf, gs, travel=args["travel"], params=p, rotations=True)
+        return dict(rot=rot, out=np.frombuffer(out.tobytes(), dtype=TL.TRAIL_DTYPE))
+
+    def expect(model, args, got):
+        buf, gs = trails_of(model.size, args, False)
+        p = dict(MATCH_PARAMS, radius=args["radius"], min_hits=8)
+        out, rot = TL.match(model.grid, model.geom, buf, gs, p, args["travel"], None, aux(got, "rot"), drift=model.drift())
+        return dict(rot=rot if got is None else got["rot"], out=out)
+
+
+_TRAIL_RELOC_SETS = {"S": [dict(trails=1, records=1, stride=42, n_rot=8, box="cell", radius=2, travel=0.0),
+                           dict(trails=1, records=4, stride=41, n_rot=45, box="tile", radius=0, travel=0.6)],
+                     "L": [dict(trails=1, records=64, stride=42, n_rot=8, box="grid", radius=2, travel=2.0),
+                           dict(trails=65, records=4, stride=41, n_rot=8, box="tile", radius=2, travel=0.6),
+                           dict(trails=1, records=64, stride=42, n_rot=180, box="cell", radius=7, travel=3.0)]}
+
+
+@op("relocalise_trails", "query", _TRAIL_RELOC_SETS)
+class _RelocTrails:
+    def run(m, args, env):
+        buf, gs = trails_of(env.size, args, True)
+        p = dict(n_rot=args["n_rot"], radius=args["radius"], box=box_of(env.size, args["box"]), min_hits=8)
+        out, rot = m.relocalise_trails(buf, gs, travel=args["travel"], params=p, rotations=True)
+        return dict(rot=rot, out=np.frombuffer(out.tobytes(), dtype=TRR.TRAIL_RELOC_DTYPE))
+
+    def expect(model, args, got):
+        buf, gs = trails_of(model.size, args, True)
+        p = dict(n_rot=args["n_rot"], radius=args["radius"], box=box_of(model.size, args["box"]), min_hits=8)
+        out, rot = TRR.reloc_trails(model.grid, model.geom, buf, gs, p, args["travel"], None, aux(got, "rot"))
+        return dict(rot=rot if got is None else got["rot"], out=out)
+
+
+@op("veil_state", "query", {"-": [dict()]}, twin=False)
+class _VeilState:
+    """The settings, the table, the running total, the flags of the last ingest -- answered or refused as the header says: the
+    packet flags after a packet ingest, the sweep flags after a sweep ingest of at least one record, zeros where no veil acted --
+    and the counters a veiled beam leaves alone (rays, hits) or lowers (cells)."""
+
+    def run(m, args, env):
+        c = m.counters()
+        return dict(radius=m.bot_veil(), sweeps=m.bot_veil_sweeps(), cells=m.bot_veil_cells(), stats=m.bot_veil_stats(),
+                    last_veiled=refusing(m.last_veiled, env.errors), last_sweeps_veiled=refusing(m.last_sweeps_veiled, env.errors),
+                    counters={k: c[k] for k in ("cells", "rays", "hits")})
+
+    def expect(model, args, got):
+        kind = model.last[0] if model.last is not None else None
+        no = Refused("not the last ingest")
+        return dict(radius=model.veil_radius, sweeps=model.veil_sweeps, cells=model.veil.cells(), stats=model.veil.total,
+                    last_veiled=model.flags if kind == "packets" else no, last_sweeps_veiled=model.flags if kind == "sweeps" else no,
+                    counters=dict(cells=int(model.mapo.n_cells_written), rays=int(model.mapo.n_rays), hits=model.hits_judged))
+
+
 _REFUSALS = (("plan", "reloc"), ("groups", "match"), ("check", "sense"), ("view", "gain"), ("filter", "territories"))
 
 
@@ -928,7 +1222,9 @@ class _Refusal:
 
 
 WRITERS = [n for n, o in OPS.items() if o.kind == "writer"]
-QUERIES = [n for n, o in OPS.items() if o.kind == "query"]
+VEIL_QUERIES = ("match_trails", "relocalise_trails", "veil_state", "match", "check_sweeps", "relocalise_sweeps", "relocalise_groups", "views", "frontier",
+                "last")          # the query list of the veil walks (generate_veil)
+QUERIES = [n for n, o in OPS.items() if o.kind == "query" and n not in VEIL_QUERIES[:3]]      # the nineteen of the first four walks
 PREDS = ("rays", "packets", "sweeps", "restore", "reset")        # the order inside a block: a reset is followed by the next block's paint
 
 
@@ -1018,6 +1314,145 @@ def generate(walks=WALKS):
     return out
 
 
+# ---- the veil walks -------------------------------------------------------------------------------------------------------------------
+VEIL_WALKS = ((136, 21), (136, 22), (68, 23))
+# One entry per block, dealt to the walks in runs of 4, 3 and 3.  veil: the set_bot_veil (radius, sweep switch) in front of the
+# block (None: as it stands -- the settings survive the reset that ends a block, the table does not); packets: the block's
+# packet ingest; form, n: its sweep ingest; graph: in graph mode, after a guarded ingest that graph mode refuses.
+#   walk 0: calls of one record with the veil acting, off, acting again (direct kernel against tiled form); then graph mode
+#   walk 1: the large calls acting and off; the packet veil without the sweep switch
+#   walk 2: 68 cells; off from the start, then radius 32, where nearly every beam of the small room ends near the other bot
+_VEIL_PLAN = (dict(veil=(3, True), packets=1, form="plain", n=1), dict(veil=(0, None), packets=1, form="match", n=1),
+              dict(veil=(8, None), packets=1, form="check", n=1), dict(veil=(32, True), packets=16, form="match", n=65, graph=True),
+              dict(veil=(32, True), packets=5000, form="plain", n=65), dict(veil=(0, None), packets=5000, form="check", n=3),
+              dict(veil=(3, False), packets=16, form="match", n=3),
+              dict(veil=None, packets=16, form="plain", n=3), dict(veil=(32, True), packets=1, form="match", n=3),
+              dict(veil=None, packets=5000, form="check", n=65))
+_VEIL_SETS = {(0, None): 0, (3, True): 1, (8, None): 2, (32, True): 3, (3, False): 4}      # set_bot_veil's argument sets
+
+
+def generate_veil(walks=VEIL_WALKS):
+    """The op lists of the veil walks: the block scheme of generate() over VEIL_QUERIES and _VEIL_PLAN.
+
+    Beyond the scheme: while the veil acts, bot 2 is placed on the end of a beam of record 0 in front of every call of one record
+    (record 0 is bot 1's); after the first such packet ingest bot 2 is forgotten and the same packet ingested again; in the last
+    block a sweep of one record follows the packet ingest and a packet of one record the sweep ingest, with nothing in between
+    that empties the table; relocalise_trails directly follows a relocalise_groups with another n_rot, box and travel, and the
+    reverse, and match_trails a match with another radius and stride, and the reverse; a walk's first reset under the veil finds
+    a bot placed by its world position."""
+    walks = tuple(walks)
+    nq = len(VEIL_QUERIES)
+    order = [VEIL_QUERIES[i] for i in np.random.default_rng([s for _, s in walks]).permutation(nq)]
+    runs = (4, 3, 3)
+    out, b0 = [], 0
+    for w, (size, seed) in enumerate(walks):
+        rng = np.random.default_rng(seed)
+        seen = {}
+
+        def item(name, cls=None, which=None, **fixed):
+            o = OPS[name]
+            k = seen[name] = seen.get(name, -1) + 1
+            cls = (cls or "SLSLS"[k % 5]) if o.sized else "-"
+            sets = [s for s in o.sets[cls] if all(s.get(f) == v for f, v in fixed.items())]
+            args = dict(sets[int(rng.integers(len(sets))) if which is None else which % len(sets)])
+            args["seed"] = int(rng.integers(1 << 30))
+            if o.sized:
+                args["size_class"] = cls
+            return name, args
+
+        def placed(ingest):
+            """(a bot_veil_place of bot 2 on the end of the first beam of the ingest's record 0 that is a hit, the ingest):
+            the ingest is drawn again until its record 0 has such a beam."""
+            name, n = ingest
+            while True:
+                one = item(name, cls="S", n=n, **({} if name == "ingest_packets" else dict(stride=751)))
+                if name == "ingest_packets":
+                    one[1]["clear"] = True
+                at = (name, n, one[1]["seed"])
+                hit = [k for k in range(4 if name == "ingest_packets" else MR.BEAMS) if beam_of(size, at, k)[2]]
+                if hit:
+                    return ("bot_veil_place", dict(bot=2, x=None, y=None, at=at, beam=hit[len(hit) // 2], seed=0)), one
+
+        def other_box(args):
+            return "tile" if args["box"] != "tile" else "cell"
+
+        ops, paired = [], set()
+        for k in range(runs[w]):
+            b = b0 + k
+            plan = _VEIL_PLAN[b]
+            if plan["veil"] is not None:
+                ops.append(item("set_bot_veil", which=_VEIL_SETS[plan["veil"]]))
+            radius = [a["radius"] for n_, a in ops if n_ == "set_bot_veil"][-1:] or [0]
+            sweeps_on = [a["sweeps"] for n_, a in ops if n_ == "set_bot_veil" and a["sweeps"] is not None][-1:] or [False]
+            acting, s_acting = radius[0] > 0, radius[0] > 0 and sweeps_on[0]
+            for p, pred in enumerate(PREDS):
+                again = None
+                if pred == "rays":
+                    if k % 2 == 0:
+                        ops.append(item("set_sweep_filter", which=1 if k % 4 == 0 else 0))
+                    ops.append(item("update_rays", which=1 if k % 3 == 2 else 0))
+                elif pred == "packets":
+                    if plan["packets"] == 1 and acting:
+                        place, one = placed(("ingest_packets", 1))
+                        ops += [place, one]
+                        if "forget" not in paired:
+                            paired.add("forget")
+                            again = [item("bot_veil_forget", which=1), (one[0], dict(one[1]))]
+                    else:                                          # sixteen packets under the veil: drawn again until one of their beams is veiled
+                        while True:
+                            one = item("ingest_packets", cls="L" if plan["packets"] == 5000 else "S", n=plan["packets"])
+                            one[1]["clear"] = True
+                            if not acting or plan["packets"] != 16 or SV.SweepVeilModel(_Geo(size), 2, radius[0]).ingest(packets_of(size, one[1]))[0].any():
+                                break
+                        ops.append(one)
+                elif pred == "sweeps":
+                    name = "ingest_sweeps_" + plan["form"]
+                    cls = "L" if plan["n"] == 65 else "S"
+                    if b == len(_VEIL_PLAN) - 1:                       # the table holds what the packet ingest left: no place
+                        ops += [item("ingest_sweeps_plain", cls="S", n=1, stride=751), item("veil_state")]
+                    if plan.get("graph"):                          # refused once in graph mode, then the ingest proper in graph mode
+                        ops += [item("set_sweep_graph", which=0), item("ingest_sweeps_check", cls=cls)]
+                    if plan["n"] == 1 and s_acting:
+                        ops += list(placed((name, 1)))
+                    else:
+                        ops.append(item(name, cls=cls, n=plan["n"]))
+                    if b == len(_VEIL_PLAN) - 1:
+                        again = [item("ingest_packets", cls="S", n=1)]
+                        again[0][1]["clear"] = True
+                else:
+                    if pred == "reset" and acting and "place" not in paired:      # (the restore before it has emptied the table)
+                        paired.add("place")
+                        ops.append(item("bot_veil_place"))
+                    ops.append(item(pred))
+                q = order[(b + p) % nq]
+                ops.append(item(q))
+                if q == "relocalise_groups" and "trails" not in paired:
+                    paired.add("trails")
+                    n_rot = 45 if ops[-1][1]["n_rot"] != 45 else 8
+                    ops.append(("relocalise_trails", dict(trails=1, records=4, stride=42, n_rot=n_rot, box=other_box(ops[-1][1]), radius=2,
+                                                          travel=0.6 if ops[-1][1]["travel"] != 0.6 else 0.0, seed=int(rng.integers(1 << 30)), size_class="S")))
+                elif q == "relocalise_trails" and "groups" not in paired:
+                    paired.add("groups")
+                    n_rot = 45 if ops[-1][1]["n_rot"] != 45 else 8
+                    ops.append(("relocalise_groups", dict(groups=(4, 1), travel=2.0 if ops[-1][1]["travel"] != 2.0 else 0.0, n_rot=n_rot,
+                                                          box=other_box(ops[-1][1]), radius=2, stride=751, seed=int(rng.integers(1 << 30)), size_class="S")))
+                elif q == "match" and "match_trails" not in paired:
+                    paired.add("match_trails")
+                    ops.append(("match_trails", dict(trails=1, records=4, stride=42 if ops[-1][1]["stride"] == 743 else 41,
+                                                     radius=2 if ops[-1][1]["radius"] != 2 else 7, travel=4.0, seed=int(rng.integers(1 << 30)), size_class="S")))
+                elif q == "match_trails" and "match" not in paired:
+                    paired.add("match")
+                    ops.append(("match", dict(n=3, stride=743 if ops[-1][1]["stride"] == 42 else 751, radius=2 if ops[-1][1]["radius"] != 2 else 7,
+                                              seed=int(rng.integers(1 << 30)), size_class="S")))
+                if pred == "sweeps" and plan.get("graph"):
+                    ops.append(item("set_sweep_graph", which=1))
+                if again:
+                    ops += again
+        b0 += runs[w]
+        out.append(ops)
+    return out
+
+
 def as_literal(ops):
     """The op list as text that evaluates to it."""
     return "[" + ",\n ".join(repr(o) for o in ops) + "]"
@@ -1027,14 +1462,15 @@ def as_literal(ops):
 def same_map(m, model):
     """'' when grid_i8() and counts() of the context are the model's."""
     h, mi = m.counts()
-    return differing(dict(grid=m.grid_i8(), hits=h, misses=mi), dict(grid=model.grid, hits=np.array(model.o.hits), misses=np.array(model.o.misses)),
+    return differing(dict(grid=m.grid_i8(), hits=h, misses=mi), dict(grid=model.grid, hits=np.array(model.mapo.hits), misses=np.array(model.mapo.misses)),
                      "map")
 
 
 def walk(m, model, env, ops, tag="", twin=None, every=5, failures=None):
     """The ops in turn on the context and on the model.  After every op (a) the answer is the model's, and a query a checkpoint
     covers answers the same when it is asked again at once; after every writer (b) grid_i8() and counts() are the oracle's and the
-    five last-ingest calls answer or refuse as the model says; every `every` ops and at the end (c) twin(m, model, env) -- a new context restored
+    five last-ingest calls answer or refuse as the model says, and so does veil_state (with the veil never switched on: an empty
+    table, a total of 0, zero flags); every `every` ops and at the end (c) twin(m, model, env) -- a new context restored
     from m.checkpoint(), with its own Env -- answers the last query a checkpoint covers as the used context answers it now.
     A difference raises AssertionError with the tag, the op's index and the list so far as a literal; with a `failures` list
     it is appended there instead and the walk goes on."""
@@ -1058,9 +1494,10 @@ def walk(m, model, env, ops, tag="", twin=None, every=5, failures=None):
             fail(i, why)
         if o.kind == "writer":
             why = same_map(m, model)
-            if not why:
-                last = OPS["last"].run(m, {}, env)
-                why = differing(last, OPS["last"].expect(model, {}, last), "last ingest")
+            for q in ("last", "veil_state"):
+                if not why:
+                    said = OPS[q].run(m, {}, env)
+                    why = differing(said, OPS[q].expect(model, {}, said), {"last": "last ingest", "veil_state": "veil"}[q])
             if why:
                 fail(i, "after the writer, " + why)
         elif o.twin:
